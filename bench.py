@@ -15,7 +15,15 @@ The default --steps 8 renders the full 1024 spp image, so `wall_to_1024spp_s` is
 contiguous sample range are submitted as one library call; the library cuts the range into sub-passes (its own choice: ~64 M
 paths each, four alive at once in regions of the state arrays, staggered so that a launch mixes the first bounces of one with the
 thin late bounces of the others) and drives them with a device-side loop -- queue counts never come back to the host.
-After the default (cfg3) run, two-step runs of cfg4 and cfg5 are appended under "also".
+
+A plain run sets up, warms up, times --steps steps, writes its outputs when --dump-outputs DIR is given and prints the result
+line.  --full adds everything else the benchmark measures: per-kernel HIP-event timing inside the timed region and the roofline
+of the dominant kernel (probes + an untimed counting pass), the CPU baseline, and, after a default (cfg3) run, two-step runs of
+cfg4 and cfg5 appended under "also".  --no-kernel-timing / --no-cpu-baseline / --no-also leave parts of --full out.
+
+--dump-outputs DIR: after the timed steps, the framebuffer the timed steps accumulated (DIR/image.npy, float32 [H, W, 4]; above
+64 MB a fixed seeded sample of its pixels, DIR/image_sample.npy + DIR/image_sample_index.npy) and the ray counts of the timed steps
+(DIR/ray_counts.npy, float64 [closest, any, camera samples]).  The inputs are seeded: the same arguments give the same inputs.
 
 --gpus N > 1: one rank per GPU.  When no launcher has set WORLD_SIZE, bench.py starts its own ranks
 (`python -m torch.distributed.run --nproc-per-node N bench.py ...` as a CHILD process, before anything touches the GPU),
@@ -48,7 +56,7 @@ WORKLOADS = ("cfg3", "cfg4", "cfg5")
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=8)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 8, cfg5: the steps of one full image)")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--spp-per-step", type=int, default=128,
                     help="samples of every pixel rendered by one step; how a call's samples are cut into sub-passes is the library's business (--spp-per-pass)")
@@ -65,6 +73,10 @@ def parse(argv=None):
     ap.add_argument("--spp-per-pass", type=int, default=0, help="samples per pixel of one sub-pass of the library's path loop (0: the library's choice)")
     ap.add_argument("--passes-in-flight", type=int, default=0, help="sub-passes the path loop keeps alive at once (0: the library's choice)")
     ap.add_argument("--no-also", action="store_true", help="default cfg3 run only: skip the short cfg4 / cfg5 runs appended under \"also\"")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure per-kernel timing + roofline, the CPU baseline and the cfg4 / cfg5 runs under \"also\" (off: the headline figure only)")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps, write what they computed to DIR/<name>.npy (float32 / float64, at most 64 MB)")
     args = ap.parse_args(argv)
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
@@ -75,7 +87,11 @@ def parse(argv=None):
         # one pass holds all 256 samples of every pixel (67 M paths, 24 GB): VolPath has one ray in flight per path, so a pass runs ~60
         # rounds whose tail is thin; the thicker the rounds the better (64 / 128 / 256 spp per pass: 0.425 / 0.364 / 0.336 s)
         if args.spp_per_step == d.spp_per_step: args.spp_per_step = 256
-        if args.steps == d.steps: args.steps = max(1, args.spp // args.spp_per_step)
+        if args.steps is None: args.steps = max(1, args.spp // args.spp_per_step)
+    if args.steps is None:
+        args.steps = 8
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     return args
 
 
@@ -352,7 +368,7 @@ def also_runs():
     """Short runs of cfg 4 and cfg 5 as children of the default run: value, wall, and the roofline of their dominant kernel."""
     out = {}
     for wl, extra in (("cfg4", ["--steps", "2", "--warmup", "1"]), ("cfg5", ["--warmup", "1"])):
-        cmd = [sys.executable, os.path.abspath(__file__), "--workload", wl, "--no-cpu-baseline", "--no-also"] + extra
+        cmd = [sys.executable, os.path.abspath(__file__), "--workload", wl, "--full", "--no-cpu-baseline", "--no-also"] + extra
         t0 = time.perf_counter()
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=240)
@@ -369,6 +385,31 @@ def also_runs():
         except Exception as e:
             out[wl] = {"error": str(e)[-200:]}
     return out
+
+
+# ------------------------------------------------------------------------------------------------ outputs
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(out_dir, acc, tot):
+    """--dump-outputs: what the timed steps computed, as a caller of the render path receives it -- the framebuffer they accumulated
+    (float32 [H, W, 4]) and their ray counts (float64 [closest-hit, any-hit, camera samples]).  An image above the 64 MB budget is
+    replaced by a fixed seeded sample of its pixels (image_sample.npy [k, 4] + their flat indices image_sample_index.npy)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    img = acc.detach().float().cpu().numpy()
+    counts = np.array([tot["rays_closest"], tot["rays_any"], tot["camera_samples"]], dtype=np.float64)
+    np.save(os.path.join(out_dir, "ray_counts.npy"), counts)
+    budget = DUMP_LIMIT_BYTES - counts.nbytes - 4096
+    if img.nbytes <= budget:
+        np.save(os.path.join(out_dir, "image.npy"), img)
+        return
+    px = img.reshape(-1, img.shape[-1])
+    k = budget // (px.shape[1] * 4 + 8)
+    idx = np.sort(np.random.default_rng(0).choice(px.shape[0], size=k, replace=False))
+    np.save(os.path.join(out_dir, "image_sample.npy"), px[idx])
+    np.save(os.path.join(out_dir, "image_sample_index.npy"), idx.astype(np.float64))
 
 
 # ------------------------------------------------------------------------------------------------ the benchmark
@@ -413,14 +454,17 @@ def main():
     import gnxraytracer_amd as gx
     import scenes
 
+    # per-kernel HIP-event timing (and the roofline priced on it) is part of --full only
+    kernel_timing = args.full and not args.no_kernel_timing
     gx.init(dev_index)
     W, H = args.width, args.height
     # every rank builds the same scene (replicated: ~12 MB of tables, + 22 MB of env-map tables for cfg 4); rank 0 writes the
-    # synthetic input files once
-    mesh_path = os.path.join(ROOT, "gpurun_out", "_meshes", f"synthetic_dragon_{args.tris}_1.3d")
+    # synthetic input files once (seeded: the same arguments give the same files) into a directory this user may write
+    cache = scenes.synthetic_cache_dir()
+    mesh_path = os.path.join(cache, f"synthetic_dragon_{args.tris}_1.3d")
     env_path = None
     if args.workload == "cfg4":
-        env_path = os.path.join(ROOT, "gpurun_out", "_meshes", "synthetic_env_1000x500.hdr")
+        env_path = os.path.join(cache, "synthetic_env_1000x500.hdr")
     if rank == 0 and args.workload in ("cfg3", "cfg4"):
         scenes.synthetic_mesh_path(args.tris)
         if env_path:
@@ -483,7 +527,7 @@ def main():
     if args.warmup > 0:
         run_steps(0, args.warmup)
     acc.zero_()
-    if not args.no_kernel_timing:
+    if kernel_timing:
         gx.lib().gnxr_set_profiling(1)
 
     def sync():
@@ -508,7 +552,8 @@ def main():
             acc = full.to(dev)
     sync()
     dt = time.perf_counter() - t0
-    gx.lib().gnxr_set_profiling(0)
+    if kernel_timing:
+        gx.lib().gnxr_set_profiling(0)
 
     note(f"timed region {dt:.3f} s")
     rays = tot["rays_closest"] + tot["rays_any"]
@@ -585,8 +630,11 @@ def main():
         "rays": {"closest": tot["rays_closest"], "any": tot["rays_any"], "per_camera_sample": rays / max(1, tot["camera_samples"])},
     }
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, acc, tot)
+
     # ---- roofline of the dominant kernel (rank 0's launches, HIP events on the render stream)
-    if not args.no_kernel_timing and tot["launches_closest"] > 0:
+    if kernel_timing and tot["launches_closest"] > 0:
         note("roofline: VALU issue and gather-rate probes + counting pass")
         peaks = {"valu": gx.probe_valu_peak(), "gather": gx.probe_gather_peak()}   # what this device reaches on each, now
         # untimed counting pass of one sample per pixel: the WIDE (4-wide, speculative) walk that the timed kernel performs,
@@ -623,10 +671,10 @@ def main():
                                       "boxes, pick the next) and sits below all three ceilings -- DESIGN.md section 4 has the measurements that rule each one out")
     if args.save_image and rank == 0:
         np.save(args.save_image, acc.cpu().numpy())
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(builder, args)
         result["cpu_baseline"]["reference_in_survey_container"] = "cfg 2 only: 1.58 Mrays/s as-is, 6.3 Mrays/s printf-free, 8-core Xeon 2.1 GHz (BASELINE.md)"
-    if world == 1 and args.workload == "cfg3" and not args.no_also and not args.no_kernel_timing:
+    if kernel_timing and world == 1 and args.workload == "cfg3" and not args.no_also:
         # BASELINE.json's other two GPU configurations, two steps each, so that their numbers are timed by whoever times this run
         # (child processes: this one first gives its 15 GB of path state back)
         del scene, out, acc

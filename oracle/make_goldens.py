@@ -16,6 +16,7 @@ What each fixture pins:
   bsdf_zoo.npz   BSDF::f / Pdf / Sample_f for one material of each kind
   light_*.npz    DiffuseAreaLight / InfiniteAreaLight / SkyBoxLight Sample_Li / Pdf_Li / Le
   render_*.npz   images + ray counts of the restated Render/Li loop running on the reference's classes
+  reference_assets.npz + *.xz / *.bz2   the reference's Resources/ inputs of tests/test_reference_assets.py and its answers on them
 """
 import os
 import struct
@@ -413,8 +414,105 @@ def hlbvh_goldens():
     save("bvh_hlbvh.npz", **out)
 
 
+# ---------------------------------------------------------------- 18: the reference's Resources/ inputs (tests/test_reference_assets.py)
+def sha256_bits(a):
+    import hashlib
+    return hashlib.sha256(np.ascontiguousarray(a, np.float32).tobytes()).hexdigest()
+
+
+def rle_rgbe_rows(data):
+    """(header lines, [scanline byte strings]) of a new-style run-length-encoded Radiance file."""
+    head, pos = data.split(b"\n\n", 1)[0], data.index(b"\n\n") + 2
+    size_line = data[pos:data.index(b"\n", pos)]
+    pos += len(size_line) + 1
+    _, h, _, w = size_line.split()
+    h, w = int(h), int(w)
+    rows = []
+    for _ in range(h):
+        start = pos
+        assert data[pos:pos + 4] == bytes([2, 2, w >> 8, w & 0xff])
+        pos += 4
+        for _c in range(4):
+            n = 0
+            while n < w:
+                c = data[pos]
+                pos += 2 if c > 128 else 1 + c
+                n += c - 128 if c > 128 else c
+            assert n == w
+        rows.append(data[start:pos])
+    assert pos == len(data)
+    return head, w, rows
+
+
+def asset_goldens():
+    """The Resources/ files tests/test_reference_assets.py reads, as data fixtures (xz / bz2 copies; a file whose copy would pass
+    1 MiB is split into two valid Radiance files of 250 scanlines each, the scanline bytes untouched), and what the compiled
+    reference returned for them: stbi_loadf's floats (as SHA-256 of their bits) and the renders of the tests (images + ray counts;
+    SHA-256 of the image bits where the image is larger than a fixture should be)."""
+    import bz2
+    import lzma
+    import tempfile
+    res = "/root/reference/Resources"
+    out = {}
+
+    def stbi(path):
+        raw = ol.run_ref(None, "hdr", None, [path])
+        w, h = struct.unpack("<2i", raw[:8])
+        return np.frombuffer(raw[8:], np.float32).reshape(h, w, 3)
+
+    def xz(name, data):
+        with open(os.path.join(G, name), "wb") as f:
+            f.write(lzma.compress(data, preset=9 | lzma.PRESET_EXTREME))
+        print("wrote", name, os.path.getsize(os.path.join(G, name)))
+
+    for name in ("MonValley1000.hdr", "TropicalRuins1000.hdr"):
+        path = os.path.join(res, name)
+        data = open(path, "rb").read()
+        ref = stbi(path)
+        out["stbi_sha256_" + name] = np.array(sha256_bits(ref))
+        out["stbi_shape_" + name] = np.array(ref.shape, np.int32)
+        if len(lzma.compress(data, preset=9 | lzma.PRESET_EXTREME)) < 1000 * 1000:
+            xz(name + ".xz", data)
+            continue
+        head, w, rows = rle_rgbe_rows(data)
+        half = len(rows) // 2
+        for part, (a, b) in enumerate(((0, half), (half, len(rows)))):
+            piece = head + b"\n\n" + b"-Y %d +X %d\n" % (b - a, w) + b"".join(rows[a:b])
+            with tempfile.TemporaryDirectory() as td:
+                q = os.path.join(td, "part.hdr")
+                open(q, "wb").write(piece)
+                assert (stbi(q).view(np.uint32) == ref[a:b].view(np.uint32)).all()
+            xz(f"{name[:-4]}_part{part}.hdr.xz", piece)
+    with tempfile.TemporaryDirectory() as td:
+        q = os.path.join(td, "env.hdr")
+        scenes.write_rgbe(q, scenes.synthetic_env(1000, 500), rle=True)
+        xz("synthetic_env_1000x500.hdr.xz", open(q, "rb").read())
+        out["stbi_sha256_synthetic"] = np.array(sha256_bits(stbi(q)))
+    vol = open(os.path.join(res, "density_render.70.volume"), "rb").read()
+    with open(os.path.join(G, "density_render.70.volume.bz2"), "wb") as f:
+        f.write(bz2.compress(vol, 9))
+
+    def ref_render(b, args, W, H):
+        sp = scene_file(b, "asset")
+        raw = ol.run_ref(sp, "render", None, args)
+        img = np.frombuffer(raw[:W * H * 16], np.float32).reshape(H, W, 4)
+        cnt = np.frombuffer(raw[W * H * 16:W * H * 16 + 16], np.uint64)
+        return img[..., :3].copy(), np.array([int(cnt[0]), int(cnt[1])], np.int64)
+
+    for strategy, code in (("spatial", 0), ("power", 2)):
+        b = scenes.dragon_cornell(2000, "zoo", env=os.path.join(res, "MonValley1000.hdr"), mesh_path=os.path.join(G, "mesh_2k.3d"))
+        out[f"env_{strategy}_img"], out[f"env_{strategy}_rays"] = ref_render(b, [96, 54, 4, 8, 1.0, code, 4, 0], 96, 54)
+    img, out["vol512_rays"] = ref_render(scenes.volume_cornell_cfg5(0.05, golden_dir=G), [512, 512, 2, 8, 1.0, 0, 8, 1], 512, 512)
+    out["vol512_sha256"] = np.array(sha256_bits(img))
+    img, out["direct256_rays"] = ref_render(scenes.material_zoo(), [256, 256, 4, 5, 1.0, 0, 8, 3, 0], 256, 256)
+    out["direct256_sha256"] = np.array(sha256_bits(img))
+    save("reference_assets.npz", **out)
+
+
 if __name__ == "__main__":
-    if sys.argv[1:] == ["direct"]:   # only section 13
+    if sys.argv[1:] == ["assets"]:     # only section 18
+        asset_goldens()
+    elif sys.argv[1:] == ["direct"]:   # only section 13
         direct_goldens(scene_file(scenes.cornell(), "cornell"), scene_file(scenes.material_zoo(), "zoo"))
     elif sys.argv[1:] == ["textured"]:   # only section 14
         texture_goldens()

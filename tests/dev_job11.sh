@@ -5,8 +5,8 @@ O=gpurun_out/r03k; mkdir -p $O
 timeout -k 10 600 python -m pytest tests -m gpu -x -q > $O/gpu_tests.log 2>&1 || { tail -60 $O/gpu_tests.log; exit 1; }
 tail -3 $O/gpu_tests.log
 for k in 1 2; do
-python bench.py --workload cfg5 --no-cpu-baseline > $O/cfg5_pack.json 2>$O/cfg5_pack.err; python -c "
+python bench.py --full --workload cfg5 --no-cpu-baseline > $O/cfg5_pack.json 2>$O/cfg5_pack.err; python -c "
 import json; d=json.loads(open('$O/cfg5_pack.json').read().strip().splitlines()[-1]); print('pack', d['value'], d['ms_per_step'], d['roofline']['kernel_seconds'])"
-GNXR_VOL_PACK=0 python bench.py --workload cfg5 --no-cpu-baseline > $O/cfg5_nopack.json 2>$O/cfg5_nopack.err; python -c "
+GNXR_VOL_PACK=0 python bench.py --full --workload cfg5 --no-cpu-baseline > $O/cfg5_nopack.json 2>$O/cfg5_nopack.err; python -c "
 import json; d=json.loads(open('$O/cfg5_nopack.json').read().strip().splitlines()[-1]); print('nopack', d['value'], d['ms_per_step'], d['roofline']['kernel_seconds'])"
 done

@@ -9,8 +9,8 @@ V="occ::$S=32,$P=8 fixed8::$S=32,$P=8,GNXR_GRID_OCC=0 occ2::$S=32,$P=8 fixed8b::
 python tests/dev_ab.py --workload cfg3 $V > $O/ab_cfg3.log 2>&1; cat $O/ab_cfg3.log
 python tests/dev_ab.py --workload cfg4 $V > $O/ab_cfg4.log 2>&1; cat $O/ab_cfg4.log
 for k in 1 2; do
-python bench.py --workload cfg5 --no-cpu-baseline > $O/cfg5_occ.json 2>$O/cfg5.err; python -c "
+python bench.py --full --workload cfg5 --no-cpu-baseline > $O/cfg5_occ.json 2>$O/cfg5.err; python -c "
 import json; d=json.loads(open('$O/cfg5_occ.json').read().strip().splitlines()[-1]); print('occ', d['value'], d['ms_per_step'], d['roofline']['kernel_seconds'])"
-GNXR_GRID_OCC=0 python bench.py --workload cfg5 --no-cpu-baseline > $O/cfg5_fixed.json 2>$O/cfg5.err; python -c "
+GNXR_GRID_OCC=0 python bench.py --full --workload cfg5 --no-cpu-baseline > $O/cfg5_fixed.json 2>$O/cfg5.err; python -c "
 import json; d=json.loads(open('$O/cfg5_fixed.json').read().strip().splitlines()[-1]); print('fixed8', d['value'], d['ms_per_step'], d['roofline']['kernel_seconds'])"
 done

@@ -14,14 +14,14 @@ if has test; then
   tail -3 $O/gpu_tests.log
 fi
 if has bench; then
-python bench.py > $O/bench_cfg3.json 2> $O/bench_cfg3.err; echo "cfg3 done"; tail -c 1500 $O/bench_cfg3.json
-python bench.py --workload cfg4 > $O/bench_cfg4.json 2> $O/bench_cfg4.err; echo "cfg4 done"; tail -c 600 $O/bench_cfg4.json
-python bench.py --workload cfg5 > $O/bench_cfg5.json 2> $O/bench_cfg5.err; echo "cfg5 done"; tail -c 600 $O/bench_cfg5.json
+python bench.py --full > $O/bench_cfg3.json 2> $O/bench_cfg3.err; echo "cfg3 done"; tail -c 1500 $O/bench_cfg3.json
+python bench.py --full --workload cfg4 > $O/bench_cfg4.json 2> $O/bench_cfg4.err; echo "cfg4 done"; tail -c 600 $O/bench_cfg4.json
+python bench.py --full --workload cfg5 > $O/bench_cfg5.json 2> $O/bench_cfg5.err; echo "cfg5 done"; tail -c 600 $O/bench_cfg5.json
 fi
 if has stats; then
 for W in cfg3 cfg4 cfg5; do
   S=4; if [ $W = cfg5 ]; then S=1; fi
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$W -- python3 bench.py --workload $W --steps $S --warmup 1 --no-cpu-baseline --no-also > $O/stats_$W.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$W -- python3 bench.py --full --workload $W --steps $S --warmup 1 --no-cpu-baseline --no-also > $O/stats_$W.log 2>&1
   echo "stats $W done"
 done
 find $O -name "*kernel_stats.csv" | head
@@ -40,6 +40,6 @@ done
 fi
 if has rehearsal; then
 # two ranks sharing the one GPU of this box over gloo: rehearsal of bench.py's own rank launch (the driver runs the real RCCL scaling bench)
-GNXR_BENCH_BACKEND=gloo python bench.py --gpus 2 --steps 4 --warmup 1 --no-cpu-baseline > $O/bench_2rank_gloo.json 2> $O/bench_2rank_gloo.err
+GNXR_BENCH_BACKEND=gloo python bench.py --full --gpus 2 --steps 4 --warmup 1 --no-cpu-baseline > $O/bench_2rank_gloo.json 2> $O/bench_2rank_gloo.err
 echo "2-rank rehearsal done"; tail -c 500 $O/bench_2rank_gloo.json
 fi

@@ -1,12 +1,31 @@
 """Scene set-ups of BASELINE.json's configs, authored through the product's SceneBuilder
 (the mirror of ui/ModelList.cpp / ui/MaterialList.cpp / ui/RenderThread.cpp:46-187)."""
 import os
+import tempfile
 
 import numpy as np
 
 import gnxraytracer_amd as gx
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# seeded synthetic inputs (stand-in mesh, environment map) are written once and reused from here; build/ is not versioned
+CACHE_DIR = os.path.join(ROOT, "build", "synthetic_inputs")
+
+
+def synthetic_cache_dir():
+    """CACHE_DIR when this user may write there; otherwise (a tree built by another user, or read-only) a directory of this user's
+    own under the system temporary directory.  The files are seeded, so either place holds the same bytes."""
+    own = os.path.join(tempfile.gettempdir(), f"gnxr_synthetic_inputs_{os.getuid()}")
+    for d in (CACHE_DIR, own):
+        try:
+            os.makedirs(d, exist_ok=True)
+        except OSError:
+            continue
+        if os.access(d, os.W_OK | os.X_OK) and (d == CACHE_DIR or os.stat(d).st_uid == os.getuid()):
+            return d
+    raise RuntimeError(f"no writable directory for the synthetic scene inputs ({CACHE_DIR}, {own})")
+
+
 WHITE = (0.91, 0.91, 0.91)
 RED = (0.9, 0.1, 0.17)
 BLUE = (0.14, 0.21, 0.87)
@@ -66,11 +85,13 @@ def disney_thin_preset(b):
 
 
 def synthetic_mesh_path(n_tris, seed=1, cache_dir=None):
-    cache_dir = cache_dir or os.path.join(ROOT, "gpurun_out", "_meshes")
+    cache_dir = cache_dir or synthetic_cache_dir()
     os.makedirs(cache_dir, exist_ok=True)
     p = os.path.join(cache_dir, f"synthetic_dragon_{n_tris}_{seed}.3d")
     if not os.path.exists(p):
-        gx.write_synthetic_3d(p, n_tris, seed)
+        tmp = p + f".{os.getpid()}.tmp"
+        gx.write_synthetic_3d(tmp, n_tris, seed)
+        os.replace(tmp, p)
     return p
 
 
@@ -137,7 +158,7 @@ def synthetic_env(w=1000, h=500, seed=4):
 
 
 def synthetic_env_path(w=1000, h=500, cache_dir=None):
-    cache_dir = cache_dir or os.path.join(ROOT, "gpurun_out", "_meshes")
+    cache_dir = cache_dir or synthetic_cache_dir()
     os.makedirs(cache_dir, exist_ok=True)
     p = os.path.join(cache_dir, f"synthetic_env_{w}x{h}.hdr")
     if not os.path.exists(p):

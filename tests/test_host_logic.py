@@ -274,3 +274,49 @@ def test_bench_call_ranges():
     for i0, n, sps, spp in ((0, 7, 64, 1024), (3, 40, 128, 1024), (0, 9, 32, 96)):
         r = bench.call_ranges(i0, n, sps, spp)
         assert sum(m for _, _, m in r) == n and all(0 <= a < b <= spp for a, b, _ in r)
+
+
+def test_bench_steps_full_and_dump_options(tmp_path, monkeypatch):
+    """--steps is the number of timed steps for every workload (cfg5 only picks its own when none is given); --full is off by
+    default; --dump-outputs writes the accumulated image and the ray counts, and a fixed seeded pixel sample above the budget."""
+    import torch
+
+    import bench
+    a = lambda *v: bench.parse(list(v))
+    assert a().steps == 8 and not a().full and a().dump_outputs == ""
+    assert a("--workload", "cfg5", "--steps", "8").steps == 8 and a("--workload", "cfg5").steps == 1
+    assert a("--full").full and a("--dump-outputs", "x").dump_outputs == "x"
+    with pytest.raises(SystemExit):
+        a("--steps", "0")
+    img = torch.arange(6 * 5 * 4, dtype=torch.float32).reshape(6, 5, 4)
+    tot = {"rays_closest": 11, "rays_any": 7, "camera_samples": 30}
+    bench.dump_outputs(str(tmp_path / "full"), img, tot)
+    got = np.load(str(tmp_path / "full" / "image.npy"))
+    assert got.dtype == np.float32 and (got == img.numpy()).all()
+    rc = np.load(str(tmp_path / "full" / "ray_counts.npy"))
+    assert rc.dtype == np.float64 and list(rc) == [11, 7, 30]
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096 + 24 + 10 * 24)   # room for 10 pixels
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), img, tot)
+    assert not (tmp_path / "s1" / "image.npy").exists()
+    idx = np.load(str(tmp_path / "s1" / "image_sample_index.npy"))
+    px = np.load(str(tmp_path / "s1" / "image_sample.npy"))
+    assert idx.dtype == np.float64 and px.shape == (10, 4) and (np.diff(idx) > 0).all()
+    assert (px == img.numpy().reshape(-1, 4)[idx.astype(np.int64)]).all()
+    assert (np.load(str(tmp_path / "s2" / "image_sample_index.npy")) == idx).all()
+
+
+def test_synthetic_inputs_fall_back_when_the_tree_cannot_be_written(tmp_path, monkeypatch):
+    """bench.py and the GPU tests write the seeded stand-in mesh / environment map once: into build/ of the tree when this user may,
+    else into a directory of this user's own under the system temporary directory -- never failing because the tree is not theirs."""
+    blocker = tmp_path / "not_a_dir"
+    blocker.write_text("")
+    monkeypatch.setattr(scenes, "CACHE_DIR", str(blocker / "synthetic_inputs"))   # makedirs under a file fails, as in a foreign tree
+    monkeypatch.setattr(scenes.tempfile, "gettempdir", lambda: str(tmp_path / "tmp"))
+    d = scenes.synthetic_cache_dir()
+    assert d == str(tmp_path / "tmp" / f"gnxr_synthetic_inputs_{os.getuid()}") and os.path.isdir(d)
+    p = scenes.synthetic_mesh_path(64)
+    assert os.path.dirname(p) == d and os.path.getsize(p) > 0
+    ok = tmp_path / "tree_build"
+    monkeypatch.setattr(scenes, "CACHE_DIR", str(ok))
+    assert scenes.synthetic_cache_dir() == str(ok)
