@@ -32,6 +32,7 @@ class GnxrError(RuntimeError):
 
 
 _lib = None
+_device = 0   # the device gnxr_init / the first device of gnxr_init_devices bound: scenes created afterwards live there
 
 
 def lib():
@@ -58,14 +59,18 @@ def _f3(v):
 
 
 def init(device_id=0):
+    global _device
     _check(lib().gnxr_init(int(device_id)))
+    _device = int(device_id)
 
 
 def init_devices(device_ids):
     """One process, several devices: scenes created afterwards are replicated on all of them and Render() shards the image rows
     over them (gnxr_init_devices)."""
+    global _device
     ids = (C.c_int32 * len(device_ids))(*[int(d) for d in device_ids])
     _check(lib().gnxr_init_devices(len(device_ids), ids))
+    _device = int(device_ids[0])
 
 
 class SceneBuilder:
@@ -286,6 +291,8 @@ class Scene:
         self._keep = builder_or_desc
         d = builder_or_desc.desc() if isinstance(builder_or_desc, SceneBuilder) else builder_or_desc
         self.n_triangles = int(d.n_triangles)
+        self.n_vertices = int(d.n_vertices)
+        self.device = _device
         _check(lib().gnxr_scene_create(C.byref(d), C.byref(self._h)))
 
     def close(self):
@@ -299,6 +306,36 @@ class Scene:
         n, dmax, nv = C.c_int32(), C.c_int32(), C.c_int32()
         _check(lib().gnxr_scene_info(self._h, C.byref(n), C.byref(dmax), C.byref(nv)))
         return {"bvh_nodes": n.value, "bvh_max_depth": dmax.value, "light_voxels": nv.value}
+
+    # editing between frames (gnxr_scene_update_vertices / gnxr_scene_set_camera)
+    def update_vertices(self, xyz, first_vertex=0, stream=None):
+        """Move vertices [first_vertex, first_vertex + len(xyz)) of the description's vertex array to xyz (world space, (n, 3) float32):
+        a numpy array (host memory) or a contiguous torch tensor on the scene's device (read on `stream`, by default the current torch
+        stream).  The BVH is refitted on the device with its topology kept; vertices of emissive triangles cannot move."""
+        if isinstance(xyz, np.ndarray):
+            if xyz.dtype != np.float32 or xyz.ndim != 2 or xyz.shape[1] != 3:
+                raise ValueError(f"update_vertices: expected a float32 array of shape (n, 3), got {xyz.dtype} {xyz.shape}")
+            xyz = np.ascontiguousarray(xyz)
+            ptr = xyz.ctypes.data
+        elif type(xyz).__module__.split(".")[0] == "torch":
+            import torch
+            if not (isinstance(xyz, torch.Tensor) and xyz.is_cuda and xyz.device.index == self.device and xyz.dtype == torch.float32 and
+                    xyz.dim() == 2 and xyz.shape[1] == 3 and xyz.is_contiguous()):
+                raise ValueError(f"update_vertices: expected a contiguous float32 (n, 3) tensor on cuda:{self.device}, got "
+                                 f"{getattr(xyz, 'dtype', None)} {tuple(getattr(xyz, 'shape', ()))} on {getattr(xyz, 'device', None)}")
+            ptr = xyz.data_ptr()
+            if stream is None:
+                stream = torch.cuda.current_stream(xyz.device)
+        else:
+            raise ValueError(f"update_vertices: expected a numpy array or a torch tensor, got {type(xyz).__name__}")
+        if stream is not None and not isinstance(stream, int):
+            stream = stream.cuda_stream   # a torch.cuda.Stream
+        _check(lib().gnxr_scene_update_vertices(self._h, int(first_vertex), int(xyz.shape[0]), C.c_void_p(ptr or None), C.c_void_p(stream or None)))
+
+    def set_camera(self, eye=(0, 0, 5), look=(0, 0, 0), up=(0, 1, 0), fov=90.0, lens_radius=0.0, focal_distance=3.0, orthographic=False, medium=-1):
+        """The camera of SceneBuilder.set_camera (and the medium it sits in, -1 == none) for later renders."""
+        cam = Camera(_f3(eye), _f3(look), _f3(up), fov, lens_radius, focal_distance, int(bool(orthographic)))
+        _check(lib().gnxr_scene_set_camera(self._h, C.byref(cam), int(medium)))
 
     # Aggregate seam: Scene::Intersect / IntersectP, batched
     def bvh(self):

@@ -124,6 +124,8 @@ PROTOTYPES = {
     "gnxr_scene_create": (C.c_int, [P(SceneDesc), P(VP)]),
     "gnxr_scene_destroy": (None, [VP]),
     "gnxr_scene_info": (C.c_int, [VP, P(i32), P(i32), P(i32)]),
+    "gnxr_scene_update_vertices": (C.c_int, [VP, i32, i32, VP, VP]),   # xyz: host or device address
+    "gnxr_scene_set_camera": (C.c_int, [VP, P(Camera), i32]),
     "gnxr_render": (C.c_int, [VP, P(RenderParams), P(f32), P(Stats)]),
     "gnxr_render_device": (C.c_int, [VP, P(RenderParams), VP, VP, P(Stats)]),
     "gnxr_render_reserve": (C.c_int, [VP, P(RenderParams)]),

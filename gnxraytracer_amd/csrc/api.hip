@@ -22,6 +22,7 @@
 #include "trace4d_kernel.hip.h"
 #endif
 #include "hlbvh_build.hip.h"
+#include "refit_kernel.hip.h"
 #include "kernel_instances.h"
 
 using namespace gnxr;
@@ -202,8 +203,26 @@ struct gnxr_scene {
     DevBuf<float4> shard_out;            // a replica's full-size output plane; its rows are peer-copied into the primary's image
     void *h_stage = nullptr;             // pinned: a replica's rows on their way to the primary when the two devices have no peer access
     size_t h_stage_bytes = 0;
+    // gnxr_scene_update_vertices: the refit's tables (CompiledScene::corner_vertex / node_parent / node4_src, uploaded at the first update),
+    // the arrival counters of k_refit_fit, the staged positions and the emissive-vertex flag
+    DevBuf<int32_t> upd_corner, upd_parent, upd_node4_src;
+    DevBuf<unsigned int> upd_arrived;
+    DevBuf<float> upd_xyz;
+    DevBuf<int> upd_flag;
+    bool host_bvh_stale = false;         // after an update cs.nodes / nodes4 / tris / leaf_boxes lag the device until sync_host_bvh()
 
     int bind() const { HIP_TRY(hipSetDevice(device)); return GNXR_OK; }
+    // the host copies of the geometry tables, downloaded on demand after gnxr_scene_update_vertices (only readers pay for them)
+    int sync_host_bvh() {
+        if (!host_bvh_stale) return GNXR_OK;
+        if (int rc = bind()) return rc;
+        HIP_TRY(hipMemcpy(cs.nodes.data(), nodes.p, cs.nodes.size() * sizeof(DNode), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(cs.nodes4.data(), nodes4.p, cs.nodes4.size() * sizeof(DNode4), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(cs.tris.data(), tris.p, cs.tris.size() * sizeof(DTri), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(cs.leaf_boxes.data(), leaf_boxes.p, cs.leaf_boxes.size() * sizeof(float), hipMemcpyDeviceToHost));
+        host_bvh_stale = false;
+        return GNXR_OK;
+    }
     ~gnxr_scene() {
         if (h_counters) (void)hipHostFree(h_counters);
         if (h_ring) (void)hipHostFree(h_ring);
@@ -637,6 +656,110 @@ int gnxr_scene_info(const gnxr_scene *s, int32_t *n_nodes, int32_t *max_depth, i
     if (n_nodes) *n_nodes = (int32_t)s->cs.nodes.size();
     if (max_depth) *max_depth = s->cs.bvh_max_depth;
     if (n_vox) *n_vox = s->grid_strategy >= 0 ? s->grid.nvox[0] * s->grid.nvox[1] * s->grid.nvox[2] : 0;
+    return GNXR_OK;
+}
+
+// ---- editing a scene in place (gnxr_scene_update_vertices / gnxr_scene_set_camera) ----
+// the refit's tables go to a device at the first update of the scene (the flag is allocated last: it marks the set complete)
+static int refit_tables(gnxr_scene *s) {
+    if (s->upd_flag.p) return GNXR_OK;
+    const CompiledScene &cs = s->cs;
+    int rc;
+    if ((rc = s->upd_corner.upload(cs.corner_vertex)) || (rc = s->upd_parent.upload(cs.node_parent)) || (rc = s->upd_node4_src.upload(cs.node4_src)) ||
+        (rc = s->upd_arrived.alloc(cs.nodes.size())) || (rc = s->upd_flag.alloc(1)))
+        return rc;
+    return GNXR_OK;
+}
+
+// positions of vertices [first, first + n) staged in s->upd_xyz -> triangles, binary tree, 4-wide tree on the scene's (bound) device;
+// returns the refitted root box.  Topology, primitive order and every id stay as they are, so the one-triangle leaves still have the
+// min / max of their triangle's corners as their box (k_refit_fit computes it so) and CompiledScene::leaf1_from_verts keeps its value.
+static int refit_apply(gnxr_scene *s, int first, int n, hipStream_t st, float root6[6]) {
+    const CompiledScene &cs = s->cs;
+    const int nt = (int)cs.tris.size(), nn = (int)cs.nodes.size(), nslots = (int)cs.node4_src.size();
+    hipLaunchKernelGGL(refit::k_refit_tris, dim3(grid_for(nt)), dim3(refit::kB), 0, st, s->tris.p, (const int *)s->upd_corner.p, nt, first, n, (const float *)s->upd_xyz.p);
+    HIP_TRY(hipMemsetAsync(s->upd_arrived.p, 0, (size_t)nn * sizeof(unsigned int), st));
+    hipLaunchKernelGGL(refit::k_refit_fit, dim3(grid_for(nn)), dim3(refit::kB), 0, st, nn, s->nodes.p, (const int *)s->upd_parent.p, s->upd_arrived.p, (const DTri *)s->tris.p,
+                       s->leaf_boxes.p);
+    // (the 4-wide slots copy finished boxes: the launch boundary orders them after the fit; k_trace4's top-of-tree LDS copy is
+    // loaded from nodes4 at the start of every launch)
+    hipLaunchKernelGGL(refit::k_refit_wide, dim3(grid_for(nslots)), dim3(refit::kB), 0, st, nslots, s->nodes4.p, (const int *)s->upd_node4_src.p, (const DNode *)s->nodes.p);
+    HIP_TRY(hipGetLastError());
+    DNode root;
+    HIP_TRY(hipMemcpyAsync(&root, s->nodes.p, sizeof(DNode), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    root6[0] = root.lo[0]; root6[1] = root.lo[1]; root6[2] = root.lo[2]; root6[3] = root.hi0; root6[4] = root.hi1; root6[5] = root.hi2;
+    return GNXR_OK;
+}
+
+// what depends on the world bound, on the host: Scene::WorldBound, the environment light's bounding sphere (DEnv, read at every render),
+// the delta lights' radius (re-uploaded) and the light-selection table (rebuilt by ensure_grid at the next render)
+static int refit_world(gnxr_scene *s, const CompiledScene &from) {
+    if (int rc = s->bind()) return rc;
+    s->cs.world_bound = from.world_bound;
+    s->cs.env = from.env;
+    s->cs.lights = from.lights;
+    HIP_TRY(hipMemcpy(s->lights.p, s->cs.lights.data(), s->cs.lights.size() * sizeof(DLight), hipMemcpyHostToDevice));
+    s->grid_strategy = -1;
+    s->host_bvh_stale = true;
+    return GNXR_OK;
+}
+
+int gnxr_scene_update_vertices(gnxr_scene *s, int32_t first_vertex, int32_t n_vertices, const float *xyz, void *hip_stream) {
+    if (!s) { set_error("null scene"); return GNXR_ERR_INVALID; }
+    if (n_vertices > 0 && !xyz) { set_error("null vertex array"); return GNXR_ERR_INVALID; }
+    if (first_vertex < 0 || n_vertices < 0 || (int64_t)first_vertex + n_vertices > (int64_t)s->cs.n_vertices) {
+        set_error("vertex range [%d, %lld) outside the scene's %d vertices", first_vertex, (long long)first_vertex + n_vertices, s->cs.n_vertices);
+        return GNXR_ERR_INVALID;
+    }
+    if (n_vertices == 0) return GNXR_OK;
+    std::lock_guard<std::recursive_mutex> lock(s->render_mutex);
+    int rc = s->bind();
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+    const size_t nf = 3 * (size_t)n_vertices;
+    if ((rc = refit_tables(s)) || (rc = s->upd_xyz.alloc(nf))) return rc;
+    // one copy path for host and device memory; ordered after what the caller queued on its stream
+    HIP_TRY(hipMemcpyAsync(s->upd_xyz.p, xyz, nf * sizeof(float), hipMemcpyDefault, st));
+    // emissive triangles keep their vertices (their DLight records hold them): refuse before anything is written
+    int h_flag = 0;
+    const int nt = (int)s->cs.tris.size();
+    HIP_TRY(hipMemsetAsync(s->upd_flag.p, 0, sizeof(int), st));
+    hipLaunchKernelGGL(refit::k_refit_check, dim3(grid_for(nt)), dim3(refit::kB), 0, st, (const DTri *)s->tris.p, (const int *)s->upd_corner.p, nt, first_vertex, n_vertices,
+                       (const float *)s->upd_xyz.p, s->upd_flag.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&h_flag, s->upd_flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (h_flag) { set_error("a vertex of an emissive (AREA_TRI) triangle would move: area lights are not updated in place"); return GNXR_ERR_UNSUPPORTED; }
+    float root6[6];
+    if ((rc = refit_apply(s, first_vertex, n_vertices, st, root6)) != GNXR_OK) return rc;
+    if (!s->replicas.empty()) {   // gnxr_init_devices: the same refit on every replica, from a host copy of the staged positions
+        std::vector<float> staged(nf);
+        HIP_TRY(hipMemcpy(staged.data(), s->upd_xyz.p, nf * sizeof(float), hipMemcpyDeviceToHost));
+        for (auto &r : s->replicas) {
+            float rroot[6];
+            if ((rc = r->bind()) || (rc = refit_tables(r.get())) || (rc = r->upd_xyz.upload(staged.data(), nf)) || (rc = refit_apply(r.get(), first_vertex, n_vertices, nullptr, rroot))) {
+                (void)s->bind();
+                return rc;
+            }
+        }
+    }
+    refit_world_bound(&s->cs, root6);
+    for (auto &r : s->replicas) if ((rc = refit_world(r.get(), s->cs)) != GNXR_OK) { (void)s->bind(); return rc; }
+    return refit_world(s, s->cs);
+}
+
+int gnxr_scene_set_camera(gnxr_scene *s, const gnxr_camera *camera, int32_t camera_medium) {
+    if (!s || !camera) { set_error("null argument"); return GNXR_ERR_INVALID; }
+    const int n_media = (int)s->cs.media.size();
+    // as gnxr_scene_create: -1 == none; without media any value means none
+    if (n_media > 0 && (camera_medium < -1 || camera_medium >= n_media)) { set_error("camera_medium %d out of range (%d media)", camera_medium, n_media); return GNXR_ERR_INVALID; }
+    std::lock_guard<std::recursive_mutex> lock(s->render_mutex);
+    for (size_t i = 0; i <= s->replicas.size(); ++i) {
+        CompiledScene &cs = i == 0 ? s->cs : s->replicas[i - 1]->cs;
+        cs.camera = *camera;
+        cs.camera_medium = n_media > 0 ? camera_medium : -1;
+    }
     return GNXR_OK;
 }
 
@@ -1479,11 +1602,15 @@ int gnxr_render(gnxr_scene *s, const gnxr_render_params *p, float *rgba_out, gnx
     return GNXR_OK;
 }
 
-int gnxr_scene_bvh(const gnxr_scene *s, float *bounds6, int32_t *meta3, int32_t *ordered, int64_t node_capacity, int64_t *n_nodes) {
-    if (!s || !n_nodes) { set_error("bad argument"); return GNXR_ERR_INVALID; }
+int gnxr_scene_bvh(const gnxr_scene *sc, float *bounds6, int32_t *meta3, int32_t *ordered, int64_t node_capacity, int64_t *n_nodes) {
+    if (!sc || !n_nodes) { set_error("bad argument"); return GNXR_ERR_INVALID; }
+    // const for the caller (the scene does not change); the host copies of the tree may still have to be refreshed after an update
+    gnxr_scene *s = const_cast<gnxr_scene *>(sc);
     const CompiledScene &cs = s->cs;
     *n_nodes = (int64_t)cs.nodes.size();
     if (!bounds6 || !meta3 || !ordered || node_capacity < *n_nodes) return GNXR_OK;
+    std::lock_guard<std::recursive_mutex> lock(s->render_mutex);
+    if (int rc = s->sync_host_bvh()) return rc;
     for (size_t i = 0; i < cs.nodes.size(); ++i) {
         const DNode &n = cs.nodes[i];
         bounds6[6 * i + 0] = n.lo[0]; bounds6[6 * i + 1] = n.lo[1]; bounds6[6 * i + 2] = n.lo[2];

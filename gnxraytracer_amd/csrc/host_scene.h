@@ -55,6 +55,11 @@ struct CompiledScene {
     std::vector<int32_t> leaf_of_prim;   // authoring index -> leaf index
     int bvh_max_depth = 0;
     Box3 world_bound;
+    // refit (gnxr_scene_update_vertices): host-only until the first update, when they go to the device
+    int n_vertices = 0;                  // gnxr_scene_desc::n_vertices
+    std::vector<int32_t> corner_vertex;  // 3 per leaf-order triangle: the authored vertex of each corner
+    std::vector<int32_t> node_parent;    // per DNode: its parent (-1 at the root)
+    std::vector<int32_t> node4_src;      // 4 per DNode4: the DNode behind each child slot (-1: kNode4Empty)
     // shading
     std::vector<DMaterial> materials;
     std::vector<DMaterial> materials_single;   // allowMultipleLobes == false (Whitted)
@@ -100,6 +105,9 @@ struct HlbvhNode { float b[6]; int32_t child[2]; int32_t axis, first, n; };   //
 typedef bool (*HlbvhBuildFn)(const float *prim_bounds6, const float *centroids3, int n, const float lo[3], const float hi[3],
                              std::vector<HlbvhNode> *nodes, int *root, uint32_t *prims_sorted);
 bool compile_scene(const gnxr_scene_desc *d, CompiledScene *out, HlbvhBuildFn hlbvh_build = nullptr);
+// after a refit: the root box of the binary BVH (lo.xyz hi.xyz) -> world_bound (grown by the spheres), the environment light's bounding
+// sphere and the distant lights' radius, computed as compile_scene computes them
+void refit_world_bound(CompiledScene *cs, const float root6[6]);
 DCamera make_camera(const gnxr_camera &c, int W, int H, int medium);      // camera/Perspective.cpp:114-135, core/Camera.h:54-75
 DHalton make_halton(int W, int H);                                          // samplers/HaltonSampler.cpp:33-60
 // light-selection table: dense restatement of core/LightDistribution.cpp (uniform / power / spatial)

@@ -154,12 +154,14 @@ namespace {
 inline bool is_leaf(const DNode &n) { return (n.meta & 0xffffu) != 0; }
 inline int32_t leaf_ref(const DNode &n) { return ~(int32_t)((uint32_t)n.offset | ((n.meta & 0x7fu) << 24)); }
 
-// returns a child reference for binary node `bi`; interior nodes become DNode4s (pre-order)
-int32_t collapse(const std::vector<DNode> &bn, int bi, std::vector<DNode4> &out, int depthStack, int *needStack) {
+// returns a child reference for binary node `bi`; interior nodes become DNode4s (pre-order).  src receives, 4 per DNode4, the binary node
+// each child slot copies its box from (-1 for an absent child): the refit refills the slots from the refitted binary tree.
+int32_t collapse(const std::vector<DNode> &bn, int bi, std::vector<DNode4> &out, std::vector<int32_t> &src, int depthStack, int *needStack) {
     const DNode &N = bn[bi];
     if (is_leaf(N)) return leaf_ref(N);
     int me = (int)out.size();
     out.push_back(DNode4());
+    src.insert(src.end(), 4, -1);
     DNode4 d;
     memset(&d, 0, sizeof(d));
     for (int k = 0; k < 4; ++k) d.child[k] = kNode4Empty;
@@ -201,7 +203,8 @@ int32_t collapse(const std::vector<DNode> &bn, int bi, std::vector<DNode4> &out,
         const DNode &g = bn[grand[k]];
         d.lox[k] = g.lo[0]; d.loy[k] = g.lo[1]; d.loz[k] = g.lo[2];
         d.hix[k] = g.hi0; d.hiy[k] = g.hi1; d.hiz[k] = g.hi2;
-        d.child[k] = collapse(bn, grand[k], out, below, needStack);
+        src[4 * (size_t)me + k] = grand[k];
+        d.child[k] = collapse(bn, grand[k], out, src, below, needStack);
     }
     out[me] = d;
     return me;
@@ -588,6 +591,43 @@ static void dist1d(const float *f, int n, float *cdf /*n+1*/, float *funcInt) { 
     else for (int i = 1; i < n + 1; ++i) cdf[i] /= *funcInt;
 }
 
+// ---- what depends on Scene::WorldBound (compile_scene, and refit_world_bound after gnxr_scene_update_vertices)
+// Scene::WorldBound covers every primitive (the light-selection grid is laid over it): the BVH's root box grown by the spheres
+static void grow_by_spheres(CompiledScene *cs) {
+    for (int i = 0; i < cs->n_spheres; ++i) {
+        const DSphere &sp = cs->spheres[i];
+        Box3 b;
+        b.grow(Vec3(sp.c[0] - sp.r, sp.c[1] - sp.r, sp.c[2] - sp.r));
+        b.grow(Vec3(sp.c[0] + sp.r, sp.c[1] + sp.r, sp.c[2] + sp.r));
+        cs->world_bound.grow(b);
+    }
+}
+// InfiniteAreaLight::Preprocess: scene.WorldBound().BoundingSphere (InfiniteAreaLight.h:23-26)
+static void env_bounding_sphere(CompiledScene *cs) {
+    DEnv &e = cs->env;
+    Vec3 c = (cs->world_bound.lo + cs->world_bound.hi) / 2;
+    e.world_center[0] = c.x; e.world_center[1] = c.y; e.world_center[2] = c.z;
+    e.world_radius = length(c - cs->world_bound.hi);
+}
+// DistantLight::Preprocess: scene.WorldBound().BoundingSphere (Geometry.h:770-773)
+static float distant_radius(const Box3 &wb) {
+    Vec3 c = (wb.lo + wb.hi) / 2;
+    bool inside = c.x >= wb.lo.x && c.x <= wb.hi.x && c.y >= wb.lo.y && c.y <= wb.hi.y && c.z >= wb.lo.z && c.z <= wb.hi.z;
+    return inside ? length(c - wb.hi) : 0.f;
+}
+
+void refit_world_bound(CompiledScene *cs, const float root6[6]) {
+    cs->world_bound = Box3();
+    cs->world_bound.lo = Vec3(root6[0], root6[1], root6[2]);
+    cs->world_bound.hi = Vec3(root6[3], root6[4], root6[5]);
+    grow_by_spheres(cs);
+    if (cs->has_env) env_bounding_sphere(cs);
+    for (size_t i = 0; i < cs->desc_lights.size(); ++i) {   // compile_scene sets the field for all three delta-light types; distant lights read it
+        const int t = cs->desc_lights[i].type;
+        if (t == GNXR_LIGHT_POINT || t == GNXR_LIGHT_SPOT || t == GNXR_LIGHT_DISTANT) cs->lights[i].radius = distant_radius(cs->world_bound);
+    }
+}
+
 // flip_y: SkyBoxLight::loadImage switches stb_image to vertically flipped loading for the whole process
 // (stbi_set_flip_vertically_on_load(true), lights/SkyBoxLight.cpp:19); an InfiniteAreaLight constructed after
 // a SkyBoxLight -- the order of ui/RenderThread.cpp:145-151 -- therefore sees its map upside down.
@@ -724,10 +764,7 @@ static void build_env(const gnxr_scene_desc *d, const gnxr_light &l, bool flip_y
     for (int v = 0; v < H2; ++v)
         for (int b = 0; b <= kEnvGuideCond; ++b)
             cs->env_cond_guide[(size_t)v * (kEnvGuideCond + 1) + b] = b == kEnvGuideCond ? (uint16_t)(W2 + 1) : (uint16_t)upper(&cs->env_cond_cdf[(size_t)v * (W2 + 1)], W2 + 1, (float)b / kEnvGuideCond);
-    // Preprocess: scene.WorldBound().BoundingSphere (InfiniteAreaLight.h:23-26)
-    Vec3 c = (cs->world_bound.lo + cs->world_bound.hi) / 2;
-    e.world_center[0] = c.x; e.world_center[1] = c.y; e.world_center[2] = c.z;
-    e.world_radius = length(c - cs->world_bound.hi);
+    env_bounding_sphere(cs);
     cs->has_env = true;
 }
 
@@ -877,9 +914,10 @@ bool compile_scene(const gnxr_scene_desc *d, CompiledScene *cs, HlbvhBuildFn hlb
     cs->bvh_max_depth = 0;
     flatten(bb.nodes, root, cs->nodes, 0, &cs->bvh_max_depth);
     cs->nodes4.clear();
+    cs->node4_src.clear();
     cs->stack4_need = 1;
-    cs->root4 = collapse(cs->nodes, 0, cs->nodes4, 0, &cs->stack4_need);
-    if (cs->nodes4.empty()) cs->nodes4.push_back(DNode4());
+    cs->root4 = collapse(cs->nodes, 0, cs->nodes4, cs->node4_src, 0, &cs->stack4_need);
+    if (cs->nodes4.empty()) { cs->nodes4.push_back(DNode4()); cs->node4_src.assign(4, -1); }
     else if (cs->root4 >= 0) {
         // Renumber the 4-wide nodes: the top of the tree in breadth-first order (indices [0, kTopNodes): what the traversal kernel keeps in
         // LDS), everything below in the depth-first order `collapse` produced (subtrees stay compact in memory).  Node numbers are only
@@ -898,11 +936,14 @@ bool compile_scene(const gnxr_scene_desc *d, CompiledScene *cs, HlbvhBuildFn hlb
         std::vector<int32_t> new_of(n);
         for (size_t i = 0; i < n; ++i) new_of[order[i]] = (int32_t)i;
         std::vector<DNode4> re(n);
+        std::vector<int32_t> re_src(4 * n);
         for (size_t i = 0; i < n; ++i) {
             re[i] = cs->nodes4[order[i]];
             for (int k = 0; k < 4; ++k) if (re[i].child[k] >= 0 && re[i].child[k] != kNode4Empty) re[i].child[k] = new_of[re[i].child[k]];
+            for (int k = 0; k < 4; ++k) re_src[4 * i + k] = cs->node4_src[4 * (size_t)order[i] + k];
         }
         cs->nodes4.swap(re);
+        cs->node4_src.swap(re_src);
         cs->root4 = new_of[cs->root4];
     }
     // bounds of every leaf of the binary tree, addressed by the leaf's first triangle: BVHAccel::Intersect tests a leaf's OWN box when
@@ -913,6 +954,9 @@ bool compile_scene(const gnxr_scene_desc *d, CompiledScene *cs, HlbvhBuildFn hlb
             float *lb = &cs->leaf_boxes[(size_t)n.offset * 8];
             lb[0] = n.lo[0]; lb[1] = n.lo[1]; lb[2] = n.lo[2]; lb[3] = n.hi0; lb[4] = n.hi1; lb[5] = n.hi2;
         }
+    cs->node_parent.assign(cs->nodes.size(), -1);   // interior node i: children i + 1 and offset
+    for (size_t i = 0; i < cs->nodes.size(); ++i)
+        if ((cs->nodes[i].meta & 0xffffu) == 0) { cs->node_parent[i + 1] = (int32_t)i; cs->node_parent[cs->nodes[i].offset] = (int32_t)i; }
     cs->world_bound.lo = Vec3(cs->nodes[0].lo[0], cs->nodes[0].lo[1], cs->nodes[0].lo[2]);
     cs->world_bound.hi = Vec3(cs->nodes[0].hi0, cs->nodes[0].hi1, cs->nodes[0].hi2);
     // ---- spheres (outside the BVH)
@@ -929,18 +973,18 @@ bool compile_scene(const gnxr_scene_desc *d, CompiledScene *cs, HlbvhBuildFn hlb
         ds.material = (sp.material >= 0 && d->materials[sp.material].type == GNXR_MAT_NONE) ? -1 : sp.material;
         ds.med_in = sp.medium_inside; ds.med_out = sp.medium_outside;
         ds.prim = d->n_triangles + i;
-        Box3 b;   // Scene::WorldBound covers every primitive (the light-selection grid is laid over it)
-        b.grow(Vec3(sp.center[0] - sp.radius, sp.center[1] - sp.radius, sp.center[2] - sp.radius));
-        b.grow(Vec3(sp.center[0] + sp.radius, sp.center[1] + sp.radius, sp.center[2] + sp.radius));
-        cs->world_bound.grow(b);
     }
     cs->n_spheres = d->n_spheres;
+    grow_by_spheres(cs);
     // ---- triangles in leaf order
     cs->tris.resize(d->n_triangles);
     cs->leaf_of_prim.assign(d->n_triangles, -1);
+    cs->n_vertices = d->n_vertices;
+    cs->corner_vertex.resize(3 * (size_t)d->n_triangles);
     for (int li = 0; li < d->n_triangles; ++li) {
         int prim = bb.ordered[li];
         cs->leaf_of_prim[prim] = li;
+        for (int c = 0; c < 3; ++c) cs->corner_vertex[3 * (size_t)li + c] = d->indices[3 * prim + c];
         DTri &t = cs->tris[li];
         Vec3 p0 = vert(d->indices[3 * prim]), p1 = vert(d->indices[3 * prim + 1]), p2 = vert(d->indices[3 * prim + 2]);
         t.p0[0] = p0.x; t.p0[1] = p0.y; t.p0[2] = p0.z; t.prim = prim;
@@ -1065,11 +1109,7 @@ bool compile_scene(const gnxr_scene_desc *d, CompiledScene *cs, HlbvhBuildFn hlb
             dl.inv_area = std::cos((kPi / 180) * l.falloff_start);          // cosFalloffStart
             Vec3 w = normalize(xform_vector(l2w, Vec3(l.center[0], l.center[1], l.center[2])));
             memcpy(dl.n, &w, 12);
-            // DistantLight::Preprocess: scene.WorldBound().BoundingSphere (Geometry.h:770-773)
-            Vec3 c = (cs->world_bound.lo + cs->world_bound.hi) / 2;
-            const Box3 &wb = cs->world_bound;
-            bool inside = c.x >= wb.lo.x && c.x <= wb.hi.x && c.y >= wb.lo.y && c.y <= wb.hi.y && c.z >= wb.lo.z && c.z <= wb.hi.z;
-            dl.radius = inside ? length(c - wb.hi) : 0.f;
+            dl.radius = distant_radius(cs->world_bound);
         } else { set_error("light %d: unknown type %d", i, l.type); return false; }
     }
     // ---- media

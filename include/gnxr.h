@@ -349,6 +349,21 @@ void gnxr_scene_destroy(gnxr_scene *scene);
 int gnxr_scene_bvh(const gnxr_scene *scene, float *bounds6, int32_t *meta3, int32_t *ordered, int64_t node_capacity, int64_t *n_nodes);
 int gnxr_scene_info(const gnxr_scene *scene, int32_t *n_bvh_nodes, int32_t *bvh_max_depth,
                     int32_t *n_light_voxels);
+/* -- editing a scene between frames (the viewer's `while (renderFlag)` loop, RenderThread.cpp:168-186): no recompilation, and the
+ * path state gnxr_render_reserve allocated stays where it is.
+ * Move vertices of an existing scene: positions [first_vertex, first_vertex + n_vertices) of the scene's vertex array
+ * (the numbering of gnxr_scene_desc.vertices, world space) become xyz[0 .. 3 n_vertices).  xyz may be host memory or
+ * device memory of the scene's (first) device; the read is ordered after work already queued on hip_stream (NULL: the null
+ * stream), and the refit runs on that stream.  The BVH keeps its topology and primitive order; its boxes are refitted on the
+ * device (exactly the LinearBVHNode bounds that topology has over the new vertices).  Returns when every device of the scene
+ * holds the new geometry.  Per-corner uvs / shading normals / tangents, spheres, materials and lights are unchanged; what depends
+ * on the world bound (environment and distant lights, the light-selection table) follows it.  GNXR_ERR_UNSUPPORTED (scene
+ * untouched) if a vertex of an emissive (AREA_TRI) triangle would change value; GNXR_ERR_INVALID for a null scene, a null xyz with
+ * n_vertices > 0 or a range outside the scene's vertices.  Traversal quality is that of the old topology: after large
+ * deformations build the scene again with gnxr_scene_create. */
+int gnxr_scene_update_vertices(gnxr_scene *scene, int32_t first_vertex, int32_t n_vertices, const float *xyz, void *hip_stream);
+/* Replace the camera (and the medium it sits in, -1 == none) for later renders; same checks as gnxr_scene_create. */
+int gnxr_scene_set_camera(gnxr_scene *scene, const gnxr_camera *camera, int32_t camera_medium);
 
 /* -- Integrator seam (replaces integrator->Render(*worldScene, frameTime), RenderThread.cpp:175).
  * rgba_out: width*height*4 fp32, row-major, pixel (x,y) at (x + y*width)*4, the layout of
