@@ -15,6 +15,7 @@ There is NO CPU fallback: every compute call goes through the HIP library and ra
 ``GnxrError`` if it (or a GPU) is missing.  The CPU restatement under ``oracle/`` is test
 infrastructure and is never imported from here.
 """
+import collections
 import ctypes as C
 import os
 
@@ -369,6 +370,65 @@ class Scene:
         _check(lib().gnxr_trace_any(self._h, rays.ctypes.data_as(C.POINTER(Ray)), len(rays),
                                     occ.ctypes.data_as(C.POINTER(C.c_uint8))))
         return occ
+
+    # batched queries on device memory (gnxr_trace_closest_device / gnxr_trace_any_device)
+    def _device_tensor(self, what, x, dtype, cols):
+        import torch
+        shape = (cols,) if cols else ()
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.device.index == self.device and x.dtype == dtype and
+                x.dim() == 1 + len(shape) and tuple(x.shape[1:]) == shape and x.is_contiguous()):
+            raise ValueError(f"{what}: expected a contiguous {dtype} (n{''.join(', %d' % c for c in shape)}) tensor on cuda:{self.device}, got "
+                             f"{type(x).__name__} {getattr(x, 'dtype', None)} {tuple(getattr(x, 'shape', ()))} on {getattr(x, 'device', None)}")
+        return x
+
+    def _query(self, name, rays, out, dtype, cols, stream):
+        import torch
+        self._device_tensor(f"{name}: rays", rays, torch.float32, 8)
+        n = rays.shape[0]
+        if out is None:
+            out = torch.empty((n, cols) if cols else (n,), dtype=dtype, device=rays.device)
+        else:
+            self._device_tensor(f"{name}: out", out, dtype, cols)
+            if out.shape[0] != n:
+                raise ValueError(f"{name}: out has {out.shape[0]} rows for {n} rays")
+        if stream is None:
+            stream = torch.cuda.current_stream(rays.device)
+        if not isinstance(stream, int):
+            stream = stream.cuda_stream   # a torch.cuda.Stream
+        fn = lib().gnxr_trace_closest_device if cols else lib().gnxr_trace_any_device
+        _check(fn(self._h, C.c_void_p(rays.data_ptr() or None), n, C.c_void_p(out.data_ptr() or None), C.c_void_p(stream or None)))
+        return out
+
+    def intersect(self, rays, out=None, stream=None):
+        """Scene::Intersect for rays already on the GPU: `rays` is a contiguous float32 (n, 8) tensor in the gnxr_ray layout (rays_tensor)
+        on the scene's device.  Returns RayHits: the (n, 8) float32 gnxr_hit records (`out` when given) and named views of them.  The
+        work is queued on `stream` (by default torch's current stream) and nothing waits for it; the results equal Intersect's bit for bit."""
+        import torch
+        hits = self._query("intersect", rays, out, torch.float32, 8, stream)
+        return RayHits(hits, hits.view(torch.int32)[:, 0], hits[:, 1], hits[:, 2:5], hits[:, 5:8])
+
+    def occluded(self, rays, out=None, stream=None):
+        """Scene::IntersectP for rays already on the GPU (see intersect): a uint8 (n,) tensor, 1 where something is hit in (0, tmax)."""
+        import torch
+        return self._query("occluded", rays, out, torch.uint8, 0, stream)
+
+
+RayHits = collections.namedtuple("RayHits", "hits prim t bary n")
+RayHits.__doc__ = """Scene.intersect's result: `hits`, the (n, 8) float32 gnxr_hit records, and views of it -- `prim` (int32: authoring-order
+triangle, n_triangles + sphere index, or -1 for a miss), `t`, `bary` (n, 3) = b0, b1, b2 and `n` (n, 3), the geometric normal."""
+
+
+def rays_tensor(o, d, tmax=float("inf")):
+    """The (n, 8) float32 gnxr_ray layout of Scene.intersect / occluded from torch tensors (the device counterpart of make_rays):
+    o, d of shape (n, 3) (or (3,) for one ray), tmax a number or an (n,) tensor."""
+    import torch
+    o = torch.as_tensor(o, dtype=torch.float32).reshape(-1, 3)
+    d = torch.as_tensor(d, dtype=torch.float32, device=o.device).reshape(-1, 3)
+    r = torch.zeros((o.shape[0], 8), dtype=torch.float32, device=o.device)
+    r[:, 0:3] = o
+    r[:, 3] = torch.as_tensor(tmax, dtype=torch.float32, device=o.device)
+    r[:, 4:7] = d
+    return r
 
 
 HIT_DTYPE = np.dtype([("prim", np.int32), ("t", np.float32), ("b0", np.float32), ("b1", np.float32), ("b2", np.float32),

@@ -131,6 +131,8 @@ PROTOTYPES = {
     "gnxr_render_reserve": (C.c_int, [VP, P(RenderParams)]),
     "gnxr_trace_closest": (C.c_int, [VP, P(Ray), i64, P(Hit)]),
     "gnxr_trace_any": (C.c_int, [VP, P(Ray), i64, P(u8)]),
+    "gnxr_trace_closest_device": (C.c_int, [VP, VP, i64, VP, VP]),   # device addresses + hipStream_t
+    "gnxr_trace_any_device": (C.c_int, [VP, VP, i64, VP, VP]),
     "gnxr_sample_halton": (C.c_int, [i32, i32, P(i32), P(i32), P(i64), P(i32), i64, P(f32)]),
     "gnxr_camera_rays": (C.c_int, [P(Camera), i32, i32, P(i32), P(i32), P(i64), i64, P(f32), P(f32)]),
     "gnxr_framebuffer_update": (C.c_int, [P(f32), P(f32), i32, i32, i32, P(u8)]),

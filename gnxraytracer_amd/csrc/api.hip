@@ -763,6 +763,39 @@ int gnxr_scene_set_camera(gnxr_scene *s, const gnxr_camera *camera, int32_t came
     return GNXR_OK;
 }
 
+// Launch shape of a traversal kernel (k_trace4 when `wide`, else k_trace) over `total` work items: LDS stack levels, LDS bytes, cached
+// top nodes and persistent blocks.  The render's trace stage and the batched queries size their launches here.
+struct TraceLaunch {
+    int entries;       // deepest stack the walk can need
+    int lds_entries;   // of which live in LDS (the rest spill to global memory: spill_needed)
+    bool spill_needed;
+    size_t lds;        // dynamic LDS bytes per block
+    int n_top;         // 4-wide nodes served from the block's LDS copy
+    int blocks;
+};
+static int trace_lds_levels_cap() {
+    static const int cap = getenv("GNXR_TRACE_LDS_LEVELS") ? std::max(2, atoi(getenv("GNXR_TRACE_LDS_LEVELS"))) : 64;   // tuning knob
+    return cap;
+}
+static TraceLaunch trace_launch(const gnxr_scene *s, bool wide, bool spheres, long long total) {
+    TraceLaunch t;
+    // LDS traversal stack: one column per lane, depth from the BVH (binary walk: depth + 1; 4-wide walk: stack4_need)
+    t.entries = wide ? s->cs.stack4_need + 1 : s->cs.bvh_max_depth + 2;
+    // 5 blocks of 4 waves per CU is what k_trace4's 96 VGPRs allow (5 waves per SIMD); the LDS of a block -- stack levels plus, for
+    // the 4-wide kernel, the set-up ray records and the node cache -- must fit 5 times into the 160 KB; deeper levels spill to
+    // global memory (LDS levels are worth more than a bigger node cache: profiles/README.md, r02 A/B table)
+    const int per_cu = g_trace_blocks_per_cu;
+    // besides the stack: the set-up ray records, the top-of-tree node cache and the order table
+    const size_t fixed_b = wide ? (size_t)(kRayRecDwords + (spheres ? 1 : 0)) * kRqStride * sizeof(int) + (size_t)kTopCache * 128 + 128 : 0;
+    t.lds_entries = std::min(std::min(t.entries, trace_lds_levels_cap()), std::max(2, (int)(((160 * 1024) / per_cu - 1024 - fixed_b) / (kBlock * sizeof(int)))));
+    t.spill_needed = t.entries > t.lds_entries;
+    t.lds = (size_t)t.lds_entries * kBlock * sizeof(int) + fixed_b;
+    t.n_top = (int)std::min<size_t>(kTopCache, s->cs.root4 >= 0 ? s->cs.nodes4.size() : 0);
+    // persistent waves: enough blocks to fill the chip, never more than the work needs
+    t.blocks = (int)std::min<long long>((long long)g_num_cus * per_cu, (total + kBlock - 1) / kBlock);
+    return t;
+}
+
 static int count_local_rows(const gnxr_render_params *p) {
     int rows = 0;
     for (int y = 0; y < p->height; ++y)
@@ -981,22 +1014,11 @@ static int render_one(gnxr_scene *s, const gnxr_render_params *pin, void *d_rgba
         // 51.7 ms per pass without counting the sort: slot order is already coherent in origin and sorting breaks the coalescing of the state
         // reads; the switch and its library sort are gone, `order` stays in TraceWork for callers that bring their own permutation)
         (void)hipMemsetAsync(&dctr->cursor, 0, sizeof(unsigned int), stream);
-        // LDS traversal stack: one column per lane, depth from the BVH (binary walk: depth + 1; 4-wide walk: stack4_need)
         const bool wide = s->wide_ok && !counting;
-        const int entries = wide ? s->cs.stack4_need + 1 : s->cs.bvh_max_depth + 2;
-        // 5 blocks of 4 waves per CU is what k_trace4's 96 VGPRs allow (5 waves per SIMD); the LDS of a block -- stack levels plus, for
-        // the 4-wide kernel, the set-up ray records and the node cache -- must fit 5 times into the 160 KB; deeper levels spill to
-        // global memory (LDS levels are worth more than a bigger node cache: profiles/README.md, r02 A/B table)
-        const int per_cu = g_trace_blocks_per_cu;
-        // besides the stack: the set-up ray records, the top-of-tree node cache and the order table
-        const size_t fixed_b = wide ? (size_t)(kRayRecDwords + (spheres ? 1 : 0)) * kRqStride * sizeof(int) + (size_t)kTopCache * 128 + 128 : 0;
-        static const int lds_levels_cap = getenv("GNXR_TRACE_LDS_LEVELS") ? std::max(2, atoi(getenv("GNXR_TRACE_LDS_LEVELS"))) : 64;   // tuning knob
-        const int lds_entries = std::min(std::min(entries, lds_levels_cap), std::max(2, (int)(((160 * 1024) / per_cu - 1024 - fixed_b) / (kBlock * sizeof(int)))));
-        const bool spill_needed = entries > lds_entries;
-        const size_t lds = (size_t)lds_entries * kBlock * sizeof(int) + fixed_b;
-        const int n_top = (int)std::min<size_t>(kTopCache, s->cs.root4 >= 0 ? s->cs.nodes4.size() : 0);
-        // persistent waves: enough blocks to fill the chip, never more than the work needs
-        int blocks = (int)std::min<long long>((long long)g_num_cus * per_cu, (total + kBlock - 1) / kBlock);
+        const TraceLaunch tl = trace_launch(s, wide, spheres, total);
+        const int entries = tl.entries, lds_entries = tl.lds_entries, n_top = tl.n_top, blocks = tl.blocks;
+        const bool spill_needed = tl.spill_needed;
+        const size_t lds = tl.lds;
         if (timing) timer.begin(0, stream);
         // rays per atomic: at most kTraceChunk; the kernel shrinks the chunk for thin launches so that every wave gets one (trace_chunk())
         static const int chunk_max = getenv("GNXR_TRACE_CHUNK") ? std::max(64, atoi(getenv("GNXR_TRACE_CHUNK")) / 64 * 64) : kTraceChunk;   // tuning knob
@@ -1009,7 +1031,7 @@ static int render_one(gnxr_scene *s, const gnxr_render_params *pin, void *d_rgba
         if (wide && dual && !count_wide) {
             const int dper_cu = GX_T4D_WAVES;   // blocks of 4 waves per CU = waves per SIMD
             const size_t dfixed = (size_t)(kRayRecDwords + (spheres ? 1 : 0)) * kRqStride * sizeof(int) + (size_t)kTopCacheD * 128 + 128;
-            const int dlds_entries = std::min(std::min(entries, lds_levels_cap), std::max(2, (int)(((160 * 1024) / dper_cu - 1024 - dfixed) / (2 * kBlock * sizeof(int)))));
+            const int dlds_entries = std::min(std::min(entries, trace_lds_levels_cap()), std::max(2, (int)(((160 * 1024) / dper_cu - 1024 - dfixed) / (2 * kBlock * sizeof(int)))));
             const int dspill_levels = std::max(0, entries - dlds_entries);
             const size_t dlds = (size_t)2 * dlds_entries * kBlock * sizeof(int) + dfixed;
             const int dn_top = (int)std::min<size_t>(kTopCacheD, s->cs.root4 >= 0 ? s->cs.nodes4.size() : 0);
@@ -1651,6 +1673,124 @@ int gnxr_trace_any(gnxr_scene *s, const gnxr_ray *rays, int64_t n, uint8_t *occl
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(occluded, dob.p, (size_t)n, hipMemcpyDeviceToHost));
     return GNXR_OK;
+}
+
+// ---- batched queries on device memory: gnxr_trace_closest_device / gnxr_trace_any_device ----
+// k_trace4 in its query modes (query_kernel.hip.h) on the caller's stream.  Nothing of the handle's render state is touched: the chunk
+// cursor and the global part of the traversal stack come from the stream-ordered allocator on the caller's stream (allocated, used and
+// freed in stream order; their size depends on the scene and the grid, never on n), so queries on several streams and a render in
+// flight on another stream never share scratch.
+
+// work items per k_trace4 launch: the kernel counts them in 32 bits (chunk_plan / chunk_range) and keeps a ray's index in an int
+static const long long kQueryLaunchMax = 1ll << 30;
+
+// The copy of `s` on the device that holds `ptr` (nullptr and the error set when `ptr` is not device memory, or no copy lives there).
+// `bytes`: the extent the call reads or writes, checked against the allocation whenever the runtime reports its range.
+static gnxr_scene *query_replica(gnxr_scene *s, const void *ptr, size_t bytes, const char *what) {
+    hipPointerAttribute_t a;
+    const hipError_t e = hipPointerGetAttributes(&a, ptr);
+    (void)hipGetLastError();   // memory the runtime has never seen makes the call fail: that is the answer, not an error of later calls
+    if (e != hipSuccess || a.type != hipMemoryTypeDevice) {
+        set_error("%s is not device memory (host arrays go through gnxr_trace_closest / gnxr_trace_any)", what);
+        return nullptr;
+    }
+    gnxr_scene *r = nullptr;
+    if (s->device == a.device) r = s;
+    for (size_t i = 0; !r && i < s->replicas.size(); ++i) if (s->replicas[i]->device == a.device) r = s->replicas[i].get();
+    if (!r) { set_error("%s lives on device %d, which holds no copy of the scene", what, a.device); return nullptr; }
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)ptr) == hipSuccess && base && (const char *)ptr + bytes > (const char *)base + size) {
+        set_error("%s: %zu bytes from %p run past the end of its allocation (%zu bytes from %p)", what, bytes, ptr, size, (void *)base);
+        return nullptr;
+    }
+    (void)hipGetLastError();
+    return r;
+}
+
+// any == false: Scene::Intersect, out = gnxr_hit[n]; any == true: Scene::IntersectP, out = uint8_t[n]
+static int trace_device(gnxr_scene *s, const gnxr_ray *d_rays, int64_t n, void *out, void *hip_stream, bool any) {
+    if (!s || n < 0 || (n > 0 && (!d_rays || !out))) { set_error("bad argument"); return GNXR_ERR_INVALID; }
+    if (n == 0) return GNXR_OK;
+    if (((uintptr_t)d_rays & 15u) != 0) { set_error("d_rays is not 16-byte aligned (two dwordx4 loads per ray)"); return GNXR_ERR_INVALID; }
+    if (!any && ((uintptr_t)out & 3u) != 0) { set_error("d_hits is not 4-byte aligned"); return GNXR_ERR_INVALID; }
+    const size_t out_bytes = (size_t)n * (!any ? sizeof(gnxr_hit) : 1);
+    gnxr_scene *r = query_replica(s, d_rays, (size_t)n * sizeof(gnxr_ray), "d_rays");
+    if (!r) return GNXR_ERR_INVALID;
+    gnxr_scene *ro = query_replica(s, out, out_bytes, !any ? "d_hits" : "d_occluded");
+    if (!ro) return GNXR_ERR_INVALID;
+    if (ro != r) { set_error("d_rays and the output live on different devices"); return GNXR_ERR_INVALID; }
+    int rc = r->bind();
+    if (rc) return rc;
+    struct Rebind { gnxr_scene *s; bool on; ~Rebind() { if (on) (void)s->bind(); } } rebind{s, r != s};   // leave the primary device current
+    hipStream_t st = (hipStream_t)hip_stream;
+    const CompiledScene &cs = r->cs;
+    // the tables the walk and the hit record read (device_scene() would also read the light and sampler state, which a render may be rebuilding)
+    DScene sc = {};
+    sc.nodes = reinterpret_cast<const float4 *>(r->nodes.p);
+    sc.nodes4 = reinterpret_cast<const float4 *>(r->nodes4.p);
+    sc.root4 = cs.root4;
+    sc.tris = r->tris.p;
+    sc.leaf_box = reinterpret_cast<const float4 *>(r->leaf_boxes.p);
+    static const bool no_verts = getenv("GNXR_LEAF_BOX_TABLE") != nullptr;   // as device_scene()
+    sc.leaf1_from_verts = (cs.leaf1_from_verts && !no_verts) ? 1 : 0;
+    sc.spheres = r->spheres.p;
+    sc.n_spheres = cs.n_spheres;
+    sc.materials = r->materials.p + 1;
+    const bool spheres = cs.n_spheres > 0;
+    if (!r->wide_ok) {   // trees the 4-wide encoding cannot hold (or GNXR_BINARY_BVH at creation): the reference's binary walk, same results
+        const int big = r->stack_size > 32;
+        if (!any) {
+            if (big) hipLaunchKernelGGL((k_trace_closest_api<64>), dim3(grid_for(n, 2)), dim3(kBlock), 0, st, sc, d_rays, (long long)n, (gnxr_hit *)out);
+            else hipLaunchKernelGGL((k_trace_closest_api<32>), dim3(grid_for(n, 5)), dim3(kBlock), 0, st, sc, d_rays, (long long)n, (gnxr_hit *)out);
+        } else {
+            if (big) hipLaunchKernelGGL((k_trace_any_api<64>), dim3(grid_for(n, 2)), dim3(kBlock), 0, st, sc, d_rays, (long long)n, (unsigned char *)out);
+            else hipLaunchKernelGGL((k_trace_any_api<32>), dim3(grid_for(n, 5)), dim3(kBlock), 0, st, sc, d_rays, (long long)n, (unsigned char *)out);
+        }
+        HIP_TRY(hipGetLastError());
+        return GNXR_OK;
+    }
+    // scratch of this call: [cursor | pad to 256 B | spill columns of the grid the largest launch uses]
+    const TraceLaunch tl = trace_launch(r, true, spheres, std::min<long long>(n, kQueryLaunchMax));
+    const size_t spill_ints = tl.spill_needed ? (size_t)(tl.entries - tl.lds_entries) * (size_t)tl.blocks * kBlock : 0;
+    char *scratch = nullptr;
+    HIP_TRY(hipMallocAsync((void **)&scratch, 256 + spill_ints * sizeof(int), st));
+    unsigned int *cursor = reinterpret_cast<unsigned int *>(scratch);
+    int *spill = reinterpret_cast<int *>(scratch + 256);
+    hipError_t e = hipSuccess;
+    for (long long base = 0; base < n && e == hipSuccess; base += kQueryLaunchMax) {
+        const long long cnt = std::min<long long>(n - base, kQueryLaunchMax);
+        const TraceLaunch t = trace_launch(r, true, spheres, cnt);
+        QueryArrays qa;
+        qa.rays = reinterpret_cast<const float4 *>(d_rays + base);
+        qa.hits = any ? nullptr : (gnxr_hit *)out + base;
+        qa.occluded = any ? (unsigned char *)out + base : nullptr;
+        TraceWork w = {};
+        w.n_closest = (int)cnt;
+        if ((e = hipMemsetAsync(cursor, 0, sizeof(unsigned int), st)) != hipSuccess) break;
+#define GX_QUERY4(S, P, Q) hipLaunchKernelGGL((k_trace4<false, S, P, Q>), dim3(t.blocks), dim3(kBlock), t.lds, st, sc, qa, w, cursor, (Counters *)nullptr, t.lds_entries, spill, kTraceChunk, t.n_top)
+#define GX_QUERY4_SP(Q) do { if (spheres) { if (t.spill_needed) GX_QUERY4(true, true, Q); else GX_QUERY4(true, false, Q); } \
+                             else { if (t.spill_needed) GX_QUERY4(false, true, Q); else GX_QUERY4(false, false, Q); } } while (0)
+        if (any) GX_QUERY4_SP(kT4QueryAny);
+        else GX_QUERY4_SP(kT4QueryClosest);
+#undef GX_QUERY4_SP
+#undef GX_QUERY4
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && !any) {
+        hipLaunchKernelGGL(k_query_finish, dim3(grid_for(n)), dim3(kBlock), 0, st, sc, reinterpret_cast<const float4 *>(d_rays), (long long)n, (gnxr_hit *)out);
+        e = hipGetLastError();
+    }
+    const hipError_t ef = hipFreeAsync(scratch, st);   // stream-ordered: after the launches above
+    HIP_TRY(e);
+    HIP_TRY(ef);
+    return GNXR_OK;
+}
+int gnxr_trace_closest_device(gnxr_scene *s, const gnxr_ray *d_rays, int64_t n, gnxr_hit *d_hits, void *hip_stream) {
+    return trace_device(s, d_rays, n, d_hits, hip_stream, false);
+}
+int gnxr_trace_any_device(gnxr_scene *s, const gnxr_ray *d_rays, int64_t n, uint8_t *d_occluded, void *hip_stream) {
+    return trace_device(s, d_rays, n, d_occluded, hip_stream, true);
 }
 
 // sampler tables without a scene (probes)

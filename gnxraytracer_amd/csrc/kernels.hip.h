@@ -736,6 +736,35 @@ static __global__ void __launch_bounds__(kBlock) k_finish(DRender r, const float
 
 // ------------------------------------------------------------------------------------------------
 // Aggregate seam kernels: Scene::Intersect / IntersectP for caller-supplied rays
+
+// The gnxr_hit of one ray's closest hit.  `code` is what the traversal found: a leaf-order triangle, -1 (nothing) or -2 - i (sphere i);
+// `h` holds that triangle's (t, b0, b1, b2), or in h.t the sphere's hit distance.  Shared by k_trace_closest_api (the host entry point)
+// and k_query_finish (query_kernel.hip.h: the device entry point), so that the two records cannot drift apart.
+GX_DEV gnxr_hit hit_record(const DScene &sc, V3 ro, V3 rd, int code, const TriHit &h) {
+    gnxr_hit out;
+    out.prim = -1; out.t = 0; out.b0 = out.b1 = out.b2 = 0; out.n[0] = out.n[1] = out.n[2] = 0;
+    if (code < -1) {
+        const int si = -2 - code;
+        SurfacePoint sp = sphere_surface_point(sc.spheres[si], ro, rd, h.t, false);
+        out.prim = sc.spheres[si].prim; out.t = h.t;
+        out.n[0] = sp.n.x; out.n[1] = sp.n.y; out.n[2] = sp.n.z;
+    }
+    if (code >= 0) {
+        const int leaf = code;
+        V3 p0, p1, p2;
+        load_tri(sc.tris, leaf, &p0, &p1, &p2);
+        V3 nn = normalize(cross(p0 - p2, p1 - p2));
+        const DTexTables &tt = tex_tables(sc.materials);
+        if (tt.tri_n || tt.tri_s) {   // per-vertex normals / tangents flip isect->n onto the shading side (SetShadingGeometry(..., true), Triangle.cpp:296)
+            V3 dndu, dndv;
+            SurfacePoint sp = surface_point_tables(tt, leaf, p0, p1, p2, h, false, &dndu, &dndv);
+            if (sp.valid) nn = sp.n;
+        }
+        out.prim = sc.tris[leaf].prim; out.t = h.t; out.b0 = h.b0; out.b1 = h.b1; out.b2 = h.b2;
+        out.n[0] = nn.x; out.n[1] = nn.y; out.n[2] = nn.z;
+    }
+    return out;
+}
 template <int STACK>
 __global__ void __launch_bounds__(kBlock) k_trace_closest_api(DScene sc, const gnxr_ray *rays, long long n, gnxr_hit *hits) {
     __shared__ int stack[STACK * kBlock];
@@ -748,27 +777,8 @@ __global__ void __launch_bounds__(kBlock) k_trace_closest_api(DScene sc, const g
         int sphereHit = -1;
         for (int si = 0; si < sc.n_spheres; ++si) { float tH; if (sphere_test(sc.spheres[si], ro, rd, tMax, &tH)) { tMax = tH; sphereHit = si; } }
         int leaf = bvh_traverse<false, kBlock, false>(sc.nodes, sc.tris, ro, rd, tMax, &stack[threadIdx.x], &h, &tc);
-        gnxr_hit out;
-        out.prim = -1; out.t = 0; out.b0 = out.b1 = out.b2 = 0; out.n[0] = out.n[1] = out.n[2] = 0;
-        if (leaf < 0 && sphereHit >= 0) {
-            SurfacePoint sp = sphere_surface_point(sc.spheres[sphereHit], ro, rd, tMax, false);
-            out.prim = sc.spheres[sphereHit].prim; out.t = tMax;
-            out.n[0] = sp.n.x; out.n[1] = sp.n.y; out.n[2] = sp.n.z;
-        }
-        if (leaf >= 0) {
-            V3 p0, p1, p2;
-            load_tri(sc.tris, leaf, &p0, &p1, &p2);
-            V3 nn = normalize(cross(p0 - p2, p1 - p2));
-            const DTexTables &tt = tex_tables(sc.materials);
-            if (tt.tri_n || tt.tri_s) {   // per-vertex normals / tangents flip isect->n onto the shading side (SetShadingGeometry(..., true), Triangle.cpp:296)
-                V3 dndu, dndv;
-                SurfacePoint sp = surface_point_tables(tt, leaf, p0, p1, p2, h, false, &dndu, &dndv);
-                if (sp.valid) nn = sp.n;
-            }
-            out.prim = sc.tris[leaf].prim; out.t = h.t; out.b0 = h.b0; out.b1 = h.b1; out.b2 = h.b2;
-            out.n[0] = nn.x; out.n[1] = nn.y; out.n[2] = nn.z;
-        }
-        hits[i] = out;
+        if (leaf < 0) h.t = tMax;   // the sphere's hit distance (unused on a miss)
+        hits[i] = hit_record(sc, ro, rd, leaf >= 0 ? leaf : (sphereHit >= 0 ? -2 - sphereHit : -1), h);
     }
 }
 template <int STACK>

@@ -19,8 +19,11 @@
 //     misses, and 55 % of all node visits go to those 64 nodes;
 //   * the traversal stack is LDS-only when the tree's worst case fits (template SPILL = false): no address-space branch per push / pop;
 //   * node addresses are a uniform base + 32-bit offsets.
+// Q selects where the rays come from and where results go: the render's path records (kT4Render), or caller-supplied rays of a batched
+// query (kT4QueryClosest / kT4QueryAny, query_kernel.hip.h).  The walk between the two is the same code.
 #pragma once
 #include "kernels.hip.h"
+#include "query_kernel.hip.h"
 
 namespace gnxr {
 
@@ -49,6 +52,8 @@ constexpr int kRqStride = (kBlock / 64) * kRayQueue;   // dwords per record fiel
 GX_DEV int trace4_lds_dwords_per_thread(bool sph) { return kRayRecDwords + (sph ? 1 : 0); }
 
 // COUNT: count node steps / triangle tests / leaf re-tests.  SPH: the scene has spheres.  SPILL: the traversal stack may outgrow its LDS part.
+// Q: the ray source / retire step (kT4Render: `pa` is the render's PathArrays; the query modes: `pa` is a QueryArrays, `w` has n_closest
+// work items and nothing else, and the cursor / spill buffers belong to the call).
 // Tuning switches (tools/build_variant.sh + tests/dev_ab.py; the A/B table is in profiles/README.md).  Defaults = the fastest measured:
 // 5 waves per SIMD (96 VGPRs), scalar slab arithmetic (the packed-fp32 forms measured in round 2 -- 124 VGPRs, 4 waves -- are gone), 64-ray set-up batches, 64 cached nodes.
 #ifndef GX_T4_WAVES
@@ -59,8 +64,8 @@ GX_DEV int trace4_lds_dwords_per_thread(bool sph) { return kRayRecDwords + (sph 
 #else
 #define GX_T4_BOUNDS __launch_bounds__(kBlock)
 #endif
-template <bool COUNT, bool SPH, bool SPILL>
-__global__ void GX_T4_BOUNDS k_trace4(DScene sc, PathArrays pa, TraceWork w, unsigned int *cursor, Counters *ctr, int lds_entries, int *spill, int chunk, int n_top) {
+template <bool COUNT, bool SPH, bool SPILL, int Q = kT4Render>
+__global__ void GX_T4_BOUNDS k_trace4(DScene sc, typename Trace4Src<Q>::type pa, TraceWork w, unsigned int *cursor, Counters *ctr, int lds_entries, int *spill, int chunk, int n_top) {
     // LDS: [lds_entries * kBlock] stack columns | [(11 | 12) * kRqStride] ray records (SoA: field * kRqStride + wave * kRayQueue + slot) |
     //      [8 * kTopCache float4] top-of-tree nodes, SoA by plane (plane * kTopCache + node: conflict-free across nodes) | [128 B] order table
     extern __shared__ int smem[];
@@ -140,7 +145,9 @@ __global__ void GX_T4_BOUNDS k_trace4(DScene sc, PathArrays pa, TraceWork w, uns
     // write the result of the lane's finished ray
     auto retire_ray = [&]() {
         const int kind = pk & 3;
-        if (kind == 0) {
+        if constexpr (Q == kT4QueryClosest) pa.hits[path].prim = hitLeaf;   // k_query_finish writes the rest of the record
+        else if constexpr (Q == kT4QueryAny) pa.occluded[path] = hitLeaf != -1 ? 1 : 0;
+        else if (kind == 0) {
             pa.hit[path] = hitLeaf;
             // The shade class of a triangle hit is looked up from `hit` by the binning pass (k_compact_count<COMPACT_HITCLASS>: tri_class[hit]) --
             // a dependent gather here would stall the whole wave once per retire.  Only hits without a triangle get their class here.
@@ -205,7 +212,12 @@ __global__ void GX_T4_BOUNDS k_trace4(DScene sc, PathArrays pa, TraceWork w, uns
                         int kind_ = 0, path_, any_ = 0;
                         float tMax_;
                         valid = true;
-                        if (i < (unsigned)w.n_closest) {
+                        if constexpr (Q != kT4Render) {   // a query: the caller's gnxr_ray i, one kind for the whole launch
+                            path_ = (int)i;
+                            o4 = pa.rays[2 * (size_t)i]; d4 = pa.rays[2 * (size_t)i + 1];
+                            tMax_ = o4.w;
+                            kind_ = Q == kT4QueryAny ? 1 : 0; any_ = kind_;
+                        } else if (i < (unsigned)w.n_closest) {
                             path_ = w.q_closest ? w.q_closest[i] : (int)i;
                             o4 = pa.ray_o[(size_t)path_ * kRS]; d4 = pa.ray_d[(size_t)path_ * kRS];
                             tMax_ = o4.w;

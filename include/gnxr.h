@@ -384,6 +384,19 @@ int gnxr_render_reserve(gnxr_scene *scene, const gnxr_render_params *params);
 /* -- Aggregate seam (replaces Scene::Intersect / Scene::IntersectP), batched ------------ */
 int gnxr_trace_closest(gnxr_scene *scene, const gnxr_ray *rays, int64_t n, gnxr_hit *hits);
 int gnxr_trace_any(gnxr_scene *scene, const gnxr_ray *rays, int64_t n, uint8_t *occluded);
+/* Scene::Intersect / IntersectP for rays in DEVICE memory, ordered on the caller's stream; returns without waiting for the GPU.
+ * d_rays: n gnxr_ray records in device memory (hipMalloc, a torch tensor's data_ptr), 16-byte aligned.  d_hits (4-byte aligned) /
+ * d_occluded: n results in device memory of the same device.  Per ray the results are exactly those of gnxr_trace_closest /
+ * gnxr_trace_any (same gnxr_hit fields, bit for bit; occluded = 1 when anything is hit in (0, tmax)).  The work is queued on
+ * hip_stream (a hipStream_t; NULL: the null stream) after what the caller queued there: no synchronisation, no read-back, and no
+ * allocation whose size depends on n (the call's scratch comes from the stream-ordered allocator on hip_stream).  Calls on different
+ * streams against one handle may run at the same time, also while a gnxr_render_device of that handle is in flight.  With
+ * gnxr_init_devices the call runs on the copy of the scene on the device that holds the pointers.  n == 0 is a no-op.
+ * GNXR_ERR_INVALID, before anything is queued, for a null scene, a null pointer with n > 0, n < 0, pointers that are not device
+ * memory (host memory, registered or not, goes through the two calls above), pointers on a device without a copy of the scene,
+ * or a misaligned pointer.  The results may be read once the stream has reached them.                                            */
+int gnxr_trace_closest_device(gnxr_scene *scene, const gnxr_ray *d_rays, int64_t n, gnxr_hit *d_hits, void *hip_stream);
+int gnxr_trace_any_device(gnxr_scene *scene, const gnxr_ray *d_rays, int64_t n, uint8_t *d_occluded, void *hip_stream);
 
 /* -- sampler / camera probes (bit-exactness test hooks) --------------------------------- */
 /* HaltonSampler(spp, [0,width)x[0,height)) value of dimension dim[i] for sample s[i] of pixel
