@@ -22,7 +22,7 @@ import os
 import numpy as np
 
 from . import _abi
-from ._abi import (Camera, Hit, Light, Material, Medium, Ray, RenderParams, SceneDesc, Stats, Texture)  # noqa: F401
+from ._abi import (Camera, Hit, Light, LiSample, Material, Medium, Ray, RenderParams, SceneDesc, Stats, Texture)  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GNXR_LIB", os.path.join(_HERE, "libgnxr.so"))   # GNXR_LIB: A/B builds during tuning
@@ -431,6 +431,39 @@ def rays_tensor(o, d, tmax=float("inf")):
     return r
 
 
+def _tensor_layout(what, x, dtype, cols):
+    """a contiguous (n, cols) tensor of `dtype` (on any device: Scene._device_tensor checks the device)"""
+    import torch
+    if not (isinstance(x, torch.Tensor) and x.dtype == dtype and x.dim() == 2 and x.shape[1] == cols and x.is_contiguous()):
+        raise ValueError(f"{what}: expected a contiguous {dtype} (n, {cols}) tensor, got "
+                         f"{type(x).__name__} {getattr(x, 'dtype', None)} {tuple(getattr(x, 'shape', ()))}")
+    return x
+
+
+def li_samples(px, py, s, medium=-1):
+    """The (n, 4) int32 gnxr_li_sample records of PathIntegrator.Li -- pixel (px, py), sample s, starting medium (-1: none) per ray --
+    on the device of the first tensor argument.  Each argument is an integer tensor of shape (n,) or (), or an integer; they broadcast."""
+    import torch
+    args = {"px": px, "py": py, "s": s, "medium": medium}
+    device = next((a.device for a in args.values() if isinstance(a, torch.Tensor)), torch.device("cpu"))
+    cols = []
+    for name, a in args.items():
+        if isinstance(a, torch.Tensor):
+            if a.dtype.is_floating_point or a.dtype.is_complex or a.dtype == torch.bool or a.dim() > 1:
+                raise ValueError(f"li_samples: {name} must be an integer tensor of shape (n,) or (), got {a.dtype} {tuple(a.shape)}")
+            a = a.to(device=device, dtype=torch.int32)
+        elif isinstance(a, (int, np.integer)) and not isinstance(a, bool):
+            a = torch.tensor(int(a), dtype=torch.int32, device=device)
+        else:
+            raise ValueError(f"li_samples: {name} must be an integer or an integer tensor, got {type(a).__name__}")
+        cols.append(a.reshape(-1))
+    try:
+        cols = torch.broadcast_tensors(*cols)
+    except RuntimeError as e:
+        raise ValueError(f"li_samples: the arguments do not broadcast: {e}") from None
+    return torch.stack(cols, dim=1).contiguous()
+
+
 HIT_DTYPE = np.dtype([("prim", np.int32), ("t", np.float32), ("b0", np.float32), ("b1", np.float32), ("b2", np.float32),
                       ("n", np.float32, 3)])
 
@@ -465,6 +498,38 @@ class PathIntegrator:
         return RenderParams(width, height, spp, spp_begin, spp_end, self.maxDepth, self.rrThreshold, self.integrator,
                             self.strategy, shard_index, shard_count, shard_rows, samples_per_pass, getattr(self, "directStrategy", 0),
                             passes_in_flight)
+
+    def Li(self, scene, rays, samples, width, height, spp, out=None, stream=None, **kw):
+        """SamplerIntegrator::Li along caller rays already on the GPU (gnxr_li_device): `rays` is a contiguous float32 (n, 8) tensor in the
+        gnxr_ray layout (rays_tensor), `samples` the int32 (n, 4) gnxr_li_sample records (li_samples): the pixel and sample of a HaltonSampler
+        over (width, height, spp) each ray stands for -- the sampler continues at dimension 5, where GetCameraSample leaves it -- and the
+        medium it starts in.  Returns (L, stats dict): L is the float32 (n, 4) tensor (`out` when given) of (Li.rgb, 1) per ray; a record
+        out of range raises GnxrError after the run and its row is 0.  Runs on `stream` (by default torch's current stream) and returns
+        once L is written.  The other keyword arguments are Render's (samples_per_pass = paths per sub-pass, passes_in_flight)."""
+        import torch
+        _tensor_layout("Li: rays", rays, torch.float32, 8)
+        _tensor_layout("Li: samples", samples, torch.int32, 4)
+        n = rays.shape[0]
+        if samples.shape[0] != n:
+            raise ValueError(f"Li: {samples.shape[0]} sample records for {n} rays")
+        if out is not None:
+            _tensor_layout("Li: out", out, torch.float32, 4)
+            if out.shape[0] != n:
+                raise ValueError(f"Li: out has {out.shape[0]} rows for {n} rays")
+        scene._device_tensor("Li: rays", rays, torch.float32, 8)
+        scene._device_tensor("Li: samples", samples, torch.int32, 4)
+        if out is None:
+            out = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
+        scene._device_tensor("Li: out", out, torch.float32, 4)
+        if stream is None:
+            stream = torch.cuda.current_stream(rays.device)
+        if not isinstance(stream, int):
+            stream = stream.cuda_stream   # a torch.cuda.Stream
+        p = self.params(width, height, spp, **kw)
+        st = Stats()
+        _check(lib().gnxr_li_device(scene._h, C.byref(p), C.c_void_p(rays.data_ptr() or None), C.c_void_p(samples.data_ptr() or None), n,
+                                    C.c_void_p(out.data_ptr() or None), C.c_void_p(stream or None), C.byref(st)))
+        return out, stats_dict(st)
 
     def Render(self, scene, width, height, spp, **kw):
         """Integrator::Render: returns (float32 image [H, W, 4], stats dict)."""

@@ -107,6 +107,10 @@ class Hit(C.Structure):
     _fields_ = [("prim", i32), ("t", f32), ("b0", f32), ("b1", f32), ("b2", f32), ("n", f32 * 3)]
 
 
+class LiSample(C.Structure):
+    _fields_ = [("px", i32), ("py", i32), ("s", i32), ("medium", i32)]
+
+
 P = C.POINTER
 VP = C.c_void_p
 
@@ -133,6 +137,7 @@ PROTOTYPES = {
     "gnxr_trace_any": (C.c_int, [VP, P(Ray), i64, P(u8)]),
     "gnxr_trace_closest_device": (C.c_int, [VP, VP, i64, VP, VP]),   # device addresses + hipStream_t
     "gnxr_trace_any_device": (C.c_int, [VP, VP, i64, VP, VP]),
+    "gnxr_li_device": (C.c_int, [VP, P(RenderParams), VP, VP, i64, VP, VP, P(Stats)]),   # device addresses + hipStream_t
     "gnxr_sample_halton": (C.c_int, [i32, i32, P(i32), P(i32), P(i64), P(i32), i64, P(f32)]),
     "gnxr_camera_rays": (C.c_int, [P(Camera), i32, i32, P(i32), P(i32), P(i64), i64, P(f32), P(f32)]),
     "gnxr_framebuffer_update": (C.c_int, [P(f32), P(f32), i32, i32, i32, P(u8)]),
@@ -178,7 +183,7 @@ PROTOTYPES = {
 }
 
 
-ABI_STRUCTS = [Material, Light, Camera, Medium, SceneDesc, RenderParams, Stats, Ray, Hit, Sphere, Texture]
+ABI_STRUCTS = [Material, Light, Camera, Medium, SceneDesc, RenderParams, Stats, Ray, Hit, Sphere, Texture, LiSample]
 
 
 def bind(lib):

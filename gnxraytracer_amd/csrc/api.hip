@@ -23,6 +23,7 @@
 #endif
 #include "hlbvh_build.hip.h"
 #include "refit_kernel.hip.h"
+#include "li_kernel.hip.h"
 #include "kernel_instances.h"
 
 using namespace gnxr;
@@ -805,9 +806,20 @@ static int count_local_rows(const gnxr_render_params *p) {
 
 static thread_local bool g_reserve_only = false;   // gnxr_render_reserve: render_one stops after its allocations
 
+// gnxr_li_device: where the paths of render_one's loops come from and where their radiance goes when they do not come from the camera.
+// The loops then work on chunks of `n` caller rays (k_raygen_rays) instead of sub-passes of samples per pixel, and a finished chunk is
+// stored per ray (k_store_li) instead of being summed into the image (li_kernel.hip.h).  All three arrays are device memory.
+struct RaySource {
+    const gnxr_ray *rays;
+    const gnxr_li_sample *samples;
+    float *L;                     // float4 per ray
+    long long n;
+};
+
 // One device: the wavefront loop over the rows `pin` assigns to this shard, on the device the scene's tables live on.
-static int render_one(gnxr_scene *s, const gnxr_render_params *pin, void *d_rgba_out, void *hip_stream, gnxr_stats *stats) {
-    if (!s || !pin || !d_rgba_out) { set_error("null argument"); return GNXR_ERR_INVALID; }
+// src != nullptr: Li for the caller's rays instead (gnxr_li_device); `d_rgba_out` is then unused.
+static int render_one(gnxr_scene *s, const gnxr_render_params *pin, void *d_rgba_out, void *hip_stream, gnxr_stats *stats, const RaySource *src = nullptr) {
+    if (!s || !pin || (!d_rgba_out && !src)) { set_error("null argument"); return GNXR_ERR_INVALID; }
     gnxr_render_params p = *pin;
     if (p.shard_count <= 0) p.shard_count = 1;
     if (p.shard_rows <= 0) p.shard_rows = 1;
@@ -847,6 +859,12 @@ static int render_one(gnxr_scene *s, const gnxr_render_params *pin, void *d_rgba
     }
     bool textured_scene = false;
     for (const DMaterial &m : s->cs.materials) if (m.shade_class == 3) textured_scene = true;
+    if (src && textured_scene && (whitted || volpath)) {
+        // (their texture lookups at the first vertex take the camera's ray differentials, whitted_kernel.hip.h / vol_kernel.hip.h; caller
+        // rays carry none.  PathIntegrator drops them: PathIntegrator.cpp:67)
+        set_error("Li for caller rays: Whitted, DirectLighting and VolPath need camera ray differentials on scenes with image textures");
+        return GNXR_ERR_UNSUPPORTED;
+    }
     std::lock_guard<std::recursive_mutex> lock(s->render_mutex);
     if (int brc = s->bind()) return brc;
     auto t_start = std::chrono::steady_clock::now();
@@ -867,6 +885,9 @@ static int render_one(gnxr_scene *s, const gnxr_render_params *pin, void *d_rgba
     r.npix = local_rows * p.width;
     if (r.npix == 0) { if (stats) memset(stats, 0, sizeof(*stats)); return GNXR_OK; }
     int nsamples = p.spp_end - p.spp_begin;
+    // the unit of work the loops cut into passes: one sample of every pixel (r.npix paths), or one caller ray
+    const long long unit = src ? 1 : r.npix;
+    const long long unit_begin = src ? 0 : p.spp_begin, unit_end = src ? src->n : p.spp_end, n_units = unit_end - unit_begin;
     int k = p.samples_per_pass;
     const bool path_int = !whitted && !volpath;
     if (k <= 0) {
@@ -882,19 +903,19 @@ static int render_one(gnxr_scene *s, const gnxr_render_params *pin, void *d_rgba
         if (volpath) target = std::min<long long>(target, 64ll << 20);   // + 8 float4 of VolPath state per path
         if (whitted) target = (4ll << 20) / std::max(1, n_records / 4);
         if (path_int) target = 64ll << 20;
-        k = (int)std::max<long long>(1, std::min<long long>(nsamples, target / r.npix));
+        k = (int)std::max<long long>(1, std::min<long long>(n_units, target / unit));
     }
-    k = std::min(k, nsamples);
+    k = (int)std::min<long long>(k, n_units);
     // PathIntegrator: up to kMaxRegions sub-passes in flight at once, each in its own region of the state arrays (the device-driven loop
     // below).  passes_in_flight = 0 picks 4, fewer when the call has fewer sub-passes or the state would not fit the 32-bit work indices
     // or ~45 % of the free HBM (~230 B per path slot beyond what this handle already holds).
     static const int regions_env = getenv("GNXR_REGIONS") ? atoi(getenv("GNXR_REGIONS")) : 0;   // tuning knob
     static const bool pipeline = getenv("GNXR_PIPELINE") ? atoi(getenv("GNXR_PIPELINE")) != 0 : true;   // experiment switch: 0 = one pass at a time
     const int kh = k;
-    const size_t half = (size_t)r.npix * kh;   // slots of one region
+    const size_t half = (size_t)unit * kh;   // slots of one region
     int in_flight = 1;
     if (path_int && pipeline) {
-        const int n_subs = (nsamples + kh - 1) / kh;
+        const int n_subs = (int)std::min<long long>(kMaxRegions, (n_units + kh - 1) / kh);
         in_flight = p.passes_in_flight > 0 ? p.passes_in_flight : (regions_env > 0 ? regions_env : 4);
         in_flight = std::max(1, std::min(std::min(in_flight, kMaxRegions), n_subs));
         size_t free_b = 0, total_b = 0;
@@ -949,7 +970,7 @@ static int render_one(gnxr_scene *s, const gnxr_render_params *pin, void *d_rgba
         const int entries = std::max(s->cs.stack4_need + 1, s->cs.bvh_max_depth + 2);
         if ((rc = s->trace_spill.alloc((size_t)g_num_cus * g_trace_blocks_per_cu * kBlock * (size_t)entries * 2)) != GNXR_OK) return rc;   // (x 2: k_trace4d keeps two columns per lane)
     }
-    if ((rc = s->accum.alloc(r.npix)) != GNXR_OK) return rc;
+    if (!src && (rc = s->accum.alloc(r.npix)) != GNXR_OK) return rc;
     const int max_tiles = (int)((cap + kCompactTile - 1) / kCompactTile);
     if ((rc = s->tile_counts.alloc((size_t)5 * max_tiles)) != GNXR_OK) return rc;
     PathArrays pa;
@@ -976,7 +997,7 @@ static int render_one(gnxr_scene *s, const gnxr_render_params *pin, void *d_rgba
     }
 
     if (g_reserve_only) { if (stats) memset(stats, 0, sizeof(*stats)); return GNXR_OK; }
-    HIP_TRY(hipMemsetAsync(s->accum.p, 0, sizeof(float4) * r.npix, stream));
+    if (!src) HIP_TRY(hipMemsetAsync(s->accum.p, 0, sizeof(float4) * r.npix, stream));
     HIP_TRY(hipMemsetAsync(s->counters.p, 0, sizeof(Counters), stream));
     struct EventPair {   // destroyed on every exit path
         hipEvent_t a = nullptr, b = nullptr;
@@ -1172,6 +1193,20 @@ else hipLaunchKernelGGL((k_shade<LM_ALL, LTV, false, true>), g, b, slds, cst[3],
     if (timing) timer.end(stream);
         return GNXR_OK;
     };
+    // The two image stages of the loops, or their caller-ray counterparts (RaySource, li_kernel.hip.h): start the paths of units
+    // [u0, u0 + kk) in the slots of `at`, and hand the radiance of a finished (sub-)pass -- L by slot -- to the image or to the caller.
+    const int n_scene_media = (int)s->cs.media.size();
+    auto raygen = [&](const PathArrays &at, long long u0, int kk, unsigned char *medium_keys) {
+        const int n_new = (int)(unit * kk);
+        if (!src) hipLaunchKernelGGL(k_raygen, dim3(grid_for(n_new)), dim3(kBlock), 0, stream, sc, r, at, n_new, (int)u0);
+        else hipLaunchKernelGGL(k_raygen_rays, dim3(grid_for(n_new)), dim3(kBlock), 0, stream, sc, r, at, reinterpret_cast<const float4 *>(src->rays + u0),
+                                reinterpret_cast<const int4 *>(src->samples + u0), n_new, n_scene_media, medium_keys, dctr, u0);
+    };
+    auto resolve = [&](const PathArrays &at, long long u0, int kk) {
+        if (!src) hipLaunchKernelGGL(k_resolve, dim3(grid_for(r.npix)), dim3(kBlock), 0, stream, at, s->accum.p, r.npix, kk);
+        else hipLaunchKernelGGL(k_store_li, dim3(grid_for(kk)), dim3(kBlock), 0, stream, (const float4 *)at.L, reinterpret_cast<const int4 *>(src->samples + u0), r,
+                                n_scene_media, kk, reinterpret_cast<float4 *>(src->L) + u0);
+    };
     unsigned int loop_iterations = 0;
     unsigned long long new_paths = 0;   // PathIntegrator: camera rays started (their count is known to the host; the other rays are counted on the device)
     if (!whitted && !volpath) {
@@ -1180,15 +1215,16 @@ else hipLaunchKernelGGL((k_shade<LM_ALL, LTV, false, true>), g, b, slds, cst[3],
         // bounces of one sub-pass with the thin late bounces of the others (Russian roulette and escapes leave a few hundred thousand of a
         // sub-pass's paths after five bounces), so launches stay thick while the resident state is in_flight x kh samples per pixel
         // instead of two 128-sample passes.  Queues hold slots of all regions in ascending order; results per path do not depend on who
-        // shares a launch, and k_resolve runs per sub-pass in sample order, so images are unchanged bit for bit.
+        // shares a launch, and k_resolve runs per sub-pass in sample order, so images are unchanged bit for bit.  Caller rays (RaySource): a
+        // sub-pass is a chunk of up to kh rays, and a chunk that has ended is stored at once (every ray owns its result: no order to keep).
         //
         // The host never waits for the iteration it enqueues: every queue count stays on the device (kernels read them there; launches are
         // sized by upper bounds), and what the host needs for its decisions -- how many paths of each region are left -- it reads from a
         // ring of pinned copies that lag the GPU by up to `lag` iterations.  A stale zero is still a zero (a region only refills when the
         // host starts a sub-pass in it), and a stale count is an upper bound.  Reference loop: core/Integrator.cpp:256-293.
-        struct Sub { int s0, kk; };
+        struct Sub { long long u0; int kk; };
         std::vector<Sub> subs;
-        for (int s0 = p.spp_begin; s0 < p.spp_end; s0 += kh) subs.push_back(Sub{s0, std::min(kh, p.spp_end - s0)});
+        for (long long u0 = unit_begin; u0 < unit_end; u0 += kh) subs.push_back(Sub{u0, (int)std::min<long long>(kh, unit_end - u0)});
         const int R = in_flight;
         struct Region { int sub = -1, started = -1; long long paths = 0; } reg[kMaxRegions];
         static const int cut_env = getenv("GNXR_PIPE_CUT") ? atoi(getenv("GNXR_PIPE_CUT")) : -1;   // tuning knob: iterations between sub-pass starts
@@ -1230,8 +1266,8 @@ else hipLaunchKernelGGL((k_shade<LM_ALL, LTV, false, true>), g, b, slds, cst[3],
                 progress = false;
                 for (int rg = 0; rg < R; ++rg) {
                     Region &g = reg[rg];
-                    if (g.sub == (int)done_subs && newest_seen > g.started && seen.region_alive[rg] == 0) {
-                        hipLaunchKernelGGL(k_resolve, dim3(grid_for(r.npix)), dim3(kBlock), 0, stream, pa_at((size_t)rg * half), s->accum.p, r.npix, subs[g.sub].kk);
+                    if (g.sub >= 0 && (src || g.sub == (int)done_subs) && newest_seen > g.started && seen.region_alive[rg] == 0) {
+                        resolve(pa_at((size_t)rg * half), subs[g.sub].u0, subs[g.sub].kk);
                         ++launches; ++passes; ++done_subs;
                         g.sub = -1;
                         progress = true;
@@ -1267,9 +1303,9 @@ else hipLaunchKernelGGL((k_shade<LM_ALL, LTV, false, true>), g, b, slds, cst[3],
             const bool start = next_sub < subs.size() && free_rg >= 0 && (!any_active || iter - last_start >= stagger);
             if (start) {
                 const Sub &nw = subs[next_sub];
-                const int n_new = r.npix * nw.kk;
+                const int n_new = (int)(unit * nw.kk);
                 const size_t base = (size_t)free_rg * half;
-                hipLaunchKernelGGL(k_raygen, dim3(grid_for(n_new)), dim3(kBlock), 0, stream, sc, r, pa_at(base), n_new, nw.s0);
+                raygen(pa_at(base), nw.u0, nw.kk, nullptr);
                 // survivors + every slot of the new sub-pass, ascending: into the buffer the shaded queue came from
                 hipLaunchKernelGGL(k_queue_merge, dim3(grid_for(n_upper + n_new)), dim3(kBlock), 0, stream, (const int *)qbuf[out_idx], dctr, any_active ? 0 : 1, free_rg, (int)base, n_new, qbuf[in_idx]);
                 launches += 2;
@@ -1297,10 +1333,10 @@ else hipLaunchKernelGGL((k_shade<LM_ALL, LTV, false, true>), g, b, slds, cst[3],
             if (++guard > (1ll << 24)) { set_error("path loop did not terminate"); return GNXR_ERR_INVALID; }
         }
     } else
-    for (int s0 = p.spp_begin; s0 < p.spp_end; s0 += k) {
-        int kk = std::min(k, p.spp_end - s0);
-        int n_paths = r.npix * kk;
-        hipLaunchKernelGGL(k_raygen, dim3(grid_for(n_paths)), dim3(kBlock), 0, stream, sc, r, pa, n_paths, s0);
+    for (long long u0 = unit_begin; u0 < unit_end; u0 += k) {
+        int kk = (int)std::min<long long>(k, unit_end - u0);
+        int n_paths = (int)(unit * kk);
+        raygen(pa, u0, kk, (src && volpath) ? s->pflags.p : nullptr);
         ++launches;
         int n = n_paths;
         const int *q_in = nullptr;            // paths alive at this vertex (nullptr == identity), ascending
@@ -1350,6 +1386,13 @@ else hipLaunchKernelGGL((k_shade<LM_ALL, LTV, false, true>), g, b, slds, cst[3],
             ++launches;
             int n_media = r.cam.medium >= 0 ? n : 0;      // paths whose ray in flight travels inside a medium
             const int *q_media = nullptr;
+            if (src) {   // caller rays: each record names its own medium; list the slots k_raygen_rays marked (pflags bit 1)
+                compact(COMPACT_FLAGS, nullptr, n, s->pflags.p, 4, 2, &dctr->q_next, q_cur, s->queue_nee.p, nullptr);
+                HIP_TRY(hipMemcpyAsync(s->h_counters, dctr, sizeof(Counters), hipMemcpyDeviceToHost, stream));
+                HIP_TRY(hipStreamSynchronize(stream));
+                n_media = (int)s->h_counters->q_nee;
+                q_media = s->queue_nee.p;
+            }
             // packing (k_vol_pack, vol_kernel.hip.h): the two sets of the per-path arrays that carry state across rounds
             static const bool vol_pack = getenv("GNXR_VOL_PACK") ? atoi(getenv("GNXR_VOL_PACK")) != 0 : true;   // experiment switch
             auto pack_set = [&](bool alt) {
@@ -1440,14 +1483,16 @@ else hipLaunchKernelGGL((k_shade<LM_ALL, LTV, false, true>), g, b, slds, cst[3],
         {
             PathArrays pr = pa;
             if (volpath) pr.L = s->vol_Lout.p;   // VolPath: results sit at the paths' original slots (packing moves the working state)
-            hipLaunchKernelGGL(k_resolve, dim3(grid_for(r.npix)), dim3(kBlock), 0, stream, pr, s->accum.p, r.npix, kk);
+            resolve(pr, u0, kk);
         }
         ++launches;
         ++passes;
         if (timing) { HIP_TRY(hipStreamSynchronize(stream)); timer.collect(); }
     }
-    hipLaunchKernelGGL(k_finish, dim3(grid_for(r.npix)), dim3(kBlock), 0, stream, r, (const float4 *)s->accum.p, (float4 *)d_rgba_out);
-    ++launches;
+    if (!src) {
+        hipLaunchKernelGGL(k_finish, dim3(grid_for(r.npix)), dim3(kBlock), 0, stream, r, (const float4 *)s->accum.p, (float4 *)d_rgba_out);
+        ++launches;
+    }
     HIP_TRY(hipEventRecord(ev1, stream));
     HIP_TRY(hipMemcpyAsync(s->h_counters, dctr, sizeof(Counters), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
@@ -1468,7 +1513,7 @@ else hipLaunchKernelGGL((k_shade<LM_ALL, LTV, false, true>), g, b, slds, cst[3],
         }
         stats->rays_closest = rays_closest + (whitted ? s->h_counters->whitted_mis : 0);
         stats->rays_any = whitted ? s->h_counters->whitted_shadow : rays_any;
-        stats->camera_samples = (uint64_t)r.npix * nsamples;
+        stats->camera_samples = src ? (uint64_t)src->n : (uint64_t)r.npix * nsamples;
         stats->nodes_visited = s->h_counters->nodes;
         stats->tris_tested = s->h_counters->tris;
         stats->seconds_render = ms * 1e-3;
@@ -1489,6 +1534,11 @@ else hipLaunchKernelGGL((k_shade<LM_ALL, LTV, false, true>), g, b, slds, cst[3],
         stats->media_steps = s->h_counters->media_steps;
         stats->leaf_retests = s->h_counters->retests;
         stats->nodes_from_memory = s->h_counters->nodes_global;
+    }
+    if (src && s->h_counters->li_bad) {
+        set_error("gnxr_li_device: sample record %llu is out of range (px in [0, %d), py in [0, %d), s in [0, %d), medium in [-1, %d)); its L is (0, 0, 0, 0)",
+                  ~s->h_counters->li_bad, p.width, p.height, p.spp, n_scene_media);
+        return GNXR_ERR_INVALID;
     }
     return GNXR_OK;
 }
@@ -1791,6 +1841,33 @@ int gnxr_trace_closest_device(gnxr_scene *s, const gnxr_ray *d_rays, int64_t n, 
 }
 int gnxr_trace_any_device(gnxr_scene *s, const gnxr_ray *d_rays, int64_t n, uint8_t *d_occluded, void *hip_stream) {
     return trace_device(s, d_rays, n, d_occluded, hip_stream, true);
+}
+
+// ---- SamplerIntegrator::Li for caller rays on device memory: gnxr_li_device ----
+// render_one's loops with a RaySource in place of the camera and the image (li_kernel.hip.h), on the copy of the scene that holds the arrays.
+int gnxr_li_device(gnxr_scene *s, const gnxr_render_params *p, const gnxr_ray *d_rays, const gnxr_li_sample *d_samples, int64_t n, float *d_L, void *hip_stream,
+                   gnxr_stats *stats) {
+    if (int rc = ensure_device()) return rc;
+    if (!s || !p || n < 0 || (n > 0 && (!d_rays || !d_samples || !d_L))) { set_error("bad argument"); return GNXR_ERR_INVALID; }
+    if (p->spp_begin != 0 || p->spp_end != 0 || p->shard_index != 0 || p->shard_count < 0 || p->shard_count > 1 || p->shard_rows < 0 || p->shard_rows > 1) {
+        set_error("Li for caller rays: spp_begin, spp_end and shard_index must be 0, shard_count and shard_rows 0 or 1 (the records name each ray's sample)");
+        return GNXR_ERR_INVALID;
+    }
+    if (n == 0) { if (stats) memset(stats, 0, sizeof(*stats)); return GNXR_OK; }
+    if ((((uintptr_t)d_rays | (uintptr_t)d_samples | (uintptr_t)d_L) & 15u) != 0) { set_error("d_rays, d_samples and d_L must be 16-byte aligned"); return GNXR_ERR_INVALID; }
+    gnxr_scene *r = query_replica(s, d_rays, (size_t)n * sizeof(gnxr_ray), "d_rays");
+    if (!r) return GNXR_ERR_INVALID;
+    gnxr_scene *rs = query_replica(s, d_samples, (size_t)n * sizeof(gnxr_li_sample), "d_samples");
+    if (!rs) return GNXR_ERR_INVALID;
+    gnxr_scene *rl = query_replica(s, d_L, (size_t)n * 4 * sizeof(float), "d_L");
+    if (!rl) return GNXR_ERR_INVALID;
+    if (rs != r || rl != r) { set_error("d_rays, d_samples and d_L live on different devices"); return GNXR_ERR_INVALID; }
+    gnxr_render_params pp = *p;
+    pp.shard_count = 1; pp.shard_rows = 1;
+    const RaySource src{d_rays, d_samples, d_L, (long long)n};
+    const int rc = render_one(r, &pp, nullptr, hip_stream, stats, &src);
+    if (r != s) (void)s->bind();   // leave the primary device current
+    return rc;
 }
 
 // sampler tables without a scene (probes)

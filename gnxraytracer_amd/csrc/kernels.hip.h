@@ -91,6 +91,7 @@ struct Counters {
     unsigned int region_lb[kMaxRegions + 1];        // position in the survivors' queue of the first slot of each state region (k_loop_tail)
     unsigned int region_alive[kMaxRegions];         // paths of each region that continue
     unsigned long long rays_continue, rays_shadow, rays_mis;   // summed over the iterations: continuation rays of surviving paths, shadow rays, MIS rays
+    unsigned long long li_bad;                      // gnxr_li_device: ~index of the first sample record out of range (0: none; li_kernel.hip.h)
 };
 
 struct DScene {

@@ -836,6 +836,7 @@ int gnxr_abi_sizeof(int which) {
     case 8: return (int)sizeof(gnxr_hit);
     case 9: return (int)sizeof(gnxr_sphere);
     case 10: return (int)sizeof(gnxr_texture);
+    case 11: return (int)sizeof(gnxr_li_sample);
     default: return -1;
     }
 }

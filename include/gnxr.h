@@ -303,6 +303,9 @@ typedef struct gnxr_hit {
     float t, b0, b1, b2;
     float n[3];                 /* geometric normal as set by Triangle::Intersect            */
 } gnxr_hit;
+/* The sample a caller ray of gnxr_li_device stands for: pixel (px, py) and sample s of the render's HaltonSampler, and the medium
+ * the ray starts in (-1: none).  16 bytes.                                                                                        */
+typedef struct gnxr_li_sample { int32_t px, py, s, medium; } gnxr_li_sample;
 
 typedef struct gnxr_scene gnxr_scene;
 
@@ -397,6 +400,26 @@ int gnxr_trace_any(gnxr_scene *scene, const gnxr_ray *rays, int64_t n, uint8_t *
  * or a misaligned pointer.  The results may be read once the stream has reached them.                                            */
 int gnxr_trace_closest_device(gnxr_scene *scene, const gnxr_ray *d_rays, int64_t n, gnxr_hit *d_hits, void *hip_stream);
 int gnxr_trace_any_device(gnxr_scene *scene, const gnxr_ray *d_rays, int64_t n, uint8_t *d_occluded, void *hip_stream);
+
+/* -- Radiance seam (SamplerIntegrator::Li, core/Integrator.h), batched on device memory ---------------------------------
+ * For ray i, d_L[4i .. 4i+3] = (Li.r, Li.g, Li.b, 1): the Li of params->integrator along d_rays[i] (o, d; tmax bounds the first
+ * Intersect; _pad is ignored), with the sampler of a render with these params -- HaltonSampler(spp, [0,width) x [0,height)) --
+ * standing where Render leaves it after GetCameraSample: pixel (px, py), sample s of d_samples[i], dimension 5.  The ray starts in
+ * d_samples[i].medium (-1: none; only VolPath reads it).  Render is this Li on the camera rays, summed in sample order and divided
+ * by spp (core/Integrator.cpp:256-293), so a camera ray and its record give exactly the L that Render adds for that sample.
+ * max_depth, rr_threshold, integrator, light_strategy, direct_strategy and passes_in_flight mean what they mean for gnxr_render;
+ * samples_per_pass is the number of paths per sub-pass (0 = auto); spp_begin, spp_end and shard_index must be 0, shard_count and
+ * shard_rows 0 or 1.  The work is ordered after what hip_stream holds; the call returns once d_L is written (stats needs the
+ * device counters).  stats is filled as by a render, with camera_samples = n.  One render or Li call per handle at a time; path
+ * state comes from the handle's buffers.  With gnxr_init_devices the call runs on the copy of the scene on the arrays' device.
+ * GNXR_ERR_INVALID, before anything is queued: null scene or params, a null pointer with n > 0, n < 0, arrays that are not device
+ * memory, on a device without a copy of the scene, on different devices or not 16-byte aligned, invalid params.
+ * GNXR_ERR_UNSUPPORTED: spp beyond the 32-bit Halton indices of gnxr_render; Whitted, DirectLighting or VolPath on a scene with
+ * image textures (their first texture lookup needs camera ray differentials).  A record out of range (px, py outside the image,
+ * s outside [0, spp), medium outside [-1, n_media)) gets L = (0, 0, 0, 0); the other rays are finished and the call returns
+ * GNXR_ERR_INVALID naming the first such record.  n == 0 is a no-op.                                                         */
+int gnxr_li_device(gnxr_scene *scene, const gnxr_render_params *params, const gnxr_ray *d_rays, const gnxr_li_sample *d_samples, int64_t n,
+                   float *d_L, void *hip_stream, gnxr_stats *stats);
 
 /* -- sampler / camera probes (bit-exactness test hooks) --------------------------------- */
 /* HaltonSampler(spp, [0,width)x[0,height)) value of dimension dim[i] for sample s[i] of pixel
