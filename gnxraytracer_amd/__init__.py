@@ -412,6 +412,96 @@ class Scene:
         import torch
         return self._query("occluded", rays, out, torch.uint8, 0, stream)
 
+    # shading queries on device memory (gnxr_bsdf_device / gnxr_light_sample_device / gnxr_light_le_device)
+    def _query_args(self, name, args, out, out_cols, stream):
+        """`args`: (what, tensor, dtype, cols) each -- contiguous (n, cols) tensors on the scene's device with one n.  Returns
+        (n, out, hipStream_t, torch stream of that handle)."""
+        import torch
+        n = None
+        for what, x, dtype, cols in args:
+            _tensor_layout(f"{name}: {what}", x, dtype, cols)
+        for what, x, dtype, cols in args:
+            self._device_tensor(f"{name}: {what}", x, dtype, cols)
+            if n is None:
+                n = x.shape[0]
+            elif x.shape[0] != n:
+                raise ValueError(f"{name}: {what} has {x.shape[0]} rows for {n} {args[0][0]}")
+        device = args[0][1].device
+        if out is None:
+            out = torch.empty((n, out_cols), dtype=torch.float32, device=device)
+        else:
+            _tensor_layout(f"{name}: out", out, torch.float32, out_cols)
+            self._device_tensor(f"{name}: out", out, torch.float32, out_cols)
+            if out.shape[0] != n:
+                raise ValueError(f"{name}: out has {out.shape[0]} rows for {n} {args[0][0]}")
+        if stream is None:
+            stream = torch.cuda.current_stream(device)
+        tstream = stream if not isinstance(stream, int) else torch.cuda.ExternalStream(stream, device=device)
+        return n, out, tstream.cuda_stream, tstream
+
+    def bsdf(self, rays, wi, u, flags=31, differentials=None, out=None, stream=None):
+        """BSDF::f / Pdf / Sample_f at the hits of rays already on the GPU (gnxr_bsdf_device): Scene::Intersect along `rays` (float32
+        (n, 8), the gnxr_ray layout of rays_tensor), ComputeScatteringFunctions(Radiance, allowMultipleLobes = true) there and, with
+        wo = Normalize(-d): f and Pdf towards the world-space `wi` (n, 3), Sample_f with `u` (n, 2), under the BxDFType mask `flags`
+        (31 = BSDF_ALL).  `differentials`: None, or (n, 12) rxOrigin, rxDirection, ryOrigin, ryDirection (they filter image textures).
+        Returns a float32 (n, 16) tensor (`out` when given) whose columns are f[0:3], pdf[3], sample_f[4:7], sample_pdf[7],
+        sample_wi[8:11], sampled_type[11], n_components[12], valid[13], dudx[14], dvdy[15]; valid is 1 where the ray hit a surface
+        with a BSDF and the row is 0 elsewhere.  The three integers of the gnxr_bsdf_result records are converted to float32 here, on
+        the same stream, so that the tensor is one dtype.  Queued on `stream` (default: torch's current stream); nothing waits."""
+        import torch
+        args = [("rays", rays, torch.float32, 8), ("wi", wi, torch.float32, 3), ("u", u, torch.float32, 2)]
+        if differentials is not None:
+            args.append(("differentials", differentials, torch.float32, 12))
+        flags = int(flags)
+        if not 0 <= flags <= 31:
+            raise ValueError(f"bsdf: flags must be a BxDFType mask in [0, 31], got {flags}")
+        n, out, st, tstream = self._query_args("bsdf", args, out, 16, stream)
+        _check(lib().gnxr_bsdf_device(self._h, C.c_void_p(rays.data_ptr() or None), C.c_void_p(wi.data_ptr() or None), C.c_void_p(u.data_ptr() or None),
+                                      C.c_void_p(differentials.data_ptr() or None) if differentials is not None else None, n, flags,
+                                      C.c_void_p(out.data_ptr() or None), C.c_void_p(st or None)))
+        if n:
+            with torch.cuda.stream(tstream):
+                out[:, 11:14] = out.view(torch.int32)[:, 11:14].to(torch.float32)
+        return out
+
+    def sample_light(self, light, p, n, u, wi_query, strategy=_abi.LIGHTS_SPATIAL, out=None, stream=None):
+        """Light::Sample_Li / Pdf_Li and the light-selection probability at points already on the GPU (gnxr_light_sample_device): for
+        the reference point `p` (m, 3) with normal `n` (m, 3) and light `light` (an index into the scene's lights: an int, or an int32
+        (m,) tensor for one light per query), Sample_Li with `u` (m, 2), Pdf_Li towards `wi_query` (m, 3), and the probability with
+        which the light distribution of `strategy` (LIGHTS_SPATIAL / LIGHTS_UNIFORM / LIGHTS_POWER or their names) picks the light at p.
+        Returns a float32 (m, 12) tensor (`out` when given): Li[0:3], pdf[3], wi[4:7], pdf_li[7], pdf_select[8], p_light[9:12] (the
+        sampled point: the far end of the shadow ray).  A light index out of range raises GnxrError after the other queries are
+        finished; its row is 0.  Queued on `stream` (default: torch's current stream); the call waits for the result's status."""
+        import torch
+        names = {"spatial": _abi.LIGHTS_SPATIAL, "uniform": _abi.LIGHTS_UNIFORM, "power": _abi.LIGHTS_POWER}
+        if isinstance(strategy, bool) or strategy not in names and strategy not in names.values():
+            raise ValueError(f"sample_light: strategy must be one of {sorted(names)} or LIGHTS_SPATIAL / LIGHTS_UNIFORM / LIGHTS_POWER, got {strategy!r}")
+        strategy = names.get(strategy, strategy)
+        args = [("p", p, torch.float32, 3), ("n", n, torch.float32, 3), ("u", u, torch.float32, 2), ("wi_query", wi_query, torch.float32, 3)]
+        m, out, st, tstream = self._query_args("sample_light", args, out, 12, stream)
+        if isinstance(light, torch.Tensor):
+            if not (light.dtype == torch.int32 and light.dim() == 1 and light.shape[0] == m and light.is_cuda and light.device == p.device):
+                raise ValueError(f"sample_light: light must be an int or an int32 ({m},) tensor on {p.device}, got {light.dtype} {tuple(light.shape)} on {light.device}")
+        elif not isinstance(light, (int, np.integer)) or isinstance(light, bool):
+            raise ValueError(f"sample_light: light must be an int or an int32 tensor, got {type(light).__name__}")
+        with torch.cuda.stream(tstream):   # the packed gnxr_light_sample_device queries: p, light, n, u, wi_query
+            q = torch.empty((m, 12), dtype=torch.float32, device=p.device)
+            q[:, 0:3] = p
+            q.view(torch.int32)[:, 3] = light if isinstance(light, torch.Tensor) else int(light)
+            q[:, 4:7] = n
+            q[:, 7:9] = u
+            q[:, 9:12] = wi_query
+        _check(lib().gnxr_light_sample_device(self._h, C.c_void_p(q.data_ptr() or None), m, int(strategy), C.c_void_p(out.data_ptr() or None), C.c_void_p(st or None)))
+        return out
+
+    def light_le(self, light, rays, out=None, stream=None):
+        """Light::Le(ray) of light `light` for escaped rays already on the GPU (gnxr_light_le_device): float32 (n, 8) rays in, a float32
+        (n, 3) tensor out (`out` when given); zero for lights that have no Le.  Queued on `stream`; nothing waits."""
+        import torch
+        n, out, st, _ = self._query_args("light_le", [("rays", rays, torch.float32, 8)], out, 3, stream)
+        _check(lib().gnxr_light_le_device(self._h, int(light), C.c_void_p(rays.data_ptr() or None), n, C.c_void_p(out.data_ptr() or None), C.c_void_p(st or None)))
+        return out
+
 
 RayHits = collections.namedtuple("RayHits", "hits prim t bary n")
 RayHits.__doc__ = """Scene.intersect's result: `hits`, the (n, 8) float32 gnxr_hit records, and views of it -- `prim` (int32: authoring-order

@@ -111,6 +111,15 @@ class LiSample(C.Structure):
     _fields_ = [("px", i32), ("py", i32), ("s", i32), ("medium", i32)]
 
 
+class BsdfResult(C.Structure):
+    _fields_ = [("f", f32 * 3), ("pdf", f32), ("sample_f", f32 * 3), ("sample_pdf", f32), ("sample_wi", f32 * 3), ("sampled_type", i32),
+                ("n_components", i32), ("valid", i32), ("dudx", f32), ("dvdy", f32)]
+
+
+class LightResult(C.Structure):
+    _fields_ = [("Li", f32 * 3), ("pdf", f32), ("wi", f32 * 3), ("pdf_li", f32), ("pdf_select", f32), ("p_light", f32 * 3)]
+
+
 P = C.POINTER
 VP = C.c_void_p
 
@@ -138,6 +147,9 @@ PROTOTYPES = {
     "gnxr_trace_closest_device": (C.c_int, [VP, VP, i64, VP, VP]),   # device addresses + hipStream_t
     "gnxr_trace_any_device": (C.c_int, [VP, VP, i64, VP, VP]),
     "gnxr_li_device": (C.c_int, [VP, P(RenderParams), VP, VP, i64, VP, VP, P(Stats)]),   # device addresses + hipStream_t
+    "gnxr_bsdf_device": (C.c_int, [VP, VP, VP, VP, VP, i64, i32, VP, VP]),   # device addresses + hipStream_t
+    "gnxr_light_sample_device": (C.c_int, [VP, VP, i64, i32, VP, VP]),
+    "gnxr_light_le_device": (C.c_int, [VP, i32, VP, i64, VP, VP]),
     "gnxr_sample_halton": (C.c_int, [i32, i32, P(i32), P(i32), P(i64), P(i32), i64, P(f32)]),
     "gnxr_camera_rays": (C.c_int, [P(Camera), i32, i32, P(i32), P(i32), P(i64), i64, P(f32), P(f32)]),
     "gnxr_framebuffer_update": (C.c_int, [P(f32), P(f32), i32, i32, i32, P(u8)]),
@@ -184,6 +196,9 @@ PROTOTYPES = {
 
 
 ABI_STRUCTS = [Material, Light, Camera, Medium, SceneDesc, RenderParams, Stats, Ray, Hit, Sphere, Texture, LiSample]
+# gnxr_abi_sizeof(12), gnxr_abi_sizeof(13): the records of the shading queries.  A table of their own: index i of ABI_STRUCTS is
+# gnxr_abi_sizeof(i) and tests/test_li_device.py pins gnxr_li_sample as its last entry.
+ABI_STRUCTS_SHADING = {12: BsdfResult, 13: LightResult}
 
 
 def bind(lib):

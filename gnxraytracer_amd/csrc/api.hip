@@ -24,6 +24,7 @@
 #include "hlbvh_build.hip.h"
 #include "refit_kernel.hip.h"
 #include "li_kernel.hip.h"
+#include "shade_query_kernel.hip.h"
 #include "kernel_instances.h"
 
 using namespace gnxr;
@@ -35,6 +36,12 @@ GX_WHITTED_INSTANCES(X)
 #define X(M, L, ST, T) extern template GX_VOL_SIGNATURE(M, L, ST, T)
 GX_VOL_INSTANCES(X)
 #undef X
+// compiled in inst_shade_query.hip
+extern template GX_BSDF_QUERY_SIGNATURE(LM_ALL)
+extern template GX_LIGHT_SAMPLE_QUERY_SIGNATURE(LT_ALL)
+extern template GX_LIGHT_LE_QUERY_SIGNATURE(LT_ALL)
+extern template GX_TRACE_CLOSEST_CODE_SIGNATURE(32)
+extern template GX_TRACE_CLOSEST_CODE_SIGNATURE(64)
 
 namespace { int hip_status(hipError_t e); }
 #define HIP_TRY(expr)                                                                                   \
@@ -234,6 +241,22 @@ struct gnxr_scene {
         for (hipEvent_t e : ev_join) if (e) (void)hipEventDestroy(e);
     }
 
+    // the lights and the environment map: what Sample_Li / Pdf_Li / Le read, without the selection table (grid, grid_table stay zero).
+    // Nothing here changes after the scene is created, except the world radius that gnxr_scene_update_vertices refits (cs.env, distant lights).
+    DLightTables light_tables_static() const {
+        DLightTables lt = {};
+        lt.lights = lights.p;
+        lt.n_lights = (int)cs.desc_lights.size();
+        lt.infinite = infinite.p;
+        lt.n_infinite = (int)cs.infinite_lights.size();
+        lt.has_env = cs.has_env ? 1 : 0;
+        lt.env = cs.env;
+        lt.env_texels = reinterpret_cast<const float4 *>(env_texels4.p);
+        lt.env_cond_func = env_cond_func.p; lt.env_cond_cdf = env_cond_cdf.p; lt.env_cond_int = env_cond_int.p;
+        lt.env_marg_func = env_marg_func.p; lt.env_marg_cdf = env_marg_cdf.p;
+        lt.env_marg_guide = env_marg_guide.p; lt.env_cond_guide = env_cond_guide.p;
+        return lt;
+    }
     DScene device_scene(int W, int H) {
         DScene d;
         d.nodes = reinterpret_cast<const float4 *>(nodes.p);
@@ -248,18 +271,9 @@ struct gnxr_scene {
         d.n_spheres = cs.n_spheres;
         d.materials = materials.p + 1;   // [0] carries the texture tables
         d.escape_class = 0;              // render_one: 3 for the PathIntegrator in a scene without image-textured materials
-        d.lt.lights = lights.p;
-        d.lt.n_lights = (int)cs.desc_lights.size();
-        d.lt.infinite = infinite.p;
-        d.lt.n_infinite = (int)cs.infinite_lights.size();
+        d.lt = light_tables_static();
         d.lt.grid = grid;
         d.lt.grid_table = grid_table.p;
-        d.lt.has_env = cs.has_env ? 1 : 0;
-        d.lt.env = cs.env;
-        d.lt.env_texels = reinterpret_cast<const float4 *>(env_texels4.p);
-        d.lt.env_cond_func = env_cond_func.p; d.lt.env_cond_cdf = env_cond_cdf.p; d.lt.env_cond_int = env_cond_int.p;
-        d.lt.env_marg_func = env_marg_func.p; d.lt.env_marg_cdf = env_marg_cdf.p;
-        d.lt.env_marg_guide = env_marg_guide.p; d.lt.env_cond_guide = env_cond_guide.p;
         d.st.perms = perms.p; d.st.primes = primes.p; d.st.prime_sums = prime_sums.p; d.st.prime_magic = prime_magic.p;
         d.st.h = make_halton(W, H);
         return d;
@@ -1758,6 +1772,60 @@ static gnxr_scene *query_replica(gnxr_scene *s, const void *ptr, size_t bytes, c
     return r;
 }
 
+// the tables the walk, the hit record and a BSDF read (device_scene() would also read the light and sampler state, which a render may be rebuilding)
+static DScene query_device_scene(gnxr_scene *r) {
+    const CompiledScene &cs = r->cs;
+    DScene sc = {};
+    sc.nodes = reinterpret_cast<const float4 *>(r->nodes.p);
+    sc.nodes4 = reinterpret_cast<const float4 *>(r->nodes4.p);
+    sc.root4 = cs.root4;
+    sc.tris = r->tris.p;
+    sc.leaf_box = reinterpret_cast<const float4 *>(r->leaf_boxes.p);
+    static const bool no_verts = getenv("GNXR_LEAF_BOX_TABLE") != nullptr;   // as device_scene()
+    sc.leaf1_from_verts = (cs.leaf1_from_verts && !no_verts) ? 1 : 0;
+    sc.spheres = r->spheres.p;
+    sc.n_spheres = cs.n_spheres;
+    sc.materials = r->materials.p + 1;
+    return sc;
+}
+
+// k_trace4 in a query mode over n rays on `st`, with the call's own scratch.  any == false: the leaf code of every ray's closest hit into
+// hits[i].prim (kT4QueryClosest); any == true: occluded[i].  Scenes on the 4-wide tree only (r->wide_ok).
+static int query_trace4(gnxr_scene *r, const DScene &sc, const gnxr_ray *d_rays, int64_t n, gnxr_hit *hits, unsigned char *occluded, bool any, hipStream_t st) {
+    const bool spheres = r->cs.n_spheres > 0;
+    // scratch of this call: [cursor | pad to 256 B | spill columns of the grid the largest launch uses]
+    const TraceLaunch tl = trace_launch(r, true, spheres, std::min<long long>(n, kQueryLaunchMax));
+    const size_t spill_ints = tl.spill_needed ? (size_t)(tl.entries - tl.lds_entries) * (size_t)tl.blocks * kBlock : 0;
+    char *scratch = nullptr;
+    HIP_TRY(hipMallocAsync((void **)&scratch, 256 + spill_ints * sizeof(int), st));
+    unsigned int *cursor = reinterpret_cast<unsigned int *>(scratch);
+    int *spill = reinterpret_cast<int *>(scratch + 256);
+    hipError_t e = hipSuccess;
+    for (long long base = 0; base < n && e == hipSuccess; base += kQueryLaunchMax) {
+        const long long cnt = std::min<long long>(n - base, kQueryLaunchMax);
+        const TraceLaunch t = trace_launch(r, true, spheres, cnt);
+        QueryArrays qa;
+        qa.rays = reinterpret_cast<const float4 *>(d_rays + base);
+        qa.hits = any ? nullptr : hits + base;
+        qa.occluded = any ? occluded + base : nullptr;
+        TraceWork w = {};
+        w.n_closest = (int)cnt;
+        if ((e = hipMemsetAsync(cursor, 0, sizeof(unsigned int), st)) != hipSuccess) break;
+#define GX_QUERY4(S, P, Q) hipLaunchKernelGGL((k_trace4<false, S, P, Q>), dim3(t.blocks), dim3(kBlock), t.lds, st, sc, qa, w, cursor, (Counters *)nullptr, t.lds_entries, spill, kTraceChunk, t.n_top)
+#define GX_QUERY4_SP(Q) do { if (spheres) { if (t.spill_needed) GX_QUERY4(true, true, Q); else GX_QUERY4(true, false, Q); } \
+                             else { if (t.spill_needed) GX_QUERY4(false, true, Q); else GX_QUERY4(false, false, Q); } } while (0)
+        if (any) GX_QUERY4_SP(kT4QueryAny);
+        else GX_QUERY4_SP(kT4QueryClosest);
+#undef GX_QUERY4_SP
+#undef GX_QUERY4
+        e = hipGetLastError();
+    }
+    const hipError_t ef = hipFreeAsync(scratch, st);   // stream-ordered: after the launches above
+    HIP_TRY(e);
+    HIP_TRY(ef);
+    return GNXR_OK;
+}
+
 // any == false: Scene::Intersect, out = gnxr_hit[n]; any == true: Scene::IntersectP, out = uint8_t[n]
 static int trace_device(gnxr_scene *s, const gnxr_ray *d_rays, int64_t n, void *out, void *hip_stream, bool any) {
     if (!s || n < 0 || (n > 0 && (!d_rays || !out))) { set_error("bad argument"); return GNXR_ERR_INVALID; }
@@ -1774,20 +1842,7 @@ static int trace_device(gnxr_scene *s, const gnxr_ray *d_rays, int64_t n, void *
     if (rc) return rc;
     struct Rebind { gnxr_scene *s; bool on; ~Rebind() { if (on) (void)s->bind(); } } rebind{s, r != s};   // leave the primary device current
     hipStream_t st = (hipStream_t)hip_stream;
-    const CompiledScene &cs = r->cs;
-    // the tables the walk and the hit record read (device_scene() would also read the light and sampler state, which a render may be rebuilding)
-    DScene sc = {};
-    sc.nodes = reinterpret_cast<const float4 *>(r->nodes.p);
-    sc.nodes4 = reinterpret_cast<const float4 *>(r->nodes4.p);
-    sc.root4 = cs.root4;
-    sc.tris = r->tris.p;
-    sc.leaf_box = reinterpret_cast<const float4 *>(r->leaf_boxes.p);
-    static const bool no_verts = getenv("GNXR_LEAF_BOX_TABLE") != nullptr;   // as device_scene()
-    sc.leaf1_from_verts = (cs.leaf1_from_verts && !no_verts) ? 1 : 0;
-    sc.spheres = r->spheres.p;
-    sc.n_spheres = cs.n_spheres;
-    sc.materials = r->materials.p + 1;
-    const bool spheres = cs.n_spheres > 0;
+    const DScene sc = query_device_scene(r);
     if (!r->wide_ok) {   // trees the 4-wide encoding cannot hold (or GNXR_BINARY_BVH at creation): the reference's binary walk, same results
         const int big = r->stack_size > 32;
         if (!any) {
@@ -1800,40 +1855,11 @@ static int trace_device(gnxr_scene *s, const gnxr_ray *d_rays, int64_t n, void *
         HIP_TRY(hipGetLastError());
         return GNXR_OK;
     }
-    // scratch of this call: [cursor | pad to 256 B | spill columns of the grid the largest launch uses]
-    const TraceLaunch tl = trace_launch(r, true, spheres, std::min<long long>(n, kQueryLaunchMax));
-    const size_t spill_ints = tl.spill_needed ? (size_t)(tl.entries - tl.lds_entries) * (size_t)tl.blocks * kBlock : 0;
-    char *scratch = nullptr;
-    HIP_TRY(hipMallocAsync((void **)&scratch, 256 + spill_ints * sizeof(int), st));
-    unsigned int *cursor = reinterpret_cast<unsigned int *>(scratch);
-    int *spill = reinterpret_cast<int *>(scratch + 256);
-    hipError_t e = hipSuccess;
-    for (long long base = 0; base < n && e == hipSuccess; base += kQueryLaunchMax) {
-        const long long cnt = std::min<long long>(n - base, kQueryLaunchMax);
-        const TraceLaunch t = trace_launch(r, true, spheres, cnt);
-        QueryArrays qa;
-        qa.rays = reinterpret_cast<const float4 *>(d_rays + base);
-        qa.hits = any ? nullptr : (gnxr_hit *)out + base;
-        qa.occluded = any ? (unsigned char *)out + base : nullptr;
-        TraceWork w = {};
-        w.n_closest = (int)cnt;
-        if ((e = hipMemsetAsync(cursor, 0, sizeof(unsigned int), st)) != hipSuccess) break;
-#define GX_QUERY4(S, P, Q) hipLaunchKernelGGL((k_trace4<false, S, P, Q>), dim3(t.blocks), dim3(kBlock), t.lds, st, sc, qa, w, cursor, (Counters *)nullptr, t.lds_entries, spill, kTraceChunk, t.n_top)
-#define GX_QUERY4_SP(Q) do { if (spheres) { if (t.spill_needed) GX_QUERY4(true, true, Q); else GX_QUERY4(true, false, Q); } \
-                             else { if (t.spill_needed) GX_QUERY4(false, true, Q); else GX_QUERY4(false, false, Q); } } while (0)
-        if (any) GX_QUERY4_SP(kT4QueryAny);
-        else GX_QUERY4_SP(kT4QueryClosest);
-#undef GX_QUERY4_SP
-#undef GX_QUERY4
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && !any) {
+    if ((rc = query_trace4(r, sc, d_rays, n, any ? nullptr : (gnxr_hit *)out, any ? (unsigned char *)out : nullptr, any, st)) != GNXR_OK) return rc;
+    if (!any) {
         hipLaunchKernelGGL(k_query_finish, dim3(grid_for(n)), dim3(kBlock), 0, st, sc, reinterpret_cast<const float4 *>(d_rays), (long long)n, (gnxr_hit *)out);
-        e = hipGetLastError();
+        HIP_TRY(hipGetLastError());
     }
-    const hipError_t ef = hipFreeAsync(scratch, st);   // stream-ordered: after the launches above
-    HIP_TRY(e);
-    HIP_TRY(ef);
     return GNXR_OK;
 }
 int gnxr_trace_closest_device(gnxr_scene *s, const gnxr_ray *d_rays, int64_t n, gnxr_hit *d_hits, void *hip_stream) {
@@ -1868,6 +1894,140 @@ int gnxr_li_device(gnxr_scene *s, const gnxr_render_params *p, const gnxr_ray *d
     const int rc = render_one(r, &pp, nullptr, hip_stream, stats, &src);
     if (r != s) (void)s->bind();   // leave the primary device current
     return rc;
+}
+
+// ---- shading queries on device memory: gnxr_bsdf_device / gnxr_light_sample_device / gnxr_light_le_device (shade_query_kernel.hip.h) ----
+
+// rays of one traversal + k_bsdf_query round: bounds the call's scratch (one gnxr_hit per ray for the leaf codes) at 128 MB whatever n is
+static const long long kBsdfQueryChunk = 1ll << 22;
+
+// The copy of `s` on the device that holds every listed array (nullptr and the error set otherwise)
+struct QueryArg { const void *p; size_t bytes; const char *what; };
+static gnxr_scene *query_replica_all(gnxr_scene *s, const QueryArg *args, int n_args) {
+    gnxr_scene *r = nullptr;
+    for (int i = 0; i < n_args; ++i) {
+        if (!args[i].p) continue;   // an optional array that was not given
+        gnxr_scene *ri = query_replica(s, args[i].p, args[i].bytes, args[i].what);
+        if (!ri) return nullptr;
+        if (r && ri != r) { set_error("%s and %s live on different devices", args[0].what, args[i].what); return nullptr; }
+        r = ri;
+    }
+    return r;
+}
+
+int gnxr_bsdf_device(gnxr_scene *s, const gnxr_ray *d_rays, const float *d_wi, const float *d_u, const float *d_differentials, int64_t n, int32_t flags,
+                     gnxr_bsdf_result *d_out, void *hip_stream) {
+    if (!s || n < 0 || (n > 0 && (!d_rays || !d_wi || !d_u || !d_out))) { set_error("bad argument"); return GNXR_ERR_INVALID; }
+    if (flags < 0 || flags > 31) { set_error("flags = %d is not a BxDFType mask (0 .. BSDF_ALL = 31)", flags); return GNXR_ERR_INVALID; }
+    if (n == 0) return GNXR_OK;
+    if ((((uintptr_t)d_rays | (uintptr_t)d_out) & 15u) != 0) { set_error("d_rays and d_out must be 16-byte aligned"); return GNXR_ERR_INVALID; }
+    if ((((uintptr_t)d_wi | (uintptr_t)d_u | (uintptr_t)d_differentials) & 3u) != 0) { set_error("d_wi, d_u and d_differentials must be 4-byte aligned"); return GNXR_ERR_INVALID; }
+    const QueryArg args[] = {{d_rays, (size_t)n * sizeof(gnxr_ray), "d_rays"}, {d_wi, (size_t)n * 12, "d_wi"}, {d_u, (size_t)n * 8, "d_u"},
+                             {d_differentials, (size_t)n * 48, "d_differentials"}, {d_out, (size_t)n * sizeof(gnxr_bsdf_result), "d_out"}};
+    if (int drc = ensure_device()) return drc;
+    gnxr_scene *r = query_replica_all(s, args, 5);
+    if (!r) return GNXR_ERR_INVALID;
+    int rc = r->bind();
+    if (rc) return rc;
+    struct Rebind { gnxr_scene *s; bool on; ~Rebind() { if (on) (void)s->bind(); } } rebind{s, r != s};   // leave the primary device current
+    hipStream_t st = (hipStream_t)hip_stream;
+    const DScene sc = query_device_scene(r);
+    gnxr_hit *codes = nullptr;
+    HIP_TRY(hipMallocAsync((void **)&codes, (size_t)std::min<long long>(n, kBsdfQueryChunk) * sizeof(gnxr_hit), st));
+    hipError_t e = hipSuccess;
+    for (long long base = 0; base < n && rc == GNXR_OK && e == hipSuccess; base += kBsdfQueryChunk) {
+        const long long cnt = std::min<long long>(n - base, kBsdfQueryChunk);
+        if (r->wide_ok) rc = query_trace4(r, sc, d_rays + base, cnt, codes, nullptr, false, st);
+        else {   // trees the 4-wide encoding cannot hold: the binary walk
+            if (r->stack_size > 32) hipLaunchKernelGGL((k_trace_closest_code<64>), dim3(grid_for(cnt, 2)), dim3(kBlock), 0, st, sc, d_rays + base, cnt, codes);
+            else hipLaunchKernelGGL((k_trace_closest_code<32>), dim3(grid_for(cnt, 5)), dim3(kBlock), 0, st, sc, d_rays + base, cnt, codes);
+            e = hipGetLastError();
+        }
+        if (rc != GNXR_OK || e != hipSuccess) break;
+        BsdfQueryArrays q;
+        q.rays = reinterpret_cast<const float4 *>(d_rays + base);
+        q.codes = codes;
+        q.wi = d_wi + 3 * base;
+        q.u = d_u + 2 * base;
+        q.diffs = d_differentials ? d_differentials + 12 * base : nullptr;
+        q.out = reinterpret_cast<float4 *>(d_out + base);
+        hipLaunchKernelGGL((k_bsdf_query<LM_ALL>), dim3(grid_for(cnt)), dim3(kBlock), 0, st, sc, q, cnt, (int)flags);
+        e = hipGetLastError();
+    }
+    const hipError_t ef = hipFreeAsync(codes, st);   // stream-ordered: after the launches above
+    if (rc != GNXR_OK) return rc;
+    HIP_TRY(e);
+    HIP_TRY(ef);
+    return GNXR_OK;
+}
+
+// the light tables of `r` with the selection table of `strategy`: the render's cache (ensure_grid), under the render lock
+static int query_light_tables(gnxr_scene *r, int32_t strategy, DLightTables *lt) {
+    if (int rc = r->ensure_grid(strategy)) return rc;
+    *lt = r->device_scene(1, 1).lt;
+    return GNXR_OK;
+}
+
+int gnxr_light_sample_device(gnxr_scene *s, const float *d_queries, int64_t n, int32_t strategy, gnxr_light_result *d_out, void *hip_stream) {
+    if (!s || n < 0 || (n > 0 && (!d_queries || !d_out))) { set_error("bad argument"); return GNXR_ERR_INVALID; }
+    if (strategy != GNXR_LIGHTS_SPATIAL && strategy != GNXR_LIGHTS_UNIFORM && strategy != GNXR_LIGHTS_POWER) {
+        set_error("strategy = %d is not a gnxr_light_strategy", strategy);
+        return GNXR_ERR_INVALID;
+    }
+    if (n == 0) return GNXR_OK;
+    if ((((uintptr_t)d_queries | (uintptr_t)d_out) & 15u) != 0) { set_error("d_queries and d_out must be 16-byte aligned"); return GNXR_ERR_INVALID; }
+    const QueryArg args[] = {{d_queries, (size_t)n * 48, "d_queries"}, {d_out, (size_t)n * sizeof(gnxr_light_result), "d_out"}};
+    if (int drc = ensure_device()) return drc;
+    gnxr_scene *r = query_replica_all(s, args, 2);
+    if (!r) return GNXR_ERR_INVALID;
+    // the selection table belongs to the renders of the copy it lives on: the primary's lock, then that copy's (render_sharded's order;
+    // gnxr_li_device on a replica holds the replica's alone)
+    std::lock_guard<std::recursive_mutex> lock(s->render_mutex);
+    std::lock_guard<std::recursive_mutex> lock_r(r->render_mutex);
+    int rc = r->bind();
+    if (rc) return rc;
+    struct Rebind { gnxr_scene *s; bool on; ~Rebind() { if (on) (void)s->bind(); } } rebind{s, r != s};
+    hipStream_t st = (hipStream_t)hip_stream;
+    DLightTables lt;
+    if ((rc = query_light_tables(r, strategy, &lt)) != GNXR_OK) return rc;
+    unsigned long long *d_bad = nullptr, bad = 0;
+    HIP_TRY(hipMallocAsync((void **)&d_bad, sizeof(unsigned long long), st));
+    hipError_t e = hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), st);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL((k_light_sample_query<LT_ALL>), dim3(grid_for(n)), dim3(kBlock), 0, st, lt, reinterpret_cast<const float4 *>(d_queries), (long long)n,
+                           reinterpret_cast<float4 *>(d_out), d_bad);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, st);
+    const hipError_t ef = hipFreeAsync(d_bad, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);   // the status has to come back
+    HIP_TRY(e);
+    HIP_TRY(ef);
+    if (bad) {
+        set_error("gnxr_light_sample_device: query %llu names a light outside [0, %d); its record is 0", (unsigned long long)~bad, lt.n_lights);
+        return GNXR_ERR_INVALID;
+    }
+    return GNXR_OK;
+}
+
+int gnxr_light_le_device(gnxr_scene *s, int32_t light, const gnxr_ray *d_rays, int64_t n, float *d_le, void *hip_stream) {
+    if (!s || n < 0 || (n > 0 && (!d_rays || !d_le))) { set_error("bad argument"); return GNXR_ERR_INVALID; }
+    if (light < 0 || light >= (int32_t)s->cs.desc_lights.size()) { set_error("light = %d is outside [0, %d)", light, (int)s->cs.desc_lights.size()); return GNXR_ERR_INVALID; }
+    if (n == 0) return GNXR_OK;
+    if (((uintptr_t)d_rays & 15u) != 0 || ((uintptr_t)d_le & 3u) != 0) { set_error("d_rays must be 16-byte aligned, d_le 4-byte aligned"); return GNXR_ERR_INVALID; }
+    const QueryArg args[] = {{d_rays, (size_t)n * sizeof(gnxr_ray), "d_rays"}, {d_le, (size_t)n * 12, "d_le"}};
+    if (int drc = ensure_device()) return drc;
+    gnxr_scene *r = query_replica_all(s, args, 2);
+    if (!r) return GNXR_ERR_INVALID;
+    int rc = r->bind();
+    if (rc) return rc;
+    struct Rebind { gnxr_scene *s; bool on; ~Rebind() { if (on) (void)s->bind(); } } rebind{s, r != s};
+    // Le reads the lights and the environment map, not the selection table: nothing here that a render rebuilds, so no lock
+    const DLightTables lt = r->light_tables_static();
+    hipLaunchKernelGGL((k_light_le_query<LT_ALL>), dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)hip_stream, lt, (int)light, reinterpret_cast<const float4 *>(d_rays),
+                       (long long)n, d_le);
+    HIP_TRY(hipGetLastError());
+    return GNXR_OK;
 }
 
 // sampler tables without a scene (probes)

@@ -272,8 +272,10 @@ GX_DEV bool sphere_test(const DSphere &sp, V3 ro, V3 rd, float tMax, float *tHit
     *tHit = (float)tShapeHit;
     return true;
 }
-// hit point, error bound, normal and BSDF frame of a sphere hit at tHit (+ Material::Bump with the constant-0 map)
-GX_DEV SurfacePoint sphere_surface_point(const DSphere &sp, V3 ro, V3 rd, float tHit, bool has_bump) {
+// hit point, error bound, normal and BSDF frame of a sphere hit at tHit (+ Material::Bump with the constant-0 map); *dpduOut / *dpdvOut
+// receive the interaction's unshaded dpdu / dpdv (what ComputeDifferentials reads)
+template <bool UV>
+GX_DEV SurfacePoint sphere_surface_point_uv(const DSphere &sp, V3 ro, V3 rd, float tHit, bool has_bump, V3 *dpduOut, V3 *dpdvOut) {
     SurfacePoint s;
     s.valid = true;
     const float radius = sp.r;
@@ -307,7 +309,11 @@ GX_DEV SurfacePoint sphere_surface_point(const DSphere &sp, V3 ro, V3 rd, float 
     s.ns = sn;
     s.ss = normalize(sdpdu);
     s.ts = cross(s.ns, s.ss);
+    if (UV) { *dpduOut = dpdu; *dpdvOut = dpdv; }
     return s;
+}
+GX_DEV SurfacePoint sphere_surface_point(const DSphere &sp, V3 ro, V3 rd, float tHit, bool has_bump) {
+    return sphere_surface_point_uv<false>(sp, ro, rd, tHit, has_bump, nullptr, nullptr);
 }
 
 // Interaction::SpawnRay / SpawnRayTo, Interaction.h:33-53

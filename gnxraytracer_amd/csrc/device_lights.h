@@ -249,11 +249,10 @@ GX_DEV float light_pdf(const DLightTables &t, int li, V3 refP, V3 refPError, V3 
     return 0.f;
 }
 
-// lightDistribution->Lookup(p) + Distribution1D::SampleDiscrete(u, &pdf)
-GX_DEV int light_select(const DLightTables &t, V3 p, float u, float *pdf) {
+// lightDistribution->Lookup(p): the Distribution1D record of the voxel that holds p -- cdf[1..n], func[0..n-1], funcInt
+GX_DEV const float *light_grid_record(const DLightTables &t, V3 p) {
     const DLightGrid &g = t.grid;
     const float *rec = t.grid_table;
-    int nl = g.n_lights;
     if (g.spatial) {
         // Bounds3::Offset + voxel clamp, LightDistribution.cpp:113-116
         V3 o(p.x - g.lo[0], p.y - g.lo[1], p.z - g.lo[2]);
@@ -265,6 +264,20 @@ GX_DEV int light_select(const DLightTables &t, V3 p, float u, float *pdf) {
         int pz = min(max((int)(o.z * g.nvox[2]), 0), g.nvox[2] - 1);
         rec += (((size_t)px * g.nvox[1] + py) * g.nvox[2] + pz) * g.stride;
     }
+    return rec;
+}
+// lightDistribution->Lookup(p)->DiscretePDF(li): `func[li] / (funcInt * Count())`, core/Sampling.h
+GX_DEV float light_select_pdf(const DLightTables &t, V3 p, int li) {
+    const float *rec = light_grid_record(t, p);
+    const int nl = t.grid.n_lights;
+    return rec[nl + li] / (rec[2 * nl] * nl);
+}
+
+// lightDistribution->Lookup(p) + Distribution1D::SampleDiscrete(u, &pdf)
+GX_DEV int light_select(const DLightTables &t, V3 p, float u, float *pdf) {
+    const DLightGrid &g = t.grid;
+    const float *rec = light_grid_record(t, p);
+    int nl = g.n_lights;
     if (nl <= 3 && (g.stride & 3) == 0) {
         // padded record (build_light_grid): the whole of it in one or two aligned loads, then the same search on registers
         const float4 a = *reinterpret_cast<const float4 *>(rec);

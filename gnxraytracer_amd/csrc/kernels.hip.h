@@ -359,6 +359,53 @@ GX_DEV Spec nee_record_Ld(const PathArrays &pa, size_t rec, float *xw) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// The two steps every consumer of a traversal result takes before it can evaluate a BSDF; shared by k_shade and the shading queries
+// (shade_query_kernel.hip.h), so that a query builds exactly the hit the render shades.
+//
+// The surface point of the hit the traversal left as a leaf code (`leaf`: a leaf-order triangle, -2 - i for sphere i, or -1: nothing, false): the triangle's vertices, material and light, (t, b0, b1, b2) recomputed as the accepting test computed them, and the
+// interaction with its shading frame -- through the scene's per-corner tables when TEX.  False when the hit does not stand (a degenerate
+// triangle, a sphere no longer within tMax).  UV: *sdpdu / *sdpdv receive a sphere's unshaded dpdu / dpdv (a triangle's come from tri_uv_frame).
+template <bool SPH, bool TEX, bool UV = false>
+GX_DEV bool shade_hit_rebuild(const DScene &sc, const DMaterial *mats, int leaf, V3 ro, V3 rd, float tMax, V3 *p0, V3 *p1, V3 *p2, TriHit *h, int *triMat, int *triLight,
+                              SurfacePoint *sp, V3 *sdpdu, V3 *sdpdv) {
+    bool found = leaf != -1;
+    if (SPH && leaf < -1) {   // sphere
+        const DSphere &sph = sc.spheres[-2 - leaf];
+        *triMat = sph.material;
+        float tH;
+        found = sphere_test(sph, ro, rd, tMax, &tH);
+        if (found) *sp = sphere_surface_point_uv<UV>(sph, ro, rd, tH, *triMat >= 0 ? mats[*triMat].has_bump != 0 : false, sdpdu, sdpdv);
+    } else if (found) {
+        const float4 *q = reinterpret_cast<const float4 *>(sc.tris + leaf);
+        float4 a = q[0], b = q[1], c = q[2];
+        *p0 = V3(a.x, a.y, a.z); *p1 = V3(b.x, b.y, b.z); *p2 = V3(c.x, c.y, c.z);
+        *triMat = __float_as_int(b.w); *triLight = __float_as_int(c.w);
+        tri_hit_recompute(*p0, *p1, *p2, ro, rd, h);   // the traversal accepted this triangle for this ray: same arithmetic, same (t, b0, b1, b2)
+        *sp = surface_point(*p0, *p1, *p2, *h, *triMat >= 0 ? mats[*triMat].has_bump != 0 : false);
+        if (TEX) {   // per-corner uvs / shading normals (defaults when the triangle has none: same arithmetic as above)
+            V3 dndu, dndv;
+            *sp = surface_point_tables(tex_tables(sc.materials), leaf, *p0, *p1, *p2, *h, *triMat >= 0 ? mats[*triMat].has_bump != 0 : false, &dndu, &dndv);
+        }
+        found = sp->valid;
+    }
+    return found;
+}
+// The material a BSDF is built from at a triangle hit: `mat` itself, or -- TEX, and Kd / Ks is an ImageTexture -- its copy in *tm with the
+// textures looked up at the hit's uv, filtered with the uv differentials the offset rays `rdf` give (ComputeDifferentials; none: unfiltered).
+template <bool TEX>
+GX_DEV const DMaterial *shade_material(const DScene &sc, const DMaterial *mat, int leaf, V3 p0, V3 p1, V3 p2, const TriHit &h, const SurfacePoint &sp, const RayDiff &rdf,
+                                       DMaterial *tm) {
+    if (TEX && leaf >= 0 && (mat->kd_tex | mat->ks_tex)) {
+        float tu, tv;
+        V3 dpdu, dpdv;
+        tri_uv_frame(p0, p1, p2, h, tri_uvs(tex_tables(sc.materials), leaf), &tu, &tv, &dpdu, &dpdv);
+        textured_material(tex_tables(sc.materials), *mat, tu, tv, compute_differentials(rdf, sp.p, sp.n, dpdu, dpdv), tm);
+        mat = tm;
+    }
+    return mat;
+}
+
+// ------------------------------------------------------------------------------------------------
 // One specialisation per (lobe set LM, light-type set LT): device_bsdf.h LM_*, device_lights.h LT_*.  `n_dev`
 // points at the fill count of `queue` written by k_compact_scan (device-side, no host round trip).
 #ifndef GX_SHADE_MINWAVES
@@ -461,27 +508,7 @@ __global__ void __launch_bounds__(kBlock, (TEX ? GX_SHADE_W_TEX : shade_min_wave
             TriHit h;
             SurfacePoint sp;
             sp.valid = false;
-            if (SPH && leaf < -1) {   // sphere
-                const DSphere &sph = sc.spheres[-2 - leaf];
-                triMat = sph.material;
-                float tH;
-                found = sphere_test(sph, ro, rd, o4.w, &tH);
-                if (found) sp = sphere_surface_point(sph, ro, rd, tH, triMat >= 0 ? mats[triMat].has_bump != 0 : false);
-            } else if (found) {
-                const float4 *q = reinterpret_cast<const float4 *>(sc.tris + leaf);
-                float4 a = q[0], b = q[1], c = q[2];
-                p0 = V3(a.x, a.y, a.z); p1 = V3(b.x, b.y, b.z); p2 = V3(c.x, c.y, c.z);
-                triMat = __float_as_int(b.w); triLight = __float_as_int(c.w);
-                tri_hit_recompute(p0, p1, p2, ro, rd, &h);   // the traversal accepted this triangle for this ray: same arithmetic, same (t, b0, b1, b2)
-                if (found) {
-                    sp = surface_point(p0, p1, p2, h, triMat >= 0 ? mats[triMat].has_bump != 0 : false);
-                    if (TEX) {   // per-corner uvs / shading normals (defaults when the triangle has none: same arithmetic as above)
-                        V3 dndu, dndv;
-                        sp = surface_point_tables(tex_tables(sc.materials), leaf, p0, p1, p2, h, triMat >= 0 ? mats[triMat].has_bump != 0 : false, &dndu, &dndv);
-                    }
-                    found = sp.valid;
-                }
-            }
+            found = shade_hit_rebuild<SPH, TEX>(sc, mats, leaf, ro, rd, o4.w, &p0, &p1, &p2, &h, &triMat, &triLight, &sp, nullptr, nullptr);
             GX_STICK(0);   // state + triangle loads, tri_test, surface_point
             // PathIntegrator.cpp:101-111: emitted light at the vertex / from the environment
             // (L is read and written only by the vertices that add to it here -- the camera vertex or a vertex after a specular bounce, on a light
@@ -501,17 +528,10 @@ __global__ void __launch_bounds__(kBlock, (TEX ? GX_SHADE_W_TEX : shade_min_wave
                     pa.ray_o[(size_t)path * kRS] = make_float4(o2.x, o2.y, o2.z, GX_INF);
                     survive = true;
                 } else {
-                    const DMaterial *mat = mats + triMat;
                     DMaterial tm;
-                    if (TEX && leaf >= 0 && (mat->kd_tex | mat->ks_tex)) {
-                        float tu, tv;
-                        V3 dpdu, dpdv;
-                        tri_uv_frame(p0, p1, p2, h, tri_uvs(tex_tables(sc.materials), leaf), &tu, &tv, &dpdu, &dpdv);
-                        RayDiff none;
-                        none.has = false;
-                        textured_material(tex_tables(sc.materials), *mat, tu, tv, compute_differentials(none, sp.p, sp.n, dpdu, dpdv), &tm);
-                        mat = &tm;
-                    }
+                    RayDiff none;
+                    none.has = false;
+                    const DMaterial *mat = shade_material<TEX>(sc, mats + triMat, leaf, p0, p1, p2, h, sp, none, &tm);
                     Bsdf<LM> bsdf;
                     bsdf.mat = mat; bsdf.ns = sp.ns; bsdf.ng = sp.n; bsdf.ss = sp.ss; bsdf.ts = sp.ts;
                     SampleStream ss(sc.st, index, dim, lsam);

@@ -837,6 +837,8 @@ int gnxr_abi_sizeof(int which) {
     case 9: return (int)sizeof(gnxr_sphere);
     case 10: return (int)sizeof(gnxr_texture);
     case 11: return (int)sizeof(gnxr_li_sample);
+    case 12: return (int)sizeof(gnxr_bsdf_result);
+    case 13: return (int)sizeof(gnxr_light_result);
     default: return -1;
     }
 }

@@ -306,6 +306,27 @@ typedef struct gnxr_hit {
 /* The sample a caller ray of gnxr_li_device stands for: pixel (px, py) and sample s of the render's HaltonSampler, and the medium
  * the ray starts in (-1: none).  16 bytes.                                                                                        */
 typedef struct gnxr_li_sample { int32_t px, py, s, medium; } gnxr_li_sample;
+/* One query of gnxr_bsdf_device: BSDF::f / Pdf towards `wi`, BSDF::Sample_f with `u`, at the hit of a ray.  64 bytes.          */
+typedef struct gnxr_bsdf_result {
+    float f[3];                 /* BSDF::f(wo, wi, flags)                                    */
+    float pdf;                  /* BSDF::Pdf(wo, wi, flags)                                  */
+    float sample_f[3];          /* BSDF::Sample_f(wo, &sample_wi, u, &sample_pdf, flags, &sampled_type); 0 when sample_pdf == 0 */
+    float sample_pdf;
+    float sample_wi[3];         /* world space; 0 when sample_pdf == 0                       */
+    int32_t sampled_type;       /* BxDFType of the sampled lobe                              */
+    int32_t n_components;       /* BSDF::NumComponents(flags)                                */
+    int32_t valid;              /* 1: the ray hit a surface that has a BSDF; 0 (and the whole record 0): miss or null material */
+    float dudx, dvdy;           /* SurfaceInteraction::dudx / dvdy (0 without ray differentials) */
+} gnxr_bsdf_result;
+/* One query of gnxr_light_sample_device.  48 bytes.                                                                              */
+typedef struct gnxr_light_result {
+    float Li[3];                /* Light::Sample_Li(ref, u, &wi, &pdf, &vis)                 */
+    float pdf;
+    float wi[3];
+    float pdf_li;               /* Light::Pdf_Li(ref, wi_query)                              */
+    float pdf_select;           /* LightDistribution::Lookup(p)->DiscretePDF(light)          */
+    float p_light[3];           /* VisibilityTester::P1().p: the sampled point on the light  */
+} gnxr_light_result;
 
 typedef struct gnxr_scene gnxr_scene;
 
@@ -420,6 +441,39 @@ int gnxr_trace_any_device(gnxr_scene *scene, const gnxr_ray *d_rays, int64_t n, 
  * GNXR_ERR_INVALID naming the first such record.  n == 0 is a no-op.                                                         */
 int gnxr_li_device(gnxr_scene *scene, const gnxr_render_params *params, const gnxr_ray *d_rays, const gnxr_li_sample *d_samples, int64_t n,
                    float *d_L, void *hip_stream, gnxr_stats *stats);
+
+/* -- Shading queries on device memory: the pieces an integrator is made of, batched -------------------------------------
+ * Same conventions as the device calls of the Aggregate seam: every array is device memory of one device that holds a copy of the
+ * scene, the work is queued on hip_stream (NULL: the null stream) after what the caller queued there, scratch comes from the
+ * stream-ordered allocator (bounded whatever n is: at most 128 MB), n == 0 is a no-op, and GNXR_ERR_INVALID comes back before anything is
+ * queued for a null scene, a null pointer with n > 0, n < 0, host pointers, pointers on a device without a copy of the scene or
+ * on different devices, or a misaligned pointer.
+ *
+ * gnxr_bsdf_device: per ray Scene::Intersect (d_rays[i]: o, d, tmax), ComputeScatteringFunctions(TransportMode::Radiance,
+ * allowMultipleLobes = true) at the hit and, with wo = Normalize(-d) as SurfaceInteraction sets it: BSDF::f(wo, wi) and
+ * BSDF::Pdf(wo, wi) for the world-space d_wi[3i..] and BSDF::Sample_f(wo, u) for d_u[2i..], all under the BxDFType mask `flags`
+ * (BSDF_ALL = 31).  d_differentials: NULL (hasDifferentials == false: the unfiltered texture lookup PathIntegrator makes) or per
+ * ray 12 floats rxOrigin, rxDirection, ryOrigin, ryDirection (they reach ImageTexture lookups of Kd / Ks and the dudx / dvdy of
+ * the record).  d_rays and d_out 16-byte aligned, the float arrays 4-byte aligned.  The traversal is the one of
+ * gnxr_trace_closest_device; the hit point, shading frame and BSDF are built by the functions the render's shade kernels use.
+ * Returns without waiting for the GPU; may run beside a render of the same handle and beside other queries.
+ *
+ * gnxr_light_sample_device: d_queries holds 12 dwords per query (48 bytes, read as three 16-byte loads): p[3], the light (int32:
+ * an index into the scene's lights), n[3], u[2], wi_query[3].  With ref = the Interaction at p with normal n and zero pError:
+ * Light::Sample_Li(ref, u) of that light, Light::Pdf_Li(ref, wi_query) and the probability with which the LightDistribution of
+ * `strategy` (gnxr_light_strategy) picks that light at p.  d_queries and d_out 16-byte aligned.  The selection table is the
+ * render's (built on first use, shared with gnxr_render, gnxr_li_device and gnxr_light_grid_table), so the call holds the render
+ * lock of the handle and of the copy it runs on: it takes its turn with renders and Li calls there.  A light index outside
+ * [0, n_lights) gives a zero record, the other queries are finished and the call returns GNXR_ERR_INVALID naming the first such
+ * query; that status has to come back, so every call waits for its own kernel (hip_stream is synchronised) before it returns.
+ *
+ * gnxr_light_le_device: Light::Le(ray) of light `light` for escaped rays (d_rays 16-byte aligned; d_le: 3 floats per ray, 4-byte
+ * aligned); zero for lights without Le (everything but the infinite and the sky-box light).  GNXR_ERR_INVALID for a light index
+ * outside [0, n_lights).                                                                                                        */
+int gnxr_bsdf_device(gnxr_scene *scene, const gnxr_ray *d_rays, const float *d_wi, const float *d_u, const float *d_differentials, int64_t n,
+                     int32_t flags, gnxr_bsdf_result *d_out, void *hip_stream);
+int gnxr_light_sample_device(gnxr_scene *scene, const float *d_queries, int64_t n, int32_t strategy, gnxr_light_result *d_out, void *hip_stream);
+int gnxr_light_le_device(gnxr_scene *scene, int32_t light, const gnxr_ray *d_rays, int64_t n, float *d_le, void *hip_stream);
 
 /* -- sampler / camera probes (bit-exactness test hooks) --------------------------------- */
 /* HaltonSampler(spp, [0,width)x[0,height)) value of dimension dim[i] for sample s[i] of pixel
