@@ -279,6 +279,12 @@ class SceneBuilder:
         return d
 
 
+def camera(eye=(0, 0, 5), look=(0, 0, 0), up=(0, 1, 0), fov=90.0, lens_radius=0.0, focal_distance=3.0, orthographic=False):
+    """The gnxr_camera record (ctypes `Camera`) of SceneBuilder.set_camera / Scene.set_camera's arguments: what RenderViews and
+    camera_rays_device take."""
+    return Camera(_f3(eye), _f3(look), _f3(up), fov, lens_radius, focal_distance, int(bool(orthographic)))
+
+
 def write_synthetic_3d(path, target_triangles=100000, seed=1):
     """Deterministic stand-in for the absent Resources/dragon.3d (`.MISSING_LARGE_BLOBS`)."""
     _check(lib().gnxr_write_synthetic_3d(os.fsencode(path), int(target_triangles), int(seed)))
@@ -335,7 +341,7 @@ class Scene:
 
     def set_camera(self, eye=(0, 0, 5), look=(0, 0, 0), up=(0, 1, 0), fov=90.0, lens_radius=0.0, focal_distance=3.0, orthographic=False, medium=-1):
         """The camera of SceneBuilder.set_camera (and the medium it sits in, -1 == none) for later renders."""
-        cam = Camera(_f3(eye), _f3(look), _f3(up), fov, lens_radius, focal_distance, int(bool(orthographic)))
+        cam = camera(eye, look, up, fov, lens_radius, focal_distance, orthographic)
         _check(lib().gnxr_scene_set_camera(self._h, C.byref(cam), int(medium)))
 
     # Aggregate seam: Scene::Intersect / IntersectP, batched
@@ -621,6 +627,45 @@ class PathIntegrator:
                                     C.c_void_p(out.data_ptr() or None), C.c_void_p(stream or None), C.byref(st)))
         return out, stats_dict(st)
 
+    def RenderViews(self, scene, cameras, width, height, spp, media=None, out=None, stream=None, **kw):
+        """Integrator::Render through every camera of `cameras` (gnxr_camera records: camera()) in one call (gnxr_render_views_device):
+        returns (float32 tensor [V, H, W, 4] on the scene's device -- `out` when given --, stats dict).  Image v is bit for bit what
+        Scene.set_camera(cameras[v], medium=media[v]) + Render gives; the scene's own camera is not touched.  `media`: None (no view
+        sits in a medium) or one medium index per view (-1: none).  The views are one path population, so many small images fill the
+        GPU; stats holds the sums over the views.  Runs on `stream` (by default torch's current stream) and returns once the images
+        are written.  The other keyword arguments are Render's, without the shard fields."""
+        import torch
+        cameras = list(cameras)
+        V = len(cameras)
+        for c in cameras:
+            if not isinstance(c, Camera):
+                raise ValueError(f"RenderViews: cameras must be gnxr Camera records (camera(...)), got {type(c).__name__}")
+        if media is not None:
+            media = [int(m) for m in media]
+            if len(media) != V:
+                raise ValueError(f"RenderViews: {len(media)} media for {V} cameras")
+        width, height = int(width), int(height)
+        if width <= 0 or height <= 0:
+            raise ValueError(f"RenderViews: invalid image size {width} x {height}")
+        device = torch.device("cuda", scene.device)
+        if out is None:
+            out = torch.empty((V, height, width, 4), dtype=torch.float32, device=device)
+        else:
+            if not (isinstance(out, torch.Tensor) and out.dim() == 4 and tuple(out.shape) == (V, height, width, 4)):
+                raise ValueError(f"RenderViews: out must have shape ({V}, {height}, {width}, 4), got {tuple(getattr(out, 'shape', ()))}")
+            _tensor_layout("RenderViews: out", out.view(-1, 4) if out.is_contiguous() else out, torch.float32, 4)
+            scene._device_tensor("RenderViews: out", out.view(-1, 4), torch.float32, 4)
+        if stream is None:
+            stream = torch.cuda.current_stream(device)
+        if not isinstance(stream, int):
+            stream = stream.cuda_stream   # a torch.cuda.Stream
+        p = self.params(width, height, spp, **kw)
+        cams = (Camera * max(V, 1))(*cameras)
+        med = (C.c_int32 * max(V, 1))(*media) if media is not None else None
+        st = Stats()
+        _check(lib().gnxr_render_views_device(scene._h, C.byref(p), cams, med, V, C.c_void_p(out.data_ptr() or None), C.c_void_p(stream or None), C.byref(st)))
+        return out, stats_dict(st)
+
     def Render(self, scene, width, height, spp, **kw):
         """Integrator::Render: returns (float32 image [H, W, 4], stats dict)."""
         p = self.params(width, height, spp, **kw)
@@ -691,6 +736,35 @@ def camera_rays(camera, width, height, px, py, s):
                                   len(px), o.ctypes.data_as(C.POINTER(C.c_float)),
                                   d.ctypes.data_as(C.POINTER(C.c_float))))
     return o, d
+
+
+def camera_rays_device(camera, width, height, px, py, s, medium=-1, stream=None):
+    """Camera rays on the GPU (gnxr_camera_rays_device): for sample s[i] of pixel (px[i], py[i]) -- contiguous int32 (n,) tensors on one
+    device -- of `camera` (camera()) over a (width, height) image, returns (rays [n, 8] float32 in the gnxr_ray layout with tmax = inf,
+    samples [n, 4] int32 = px, py, s, medium): the two arrays integrator.Li takes.  o and d carry the bits of camera_rays.  Queued on
+    `stream` (by default torch's current stream); a record outside the image or with s < 0 raises GnxrError, its row is 0."""
+    import torch
+    n = None
+    for what, x in (("px", px), ("py", py), ("s", s)):
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.int32 and x.dim() == 1 and x.is_contiguous() and x.device == px.device):
+            raise ValueError(f"camera_rays_device: {what} must be a contiguous int32 (n,) tensor on one GPU, got "
+                             f"{type(x).__name__} {getattr(x, 'dtype', None)} {tuple(getattr(x, 'shape', ()))} on {getattr(x, 'device', None)}")
+        if n is None:
+            n = x.shape[0]
+        elif x.shape[0] != n:
+            raise ValueError(f"camera_rays_device: {what} has {x.shape[0]} entries for {n} px")
+    if not isinstance(camera, Camera):
+        raise ValueError(f"camera_rays_device: camera must be a gnxr Camera record (camera(...)), got {type(camera).__name__}")
+    if stream is None:
+        stream = torch.cuda.current_stream(px.device)
+    tstream = stream if not isinstance(stream, int) else torch.cuda.ExternalStream(stream, device=px.device)
+    with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensors to the stream that writes them)
+        rays = torch.empty((n, 8), dtype=torch.float32, device=px.device)
+        samples = torch.empty((n, 4), dtype=torch.int32, device=px.device)
+    _check(lib().gnxr_camera_rays_device(C.byref(camera), int(medium), int(width), int(height), C.c_void_p(px.data_ptr() or None), C.c_void_p(py.data_ptr() or None),
+                                         C.c_void_p(s.data_ptr() or None), n, C.c_void_p(rays.data_ptr() or None), C.c_void_p(samples.data_ptr() or None),
+                                         C.c_void_p(tstream.cuda_stream or None)))
+    return rays, samples
 
 
 def save_png(path, rgba8):

@@ -147,6 +147,8 @@ PROTOTYPES = {
     "gnxr_trace_closest_device": (C.c_int, [VP, VP, i64, VP, VP]),   # device addresses + hipStream_t
     "gnxr_trace_any_device": (C.c_int, [VP, VP, i64, VP, VP]),
     "gnxr_li_device": (C.c_int, [VP, P(RenderParams), VP, VP, i64, VP, VP, P(Stats)]),   # device addresses + hipStream_t
+    "gnxr_render_views_device": (C.c_int, [VP, P(RenderParams), P(Camera), P(i32), i32, VP, VP, P(Stats)]),   # cameras, media: host; images: device
+    "gnxr_camera_rays_device": (C.c_int, [P(Camera), i32, i32, i32, VP, VP, VP, i64, VP, VP, VP]),   # device addresses + hipStream_t
     "gnxr_bsdf_device": (C.c_int, [VP, VP, VP, VP, VP, i64, i32, VP, VP]),   # device addresses + hipStream_t
     "gnxr_light_sample_device": (C.c_int, [VP, VP, i64, i32, VP, VP]),
     "gnxr_light_le_device": (C.c_int, [VP, i32, VP, i64, VP, VP]),

@@ -24,6 +24,7 @@
 #include "hlbvh_build.hip.h"
 #include "refit_kernel.hip.h"
 #include "li_kernel.hip.h"
+#include "views_kernel.hip.h"
 #include "shade_query_kernel.hip.h"
 #include "kernel_instances.h"
 
@@ -217,6 +218,9 @@ struct gnxr_scene {
     DevBuf<unsigned int> upd_arrived;
     DevBuf<float> upd_xyz;
     DevBuf<int> upd_flag;
+    // gnxr_render_views_device: the DCamera record of every view (the host copy is what the stream-ordered upload reads; both only grow)
+    DevBuf<DCamera> view_cams;
+    std::vector<DCamera> h_view_cams;
     bool host_bvh_stale = false;         // after an update cs.nodes / nodes4 / tris / leaf_boxes lag the device until sync_host_bvh()
 
     int bind() const { HIP_TRY(hipSetDevice(device)); return GNXR_OK; }
@@ -830,9 +834,19 @@ struct RaySource {
     long long n;
 };
 
+// gnxr_render_views_device: the cameras of render_one's loops when a call renders several views.  The V views are one path population of
+// V * W * H pixels per sample (views_kernel.hip.h): the loops size their passes on it, and the image is the V images one after the other.
+struct ViewSource {
+    const gnxr_camera *cameras;   // host memory, n_views records
+    const int32_t *media;         // host memory, n_views entries in [-1, n_media) (checked by the caller), or nullptr: all -1
+    int n_views;
+};
+
 // One device: the wavefront loop over the rows `pin` assigns to this shard, on the device the scene's tables live on.
 // src != nullptr: Li for the caller's rays instead (gnxr_li_device); `d_rgba_out` is then unused.
-static int render_one(gnxr_scene *s, const gnxr_render_params *pin, void *d_rgba_out, void *hip_stream, gnxr_stats *stats, const RaySource *src = nullptr) {
+// views != nullptr: the views' cameras instead of the scene's (gnxr_render_views_device); `d_rgba_out` holds n_views images.
+static int render_one(gnxr_scene *s, const gnxr_render_params *pin, void *d_rgba_out, void *hip_stream, gnxr_stats *stats, const RaySource *src = nullptr,
+                      const ViewSource *views = nullptr) {
     if (!s || !pin || (!d_rgba_out && !src)) { set_error("null argument"); return GNXR_ERR_INVALID; }
     gnxr_render_params p = *pin;
     if (p.shard_count <= 0) p.shard_count = 1;
@@ -879,6 +893,12 @@ static int render_one(gnxr_scene *s, const gnxr_render_params *pin, void *d_rgba
         set_error("Li for caller rays: Whitted, DirectLighting and VolPath need camera ray differentials on scenes with image textures");
         return GNXR_ERR_UNSUPPORTED;
     }
+    if (views && textured_scene && volpath) {
+        // (k_vol_step recomputes the camera's offset rays at the first surface from DRender::cam, vol_kernel.hip.h: the one camera read
+        // inside a shade kernel.  Whitted / DirectLighting store them per path at raygen, PathIntegrator drops them: both render views)
+        set_error("views: VolPath on a scene with image textures recomputes the camera's ray differentials inside its shade kernels; render its views one by one");
+        return GNXR_ERR_UNSUPPORTED;
+    }
     std::lock_guard<std::recursive_mutex> lock(s->render_mutex);
     if (int brc = s->bind()) return brc;
     auto t_start = std::chrono::steady_clock::now();
@@ -892,11 +912,22 @@ static int render_one(gnxr_scene *s, const gnxr_render_params *pin, void *d_rgba
     sc.st.h.base32_max = (int32_t)std::min<unsigned long long>(0x7fffffffull, 0xffffffffull / ((unsigned long long)sc.st.h.stride * ((unsigned long long)p.spp * max_light_samples + 1)));
     DRender r;
     memset(&r, 0, sizeof(r));
-    r.cam = make_camera(s->cs.camera, p.width, p.height, s->cs.camera_medium);
+    // views: one DCamera per view; r.cam (the first view's) is read by no kernel of a views render
+    bool views_mixed_media = false;
+    if (views) {
+        s->h_view_cams.resize(std::max<size_t>(s->h_view_cams.size(), (size_t)views->n_views));
+        for (int v = 0; v < views->n_views; ++v) {
+            s->h_view_cams[v] = make_camera(views->cameras[v], p.width, p.height, views->media ? views->media[v] : -1);
+            if (s->h_view_cams[v].medium != s->h_view_cams[0].medium) views_mixed_media = true;
+        }
+        r.cam = s->h_view_cams[0];
+    } else {
+        r.cam = make_camera(s->cs.camera, p.width, p.height, s->cs.camera_medium);
+    }
     r.W = p.width; r.H = p.height; r.spp = p.spp; r.max_depth = p.max_depth; r.rr_threshold = p.rr_threshold;
     r.shard_index = p.shard_index; r.shard_count = p.shard_count; r.shard_rows = p.shard_rows;
     int local_rows = count_local_rows(&p);
-    r.npix = local_rows * p.width;
+    r.npix = views ? views->n_views * p.width * p.height : local_rows * p.width;
     if (r.npix == 0) { if (stats) memset(stats, 0, sizeof(*stats)); return GNXR_OK; }
     int nsamples = p.spp_end - p.spp_begin;
     // the unit of work the loops cut into passes: one sample of every pixel (r.npix paths), or one caller ray
@@ -1010,7 +1041,10 @@ static int render_one(gnxr_scene *s, const gnxr_render_params *pin, void *d_rgba
         sc.materials = s->materials_single.p + 1;
     }
 
+    if (views && (rc = s->view_cams.alloc(s->h_view_cams.size())) != GNXR_OK) return rc;
     if (g_reserve_only) { if (stats) memset(stats, 0, sizeof(*stats)); return GNXR_OK; }
+    // (stream-ordered: the table is read by this call's raygen kernels only, and the call returns after the stream has drained)
+    if (views) HIP_TRY(hipMemcpyAsync(s->view_cams.p, s->h_view_cams.data(), (size_t)views->n_views * sizeof(DCamera), hipMemcpyHostToDevice, stream));
     if (!src) HIP_TRY(hipMemsetAsync(s->accum.p, 0, sizeof(float4) * r.npix, stream));
     HIP_TRY(hipMemsetAsync(s->counters.p, 0, sizeof(Counters), stream));
     struct EventPair {   // destroyed on every exit path
@@ -1212,7 +1246,8 @@ else hipLaunchKernelGGL((k_shade<LM_ALL, LTV, false, true>), g, b, slds, cst[3],
     const int n_scene_media = (int)s->cs.media.size();
     auto raygen = [&](const PathArrays &at, long long u0, int kk, unsigned char *medium_keys) {
         const int n_new = (int)(unit * kk);
-        if (!src) hipLaunchKernelGGL(k_raygen, dim3(grid_for(n_new)), dim3(kBlock), 0, stream, sc, r, at, n_new, (int)u0);
+        if (views) hipLaunchKernelGGL(k_raygen_views, dim3(grid_for(n_new)), dim3(kBlock), 0, stream, sc, r, (const DCamera *)s->view_cams.p, at, n_new, (int)u0, medium_keys);
+        else if (!src) hipLaunchKernelGGL(k_raygen, dim3(grid_for(n_new)), dim3(kBlock), 0, stream, sc, r, at, n_new, (int)u0);
         else hipLaunchKernelGGL(k_raygen_rays, dim3(grid_for(n_new)), dim3(kBlock), 0, stream, sc, r, at, reinterpret_cast<const float4 *>(src->rays + u0),
                                 reinterpret_cast<const int4 *>(src->samples + u0), n_new, n_scene_media, medium_keys, dctr, u0);
     };
@@ -1350,7 +1385,9 @@ else hipLaunchKernelGGL((k_shade<LM_ALL, LTV, false, true>), g, b, slds, cst[3],
     for (long long u0 = unit_begin; u0 < unit_end; u0 += k) {
         int kk = (int)std::min<long long>(k, unit_end - u0);
         int n_paths = (int)(unit * kk);
-        raygen(pa, u0, kk, (src && volpath) ? s->pflags.p : nullptr);
+        // caller rays name a medium each, views may sit in different media: raygen marks the slots that start inside one
+        const bool list_media = volpath && (src || views_mixed_media);
+        raygen(pa, u0, kk, list_media ? s->pflags.p : nullptr);
         ++launches;
         int n = n_paths;
         const int *q_in = nullptr;            // paths alive at this vertex (nullptr == identity), ascending
@@ -1360,7 +1397,11 @@ else hipLaunchKernelGGL((k_shade<LM_ALL, LTV, false, true>), g, b, slds, cst[3],
             // depth-first recursion per path (whitted_kernel.hip.h): the path's ray + the previous vertex's shadow rays per round
             hipLaunchKernelGGL(k_whitted_init, dim3(grid_for(n_paths)), dim3(kBlock), 0, stream, pa, wa, n_paths);
             ++launches;
-            if (textured) { hipLaunchKernelGGL(k_whitted_init_diff, dim3(grid_for(n_paths)), dim3(kBlock), 0, stream, sc, r, pa, wa, n_paths); ++launches; }
+            if (textured) {
+                if (views) hipLaunchKernelGGL(k_whitted_init_diff_views, dim3(grid_for(n_paths)), dim3(kBlock), 0, stream, sc, r, (const DCamera *)s->view_cams.p, pa, wa, n_paths);
+                else hipLaunchKernelGGL(k_whitted_init_diff, dim3(grid_for(n_paths)), dim3(kBlock), 0, stream, sc, r, pa, wa, n_paths);
+                ++launches;
+            }
             int n_cl = n, n_shp = 0;
             const int *q_cl = nullptr;
             unsigned long long *d_shadow = &dctr->whitted_shadow;
@@ -1400,7 +1441,7 @@ else hipLaunchKernelGGL((k_shade<LM_ALL, LTV, false, true>), g, b, slds, cst[3],
             ++launches;
             int n_media = r.cam.medium >= 0 ? n : 0;      // paths whose ray in flight travels inside a medium
             const int *q_media = nullptr;
-            if (src) {   // caller rays: each record names its own medium; list the slots k_raygen_rays marked (pflags bit 1)
+            if (list_media) {   // caller rays: each record names its own medium (views: each view); list the slots raygen marked (pflags bit 1)
                 compact(COMPACT_FLAGS, nullptr, n, s->pflags.p, 4, 2, &dctr->q_next, q_cur, s->queue_nee.p, nullptr);
                 HIP_TRY(hipMemcpyAsync(s->h_counters, dctr, sizeof(Counters), hipMemcpyDeviceToHost, stream));
                 HIP_TRY(hipStreamSynchronize(stream));
@@ -1896,6 +1937,43 @@ int gnxr_li_device(gnxr_scene *s, const gnxr_render_params *p, const gnxr_ray *d
     return rc;
 }
 
+// ---- many cameras in one render on device memory: gnxr_render_views_device ----
+// render_one's loops with a ViewSource in place of the scene's camera (views_kernel.hip.h), on the copy of the scene that holds the images.
+int gnxr_render_views_device(gnxr_scene *s, const gnxr_render_params *p, const gnxr_camera *cameras, const int32_t *camera_media, int32_t n_views, void *d_rgba_out,
+                             void *hip_stream, gnxr_stats *stats) {
+    if (!s || !p || n_views < 0 || (n_views > 0 && !cameras)) { set_error("bad argument"); return GNXR_ERR_INVALID; }
+    if (p->shard_index != 0 || p->shard_count < 0 || p->shard_count > 1 || p->shard_rows < 0 || p->shard_rows > 1) {
+        set_error("views: shard_index must be 0, shard_count and shard_rows 0 or 1 (a caller that shards splits the list of views)");
+        return GNXR_ERR_INVALID;
+    }
+    if (p->width <= 0 || p->height <= 0 || p->spp <= 0 || p->spp_begin < 0 || p->spp_end > p->spp || (p->spp_end > 0 && p->spp_begin >= p->spp_end) || p->spp_begin >= p->spp ||
+        p->max_depth < 0 || p->max_depth > 250) {
+        set_error("invalid render parameters");
+        return GNXR_ERR_INVALID;
+    }
+    if (n_views == 0) { if (stats) memset(stats, 0, sizeof(*stats)); return GNXR_OK; }
+    if (!d_rgba_out || ((uintptr_t)d_rgba_out & 15u) != 0) { set_error("d_rgba_out is null or not 16-byte aligned"); return GNXR_ERR_INVALID; }
+    // a path slot is sample * (n_views * W * H) + pixel in an int, and the traversal's work cursor counts three items per slot in 32 bits
+    const long long kMaxViewPixels = ((1ll << 32) - 1) / 3;
+    const long long total = (long long)n_views * p->width * p->height;
+    if (total > kMaxViewPixels) {
+        set_error("views: n_views * width * height = %lld pixels overflow the 32-bit path indexing (at most %lld per call); split the list of views", total, kMaxViewPixels);
+        return GNXR_ERR_INVALID;
+    }
+    if (int rc = ensure_device()) return rc;
+    const int n_media = (int)s->cs.media.size();
+    for (int v = 0; camera_media && v < n_views; ++v)
+        if (camera_media[v] < -1 || camera_media[v] >= n_media) { set_error("views: camera_media[%d] = %d is outside [-1, %d)", v, camera_media[v], n_media); return GNXR_ERR_INVALID; }
+    gnxr_scene *r = query_replica(s, d_rgba_out, (size_t)total * sizeof(float4), "d_rgba_out");
+    if (!r) return GNXR_ERR_INVALID;
+    gnxr_render_params pp = *p;
+    pp.shard_count = 1; pp.shard_rows = 1;
+    const ViewSource vs{cameras, camera_media, (int)n_views};
+    const int rc = render_one(r, &pp, d_rgba_out, hip_stream, stats, nullptr, &vs);
+    if (r != s) (void)s->bind();   // leave the primary device current
+    return rc;
+}
+
 // ---- shading queries on device memory: gnxr_bsdf_device / gnxr_light_sample_device / gnxr_light_le_device (shade_query_kernel.hip.h) ----
 
 // rays of one traversal + k_bsdf_query round: bounds the call's scratch (one gnxr_hit per ray for the leaf codes) at 128 MB whatever n is
@@ -2087,6 +2165,76 @@ int gnxr_camera_rays(const gnxr_camera *cam, int32_t width, int32_t height, cons
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(o_out, dob.p, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(d_out, dd.p, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
+    return GNXR_OK;
+}
+
+// The sampler tables of probe_tables on `device`, uploaded once per device and kept until the process ends (never freed: the runtime may
+// be gone when static destructors run).  h of the returned tables is the caller's to set (make_halton).
+static int device_probe_tables(int device, DSamplerTables *st) {
+    struct Set { CompiledScene cs; DevBuf<uint16_t> perms; DevBuf<int32_t> primes, sums; DevBuf<uint32_t> magic; DSamplerTables st; };
+    static std::mutex m;
+    static std::vector<std::pair<int, Set *>> sets;
+    std::lock_guard<std::mutex> lock(m);
+    for (auto &e : sets) if (e.first == device) { *st = e.second->st; return GNXR_OK; }
+    std::unique_ptr<Set> set(new (std::nothrow) Set());
+    if (!set) return GNXR_ERR_OOM;
+    if (int rc = probe_tables(&set->cs, &set->perms, &set->primes, &set->sums, &set->magic, &set->st, 1, 1)) return rc;
+    *st = set->st;
+    sets.emplace_back(device, set.release());
+    return GNXR_OK;
+}
+
+// The device-memory form of gnxr_camera_rays: rays and sample records for gnxr_li_device, written on the caller's stream.  No scene: the
+// sampler tables are cached per device, the camera travels as a kernel argument, and the only allocation is the 8-byte status word.
+int gnxr_camera_rays_device(const gnxr_camera *cam, int32_t camera_medium, int32_t width, int32_t height, const int32_t *d_px, const int32_t *d_py, const int32_t *d_s,
+                            int64_t n, gnxr_ray *d_rays, gnxr_li_sample *d_samples, void *hip_stream) {
+    if (!cam || n < 0 || width <= 0 || height <= 0 || camera_medium < -1 || (n > 0 && (!d_px || !d_py || !d_s || !d_rays || !d_samples))) { set_error("bad argument"); return GNXR_ERR_INVALID; }
+    if (n == 0) return GNXR_OK;
+    if ((((uintptr_t)d_rays | (uintptr_t)d_samples) & 15u) != 0) { set_error("d_rays and d_samples must be 16-byte aligned"); return GNXR_ERR_INVALID; }
+    if ((((uintptr_t)d_px | (uintptr_t)d_py | (uintptr_t)d_s) & 3u) != 0) { set_error("d_px, d_py and d_s must be 4-byte aligned"); return GNXR_ERR_INVALID; }
+    if (int rc = ensure_device()) return rc;
+    const QueryArg args[] = {{d_px, (size_t)n * 4, "d_px"}, {d_py, (size_t)n * 4, "d_py"}, {d_s, (size_t)n * 4, "d_s"}, {d_rays, (size_t)n * sizeof(gnxr_ray), "d_rays"},
+                             {d_samples, (size_t)n * sizeof(gnxr_li_sample), "d_samples"}};
+    int device = -1;
+    for (const QueryArg &a : args) {
+        hipPointerAttribute_t at;
+        const hipError_t e = hipPointerGetAttributes(&at, a.p);
+        (void)hipGetLastError();
+        if (e != hipSuccess || at.type != hipMemoryTypeDevice) { set_error("%s is not device memory (host arrays go through gnxr_camera_rays)", a.what); return GNXR_ERR_INVALID; }
+        if (device >= 0 && at.device != device) { set_error("%s and %s live on different devices", args[0].what, a.what); return GNXR_ERR_INVALID; }
+        device = at.device;
+        hipDeviceptr_t base = nullptr;
+        size_t size = 0;
+        if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)a.p) == hipSuccess && base && (const char *)a.p + a.bytes > (const char *)base + size) {
+            set_error("%s: %zu bytes from %p run past the end of its allocation (%zu bytes from %p)", a.what, a.bytes, a.p, size, (void *)base);
+            return GNXR_ERR_INVALID;
+        }
+        (void)hipGetLastError();
+    }
+    HIP_TRY(hipSetDevice(device));
+    struct Rebind { int dev; ~Rebind() { if (dev >= 0) (void)hipSetDevice(dev); } } rebind{device != g_device ? g_device : -1};   // leave the bound device current
+    DSamplerTables st;
+    if (int rc = device_probe_tables(device, &st)) return rc;
+    st.h = make_halton(width, height);
+    const DCamera dc = make_camera(*cam, width, height, camera_medium);
+    hipStream_t stream = (hipStream_t)hip_stream;
+    unsigned long long *d_bad = nullptr, bad = 0;
+    HIP_TRY(hipMallocAsync((void **)&d_bad, sizeof(unsigned long long), stream));
+    hipError_t e = hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_camera_rays, dim3(grid_for(n)), dim3(kBlock), 0, stream, st, dc, (int)width, (int)height, (const int *)d_px, (const int *)d_py, (const int *)d_s,
+                           (long long)n, reinterpret_cast<float4 *>(d_rays), reinterpret_cast<int4 *>(d_samples), d_bad);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, stream);
+    const hipError_t ef = hipFreeAsync(d_bad, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);   // only the status word has to come back: the records are on the stream
+    HIP_TRY(e);
+    HIP_TRY(ef);
+    if (bad) {
+        set_error("gnxr_camera_rays_device: record %llu is out of range (px in [0, %d), py in [0, %d), s >= 0); its ray and sample are 0", (unsigned long long)~bad, width, height);
+        return GNXR_ERR_INVALID;
+    }
     return GNXR_OK;
 }
 

@@ -442,6 +442,43 @@ int gnxr_trace_any_device(gnxr_scene *scene, const gnxr_ray *d_rays, int64_t n, 
 int gnxr_li_device(gnxr_scene *scene, const gnxr_render_params *params, const gnxr_ray *d_rays, const gnxr_li_sample *d_samples, int64_t n,
                    float *d_L, void *hip_stream, gnxr_stats *stats);
 
+/* -- Many cameras in one render, on device memory ------------------------------------------------------------------------
+ * gnxr_render_views_device renders n_views images of one scene in one call.  cameras (host memory, n_views records) and
+ * camera_media (host memory, n_views entries in [-1, n_media); NULL: all -1) name each view's camera and the medium it sits in;
+ * d_rgba_out is device memory for n_views images of width*height*4 fp32, image v at v*width*height*4, each in the layout of
+ * gnxr_render_device.  Image v is, bit for bit, what gnxr_scene_set_camera(scene, &cameras[v], camera_media[v]) followed by
+ * gnxr_render_device(scene, params, ...) writes; the scene's own camera is neither read nor changed.  The views are one path
+ * population (a pixel index that carries the view number), so sub-passes are sized on n_views*width*height pixels: many small
+ * images fill the device where one would not.  spp_begin / spp_end, samples_per_pass (samples of EVERY view per sub-pass),
+ * passes_in_flight, max_depth, the integrator and the strategies mean what they mean for gnxr_render_device; all four
+ * integrators are supported.  shard_index must be 0, shard_count and shard_rows 0 or 1 (a caller that shards splits the list of
+ * views).  stats carries the sums of the ray counters and of camera_samples over the views.  Locking and ordering as for
+ * gnxr_render_device: one render, Li or views call per handle at a time, queued after what hip_stream holds, back when the images
+ * are written.  With gnxr_init_devices the call runs on the copy of the scene on the device that holds d_rgba_out.  n_views == 0
+ * is a no-op.
+ * GNXR_ERR_INVALID, before anything is queued: null scene or params; null cameras with n_views > 0; n_views < 0; an output that is
+ * null, not device memory, on a device without a copy of the scene or not 16-byte aligned; invalid params or shard fields; a
+ * medium outside [-1, n_media); n_views*width*height beyond the 32-bit path indexing (at most (2^32 - 1) / 3 pixels per call).
+ * GNXR_ERR_UNSUPPORTED: what gnxr_render_device refuses, and VolPath on a scene with image textures (its shade kernels recompute
+ * the camera's ray differentials at the first surface; Whitted and DirectLighting store them per path at raygen and render views
+ * of textured scenes, PathIntegrator does not use them).
+ *
+ * gnxr_camera_rays_device is the device-memory form of gnxr_camera_rays and needs no scene: for sample d_s[i] of pixel
+ * (d_px[i], d_py[i]) of a HaltonSampler over [0,width) x [0,height) it writes the camera ray into d_rays[i] -- o and d with the
+ * bits gnxr_camera_rays gives, tmax = +inf, _pad = 0 -- and {px, py, s, camera_medium} into d_samples[i]: the two arrays
+ * gnxr_li_device takes.  All five arrays are device memory of one device; d_rays and d_samples 16-byte aligned, the int arrays
+ * 4-byte aligned.  The kernel runs on hip_stream after what the caller queued there; no allocation grows with n (the sampler
+ * tables are uploaded once per device, the status word comes from the stream-ordered allocator).  A record with px, py outside
+ * the image or s < 0 gets a zeroed ray and sample; the other records are finished and the call returns GNXR_ERR_INVALID naming
+ * the first such record.  That status has to come back, so the call waits for its own kernel (hip_stream is synchronised)
+ * before it returns, as gnxr_light_sample_device does.  n == 0 is a no-op.  GNXR_ERR_INVALID, before anything is queued: a null
+ * camera, a null array with n > 0, n < 0, width or height <= 0, camera_medium < -1, arrays that are not device memory, on
+ * different devices or misaligned.                                                                                            */
+int gnxr_render_views_device(gnxr_scene *scene, const gnxr_render_params *params, const gnxr_camera *cameras, const int32_t *camera_media,
+                             int32_t n_views, void *d_rgba_out, void *hip_stream, gnxr_stats *stats);
+int gnxr_camera_rays_device(const gnxr_camera *camera, int32_t camera_medium, int32_t width, int32_t height, const int32_t *d_px,
+                            const int32_t *d_py, const int32_t *d_s, int64_t n, gnxr_ray *d_rays, gnxr_li_sample *d_samples, void *hip_stream);
+
 /* -- Shading queries on device memory: the pieces an integrator is made of, batched -------------------------------------
  * Same conventions as the device calls of the Aggregate seam: every array is device memory of one device that holds a copy of the
  * scene, the work is queued on hip_stream (NULL: the null stream) after what the caller queued there, scratch comes from the

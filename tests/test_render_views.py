@@ -1,0 +1,412 @@
+"""Many cameras in one render: gnxr_render_views_device / Integrator.RenderViews, and camera rays on device memory:
+gnxr_camera_rays_device / camera_rays_device.
+
+The V views of a call are one path population whose pixel index carries the view number (csrc/views_kernel.hip.h), so image v must be
+what Scene.set_camera(cameras[v]) + Render gives -- and through it what the oracle renders for a builder whose set_camera was called
+with that camera.  Every comparison is bit for bit (NaN equal to NaN), and images must be non-zero somewhere."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+import torch  # noqa: F401  (before libgnxr.so is loaded: torch's HIP runtime must come up first for device tensors in this process)
+
+import oracle_lib as ol
+import scenes
+from conftest import GOLDEN, ROOT, golden
+
+MESH2K = os.path.join(GOLDEN, "mesh_2k.3d")
+ENV = os.path.join(GOLDEN, "env_100x50.hdr")
+TEX = os.path.join(GOLDEN, "tex_smile_96x80.hdr")
+ERR_INVALID, ERR_NO_DEVICE, ERR_UNSUPPORTED = -1, -2, -4
+TIME_KEYS = ("seconds_render", "seconds_trace", "seconds_total", "seconds_closest", "seconds_nee", "seconds_shade")
+# The device-driven path loop runs ahead of lagging copies of the device counters (api.hip): how many turns the host takes, and so how
+# many launches it makes, before it sees that a sub-pass has ended depends on when those copies arrive.  These two measure time as well.
+HOST_PACED_KEYS = ("loop_iterations", "kernel_launches")
+
+# different eyes, one thin lens, one orthographic, one inside the box looking at the light (the Cornell box spans [-2.5, 2.5]^3, the
+# light sits under its ceiling)
+CAMS = [dict(eye=(0, 0, 5), look=(0, 0, 0), fov=90.0),
+        dict(eye=(1.2, 0.6, 4.4), look=(-0.2, -0.4, 0.0), fov=55.0),
+        dict(eye=(0.3, 0.2, 4.8), look=(0.0, -0.5, 0.0), fov=50.0, lens_radius=0.08, focal_distance=4.5),
+        dict(eye=(0.0, 0.4, 5.0), look=(0.0, 0.0, 0.0), orthographic=True),
+        dict(eye=(0.4, -1.8, 0.9), look=(0.0, 2.4, 0.0), up=(0, 0, -1), fov=75.0)]
+
+
+def biteq(a, b):
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    return a.shape == b.shape and bool(((a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))).all())
+
+
+def views(integ, scene, cams, W, H, spp, **kw):
+    import gnxraytracer_amd as gx
+    img, st = integ.RenderViews(scene, [gx.camera(**c) for c in cams], W, H, spp, **kw)
+    torch.cuda.synchronize()
+    return img.cpu().numpy(), st
+
+
+def oracle_views(b, integ, cams, W, H, spp, media=None, **kw):
+    """the oracle's render through every camera: the builder's set_camera (and set_camera_medium) per view"""
+    out = []
+    for v, c in enumerate(cams):
+        b.set_camera(**c)
+        if media is not None:
+            b.set_camera_medium(media[v])
+        out.append(ol.OracleScene(b).render(integ, W, H, spp, **kw))
+    return out
+
+
+def sequential(integ, scene, cams, W, H, spp, media=None, **kw):
+    """the only way without RenderViews: Scene.set_camera + Render per view"""
+    out = []
+    for v, c in enumerate(cams):
+        scene.set_camera(**c, medium=-1 if media is None else media[v])
+        out.append(integ.Render(scene, W, H, spp, **kw))
+    return out
+
+
+def check_against(img, st, ref, keys=("rays_closest", "rays_any")):
+    assert img.shape[0] == len(ref)
+    for v, (rimg, _) in enumerate(ref):
+        assert biteq(img[v][..., :3], rimg[..., :3]), f"view {v}"
+        assert img[v][..., :3].any() and (img[v][..., 3] == 1).all(), f"view {v}"
+    for k in keys:
+        assert st[k] == sum(r[1][k] for r in ref), (k, st[k], [r[1][k] for r in ref])
+
+
+def dummy_args(gx):
+    """host memory that passes every argument check, a 16-byte aligned address, a misaligned one and a handle that must not be touched"""
+    buf = (C.c_float * 4096)()
+    base = (C.addressof(buf) + 15) & ~15
+    return buf, C.c_void_p(base), C.c_void_p(base + 4), C.c_void_p(base)
+
+
+# ---------------------------------------------------------------- CPU
+def test_views_entry_points_declared_exported_and_bound(gx):
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "gnxr.h")).read(), flags=re.S)
+    lib = C.CDLL(gx.LIB_PATH)
+    for name in ("gnxr_render_views_device", "gnxr_camera_rays_device"):
+        assert re.search(r"\b%s\s*\(" % name, hdr), name
+        assert hasattr(lib, name), name
+        assert name in gx._abi.PROTOTYPES, name
+    # no new record type: the ABI version and the set of gnxr_abi_sizeof indices are those of the parent
+    assert gx.lib().gnxr_abi_version() == 5 and gx.lib().gnxr_abi_sizeof(13) > 0 and gx.lib().gnxr_abi_sizeof(14) == -1
+
+
+def test_views_reject_bad_arguments_before_any_device_work(gx):
+    """GNXR_ERR_INVALID before the handle or the device is looked at (the handle is a dummy a call must not touch); n_views == 0 and
+    n == 0 are no-ops; arguments that pass every check need the runtime: GNXR_ERR_NO_DEVICE on a box without a GPU."""
+    L = gx.lib()
+    buf, p, odd, dummy = dummy_args(gx)
+    integ = gx.PathIntegrator(5)
+    ok = integ.params(64, 48, 4)
+    cams = (gx.Camera * 2)(gx.camera(), gx.camera(eye=(1, 0, 5)))
+    st = gx.Stats()
+    V = L.gnxr_render_views_device
+    assert V(None, C.byref(ok), cams, None, 2, p, None, C.byref(st)) == ERR_INVALID
+    assert V(dummy, None, cams, None, 2, p, None, C.byref(st)) == ERR_INVALID
+    assert V(dummy, C.byref(ok), None, None, 2, p, None, C.byref(st)) == ERR_INVALID
+    assert V(dummy, C.byref(ok), cams, None, -1, p, None, C.byref(st)) == ERR_INVALID
+    for bad in (dict(shard_index=1), dict(shard_count=2), dict(shard_index=1, shard_count=2), dict(shard_rows=2)):
+        q = integ.params(64, 48, 4, **bad)
+        assert V(dummy, C.byref(q), cams, None, 2, p, None, C.byref(st)) == ERR_INVALID, bad
+    for q in (integ.params(0, 48, 4), integ.params(64, 48, 0), integ.params(64, 48, 4, spp_begin=3, spp_end=2), integ.params(64, 48, 4, spp_end=5)):
+        assert V(dummy, C.byref(q), cams, None, 2, p, None, C.byref(st)) == ERR_INVALID
+    assert V(dummy, C.byref(ok), cams, None, 2, None, None, C.byref(st)) == ERR_INVALID
+    assert V(dummy, C.byref(ok), cams, None, 2, odd, None, C.byref(st)) == ERR_INVALID
+    assert "aligned" in L.gnxr_last_error().decode()
+    big = integ.params(32768, 32768, 1)   # 2 x 2^30 pixels: beyond the 32-bit path indexing
+    assert V(dummy, C.byref(big), cams, None, 2, p, None, C.byref(st)) == ERR_INVALID
+    assert "path indexing" in L.gnxr_last_error().decode()
+    st.camera_samples = 7
+    assert V(dummy, C.byref(ok), None, None, 0, None, None, C.byref(st)) == 0 and st.camera_samples == 0
+
+    R = L.gnxr_camera_rays_device
+    cam = gx.camera()
+    assert R(None, -1, 64, 48, p, p, p, 4, p, p, None) == ERR_INVALID
+    for k in range(5):
+        a = [p] * 5
+        a[k] = None
+        assert R(C.byref(cam), -1, 64, 48, a[0], a[1], a[2], 4, a[3], a[4], None) == ERR_INVALID, k
+    assert R(C.byref(cam), -1, 64, 48, p, p, p, -1, p, p, None) == ERR_INVALID
+    assert R(C.byref(cam), -1, 0, 48, p, p, p, 4, p, p, None) == ERR_INVALID
+    assert R(C.byref(cam), -2, 64, 48, p, p, p, 4, p, p, None) == ERR_INVALID
+    assert R(C.byref(cam), -1, 64, 48, p, p, p, 4, odd, p, None) == ERR_INVALID
+    assert R(C.byref(cam), -1, 64, 48, p, p, p, 4, p, odd, None) == ERR_INVALID
+    assert "aligned" in L.gnxr_last_error().decode()
+    assert R(C.byref(cam), -1, 64, 48, C.c_void_p(p.value + 2), p, p, 4, p, p, None) == ERR_INVALID
+    assert R(C.byref(cam), -1, 64, 48, None, None, None, 0, None, None, None) == 0
+    if not torch.cuda.is_available():
+        assert V(dummy, C.byref(ok), cams, None, 2, p, None, C.byref(st)) == ERR_NO_DEVICE
+        assert R(C.byref(cam), -1, 64, 48, p, p, p, 4, p, p, None) == ERR_NO_DEVICE
+    del buf
+
+
+def test_camera_record_and_python_checks(gx):
+    """gx.camera builds the record Scene.set_camera builds; RenderViews and camera_rays_device refuse other inputs before a library call"""
+    c = gx.camera((1, 2, 3), (0, 0.5, 0), (0, 0, 1), 70.0, 0.1, 4.0, True)
+    assert isinstance(c, gx.Camera) and list(c.eye) == [1, 2, 3] and list(c.look) == [0, 0.5, 0] and list(c.up) == [0, 0, 1]
+    assert (c.fov_deg, c.focal_distance, c.orthographic) == (70.0, 4.0, 1) and abs(c.lens_radius - 0.1) < 1e-7
+    d = gx.camera()
+    assert (list(d.eye), list(d.look), list(d.up), d.fov_deg, d.lens_radius, d.focal_distance, d.orthographic) == ([0, 0, 5], [0, 0, 0], [0, 1, 0], 90.0, 0.0, 3.0, 0)
+    s = object.__new__(gx.Scene)
+    s._h, s.device = None, 0
+    integ = gx.PathIntegrator(5)
+    for kw in (dict(cameras=[dict(eye=(0, 0, 5))]), dict(cameras=[d], media=[0, 1]), dict(cameras=[d], out=torch.zeros((1, 8, 8, 3))),
+               dict(cameras=[d], out=torch.zeros((2, 8, 8, 4))), dict(cameras=[d], out=torch.zeros((1, 8, 8, 4), dtype=torch.float64)),
+               dict(cameras=[d], out=torch.zeros((1, 8, 8, 4))), dict(cameras=[d, 3])):   # (the last `out` is host memory)
+        with pytest.raises(ValueError):
+            integ.RenderViews(s, kw.pop("cameras"), 8, 8, 2, **kw)
+    z = torch.zeros(4, dtype=torch.int32)
+    for bad in ((z, z, z), (z.long(), z, z)):
+        with pytest.raises(ValueError):
+            gx.camera_rays_device(d, 8, 8, *bad)
+
+
+# ---------------------------------------------------------------- GPU
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["path", "whitted", "direct"])
+@pytest.mark.parametrize("name", ["cornell_sky", "dragon_env"])
+def test_views_match_oracle(gpu, name, kind):
+    """1. five cameras, 64 x 48 at 8 spp: image v == the oracle's render with camera v; the ray counts are the sums of the oracle's"""
+    make = {"cornell_sky": lambda: scenes.cornell(sky=True), "dragon_env": lambda: scenes.dragon_cornell(2000, "glass+metal", env=ENV, mesh_path=MESH2K)}[name]
+    integ = {"path": gpu.PathIntegrator(5, 1.0, "spatial"), "whitted": gpu.WhittedIntegrator(5), "direct": gpu.DirectLightingIntegrator("all", 5)}[kind]
+    scene = gpu.Scene(make())
+    img, st = views(integ, scene, CAMS, 64, 48, 8)
+    assert img.shape == (5, 48, 64, 4) and st["camera_samples"] == 5 * 64 * 48 * 8
+    check_against(img, st, oracle_views(make(), integ, CAMS, 64, 48, 8))
+    assert not biteq(img[0], img[1])
+    scene.close()
+
+
+@pytest.mark.gpu
+def test_views_volpath_per_view_media(gpu):
+    """2. VolPath: one view inside the fog, one with camera_medium -1, in one call (and all inside, all outside) against the oracle built
+    with set_camera_medium"""
+    integ = gpu.VolPathIntegrator(5, 1.0, "spatial")
+    m = scenes.cornell_in_fog().desc().camera_medium
+    assert m >= 0
+    cams = [CAMS[1], CAMS[1], CAMS[0]]
+    scene = gpu.Scene(scenes.cornell_in_fog())
+    for media in ([m, -1, m], [m, m, m], [-1, -1, -1]):
+        img, st = views(integ, scene, cams, 64, 48, 4, media=media)
+        check_against(img, st, oracle_views(scenes.cornell_in_fog(), integ, cams, 64, 48, 4, media=media))
+    img, _ = views(integ, scene, cams, 64, 48, 4, media=[m, -1, m])
+    assert not biteq(img[0], img[1])   # the same camera inside and outside the fog
+    scene.close()
+
+
+@pytest.mark.gpu
+def test_views_match_sequential_renders(gpu):
+    """3. V = 1 == Render with every counter that does not measure time; V = 7 == 7 x (set_camera + Render) at 96 x 80 x 16 whatever
+    samples_per_pass and passes_in_flight are; the scene's own camera is untouched"""
+    b = scenes.dragon_cornell(2000, "glass+metal", env=ENV, mesh_path=MESH2K)
+    scene = gpu.Scene(b)
+    integ = gpu.PathIntegrator(5, 1.0, "spatial")
+    W, H, spp = 96, 80, 16
+    own, own_st = integ.Render(scene, W, H, spp)
+    d = b.desc().camera
+    same = dict(eye=tuple(d.eye), look=tuple(d.look), up=tuple(d.up), fov=d.fov_deg, lens_radius=d.lens_radius, focal_distance=d.focal_distance,
+                orthographic=bool(d.orthographic))
+    one, one_st = views(integ, scene, [same], W, H, spp)
+    assert biteq(one[0], own) and own[..., :3].any()
+    for k in own_st:
+        if k not in TIME_KEYS + HOST_PACED_KEYS:
+            assert one_st[k] == own_st[k], (k, one_st[k], own_st[k])
+    cams = CAMS + [dict(eye=(-1.5, 1.0, 4.0), look=(0.5, 0.0, 0.0), fov=65.0), dict(eye=(0.0, 2.0, 4.9), look=(0.0, -1.0, 0.0), fov=40.0)]
+    assert len(cams) == 7
+    first = None
+    for spass in (0, 3):
+        for pif in (0, 1, 4):
+            img, st = views(integ, scene, cams, W, H, spp, samples_per_pass=spass, passes_in_flight=pif)
+            if first is None:
+                first = img
+            assert biteq(img, first), (spass, pif)
+            if spass == 3:
+                assert st["passes"] == 6 and st["passes_in_flight"] == (pif or 4)
+            # the scene's own camera was neither read nor changed
+            again, again_st = integ.Render(scene, W, H, spp)
+            assert biteq(again, own) and again_st["rays_closest"] == own_st["rays_closest"]
+    check_against(first, views(integ, scene, cams, W, H, spp)[1], sequential(integ, scene, cams, W, H, spp))
+    scene.close()
+
+
+@pytest.mark.gpu
+def test_views_sample_ranges(gpu):
+    """4. two calls over samples [0, 5) and [5, 8) against the oracle's partial renders of each view"""
+    make = lambda: scenes.cornell(sky=True)
+    scene = gpu.Scene(make())
+    integ = gpu.PathIntegrator(5, 1.0, "spatial")
+    cams = CAMS[:3]
+    for lo, hi in ((0, 5), (5, 8)):
+        img, st = views(integ, scene, cams, 64, 48, 8, spp_begin=lo, spp_end=hi)
+        assert st["camera_samples"] == 3 * 64 * 48 * (hi - lo)
+        check_against(img, st, oracle_views(make(), integ, cams, 64, 48, 8, spp_begin=lo, spp_end=hi))
+    scene.close()
+
+
+def dev_i32(a):
+    return torch.from_numpy(np.ascontiguousarray(a, np.int32)).cuda()
+
+
+def device_rays(gpu, cam, W, H, px, py, s, medium=-1):
+    rays, samples = gpu.camera_rays_device(cam, W, H, dev_i32(px), dev_i32(py), dev_i32(s), medium=medium)
+    torch.cuda.synchronize()
+    return rays, samples
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("res", [(256, 256), (1920, 1080)])
+def test_camera_rays_device_golden(gpu, res):
+    """5. the default Cornell camera against the rays recorded from the compiled reference (the goldens of test_camera_rays_bit_exact)"""
+    g = golden(f"camrays_{res[0]}x{res[1]}.npz")
+    q = g["q"]
+    rays, samples = device_rays(gpu, scenes.cornell().desc().camera, res[0], res[1], q[:, 0], q[:, 1], q[:, 2])
+    r = rays.cpu().numpy()
+    assert r.shape == (len(q), 8) and biteq(np.concatenate([r[:, 0:3], r[:, 4:7]], 1), g["od"])
+    assert np.isposinf(r[:, 3]).all() and (r[:, 7].view(np.uint32) == 0).all()
+    assert (samples.cpu().numpy() == np.concatenate([q[:, :3], np.full((len(q), 1), -1)], 1)).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["lens", "ortho"])
+def test_camera_rays_device_lens_and_ortho(gpu, kind):
+    """5. a thin-lens and an orthographic camera (no recorded golden): == the host probe and == the oracle, 4096 seeded triples; the
+    sample records == li_samples"""
+    cam = gpu.camera(**(CAMS[2] if kind == "lens" else CAMS[3]))
+    W, H = 200, 120
+    rng = np.random.default_rng(77)
+    px, py, s = rng.integers(0, W, 4096), rng.integers(0, H, 4096), rng.integers(0, 1024, 4096)
+    rays, samples = device_rays(gpu, cam, W, H, px, py, s, medium=3)
+    r = rays.cpu().numpy()
+    od = np.concatenate([r[:, 0:3], r[:, 4:7]], 1)
+    assert biteq(od, np.concatenate(gpu.camera_rays(cam, W, H, px, py, s), 1))
+    assert biteq(od, np.concatenate(ol.oracle_camera_rays(cam, W, H, px.astype(np.int32), py.astype(np.int32), s.astype(np.int64)), 1))
+    assert np.isposinf(r[:, 3]).all() and (r[:, 7].view(np.uint32) == 0).all()
+    assert torch.equal(samples, gpu.li_samples(dev_i32(px), dev_i32(py), dev_i32(s), 3))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["path", "volpath"])
+def test_views_compose_with_li(gpu, kind):
+    """6. rays and records of camera_rays_device over every pixel and sample of one view, through integrator.Li, summed in sample order in
+    float32 and divided by spp == that view's image from RenderViews"""
+    fog = kind == "volpath"
+    b = scenes.cornell_in_fog() if fog else scenes.dragon_cornell(2000, "glass+metal", env=ENV, mesh_path=MESH2K)
+    m = b.desc().camera_medium if fog else -1
+    integ = gpu.VolPathIntegrator(5, 1.0, "spatial") if fog else gpu.PathIntegrator(5, 1.0, "spatial")
+    scene = gpu.Scene(b)
+    W, H, spp = 64, 48, 8
+    cams = [CAMS[0], CAMS[2], CAMS[1]]
+    media = [-1, m, m] if fog else None
+    img, _ = views(integ, scene, cams, W, H, spp, media=media)
+    v = 1
+    s, py, px = (a.reshape(-1) for a in np.meshgrid(np.arange(spp), np.arange(H), np.arange(W), indexing="ij"))
+    rays, samples = device_rays(gpu, gpu.camera(**cams[v]), W, H, px, py, s, medium=m)
+    L, st = integ.Li(scene, rays, samples, W, H, spp)
+    torch.cuda.synchronize()
+    L = L.cpu().numpy().reshape(spp, H, W, 4)
+    acc = np.zeros((H, W, 3), np.float32)
+    for j in range(spp):
+        acc += L[j, :, :, :3]
+    assert biteq(acc / np.float32(spp), img[v][..., :3]) and acc.any()
+    scene.close()
+
+
+@pytest.mark.gpu
+def test_views_errors_with_a_live_scene(gpu):
+    """7. host memory as output and a medium out of range are GNXR_ERR_INVALID; a textured scene renders its views with Whitted and
+    DirectLighting (against the oracle) and refuses VolPath with the documented GNXR_ERR_UNSUPPORTED; a bad camera-ray record is zeroed
+    and reported; after each refusal a normal Render works and is unchanged"""
+    b = scenes.cornell_in_fog()
+    scene = gpu.Scene(b)
+    integ = gpu.PathIntegrator(5, 1.0, "spatial")
+    W, H, spp = 64, 48, 4
+    ref, _ = integ.Render(scene, W, H, spp)
+    fn = gpu.lib().gnxr_render_views_device
+    p = integ.params(W, H, spp)
+    cams = (gpu.Camera * 2)(gpu.camera(**CAMS[0]), gpu.camera(**CAMS[1]))
+    st = gpu.Stats()
+    host = np.zeros((2, H, W, 4), np.float32)
+    out = torch.full((2, H, W, 4), 7.0, device="cuda")
+
+    def unchanged():
+        torch.cuda.synchronize()
+        assert (out == 7.0).all()
+        again, _ = integ.Render(scene, W, H, spp)
+        assert biteq(again, ref) and ref[..., :3].any()
+
+    assert fn(scene._h, C.byref(p), cams, None, 2, C.c_void_p(host.ctypes.data), None, C.byref(st)) == ERR_INVALID
+    assert "device memory" in gpu.lib().gnxr_last_error().decode()
+    unchanged()
+    for bad in ([0, 1], [-2, 0], [0, 5]):   # cornell_in_fog has one medium
+        with pytest.raises(gpu.GnxrError, match=f"error {ERR_INVALID}"):
+            integ.RenderViews(scene, list(cams), W, H, spp, media=bad, out=out)
+        unchanged()
+    scene.close()
+    # media are refused strictly: a scene without media takes -1 only
+    plain = gpu.Scene(scenes.cornell())
+    with pytest.raises(gpu.GnxrError, match=f"error {ERR_INVALID}"):
+        integ.RenderViews(plain, list(cams), W, H, spp, media=[0, -1], out=out)
+    plain.close()
+
+    tb = lambda: scenes.textured_cornell(TEX)
+    tscene = gpu.Scene(tb())
+    tref, _ = gpu.WhittedIntegrator(5).Render(tscene, W, H, spp)
+    tcams = [CAMS[0], CAMS[2], CAMS[3]]
+    for it in (gpu.WhittedIntegrator(5), gpu.DirectLightingIntegrator("all", 5), gpu.PathIntegrator(5, 1.0, "spatial")):
+        img, vst = views(it, tscene, tcams, W, H, spp)
+        check_against(img, vst, oracle_views(tb(), it, tcams, W, H, spp))
+    with pytest.raises(gpu.GnxrError, match=f"error {ERR_UNSUPPORTED}"):
+        gpu.VolPathIntegrator(5).RenderViews(tscene, [gpu.camera(**c) for c in tcams], W, H, spp, out=torch.full((3, H, W, 4), 7.0, device="cuda"))
+    again, _ = gpu.WhittedIntegrator(5).Render(tscene, W, H, spp)
+    assert biteq(again, tref) and tref[..., :3].any()
+    tscene.close()
+
+    # camera rays: a record outside the image and one with s < 0 are zeroed, the others finished, the call reports the first
+    px, py, s = np.arange(8) % W, np.arange(8) % H, np.arange(8)
+    good_r, good_s = device_rays(gpu, gpu.camera(), W, H, px, py, s)
+    px2, s2 = px.copy(), s.copy()
+    px2[2], s2[5] = W, -1
+    with pytest.raises(gpu.GnxrError, match="record 2 "):
+        gpu.camera_rays_device(gpu.camera(), W, H, dev_i32(px2), dev_i32(py), dev_i32(s2))
+    fnr = gpu.lib().gnxr_camera_rays_device
+    rays = torch.full((8, 8), 7.0, device="cuda")
+    samples = torch.full((8, 4), 7, dtype=torch.int32, device="cuda")
+    a, c, e = dev_i32(px2), dev_i32(py), dev_i32(s2)
+    vp = lambda t: C.c_void_p(t.data_ptr())
+    cam = gpu.camera()
+    assert fnr(C.byref(cam), -1, W, H, vp(a), vp(c), vp(e), 8, vp(rays), vp(samples), None) == ERR_INVALID
+    torch.cuda.synchronize()
+    keep = np.ones(8, bool)
+    keep[[2, 5]] = False
+    assert (rays.cpu().numpy()[~keep].view(np.uint32) == 0).all() and (samples.cpu().numpy()[~keep] == 0).all()
+    assert biteq(rays.cpu().numpy()[keep], good_r.cpu().numpy()[keep]) and (samples.cpu().numpy()[keep] == good_s.cpu().numpy()[keep]).all()
+    host_px = np.ascontiguousarray(px2, np.int32)
+    assert fnr(C.byref(cam), -1, W, H, C.c_void_p(host_px.ctypes.data), vp(c), vp(e), 8, vp(rays), vp(samples), None) == ERR_INVALID
+    assert "device memory" in gpu.lib().gnxr_last_error().decode()
+
+
+@pytest.mark.gpu
+def test_views_stream_order(gpu):
+    """8. two RenderViews calls on one non-default stream into the same `out`, each followed by a clone on that stream"""
+    b = scenes.cornell(sky=True)
+    scene = gpu.Scene(b)
+    integ = gpu.PathIntegrator(5, 1.0, "spatial")
+    W, H, spp = 64, 48, 4
+    A, B = CAMS[:2], CAMS[2:4]
+    ea, _ = views(integ, scene, A, W, H, spp)
+    eb, _ = views(integ, scene, B, W, H, spp)
+    assert not biteq(ea, eb)
+    stream = torch.cuda.Stream()
+    out = torch.zeros((2, H, W, 4), device="cuda")
+    stream.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(stream):
+        integ.RenderViews(scene, [gpu.camera(**c) for c in A], W, H, spp, out=out, stream=stream)
+        ca = out.clone()
+        integ.RenderViews(scene, [gpu.camera(**c) for c in B], W, H, spp, out=out)   # torch's current stream is `stream`
+        cb = out.clone()
+    stream.synchronize()
+    assert biteq(ca.cpu().numpy(), ea) and biteq(cb.cpu().numpy(), eb)
+    scene.close()
