@@ -1712,11 +1712,14 @@ int gnxr_render(gnxr_scene *s, const gnxr_render_params *p, float *rgba_out, gnx
     size_t npx = (size_t)p->width * p->height;
     std::lock_guard<std::recursive_mutex> lock(s->render_mutex);   // s->out is shared by every gnxr_render on this handle
     if (int brc = s->bind()) return brc;
+    const bool grew = !(s->out.p && npx <= s->out.n);
     int rc = s->out.alloc(npx);
     if (rc) return rc;
     HIP_TRY(hipMemset(s->out.p, 0, npx * sizeof(float4)));
     rc = render_sharded(s, p, s->out.p, nullptr, stats);
-    if (rc) return rc;
+    // a refused call (render_one checks its parameters and plan before it allocates path state) leaves device memory as it found it:
+    // the image this call grew for it goes too
+    if (rc) { if (grew) s->out.release(); return rc; }
     // copy back only the rows this shard owns
     int sc = p->shard_count > 0 ? p->shard_count : 1, sr = p->shard_rows > 0 ? p->shard_rows : 1;
     if (sc == 1) {
