@@ -1,0 +1,203 @@
+// api_scene.hip.h -- gnxr_scene: the device tables of a scene, its per-render state and its light-selection table.
+// Part of api.hip's translation unit (after api_common.hip.h).
+#pragma once
+
+// The per-render state of a handle: path slots, queues and scratch, grown on demand by reserve() to what a launch plan needs (RenderPlan
+// and the member functions: api_render.hip.h) and kept for the next render.
+struct RenderPlan;
+struct RenderState {
+    DevBuf<float4> rec[kRecGroups], mis_Y;   // the record groups of the path slots (PathArrays, kernels.hip.h)
+    static void record_ptrs(DevBuf<float4> *b, float4 *g[kRecGroups]) { for (int i = 0; i < kRecGroups; ++i) g[i] = b[i].p; }
+    DevBuf<float4> L, accum;
+    DevBuf<int> hit, queue_a, queue_b, queue_nee, queue_c0, queue_c1, queue_c2, queue_c3;
+    DevBuf<unsigned char> pflags, pclass;
+    DevBuf<unsigned int> nee_vis;
+    DevBuf<unsigned int> tile_counts;
+    DevBuf<int> trace_spill;   // global part of k_trace's per-lane traversal stacks
+    DevBuf<float4> vol_n1, vol_f, vol_Li, vol_Tr, vol_Ld, vol_mres;   // VolPath light-estimate records (vol_kernel.hip.h)
+    DevBuf<int4> vol_vs;
+    DevBuf<unsigned char> vol_state;
+    // VolPath packing (k_vol_pack): the second set of the state arrays, the original slot of every path, the renumbering map and the results
+    DevBuf<float4> vol_alt[kVolPackF4], vol_alt_rec[kRecGroups], vol_Lout;
+    DevBuf<unsigned char> vol_alt_state;
+    DevBuf<int> vol_orig, vol_alt_orig, vol_newslot;
+    DevBuf<float4> wh_o, wh_d, wh_L, wh_w;   // Whitted recursion frames (whitted_kernel.hip.h)
+    DevBuf<float4> wh_rxo, wh_rxd, wh_ryo, wh_ryd;   // their ray differentials (scenes with image textures)
+    DevBuf<float> wh_pdf;
+    DevBuf<int> wh_rec;
+    DevBuf<DCamera> view_cams;   // gnxr_render_views_device: the DCamera record of every view
+
+    int reserve(const RenderPlan &pl);
+    static unsigned long long state_bytes(const RenderPlan &pl);
+    // the kernels' views of the arrays
+    PathArrays path_arrays();
+    VolArrays vol_arrays();
+    WhittedArrays whitted_arrays(const RenderPlan &pl, int n_lights);
+    VolPackSet pack_set(bool alt);
+};
+
+struct gnxr_scene {
+    CompiledScene cs;
+    // device tables
+    DevBuf<DNode> nodes;
+    DevBuf<DNode4> nodes4;
+    DevBuf<DTri> tris;
+    DevBuf<float> leaf_boxes;
+    DevBuf<uint8_t> tri_class;
+    DevBuf<DSphere> spheres;
+    DevBuf<DMaterial> materials, materials_single;
+    DevBuf<DTexture> textures;
+    DevBuf<float> tex_texels, ewa_lut, tri_uv, tri_n, tri_s;
+    DevBuf<DLight> lights;
+    DevBuf<int32_t> infinite;
+    DevBuf<uint16_t> perms;
+    DevBuf<int32_t> primes, prime_sums;
+    DevBuf<uint32_t> prime_magic;
+    DevBuf<float> env_texels4, env_cond_func, env_cond_cdf, env_cond_int, env_marg_func, env_marg_cdf;
+    DevBuf<uint16_t> env_marg_guide, env_cond_guide;
+    DevBuf<float> grid_table;
+    DevBuf<DMedium> dmedia;
+    DevBuf<float> grid_density;
+    DevBuf<int32_t> tri_media;
+    DLightGrid grid;
+    int grid_strategy = -1;
+    RenderState st;            // per-render state (grown on demand)
+    DevBuf<float4> out;        // gnxr_render: the image on the device
+    DevBuf<Counters> counters;
+    Counters *h_counters = nullptr;  // pinned
+    // the device-driven PathIntegrator loop: lagging copies of the counters (pinned ring, one event per slot) -- the host reads them
+    // without ever waiting for the iteration it has just enqueued
+    // k_shade runs one kernel per material class; the classes are independent, so they go to different streams and fill each other's ends
+    hipStream_t aux_stream[2] = {nullptr, nullptr};
+    hipEvent_t ev_fork = nullptr, ev_join[2] = {nullptr, nullptr};
+    static constexpr int kRing = 8;
+    Counters *h_ring = nullptr;      // pinned, kRing entries
+    hipEvent_t ring_ev[kRing] = {};
+    int stack_size = 32;
+    bool wide_ok = true;   // 4-wide traversal usable (leaf sizes / triangle count fit the reference encoding)
+    std::recursive_mutex render_mutex;   // one render in flight per handle; gnxr_render holds it around its staging buffer too
+    int device = 0;                      // the HIP device the tables live on
+    std::vector<std::unique_ptr<gnxr_scene>> replicas;   // the same scene on the other devices of gnxr_init_devices (element 0 of that list is this one)
+    DevBuf<float4> shard_out;            // a replica's full-size output plane; its rows are peer-copied into the primary's image
+    void *h_stage = nullptr;             // pinned: a replica's rows on their way to the primary when the two devices have no peer access
+    size_t h_stage_bytes = 0;
+    // gnxr_scene_update_vertices: the refit's tables (CompiledScene::corner_vertex / node_parent / node4_src, uploaded at the first update),
+    // the arrival counters of k_refit_fit, the staged positions and the emissive-vertex flag
+    DevBuf<int32_t> upd_corner, upd_parent, upd_node4_src;
+    DevBuf<unsigned int> upd_arrived;
+    DevBuf<float> upd_xyz;
+    DevBuf<int> upd_flag;
+    // gnxr_render_views_device: the host copy of st.view_cams (what the stream-ordered upload reads; both only grow)
+    std::vector<DCamera> h_view_cams;
+    bool host_bvh_stale = false;         // after an update cs.nodes / nodes4 / tris / leaf_boxes lag the device until sync_host_bvh()
+
+    int bind() const { HIP_TRY(hipSetDevice(device)); return GNXR_OK; }
+    // the host copies of the geometry tables, downloaded on demand after gnxr_scene_update_vertices (only readers pay for them)
+    int sync_host_bvh() {
+        if (!host_bvh_stale) return GNXR_OK;
+        if (int rc = bind()) return rc;
+        HIP_TRY(hipMemcpy(cs.nodes.data(), nodes.p, cs.nodes.size() * sizeof(DNode), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(cs.nodes4.data(), nodes4.p, cs.nodes4.size() * sizeof(DNode4), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(cs.tris.data(), tris.p, cs.tris.size() * sizeof(DTri), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(cs.leaf_boxes.data(), leaf_boxes.p, cs.leaf_boxes.size() * sizeof(float), hipMemcpyDeviceToHost));
+        host_bvh_stale = false;
+        return GNXR_OK;
+    }
+    ~gnxr_scene() {
+        if (h_counters) (void)hipHostFree(h_counters);
+        if (h_ring) (void)hipHostFree(h_ring);
+        if (h_stage) (void)hipHostFree(h_stage);
+        for (hipEvent_t e : ring_ev) if (e) (void)hipEventDestroy(e);
+        for (hipStream_t a : aux_stream) if (a) (void)hipStreamDestroy(a);
+        if (ev_fork) (void)hipEventDestroy(ev_fork);
+        for (hipEvent_t e : ev_join) if (e) (void)hipEventDestroy(e);
+    }
+
+    // the lights and the environment map: what Sample_Li / Pdf_Li / Le read, without the selection table (grid, grid_table stay zero).
+    // Nothing here changes after the scene is created, except the world radius that gnxr_scene_update_vertices refits (cs.env, distant lights).
+    DLightTables light_tables_static() const {
+        DLightTables lt = {};
+        lt.lights = lights.p;
+        lt.n_lights = (int)cs.desc_lights.size();
+        lt.infinite = infinite.p;
+        lt.n_infinite = (int)cs.infinite_lights.size();
+        lt.has_env = cs.has_env ? 1 : 0;
+        lt.env = cs.env;
+        lt.env_texels = reinterpret_cast<const float4 *>(env_texels4.p);
+        lt.env_cond_func = env_cond_func.p; lt.env_cond_cdf = env_cond_cdf.p; lt.env_cond_int = env_cond_int.p;
+        lt.env_marg_func = env_marg_func.p; lt.env_marg_cdf = env_marg_cdf.p;
+        lt.env_marg_guide = env_marg_guide.p; lt.env_cond_guide = env_cond_guide.p;
+        return lt;
+    }
+    DScene device_scene(int W, int H) {
+        DScene d;
+        d.nodes = reinterpret_cast<const float4 *>(nodes.p);
+        d.nodes4 = reinterpret_cast<const float4 *>(nodes4.p);
+        d.root4 = cs.root4;
+        d.tris = tris.p;
+        d.leaf_box = reinterpret_cast<const float4 *>(leaf_boxes.p);
+        d.tri_class = tri_class.p;
+        d.leaf1_from_verts = (cs.leaf1_from_verts && !Knobs::leaf_box_table()) ? 1 : 0;
+        d.spheres = spheres.p;
+        d.n_spheres = cs.n_spheres;
+        d.materials = materials.p + 1;   // [0] carries the texture tables
+        d.escape_class = 0;              // render_one (RenderPlan::escape_queue): 3 for the PathIntegrator in a scene without image-textured materials
+        d.lt = light_tables_static();
+        d.lt.grid = grid;
+        d.lt.grid_table = grid_table.p;
+        d.st.perms = perms.p; d.st.primes = primes.p; d.st.prime_sums = prime_sums.p; d.st.prime_magic = prime_magic.p;
+        d.st.h = make_halton(W, H);
+        return d;
+    }
+    DMediaTables media_tables() {
+        DMediaTables m;
+        m.media = dmedia.p;
+        m.density = grid_density.p;
+        m.tri_media = cs.tri_media.empty() ? nullptr : reinterpret_cast<const int2 *>(tri_media.p);
+        return m;
+    }
+    // light-selection table (core/LightDistribution.cpp).  The spatial strategy's dense voxel table is filled on the device
+    // (k_light_grid, ~1 ms instead of ~1 s of host threads for 64^3 voxels); GNXR_HOST_LIGHT_GRID=1 forces the host
+    // restatement, which produces the same bits (tests/test_gpu_parity.py::test_light_grid_device_equals_host).
+    int ensure_grid(int strategy, bool force_host = false) {
+        if (grid_strategy == strategy && !force_host) return GNXR_OK;
+        const int nl = (int)cs.desc_lights.size();
+        const bool on_device = strategy == GNXR_LIGHTS_SPATIAL && nl >= 2 && !force_host && !Knobs::host_light_grid();
+        std::vector<float> table;
+        build_light_grid(cs, strategy, &grid, &table, /*layout_only=*/true);
+        {   // the dense spatial table holds nvox^3 x (2 lights + 1) floats: refuse what cannot fit instead of failing inside an allocation
+            const unsigned long long bytes = (unsigned long long)grid.nvox[0] * grid.nvox[1] * grid.nvox[2] * (unsigned long long)grid.stride * sizeof(float);
+            size_t free_b = 0, total_b = 0;
+            unsigned long long limit = 64ull << 30;
+            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) limit = std::min<unsigned long long>(limit, free_b / 2);
+            if (bytes > limit) {
+                set_error("spatial light distribution: %d x %d x %d voxels x %d lights need %.1f GB (limit %.1f GB); use GNXR_LIGHTS_POWER or GNXR_LIGHTS_UNIFORM for this many lights",
+                          grid.nvox[0], grid.nvox[1], grid.nvox[2], nl, bytes * 1e-9, limit * 1e-9);
+                return GNXR_ERR_UNSUPPORTED;
+            }
+        }
+        if (!on_device) build_light_grid(cs, strategy, &grid, &table, false);
+        int rc;
+        if (on_device) {
+            const size_t nv = (size_t)grid.nvox[0] * grid.nvox[1] * grid.nvox[2];
+            if ((rc = grid_table.alloc(nv * grid.stride)) != GNXR_OK) return rc;
+            HIP_TRY(hipMemset(grid_table.p, 0, nv * grid.stride * sizeof(float)));   // padded records: the pad floats are zero, as in the host-built table
+            float ri[5 * 128];
+            light_grid_probes(cs, ri);
+            DevBuf<float> d_ri;
+            if ((rc = d_ri.upload(ri, 5 * 128)) != GNXR_OK) return rc;
+            DLightTables lt = device_scene(1, 1).lt;
+            bool area_only = true;
+            for (const gnxr_light &l : cs.desc_lights) if (l.type != GNXR_LIGHT_AREA_TRI) area_only = false;
+            const int blocks = (int)std::min<size_t>((nv + kBlock - 1) / kBlock, (size_t)g_num_cus * 8);
+            if (nl > kGridMaxLights) {   // mesh lights: any number of lights, the table is the scratch space
+                if (area_only) hipLaunchKernelGGL((k_light_grid_any<LT_AREA>), dim3(blocks), dim3(kBlock), 0, 0, lt, grid, (const float *)d_ri.p, grid_table.p);
+                else hipLaunchKernelGGL((k_light_grid_any<LT_ALL>), dim3(blocks), dim3(kBlock), 0, 0, lt, grid, (const float *)d_ri.p, grid_table.p);
+            } else if (area_only) hipLaunchKernelGGL((k_light_grid<LT_AREA>), dim3(blocks), dim3(kBlock), 0, 0, lt, grid, (const float *)d_ri.p, grid_table.p);
+            else hipLaunchKernelGGL((k_light_grid<LT_ALL>), dim3(blocks), dim3(kBlock), 0, 0, lt, grid, (const float *)d_ri.p, grid_table.p);
+            HIP_TRY(hipDeviceSynchronize());
+        } else if ((rc = grid_table.upload(table)) != GNXR_OK) return rc;
+        grid_strategy = force_host ? -1 : strategy;
+        return GNXR_OK;
+    }
+};

@@ -98,7 +98,7 @@ struct CompiledScene {
     std::vector<gnxr_light> desc_lights;
 };
 
-// HLBVH (GNXR_BVH_HLBVH, BVHAccel.cpp:369-626) is built by the caller's device stage (api.hip + hlbvh_build.hip.h): Morton codes, radix
+// HLBVH (GNXR_BVH_HLBVH, BVHAccel.cpp:369-626) is built by the caller's device stage (api_hlbvh.hip.h + hlbvh_build.hip.h): Morton codes, radix
 // sort, one LBVH per treelet and the SAH over the treelet roots.  It returns the build tree -- leaves index the sorted primitive array
 // (`first`, `n`), interior nodes carry their two children and the split axis -- its root, and the sorted primitive order.
 struct HlbvhNode { float b[6]; int32_t child[2]; int32_t axis, first, n; };   // bounds lo.xyz hi.xyz

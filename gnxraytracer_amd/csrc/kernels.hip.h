@@ -85,7 +85,7 @@ struct Counters {
     unsigned long long media_cont;                  // segments k_vol_media left at its step cap (each is traced and handed to it once more)
     unsigned long long retests;                     // k_trace<COUNT, WIDE>: leaf boxes re-tested against a shrunken tMax (32 B each)
     unsigned long long nodes_global;                // k_trace4<COUNT>: node visits served from global memory (the others come from the LDS copy of the top of the tree)
-    // ---- the device-driven PathIntegrator loop (api.hip): the host never waits for these, it reads lagging copies
+    // ---- the device-driven PathIntegrator loop (run_path_loop, api_render.hip.h): the host never waits for these, it reads lagging copies
     unsigned int n_queue;                           // entries of the trace queue after k_queue_merge put a new sub-pass in
     unsigned int iter;                              // stamp: the loop iteration whose shade stage produced the counts above
     unsigned int region_lb[kMaxRegions + 1];        // position in the survivors' queue of the first slot of each state region (k_loop_tail)

@@ -1,7 +1,7 @@
 """The launch plans at the sizes the benchmark and callers really use (run with -m gpu on an MI355X).
 
 The other GPU modules pin the path loop at 48 x 40 or render two of the 1024 samples at 1920 x 1080: one sub-pass, one region, no reuse.
-bench.py's call gets another plan (csrc/api.hip, the block that starts at `int k = p.samples_per_pass`): 32 sub-passes of 32 spp, four alive
+bench.py's call gets another plan (csrc/api_render.hip.h, RenderPlan::size_passes): 32 sub-passes of 32 spp, four alive
 at once in regions of one 265 420 800-slot state, every region reused eight times, queues of different sub-passes merged, lagging counter
 copies, ~130 k compaction tiles.  This module runs those plans -- and full-size batches through the device-memory entry points -- and
 compares them bit for bit (image words and both ray counts; no tolerance anywhere) in two legs:
@@ -36,8 +36,8 @@ pytestmark = pytest.mark.gpu
 W, H = 1920, 1080
 PIX = W * H
 ERR_INVALID, ERR_UNSUPPORTED = -1, -4
-SLOT_BYTES = 238            # path state per slot (api.hip's estimate; the plan rules below are stated in it)
-STATE_CAP = 150e9           # api.hip never grants more path state than this
+SLOT_BYTES = 238            # path state per slot (kSlotBytesEstimate, csrc/api_render.hip.h; the plan rules below are stated in it)
+STATE_CAP = 150e9           # kStateCapBytes: size_passes never grants more path state than this
 COUNT_KEYS = ("rays_closest", "rays_any", "camera_samples")   # (loop_iterations / kernel_launches depend on when lagging counters arrive)
 RAY_KEYS = ("rays_closest", "rays_any")                       # what the oracle counts
 # hipMalloc hands out device memory in 2 MiB units on this runtime: a refused call may move free memory by bookkeeping of that size, not by

@@ -552,7 +552,7 @@ def test_randomised_sweep_against_oracle(gpu):
 
 @pytest.mark.parametrize("name", ["cornell", "mesh2k"])
 def test_pipelined_passes_equal_one_pass(gpu, name):
-    """The device-driven path loop (csrc/api.hip: up to eight sub-passes alive at once in regions of the state arrays, queue counts on the
+    """The device-driven path loop (run_path_loop in csrc/api_render.hip.h: up to eight sub-passes alive at once in regions of the state arrays, queue counts on the
     device, k_queue_merge / k_loop_tail) against the same samples rendered as ONE pass and against the oracle: images and ray counts bit for
     bit, for sub-pass sizes that divide the sample range, that do not, for every number of sub-passes in flight, and for a sample sub-range."""
     b = scenes.cornell() if name == "cornell" else _scene("mesh2k")

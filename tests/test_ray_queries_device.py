@@ -86,7 +86,7 @@ def chain_scene(gx, n=36):
 
 
 def lds_stack_levels(spheres, blocks_per_cu=5):
-    """LDS levels of k_trace4's traversal stack (api.hip trace_launch; the default 5 blocks per CU): the deeper levels spill"""
+    """LDS levels of k_trace4's traversal stack (trace_launch in csrc/api_render.hip.h; the default 5 blocks per CU): the deeper levels spill"""
     fixed = (11 + (1 if spheres else 0)) * 256 * 4 + 64 * 128 + 128   # ray records, top-of-tree cache, order table
     return min(64, max(2, ((160 * 1024) // blocks_per_cu - 1024 - fixed) // (256 * 4)))
 

@@ -21,7 +21,7 @@ ENV = os.path.join(GOLDEN, "env_100x50.hdr")
 TEX = os.path.join(GOLDEN, "tex_smile_96x80.hdr")
 ERR_INVALID, ERR_NO_DEVICE, ERR_UNSUPPORTED = -1, -2, -4
 TIME_KEYS = ("seconds_render", "seconds_trace", "seconds_total", "seconds_closest", "seconds_nee", "seconds_shade")
-# The device-driven path loop runs ahead of lagging copies of the device counters (api.hip): how many turns the host takes, and so how
+# The device-driven path loop runs ahead of lagging copies of the device counters (run_path_loop, csrc/api_render.hip.h): how many turns the host takes, and so how
 # many launches it makes, before it sees that a sub-pass has ended depends on when those copies arrive.  These two measure time as well.
 HOST_PACED_KEYS = ("loop_iterations", "kernel_launches")
 
