@@ -245,8 +245,14 @@ int RenderState::reserve(const RenderPlan &pl) {
     // global part of k_trace's traversal stacks (the deepest walk either BVH layout can need), sized for a full grid
     if ((rc = trace_spill.alloc((size_t)g_num_cus * g_trace_blocks_per_cu * kBlock * (size_t)pl.spill_entries * 2)) != GNXR_OK) return rc;   // (x 2: k_trace4d keeps two columns per lane)
     if (!pl.caller_rays && (rc = accum.alloc(pl.npix)) != GNXR_OK) return rc;
-    const int max_tiles = (int)((cap + kCompactTile - 1) / kCompactTile);
-    if ((rc = tile_counts.alloc((size_t)5 * max_tiles)) != GNXR_OK) return rc;
+    const size_t max_tiles = (cap + kCompactTile - 1) / kCompactTile;
+    if (tile_desc.n < kCompactMaxOut * max_tiles || !tile_desc.p) {   // fresh memory: every descriptor "not ready" (tag 0 belongs to no compaction)
+        if ((rc = tile_desc.alloc(kCompactMaxOut * max_tiles)) != GNXR_OK) return rc;
+        HIP_TRY(hipMemset(tile_desc.p, 0, tile_desc.n * sizeof(unsigned long long)));
+        HIP_TRY(hipDeviceSynchronize());   // the render's stream may not wait for the null stream: the clear is complete before any compaction is queued
+        compact_seq = 0;
+    }
+    if ((rc = compact_ticket.alloc(2)) != GNXR_OK) return rc;
     if (pl.n_views > 0 && (rc = view_cams.alloc((size_t)pl.n_views)) != GNXR_OK) return rc;
     return GNXR_OK;
 }
@@ -255,7 +261,9 @@ int RenderState::reserve(const RenderPlan &pl) {
 // per-path bytes.  This is the stats' own count; it is NOT the 238 B estimate (kSlotBytesEstimate) that the in-flight rule plans with.
 unsigned long long RenderState::state_bytes(const RenderPlan &pl) {
     const unsigned long long per_slot = (2ull * kRecGroups + 2) * sizeof(float4) + 8ull * sizeof(int) + 2 + sizeof(unsigned int);   // five record groups + mis_Y + L, hit + seven queues, pflags + pclass, nee_vis
-    return (unsigned long long)pl.cap * per_slot + (pl.volpath ? (unsigned long long)pl.cap * (6ull * sizeof(float4) + sizeof(int4) + 1) : 0ull);
+    const unsigned long long tiles = ((unsigned long long)pl.cap + kCompactTile - 1) / kCompactTile;   // + the compaction's tile descriptors
+    return (unsigned long long)pl.cap * per_slot + tiles * kCompactMaxOut * sizeof(unsigned long long) +
+           (pl.volpath ? (unsigned long long)pl.cap * (6ull * sizeof(float4) + sizeof(int4) + 1) : 0ull);
 }
 
 PathArrays RenderState::path_arrays() {
@@ -400,34 +408,39 @@ void RenderRun::launch_trace(TraceWork w, int n_sh, int n_mis, bool count_rays) 
     ++launches;
 }
 
-// stream compaction (compact_kernel.hip.h): count -> scan -> scatter, no global atomics
+// stream compaction (compact_kernel.hip.h): one launch, one pass over the queue
 // (n_dev: the item count lives on the device; `nin` then bounds it and sizes the launch)
 void RenderRun::compact(int mode, const int *qin, int nin, const unsigned char *keys, int nout, int nscatter, unsigned int *totals, int *o0, int *o1, int *o2, int *o3, int split,
                         const unsigned *n_dev) {
-    int tiles = (nin + kCompactTile - 1) / kCompactTile;
-    int g = std::max(1, std::min(tiles, g_num_cus * g_grid_bpc));
-    unsigned int *tc = st.tile_counts.p;
-    // HITCLASS: the class of the triangle a path hit, looked up and left in `keys` for the scatter pass
+    const int tiles = (nin + kCompactTile - 1) / kCompactTile;
+    const int g = std::max(1, std::min(tiles, g_num_cus * kCompactBlocksPerCu));
+    // every compaction of the handle has a sequence number of its own; when the 30 bits of a descriptor's tag run out, start over on cleared descriptors
+    if (st.compact_seq >= (1u << 30) - 1u) {
+        (void)hipMemsetAsync(st.tile_desc.p, 0, st.tile_desc.n * sizeof(unsigned long long), stream);
+        st.compact_seq = 0;
+    }
+    const unsigned seq = ++st.compact_seq;
+    const CompactScratch cs{st.tile_desc.p, tiles, st.compact_ticket.p + (seq & 1u), st.compact_ticket.p + ((seq + 1u) & 1u), seq};
+    // HITCLASS: the class of the triangle a path hit is looked up from `hit`; `keys` (pclass) holds it for misses and sphere hits
     const bool hitclass = mode == COMPACT_HITCLASS;
     const int *hit = hitclass ? (const int *)st.hit.p : nullptr;
     const unsigned char *cls = hitclass ? (const unsigned char *)s->tri_class.p : nullptr;
-    unsigned char *keys_out = hitclass ? st.pclass.p : nullptr;
-#define GX_COUNT(M, N, SPLIT) hipLaunchKernelGGL((k_compact_count<M, N>), dim3(g), dim3(kCompactBlock), 0, stream, qin, nin, keys, tc, tiles, hit, cls, keys_out, SPLIT, n_dev)
-#define GX_SCATTER(M, N, O3) hipLaunchKernelGGL((k_compact_scatter<M, N>), dim3(g), dim3(kCompactBlock), 0, stream, qin, nin, keys, (const unsigned int *)tc, tiles, o0, o1, o2, O3, n_dev)
-    // FLAGS with a fifth count: the paths that continue AND live in the lower half of the state arrays (slot < split)
-    if (mode == COMPACT_FLAGS && nout == 5) GX_COUNT(COMPACT_FLAGS, 5, split);
-    else if (mode == COMPACT_FLAGS) GX_COUNT(COMPACT_FLAGS, 4, 0);
-    else if (hitclass) { if (nout == 4) GX_COUNT(COMPACT_HITCLASS, 4, 0); else GX_COUNT(COMPACT_HITCLASS, 3, 0); }
-    else if (nout == 4) GX_COUNT(COMPACT_CLASS, 4, 0);
-    else GX_COUNT(COMPACT_CLASS, 3, 0);
-    hipLaunchKernelGGL(k_compact_scan, dim3(nout), dim3(1024), 0, stream, tc, tiles, totals, n_dev);
-    if (mode == COMPACT_FLAGS && nscatter == 3) GX_SCATTER(COMPACT_FLAGS, 3, (int *)nullptr);
-    else if (mode == COMPACT_FLAGS) GX_SCATTER(COMPACT_FLAGS, 2, (int *)nullptr);
-    else if (nscatter == 4) GX_SCATTER(COMPACT_CLASS, 4, o3);
-    else GX_SCATTER(COMPACT_CLASS, 3, (int *)nullptr);
-#undef GX_SCATTER
-#undef GX_COUNT
-    launches += 3;
+#define GX_COMPACT(M, N, NS) hipLaunchKernelGGL((k_compact<M, N, NS>), dim3(g), dim3(kCompactBlock), 0, stream, qin, nin, keys, cs, totals, o0, o1, o2, o3, hit, cls, split, n_dev, dctr)
+    if (mode == COMPACT_FLAGS) {
+        // a fifth count: the paths that continue AND live in the lower half of the state arrays (slot < split)
+        if (nout == 5) { if (nscatter == 3) GX_COMPACT(COMPACT_FLAGS, 5, 3); else GX_COMPACT(COMPACT_FLAGS, 5, 2); }
+        else { if (nscatter == 3) GX_COMPACT(COMPACT_FLAGS, 4, 3); else GX_COMPACT(COMPACT_FLAGS, 4, 2); }
+    } else if (hitclass) { if (nout == 4) GX_COMPACT(COMPACT_HITCLASS, 4, 4); else GX_COMPACT(COMPACT_HITCLASS, 3, 3); }
+    else if (nout == 4) GX_COMPACT(COMPACT_CLASS, 4, 4);
+    else GX_COMPACT(COMPACT_CLASS, 3, 3);
+#undef GX_COMPACT
+    launches += 1;
+}
+// a look-back of k_compact gave up (Counters::compact_stall): the queues of this render are incomplete
+static int compact_stalled(const Counters &c) {
+    if (!c.compact_stall) return GNXR_OK;
+    set_error("queue compaction: a tile waited for its predecessors beyond the poll limit (k_compact); the render was abandoned");
+    return GNXR_ERR_RUNTIME;
 }
 
 // PathIntegrator::Li at the vertices the last trace found: class binning, one k_shade per class, queue compaction.  What they spawned is
@@ -591,7 +604,7 @@ static int run_path_loop(RenderRun &run) {
                 const int slot = ((j % gnxr_scene::kRing) + gnxr_scene::kRing) % gnxr_scene::kRing;
                 if (j < 0 || ring_iter[slot] != j) continue;
                 const hipError_t q = hipEventQuery(s->ring_ev[slot]);
-                if (q == hipSuccess) { seen = s->h_ring[slot]; newest_seen = j; break; }
+                if (q == hipSuccess) { seen = s->h_ring[slot]; newest_seen = j; if (int rc = compact_stalled(seen)) return rc; break; }
                 if (q != hipErrorNotReady) { set_error("HIP runtime error in the path loop: hipEventQuery: %s", hipGetErrorString(q)); return hip_status(q); }
                 (void)hipGetLastError();   // "not ready" is reported as an error: clear that one, and nothing else
             }
@@ -719,6 +732,7 @@ static int run_whitted_pass(RenderRun &run, long long u0, int kk) {
         if (run.timing) run.timer.end(stream);
         HIP_TRY(hipMemcpyAsync(run.s->h_counters, dctr, sizeof(Counters), hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
+        if (int rc = compact_stalled(*run.s->h_counters)) return rc;
         n = (int)run.s->h_counters->q_next;
         n_shp = (int)run.s->h_counters->q_nee;
         n_cl = (int)run.s->h_counters->q_shadow;   // count of pflags bit2: paths with a closest-hit ray to trace
@@ -755,6 +769,7 @@ static int run_volpath_pass(RenderRun &run, long long u0, int kk) {
         run.compact(COMPACT_FLAGS, nullptr, n, st.pflags.p, 4, 2, &dctr->q_next, q_cur, st.queue_nee.p, nullptr);
         HIP_TRY(hipMemcpyAsync(s->h_counters, dctr, sizeof(Counters), hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
+        if (int rc = compact_stalled(*s->h_counters)) return rc;
         n_media = (int)s->h_counters->q_nee;
         q_media = st.queue_nee.p;
     }
@@ -803,6 +818,7 @@ static int run_volpath_pass(RenderRun &run, long long u0, int kk) {
         if (run.timing) run.timer.end(stream);
         HIP_TRY(hipMemcpyAsync(s->h_counters, dctr, sizeof(Counters), hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
+        if (int rc = compact_stalled(*s->h_counters)) return rc;
         n = (int)s->h_counters->q_next;
         n_media = (int)s->h_counters->q_nee;
         q_media = st.queue_nee.p;
@@ -935,6 +951,7 @@ static int render_one(gnxr_scene *s, const gnxr_render_params *pin, void *d_rgba
     if (views) HIP_TRY(hipMemcpyAsync(s->st.view_cams.p, s->h_view_cams.data(), (size_t)views->n_views * sizeof(DCamera), hipMemcpyHostToDevice, stream));
     if (!src) HIP_TRY(hipMemsetAsync(s->st.accum.p, 0, sizeof(float4) * r.npix, stream));
     HIP_TRY(hipMemsetAsync(run.dctr, 0, sizeof(Counters), stream));
+    HIP_TRY(hipMemsetAsync(s->st.compact_ticket.p, 0, 2 * sizeof(unsigned int), stream));   // once per render; from pass to pass k_compact zeroes its successor's counter
     struct EventPair {   // destroyed on every exit path
         hipEvent_t a = nullptr, b = nullptr;
         ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
@@ -952,6 +969,7 @@ static int render_one(gnxr_scene *s, const gnxr_render_params *pin, void *d_rgba
     HIP_TRY(hipStreamSynchronize(stream));
     HIP_TRY(hipGetLastError());
     if (run.timing) run.timer.collect();
+    if ((rc = compact_stalled(*s->h_counters)) != GNXR_OK) return rc;
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
     if (stats) fill_stats(run, ms * 1e-3, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(), stats);

@@ -12,7 +12,11 @@ struct RenderState {
     DevBuf<int> hit, queue_a, queue_b, queue_nee, queue_c0, queue_c1, queue_c2, queue_c3;
     DevBuf<unsigned char> pflags, pclass;
     DevBuf<unsigned int> nee_vis;
-    DevBuf<unsigned int> tile_counts;
+    // k_compact's scratch (compact_kernel.hip.h): a descriptor per (predicate, tile), the two alternating ticket counters, and the sequence
+    // number of the handle's last compaction (descriptors of earlier passes carry earlier numbers: nothing is cleared between passes)
+    DevBuf<unsigned long long> tile_desc;
+    DevBuf<unsigned int> compact_ticket;
+    unsigned int compact_seq = 0;
     DevBuf<int> trace_spill;   // global part of k_trace's per-lane traversal stacks
     DevBuf<float4> vol_n1, vol_f, vol_Li, vol_Tr, vol_Ld, vol_mres;   // VolPath light-estimate records (vol_kernel.hip.h)
     DevBuf<int4> vol_vs;

@@ -12,7 +12,7 @@
 //   k_resolve       colObj += Li in sample order, box average                                   (A1)
 //
 // State lives in HBM as 32-byte records grouped by consumer plus a few plain arrays (PathArrays below); queues hold path slots and
-// are compacted order-preservingly with wave64 ballots + a tile scan (compact_kernel.hip.h: no atomics).
+// are compacted order-preservingly with wave64 ballots + a chained tile scan (compact_kernel.hip.h: one pass, no atomic appends).
 // No MFMA: the work is BVH pointer chasing and divergent shading, bound by VALU issue and memory latency.
 #pragma once
 #include "device_bsdf.h"
@@ -43,7 +43,7 @@ struct PathArrays {
     float4 *L;        // L.rgb
     int *hit;         // leaf-order triangle of the closest hit, -1 == miss
     unsigned char *pflags;  // written by k_shade: bit0 continues, bit1 NEE record, bit2 shadow ray, bit3 MIS ray
-    unsigned char *pclass;  // written by k_trace: shade-kernel class of the hit material (DMaterial::shade_class)
+    unsigned char *pclass;  // written by k_trace for misses and sphere hits: shade-kernel class (DMaterial::shade_class; triangle hits: tri_class[hit], k_compact)
     // next-event-estimation records written by k_shade, consumed by k_nee
     float4 *sh_o;     // [2] shadow ray origin, tMax
     float4 *sh_d;     // [2] shadow ray direction, flags (bit0 shadow ray valid, bit1 MIS ray valid)
@@ -75,7 +75,7 @@ struct PathArrays {
 constexpr int kMaxRegions = 8;   // sub-passes in flight at most (each in its own region of the state arrays)
 struct Counters {
     unsigned long long nodes, tris;
-    unsigned int q_next, q_nee, q_shadow, q_mis;   // k_compact_scan totals: paths that continue / have NEE / shadow rays / MIS rays
+    unsigned int q_next, q_nee, q_shadow, q_mis;   // k_compact totals: paths that continue / have NEE / shadow rays / MIS rays
     unsigned int q_low;                             // ... / continue and live in the lower half of the state arrays (follows q_mis: the fifth total)
     unsigned int q_class[4];                        // fill counts of the per-material-class shade queues (3: image-textured)
     unsigned int cursor;                            // k_trace work cursor
@@ -92,6 +92,7 @@ struct Counters {
     unsigned int region_alive[kMaxRegions];         // paths of each region that continue
     unsigned long long rays_continue, rays_shadow, rays_mis;   // summed over the iterations: continuation rays of surviving paths, shadow rays, MIS rays
     unsigned long long li_bad;                      // gnxr_li_device: ~index of the first sample record out of range (0: none; li_kernel.hip.h)
+    unsigned int compact_stall;                     // k_compact: a look-back reached its poll cap (never in a correct run; the host reports GNXR_ERR_RUNTIME)
 };
 
 struct DScene {
@@ -407,7 +408,7 @@ GX_DEV const DMaterial *shade_material(const DScene &sc, const DMaterial *mat, i
 
 // ------------------------------------------------------------------------------------------------
 // One specialisation per (lobe set LM, light-type set LT): device_bsdf.h LM_*, device_lights.h LT_*.  `n_dev`
-// points at the fill count of `queue` written by k_compact_scan (device-side, no host round trip).
+// points at the fill count of `queue` written by k_compact (device-side, no host round trip).
 #ifndef GX_SHADE_MINWAVES
 #define GX_SHADE_MINWAVES 2
 #endif

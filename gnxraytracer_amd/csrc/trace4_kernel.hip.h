@@ -149,7 +149,7 @@ __global__ void GX_T4_BOUNDS k_trace4(DScene sc, typename Trace4Src<Q>::type pa,
         else if constexpr (Q == kT4QueryAny) pa.occluded[path] = hitLeaf != -1 ? 1 : 0;
         else if (kind == 0) {
             pa.hit[path] = hitLeaf;
-            // The shade class of a triangle hit is looked up from `hit` by the binning pass (k_compact_count<COMPACT_HITCLASS>: tri_class[hit]) --
+            // The shade class of a triangle hit is looked up from `hit` by the binning pass (k_compact<COMPACT_HITCLASS>: tri_class[hit]) --
             // a dependent gather here would stall the whole wave once per retire.  Only hits without a triangle get their class here.
             if (hitLeaf < 0) {
                 int cls = sc.escape_class;   // misses that still have to collect an infinite light: a queue of their own, or the code of class 0

@@ -386,7 +386,7 @@ __global__ void __launch_bounds__(kBlock) k_trace(DScene sc, PathArrays pa, Trac
         if (item >= 0 && cur == -1 && leafN == 0) {
             if (kind == 0) {
                 pa.hit[path] = hitLeaf;
-                if (hitLeaf < 0) {   // triangle hits: the binning pass looks the class up from `hit` (k_compact_count<COMPACT_HITCLASS>)
+                if (hitLeaf < 0) {   // triangle hits: the binning pass looks the class up from `hit` (k_compact<COMPACT_HITCLASS>)
                     int cls = sc.escape_class;   // misses that still have to collect an infinite light: a queue of their own, or the code of class 0
                     if (SPH && hitLeaf != -1) { const int mat = sc.spheres[-2 - hitLeaf].material; if (mat >= 0) cls = sc.materials[mat].shade_class; }
                     else if (sc.lt.n_infinite == 0) {
