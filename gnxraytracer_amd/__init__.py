@@ -254,6 +254,14 @@ class SceneBuilder:
         self.set_material_texture(m, "ks", t)
         return m
 
+    def material_albedo(self, material):
+        """gnxr_material_albedo of material `material` of this builder (see material_albedo): float32 (3,)."""
+        d = self.desc()
+        material = int(material)
+        if not 0 <= material < d.n_materials:
+            raise ValueError(f"material_albedo: material {material} is outside [0, {d.n_materials})")
+        return _material_albedo(d.materials[material])
+
     def AddSphere(self, center, radius, material, medium_inside=-1, medium_outside=-1):
         """pbrt-v3 quadratic sphere (the reference's shape/Sphere.h is an unfinished stub; see include/gnxr.h)."""
         c = (C.c_float * 3)(*[float(v) for v in center])
@@ -283,6 +291,25 @@ def camera(eye=(0, 0, 5), look=(0, 0, 0), up=(0, 1, 0), fov=90.0, lens_radius=0.
     """The gnxr_camera record (ctypes `Camera`) of SceneBuilder.set_camera / Scene.set_camera's arguments: what RenderViews and
     camera_rays_device take."""
     return Camera(_f3(eye), _f3(look), _f3(up), fov, lens_radius, focal_distance, int(bool(orthographic)))
+
+
+def _material_albedo(m):
+    rgb = (C.c_float * 3)()
+    _check(lib().gnxr_material_albedo(C.byref(m), rgb))
+    return np.array(rgb[:], dtype=np.float32)
+
+
+def material_albedo(**material_fields):
+    """gnxr_material_albedo (host, needs no GPU): the colour the albedo channel of RenderAOV reports for a material with these gnxr_material
+    fields (the keywords of SceneBuilder.add_material) -- kd clamped to [0, inf) for MATTE / PLASTIC / DISNEY, kr for MIRROR, 1 for GLASS,
+    the normal-incidence conductor reflectance for METAL, 0 for NONE -- as a float32 (3,) array.  A kd_texture does not change it."""
+    m = Material()
+    for k, v in material_fields.items():
+        if isinstance(v, (tuple, list, np.ndarray)):
+            setattr(m, k, (C.c_float * len(v))(*[float(x) for x in v]))
+        else:
+            setattr(m, k, v)
+    return _material_albedo(m)
 
 
 def write_synthetic_3d(path, target_triangles=100000, seed=1):
@@ -665,6 +692,75 @@ class PathIntegrator:
         st = Stats()
         _check(lib().gnxr_render_views_device(scene._h, C.byref(p), cams, med, V, C.c_void_p(out.data_ptr() or None), C.c_void_p(stream or None), C.byref(st)))
         return out, stats_dict(st)
+
+    AOV_CHANNELS = ("albedo", "normal", "shading_normal", "depth", "ids")
+
+    def RenderAOV(self, scene, width, height, spp, cameras=None, media=None, channels=AOV_CHANNELS, out=None, stream=None, **kw):
+        """First-hit feature buffers (gnxr_render_aov_device): what a denoiser or a data-set writer wants beside the beauty image, averaged
+        over the same Halton camera samples as Render / RenderViews.  Returns (dict of torch tensors on the scene's device, stats dict):
+        "albedo" (V, H, W, 4) = mean albedo rgb + coverage, "normal" and "shading_normal" (V, H, W, 4) with w = 0, "depth" (V, H, W) float32
+        and "ids" (V, H, W, 2) int32 = (primitive, authored material) of the lowest sample, -1 on a miss or a surface without material.
+        `cameras`: gnxr Camera records (camera()), or None for the scene's own camera, which also drops the leading V.  `media`: one medium
+        index per camera or None.  `channels`: the buffers wanted; `out`: a dict with preallocated tensors for some or all of them.  The
+        buffers stop at the first hit: no specular bounce is followed, no medium boundary skipped.  Runs on `stream` (by default torch's
+        current stream) and returns once the buffers are written.  Keyword arguments: spp_begin, spp_end, samples_per_pass (the integrator's
+        own settings are not used)."""
+        import torch
+        channels = tuple(channels)
+        bad = [c for c in channels if c not in self.AOV_CHANNELS]
+        if bad or not channels or len(set(channels)) != len(channels):
+            raise ValueError(f"RenderAOV: channels must be a non-empty selection of {self.AOV_CHANNELS}, got {channels}")
+        V = 1
+        if cameras is not None:
+            cameras = list(cameras)
+            V = len(cameras)
+            for c in cameras:
+                if not isinstance(c, Camera):
+                    raise ValueError(f"RenderAOV: cameras must be gnxr Camera records (camera(...)), got {type(c).__name__}")
+            if media is not None:
+                media = [int(m) for m in media]
+                if len(media) != V:
+                    raise ValueError(f"RenderAOV: {len(media)} media for {V} cameras")
+        elif media is not None:
+            raise ValueError("RenderAOV: media goes with cameras; the scene's own camera sits in the scene's camera medium")
+        width, height = int(width), int(height)
+        if width <= 0 or height <= 0:
+            raise ValueError(f"RenderAOV: invalid image size {width} x {height}")
+        unknown = [k for k in kw if k not in ("spp_begin", "spp_end", "samples_per_pass")]
+        if unknown:
+            raise ValueError(f"RenderAOV: unexpected arguments {unknown} (spp_begin, spp_end, samples_per_pass)")
+        device = torch.device("cuda", scene.device)
+        lead = (V,) if cameras is not None else ()
+        shapes = {"albedo": (4,), "normal": (4,), "shading_normal": (4,), "depth": (), "ids": (2,)}
+        out = dict(out) if out is not None else {}
+        extra = [c for c in out if c not in channels]
+        if extra:
+            raise ValueError(f"RenderAOV: out holds {extra}, which channels does not name")
+        if stream is None:
+            stream = torch.cuda.current_stream(device)
+        tstream = stream if not isinstance(stream, int) else torch.cuda.ExternalStream(stream, device=device)
+        res = {}
+        for c in channels:
+            shape = lead + (height, width) + shapes[c]
+            dtype = torch.int32 if c == "ids" else torch.float32
+            t = out.get(c)
+            if t is None:
+                with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensors to the stream that writes them)
+                    t = torch.empty(shape, dtype=dtype, device=device)
+            elif not (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == scene.device and t.dtype == dtype and tuple(t.shape) == shape and
+                      t.is_contiguous()):
+                raise ValueError(f"RenderAOV: out[{c!r}] must be a contiguous {dtype} tensor of shape {shape} on cuda:{scene.device}, got "
+                                 f"{type(t).__name__} {getattr(t, 'dtype', None)} {tuple(getattr(t, 'shape', ()))} on {getattr(t, 'device', None)}")
+            res[c] = t
+        ptr = lambda c: C.c_void_p(res[c].data_ptr() or None) if c in res else None
+        bufs = _abi.AovBuffers(ptr("albedo"), ptr("normal"), ptr("shading_normal"), ptr("depth"), ptr("ids"))
+        p = self.params(width, height, spp, **kw)
+        cams = (Camera * V)(*cameras) if cameras else None
+        med = (C.c_int32 * V)(*media) if media else None
+        st = Stats()
+        _check(lib().gnxr_render_aov_device(scene._h, C.byref(p), cams, med, V if cameras is not None else 1, C.byref(bufs), C.c_void_p(tstream.cuda_stream or None),
+                                            C.byref(st)))
+        return res, stats_dict(st)
 
     def Render(self, scene, width, height, spp, **kw):
         """Integrator::Render: returns (float32 image [H, W, 4], stats dict)."""

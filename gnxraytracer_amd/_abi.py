@@ -116,6 +116,10 @@ class BsdfResult(C.Structure):
                 ("n_components", i32), ("valid", i32), ("dudx", f32), ("dvdy", f32)]
 
 
+class AovBuffers(C.Structure):
+    _fields_ = [("d_albedo", C.c_void_p), ("d_normal", C.c_void_p), ("d_shading_normal", C.c_void_p), ("d_depth", C.c_void_p), ("d_ids", C.c_void_p)]
+
+
 class LightResult(C.Structure):
     _fields_ = [("Li", f32 * 3), ("pdf", f32), ("wi", f32 * 3), ("pdf_li", f32), ("pdf_select", f32), ("p_light", f32 * 3)]
 
@@ -148,6 +152,8 @@ PROTOTYPES = {
     "gnxr_trace_any_device": (C.c_int, [VP, VP, i64, VP, VP]),
     "gnxr_li_device": (C.c_int, [VP, P(RenderParams), VP, VP, i64, VP, VP, P(Stats)]),   # device addresses + hipStream_t
     "gnxr_render_views_device": (C.c_int, [VP, P(RenderParams), P(Camera), P(i32), i32, VP, VP, P(Stats)]),   # cameras, media: host; images: device
+    "gnxr_render_aov_device": (C.c_int, [VP, P(RenderParams), P(Camera), P(i32), i32, P(AovBuffers), VP, P(Stats)]),   # cameras, media: host; buffers: device
+    "gnxr_material_albedo": (C.c_int, [P(Material), P(f32)]),
     "gnxr_camera_rays_device": (C.c_int, [P(Camera), i32, i32, i32, VP, VP, VP, i64, VP, VP, VP]),   # device addresses + hipStream_t
     "gnxr_bsdf_device": (C.c_int, [VP, VP, VP, VP, VP, i64, i32, VP, VP]),   # device addresses + hipStream_t
     "gnxr_light_sample_device": (C.c_int, [VP, VP, i64, i32, VP, VP]),

@@ -27,6 +27,7 @@
 #include "li_kernel.hip.h"
 #include "views_kernel.hip.h"
 #include "shade_query_kernel.hip.h"
+#include "aov_kernel.hip.h"
 #include "kernel_instances.h"
 
 using namespace gnxr;
@@ -44,6 +45,10 @@ extern template GX_LIGHT_SAMPLE_QUERY_SIGNATURE(LT_ALL)
 extern template GX_LIGHT_LE_QUERY_SIGNATURE(LT_ALL)
 extern template GX_TRACE_CLOSEST_CODE_SIGNATURE(32)
 extern template GX_TRACE_CLOSEST_CODE_SIGNATURE(64)
+// compiled in inst_aov.hip
+#define X(M) extern template GX_AOV_RESOLVE_SIGNATURE(M)
+GX_AOV_INSTANCES(X)
+#undef X
 
 #include "api_common.hip.h"
 #include "api_scene.hip.h"
@@ -126,6 +131,7 @@ static int upload_scene(gnxr_scene *s) {
 #define UP(field) if ((rc = s->field.upload(cs.field)) != GNXR_OK) return rc;
     UP(nodes) UP(nodes4) UP(tris) UP(leaf_boxes) UP(tri_class) UP(lights) UP(perms) UP(primes) UP(prime_sums) UP(prime_magic)
     UP(dmedia) UP(grid_density) UP(tri_media) UP(spheres) UP(textures) UP(tex_texels) UP(ewa_lut) UP(tri_uv) UP(tri_n) UP(tri_s)
+    UP(aov_albedo) UP(material_authored)
     UP(env_texels4) UP(env_cond_func) UP(env_cond_cdf) UP(env_cond_int) UP(env_marg_func) UP(env_marg_cdf) UP(env_marg_guide) UP(env_cond_guide)
 #undef UP
     {   // materials, preceded by one record that carries the texture tables (tex_tables(), device_texture.h)
@@ -383,6 +389,7 @@ int gnxr_trace_any(gnxr_scene *s, const gnxr_ray *rays, int64_t n, uint8_t *occl
 }  // extern "C"
 
 #include "api_query.hip.h"
+#include "api_aov.hip.h"
 
 extern "C" {
 

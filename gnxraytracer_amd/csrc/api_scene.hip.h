@@ -52,6 +52,8 @@ struct gnxr_scene {
     DevBuf<DMaterial> materials, materials_single;
     DevBuf<DTexture> textures;
     DevBuf<float> tex_texels, ewa_lut, tri_uv, tri_n, tri_s;
+    DevBuf<float> aov_albedo;            // feature buffers (api_aov.hip.h): CompiledScene::aov_albedo / material_authored
+    DevBuf<int32_t> material_authored;
     DevBuf<DLight> lights;
     DevBuf<int32_t> infinite;
     DevBuf<uint16_t> perms;

@@ -69,6 +69,8 @@ struct CompiledScene {
     std::vector<float> tri_uv;                 // empty, or 8 floats per leaf-order triangle: (u,v) x 3 corners + pad
     std::vector<float> tri_n;                  // empty, or 12 floats per leaf-order triangle: 3 shading normals + pad (zeros == none)
     std::vector<float> tri_s;                  // the same for TriangleMesh::s (shading tangents)
+    std::vector<float> aov_albedo;             // feature buffers: float4 per AUTHORED material, gnxr_material_albedo's rgb + the bits of kd_texture
+    std::vector<int32_t> material_authored;    // per entry of `materials` (the attribute copies included): the authored material index
     std::vector<DLight> lights;
     std::vector<int32_t> infinite_lights;
     // sampler

@@ -225,6 +225,28 @@ static inline RGB clamp0(const float *p) { return {{clampf(p[0], 0, INFINITY), c
 static inline bool black(const RGB &r) { return r.c[0] == 0 && r.c[1] == 0 && r.c[2] == 0; }
 static inline RGB scale_rgb(const RGB &r, float s) { return {{r.c[0] * s, r.c[1] * s, r.c[2] * s}}; }
 
+// gnxr_material_albedo (include/gnxr.h): the colour a feature buffer reports for a material.  Kd / Kr are clamped as compile_material
+// clamps them; a metal's is its Fresnel reflectance at normal incidence, evaluated in the operation order the header documents.
+static bool material_albedo(const gnxr_material &m, float rgb[3]) {
+    rgb[0] = rgb[1] = rgb[2] = 0.f;
+    switch (m.type) {
+    case GNXR_MAT_NONE: return true;
+    case GNXR_MAT_MATTE: case GNXR_MAT_PLASTIC: case GNXR_MAT_DISNEY: memcpy(rgb, clamp0(m.kd).c, 12); return true;
+    case GNXR_MAT_MIRROR: memcpy(rgb, clamp0(m.kr).c, 12); return true;
+    case GNXR_MAT_GLASS: rgb[0] = rgb[1] = rgb[2] = 1.f; return true;
+    case GNXR_MAT_METAL:
+        for (int c = 0; c < 3; ++c) {
+            // volatile: every operation is rounded to fp32 on its own, whatever the host compiler's contraction setting
+            volatile float a = m.eta[c] - 1.f, b = m.eta[c] + 1.f, k2 = m.k[c] * m.k[c];
+            volatile float aa = a * a, bb = b * b;
+            volatile float num = aa + k2, den = bb + k2;
+            rgb[c] = num / den;
+        }
+        return true;
+    default: return false;
+    }
+}
+
 static DLobe blank_lobe(int kind, int type) {
     DLobe l;
     memset(&l, 0, sizeof(l));
@@ -1058,6 +1080,20 @@ bool compile_scene(const gnxr_scene_desc *d, CompiledScene *cs, HlbvhBuildFn hlb
             t.material = attr_copy[t.material];
         }
     }
+    // ---- feature buffers (gnxr_render_aov_device): one albedo per AUTHORED material (w: the bits of kd_texture, so that the device knows
+    // where to look the colour up instead) and the way back from an internal material -- the attribute copies above included -- to the
+    // authored index the ids channel reports
+    cs->aov_albedo.assign((size_t)std::max(1, d->n_materials) * 4, 0.f);
+    for (int i = 0; i < d->n_materials; ++i) {
+        if (!material_albedo(d->materials[i], &cs->aov_albedo[(size_t)i * 4])) { set_error("unknown material type %d", d->materials[i].type); return false; }
+        memcpy(&cs->aov_albedo[(size_t)i * 4 + 3], &d->materials[i].kd_texture, 4);
+    }
+    cs->material_authored.assign(cs->materials.size(), 0);
+    for (int i = 0; i < d->n_materials; ++i) cs->material_authored[i] = i;
+    for (int li = 0; li < d->n_triangles; ++li) {
+        const int m = cs->tris[li].material, authored = d->tri_material[cs->tris[li].prim];
+        if (m >= 0) cs->material_authored[m] = authored;
+    }
     cs->tri_class.assign(d->n_triangles, 0);
     for (int li = 0; li < d->n_triangles; ++li) {
         const int m = cs->tris[li].material;
@@ -1375,3 +1411,9 @@ void light_grid_probes(const CompiledScene &cs, float *ri /* [5][128] */) {
 }
 
 }  // namespace gnxr
+
+extern "C" int gnxr_material_albedo(const gnxr_material *m, float rgb[3]) {
+    if (!m || !rgb) { gnxr::set_error("null argument"); return GNXR_ERR_INVALID; }
+    if (!gnxr::material_albedo(*m, rgb)) { gnxr::set_error("unknown material type %d", m->type); return GNXR_ERR_INVALID; }
+    return GNXR_OK;
+}

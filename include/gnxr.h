@@ -479,6 +479,63 @@ int gnxr_render_views_device(gnxr_scene *scene, const gnxr_render_params *params
 int gnxr_camera_rays_device(const gnxr_camera *camera, int32_t camera_medium, int32_t width, int32_t height, const int32_t *d_px,
                             const int32_t *d_py, const int32_t *d_s, int64_t n, gnxr_ray *d_rays, gnxr_li_sample *d_samples, void *hip_stream);
 
+/* -- First-hit feature buffers on device memory: depth, normals, albedo and ids per view -----------------------------------
+ * gnxr_render_aov_device writes, for n_views images of one scene, the buffers a denoiser or a data-set writer wants beside the beauty
+ * image, anti-aliased exactly as the beauty image is: for view v, pixel (x, y) and every sample s of [spp_begin, spp_end) (0, 0 = all)
+ * the camera ray is the one gnxr_camera_rays_device writes for cameras[v] -- the one gnxr_render_views_device traces -- and the hit is
+ * Scene::Intersect on it with the bits of gnxr_trace_closest_device (spheres included).  cameras == NULL with n_views == 1 means the
+ * scene's own camera and camera medium (camera_media is then not read).  Per channel the per-sample values are added in fp32 in
+ * increasing sample order, starting from 0, and the sum is divided by (float)spp -- what the render does with L -- so a call over
+ * [a, b) returns that range's share of the mean and the shares of disjoint ranges add up.  A miss adds 0 to every channel.  Image v of
+ * a channel sits at v*width*height*stride, pixel (x, y) at x + y*width.
+ *   d_albedo          the albedo of the hit's material (gnxr_material_albedo; where kd_texture != 0 the kd is the UNFILTERED lookup of
+ *                     that texture at the hit's uv: the lookup PathIntegrator's shade kernel makes, hasDifferentials == false);
+ *                     w = coverage: 1 added per sample that hit anything
+ *   d_normal          gnxr_hit.n: the geometric normal, flipped onto the shading side on triangles with normals or tangents; w = 0
+ *   d_shading_normal  the shading normal the shade kernels build the BSDF on: interpolated per-vertex normals, the SetShadingGeometry
+ *                     flip, Material::Bump with the zero map (has_bump), a sphere's own; w = 0
+ *   d_depth           gnxr_hit.t
+ *   d_ids             not averaged: {gnxr_hit.prim, material} of the LOWEST sample of the call's range (spp_begin), {-1, -1} on a miss.
+ *                     The material is the index into desc.materials as authored (spheres[i].material for a sphere), never the
+ *                     internal copy triangles with uvs or normals of their own are given; -1 where the surface has no material
+ *                     (index -1 or a GNXR_MAT_NONE material: a medium boundary)
+ * FIRST HIT ONLY: a null-material surface is a hit like any other (material -1, albedo 0, its own depth and normals); the buffers
+ * neither follow specular bounces nor step through medium boundaries.
+ * params: width, height, spp, spp_begin, spp_end as for gnxr_render_views_device; samples_per_pass = samples of EVERY view per
+ * sub-pass (0 = auto: sized from the free device memory; the buffers do not depend on it); integrator, max_depth, rr_threshold, the
+ * strategies and passes_in_flight are ignored; shard_index must be 0, shard_count and shard_rows 0 or 1.  The call keeps 32 bytes per
+ * camera sample of a sub-pass (the ray; the hit's leaf code travels in its pad word) and 16 to 48 bytes per pixel of running sums, all
+ * from the stream-ordered allocator: nothing of the path state gnxr_render_reserve allocates is touched.  stats receives
+ * camera_samples, rays_closest, passes, kernel_launches, state_bytes and the seconds.  Locking, stream ordering, the choice of the
+ * copy under gnxr_init_devices (the device that holds the buffers) and n_views == 0 (a no-op) are as for gnxr_render_views_device;
+ * the call returns when the buffers are written.
+ * GNXR_ERR_INVALID, before anything is queued: a null scene, params or out; all five channels NULL; a channel that is not device
+ * memory, on a device without a copy of the scene or on another device than the others; a four-float channel that is not 16-byte
+ * aligned, depth or ids not 4-byte aligned; n_views < 0; null cameras with n_views > 1; a medium outside [-1, n_media); invalid
+ * params or shard fields; n_views*width*height beyond the limit of gnxr_render_views_device.  GNXR_ERR_UNSUPPORTED: spp beyond the
+ * 32-bit Halton indices of gnxr_render.
+ *
+ * gnxr_material_albedo (host, needs no device) is the single definition of a material's albedo; the device table is built with it.
+ *   MATTE, PLASTIC, DISNEY : kd, each channel clamped to [0, inf) as the materials clamp it (Spectrum::Clamp)
+ *   MIRROR                 : kr, clamped the same way
+ *   GLASS                  : (1, 1, 1)
+ *   METAL                  : the conductor's reflectance at normal incidence, per channel in fp32, every operation rounded on its own
+ *                            (no fused multiply-add), in this order:
+ *                                a = eta - 1;  b = eta + 1;  k2 = k * k;  num = a * a + k2;  den = b * b + k2;  albedo = num / den
+ *   NONE                   : 0
+ * A kd_texture does not change the value returned here (the texture is looked up per hit on the device).  GNXR_ERR_INVALID for a
+ * null pointer or an unknown type.                                                                                              */
+typedef struct gnxr_aov_buffers {   /* device pointers; NULL = channel not wanted */
+    float   *d_albedo;          /* V*W*H*4: mean albedo rgb, w = coverage (fraction of the spp samples that hit anything) */
+    float   *d_normal;          /* V*W*H*4: mean geometric normal (the bits of gnxr_hit.n per sample), w = 0 */
+    float   *d_shading_normal;  /* V*W*H*4: mean shading normal (the ns the shade kernels build the BSDF on), w = 0 */
+    float   *d_depth;           /* V*W*H:   mean gnxr_hit.t */
+    int32_t *d_ids;             /* V*W*H*2: {gnxr_hit.prim, material index} of the LOWEST sample of the call's range; -1,-1 on a miss */
+} gnxr_aov_buffers;
+int gnxr_render_aov_device(gnxr_scene *scene, const gnxr_render_params *params, const gnxr_camera *cameras, const int32_t *camera_media,
+                           int32_t n_views, const gnxr_aov_buffers *out, void *hip_stream, gnxr_stats *stats);
+int gnxr_material_albedo(const gnxr_material *m, float rgb[3]);
+
 /* -- Shading queries on device memory: the pieces an integrator is made of, batched -------------------------------------
  * Same conventions as the device calls of the Aggregate seam: every array is device memory of one device that holds a copy of the
  * scene, the work is queued on hip_stream (NULL: the null stream) after what the caller queued there, scratch comes from the
