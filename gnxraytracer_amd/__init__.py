@@ -418,18 +418,10 @@ class Scene:
         import torch
         self._device_tensor(f"{name}: rays", rays, torch.float32, 8)
         n = rays.shape[0]
-        if out is None:
-            out = torch.empty((n, cols) if cols else (n,), dtype=dtype, device=rays.device)
-        else:
-            self._device_tensor(f"{name}: out", out, dtype, cols)
-            if out.shape[0] != n:
-                raise ValueError(f"{name}: out has {out.shape[0]} rows for {n} rays")
-        if stream is None:
-            stream = torch.cuda.current_stream(rays.device)
-        if not isinstance(stream, int):
-            stream = stream.cuda_stream   # a torch.cuda.Stream
+        out = _out_tensor(f"{name}: out", out, (n, cols) if cols else (n,), dtype, rays.device)
+        st, _ = _stream_pair(stream, rays.device)
         fn = lib().gnxr_trace_closest_device if cols else lib().gnxr_trace_any_device
-        _check(fn(self._h, C.c_void_p(rays.data_ptr() or None), n, C.c_void_p(out.data_ptr() or None), C.c_void_p(stream or None)))
+        _check(fn(self._h, C.c_void_p(rays.data_ptr() or None), n, C.c_void_p(out.data_ptr() or None), C.c_void_p(st or None)))
         return out
 
     def intersect(self, rays, out=None, stream=None):
@@ -459,18 +451,8 @@ class Scene:
                 n = x.shape[0]
             elif x.shape[0] != n:
                 raise ValueError(f"{name}: {what} has {x.shape[0]} rows for {n} {args[0][0]}")
-        device = args[0][1].device
-        if out is None:
-            out = torch.empty((n, out_cols), dtype=torch.float32, device=device)
-        else:
-            _tensor_layout(f"{name}: out", out, torch.float32, out_cols)
-            self._device_tensor(f"{name}: out", out, torch.float32, out_cols)
-            if out.shape[0] != n:
-                raise ValueError(f"{name}: out has {out.shape[0]} rows for {n} {args[0][0]}")
-        if stream is None:
-            stream = torch.cuda.current_stream(device)
-        tstream = stream if not isinstance(stream, int) else torch.cuda.ExternalStream(stream, device=device)
-        return n, out, tstream.cuda_stream, tstream
+        out = _out_tensor(f"{name}: out", out, (n, out_cols), torch.float32, args[0][1].device)
+        return (n, out) + _stream_pair(stream, args[0][1].device)
 
     def bsdf(self, rays, wi, u, flags=31, differentials=None, out=None, stream=None):
         """BSDF::f / Pdf / Sample_f at the hits of rays already on the GPU (gnxr_bsdf_device): Scene::Intersect along `rays` (float32
@@ -554,6 +536,46 @@ def rays_tensor(o, d, tmax=float("inf")):
     return r
 
 
+def _stream_pair(stream, device):
+    """`stream` -- None (torch's current stream on `device`), a torch.cuda.Stream, or a hipStream_t as an int -- as the pair
+    (hipStream_t as an int, torch stream of that handle)."""
+    import torch
+    if stream is None:
+        stream = torch.cuda.current_stream(device)
+    elif isinstance(stream, int):
+        stream = torch.cuda.ExternalStream(stream, device=device)
+    return stream.cuda_stream, stream
+
+
+def _out_tensor(what, out, shape, dtype, device):
+    """The result tensor of a call on device memory: `out` when given -- it must be a contiguous `dtype` tensor of `shape` on `device`,
+    the device of the call's inputs or of its scene -- else a new one."""
+    import torch
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if not (isinstance(out, torch.Tensor) and out.device == device and out.dtype == dtype and tuple(out.shape) == tuple(shape) and out.is_contiguous()):
+        raise ValueError(f"{what} must be a contiguous {dtype} tensor of shape {tuple(shape)} on {device}, got "
+                         f"{type(out).__name__} {getattr(out, 'dtype', None)} {tuple(getattr(out, 'shape', ()))} on {getattr(out, 'device', None)}")
+    return out
+
+
+def _view_args(name, cameras, media, width, height):
+    """The views of RenderViews / RenderAOV, checked: (list of Camera records -- None stays None --, list of media or None, width, height)"""
+    if cameras is not None:
+        cameras = list(cameras)
+        for c in cameras:
+            if not isinstance(c, Camera):
+                raise ValueError(f"{name}: cameras must be gnxr Camera records (camera(...)), got {type(c).__name__}")
+        if media is not None:
+            media = [int(m) for m in media]
+            if len(media) != len(cameras):
+                raise ValueError(f"{name}: {len(media)} media for {len(cameras)} cameras")
+    width, height = int(width), int(height)
+    if width <= 0 or height <= 0:
+        raise ValueError(f"{name}: invalid image size {width} x {height}")
+    return cameras, media, width, height
+
+
 def _tensor_layout(what, x, dtype, cols):
     """a contiguous (n, cols) tensor of `dtype` (on any device: Scene._device_tensor checks the device)"""
     import torch
@@ -635,19 +657,10 @@ class PathIntegrator:
         n = rays.shape[0]
         if samples.shape[0] != n:
             raise ValueError(f"Li: {samples.shape[0]} sample records for {n} rays")
-        if out is not None:
-            _tensor_layout("Li: out", out, torch.float32, 4)
-            if out.shape[0] != n:
-                raise ValueError(f"Li: out has {out.shape[0]} rows for {n} rays")
+        out = _out_tensor("Li: out", out, (n, 4), torch.float32, rays.device)
         scene._device_tensor("Li: rays", rays, torch.float32, 8)
         scene._device_tensor("Li: samples", samples, torch.int32, 4)
-        if out is None:
-            out = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
-        scene._device_tensor("Li: out", out, torch.float32, 4)
-        if stream is None:
-            stream = torch.cuda.current_stream(rays.device)
-        if not isinstance(stream, int):
-            stream = stream.cuda_stream   # a torch.cuda.Stream
+        stream, _ = _stream_pair(stream, rays.device)
         p = self.params(width, height, spp, **kw)
         st = Stats()
         _check(lib().gnxr_li_device(scene._h, C.byref(p), C.c_void_p(rays.data_ptr() or None), C.c_void_p(samples.data_ptr() or None), n,
@@ -662,30 +675,10 @@ class PathIntegrator:
         GPU; stats holds the sums over the views.  Runs on `stream` (by default torch's current stream) and returns once the images
         are written.  The other keyword arguments are Render's, without the shard fields."""
         import torch
-        cameras = list(cameras)
+        cameras, media, width, height = _view_args("RenderViews", list(cameras), media, width, height)
         V = len(cameras)
-        for c in cameras:
-            if not isinstance(c, Camera):
-                raise ValueError(f"RenderViews: cameras must be gnxr Camera records (camera(...)), got {type(c).__name__}")
-        if media is not None:
-            media = [int(m) for m in media]
-            if len(media) != V:
-                raise ValueError(f"RenderViews: {len(media)} media for {V} cameras")
-        width, height = int(width), int(height)
-        if width <= 0 or height <= 0:
-            raise ValueError(f"RenderViews: invalid image size {width} x {height}")
-        device = torch.device("cuda", scene.device)
-        if out is None:
-            out = torch.empty((V, height, width, 4), dtype=torch.float32, device=device)
-        else:
-            if not (isinstance(out, torch.Tensor) and out.dim() == 4 and tuple(out.shape) == (V, height, width, 4)):
-                raise ValueError(f"RenderViews: out must have shape ({V}, {height}, {width}, 4), got {tuple(getattr(out, 'shape', ()))}")
-            _tensor_layout("RenderViews: out", out.view(-1, 4) if out.is_contiguous() else out, torch.float32, 4)
-            scene._device_tensor("RenderViews: out", out.view(-1, 4), torch.float32, 4)
-        if stream is None:
-            stream = torch.cuda.current_stream(device)
-        if not isinstance(stream, int):
-            stream = stream.cuda_stream   # a torch.cuda.Stream
+        out = _out_tensor("RenderViews: out", out, (V, height, width, 4), torch.float32, torch.device("cuda", scene.device))
+        stream, _ = _stream_pair(stream, out.device)
         p = self.params(width, height, spp, **kw)
         cams = (Camera * max(V, 1))(*cameras)
         med = (C.c_int32 * max(V, 1))(*media) if media is not None else None
@@ -710,22 +703,10 @@ class PathIntegrator:
         bad = [c for c in channels if c not in self.AOV_CHANNELS]
         if bad or not channels or len(set(channels)) != len(channels):
             raise ValueError(f"RenderAOV: channels must be a non-empty selection of {self.AOV_CHANNELS}, got {channels}")
-        V = 1
-        if cameras is not None:
-            cameras = list(cameras)
-            V = len(cameras)
-            for c in cameras:
-                if not isinstance(c, Camera):
-                    raise ValueError(f"RenderAOV: cameras must be gnxr Camera records (camera(...)), got {type(c).__name__}")
-            if media is not None:
-                media = [int(m) for m in media]
-                if len(media) != V:
-                    raise ValueError(f"RenderAOV: {len(media)} media for {V} cameras")
-        elif media is not None:
+        if cameras is None and media is not None:
             raise ValueError("RenderAOV: media goes with cameras; the scene's own camera sits in the scene's camera medium")
-        width, height = int(width), int(height)
-        if width <= 0 or height <= 0:
-            raise ValueError(f"RenderAOV: invalid image size {width} x {height}")
+        cameras, media, width, height = _view_args("RenderAOV", cameras, media, width, height)
+        V = len(cameras) if cameras is not None else 1
         unknown = [k for k in kw if k not in ("spp_begin", "spp_end", "samples_per_pass")]
         if unknown:
             raise ValueError(f"RenderAOV: unexpected arguments {unknown} (spp_begin, spp_end, samples_per_pass)")
@@ -736,29 +717,18 @@ class PathIntegrator:
         extra = [c for c in out if c not in channels]
         if extra:
             raise ValueError(f"RenderAOV: out holds {extra}, which channels does not name")
-        if stream is None:
-            stream = torch.cuda.current_stream(device)
-        tstream = stream if not isinstance(stream, int) else torch.cuda.ExternalStream(stream, device=device)
+        hstream, tstream = _stream_pair(stream, device)
         res = {}
-        for c in channels:
-            shape = lead + (height, width) + shapes[c]
-            dtype = torch.int32 if c == "ids" else torch.float32
-            t = out.get(c)
-            if t is None:
-                with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensors to the stream that writes them)
-                    t = torch.empty(shape, dtype=dtype, device=device)
-            elif not (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == scene.device and t.dtype == dtype and tuple(t.shape) == shape and
-                      t.is_contiguous()):
-                raise ValueError(f"RenderAOV: out[{c!r}] must be a contiguous {dtype} tensor of shape {shape} on cuda:{scene.device}, got "
-                                 f"{type(t).__name__} {getattr(t, 'dtype', None)} {tuple(getattr(t, 'shape', ()))} on {getattr(t, 'device', None)}")
-            res[c] = t
+        with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensors to the stream that writes them)
+            for c in channels:
+                res[c] = _out_tensor(f"RenderAOV: out[{c!r}]", out.get(c), lead + (height, width) + shapes[c], torch.int32 if c == "ids" else torch.float32, device)
         ptr = lambda c: C.c_void_p(res[c].data_ptr() or None) if c in res else None
         bufs = _abi.AovBuffers(ptr("albedo"), ptr("normal"), ptr("shading_normal"), ptr("depth"), ptr("ids"))
         p = self.params(width, height, spp, **kw)
         cams = (Camera * V)(*cameras) if cameras else None
         med = (C.c_int32 * V)(*media) if media else None
         st = Stats()
-        _check(lib().gnxr_render_aov_device(scene._h, C.byref(p), cams, med, V if cameras is not None else 1, C.byref(bufs), C.c_void_p(tstream.cuda_stream or None),
+        _check(lib().gnxr_render_aov_device(scene._h, C.byref(p), cams, med, V if cameras is not None else 1, C.byref(bufs), C.c_void_p(hstream or None),
                                             C.byref(st)))
         return res, stats_dict(st)
 
@@ -851,15 +821,13 @@ def camera_rays_device(camera, width, height, px, py, s, medium=-1, stream=None)
             raise ValueError(f"camera_rays_device: {what} has {x.shape[0]} entries for {n} px")
     if not isinstance(camera, Camera):
         raise ValueError(f"camera_rays_device: camera must be a gnxr Camera record (camera(...)), got {type(camera).__name__}")
-    if stream is None:
-        stream = torch.cuda.current_stream(px.device)
-    tstream = stream if not isinstance(stream, int) else torch.cuda.ExternalStream(stream, device=px.device)
+    st, tstream = _stream_pair(stream, px.device)
     with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensors to the stream that writes them)
         rays = torch.empty((n, 8), dtype=torch.float32, device=px.device)
         samples = torch.empty((n, 4), dtype=torch.int32, device=px.device)
     _check(lib().gnxr_camera_rays_device(C.byref(camera), int(medium), int(width), int(height), C.c_void_p(px.data_ptr() or None), C.c_void_p(py.data_ptr() or None),
                                          C.c_void_p(s.data_ptr() or None), n, C.c_void_p(rays.data_ptr() or None), C.c_void_p(samples.data_ptr() or None),
-                                         C.c_void_p(tstream.cuda_stream or None)))
+                                         C.c_void_p(st or None)))
     return rays, samples
 
 

@@ -1,6 +1,6 @@
 // api.hip -- C ABI of libgnxr.so (include/gnxr.h): one translation unit.  This file keeps initialisation, scene creation and editing,
 // the render entry points and the host-memory probes; the rest lives in the api_*.hip.h headers included below (shared pieces, gnxr_scene,
-// the HLBVH build driver, the peak probes, the render path, the entry points on device memory).  One process drives one GPU (gnxr_init
+// the HLBVH build driver, the peak probes, the front end of the calls on device memory, the render path, the entry points on device memory).  One process drives one GPU (gnxr_init
 // binds the device); multi-GPU runs are one process per GPU with the image rows sharded by gnxr_render_params.
 #include <hip/hip_runtime.h>
 
@@ -16,12 +16,6 @@
 #include "host_scene.h"
 #include "kernels.hip.h"
 #include "trace4_kernel.hip.h"
-#ifndef GX_WITH_TRACE4D
-#define GX_WITH_TRACE4D 0   // the two-rays-per-lane traversal kernel: a measured negative result (profiles/README.md, round 3), built only on request
-#endif
-#if GX_WITH_TRACE4D
-#include "trace4d_kernel.hip.h"
-#endif
 #include "hlbvh_build.hip.h"
 #include "refit_kernel.hip.h"
 #include "li_kernel.hip.h"
@@ -54,6 +48,7 @@ GX_AOV_INSTANCES(X)
 #include "api_scene.hip.h"
 #include "api_hlbvh.hip.h"
 #include "api_probes.hip.h"
+#include "api_device_call.hip.h"
 #include "api_render.hip.h"
 
 extern "C" {
@@ -364,9 +359,7 @@ int gnxr_trace_closest(gnxr_scene *s, const gnxr_ray *rays, int64_t n, gnxr_hit 
     int rc;
     if ((rc = dr.upload(rays, (size_t)n)) || (rc = dh.alloc((size_t)n))) return rc;
     DScene sc = s->device_scene(1, 1);
-    if (s->stack_size > 32) hipLaunchKernelGGL((k_trace_closest_api<64>), dim3(grid_for(n, 2)), dim3(kBlock), 0, 0, sc, (const gnxr_ray *)dr.p, (long long)n, dh.p);
-    else hipLaunchKernelGGL((k_trace_closest_api<32>), dim3(grid_for(n, 5)), dim3(kBlock), 0, 0, sc, (const gnxr_ray *)dr.p, (long long)n, dh.p);
-    HIP_TRY(hipGetLastError());
+    if ((rc = binary_trace_api(s, sc, dr.p, n, dh.p, /*any=*/false, nullptr)) != GNXR_OK) return rc;
     HIP_TRY(hipMemcpy(hits, dh.p, (size_t)n * sizeof(gnxr_hit), hipMemcpyDeviceToHost));
     return GNXR_OK;
 }
@@ -379,9 +372,7 @@ int gnxr_trace_any(gnxr_scene *s, const gnxr_ray *rays, int64_t n, uint8_t *occl
     int rc;
     if ((rc = dr.upload(rays, (size_t)n)) || (rc = dob.alloc((size_t)n))) return rc;
     DScene sc = s->device_scene(1, 1);
-    if (s->stack_size > 32) hipLaunchKernelGGL((k_trace_any_api<64>), dim3(grid_for(n, 2)), dim3(kBlock), 0, 0, sc, (const gnxr_ray *)dr.p, (long long)n, dob.p);
-    else hipLaunchKernelGGL((k_trace_any_api<32>), dim3(grid_for(n, 5)), dim3(kBlock), 0, 0, sc, (const gnxr_ray *)dr.p, (long long)n, dob.p);
-    HIP_TRY(hipGetLastError());
+    if ((rc = binary_trace_api(s, sc, dr.p, n, dob.p, /*any=*/true, nullptr)) != GNXR_OK) return rc;
     HIP_TRY(hipMemcpy(occluded, dob.p, (size_t)n, hipMemcpyDeviceToHost));
     return GNXR_OK;
 }
@@ -496,15 +487,16 @@ int gnxr_camera_rays_device(const gnxr_camera *cam, int32_t camera_medium, int32
         }
         (void)hipGetLastError();
     }
-    HIP_TRY(hipSetDevice(device));
-    struct Rebind { int dev; ~Rebind() { if (dev >= 0) (void)hipSetDevice(dev); } } rebind{device != g_device ? g_device : -1};   // leave the bound device current
+    DeviceCall call;
+    if (int rc = call.bind(device)) return rc;
     DSamplerTables st;
     if (int rc = device_probe_tables(device, &st)) return rc;
     st.h = make_halton(width, height);
     const DCamera dc = make_camera(*cam, width, height, camera_medium);
     hipStream_t stream = (hipStream_t)hip_stream;
-    unsigned long long *d_bad = nullptr, bad = 0;
-    HIP_TRY(hipMallocAsync((void **)&d_bad, sizeof(unsigned long long), stream));
+    StreamScratch scratch;
+    HIP_TRY(scratch.alloc(sizeof(unsigned long long), stream));
+    unsigned long long *d_bad = reinterpret_cast<unsigned long long *>(scratch.p), bad = 0;
     hipError_t e = hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), stream);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(k_camera_rays, dim3(grid_for(n)), dim3(kBlock), 0, stream, st, dc, (int)width, (int)height, (const int *)d_px, (const int *)d_py, (const int *)d_s,
@@ -512,10 +504,8 @@ int gnxr_camera_rays_device(const gnxr_camera *cam, int32_t camera_medium, int32
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, stream);
-    const hipError_t ef = hipFreeAsync(d_bad, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);   // only the status word has to come back: the records are on the stream
     HIP_TRY(e);
-    HIP_TRY(ef);
     if (bad) {
         set_error("gnxr_camera_rays_device: record %llu is out of range (px in [0, %d), py in [0, %d), s >= 0); its ray and sample are 0", (unsigned long long)~bad, width, height);
         return GNXR_ERR_INVALID;

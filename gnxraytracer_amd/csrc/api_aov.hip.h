@@ -1,16 +1,9 @@
 // api_aov.hip.h -- first-hit feature buffers on device memory: gnxr_render_aov_device (aov_kernel.hip.h).
-// Part of api.hip's translation unit (after api_query.hip.h: the call's traversal is query_trace4, its replica choice query_replica_all).
+// Part of api.hip's translation unit (after api_query.hip.h: the call's traversal is closest_hit_codes; its front end is api_device_call.hip.h).
 #pragma once
 
 // largest share of the free device memory, and largest amount at all, that the rays of one sub-pass may take when samples_per_pass is 0
 static const size_t kAovFreeShare = 4, kAovRayBytesMax = (size_t)1 << 30;
-
-// the call's scratch: one stream-ordered allocation, returned in stream order on every exit path
-struct AovScratch {
-    char *p = nullptr;
-    hipStream_t st = nullptr;
-    ~AovScratch() { if (p) (void)hipFreeAsync(p, st); }
-};
 
 extern "C" {
 
@@ -18,15 +11,8 @@ int gnxr_render_aov_device(gnxr_scene *s, const gnxr_render_params *p, const gnx
                            const gnxr_aov_buffers *out, void *hip_stream, gnxr_stats *stats) {
     if (!s || !p || !out) { set_error("null argument"); return GNXR_ERR_INVALID; }
     if (n_views < 0 || (!cameras && n_views > 1)) { set_error("feature buffers: n_views = %d with %s cameras", n_views, cameras ? "these" : "null"); return GNXR_ERR_INVALID; }
-    if (p->shard_index != 0 || p->shard_count < 0 || p->shard_count > 1 || p->shard_rows < 0 || p->shard_rows > 1) {
-        set_error("feature buffers: shard_index must be 0, shard_count and shard_rows 0 or 1 (a caller that shards splits the list of views)");
-        return GNXR_ERR_INVALID;
-    }
-    if (p->width <= 0 || p->height <= 0 || p->spp <= 0 || p->spp_begin < 0 || p->spp_end > p->spp || (p->spp_end > 0 && p->spp_begin >= p->spp_end) || p->spp_begin >= p->spp ||
-        p->samples_per_pass < 0) {
-        set_error("invalid render parameters");
-        return GNXR_ERR_INVALID;
-    }
+    if (int rc = check_unsharded(*p, "feature buffers", "a caller that shards splits the list of views")) return rc;
+    if (!image_and_samples_ok(*p) || p->samples_per_pass < 0) return invalid_render_params();
     if (!out->d_albedo && !out->d_normal && !out->d_shading_normal && !out->d_depth && !out->d_ids) { set_error("feature buffers: no channel requested"); return GNXR_ERR_INVALID; }
     if ((((uintptr_t)out->d_albedo | (uintptr_t)out->d_normal | (uintptr_t)out->d_shading_normal) & 15u) != 0) {
         set_error("d_albedo, d_normal and d_shading_normal must be 16-byte aligned");
@@ -34,42 +20,33 @@ int gnxr_render_aov_device(gnxr_scene *s, const gnxr_render_params *p, const gnx
     }
     if ((((uintptr_t)out->d_depth | (uintptr_t)out->d_ids) & 3u) != 0) { set_error("d_depth and d_ids must be 4-byte aligned"); return GNXR_ERR_INVALID; }
     // a sample slot is sample * (n_views * W * H) + pixel, traced by the kernel of the views call: its limit
-    const long long kMaxViewPixels = ((1ll << 32) - 1) / 3;
-    const long long total = (long long)n_views * p->width * p->height;
-    if (total > kMaxViewPixels) {
-        set_error("feature buffers: n_views * width * height = %lld pixels overflow the 32-bit path indexing (at most %lld per call); split the list of views", total, kMaxViewPixels);
-        return GNXR_ERR_INVALID;
-    }
-    const int n_media = (int)s->cs.media.size();
-    for (int v = 0; cameras && camera_media && v < n_views; ++v)
-        if (camera_media[v] < -1 || camera_media[v] >= n_media) { set_error("feature buffers: camera_media[%d] = %d is outside [-1, %d)", v, camera_media[v], n_media); return GNXR_ERR_INVALID; }
+    long long total = 0;
+    if (int rc = check_view_pixels(*p, n_views, "feature buffers", &total)) return rc;
+    if (!cameras) camera_media = nullptr;   // the scene's own camera sits in the scene's camera medium
+    if (int rc = check_view_media(s, camera_media, n_views, "feature buffers")) return rc;
     if (n_views == 0) { if (stats) memset(stats, 0, sizeof(*stats)); return GNXR_OK; }
     if (int rc = ensure_device()) return rc;
     const size_t npx = (size_t)total;
     const QueryArg args[] = {{out->d_albedo, npx * 16, "d_albedo"}, {out->d_normal, npx * 16, "d_normal"}, {out->d_shading_normal, npx * 16, "d_shading_normal"},
                              {out->d_depth, npx * 4, "d_depth"}, {out->d_ids, npx * 8, "d_ids"}};
-    gnxr_scene *r = query_replica_all(s, args, 5);
-    if (!r) return GNXR_ERR_INVALID;
+    DeviceCall call;
+    int rc = call.bind(s, args);
+    if (rc) return rc;
+    gnxr_scene *r = call.r;
     // ids alone come from the lowest sample of the range: nothing else is traced then
     const bool ids_only = !out->d_albedo && !out->d_normal && !out->d_shading_normal && !out->d_depth;
     const int W = p->width, H = p->height, s_begin = p->spp_begin, s_end = ids_only ? p->spp_begin + 1 : (p->spp_end > 0 ? p->spp_end : p->spp), ns = s_end - s_begin;
 
     std::lock_guard<std::recursive_mutex> lock(r->render_mutex);   // as render_one: one render, Li, views or feature-buffer call per handle at a time
-    int rc = r->bind();
-    if (rc) return rc;
-    struct Rebind { gnxr_scene *s; bool on; ~Rebind() { if (on) (void)s->bind(); } } rebind{s, r != s};   // leave the primary device current
     const auto t_start = std::chrono::steady_clock::now();
     hipStream_t st = (hipStream_t)hip_stream;
     DScene sc = query_device_scene(r);
     sc.st.perms = r->perms.p; sc.st.primes = r->primes.p; sc.st.prime_sums = r->prime_sums.p; sc.st.prime_magic = r->prime_magic.p;
     sc.st.h = make_halton(W, H);
-    // the device sampler keeps the Halton index in 32 bits (render_one's rule, for the camera dimensions alone)
-    const unsigned long long index_bound = (unsigned long long)sc.st.h.stride * ((unsigned long long)p->spp + 1);
-    if (index_bound >= (1ull << 32)) { set_error("spp too large for 32-bit Halton indices"); return GNXR_ERR_UNSUPPORTED; }
-    sc.st.h.base32_max = (int32_t)std::min<unsigned long long>(0x7fffffffull, 0xffffffffull / index_bound);
+    if ((rc = halton_index_bound(&sc.st.h, p->spp, 1)) != GNXR_OK) return rc;   // (the camera dimensions alone: no array samples)
 
     std::vector<DCamera> h_cams((size_t)n_views);
-    if (cameras) for (int v = 0; v < n_views; ++v) h_cams[v] = make_camera(cameras[v], W, H, camera_media && n_media > 0 ? camera_media[v] : -1);
+    if (cameras) make_view_cameras(cameras, camera_media, n_views, W, H, h_cams.data());
     else h_cams[0] = make_camera(r->cs.camera, W, H, r->cs.camera_medium);
 
     // ---- plan: k samples of every pixel per sub-pass, 32 bytes each; auto: what a share of the free memory holds
@@ -86,13 +63,11 @@ int gnxr_render_aov_device(gnxr_scene *s, const gnxr_render_params *p, const gnx
     const size_t cam_bytes = pad256((size_t)n_views * sizeof(DCamera)), ray_bytes = pad256((size_t)k * npx * sizeof(gnxr_ray)), acc_bytes = pad256(npx * sizeof(float4));
     const bool accA = out->d_albedo != nullptr, accN = out->d_normal || out->d_depth, accS = out->d_shading_normal != nullptr;
     const size_t sums_bytes = acc_bytes * ((accA ? 1 : 0) + (accN ? 1 : 0) + (accS ? 1 : 0));
-    AovScratch scratch;
-    scratch.st = st;
+    StreamScratch scratch;
     {
-        const hipError_t e = hipMallocAsync((void **)&scratch.p, cam_bytes + ray_bytes + sums_bytes, st);
+        const hipError_t e = scratch.alloc(cam_bytes + ray_bytes + sums_bytes, st);
         if (e != hipSuccess) {
             (void)hipGetLastError();
-            scratch.p = nullptr;
             set_error("feature buffers: %zu bytes of scratch (%lld samples of %zu pixels per sub-pass) could not be allocated: %s", cam_bytes + ray_bytes + sums_bytes, k, npx, hipGetErrorString(e));
             return hip_status(e);
         }
@@ -108,10 +83,7 @@ int gnxr_render_aov_device(gnxr_scene *s, const gnxr_render_params *p, const gnx
     static_assert(sizeof(gnxr_ray) == sizeof(gnxr_hit) && offsetof(gnxr_hit, prim) == 0 && offsetof(gnxr_ray, _pad) == 28, "the leaf code overlays gnxr_ray::_pad");
     gnxr_hit *d_codes = reinterpret_cast<gnxr_hit *>(reinterpret_cast<char *>(d_rays) + offsetof(gnxr_ray, _pad));
 
-    struct EventPair {
-        hipEvent_t a = nullptr, b = nullptr;
-        ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    } ev;
+    EventPair ev;
     HIP_TRY(hipEventCreate(&ev.a));
     HIP_TRY(hipEventCreate(&ev.b));
     HIP_TRY(hipEventRecord(ev.a, st));
@@ -134,13 +106,7 @@ int gnxr_render_aov_device(gnxr_scene *s, const gnxr_render_params *p, const gnx
         const long long n = (long long)kk * (long long)npx;
         hipLaunchKernelGGL(k_aov_raygen, dim3(grid_for(n)), dim3(kBlock), 0, st, sc.st, rr, (const DCamera *)d_cams, reinterpret_cast<float4 *>(d_rays), n, s0);
         HIP_TRY(hipGetLastError());
-        if (r->wide_ok) {
-            if ((rc = query_trace4(r, sc, d_rays, n, d_codes, nullptr, false, st)) != GNXR_OK) return rc;
-        } else {   // trees the 4-wide encoding cannot hold: the binary walk (as gnxr_bsdf_device)
-            if (r->stack_size > 32) hipLaunchKernelGGL((k_trace_closest_code<64>), dim3(grid_for(n, 2)), dim3(kBlock), 0, st, sc, (const gnxr_ray *)d_rays, n, d_codes);
-            else hipLaunchKernelGGL((k_trace_closest_code<32>), dim3(grid_for(n, 5)), dim3(kBlock), 0, st, sc, (const gnxr_ray *)d_rays, n, d_codes);
-            HIP_TRY(hipGetLastError());
-        }
+        if ((rc = closest_hit_codes(r, sc, d_rays, n, d_codes, st)) != GNXR_OK) return rc;
         const int first = s0 == s_begin ? 1 : 0, want_depth = out->d_depth ? 1 : 0;
         int2 *ids = reinterpret_cast<int2 *>(out->d_ids);
 #define GX_AOV_RESOLVE(M) case M: hipLaunchKernelGGL((k_aov_resolve<M>), dim3(grid_for(total)), dim3(kBlock), 0, st, sc, at, reinterpret_cast<const float4 *>(d_rays), (int)total, kk, first, acc, want_depth, ids); break;

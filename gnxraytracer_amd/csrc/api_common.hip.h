@@ -68,8 +68,6 @@ struct Knobs {
     static int trace_lds_levels() { GX_ONCE(int, env_set("GNXR_TRACE_LDS_LEVELS") ? std::max(2, env_int("GNXR_TRACE_LDS_LEVELS", 0)) : 64); }
     // GNXR_TRACE_CHUNK: rays a wave takes per atomic, a multiple of 64 (default kTraceChunk).  Once
     static int trace_chunk() { GX_ONCE(int, env_set("GNXR_TRACE_CHUNK") ? std::max(64, env_int("GNXR_TRACE_CHUNK", 0) / 64 * 64) : kTraceChunk); }
-    // GNXR_TRACE_DUAL: 1 = two rays per lane (trace4d_kernel.hip.h; builds with GX_WITH_TRACE4D only; default 0).  Once
-    static bool trace_dual() { GX_ONCE(bool, env_int("GNXR_TRACE_DUAL", 0) != 0); }
     // GNXR_LEAF_BOX_TABLE: set = one-triangle leaves read leaf_boxes instead of their vertices (experiment; default unset).  Once
     static bool leaf_box_table() { GX_ONCE(bool, env_set("GNXR_LEAF_BOX_TABLE")); }
     // GNXR_REGIONS: sub-passes in flight when passes_in_flight is 0 (default 0 = 4).  Once

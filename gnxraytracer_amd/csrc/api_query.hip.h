@@ -1,5 +1,5 @@
 // api_query.hip.h -- the entry points on device memory: batched ray queries, Li for caller rays, views, shading queries.
-// Part of api.hip's translation unit (after api_render.hip.h).
+// Part of api.hip's translation unit (after api_render.hip.h; the calls' front end -- replica choice, scratch, parameter checks -- is api_device_call.hip.h).
 #pragma once
 
 extern "C" {
@@ -12,30 +12,6 @@ extern "C" {
 
 // work items per k_trace4 launch: the kernel counts them in 32 bits (chunk_plan / chunk_range) and keeps a ray's index in an int
 static const long long kQueryLaunchMax = 1ll << 30;
-
-// The copy of `s` on the device that holds `ptr` (nullptr and the error set when `ptr` is not device memory, or no copy lives there).
-// `bytes`: the extent the call reads or writes, checked against the allocation whenever the runtime reports its range.
-static gnxr_scene *query_replica(gnxr_scene *s, const void *ptr, size_t bytes, const char *what) {
-    hipPointerAttribute_t a;
-    const hipError_t e = hipPointerGetAttributes(&a, ptr);
-    (void)hipGetLastError();   // memory the runtime has never seen makes the call fail: that is the answer, not an error of later calls
-    if (e != hipSuccess || a.type != hipMemoryTypeDevice) {
-        set_error("%s is not device memory (host arrays go through gnxr_trace_closest / gnxr_trace_any)", what);
-        return nullptr;
-    }
-    gnxr_scene *r = nullptr;
-    if (s->device == a.device) r = s;
-    for (size_t i = 0; !r && i < s->replicas.size(); ++i) if (s->replicas[i]->device == a.device) r = s->replicas[i].get();
-    if (!r) { set_error("%s lives on device %d, which holds no copy of the scene", what, a.device); return nullptr; }
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)ptr) == hipSuccess && base && (const char *)ptr + bytes > (const char *)base + size) {
-        set_error("%s: %zu bytes from %p run past the end of its allocation (%zu bytes from %p)", what, bytes, ptr, size, (void *)base);
-        return nullptr;
-    }
-    (void)hipGetLastError();
-    return r;
-}
 
 // the tables the walk, the hit record and a BSDF read (device_scene() would also read the light and sampler state, which a render may be rebuilding)
 static DScene query_device_scene(gnxr_scene *r) {
@@ -60,12 +36,11 @@ static int query_trace4(gnxr_scene *r, const DScene &sc, const gnxr_ray *d_rays,
     // scratch of this call: [cursor | pad to 256 B | spill columns of the grid the largest launch uses]
     const TraceLaunch tl = trace_launch(r, true, spheres, std::min<long long>(n, kQueryLaunchMax));
     const size_t spill_ints = tl.spill_needed ? (size_t)(tl.entries - tl.lds_entries) * (size_t)tl.blocks * kBlock : 0;
-    char *scratch = nullptr;
-    HIP_TRY(hipMallocAsync((void **)&scratch, 256 + spill_ints * sizeof(int), st));
-    unsigned int *cursor = reinterpret_cast<unsigned int *>(scratch);
-    int *spill = reinterpret_cast<int *>(scratch + 256);
-    hipError_t e = hipSuccess;
-    for (long long base = 0; base < n && e == hipSuccess; base += kQueryLaunchMax) {
+    StreamScratch scratch;
+    HIP_TRY(scratch.alloc(256 + spill_ints * sizeof(int), st));
+    unsigned int *cursor = reinterpret_cast<unsigned int *>(scratch.p);
+    int *spill = reinterpret_cast<int *>(scratch.p + 256);
+    for (long long base = 0; base < n; base += kQueryLaunchMax) {
         const long long cnt = std::min<long long>(n - base, kQueryLaunchMax);
         const TraceLaunch t = trace_launch(r, true, spheres, cnt);
         QueryArrays qa;
@@ -74,7 +49,7 @@ static int query_trace4(gnxr_scene *r, const DScene &sc, const gnxr_ray *d_rays,
         qa.occluded = any ? occluded + base : nullptr;
         TraceWork w = {};
         w.n_closest = (int)cnt;
-        if ((e = hipMemsetAsync(cursor, 0, sizeof(unsigned int), st)) != hipSuccess) break;
+        HIP_TRY(hipMemsetAsync(cursor, 0, sizeof(unsigned int), st));
 #define GX_QUERY4(S, P, Q) hipLaunchKernelGGL((k_trace4<false, S, P, Q>), dim3(t.blocks), dim3(kBlock), t.lds, st, sc, qa, w, cursor, (Counters *)nullptr, t.lds_entries, spill, kTraceChunk, t.n_top)
 #define GX_QUERY4_SP(Q) do { if (spheres) { if (t.spill_needed) GX_QUERY4(true, true, Q); else GX_QUERY4(true, false, Q); } \
                              else { if (t.spill_needed) GX_QUERY4(false, true, Q); else GX_QUERY4(false, false, Q); } } while (0)
@@ -82,11 +57,18 @@ static int query_trace4(gnxr_scene *r, const DScene &sc, const gnxr_ray *d_rays,
         else GX_QUERY4_SP(kT4QueryClosest);
 #undef GX_QUERY4_SP
 #undef GX_QUERY4
-        e = hipGetLastError();
+        HIP_TRY(hipGetLastError());
     }
-    const hipError_t ef = hipFreeAsync(scratch, st);   // stream-ordered: after the launches above
-    HIP_TRY(e);
-    HIP_TRY(ef);
+    return GNXR_OK;
+}
+
+// The leaf code of every ray's closest hit into codes[i].prim, for the calls that shade what the rays hit: k_trace4's closest-hit query
+// on the 4-wide tree, else the binary walk (64 stack entries at 2 blocks per CU, 32 at 5).
+static int closest_hit_codes(gnxr_scene *r, const DScene &sc, const gnxr_ray *d_rays, long long n, gnxr_hit *codes, hipStream_t st) {
+    if (r->wide_ok) return query_trace4(r, sc, d_rays, n, codes, nullptr, false, st);
+    if (r->stack_size > 32) hipLaunchKernelGGL((k_trace_closest_code<64>), dim3(grid_for(n, 2)), dim3(kBlock), 0, st, sc, d_rays, n, codes);
+    else hipLaunchKernelGGL((k_trace_closest_code<32>), dim3(grid_for(n, 5)), dim3(kBlock), 0, st, sc, d_rays, n, codes);
+    HIP_TRY(hipGetLastError());
     return GNXR_OK;
 }
 
@@ -96,29 +78,14 @@ static int trace_device(gnxr_scene *s, const gnxr_ray *d_rays, int64_t n, void *
     if (n == 0) return GNXR_OK;
     if (((uintptr_t)d_rays & 15u) != 0) { set_error("d_rays is not 16-byte aligned (two dwordx4 loads per ray)"); return GNXR_ERR_INVALID; }
     if (!any && ((uintptr_t)out & 3u) != 0) { set_error("d_hits is not 4-byte aligned"); return GNXR_ERR_INVALID; }
-    const size_t out_bytes = (size_t)n * (!any ? sizeof(gnxr_hit) : 1);
-    gnxr_scene *r = query_replica(s, d_rays, (size_t)n * sizeof(gnxr_ray), "d_rays");
-    if (!r) return GNXR_ERR_INVALID;
-    gnxr_scene *ro = query_replica(s, out, out_bytes, !any ? "d_hits" : "d_occluded");
-    if (!ro) return GNXR_ERR_INVALID;
-    if (ro != r) { set_error("d_rays and the output live on different devices"); return GNXR_ERR_INVALID; }
-    int rc = r->bind();
+    const QueryArg args[] = {{d_rays, (size_t)n * sizeof(gnxr_ray), "d_rays"}, {out, (size_t)n * (!any ? sizeof(gnxr_hit) : 1), !any ? "d_hits" : "d_occluded"}};
+    DeviceCall call;
+    int rc = call.bind(s, args);
     if (rc) return rc;
-    struct Rebind { gnxr_scene *s; bool on; ~Rebind() { if (on) (void)s->bind(); } } rebind{s, r != s};   // leave the primary device current
+    gnxr_scene *r = call.r;
     hipStream_t st = (hipStream_t)hip_stream;
     const DScene sc = query_device_scene(r);
-    if (!r->wide_ok) {   // trees the 4-wide encoding cannot hold (or GNXR_BINARY_BVH at creation): the reference's binary walk, same results
-        const int big = r->stack_size > 32;
-        if (!any) {
-            if (big) hipLaunchKernelGGL((k_trace_closest_api<64>), dim3(grid_for(n, 2)), dim3(kBlock), 0, st, sc, d_rays, (long long)n, (gnxr_hit *)out);
-            else hipLaunchKernelGGL((k_trace_closest_api<32>), dim3(grid_for(n, 5)), dim3(kBlock), 0, st, sc, d_rays, (long long)n, (gnxr_hit *)out);
-        } else {
-            if (big) hipLaunchKernelGGL((k_trace_any_api<64>), dim3(grid_for(n, 2)), dim3(kBlock), 0, st, sc, d_rays, (long long)n, (unsigned char *)out);
-            else hipLaunchKernelGGL((k_trace_any_api<32>), dim3(grid_for(n, 5)), dim3(kBlock), 0, st, sc, d_rays, (long long)n, (unsigned char *)out);
-        }
-        HIP_TRY(hipGetLastError());
-        return GNXR_OK;
-    }
+    if (!r->wide_ok) return binary_trace_api(r, sc, d_rays, n, out, any, st);   // same results
     if ((rc = query_trace4(r, sc, d_rays, n, any ? nullptr : (gnxr_hit *)out, any ? (unsigned char *)out : nullptr, any, st)) != GNXR_OK) return rc;
     if (!any) {
         hipLaunchKernelGGL(k_query_finish, dim3(grid_for(n)), dim3(kBlock), 0, st, sc, reinterpret_cast<const float4 *>(d_rays), (long long)n, (gnxr_hit *)out);
@@ -139,25 +106,17 @@ int gnxr_li_device(gnxr_scene *s, const gnxr_render_params *p, const gnxr_ray *d
                    gnxr_stats *stats) {
     if (int rc = ensure_device()) return rc;
     if (!s || !p || n < 0 || (n > 0 && (!d_rays || !d_samples || !d_L))) { set_error("bad argument"); return GNXR_ERR_INVALID; }
-    if (p->spp_begin != 0 || p->spp_end != 0 || p->shard_index != 0 || p->shard_count < 0 || p->shard_count > 1 || p->shard_rows < 0 || p->shard_rows > 1) {
-        set_error("Li for caller rays: spp_begin, spp_end and shard_index must be 0, shard_count and shard_rows 0 or 1 (the records name each ray's sample)");
-        return GNXR_ERR_INVALID;
-    }
+    if (p->spp_begin != 0 || p->spp_end != 0) { set_error("Li for caller rays: spp_begin and spp_end must be 0 (the records name each ray's sample)"); return GNXR_ERR_INVALID; }
+    if (int rc = check_unsharded(*p, "Li for caller rays", "the records name each ray's sample")) return rc;
     if (n == 0) { if (stats) memset(stats, 0, sizeof(*stats)); return GNXR_OK; }
     if ((((uintptr_t)d_rays | (uintptr_t)d_samples | (uintptr_t)d_L) & 15u) != 0) { set_error("d_rays, d_samples and d_L must be 16-byte aligned"); return GNXR_ERR_INVALID; }
-    gnxr_scene *r = query_replica(s, d_rays, (size_t)n * sizeof(gnxr_ray), "d_rays");
-    if (!r) return GNXR_ERR_INVALID;
-    gnxr_scene *rs = query_replica(s, d_samples, (size_t)n * sizeof(gnxr_li_sample), "d_samples");
-    if (!rs) return GNXR_ERR_INVALID;
-    gnxr_scene *rl = query_replica(s, d_L, (size_t)n * 4 * sizeof(float), "d_L");
-    if (!rl) return GNXR_ERR_INVALID;
-    if (rs != r || rl != r) { set_error("d_rays, d_samples and d_L live on different devices"); return GNXR_ERR_INVALID; }
+    const QueryArg args[] = {{d_rays, (size_t)n * sizeof(gnxr_ray), "d_rays"}, {d_samples, (size_t)n * sizeof(gnxr_li_sample), "d_samples"}, {d_L, (size_t)n * 4 * sizeof(float), "d_L"}};
+    DeviceCall call;
+    if (int rc = call.bind(s, args)) return rc;
     gnxr_render_params pp = *p;
     pp.shard_count = 1; pp.shard_rows = 1;
     const RaySource src{d_rays, d_samples, d_L, (long long)n};
-    const int rc = render_one(r, &pp, nullptr, hip_stream, stats, /*reserve_only=*/false, &src);
-    if (r != s) (void)s->bind();   // leave the primary device current
-    return rc;
+    return render_one(call.r, &pp, nullptr, hip_stream, stats, /*reserve_only=*/false, &src);
 }
 
 // ---- many cameras in one render on device memory: gnxr_render_views_device ----
@@ -165,56 +124,27 @@ int gnxr_li_device(gnxr_scene *s, const gnxr_render_params *p, const gnxr_ray *d
 int gnxr_render_views_device(gnxr_scene *s, const gnxr_render_params *p, const gnxr_camera *cameras, const int32_t *camera_media, int32_t n_views, void *d_rgba_out,
                              void *hip_stream, gnxr_stats *stats) {
     if (!s || !p || n_views < 0 || (n_views > 0 && !cameras)) { set_error("bad argument"); return GNXR_ERR_INVALID; }
-    if (p->shard_index != 0 || p->shard_count < 0 || p->shard_count > 1 || p->shard_rows < 0 || p->shard_rows > 1) {
-        set_error("views: shard_index must be 0, shard_count and shard_rows 0 or 1 (a caller that shards splits the list of views)");
-        return GNXR_ERR_INVALID;
-    }
-    if (p->width <= 0 || p->height <= 0 || p->spp <= 0 || p->spp_begin < 0 || p->spp_end > p->spp || (p->spp_end > 0 && p->spp_begin >= p->spp_end) || p->spp_begin >= p->spp ||
-        p->max_depth < 0 || p->max_depth > 250) {
-        set_error("invalid render parameters");
-        return GNXR_ERR_INVALID;
-    }
+    if (int rc = check_unsharded(*p, "views", "a caller that shards splits the list of views")) return rc;
+    if (!image_and_samples_ok(*p) || p->max_depth < 0 || p->max_depth > 250) return invalid_render_params();
     if (n_views == 0) { if (stats) memset(stats, 0, sizeof(*stats)); return GNXR_OK; }
     if (!d_rgba_out || ((uintptr_t)d_rgba_out & 15u) != 0) { set_error("d_rgba_out is null or not 16-byte aligned"); return GNXR_ERR_INVALID; }
-    // a path slot is sample * (n_views * W * H) + pixel in an int, and the traversal's work cursor counts three items per slot in 32 bits
-    const long long kMaxViewPixels = ((1ll << 32) - 1) / 3;
-    const long long total = (long long)n_views * p->width * p->height;
-    if (total > kMaxViewPixels) {
-        set_error("views: n_views * width * height = %lld pixels overflow the 32-bit path indexing (at most %lld per call); split the list of views", total, kMaxViewPixels);
-        return GNXR_ERR_INVALID;
-    }
+    long long total = 0;
+    if (int rc = check_view_pixels(*p, n_views, "views", &total)) return rc;
     if (int rc = ensure_device()) return rc;
-    const int n_media = (int)s->cs.media.size();
-    for (int v = 0; camera_media && v < n_views; ++v)
-        if (camera_media[v] < -1 || camera_media[v] >= n_media) { set_error("views: camera_media[%d] = %d is outside [-1, %d)", v, camera_media[v], n_media); return GNXR_ERR_INVALID; }
-    gnxr_scene *r = query_replica(s, d_rgba_out, (size_t)total * sizeof(float4), "d_rgba_out");
-    if (!r) return GNXR_ERR_INVALID;
+    if (int rc = check_view_media(s, camera_media, n_views, "views")) return rc;
+    const QueryArg args[] = {{d_rgba_out, (size_t)total * sizeof(float4), "d_rgba_out"}};
+    DeviceCall call;
+    if (int rc = call.bind(s, args)) return rc;
     gnxr_render_params pp = *p;
     pp.shard_count = 1; pp.shard_rows = 1;
     const ViewSource vs{cameras, camera_media, (int)n_views};
-    const int rc = render_one(r, &pp, d_rgba_out, hip_stream, stats, /*reserve_only=*/false, nullptr, &vs);
-    if (r != s) (void)s->bind();   // leave the primary device current
-    return rc;
+    return render_one(call.r, &pp, d_rgba_out, hip_stream, stats, /*reserve_only=*/false, nullptr, &vs);
 }
 
 // ---- shading queries on device memory: gnxr_bsdf_device / gnxr_light_sample_device / gnxr_light_le_device (shade_query_kernel.hip.h) ----
 
 // rays of one traversal + k_bsdf_query round: bounds the call's scratch (one gnxr_hit per ray for the leaf codes) at 128 MB whatever n is
 static const long long kBsdfQueryChunk = 1ll << 22;
-
-// The copy of `s` on the device that holds every listed array (nullptr and the error set otherwise)
-struct QueryArg { const void *p; size_t bytes; const char *what; };
-static gnxr_scene *query_replica_all(gnxr_scene *s, const QueryArg *args, int n_args) {
-    gnxr_scene *r = nullptr;
-    for (int i = 0; i < n_args; ++i) {
-        if (!args[i].p) continue;   // an optional array that was not given
-        gnxr_scene *ri = query_replica(s, args[i].p, args[i].bytes, args[i].what);
-        if (!ri) return nullptr;
-        if (r && ri != r) { set_error("%s and %s live on different devices", args[0].what, args[i].what); return nullptr; }
-        r = ri;
-    }
-    return r;
-}
 
 int gnxr_bsdf_device(gnxr_scene *s, const gnxr_ray *d_rays, const float *d_wi, const float *d_u, const float *d_differentials, int64_t n, int32_t flags,
                      gnxr_bsdf_result *d_out, void *hip_stream) {
@@ -226,25 +156,18 @@ int gnxr_bsdf_device(gnxr_scene *s, const gnxr_ray *d_rays, const float *d_wi, c
     const QueryArg args[] = {{d_rays, (size_t)n * sizeof(gnxr_ray), "d_rays"}, {d_wi, (size_t)n * 12, "d_wi"}, {d_u, (size_t)n * 8, "d_u"},
                              {d_differentials, (size_t)n * 48, "d_differentials"}, {d_out, (size_t)n * sizeof(gnxr_bsdf_result), "d_out"}};
     if (int drc = ensure_device()) return drc;
-    gnxr_scene *r = query_replica_all(s, args, 5);
-    if (!r) return GNXR_ERR_INVALID;
-    int rc = r->bind();
+    DeviceCall call;
+    int rc = call.bind(s, args);
     if (rc) return rc;
-    struct Rebind { gnxr_scene *s; bool on; ~Rebind() { if (on) (void)s->bind(); } } rebind{s, r != s};   // leave the primary device current
+    gnxr_scene *r = call.r;
     hipStream_t st = (hipStream_t)hip_stream;
     const DScene sc = query_device_scene(r);
-    gnxr_hit *codes = nullptr;
-    HIP_TRY(hipMallocAsync((void **)&codes, (size_t)std::min<long long>(n, kBsdfQueryChunk) * sizeof(gnxr_hit), st));
-    hipError_t e = hipSuccess;
-    for (long long base = 0; base < n && rc == GNXR_OK && e == hipSuccess; base += kBsdfQueryChunk) {
+    StreamScratch scratch;
+    HIP_TRY(scratch.alloc((size_t)std::min<long long>(n, kBsdfQueryChunk) * sizeof(gnxr_hit), st));
+    gnxr_hit *codes = reinterpret_cast<gnxr_hit *>(scratch.p);
+    for (long long base = 0; base < n; base += kBsdfQueryChunk) {
         const long long cnt = std::min<long long>(n - base, kBsdfQueryChunk);
-        if (r->wide_ok) rc = query_trace4(r, sc, d_rays + base, cnt, codes, nullptr, false, st);
-        else {   // trees the 4-wide encoding cannot hold: the binary walk
-            if (r->stack_size > 32) hipLaunchKernelGGL((k_trace_closest_code<64>), dim3(grid_for(cnt, 2)), dim3(kBlock), 0, st, sc, d_rays + base, cnt, codes);
-            else hipLaunchKernelGGL((k_trace_closest_code<32>), dim3(grid_for(cnt, 5)), dim3(kBlock), 0, st, sc, d_rays + base, cnt, codes);
-            e = hipGetLastError();
-        }
-        if (rc != GNXR_OK || e != hipSuccess) break;
+        if ((rc = closest_hit_codes(r, sc, d_rays + base, cnt, codes, st)) != GNXR_OK) return rc;
         BsdfQueryArrays q;
         q.rays = reinterpret_cast<const float4 *>(d_rays + base);
         q.codes = codes;
@@ -253,12 +176,8 @@ int gnxr_bsdf_device(gnxr_scene *s, const gnxr_ray *d_rays, const float *d_wi, c
         q.diffs = d_differentials ? d_differentials + 12 * base : nullptr;
         q.out = reinterpret_cast<float4 *>(d_out + base);
         hipLaunchKernelGGL((k_bsdf_query<LM_ALL>), dim3(grid_for(cnt)), dim3(kBlock), 0, st, sc, q, cnt, (int)flags);
-        e = hipGetLastError();
+        HIP_TRY(hipGetLastError());
     }
-    const hipError_t ef = hipFreeAsync(codes, st);   // stream-ordered: after the launches above
-    if (rc != GNXR_OK) return rc;
-    HIP_TRY(e);
-    HIP_TRY(ef);
     return GNXR_OK;
 }
 
@@ -279,20 +198,19 @@ int gnxr_light_sample_device(gnxr_scene *s, const float *d_queries, int64_t n, i
     if ((((uintptr_t)d_queries | (uintptr_t)d_out) & 15u) != 0) { set_error("d_queries and d_out must be 16-byte aligned"); return GNXR_ERR_INVALID; }
     const QueryArg args[] = {{d_queries, (size_t)n * 48, "d_queries"}, {d_out, (size_t)n * sizeof(gnxr_light_result), "d_out"}};
     if (int drc = ensure_device()) return drc;
-    gnxr_scene *r = query_replica_all(s, args, 2);
-    if (!r) return GNXR_ERR_INVALID;
-    // the selection table belongs to the renders of the copy it lives on: the primary's lock, then that copy's (render_sharded's order;
-    // gnxr_li_device on a replica holds the replica's alone)
+    DeviceCall call;
+    int rc = call.bind(s, args);
+    if (rc) return rc;
+    gnxr_scene *r = call.r;
+    // the selection table belongs to the renders of the copy it lives on: both locks, in DeviceCall's order
     std::lock_guard<std::recursive_mutex> lock(s->render_mutex);
     std::lock_guard<std::recursive_mutex> lock_r(r->render_mutex);
-    int rc = r->bind();
-    if (rc) return rc;
-    struct Rebind { gnxr_scene *s; bool on; ~Rebind() { if (on) (void)s->bind(); } } rebind{s, r != s};
     hipStream_t st = (hipStream_t)hip_stream;
     DLightTables lt;
     if ((rc = query_light_tables(r, strategy, &lt)) != GNXR_OK) return rc;
-    unsigned long long *d_bad = nullptr, bad = 0;
-    HIP_TRY(hipMallocAsync((void **)&d_bad, sizeof(unsigned long long), st));
+    StreamScratch scratch;
+    HIP_TRY(scratch.alloc(sizeof(unsigned long long), st));
+    unsigned long long *d_bad = reinterpret_cast<unsigned long long *>(scratch.p), bad = 0;
     hipError_t e = hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), st);
     if (e == hipSuccess) {
         hipLaunchKernelGGL((k_light_sample_query<LT_ALL>), dim3(grid_for(n)), dim3(kBlock), 0, st, lt, reinterpret_cast<const float4 *>(d_queries), (long long)n,
@@ -300,10 +218,8 @@ int gnxr_light_sample_device(gnxr_scene *s, const float *d_queries, int64_t n, i
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, st);
-    const hipError_t ef = hipFreeAsync(d_bad, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);   // the status has to come back
     HIP_TRY(e);
-    HIP_TRY(ef);
     if (bad) {
         set_error("gnxr_light_sample_device: query %llu names a light outside [0, %d); its record is 0", (unsigned long long)~bad, lt.n_lights);
         return GNXR_ERR_INVALID;
@@ -318,11 +234,9 @@ int gnxr_light_le_device(gnxr_scene *s, int32_t light, const gnxr_ray *d_rays, i
     if (((uintptr_t)d_rays & 15u) != 0 || ((uintptr_t)d_le & 3u) != 0) { set_error("d_rays must be 16-byte aligned, d_le 4-byte aligned"); return GNXR_ERR_INVALID; }
     const QueryArg args[] = {{d_rays, (size_t)n * sizeof(gnxr_ray), "d_rays"}, {d_le, (size_t)n * 12, "d_le"}};
     if (int drc = ensure_device()) return drc;
-    gnxr_scene *r = query_replica_all(s, args, 2);
-    if (!r) return GNXR_ERR_INVALID;
-    int rc = r->bind();
-    if (rc) return rc;
-    struct Rebind { gnxr_scene *s; bool on; ~Rebind() { if (on) (void)s->bind(); } } rebind{s, r != s};
+    DeviceCall call;
+    if (int rc = call.bind(s, args)) return rc;
+    const gnxr_scene *r = call.r;
     // Le reads the lights and the environment map, not the selection table: nothing here that a render rebuilds, so no lock
     const DLightTables lt = r->light_tables_static();
     hipLaunchKernelGGL((k_light_le_query<LT_ALL>), dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)hip_stream, lt, (int)light, reinterpret_cast<const float4 *>(d_rays),

@@ -96,11 +96,7 @@ static int plan_render(const CompiledScene &cs, const gnxr_render_params *pin, c
     if (p.shard_count <= 0) p.shard_count = 1;
     if (p.shard_rows <= 0) p.shard_rows = 1;
     if (p.spp_end <= 0) p.spp_end = p.spp;
-    if (p.width <= 0 || p.height <= 0 || p.spp <= 0 || p.spp_begin < 0 || p.spp_end > p.spp || p.spp_begin >= p.spp_end || p.shard_index < 0 ||
-        p.shard_index >= p.shard_count || p.max_depth < 0 || p.max_depth > 250) {
-        set_error("invalid render parameters");
-        return GNXR_ERR_INVALID;
-    }
+    if (!image_and_samples_ok(p) || p.shard_index < 0 || p.shard_index >= p.shard_count || p.max_depth < 0 || p.max_depth > 250) return invalid_render_params();
     if (p.integrator != GNXR_INTEGRATOR_PATH && p.integrator != GNXR_INTEGRATOR_VOLPATH && p.integrator != GNXR_INTEGRATOR_WHITTED &&
         p.integrator != GNXR_INTEGRATOR_DIRECT) {
         set_error("unknown integrator %d", p.integrator);
@@ -243,7 +239,7 @@ int RenderState::reserve(const RenderPlan &pl) {
     }
 #undef AL
     // global part of k_trace's traversal stacks (the deepest walk either BVH layout can need), sized for a full grid
-    if ((rc = trace_spill.alloc((size_t)g_num_cus * g_trace_blocks_per_cu * kBlock * (size_t)pl.spill_entries * 2)) != GNXR_OK) return rc;   // (x 2: k_trace4d keeps two columns per lane)
+    if ((rc = trace_spill.alloc((size_t)g_num_cus * g_trace_blocks_per_cu * kBlock * (size_t)pl.spill_entries)) != GNXR_OK) return rc;
     if (!pl.caller_rays && (rc = accum.alloc(pl.npix)) != GNXR_OK) return rc;
     const size_t max_tiles = (cap + kCompactTile - 1) / kCompactTile;
     if (tile_desc.n < kCompactMaxOut * max_tiles || !tile_desc.p) {   // fresh memory: every descriptor "not ready" (tag 0 belongs to no compaction)
@@ -364,30 +360,12 @@ void RenderRun::launch_trace(TraceWork w, int n_sh, int n_mis, bool count_rays) 
     (void)hipMemsetAsync(&dctr->cursor, 0, sizeof(unsigned int), stream);
     const bool wide = s->wide_ok && !counting;
     const TraceLaunch tl = trace_launch(s, wide, spheres, total);
-    const int entries = tl.entries, lds_entries = tl.lds_entries, n_top = tl.n_top, blocks = tl.blocks;
-    const bool spill_needed = tl.spill_needed;
-    const size_t lds = tl.lds;
     if (timing) timer.begin(0, stream);
     // rays per atomic: at most kTraceChunk; the kernel shrinks the chunk for thin launches so that every wave gets one (trace_chunk())
     const int chunk = Knobs::trace_chunk();
-#define GX_TRACE(C, W, S) hipLaunchKernelGGL((k_trace<C, W, S>), dim3(blocks), dim3(kBlock), lds, stream, sc, pa, w, &dctr->cursor, dctr, lds_entries, st.trace_spill.p, chunk)
-#define GX_TRACE4(C, S, P) hipLaunchKernelGGL((k_trace4<C, S, P>), dim3(blocks), dim3(kBlock), lds, stream, sc, pa, w, &dctr->cursor, dctr, lds_entries, st.trace_spill.p, chunk, n_top)
-#define GX_TRACE4_CS(C, S) do { if (spill_needed) GX_TRACE4(C, S, true); else GX_TRACE4(C, S, false); } while (0)
-#if GX_WITH_TRACE4D
-    if (wide && Knobs::trace_dual() && !count_wide) {   // two rays per lane (trace4d_kernel.hip.h)
-        const int dper_cu = GX_T4D_WAVES;   // blocks of 4 waves per CU = waves per SIMD
-        const size_t dfixed = (size_t)(kRayRecDwords + (spheres ? 1 : 0)) * kRqStride * sizeof(int) + (size_t)kTopCacheD * 128 + 128;
-        const int dlds_entries = std::min(std::min(entries, Knobs::trace_lds_levels()), std::max(2, (int)(((160 * 1024) / dper_cu - 1024 - dfixed) / (2 * kBlock * sizeof(int)))));
-        const int dspill_levels = std::max(0, entries - dlds_entries);
-        const size_t dlds = (size_t)2 * dlds_entries * kBlock * sizeof(int) + dfixed;
-        const int dn_top = (int)std::min<size_t>(kTopCacheD, s->cs.root4 >= 0 ? s->cs.nodes4.size() : 0);
-        const int dblocks = (int)std::min<long long>((long long)g_num_cus * dper_cu, (total + 2 * kBlock - 1) / (2 * kBlock));
-#define GX_TRACE4D(S, P) hipLaunchKernelGGL((k_trace4d<S, P>), dim3(std::max(1, dblocks)), dim3(kBlock), dlds, stream, sc, pa, w, &dctr->cursor, dctr, dlds_entries, dspill_levels, st.trace_spill.p, chunk, dn_top)
-        if (spheres) { if (dspill_levels > 0) GX_TRACE4D(true, true); else GX_TRACE4D(true, false); }
-        else { if (dspill_levels > 0) GX_TRACE4D(false, true); else GX_TRACE4D(false, false); }
-#undef GX_TRACE4D
-    } else
-#endif
+#define GX_TRACE(C, W, S) hipLaunchKernelGGL((k_trace<C, W, S>), dim3(tl.blocks), dim3(kBlock), tl.lds, stream, sc, pa, w, &dctr->cursor, dctr, tl.lds_entries, st.trace_spill.p, chunk)
+#define GX_TRACE4(C, S, P) hipLaunchKernelGGL((k_trace4<C, S, P>), dim3(tl.blocks), dim3(kBlock), tl.lds, stream, sc, pa, w, &dctr->cursor, dctr, tl.lds_entries, st.trace_spill.p, chunk, tl.n_top)
+#define GX_TRACE4_CS(C, S) do { if (tl.spill_needed) GX_TRACE4(C, S, true); else GX_TRACE4(C, S, false); } while (0)
     if (wide) {   // the 4-wide walk (trace4_kernel.hip.h); count_wide: its counting variant
         if (spheres) { if (count_wide) GX_TRACE4_CS(true, true); else GX_TRACE4_CS(false, true); }
         else { if (count_wide) GX_TRACE4_CS(true, false); else GX_TRACE4_CS(false, false); }
@@ -913,10 +891,7 @@ static int render_one(gnxr_scene *s, const gnxr_render_params *pin, void *d_rgba
     hipStream_t stream = (hipStream_t)hip_stream;
     if ((rc = s->ensure_grid(p.light_strategy)) != GNXR_OK) return rc;
     DScene sc = s->device_scene(p.width, p.height);
-    // the device sampler keeps the Halton index in 32 bits
-    if ((unsigned long long)sc.st.h.stride * ((unsigned long long)p.spp * pl.max_light_samples + 1) >= (1ull << 32)) { set_error("spp too large for 32-bit Halton indices"); return GNXR_ERR_UNSUPPORTED; }
-    // every index this render draws is below stride * (spp * n + 1); reversedDigits of base b stays below b * index (device_sampler.h)
-    sc.st.h.base32_max = (int32_t)std::min<unsigned long long>(0x7fffffffull, 0xffffffffull / ((unsigned long long)sc.st.h.stride * ((unsigned long long)p.spp * pl.max_light_samples + 1)));
+    if ((rc = halton_index_bound(&sc.st.h, p.spp, pl.max_light_samples)) != GNXR_OK) return rc;
     if (pl.whitted) sc.materials = s->materials_single.p + 1;
     sc.escape_class = pl.escape_queue ? 3 : 0;
     DRender r;
@@ -925,10 +900,8 @@ static int render_one(gnxr_scene *s, const gnxr_render_params *pin, void *d_rgba
     bool views_mixed_media = false;
     if (views) {
         s->h_view_cams.resize(std::max<size_t>(s->h_view_cams.size(), (size_t)views->n_views));
-        for (int v = 0; v < views->n_views; ++v) {
-            s->h_view_cams[v] = make_camera(views->cameras[v], p.width, p.height, views->media ? views->media[v] : -1);
-            if (s->h_view_cams[v].medium != s->h_view_cams[0].medium) views_mixed_media = true;
-        }
+        make_view_cameras(views->cameras, views->media, views->n_views, p.width, p.height, s->h_view_cams.data());
+        for (int v = 1; v < views->n_views; ++v) if (s->h_view_cams[v].medium != s->h_view_cams[0].medium) views_mixed_media = true;
         r.cam = s->h_view_cams[0];
     } else {
         r.cam = make_camera(s->cs.camera, p.width, p.height, s->cs.camera_medium);
@@ -952,10 +925,7 @@ static int render_one(gnxr_scene *s, const gnxr_render_params *pin, void *d_rgba
     if (!src) HIP_TRY(hipMemsetAsync(s->st.accum.p, 0, sizeof(float4) * r.npix, stream));
     HIP_TRY(hipMemsetAsync(run.dctr, 0, sizeof(Counters), stream));
     HIP_TRY(hipMemsetAsync(s->st.compact_ticket.p, 0, 2 * sizeof(unsigned int), stream));   // once per render; from pass to pass k_compact zeroes its successor's counter
-    struct EventPair {   // destroyed on every exit path
-        hipEvent_t a = nullptr, b = nullptr;
-        ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    } ev;
+    EventPair ev;
     HIP_TRY(hipEventCreate(&ev.a));
     HIP_TRY(hipEventCreate(&ev.b));
     HIP_TRY(hipEventRecord(ev.a, stream));
@@ -993,7 +963,7 @@ static int render_sharded(gnxr_scene *s, const gnxr_render_params *pin, void *d_
     if (base.shard_count <= 0) base.shard_count = 1;
     if (base.shard_rows <= 0) base.shard_rows = 1;
     if (base.shard_rows != 1) { set_error("multi-device rendering deals single rows: shard_rows must be 1"); return GNXR_ERR_UNSUPPORTED; }
-    if (base.width <= 0 || base.height <= 0 || base.shard_index < 0 || base.shard_index >= base.shard_count) { set_error("invalid render parameters"); return GNXR_ERR_INVALID; }
+    if (base.width <= 0 || base.height <= 0 || base.shard_index < 0 || base.shard_index >= base.shard_count) return invalid_render_params();
     std::lock_guard<std::recursive_mutex> lock(s->render_mutex);
     const size_t npx = (size_t)base.width * base.height;
     std::vector<int> rcs(nd, GNXR_OK);

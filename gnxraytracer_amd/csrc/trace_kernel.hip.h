@@ -46,7 +46,7 @@ GX_DEV int trace_chunk(unsigned total, int chunk_max) {
     return (int)min((unsigned)chunk_max, max(64u, per));
 }
 
-// Hand-out schedule of a launch's work items (k_trace4 / k_trace4d).  The global cursor counts CHUNKS, one atomic per fetch, and chunk v
+// Hand-out schedule of a launch's work items (k_trace4).  The global cursor counts CHUNKS, one atomic per fetch, and chunk v
 // maps to a range of items by position: `c`-item chunks (512, or a wave's even share when the launch is thin) for most of the launch,
 // then 128-item and finally 64-item chunks for the last ~1.5 chunks' worth of work per wave -- so the waves of a launch finish within a
 // 64-ray batch of each other instead of within a 512-ray chunk (~0.15 ms per launch: nothing for a 265 M-ray launch, 3 - 4 % of the 25 M-ray
