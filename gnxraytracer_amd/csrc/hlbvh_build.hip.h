@@ -11,7 +11,8 @@
 // instead of by recursion.  Bounds are unions (min / max: exact in any order), fitted bottom-up.  buildUpperSAH's partition decides only
 // WHICH roots go left -- bucket counts, bucket boxes and costs do not depend on the order inside a range -- so its std::partition is
 // replaced by a scan-based one.  The result is the reference's tree node for node (tests/test_gpu_parity.py::
-// test_hlbvh_build_matches_reference compares the flattened LinearBVHNode[] and the primitive order with a dump of the compiled reference).
+// test_hlbvh_build_matches_reference compares the flattened LinearBVHNode[] and the primitive order with a dump of the compiled reference;
+// tests/test_hlbvh_build.py compares them with a sequential numpy restatement of the builder from 1 to 2 200 000 primitives).
 #pragma once
 #include <hip/hip_runtime.h>
 

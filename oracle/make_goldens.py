@@ -412,6 +412,15 @@ def hlbvh_goldens():
         assert same.all()
     out["cfg"] = np.array([64, 48, 8, 5], np.int32)
     save("bvh_hlbvh.npz", **out)
+    # above one sort tile of the device build (2048 primitives): the synthetic dragon at 6000 triangles in the Cornell box, tree only
+    # (tests/test_hlbvh_build.py pins its numpy restatement of the builder and the device build to it)
+    b = scenes.dragon_cornell(6000, "glass+metal", mesh_path=scenes.synthetic_mesh_path(6000))
+    b.set_bvh_split_method("hlbvh")
+    raw = ol.run_ref(scene_file(b, "hlbvh_6k"), "bvh", None)
+    nn = struct.unpack("<i", raw[:4])[0]
+    rec = np.frombuffer(raw[4:4 + nn * 36], np.uint8).reshape(nn, 36)
+    save("bvh_hlbvh_6k.npz", bounds=rec[:, :24].copy().view(np.float32).reshape(nn, 6), meta=rec[:, 24:].copy().view(np.int32).reshape(nn, 3),
+         order=np.frombuffer(raw[4 + nn * 36:], np.int32).copy())
 
 
 # ---------------------------------------------------------------- 18: the reference's Resources/ inputs (tests/test_reference_assets.py)

@@ -760,7 +760,8 @@ def test_light_grid_with_many_lights(gpu):
 def test_hlbvh_build_matches_reference(gpu, name):
     """GNXR_BVH_HLBVH: Morton codes, radix sort, LBVH treelets and the SAH upper tree, all built on the device
     (csrc/hlbvh_build.hip.h), must give the LinearBVHNode[] and primitive order of the reference's BVHAccel(prims, 1, SplitMethod::HLBVH), bit for bit; rendering
-    through it gives the reference's image and ray counts, and the traversal statistics of the oracle walking the same tree."""
+    through it gives the reference's image and ray counts, and the traversal statistics of the oracle walking the same tree.
+    Both dumps fit one sort tile of the build: tests/test_hlbvh_build.py covers it beyond that."""
     g = golden("bvh_hlbvh.npz")
     W, H, spp, depth = (int(v) for v in g["cfg"])
     b = scenes.smooth_cornell(os.path.join(GOLDEN, "tex_smile_96x80.hdr")) if name == "smooth" else \
