@@ -362,9 +362,16 @@ class Scene:
                 stream = torch.cuda.current_stream(xyz.device)
         else:
             raise ValueError(f"update_vertices: expected a numpy array or a torch tensor, got {type(xyz).__name__}")
-        if stream is not None and not isinstance(stream, int):
-            stream = stream.cuda_stream   # a torch.cuda.Stream
+        stream = _stream_handle("update_vertices", stream)
         _check(lib().gnxr_scene_update_vertices(self._h, int(first_vertex), int(xyz.shape[0]), C.c_void_p(ptr or None), C.c_void_p(stream or None)))
+
+    def rebuild_bvh(self, stream=None):
+        """Rebuild the BVH on the device over the vertices the scene holds now (after update_vertices): the HLBVH tree a new Scene over
+        those vertices would get, with materials, textures, tables and the reserved path state kept.  `stream`: None (the null stream),
+        a torch.cuda.Stream or a hipStream_t as a non-negative integer (TypeError / ValueError otherwise); the work is ordered after what it
+        holds."""
+        handle = _stream_handle("rebuild_bvh", stream)
+        _check(lib().gnxr_scene_rebuild_bvh(self._h, C.c_void_p(handle or None)))
 
     def set_camera(self, eye=(0, 0, 5), look=(0, 0, 0), up=(0, 1, 0), fov=90.0, lens_radius=0.0, focal_distance=3.0, orthographic=False, medium=-1):
         """The camera of SceneBuilder.set_camera (and the medium it sits in, -1 == none) for later renders."""
@@ -380,6 +387,15 @@ class Scene:
         ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
         _check(lib().gnxr_scene_bvh(self._h, bounds.ctypes.data_as(C.POINTER(C.c_float)), ip(meta), ip(order), n.value, C.byref(n)))
         return bounds, meta, order
+
+    def bvh4(self):
+        """Test hook: (nodes [n, 32] uint32 = the 128-byte DNode4 records of the first device, root reference, worst-case stack entries)
+        of the 4-wide tree."""
+        n, root4, need = C.c_int64(0), C.c_int32(0), C.c_int32(0)
+        _check(lib().gnxr_scene_bvh4(self._h, None, 0, C.byref(n), C.byref(root4), C.byref(need)))
+        nodes = np.zeros((n.value, 32), np.uint32)
+        _check(lib().gnxr_scene_bvh4(self._h, C.c_void_p(nodes.ctypes.data), n.value, C.byref(n), C.byref(root4), C.byref(need)))
+        return nodes, root4.value, need.value
 
     def light_grid_table(self, strategy="spatial", on_host=False):
         """Test hook: the light-selection table (device-built or host-built)."""
@@ -534,6 +550,23 @@ def rays_tensor(o, d, tmax=float("inf")):
     r[:, 3] = torch.as_tensor(tmax, dtype=torch.float32, device=o.device)
     r[:, 4:7] = d
     return r
+
+
+def _stream_handle(what, stream):
+    """`stream` of the scene-editing calls -- None (the null stream), a torch.cuda.Stream or a hipStream_t as an integer -- as an int;
+    TypeError for anything else, ValueError for a negative handle, both before the library is reached."""
+    import numbers
+    if stream is None:
+        return 0
+    if isinstance(stream, numbers.Integral) and not isinstance(stream, bool):
+        handle = int(stream)
+    elif isinstance(getattr(stream, "cuda_stream", None), int):
+        handle = stream.cuda_stream   # a torch.cuda.Stream
+    else:
+        raise TypeError(f"{what}: stream must be None, a torch.cuda.Stream or a hipStream_t as an integer, got {type(stream).__name__}")
+    if handle < 0:
+        raise ValueError(f"{what}: a hipStream_t is not negative, got {handle}")
+    return handle
 
 
 def _stream_pair(stream, device):

@@ -142,6 +142,7 @@ PROTOTYPES = {
     "gnxr_scene_destroy": (None, [VP]),
     "gnxr_scene_info": (C.c_int, [VP, P(i32), P(i32), P(i32)]),
     "gnxr_scene_update_vertices": (C.c_int, [VP, i32, i32, VP, VP]),   # xyz: host or device address
+    "gnxr_scene_rebuild_bvh": (C.c_int, [VP, VP]),   # scene, hipStream_t
     "gnxr_scene_set_camera": (C.c_int, [VP, P(Camera), i32]),
     "gnxr_render": (C.c_int, [VP, P(RenderParams), P(f32), P(Stats)]),
     "gnxr_render_device": (C.c_int, [VP, P(RenderParams), VP, VP, P(Stats)]),
@@ -197,6 +198,7 @@ PROTOTYPES = {
     "gnxr_builder_set_triangle_tangents": (C.c_int, [VP, i32, i32, P(f32)]),
     "gnxr_builder_set_bvh_split_method": (C.c_int, [VP, i32]),
     "gnxr_scene_bvh": (C.c_int, [VP, P(f32), P(i32), P(i32), i64, P(i64)]),
+    "gnxr_scene_bvh4": (C.c_int, [VP, VP, i64, P(i64), P(i32), P(i32)]),
     "gnxr_builder_set_camera": (C.c_int, [VP, P(Camera)]),
     "gnxr_builder_desc": (C.c_int, [VP, P(SceneDesc)]),
     "gnxr_write_synthetic_3d": (C.c_int, [C.c_char_p, i32, u32]),

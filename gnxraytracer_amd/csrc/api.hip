@@ -1,6 +1,6 @@
 // api.hip -- C ABI of libgnxr.so (include/gnxr.h): one translation unit.  This file keeps initialisation, scene creation and editing,
 // the render entry points and the host-memory probes; the rest lives in the api_*.hip.h headers included below (shared pieces, gnxr_scene,
-// the HLBVH build driver, the peak probes, the front end of the calls on device memory, the render path, the entry points on device memory).  One process drives one GPU (gnxr_init
+// the HLBVH build driver, the in-place BVH rebuild, the peak probes, the front end of the calls on device memory, the render path, the entry points on device memory).  One process drives one GPU (gnxr_init
 // binds the device); multi-GPU runs are one process per GPU with the image rows sharded by gnxr_render_params.
 #include <hip/hip_runtime.h>
 
@@ -18,6 +18,7 @@
 #include "trace4_kernel.hip.h"
 #include "hlbvh_build.hip.h"
 #include "refit_kernel.hip.h"
+#include "rebuild_kernel.hip.h"
 #include "li_kernel.hip.h"
 #include "views_kernel.hip.h"
 #include "shade_query_kernel.hip.h"
@@ -379,6 +380,7 @@ int gnxr_trace_any(gnxr_scene *s, const gnxr_ray *rays, int64_t n, uint8_t *occl
 
 }  // extern "C"
 
+#include "api_rebuild.hip.h"
 #include "api_query.hip.h"
 #include "api_aov.hip.h"
 

@@ -96,9 +96,11 @@ struct gnxr_scene {
     // gnxr_render_views_device: the host copy of st.view_cams (what the stream-ordered upload reads; both only grow)
     std::vector<DCamera> h_view_cams;
     bool host_bvh_stale = false;         // after an update cs.nodes / nodes4 / tris / leaf_boxes lag the device until sync_host_bvh()
+    bool host_order_stale = false;       // after gnxr_scene_rebuild_bvh the host copies of what is held in leaf or node order lag too (the upd_* tables are current)
 
     int bind() const { HIP_TRY(hipSetDevice(device)); return GNXR_OK; }
-    // the host copies of the geometry tables, downloaded on demand after gnxr_scene_update_vertices (only readers pay for them)
+    // the host copies of the geometry tables, downloaded on demand after gnxr_scene_update_vertices / gnxr_scene_rebuild_bvh (only
+    // readers pay for them; the rebuild has already given the vectors their new sizes)
     int sync_host_bvh() {
         if (!host_bvh_stale) return GNXR_OK;
         if (int rc = bind()) return rc;
@@ -106,6 +108,18 @@ struct gnxr_scene {
         HIP_TRY(hipMemcpy(cs.nodes4.data(), nodes4.p, cs.nodes4.size() * sizeof(DNode4), hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(cs.tris.data(), tris.p, cs.tris.size() * sizeof(DTri), hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(cs.leaf_boxes.data(), leaf_boxes.p, cs.leaf_boxes.size() * sizeof(float), hipMemcpyDeviceToHost));
+        if (host_order_stale) {
+            HIP_TRY(hipMemcpy(cs.corner_vertex.data(), upd_corner.p, cs.corner_vertex.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(cs.node_parent.data(), upd_parent.p, cs.node_parent.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(cs.node4_src.data(), upd_node4_src.p, cs.node4_src.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(cs.tri_class.data(), tri_class.p, cs.tri_class.size(), hipMemcpyDeviceToHost));
+            if (!cs.tri_media.empty()) HIP_TRY(hipMemcpy(cs.tri_media.data(), tri_media.p, cs.tri_media.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+            if (!cs.tri_uv.empty()) HIP_TRY(hipMemcpy(cs.tri_uv.data(), tri_uv.p, cs.tri_uv.size() * sizeof(float), hipMemcpyDeviceToHost));
+            if (!cs.tri_n.empty()) HIP_TRY(hipMemcpy(cs.tri_n.data(), tri_n.p, cs.tri_n.size() * sizeof(float), hipMemcpyDeviceToHost));
+            if (!cs.tri_s.empty()) HIP_TRY(hipMemcpy(cs.tri_s.data(), tri_s.p, cs.tri_s.size() * sizeof(float), hipMemcpyDeviceToHost));
+            for (size_t li = 0; li < cs.tris.size(); ++li) cs.leaf_of_prim[cs.tris[li].prim] = (int32_t)li;
+            host_order_stale = false;
+        }
         host_bvh_stale = false;
         return GNXR_OK;
     }

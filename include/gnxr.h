@@ -371,6 +371,10 @@ void gnxr_scene_destroy(gnxr_scene *scene);
  * offset / nPrimitives / axis into `meta3`) and the primitive order (`ordered`, n_triangles entries); *n_nodes receives the node
  * count, arrays are filled when node_capacity allows. */
 int gnxr_scene_bvh(const gnxr_scene *scene, float *bounds6, int32_t *meta3, int32_t *ordered, int64_t node_capacity, int64_t *n_nodes);
+/* Test hook: the 4-wide node table of the scene's first device (128 bytes per node into `nodes128`, filled when node_capacity
+ * allows; *n_nodes4 receives the node count) and the quantities the traversal plan is sized from: the root reference and the
+ * worst-case stack entries (either may be NULL). */
+int gnxr_scene_bvh4(const gnxr_scene *scene, void *nodes128, int64_t node_capacity, int64_t *n_nodes4, int32_t *root4, int32_t *stack_need);
 int gnxr_scene_info(const gnxr_scene *scene, int32_t *n_bvh_nodes, int32_t *bvh_max_depth,
                     int32_t *n_light_voxels);
 /* -- editing a scene between frames (the viewer's `while (renderFlag)` loop, RenderThread.cpp:168-186): no recompilation, and the
@@ -384,8 +388,19 @@ int gnxr_scene_info(const gnxr_scene *scene, int32_t *n_bvh_nodes, int32_t *bvh_
  * on the world bound (environment and distant lights, the light-selection table) follows it.  GNXR_ERR_UNSUPPORTED (scene
  * untouched) if a vertex of an emissive (AREA_TRI) triangle would change value; GNXR_ERR_INVALID for a null scene, a null xyz with
  * n_vertices > 0 or a range outside the scene's vertices.  Traversal quality is that of the old topology: after large
- * deformations build the scene again with gnxr_scene_create. */
+ * deformations build the scene again with gnxr_scene_create, or keep the handle and call gnxr_scene_rebuild_bvh. */
 int gnxr_scene_update_vertices(gnxr_scene *scene, int32_t first_vertex, int32_t n_vertices, const float *xyz, void *hip_stream);
+/* Rebuild the triangle BVH of an existing scene over the vertices it currently holds on the device (the state after any number of
+ * gnxr_scene_update_vertices calls), entirely on the device: the tree, its 4-wide form, the primitive order and everything kept in
+ * that order become what gnxr_scene_create builds with bvh_split_method = GNXR_BVH_HLBVH from a description carrying those vertices,
+ * whatever split method the scene was created with.  Materials, textures, environment tables, media, spheres, sampler tables, the
+ * camera and the path state of gnxr_render_reserve stay where they are; the world bound is the one the refits left; the
+ * light-selection table is rebuilt at the next render.  The work is ordered after what hip_stream holds (NULL: the null stream), the
+ * call takes the handle's render lock and returns when every device of the scene holds the new tree.  Besides counts and flags only
+ * the light records (their triangle references follow the new order) cross to the host; no node or triangle table does.  Every failure leaves the scene exactly as it was: GNXR_ERR_INVALID for a null scene or an input on which the
+ * reference's HLBVH build does not terminate (coincident treelet centroids, a leaf over 65535 primitives), GNXR_ERR_UNSUPPORTED for a
+ * tree deeper than the 64-entry traversal stack, GNXR_ERR_OOM. */
+int gnxr_scene_rebuild_bvh(gnxr_scene *scene, void *hip_stream);
 /* Replace the camera (and the medium it sits in, -1 == none) for later renders; same checks as gnxr_scene_create. */
 int gnxr_scene_set_camera(gnxr_scene *scene, const gnxr_camera *camera, int32_t camera_medium);
 
