@@ -342,10 +342,12 @@ class Scene:
         return {"bvh_nodes": n.value, "bvh_max_depth": dmax.value, "light_voxels": nv.value}
 
     # editing between frames (gnxr_scene_update_vertices / gnxr_scene_set_camera)
-    def update_vertices(self, xyz, first_vertex=0, stream=None):
+    def update_vertices(self, xyz, first_vertex=0, stream=None, move_lights=False):
         """Move vertices [first_vertex, first_vertex + len(xyz)) of the description's vertex array to xyz (world space, (n, 3) float32):
         a numpy array (host memory) or a contiguous torch tensor on the scene's device (read on `stream`, by default the current torch
-        stream).  The BVH is refitted on the device with its topology kept; vertices of emissive triangles cannot move."""
+        stream).  The BVH is refitted on the device with its topology kept.  Vertices of emissive triangles cannot move unless
+        move_lights=True (gnxr_scene_update_vertices_ex with GNXR_UPDATE_MOVE_LIGHTS): then the area lights' records follow their
+        triangles on the device."""
         if isinstance(xyz, np.ndarray):
             if xyz.dtype != np.float32 or xyz.ndim != 2 or xyz.shape[1] != 3:
                 raise ValueError(f"update_vertices: expected a float32 array of shape (n, 3), got {xyz.dtype} {xyz.shape}")
@@ -363,7 +365,23 @@ class Scene:
         else:
             raise ValueError(f"update_vertices: expected a numpy array or a torch tensor, got {type(xyz).__name__}")
         stream = _stream_handle("update_vertices", stream)
-        _check(lib().gnxr_scene_update_vertices(self._h, int(first_vertex), int(xyz.shape[0]), C.c_void_p(ptr or None), C.c_void_p(stream or None)))
+        if move_lights:
+            _check(lib().gnxr_scene_update_vertices_ex(self._h, int(first_vertex), int(xyz.shape[0]), C.c_void_p(ptr or None), _abi.UPDATE_MOVE_LIGHTS,
+                                                       C.c_void_p(stream or None)))
+        else:
+            _check(lib().gnxr_scene_update_vertices(self._h, int(first_vertex), int(xyz.shape[0]), C.c_void_p(ptr or None), C.c_void_p(stream or None)))
+
+    def update_lights(self, lights, first_light=0):
+        """Replace lights [first_light, first_light + len(lights)) of the scene's light list by `lights` (gnxr Light records, e.g. copies
+        of SceneBuilder.desc().lights[i] with fields changed): le / two_sided / n_samples of an area light, anything of a point, spot or
+        distant light, centre and radius of the sky box (gnxr_scene_update_lights).  A changed type, a changed triangle or a changed
+        INFINITE record raises GnxrError and leaves the scene as it was."""
+        lights = list(lights)
+        for l in lights:
+            if not isinstance(l, Light):
+                raise ValueError(f"update_lights: lights must be gnxr Light records, got {type(l).__name__}")
+        arr = (Light * max(len(lights), 1))(*lights)
+        _check(lib().gnxr_scene_update_lights(self._h, int(first_light), len(lights), arr))
 
     def rebuild_bvh(self, stream=None):
         """Rebuild the BVH on the device over the vertices the scene holds now (after update_vertices): the HLBVH tree a new Scene over

@@ -18,6 +18,8 @@ INTEGRATOR_PATH, INTEGRATOR_VOLPATH, INTEGRATOR_WHITTED, INTEGRATOR_DIRECT = 0, 
 DIRECT_SAMPLE_ALL, DIRECT_SAMPLE_ONE = 0, 1
 LIGHTS_SPATIAL, LIGHTS_UNIFORM, LIGHTS_POWER = 0, 1, 2
 MEDIUM_HOMOGENEOUS, MEDIUM_GRID = 1, 2
+# flags of gnxr_scene_update_vertices_ex
+UPDATE_MOVE_LIGHTS = 1
 
 f32, i32, u8, i64, u32, u64 = C.c_float, C.c_int32, C.c_uint8, C.c_int64, C.c_uint32, C.c_uint64
 
@@ -142,6 +144,8 @@ PROTOTYPES = {
     "gnxr_scene_destroy": (None, [VP]),
     "gnxr_scene_info": (C.c_int, [VP, P(i32), P(i32), P(i32)]),
     "gnxr_scene_update_vertices": (C.c_int, [VP, i32, i32, VP, VP]),   # xyz: host or device address
+    "gnxr_scene_update_vertices_ex": (C.c_int, [VP, i32, i32, VP, u32, VP]),   # ..., flags (UPDATE_MOVE_LIGHTS), hipStream_t
+    "gnxr_scene_update_lights": (C.c_int, [VP, i32, i32, P(Light)]),
     "gnxr_scene_rebuild_bvh": (C.c_int, [VP, VP]),   # scene, hipStream_t
     "gnxr_scene_set_camera": (C.c_int, [VP, P(Camera), i32]),
     "gnxr_render": (C.c_int, [VP, P(RenderParams), P(f32), P(Stats)]),

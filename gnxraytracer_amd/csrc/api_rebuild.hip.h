@@ -5,7 +5,8 @@
 // buffers swapped into the scene (rebuild_commit, pointer swaps only; the one device write that could still fail, the DTexTables record,
 // is made before them: rebuild_point_tables), so a refused or failed call leaves the scene as it was.  What crosses to the host:
 // the six floats of the centroid bounds, the run / treelet / level counts of the HLBVH stage, the node counts, and the result scalars
-// (rebuild::R_*); and the DLight records, whose host copy refit_world uploads again after the next gnxr_scene_update_vertices.
+// (rebuild::R_*); and the DLight records, whose host copy refit_world uploads again after the next gnxr_scene_update_vertices (and from
+// which gnxr_scene_update_lights takes an area light's corners and tri_leaf).
 #pragma once
 
 namespace {

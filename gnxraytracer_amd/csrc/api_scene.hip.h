@@ -134,7 +134,8 @@ struct gnxr_scene {
     }
 
     // the lights and the environment map: what Sample_Li / Pdf_Li / Le read, without the selection table (grid, grid_table stay zero).
-    // Nothing here changes after the scene is created, except the world radius that gnxr_scene_update_vertices refits (cs.env, distant lights).
+    // After the scene is created only the editing calls change what is behind these pointers: gnxr_scene_update_vertices refits the world radius
+    // (cs.env, distant lights), GNXR_UPDATE_MOVE_LIGHTS moves the area lights, gnxr_scene_update_lights rewrites light records.
     DLightTables light_tables_static() const {
         DLightTables lt = {};
         lt.lights = lights.p;

@@ -110,6 +110,9 @@ bool compile_scene(const gnxr_scene_desc *d, CompiledScene *out, HlbvhBuildFn hl
 // after a refit: the root box of the binary BVH (lo.xyz hi.xyz) -> world_bound (grown by the spheres), the environment light's bounding
 // sphere and the distant lights' radius, computed as compile_scene computes them
 void refit_world_bound(CompiledScene *cs, const float root6[6]);
+// one DLight from its description, as compile_scene makes it (gnxr_scene_update_lights): for AREA_TRI from the corners of its triangle and
+// its leaf index; for INFINITE the record without the environment tables; false (error set) for an unknown type
+bool compile_light(const gnxr_light &l, int index, const Vec3 corners[3], int tri_leaf, const Box3 &world_bound, DLight *out);
 DCamera make_camera(const gnxr_camera &c, int W, int H, int medium);      // camera/Perspective.cpp:114-135, core/Camera.h:54-75
 DHalton make_halton(int W, int H);                                          // samplers/HaltonSampler.cpp:33-60
 // light-selection table: dense restatement of core/LightDistribution.cpp (uniform / power / spatial)

@@ -5,6 +5,7 @@
 //   k_refit_tris     DTri corners whose authored vertex is in the updated range take the new position (.w ids kept)
 //   k_refit_fit      leaf boxes (DNode + leaf_boxes) and interior unions, bottom-up with arrival counters (the form of k_hl_fit)
 //   k_refit_wide     DNode4 child slots <- the binary node each one was collapsed from (CompiledScene::node4_src)
+//   k_refit_lights   GNXR_UPDATE_MOVE_LIGHTS (instead of k_refit_check): corners, area and normal of every AREA_TRI DLight from its triangle
 //
 // Every box is a union of primitive bounds -- an exact componentwise min / max -- so the refitted tree is exactly the LinearBVHNode[]
 // BVHAccel would hold for this topology over the new vertices.  min / max are written as std::min / std::max are (`b < a ? b : a`,
@@ -104,6 +105,35 @@ static __global__ void __launch_bounds__(kB) k_refit_wide(int n_slots, DNode4 *_
         const DNode &g = nodes[s];
         d.lox[k] = g.lo[0]; d.loy[k] = g.lo[1]; d.loz[k] = g.lo[2];
         d.hix[k] = g.hi0; d.hiy[k] = g.hi1; d.hiz[k] = g.hi2;
+    }
+}
+
+// One lane per light; every AREA_TRI record (tri_leaf >= 0) takes p0 p1 p2, area, inv_area and n from its leaf-order triangle, moved or
+// not.  The arithmetic is compile_scene's (scene_compile.cpp, host_math.h: Triangle::Area and the normal of Triangle::Sample), operation for
+// operation, so a record whose corners did not change keeps its bits: fp32 corner differences, a cross product of double products
+// (each product of two floats is exact in double; one rounding in the subtraction, one to float), an fp32 dot product summed left to
+// right, IEEE sqrt and division, area = length / 2, n = cross * (1 / length).  A zero-area triangle gets area 0, inv_area inf and a NaN
+// normal, as gnxr_scene_create gives it.
+static __global__ void __launch_bounds__(kB) k_refit_lights(DLight *__restrict__ lights, int n_lights, const DTri *__restrict__ tris, int n_tris) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_lights; i += gridDim.x * blockDim.x) {
+        DLight &l = lights[i];
+        const int li = l.tri_leaf;
+        if (li < 0 || li >= n_tris) continue;   // not an area light
+        const DTri &t = tris[li];
+        float a[3], b[3];
+        for (int k = 0; k < 3; ++k) {
+            l.p0[k] = t.p0[k]; l.p1[k] = t.p1[k]; l.p2[k] = t.p2[k];
+            a[k] = t.p1[k] - t.p0[k];
+            b[k] = t.p2[k] - t.p0[k];
+        }
+        const double ax = a[0], ay = a[1], az = a[2], bx = b[0], by = b[1], bz = b[2];
+        const float cx = (float)((ay * bz) - (az * by)), cy = (float)((az * bx) - (ax * bz)), cz = (float)((ax * by) - (ay * bx));   // Geometry.h:925-931
+        const float len = __builtin_sqrtf(cx * cx + cy * cy + cz * cz);   // (IEEE under hipcc's defaults: device_math.h gx_sqrt)
+        const float area = 0.5f * len;
+        l.area = area;
+        l.inv_area = 1 / area;
+        const float inv = 1.f / len;   // Vector3::operator/, Geometry.h:206-210
+        l.n[0] = cx * inv; l.n[1] = cy * inv; l.n[2] = cz * inv;
     }
 }
 

@@ -638,6 +638,45 @@ static float distant_radius(const Box3 &wb) {
     return inside ? length(c - wb.hi) : 0.f;
 }
 
+// One DLight record from its description: the per-light part of compile_scene, which gnxr_scene_update_lights runs again on a live scene.
+// AREA_TRI: `corners` are the world-space corners of triangle l.tri as the scene holds them, tri_leaf its leaf index.  INFINITE: the record
+// only; its tables are build_env's.  world_bound: Scene::WorldBound (the delta lights' Preprocess radius).
+bool compile_light(const gnxr_light &l, int index, const Vec3 corners[3], int tri_leaf, const Box3 &world_bound, DLight *out) {
+    DLight &dl = *out;
+    memset(&dl, 0, sizeof(dl));
+    dl.type = l.type; dl.two_sided = l.two_sided; dl.tri_leaf = -1;
+    dl.n_samples = std::max(1, l.n_samples);
+    memcpy(dl.le, l.le, 12);
+    if (l.type == GNXR_LIGHT_AREA_TRI) {
+        dl.tri_leaf = tri_leaf;
+        Vec3 p0 = corners[0], p1 = corners[1], p2 = corners[2];
+        memcpy(dl.p0, &p0, 12); memcpy(dl.p1, &p1, 12); memcpy(dl.p2, &p2, 12);
+        dl.area = (float)(0.5 * length(cross(p1 - p0, p2 - p0)));  // Triangle::Area, Triangle.cpp:455-462
+        dl.inv_area = 1 / dl.area;
+        Vec3 n = normalize(cross(p1 - p0, p2 - p0));                // Triangle::Sample, Triangle.cpp:473
+        memcpy(dl.n, &n, 12);
+    } else if (l.type == GNXR_LIGHT_INFINITE) {
+        dl.env = 1;
+    } else if (l.type == GNXR_LIGHT_SKYBOX) {
+        memcpy(dl.center, l.center, 12);
+        dl.radius = l.radius;
+    } else if (l.type == GNXR_LIGHT_POINT || l.type == GNXR_LIGHT_SPOT || l.type == GNXR_LIGHT_DISTANT) {
+        // lights/PointLight.cpp, SpotLight.cpp, DistantLight.cpp (field reuse: device_lights.h light_sample)
+        Mat4 l2w, w2l;
+        memcpy(&l2w.m[0][0], l.light_to_world, 64);
+        w2l = inverse(l2w);                                             // Transform(const Matrix4x4 &): mInv = Inverse(m)
+        Vec3 pL = xform_point(l2w, Vec3(0, 0, 0));
+        memcpy(dl.p0, &pL, 12);
+        for (int c = 0; c < 3; ++c) { dl.p1[c] = w2l.m[0][c]; dl.p2[c] = w2l.m[1][c]; dl.center[c] = w2l.m[2][c]; }
+        dl.area = std::cos((kPi / 180) * l.radius);                     // cosTotalWidth
+        dl.inv_area = std::cos((kPi / 180) * l.falloff_start);          // cosFalloffStart
+        Vec3 w = normalize(xform_vector(l2w, Vec3(l.center[0], l.center[1], l.center[2])));
+        memcpy(dl.n, &w, 12);
+        dl.radius = distant_radius(world_bound);
+    } else { set_error("light %d: unknown type %d", index, l.type); return false; }
+    return true;
+}
+
 void refit_world_bound(CompiledScene *cs, const float root6[6]) {
     cs->world_bound = Box3();
     cs->world_bound.lo = Vec3(root6[0], root6[1], root6[2]);
@@ -1107,46 +1146,24 @@ bool compile_scene(const gnxr_scene_desc *d, CompiledScene *cs, HlbvhBuildFn hlb
     cs->has_env = false;
     for (int i = 0; i < d->n_lights; ++i) {
         const gnxr_light &l = d->lights[i];
-        DLight &dl = cs->lights[i];
-        dl.type = l.type; dl.two_sided = l.two_sided; dl.tri_leaf = -1;
-        dl.n_samples = std::max(1, l.n_samples);
-        memcpy(dl.le, l.le, 12);
+        Vec3 corners[3];
+        int tri_leaf = -1;
         if (l.type == GNXR_LIGHT_AREA_TRI) {
             if (l.tri < 0 || l.tri >= d->n_triangles) { set_error("light %d: triangle out of range", i); return false; }
             if (d->tri_light[l.tri] != i) { set_error("light %d: tri_light[%d] does not point back", i, l.tri); return false; }
-            dl.tri_leaf = cs->leaf_of_prim[l.tri];
-            Vec3 p0 = vert(d->indices[3 * l.tri]), p1 = vert(d->indices[3 * l.tri + 1]), p2 = vert(d->indices[3 * l.tri + 2]);
-            memcpy(dl.p0, &p0, 12); memcpy(dl.p1, &p1, 12); memcpy(dl.p2, &p2, 12);
-            dl.area = (float)(0.5 * length(cross(p1 - p0, p2 - p0)));  // Triangle::Area, Triangle.cpp:455-462
-            dl.inv_area = 1 / dl.area;
-            Vec3 n = normalize(cross(p1 - p0, p2 - p0));                // Triangle::Sample, Triangle.cpp:473
-            memcpy(dl.n, &n, 12);
+            tri_leaf = cs->leaf_of_prim[l.tri];
+            for (int c = 0; c < 3; ++c) corners[c] = vert(d->indices[3 * l.tri + c]);
         } else if (l.type == GNXR_LIGHT_INFINITE) {
             if (!d->env_rgb || d->env_width <= 0 || d->env_height <= 0) { set_error("INFINITE light without env map"); return false; }
             if (cs->has_env) { set_error("only one INFINITE light is supported"); return false; }
-            dl.env = 1;
+        }
+        if (!compile_light(l, i, corners, tri_leaf, cs->world_bound, &cs->lights[i])) return false;
+        if (l.type == GNXR_LIGHT_INFINITE) {
             bool flip_y = false;
             for (int k = 0; k < i; ++k) if (d->lights[k].type == GNXR_LIGHT_SKYBOX) flip_y = true;
             build_env(d, l, flip_y, cs);
-            cs->infinite_lights.push_back(i);
-        } else if (l.type == GNXR_LIGHT_SKYBOX) {
-            memcpy(dl.center, l.center, 12);
-            dl.radius = l.radius;
-            cs->infinite_lights.push_back(i);
-        } else if (l.type == GNXR_LIGHT_POINT || l.type == GNXR_LIGHT_SPOT || l.type == GNXR_LIGHT_DISTANT) {
-            // lights/PointLight.cpp, SpotLight.cpp, DistantLight.cpp (field reuse: device_lights.h light_sample)
-            Mat4 l2w, w2l;
-            memcpy(&l2w.m[0][0], l.light_to_world, 64);
-            w2l = inverse(l2w);                                             // Transform(const Matrix4x4 &): mInv = Inverse(m)
-            Vec3 pL = xform_point(l2w, Vec3(0, 0, 0));
-            memcpy(dl.p0, &pL, 12);
-            for (int c = 0; c < 3; ++c) { dl.p1[c] = w2l.m[0][c]; dl.p2[c] = w2l.m[1][c]; dl.center[c] = w2l.m[2][c]; }
-            dl.area = std::cos((kPi / 180) * l.radius);                     // cosTotalWidth
-            dl.inv_area = std::cos((kPi / 180) * l.falloff_start);          // cosFalloffStart
-            Vec3 w = normalize(xform_vector(l2w, Vec3(l.center[0], l.center[1], l.center[2])));
-            memcpy(dl.n, &w, 12);
-            dl.radius = distant_radius(cs->world_bound);
-        } else { set_error("light %d: unknown type %d", i, l.type); return false; }
+        }
+        if (l.type == GNXR_LIGHT_INFINITE || l.type == GNXR_LIGHT_SKYBOX) cs->infinite_lights.push_back(i);
     }
     // ---- media
     cs->media.clear();

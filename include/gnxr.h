@@ -386,10 +386,33 @@ int gnxr_scene_info(const gnxr_scene *scene, int32_t *n_bvh_nodes, int32_t *bvh_
  * device (exactly the LinearBVHNode bounds that topology has over the new vertices).  Returns when every device of the scene
  * holds the new geometry.  Per-corner uvs / shading normals / tangents, spheres, materials and lights are unchanged; what depends
  * on the world bound (environment and distant lights, the light-selection table) follows it.  GNXR_ERR_UNSUPPORTED (scene
- * untouched) if a vertex of an emissive (AREA_TRI) triangle would change value; GNXR_ERR_INVALID for a null scene, a null xyz with
+ * untouched) if a vertex of an emissive (AREA_TRI) triangle would change value: area lights move through
+ * gnxr_scene_update_vertices_ex with GNXR_UPDATE_MOVE_LIGHTS.  GNXR_ERR_INVALID for a null scene, a null xyz with
  * n_vertices > 0 or a range outside the scene's vertices.  Traversal quality is that of the old topology: after large
  * deformations build the scene again with gnxr_scene_create, or keep the handle and call gnxr_scene_rebuild_bvh. */
 int gnxr_scene_update_vertices(gnxr_scene *scene, int32_t first_vertex, int32_t n_vertices, const float *xyz, void *hip_stream);
+/* gnxr_scene_update_vertices with flags; flags == 0 is that call exactly.  GNXR_UPDATE_MOVE_LIGHTS: vertices of emissive triangles may
+ * move too.  Nothing is refused for them; after the refit a kernel on the same stream rewrites corners, area and normal of EVERY
+ * AREA_TRI light record from its triangle (one light per emissive triangle: a moving mesh light is thousands of records), with the
+ * arithmetic gnxr_scene_create applies to them, so the records -- and every render, light sample and light-selection table after the
+ * call -- are bit for bit those of a scene created from a description carrying the vertices the scene now holds (tree aside: it keeps
+ * its topology), and re-sending unchanged vertices changes nothing.  A triangle moved to zero area gets the infinite inv_area and NaN
+ * normal gnxr_scene_create gives it; that is not an error.  The records (112 bytes per light) come back to the host with the root box.
+ * GNXR_ERR_INVALID, before any device is touched, for unknown flag bits, a null scene, a null xyz with n_vertices > 0 or a range
+ * outside the scene's vertices. */
+#define GNXR_UPDATE_MOVE_LIGHTS 1u
+int gnxr_scene_update_vertices_ex(gnxr_scene *scene, int32_t first_vertex, int32_t n_vertices, const float *xyz, uint32_t flags, void *hip_stream);
+/* Replace the parameters of lights [first_light, first_light + n_lights) of the scene's light list (the numbering of
+ * gnxr_scene_desc.lights) by lights[0 .. n_lights): afterwards the scene renders, bit for bit, as a scene created from the same
+ * description with those light records.  What may change: le, two_sided and n_samples of an AREA_TRI light (its corners, area and
+ * normal stay those of the vertices the scene holds now, moved or not); every field of a POINT, SPOT or DISTANT light; center and
+ * radius of a SKYBOX light.  GNXR_ERR_UNSUPPORTED for a record whose type differs from the light's, an AREA_TRI record whose tri
+ * differs, or an INFINITE record that differs in any byte (the environment tables are built by gnxr_scene_create only);
+ * GNXR_ERR_INVALID for a null scene, a null lights with n_lights > 0 or a range outside the scene's lights.  Every refusal leaves the
+ * scene exactly as it was: all records are built into a copy first.  The call takes the handle's render lock, writes the records of
+ * every device of the scene and returns; the BVH, textures, tables and the path state of gnxr_render_reserve stay, the light-selection
+ * table is rebuilt at the next render. */
+int gnxr_scene_update_lights(gnxr_scene *scene, int32_t first_light, int32_t n_lights, const gnxr_light *lights);
 /* Rebuild the triangle BVH of an existing scene over the vertices it currently holds on the device (the state after any number of
  * gnxr_scene_update_vertices calls), entirely on the device: the tree, its 4-wide form, the primitive order and everything kept in
  * that order become what gnxr_scene_create builds with bvh_split_method = GNXR_BVH_HLBVH from a description carrying those vertices,
