@@ -1,7 +1,7 @@
-// api.hip -- C ABI of libgnxr.so (include/gnxr.h): one translation unit.  This file keeps initialisation, scene creation and editing,
-// the render entry points and the host-memory probes; the rest lives in the api_*.hip.h headers included below (shared pieces, gnxr_scene,
-// the HLBVH build driver, the in-place BVH rebuild, the peak probes, the front end of the calls on device memory, the render path, the entry points on device memory).  One process drives one GPU (gnxr_init
-// binds the device); multi-GPU runs are one process per GPU with the image rows sharded by gnxr_render_params.
+// api.hip -- C ABI of libgnxr.so (include/gnxr.h): one translation unit.  This file keeps initialisation, scene creation, the render entry
+// points and the host-memory probes; the rest lives in the api_*.hip.h headers included below (shared pieces, gnxr_scene, the HLBVH build
+// driver, the peak probes, the front end of the calls on device memory, the render path, the editing calls, the in-place BVH rebuild, the
+// entry points on device memory).  One process drives one GPU (gnxr_init), or several behind every handle (gnxr_init_devices).
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -115,29 +115,25 @@ int gnxr_debug_trace_stats(unsigned long long *out16, int reset) {   // 24 slots
 }
 #endif
 
-// device side of gnxr_scene_create: everything compile_scene produced goes to the scene's device
-static int upload_scene(gnxr_scene *s) {
-    CompiledScene &cs = s->cs;
-    int rc = s->bind();
-    if (rc) return rc;
+// device side of gnxr_scene_create: everything compile_scene produced goes to the copy's (bound) device (an each_copy callable)
+static int upload_scene(gnxr_scene *s, size_t) {
+    const CompiledScene &cs = s->cs;
+    int rc;
     if (cs.bvh_max_depth + 1 > 64) { set_error("BVH depth %d exceeds the 64-entry traversal stack (BVHAccel.cpp:661)", cs.bvh_max_depth); return GNXR_ERR_UNSUPPORTED; }
-    s->stack_size = cs.bvh_max_depth + 1 <= 32 ? 32 : 64;
-    s->wide_ok = cs.tris.size() < (1u << 24) && cs.stack4_need + 1 <= 128 && !Knobs::binary_bvh();
-    for (const DNode &n : cs.nodes) if ((n.meta & 0xffffu) > 127) s->wide_ok = false;
+    s->set_traversal(std::any_of(cs.nodes.begin(), cs.nodes.end(), [](const DNode &n) { return (n.meta & 0xffffu) > 127; }));
 #define UP(field) if ((rc = s->field.upload(cs.field)) != GNXR_OK) return rc;
     UP(nodes) UP(nodes4) UP(tris) UP(leaf_boxes) UP(tri_class) UP(lights) UP(perms) UP(primes) UP(prime_sums) UP(prime_magic)
     UP(dmedia) UP(grid_density) UP(tri_media) UP(spheres) UP(textures) UP(tex_texels) UP(ewa_lut) UP(tri_uv) UP(tri_n) UP(tri_s)
     UP(aov_albedo) UP(material_authored)
     UP(env_texels4) UP(env_cond_func) UP(env_cond_cdf) UP(env_cond_int) UP(env_marg_func) UP(env_marg_cdf) UP(env_marg_guide) UP(env_cond_guide)
 #undef UP
-    {   // materials, preceded by one record that carries the texture tables (tex_tables(), device_texture.h)
-        DTexTables tt;
-        tt.textures = s->textures.p; tt.texels = reinterpret_cast<const float4 *>(s->tex_texels.p); tt.ewa_lut = s->ewa_lut.p; tt.tri_uv = cs.tri_uv.empty() ? nullptr : s->tri_uv.p; tt.tri_n = cs.tri_n.empty() ? nullptr : s->tri_n.p; tt.tri_s = cs.tri_s.empty() ? nullptr : s->tri_s.p;   // (an empty upload still allocates)
+    {   // materials, preceded by one record that carries the texture tables
+        const DTexTables rec = s->tex_tables(s->tri_uv.p, s->tri_n.p, s->tri_s.p);
         for (int k = 0; k < 2; ++k) {
             const std::vector<DMaterial> &src = k == 0 ? cs.materials : cs.materials_single;
             std::vector<DMaterial> up(src.size() + 1);
             memset(&up[0], 0, sizeof(DMaterial));
-            memcpy(&up[0], &tt, sizeof(tt));
+            memcpy(&up[0], &rec, sizeof(rec));
             std::copy(src.begin(), src.end(), up.begin() + 1);
             if ((rc = (k == 0 ? s->materials : s->materials_single).upload(up)) != GNXR_OK) return rc;
         }
@@ -157,25 +153,16 @@ int gnxr_scene_create(const gnxr_scene_desc *desc, gnxr_scene **out) {
     if (!desc || !out) { set_error("null argument"); return GNXR_ERR_INVALID; }
     int rc = ensure_device();
     if (rc) return rc;
-    gnxr_scene *s = new (std::nothrow) gnxr_scene();
+    gnxr_scene *s = new (std::nothrow) gnxr_scene(g_device);
     if (!s) return GNXR_ERR_OOM;
-    s->device = g_device;
     if (!compile_scene(desc, &s->cs, device_hlbvh_build)) { delete s; return GNXR_ERR_INVALID; }
-    if ((rc = upload_scene(s)) != GNXR_OK) { delete s; return rc; }
-    // gnxr_init_devices: the same tables on every other device of the list (the host-side compilation is shared)
-    for (size_t i = 1; i < g_devices.size(); ++i) {
-        std::unique_ptr<gnxr_scene> r(new (std::nothrow) gnxr_scene());
-        if (!r) { delete s; return GNXR_ERR_OOM; }
-        r->device = g_devices[i];
-        r->cs = s->cs;
-        if ((rc = upload_scene(r.get())) != GNXR_OK) { delete s; (void)hipSetDevice(g_device); return rc; }
-        s->replicas.push_back(std::move(r));
-    }
-    if ((rc = s->bind()) != GNXR_OK) { delete s; return rc; }
+    // gnxr_init_devices: a copy on every other device of the list, sharing the host scene; then the same tables on every device
+    for (size_t i = 1; i < g_devices.size(); ++i) s->replicas.push_back(std::make_unique<gnxr_scene>(g_devices[i], s->host));
+    if ((rc = s->each_copy(upload_scene)) != GNXR_OK) { delete s; return rc; }
     const CompiledScene &cs = s->cs;
     if (getenv("GNXR_VERBOSE"))
         fprintf(stderr, "[gnxr] scene: %zu tris, %zu nodes (depth %d), %zu 4-wide nodes (stack %d), wide=%d, %zu device(s)\n", cs.tris.size(), cs.nodes.size(), cs.bvh_max_depth,
-                cs.nodes4.size(), cs.stack4_need, (int)s->wide_ok, 1 + s->replicas.size());
+                cs.nodes4.size(), cs.stack4_need, (int)s->wide_ok, s->n_copies());
     *out = s;
     return GNXR_OK;
 }
@@ -186,207 +173,6 @@ int gnxr_scene_info(const gnxr_scene *s, int32_t *n_nodes, int32_t *max_depth, i
     if (n_nodes) *n_nodes = (int32_t)s->cs.nodes.size();
     if (max_depth) *max_depth = s->cs.bvh_max_depth;
     if (n_vox) *n_vox = s->grid_strategy >= 0 ? s->grid.nvox[0] * s->grid.nvox[1] * s->grid.nvox[2] : 0;
-    return GNXR_OK;
-}
-
-// ---- editing a scene in place (gnxr_scene_update_vertices[_ex] / gnxr_scene_update_lights / gnxr_scene_set_camera) ----
-// the refit's tables go to a device at the first update of the scene (the flag is allocated last: it marks the set complete)
-static int refit_tables(gnxr_scene *s) {
-    if (s->upd_flag.p) return GNXR_OK;
-    const CompiledScene &cs = s->cs;
-    int rc;
-    if ((rc = s->upd_corner.upload(cs.corner_vertex)) || (rc = s->upd_parent.upload(cs.node_parent)) || (rc = s->upd_node4_src.upload(cs.node4_src)) ||
-        (rc = s->upd_arrived.alloc(cs.nodes.size())) || (rc = s->upd_flag.alloc(1)))
-        return rc;
-    return GNXR_OK;
-}
-
-// positions of vertices [first, first + n) staged in s->upd_xyz -> triangles, binary tree, 4-wide tree on the scene's (bound) device;
-// returns the refitted root box.  Topology, primitive order and every id stay as they are, so the one-triangle leaves still have the
-// min / max of their triangle's corners as their box (k_refit_fit computes it so) and CompiledScene::leaf1_from_verts keeps its value.
-// move_lights (GNXR_UPDATE_MOVE_LIGHTS): the AREA_TRI light records are recomputed from the moved triangles (k_refit_lights); with h_lights
-// every record comes back with the root box, behind the same synchronisation: refit_world uploads the host copy over the device's afterwards.
-static int refit_apply(gnxr_scene *s, int first, int n, hipStream_t st, float root6[6], bool move_lights = false, std::vector<DLight> *h_lights = nullptr) {
-    const CompiledScene &cs = s->cs;
-    const int nt = (int)cs.tris.size(), nn = (int)cs.nodes.size(), nslots = (int)cs.node4_src.size();
-    hipLaunchKernelGGL(refit::k_refit_tris, dim3(grid_for(nt)), dim3(refit::kB), 0, st, s->tris.p, (const int *)s->upd_corner.p, nt, first, n, (const float *)s->upd_xyz.p);
-    HIP_TRY(hipMemsetAsync(s->upd_arrived.p, 0, (size_t)nn * sizeof(unsigned int), st));
-    hipLaunchKernelGGL(refit::k_refit_fit, dim3(grid_for(nn)), dim3(refit::kB), 0, st, nn, s->nodes.p, (const int *)s->upd_parent.p, s->upd_arrived.p, (const DTri *)s->tris.p,
-                       s->leaf_boxes.p);
-    // (the 4-wide slots copy finished boxes: the launch boundary orders them after the fit; k_trace4's top-of-tree LDS copy is
-    // loaded from nodes4 at the start of every launch)
-    hipLaunchKernelGGL(refit::k_refit_wide, dim3(grid_for(nslots)), dim3(refit::kB), 0, st, nslots, s->nodes4.p, (const int *)s->upd_node4_src.p, (const DNode *)s->nodes.p);
-    const int n_lights = (int)cs.desc_lights.size();   // (a scene without lights still holds one blank record)
-    if (move_lights && n_lights > 0) hipLaunchKernelGGL(refit::k_refit_lights, dim3(grid_for(n_lights)), dim3(refit::kB), 0, st, s->lights.p, n_lights, (const DTri *)s->tris.p, nt);
-    HIP_TRY(hipGetLastError());
-    DNode root;
-    HIP_TRY(hipMemcpyAsync(&root, s->nodes.p, sizeof(DNode), hipMemcpyDeviceToHost, st));
-    if (h_lights) {
-        h_lights->resize(cs.lights.size());
-        HIP_TRY(hipMemcpyAsync(h_lights->data(), s->lights.p, cs.lights.size() * sizeof(DLight), hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    root6[0] = root.lo[0]; root6[1] = root.lo[1]; root6[2] = root.lo[2]; root6[3] = root.hi0; root6[4] = root.hi1; root6[5] = root.hi2;
-    return GNXR_OK;
-}
-
-// what depends on the world bound, on the host: Scene::WorldBound, the environment light's bounding sphere (DEnv, read at every render),
-// the delta lights' radius (re-uploaded) and the light-selection table (rebuilt by ensure_grid at the next render)
-static int refit_world(gnxr_scene *s, const CompiledScene &from) {
-    if (int rc = s->bind()) return rc;
-    s->cs.world_bound = from.world_bound;
-    s->cs.env = from.env;
-    s->cs.lights = from.lights;
-    HIP_TRY(hipMemcpy(s->lights.p, s->cs.lights.data(), s->cs.lights.size() * sizeof(DLight), hipMemcpyHostToDevice));
-    s->grid_strategy = -1;
-    s->host_bvh_stale = true;
-    return GNXR_OK;
-}
-
-int gnxr_scene_update_vertices_ex(gnxr_scene *s, int32_t first_vertex, int32_t n_vertices, const float *xyz, uint32_t flags, void *hip_stream) {
-    if (!s) { set_error("null scene"); return GNXR_ERR_INVALID; }
-    if (flags & ~(uint32_t)GNXR_UPDATE_MOVE_LIGHTS) { set_error("unknown update flags 0x%x", flags); return GNXR_ERR_INVALID; }
-    if (n_vertices > 0 && !xyz) { set_error("null vertex array"); return GNXR_ERR_INVALID; }
-    if (first_vertex < 0 || n_vertices < 0 || (int64_t)first_vertex + n_vertices > (int64_t)s->cs.n_vertices) {
-        set_error("vertex range [%d, %lld) outside the scene's %d vertices", first_vertex, (long long)first_vertex + n_vertices, s->cs.n_vertices);
-        return GNXR_ERR_INVALID;
-    }
-    if (n_vertices == 0) return GNXR_OK;
-    const bool move_lights = (flags & GNXR_UPDATE_MOVE_LIGHTS) != 0;
-    std::lock_guard<std::recursive_mutex> lock(s->render_mutex);
-    int rc = s->bind();
-    if (rc) return rc;
-    hipStream_t st = (hipStream_t)hip_stream;
-    const size_t nf = 3 * (size_t)n_vertices;
-    if ((rc = refit_tables(s)) || (rc = s->upd_xyz.alloc(nf))) return rc;
-    // one copy path for host and device memory; ordered after what the caller queued on its stream
-    HIP_TRY(hipMemcpyAsync(s->upd_xyz.p, xyz, nf * sizeof(float), hipMemcpyDefault, st));
-    if (!move_lights) {
-        // emissive triangles keep their vertices (their DLight records hold them): refuse before anything is written
-        int h_flag = 0;
-        const int nt = (int)s->cs.tris.size();
-        HIP_TRY(hipMemsetAsync(s->upd_flag.p, 0, sizeof(int), st));
-        hipLaunchKernelGGL(refit::k_refit_check, dim3(grid_for(nt)), dim3(refit::kB), 0, st, (const DTri *)s->tris.p, (const int *)s->upd_corner.p, nt, first_vertex, n_vertices,
-                           (const float *)s->upd_xyz.p, s->upd_flag.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&h_flag, s->upd_flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (h_flag) {
-            set_error("a vertex of an emissive (AREA_TRI) triangle would move: pass GNXR_UPDATE_MOVE_LIGHTS to gnxr_scene_update_vertices_ex to move area lights");
-            return GNXR_ERR_UNSUPPORTED;
-        }
-    }
-    float root6[6];
-    // the moved light records, held back until all devices have refitted (a failure before that leaves the host copy alone).  Every device
-    // holds the same tree and the same records (refit_world copies this scene's onto the replicas), so this device's are fetched for all.
-    std::vector<DLight> moved;
-    if ((rc = refit_apply(s, first_vertex, n_vertices, st, root6, move_lights, move_lights ? &moved : nullptr)) != GNXR_OK) return rc;
-    if (!s->replicas.empty()) {   // gnxr_init_devices: the same refit on every replica, from a host copy of the staged positions
-        std::vector<float> staged(nf);
-        HIP_TRY(hipMemcpy(staged.data(), s->upd_xyz.p, nf * sizeof(float), hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < s->replicas.size(); ++i) {
-            gnxr_scene *r = s->replicas[i].get();
-            float rroot[6];
-            if ((rc = r->bind()) || (rc = refit_tables(r)) || (rc = r->upd_xyz.upload(staged.data(), nf)) ||
-                (rc = refit_apply(r, first_vertex, n_vertices, nullptr, rroot, move_lights))) {
-                (void)s->bind();
-                return rc;
-            }
-        }
-    }
-    // the fetched records become the host copies BEFORE refit_world_bound refreshes the delta lights' radius in them and refit_world
-    // uploads them: the power table (build_light_grid) reads cs.lights[i].area, and a stale copy would undo the kernel's work
-    if (move_lights) s->cs.lights = std::move(moved);
-    refit_world_bound(&s->cs, root6);
-    for (size_t i = 0; i < s->replicas.size(); ++i)
-        if ((rc = refit_world(s->replicas[i].get(), s->cs)) != GNXR_OK) { (void)s->bind(); return rc; }
-    return refit_world(s, s->cs);
-}
-
-int gnxr_scene_update_vertices(gnxr_scene *s, int32_t first_vertex, int32_t n_vertices, const float *xyz, void *hip_stream) {
-    return gnxr_scene_update_vertices_ex(s, first_vertex, n_vertices, xyz, 0, hip_stream);
-}
-
-// The new records of lights [first, first + n): nothing of the scene is touched before every one of them has passed.  What a record may
-// change: AREA_TRI le / two_sided / n_samples (its triangle stays; corners, area and normal come from the vertices the scene holds NOW,
-// which cs.lights carries: gnxr_scene_update_vertices_ex and gnxr_scene_rebuild_bvh keep that copy current); POINT / SPOT / DISTANT
-// everything; SKYBOX centre and radius; INFINITE nothing (its importance tables and texels are not rebuilt here).
-static int build_light_update(const CompiledScene &cs, int first, int n, const gnxr_light *in, std::vector<DLight> *lights, std::vector<gnxr_light> *desc) {
-    *lights = cs.lights;
-    *desc = cs.desc_lights;
-    for (int k = 0; k < n; ++k) {
-        const int i = first + k;
-        const gnxr_light &was = cs.desc_lights[i], &l = in[k];
-        if (l.type != was.type) { set_error("light %d: the type of a light cannot change in place (%d -> %d)", i, was.type, l.type); return GNXR_ERR_UNSUPPORTED; }
-        if (l.type == GNXR_LIGHT_INFINITE) {
-            if (memcmp(&l, &was, sizeof(gnxr_light)) != 0) { set_error("light %d: an INFINITE light cannot change in place (its tables are built by gnxr_scene_create)", i); return GNXR_ERR_UNSUPPORTED; }
-            continue;
-        }
-        Vec3 corners[3];
-        int tri_leaf = -1;
-        if (l.type == GNXR_LIGHT_AREA_TRI) {
-            if (l.tri != was.tri) { set_error("light %d: the triangle of an area light cannot change in place (%d -> %d)", i, was.tri, l.tri); return GNXR_ERR_UNSUPPORTED; }
-            const DLight &cur = cs.lights[i];
-            tri_leaf = cur.tri_leaf;
-            corners[0] = Vec3(cur.p0[0], cur.p0[1], cur.p0[2]); corners[1] = Vec3(cur.p1[0], cur.p1[1], cur.p1[2]); corners[2] = Vec3(cur.p2[0], cur.p2[1], cur.p2[2]);
-        }
-        if (!compile_light(l, i, corners, tri_leaf, cs.world_bound, &(*lights)[i])) return GNXR_ERR_INVALID;
-        (*desc)[i] = l;
-    }
-    return GNXR_OK;
-}
-
-int gnxr_scene_update_lights(gnxr_scene *s, int32_t first_light, int32_t n_lights, const gnxr_light *lights) {
-    if (!s) { set_error("null scene"); return GNXR_ERR_INVALID; }
-    if (n_lights > 0 && !lights) { set_error("null light array"); return GNXR_ERR_INVALID; }
-    const int64_t have = (int64_t)s->cs.desc_lights.size();   // (the number of lights never changes)
-    if (first_light < 0 || n_lights < 0 || (int64_t)first_light + n_lights > have) {
-        set_error("light range [%d, %lld) outside the scene's %lld lights", first_light, (long long)first_light + n_lights, (long long)have);
-        return GNXR_ERR_INVALID;
-    }
-    if (n_lights == 0) return GNXR_OK;
-    std::lock_guard<std::recursive_mutex> lock(s->render_mutex);
-    const size_t n_dev = 1 + s->replicas.size();
-    const auto dev = [&](size_t i) { return i == 0 ? s : s->replicas[i - 1].get(); };
-    // 1. the records into a copy (one set: every device holds the same tree and the same records)
-    std::vector<DLight> recs;
-    std::vector<gnxr_light> descs;
-    if (int rc = build_light_update(s->cs, first_light, n_lights, lights, &recs, &descs)) return rc;
-    // 2. the uploads; one that fails puts the old records back on the devices already written
-    for (size_t i = 0; i < n_dev; ++i) {
-        gnxr_scene *d = dev(i);
-        hipError_t e = hipSetDevice(d->device);
-        if (e == hipSuccess) e = hipMemcpy(d->lights.p, recs.data(), recs.size() * sizeof(DLight), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            for (size_t j = 0; j <= i; ++j)
-                if (hipSetDevice(dev(j)->device) == hipSuccess) (void)hipMemcpy(dev(j)->lights.p, dev(j)->cs.lights.data(), dev(j)->cs.lights.size() * sizeof(DLight), hipMemcpyHostToDevice);
-            (void)hipGetLastError();
-            (void)s->bind();
-            set_error("HIP error: %s", hipGetErrorString(e));
-            return GNXR_ERR_RUNTIME;
-        }
-    }
-    // 3. the host copies (the render plan reads desc_lights' n_samples) and a new light-selection table at the next render
-    for (size_t i = 0; i < n_dev; ++i) {
-        gnxr_scene *d = dev(i);
-        d->cs.lights = recs;
-        d->cs.desc_lights = descs;
-        d->grid_strategy = -1;
-    }
-    return s->bind();
-}
-
-int gnxr_scene_set_camera(gnxr_scene *s, const gnxr_camera *camera, int32_t camera_medium) {
-    if (!s || !camera) { set_error("null argument"); return GNXR_ERR_INVALID; }
-    const int n_media = (int)s->cs.media.size();
-    // as gnxr_scene_create: -1 == none; without media any value means none
-    if (n_media > 0 && (camera_medium < -1 || camera_medium >= n_media)) { set_error("camera_medium %d out of range (%d media)", camera_medium, n_media); return GNXR_ERR_INVALID; }
-    std::lock_guard<std::recursive_mutex> lock(s->render_mutex);
-    for (size_t i = 0; i <= s->replicas.size(); ++i) {
-        CompiledScene &cs = i == 0 ? s->cs : s->replicas[i - 1]->cs;
-        cs.camera = *camera;
-        cs.camera_medium = n_media > 0 ? camera_medium : -1;
-    }
     return GNXR_OK;
 }
 
@@ -477,6 +263,7 @@ int gnxr_trace_any(gnxr_scene *s, const gnxr_ray *rays, int64_t n, uint8_t *occl
 
 }  // extern "C"
 
+#include "api_edit.hip.h"
 #include "api_rebuild.hip.h"
 #include "api_query.hip.h"
 #include "api_aov.hip.h"

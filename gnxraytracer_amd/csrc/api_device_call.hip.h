@@ -16,8 +16,7 @@ static gnxr_scene *query_replica(gnxr_scene *s, const void *ptr, size_t bytes, c
         return nullptr;
     }
     gnxr_scene *r = nullptr;
-    if (s->device == a.device) r = s;
-    for (size_t i = 0; !r && i < s->replicas.size(); ++i) if (s->replicas[i]->device == a.device) r = s->replicas[i].get();
+    for (size_t i = 0; !r && i < s->n_copies(); ++i) if (s->copy(i)->device == a.device) r = s->copy(i);
     if (!r) { set_error("%s lives on device %d, which holds no copy of the scene", what, a.device); return nullptr; }
     hipDeviceptr_t base = nullptr;
     size_t size = 0;

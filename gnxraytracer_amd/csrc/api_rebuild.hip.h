@@ -1,9 +1,10 @@
 // api_rebuild.hip.h -- gnxr_scene_rebuild_bvh: host driver of the in-place rebuild (rebuild_kernel.hip.h).  Part of api.hip's translation
-// unit (after refit_tables in api.hip).
+// unit (after api_edit.hip.h: the rebuild keeps the refit's tables, refit_tables, current).
 //
-// Every device of the handle builds into FRESH buffers (rebuild_on_device); only when all of them have reported clean flags are the
-// buffers swapped into the scene (rebuild_commit, pointer swaps only; the one device write that could still fail, the DTexTables record,
-// is made before them: rebuild_point_tables), so a refused or failed call leaves the scene as it was.  What crosses to the host:
+// Every device of the handle builds into FRESH buffers (rebuild_on_device); only when all of them have reported clean flags and the same
+// tree are the buffers swapped into the copies (rebuild_commit_copy, pointer swaps only; the one device write that could still fail, the
+// DTexTables record, is made before them: rebuild_point_tables) and the host scene told once (rebuild_commit_host), so a refused or failed
+// call leaves the scene as it was.  What crosses to the host:
 // the six floats of the centroid bounds, the run / treelet / level counts of the HLBVH stage, the node counts, and the result scalars
 // (rebuild::R_*); and the DLight records, whose host copy refit_world uploads again after the next gnxr_scene_update_vertices (and from
 // which gnxr_scene_update_lights takes an area light's corners and tri_leaf).
@@ -26,6 +27,11 @@ struct Rebuilt {
     std::vector<DLight> h_lights;
     int n_nodes = 0, n_nodes4 = 0, root4 = 0, stack4_need = 1, max_depth = 0, leaf1_from_verts = 1;
     bool leaf_over_127 = false;
+    // the result scalars: what the host scene records of a tree.  Every device builds the same one.
+    bool same_tree(const Rebuilt &o) const {
+        return n_nodes == o.n_nodes && n_nodes4 == o.n_nodes4 && root4 == o.root4 && stack4_need == o.stack4_need && max_depth == o.max_depth &&
+               leaf1_from_verts == o.leaf1_from_verts && leaf_over_127 == o.leaf_over_127;
+    }
 };
 
 // the tree over the vertices `s` holds on its (bound) device, into `r`; nothing of `s` changes
@@ -159,20 +165,25 @@ int rebuild_on_device(gnxr_scene *s, hipStream_t st, Rebuilt *r) {
 bool rebuild_has_attrs(const Rebuilt &r) { return r.tri_uv.p || r.tri_n.p || r.tri_s.p; }
 int rebuild_point_tables(gnxr_scene *s, const Rebuilt &r, bool to_new) {
     if (!rebuild_has_attrs(r)) return GNXR_OK;
-    const CompiledScene &cs = s->cs;
-    DTexTables tt;
-    tt.textures = s->textures.p; tt.texels = reinterpret_cast<const float4 *>(s->tex_texels.p); tt.ewa_lut = s->ewa_lut.p;
-    tt.tri_uv = cs.tri_uv.empty() ? nullptr : (to_new ? r.tri_uv.p : s->tri_uv.p);
-    tt.tri_n = cs.tri_n.empty() ? nullptr : (to_new ? r.tri_n.p : s->tri_n.p);
-    tt.tri_s = cs.tri_s.empty() ? nullptr : (to_new ? r.tri_s.p : s->tri_s.p);
-    HIP_TRY(hipMemcpy(s->materials.p, &tt, sizeof(tt), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(s->materials_single.p, &tt, sizeof(tt), hipMemcpyHostToDevice));
+    const DTexTables rec = to_new ? s->tex_tables(r.tri_uv.p, r.tri_n.p, r.tri_s.p) : s->tex_tables(s->tri_uv.p, s->tri_n.p, s->tri_s.p);
+    HIP_TRY(hipMemcpy(s->materials.p, &rec, sizeof(rec), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->materials_single.p, &rec, sizeof(rec), hipMemcpyHostToDevice));
     return GNXR_OK;
 }
 
-// the new tables into the scene: pointer swaps and host bookkeeping only, nothing here can fail
-void rebuild_commit(gnxr_scene *s, Rebuilt &r) {
+// The new tree into the scene, in two steps that cannot fail.  First the host scene, once, from the primary's result: sizes now, contents
+// at the next sync_host_bvh.
+void rebuild_commit_host(gnxr_scene *s, Rebuilt &r) {
     CompiledScene &cs = s->cs;
+    cs.nodes.resize(r.n_nodes); cs.node_parent.resize(r.n_nodes);
+    cs.nodes4.resize(r.n_nodes4); cs.node4_src.resize(4 * (size_t)r.n_nodes4);
+    cs.root4 = r.root4; cs.stack4_need = r.stack4_need; cs.bvh_max_depth = r.max_depth; cs.leaf1_from_verts = r.leaf1_from_verts;
+    cs.lights = std::move(r.h_lights);
+    s->host->host_bvh_stale = true;
+    s->host->host_order_stale = true;
+}
+// ... then every copy's tables: pointer swaps, and what the copy derives from the host scene
+void rebuild_commit_copy(gnxr_scene *s, Rebuilt &r) {
     swap_buf(s->nodes, r.nodes); swap_buf(s->nodes4, r.nodes4); swap_buf(s->tris, r.tris); swap_buf(s->leaf_boxes, r.leaf_boxes); swap_buf(s->tri_class, r.tri_class);
     swap_buf(s->lights, r.lights);
     if (r.tri_media.p) swap_buf(s->tri_media, r.tri_media);
@@ -181,15 +192,7 @@ void rebuild_commit(gnxr_scene *s, Rebuilt &r) {
     if (r.tri_s.p) swap_buf(s->tri_s, r.tri_s);
     // the refit's tables were just computed for the new tree: they go in directly
     swap_buf(s->upd_corner, r.corner); swap_buf(s->upd_parent, r.parent); swap_buf(s->upd_node4_src, r.node4_src); swap_buf(s->upd_arrived, r.arrived);
-    // host bookkeeping: sizes now, contents at the next sync_host_bvh
-    cs.nodes.resize(r.n_nodes); cs.node_parent.resize(r.n_nodes);
-    cs.nodes4.resize(r.n_nodes4); cs.node4_src.resize(4 * (size_t)r.n_nodes4);
-    cs.root4 = r.root4; cs.stack4_need = r.stack4_need; cs.bvh_max_depth = r.max_depth; cs.leaf1_from_verts = r.leaf1_from_verts;
-    cs.lights = r.h_lights;
-    s->stack_size = cs.bvh_max_depth + 1 <= 32 ? 32 : 64;   // as upload_scene
-    s->wide_ok = cs.tris.size() < (1u << 24) && cs.stack4_need + 1 <= 128 && !Knobs::binary_bvh() && !r.leaf_over_127;
-    s->host_bvh_stale = true;
-    s->host_order_stale = true;
+    s->set_traversal(r.leaf_over_127);
     s->grid_strategy = -1;
 }
 
@@ -200,33 +203,22 @@ extern "C" int gnxr_scene_rebuild_bvh(gnxr_scene *s, void *hip_stream) {
     std::lock_guard<std::recursive_mutex> lock(s->render_mutex);
     int rc = s->bind();
     if (rc) return rc;
-    const size_t n_dev = 1 + s->replicas.size();
-    const auto dev = [&](size_t i) { return i == 0 ? s : s->replicas[i - 1].get(); };
-    // 1. every device builds into fresh buffers
-    std::vector<std::unique_ptr<Rebuilt>> built;
-    for (size_t i = 0; i < n_dev; ++i) {
-        built.emplace_back(new Rebuilt());
-        if ((rc = dev(i)->bind()) || (rc = rebuild_on_device(dev(i), i == 0 ? (hipStream_t)hip_stream : nullptr, built.back().get()))) {
-            (void)hipGetLastError();
-            (void)s->bind();
-            return rc;
-        }
-    }
+    // 1. every device builds into fresh buffers (the primary on the caller's stream), and all must have built the same tree
+    std::vector<Rebuilt> built(s->n_copies());
+    if ((rc = s->each_copy([&](gnxr_scene *c, size_t i) { return rebuild_on_device(c, i == 0 ? (hipStream_t)hip_stream : nullptr, &built[i]); }))) return rc;
+    for (size_t i = 1; i < built.size(); ++i)
+        if (!built[i].same_tree(built[0])) { set_error("BVH rebuild: the devices disagree (internal error)"); return GNXR_ERR_RUNTIME; }
     // 2. the only writes that can still fail; a failure points every record back at the tables the scene holds
-    for (size_t i = 0; i < n_dev; ++i) {
-        if ((rc = dev(i)->bind()) || (rc = rebuild_point_tables(dev(i), *built[i], /*to_new=*/true))) {
-            const std::string why = get_error();
-            for (size_t j = 0; j <= i; ++j) if (dev(j)->bind() == GNXR_OK) (void)rebuild_point_tables(dev(j), *built[j], /*to_new=*/false);
-            (void)hipGetLastError();
-            (void)s->bind();
-            set_error("%s", why.c_str());
-            return rc;
-        }
+    if ((rc = s->each_copy([&](gnxr_scene *c, size_t i) { return rebuild_point_tables(c, built[i], /*to_new=*/true); }))) {
+        const std::string why = get_error();
+        (void)s->each_copy([&](gnxr_scene *c, size_t i) { return rebuild_point_tables(c, built[i], /*to_new=*/false); });
+        set_error("%s", why.c_str()); return rc;
     }
-    // 3. the swaps
-    for (size_t i = 0; i < n_dev; ++i) rebuild_commit(dev(i), *built[i]);
+    // 3. the host scene, then the swaps
+    rebuild_commit_host(s, built[0]);
+    for (size_t i = 0; i < s->n_copies(); ++i) rebuild_commit_copy(s->copy(i), built[i]);
     // the old tables are released with `built` (hipFree waits for what still reads them)
-    return s->bind();
+    return GNXR_OK;
 }
 
 extern "C" int gnxr_scene_bvh4(const gnxr_scene *sc, void *nodes128, int64_t node_capacity, int64_t *n_nodes4, int32_t *root4, int32_t *stack_need) {

@@ -957,7 +957,7 @@ static int render_one(gnxr_scene *s, const gnxr_render_params *pin, void *d_rgba
 // one strided 2D copy per device).  A single device takes the direct path.
 static int render_sharded(gnxr_scene *s, const gnxr_render_params *pin, void *d_rgba_out, void *hip_stream, gnxr_stats *stats, bool reserve_only = false) {
     if (!s || !pin || !d_rgba_out) { set_error("null argument"); return GNXR_ERR_INVALID; }
-    const int nd = 1 + (int)s->replicas.size();
+    const int nd = (int)s->n_copies();
     if (nd == 1) return render_one(s, pin, d_rgba_out, hip_stream, stats, reserve_only);
     gnxr_render_params base = *pin;
     if (base.shard_count <= 0) base.shard_count = 1;
@@ -975,7 +975,7 @@ static int render_sharded(gnxr_scene *s, const gnxr_render_params *pin, void *d_
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(caller));   // the image must be safe to write from the other devices' streams
     auto worker = [&](int i) {
-        gnxr_scene *r = i == 0 ? s : s->replicas[i - 1].get();
+        gnxr_scene *r = s->copy(i);
         gnxr_render_params p = base;   // rows y == shard_index (mod shard_count) of the caller, every nd-th of them
         p.shard_index = base.shard_index + base.shard_count * i;
         p.shard_count = base.shard_count * nd;
@@ -1020,13 +1020,13 @@ static int render_sharded(gnxr_scene *s, const gnxr_render_params *pin, void *d_
     (void)s->bind();
     for (int i = 1; i < nd; ++i) {   // host-staged shards: upload their rows into the image on the primary device
         if (staged[i] <= 0 || rcs[i] != GNXR_OK) continue;
-        gnxr_scene *r = s->replicas[i - 1].get();
+        gnxr_scene *r = s->copy(i);
         const int first = base.shard_index + base.shard_count * i, step = base.shard_count * nd;
         const size_t rowb = (size_t)base.width * sizeof(float4);
         hipError_t e = hipMemcpy2D((char *)d_rgba_out + (size_t)first * rowb, rowb * step, r->h_stage, rowb, rowb, staged[i], hipMemcpyHostToDevice);
         if (e != hipSuccess) { rcs[i] = hip_status(e); errs[i] = std::string("upload of the staged rows failed: ") + hipGetErrorString(e); }
     }
-    for (int i = 0; i < nd; ++i) if (rcs[i] != GNXR_OK) { set_error("device %d: %s", i == 0 ? s->device : s->replicas[i - 1]->device, errs[i].c_str()); return rcs[i]; }
+    for (int i = 0; i < nd; ++i) if (rcs[i] != GNXR_OK) { set_error("device %d: %s", s->copy(i)->device, errs[i].c_str()); return rcs[i]; }
     if (stats) {
         *stats = sts[0];
         for (int i = 1; i < nd; ++i) {

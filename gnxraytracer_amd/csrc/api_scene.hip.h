@@ -1,4 +1,5 @@
-// api_scene.hip.h -- gnxr_scene: the device tables of a scene, its per-render state and its light-selection table.
+// api_scene.hip.h -- gnxr_scene: one copy of a scene (its device tables, per-render state and light-selection table) and the host scene
+// all copies of a handle share.
 // Part of api.hip's translation unit (after api_common.hip.h).
 #pragma once
 
@@ -40,8 +41,18 @@ struct RenderState {
     VolPackSet pack_set(bool alt);
 };
 
-struct gnxr_scene {
+// The host side of a handle: ONE per gnxr_scene_create, shared by the copies on every device of gnxr_init_devices.  Written only under the
+// primary's render_mutex (the editing calls, sync_host_bvh); the workers of render_sharded and the calls bound to a replica read it.
+struct SceneHost {
     CompiledScene cs;
+    bool host_bvh_stale = false;     // after an update cs.nodes / nodes4 / tris / leaf_boxes lag the primary's device until sync_host_bvh()
+    bool host_order_stale = false;   // after gnxr_scene_rebuild_bvh the host copies of what is held in leaf or node order lag too (the upd_* tables are current)
+};
+
+struct gnxr_scene {
+    const std::shared_ptr<SceneHost> host;
+    CompiledScene &cs;   // host->cs
+    explicit gnxr_scene(int device_, std::shared_ptr<SceneHost> h = std::make_shared<SceneHost>()) : host(std::move(h)), cs(host->cs), device(device_) {}
     // device tables
     DevBuf<DNode> nodes;
     DevBuf<DNode4> nodes4;
@@ -82,8 +93,22 @@ struct gnxr_scene {
     int stack_size = 32;
     bool wide_ok = true;   // 4-wide traversal usable (leaf sizes / triangle count fit the reference encoding)
     std::recursive_mutex render_mutex;   // one render in flight per handle; gnxr_render holds it around its staging buffer too
-    int device = 0;                      // the HIP device the tables live on
-    std::vector<std::unique_ptr<gnxr_scene>> replicas;   // the same scene on the other devices of gnxr_init_devices (element 0 of that list is this one)
+    const int device;                    // the HIP device the tables live on
+    // the same scene on the other devices of gnxr_init_devices (element 0 of that list is this one), and all copies: 0 is this one, the primary
+    std::vector<std::unique_ptr<gnxr_scene>> replicas;
+    size_t n_copies() const { return 1 + replicas.size(); }
+    gnxr_scene *copy(size_t i) { return i == 0 ? this : replicas[i - 1].get(); }
+    // f(copy, i) on every copy in turn, its device bound.  The first failure ends the walk: the runtime's last error is cleared and that
+    // status returned (its message stays).  Either way the primary's device is current afterwards.
+    template <typename F>
+    int each_copy(F &&f) {
+        int rc = GNXR_OK;
+        for (size_t i = 0; i < n_copies() && rc == GNXR_OK; ++i)
+            if ((rc = copy(i)->bind()) == GNXR_OK) rc = f(copy(i), i);
+        if (rc == GNXR_OK) return bind();
+        (void)hipGetLastError(); (void)hipSetDevice(device);
+        return rc;
+    }
     DevBuf<float4> shard_out;            // a replica's full-size output plane; its rows are peer-copied into the primary's image
     void *h_stage = nullptr;             // pinned: a replica's rows on their way to the primary when the two devices have no peer access
     size_t h_stage_bytes = 0;
@@ -95,20 +120,18 @@ struct gnxr_scene {
     DevBuf<int> upd_flag;
     // gnxr_render_views_device: the host copy of st.view_cams (what the stream-ordered upload reads; both only grow)
     std::vector<DCamera> h_view_cams;
-    bool host_bvh_stale = false;         // after an update cs.nodes / nodes4 / tris / leaf_boxes lag the device until sync_host_bvh()
-    bool host_order_stale = false;       // after gnxr_scene_rebuild_bvh the host copies of what is held in leaf or node order lag too (the upd_* tables are current)
 
     int bind() const { HIP_TRY(hipSetDevice(device)); return GNXR_OK; }
     // the host copies of the geometry tables, downloaded on demand after gnxr_scene_update_vertices / gnxr_scene_rebuild_bvh (only
-    // readers pay for them; the rebuild has already given the vectors their new sizes)
+    // readers pay for them; the rebuild has already given the vectors their new sizes).  Called on the handle: the primary's device is read.
     int sync_host_bvh() {
-        if (!host_bvh_stale) return GNXR_OK;
+        if (!host->host_bvh_stale) return GNXR_OK;
         if (int rc = bind()) return rc;
         HIP_TRY(hipMemcpy(cs.nodes.data(), nodes.p, cs.nodes.size() * sizeof(DNode), hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(cs.nodes4.data(), nodes4.p, cs.nodes4.size() * sizeof(DNode4), hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(cs.tris.data(), tris.p, cs.tris.size() * sizeof(DTri), hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(cs.leaf_boxes.data(), leaf_boxes.p, cs.leaf_boxes.size() * sizeof(float), hipMemcpyDeviceToHost));
-        if (host_order_stale) {
+        if (host->host_order_stale) {
             HIP_TRY(hipMemcpy(cs.corner_vertex.data(), upd_corner.p, cs.corner_vertex.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
             HIP_TRY(hipMemcpy(cs.node_parent.data(), upd_parent.p, cs.node_parent.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
             HIP_TRY(hipMemcpy(cs.node4_src.data(), upd_node4_src.p, cs.node4_src.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -118,9 +141,9 @@ struct gnxr_scene {
             if (!cs.tri_n.empty()) HIP_TRY(hipMemcpy(cs.tri_n.data(), tri_n.p, cs.tri_n.size() * sizeof(float), hipMemcpyDeviceToHost));
             if (!cs.tri_s.empty()) HIP_TRY(hipMemcpy(cs.tri_s.data(), tri_s.p, cs.tri_s.size() * sizeof(float), hipMemcpyDeviceToHost));
             for (size_t li = 0; li < cs.tris.size(); ++li) cs.leaf_of_prim[cs.tris[li].prim] = (int32_t)li;
-            host_order_stale = false;
+            host->host_order_stale = false;
         }
-        host_bvh_stale = false;
+        host->host_bvh_stale = false;
         return GNXR_OK;
     }
     ~gnxr_scene() {
@@ -169,6 +192,20 @@ struct gnxr_scene {
         d.st.perms = perms.p; d.st.primes = primes.p; d.st.prime_sums = prime_sums.p; d.st.prime_magic = prime_magic.p;
         d.st.h = make_halton(W, H);
         return d;
+    }
+    // the record in front of the materials (tex_tables(), device_texture.h): the texture tables and the per-corner attribute tables the
+    // scene has, at the given addresses (an empty upload still allocates, so an absent table is decided by the host scene)
+    DTexTables tex_tables(const float *uv, const float *n, const float *s) const {
+        DTexTables tt;
+        tt.textures = textures.p; tt.texels = reinterpret_cast<const float4 *>(tex_texels.p); tt.ewa_lut = ewa_lut.p;
+        tt.tri_uv = cs.tri_uv.empty() ? nullptr : uv; tt.tri_n = cs.tri_n.empty() ? nullptr : n; tt.tri_s = cs.tri_s.empty() ? nullptr : s;
+        return tt;
+    }
+    // what the tree allows: the binary walk's stack size and whether the 4-wide traversal can hold it (leaf sizes / triangle count fit the
+    // reference encoding).  leaf_over_127: some leaf holds more than 127 primitives.
+    void set_traversal(bool leaf_over_127) {
+        stack_size = cs.bvh_max_depth + 1 <= 32 ? 32 : 64;
+        wide_ok = cs.tris.size() < (1u << 24) && cs.stack4_need + 1 <= 128 && !Knobs::binary_bvh() && !leaf_over_127;
     }
     DMediaTables media_tables() {
         DMediaTables m;

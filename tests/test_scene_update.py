@@ -314,15 +314,18 @@ def test_refit_refusals(gpu):
     assert gpu.lib().gnxr_scene_update_vertices(scene._h, 0, 4, None, None) == ERR_INVALID
 
 
+CAMERAS = {"moved": dict(eye=(1.2, 0.6, 4.4), look=(-0.2, -0.4, 0.0), fov=55.0),
+           "lens": dict(eye=(0.3, 0.2, 4.8), look=(0.0, -0.5, 0.0), fov=50.0, lens_radius=0.08, focal_distance=4.5),
+           "ortho": dict(eye=(0.0, 0.4, 5.0), look=(0.0, 0.0, 0.0), orthographic=True),
+           "fog": dict(eye=(-0.8, 0.3, 4.6), look=(0.2, -0.2, 0.0), fov=65.0),
+           "fog_out": dict(eye=(-0.8, 0.3, 4.6), look=(0.2, -0.2, 0.0), fov=65.0)}
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("kind", ["moved", "lens", "ortho", "fog", "fog_out"])
 def test_set_camera_equals_fresh_scene(gpu, kind):
     """After set_camera the render is that of a scene created with that camera."""
-    cam = {"moved": dict(eye=(1.2, 0.6, 4.4), look=(-0.2, -0.4, 0.0), fov=55.0),
-           "lens": dict(eye=(0.3, 0.2, 4.8), look=(0.0, -0.5, 0.0), fov=50.0, lens_radius=0.08, focal_distance=4.5),
-           "ortho": dict(eye=(0.0, 0.4, 5.0), look=(0.0, 0.0, 0.0), orthographic=True),
-           "fog": dict(eye=(-0.8, 0.3, 4.6), look=(0.2, -0.2, 0.0), fov=65.0),
-           "fog_out": dict(eye=(-0.8, 0.3, 4.6), look=(0.2, -0.2, 0.0), fov=65.0)}[kind]
+    cam = CAMERAS[kind]
     fog = kind.startswith("fog")
     b = scenes.cornell_in_fog() if fog else scenes.dragon_cornell(2000, "glass+metal", mesh_path=MESH2K)
     medium = -1 if kind == "fog_out" else (0 if fog else -1)
@@ -352,5 +355,41 @@ def test_refit_on_replicas(gpu):
         integ.Render(multi, 16, 12, 1)
         multi.update_vertices(v2[:nv])
         same_render(gpu, integ, multi, single, W, H, spp)
+    finally:
+        gpu.init(0)
+
+
+@pytest.mark.gpu
+def test_edit_sequence_on_replicas(gpu):
+    """Device 0 listed twice: every editing call, one after the other, leaves the replicated scene where it leaves a scene on one device.
+    Both copies render (rows are dealt over them), so a camera, a light record or a tree that stayed behind on the second copy shows as
+    every other row differing; the host scene the copies share must end as the single scene's."""
+    from test_light_update import desc_lights, light_records, move_light   # (that module imports this one)
+    b, nv = dragon(gpu, env=ENV)
+    v2 = move_light(deform(vertices(b), nv, seed=21, shift=(0.3, 0.2, 2.5)), emissive_vertices(b))
+    v3 = deform(v2, nv, seed=22)
+    ls = desc_lights(gpu, b)
+    for l in ls[:2]:
+        l.le[:] = [2.0, 6.0, 3.0]
+    integ, (W, H, spp) = gpu.PathIntegrator(5, 1.0, "spatial"), (64, 48, 4)
+    steps = [lambda s: integ.Render(s, 16, 12, 1),
+             lambda s: s.set_camera(**CAMERAS["moved"]),
+             lambda s: s.update_lights(ls[:2]),
+             lambda s: s.update_vertices(v2, move_lights=True),
+             lambda s: s.rebuild_bvh(),
+             lambda s: s.update_vertices(v3[:nv]),
+             lambda s: s.set_camera(**CAMERAS["lens"])]
+    single = gpu.Scene(b)
+    try:
+        gpu.init_devices([0, 0])
+        multi = gpu.Scene(b)
+        for k, step in enumerate(steps, 1):
+            step(single)
+            step(multi)
+            if k in (2, 4, 5, 7):
+                same_render(gpu, integ, multi, single, W, H, spp)
+        for x, y in zip(single.bvh() + single.bvh4(), multi.bvh() + multi.bvh4()):
+            assert biteq(x, y) if getattr(x, "dtype", None) == np.float32 else np.array_equal(x, y)
+        assert biteq(light_records(single, len(ls)), light_records(multi, len(ls)))
     finally:
         gpu.init(0)
