@@ -303,13 +303,18 @@ def material_albedo(**material_fields):
     """gnxr_material_albedo (host, needs no GPU): the colour the albedo channel of RenderAOV reports for a material with these gnxr_material
     fields (the keywords of SceneBuilder.add_material) -- kd clamped to [0, inf) for MATTE / PLASTIC / DISNEY, kr for MIRROR, 1 for GLASS,
     the normal-incidence conductor reflectance for METAL, 0 for NONE -- as a float32 (3,) array.  A kd_texture does not change it."""
+    return _material_albedo(material(**material_fields))
+
+
+def material(**material_fields):
+    """One gnxr_material record (ctypes `Material`) from the keywords of SceneBuilder.add_material: what Scene.update_materials takes."""
     m = Material()
     for k, v in material_fields.items():
         if isinstance(v, (tuple, list, np.ndarray)):
             setattr(m, k, (C.c_float * len(v))(*[float(x) for x in v]))
         else:
             setattr(m, k, v)
-    return _material_albedo(m)
+    return m
 
 
 def write_synthetic_3d(path, target_triangles=100000, seed=1):
@@ -382,6 +387,50 @@ class Scene:
                 raise ValueError(f"update_lights: lights must be gnxr Light records, got {type(l).__name__}")
         arr = (Light * max(len(lights), 1))(*lights)
         _check(lib().gnxr_scene_update_lights(self._h, int(first_light), len(lights), arr))
+
+    def update_materials(self, materials, first_material=0):
+        """Replace materials [first_material, first_material + len(materials)) of the scene's material list by `materials` (gnxr Material
+        records: material(type=..., kd=...), or copies of SceneBuilder.desc().materials[i] with fields changed).  Every field may change,
+        the type included (gnxr_scene_update_materials); afterwards the scene renders as one created with those records.  An unknown
+        type or a texture the scene does not have raises GnxrError and leaves the scene as it was."""
+        materials = list(materials)
+        for m in materials:
+            if not isinstance(m, Material):
+                raise ValueError(f"update_materials: materials must be gnxr Material records, got {type(m).__name__}")
+        arr = (Material * max(len(materials), 1))(*materials)
+        _check(lib().gnxr_scene_update_materials(self._h, int(first_material), len(materials), arr))
+
+    def set_triangle_materials(self, ids, first_triangle=0, stream=None):
+        """Give triangles [first_triangle, first_triangle + len(ids)) (authoring order) the materials `ids`: an int32 (n,) numpy array
+        (host memory) or a contiguous int32 (n,) torch tensor on the scene's device (read on `stream`, by default the current torch
+        stream), values in [-1, n_materials), -1 == no material (gnxr_scene_set_triangle_materials)."""
+        if isinstance(ids, np.ndarray):
+            if ids.dtype != np.int32 or ids.ndim != 1:
+                raise ValueError(f"set_triangle_materials: expected an int32 array of shape (n,), got {ids.dtype} {ids.shape}")
+            ids = np.ascontiguousarray(ids)
+            ptr = ids.ctypes.data
+        elif type(ids).__module__.split(".")[0] == "torch":
+            import torch
+            if not (isinstance(ids, torch.Tensor) and ids.is_cuda and ids.device.index == self.device and ids.dtype == torch.int32 and
+                    ids.dim() == 1 and ids.is_contiguous()):
+                raise ValueError(f"set_triangle_materials: expected a contiguous int32 (n,) tensor on cuda:{self.device}, got "
+                                 f"{getattr(ids, 'dtype', None)} {tuple(getattr(ids, 'shape', ()))} on {getattr(ids, 'device', None)}")
+            ptr = ids.data_ptr()
+            if stream is None:
+                stream = torch.cuda.current_stream(ids.device)
+        else:
+            raise ValueError(f"set_triangle_materials: expected a numpy array or a torch tensor, got {type(ids).__name__}")
+        stream = _stream_handle("set_triangle_materials", stream)
+        _check(lib().gnxr_scene_set_triangle_materials(self._h, int(first_triangle), int(ids.shape[0]), C.c_void_p(ptr or None), C.c_void_p(stream or None)))
+
+    def triangle_materials(self):
+        """Test hook: per triangle in authoring order, read from the device, (authored material index it shows or -1, shade class):
+        (int32 (n,), uint8 (n,))."""
+        mat = np.zeros(self.n_triangles, np.int32); cls = np.zeros(self.n_triangles, np.uint8)
+        rc = lib().gnxr_scene_triangle_materials(self._h, mat.ctypes.data_as(C.POINTER(C.c_int32)), cls.ctypes.data_as(C.POINTER(C.c_uint8)), self.n_triangles)
+        if rc < 0:
+            _check(rc)
+        return mat, cls
 
     def rebuild_bvh(self, stream=None):
         """Rebuild the BVH on the device over the vertices the scene holds now (after update_vertices): the HLBVH tree a new Scene over

@@ -147,6 +147,9 @@ PROTOTYPES = {
     "gnxr_scene_update_vertices_ex": (C.c_int, [VP, i32, i32, VP, u32, VP]),   # ..., flags (UPDATE_MOVE_LIGHTS), hipStream_t
     "gnxr_scene_update_lights": (C.c_int, [VP, i32, i32, P(Light)]),
     "gnxr_scene_rebuild_bvh": (C.c_int, [VP, VP]),   # scene, hipStream_t
+    "gnxr_scene_update_materials": (C.c_int, [VP, i32, i32, P(Material)]),
+    "gnxr_scene_set_triangle_materials": (C.c_int, [VP, i32, i32, VP, VP]),   # scene, first, n, host or device int32 ids, hipStream_t
+    "gnxr_scene_triangle_materials": (C.c_int, [VP, P(i32), P(C.c_uint8), C.c_int64]),
     "gnxr_scene_set_camera": (C.c_int, [VP, P(Camera), i32]),
     "gnxr_render": (C.c_int, [VP, P(RenderParams), P(f32), P(Stats)]),
     "gnxr_render_device": (C.c_int, [VP, P(RenderParams), VP, VP, P(Stats)]),

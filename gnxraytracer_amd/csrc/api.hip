@@ -18,6 +18,7 @@
 #include "trace4_kernel.hip.h"
 #include "hlbvh_build.hip.h"
 #include "refit_kernel.hip.h"
+#include "material_kernel.hip.h"
 #include "rebuild_kernel.hip.h"
 #include "li_kernel.hip.h"
 #include "views_kernel.hip.h"
@@ -124,10 +125,14 @@ static int upload_scene(gnxr_scene *s, size_t) {
 #define UP(field) if ((rc = s->field.upload(cs.field)) != GNXR_OK) return rc;
     UP(nodes) UP(nodes4) UP(tris) UP(leaf_boxes) UP(tri_class) UP(lights) UP(perms) UP(primes) UP(prime_sums) UP(prime_magic)
     UP(dmedia) UP(grid_density) UP(tri_media) UP(spheres) UP(textures) UP(tex_texels) UP(ewa_lut) UP(tri_uv) UP(tri_n) UP(tri_s)
-    UP(aov_albedo) UP(material_authored)
+    UP(aov_albedo)
     UP(env_texels4) UP(env_cond_func) UP(env_cond_cdf) UP(env_cond_int) UP(env_marg_func) UP(env_marg_cdf) UP(env_marg_guide) UP(env_cond_guide)
 #undef UP
-    {   // materials, preceded by one record that carries the texture tables
+    {   // materials, preceded by one record that carries the texture tables.  A material edit may give every authored material an attribute
+        // copy: the buffers are sized for that once, so that no edit reallocates them under queries in flight
+        const size_t worst = 2 * cs.desc_materials.size();
+        if ((rc = s->material_authored.alloc(worst)) || (rc = s->materials.alloc(1 + worst)) || (rc = s->materials_single.alloc(1 + worst))) return rc;
+        if ((rc = s->material_authored.upload(cs.material_authored)) != GNXR_OK) return rc;
         const DTexTables rec = s->tex_tables(s->tri_uv.p, s->tri_n.p, s->tri_s.p);
         for (int k = 0; k < 2; ++k) {
             const std::vector<DMaterial> &src = k == 0 ? cs.materials : cs.materials_single;

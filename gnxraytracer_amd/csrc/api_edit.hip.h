@@ -1,6 +1,7 @@
-// api_edit.hip.h -- editing a scene in place: gnxr_scene_update_vertices[_ex] (the BVH refit, refit_kernel.hip.h), gnxr_scene_update_lights
-// and gnxr_scene_set_camera.  Part of api.hip's translation unit (before api_rebuild.hip.h, which uses refit_tables).  An edit changes the
-// handle's one host scene (SceneHost) once and the device tables of every copy in turn (each_copy), under the primary's render_mutex.
+// api_edit.hip.h -- editing a scene in place: gnxr_scene_update_vertices[_ex] (the BVH refit, refit_kernel.hip.h), gnxr_scene_update_lights,
+// gnxr_scene_update_materials / gnxr_scene_set_triangle_materials (material_kernel.hip.h) and gnxr_scene_set_camera.  Part of api.hip's
+// translation unit (before api_rebuild.hip.h, which uses refit_tables).  An edit changes the handle's one host scene (SceneHost) once and
+// the device tables of every copy in turn (each_copy), under the primary's render_mutex.
 #pragma once
 
 // the refit's tables go to a device at the first update of the scene (the flag is allocated last: it marks the set complete)
@@ -169,6 +170,165 @@ extern "C" int gnxr_scene_update_lights(gnxr_scene *s, int32_t first_light, int3
     s->cs.desc_lights = std::move(descs);
     for (size_t i = 0; i < s->n_copies(); ++i) s->copy(i)->grid_strategy = -1;
     return GNXR_OK;
+}
+
+// ---- materials.  Both edits build the tables compile_materials gives the edited description into a copy (MaterialEdit), write every copy of
+// the scene with material_apply and only then make them the host scene's.
+
+// the authoring-order tables of k_material_tris go to a (bound) device at the first material edit of the scene
+static int material_tables(gnxr_scene *s) {
+    if (s->mat_map.p) return GNXR_OK;
+    const CompiledScene &cs = s->cs;
+    int rc;
+    if ((rc = s->mat_tri.upload(cs.tri_material)) || (rc = s->mat_own.upload(cs.tri_own_attr)) || (rc = s->mat_map.alloc(cs.mat_map.size()))) return rc;
+    return GNXR_OK;
+}
+
+struct MaterialEdit {
+    MaterialTables mt;
+    std::vector<DSphere> spheres;         // DSphere::material follows its material's type (-1 for GNXR_MAT_NONE)
+    const int32_t *ids = nullptr;         // gnxr_scene_set_triangle_materials: host copy of tri_material[first, first + n)
+    int first = 0, n = 0;
+};
+
+// the state the host scene holds, in the form of an edit (what a failed upload puts back)
+static MaterialEdit material_current(const CompiledScene &cs, int first, int n) {
+    MaterialEdit e;
+    e.mt.materials = cs.materials; e.mt.materials_single = cs.materials_single; e.mt.aov_albedo = cs.aov_albedo;
+    e.mt.material_authored = cs.material_authored; e.mt.mat_map = cs.mat_map;
+    e.spheres = cs.spheres;
+    e.ids = n > 0 ? cs.tri_material.data() + first : nullptr; e.first = first; e.n = n;
+    return e;
+}
+
+static std::vector<DSphere> material_spheres(const CompiledScene &cs, const std::vector<gnxr_material> &mats) {
+    std::vector<DSphere> sp = cs.spheres;
+    for (size_t i = 0; i < cs.sphere_material.size(); ++i) {
+        const int m = cs.sphere_material[i];
+        sp[i].material = (m >= 0 && mats[m].type == GNXR_MAT_NONE) ? -1 : m;
+    }
+    return sp;
+}
+
+// One copy's share of a material edit, on its (bound) device: the small tables over the device's (their buffers were sized for the worst
+// case by upload_scene), the edited range of the authored ids, then one pass over the leaf-order triangles.  Everything is queued on st and
+// waited for.  Nothing here reads the host's leaf-order tables: they may be stale after a rebuild, and DTri::prim is all the kernel needs.
+static int material_apply(gnxr_scene *s, const MaterialEdit &e, hipStream_t st) {
+    const CompiledScene &cs = s->cs;
+    const size_t ni = e.mt.materials.size();
+    if (int rc = material_tables(s)) return rc;
+    if (ni + 1 > s->materials.n || ni + 1 > s->materials_single.n || ni > s->material_authored.n || e.mt.mat_map.size() > s->mat_map.n || e.mt.aov_albedo.size() > s->aov_albedo.n ||
+        e.spheres.size() > s->spheres.n || (size_t)e.first + e.n > s->mat_tri.n) {
+        set_error("material edit: %zu internal materials do not fit the scene's tables", ni);
+        return GNXR_ERR_RUNTIME;
+    }
+    HIP_TRY(hipMemcpyAsync(s->materials.p + 1, e.mt.materials.data(), ni * sizeof(DMaterial), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s->materials_single.p + 1, e.mt.materials_single.data(), ni * sizeof(DMaterial), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s->aov_albedo.p, e.mt.aov_albedo.data(), e.mt.aov_albedo.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s->material_authored.p, e.mt.material_authored.data(), ni * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s->mat_map.p, e.mt.mat_map.data(), e.mt.mat_map.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s->spheres.p, e.spheres.data(), e.spheres.size() * sizeof(DSphere), hipMemcpyHostToDevice, st));
+    if (e.n > 0) HIP_TRY(hipMemcpyAsync(s->mat_tri.p + e.first, e.ids, (size_t)e.n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    const int nt = (int)cs.tris.size();
+    hipLaunchKernelGGL(matedit::k_material_tris, dim3(grid_for(nt)), dim3(refit::kB), 0, st, s->tris.p, s->tri_class.p, nt, (const int *)s->mat_tri.p,
+                       (const unsigned char *)s->mat_own.p, reinterpret_cast<const int4 *>(s->mat_map.p));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    return GNXR_OK;
+}
+
+// every copy takes the edit (the primary on the caller's stream); a copy that fails puts the host's state, still the old one, back on all
+static int material_apply_all(gnxr_scene *s, const MaterialEdit &e, hipStream_t st) {
+    const int rc = s->each_copy([&](gnxr_scene *d, size_t i) -> int { return material_apply(d, e, i == 0 ? st : nullptr); });
+    if (rc == GNXR_OK) return rc;
+    const std::string why = get_error();
+    const MaterialEdit old = material_current(s->cs, e.first, e.n);
+    (void)s->each_copy([&](gnxr_scene *d, size_t) -> int { return d->mat_map.p ? material_apply(d, old, nullptr) : GNXR_OK; });
+    set_error("%s", why.c_str());
+    return rc;
+}
+
+extern "C" int gnxr_scene_update_materials(gnxr_scene *s, int32_t first_material, int32_t n_materials, const gnxr_material *materials) {
+    if (!s) { set_error("null scene"); return GNXR_ERR_INVALID; }
+    if (n_materials > 0 && !materials) { set_error("null material array"); return GNXR_ERR_INVALID; }
+    const int64_t have = (int64_t)s->cs.desc_materials.size();   // (the number of materials never changes)
+    if (first_material < 0 || n_materials < 0 || (int64_t)first_material + n_materials > have) {
+        set_error("material range [%d, %lld) outside the scene's %lld materials", first_material, (long long)first_material + n_materials, (long long)have);
+        return GNXR_ERR_INVALID;
+    }
+    if (n_materials == 0) return GNXR_OK;
+    std::lock_guard<std::recursive_mutex> lock(s->render_mutex);
+    CompiledScene &cs = s->cs;
+    // 1. all records into a copy: a refusal leaves the scene as it was
+    std::vector<gnxr_material> descs = cs.desc_materials;
+    std::copy(materials, materials + n_materials, descs.begin() + first_material);
+    MaterialEdit e;
+    if (!compile_materials(descs.data(), (int)descs.size(), (int)cs.textures.size(), cs.sphere_material, cs.tri_material.data(), cs.tri_own_attr.data(), (int)cs.tri_material.size(),
+                           nullptr, &e.mt))
+        return GNXR_ERR_INVALID;
+    e.spheres = material_spheres(cs, descs);
+    // 2. every copy of the scene, 3. the host scene (the render plan derives the kernel set from cs.materials at every call)
+    if (int rc = material_apply_all(s, e, nullptr)) return rc;
+    e.mt.move_to(&cs);
+    cs.desc_materials = std::move(descs);
+    cs.spheres = std::move(e.spheres);
+    s->host->host_bvh_stale = true;   // cs.tris / cs.tri_class lag the device until sync_host_bvh()
+    return GNXR_OK;
+}
+
+extern "C" int gnxr_scene_set_triangle_materials(gnxr_scene *s, int32_t first_triangle, int32_t n_triangles, const int32_t *material, void *hip_stream) {
+    if (!s) { set_error("null scene"); return GNXR_ERR_INVALID; }
+    if (n_triangles > 0 && !material) { set_error("null material id array"); return GNXR_ERR_INVALID; }
+    const int64_t have = (int64_t)s->cs.tri_material.size();
+    if (first_triangle < 0 || n_triangles < 0 || (int64_t)first_triangle + n_triangles > have) {
+        set_error("triangle range [%d, %lld) outside the scene's %lld triangles", first_triangle, (long long)first_triangle + n_triangles, (long long)have);
+        return GNXR_ERR_INVALID;
+    }
+    if (n_triangles == 0) return GNXR_OK;
+    std::lock_guard<std::recursive_mutex> lock(s->render_mutex);
+    int rc = s->bind();
+    if (rc) return rc;
+    CompiledScene &cs = s->cs;
+    hipStream_t st = (hipStream_t)hip_stream;
+    // the ids come to the host (one copy path for host and device memory, ordered after what the caller queued on its stream): which
+    // authored materials triangles with attributes of their own use decides the attribute copies.  Validated before anything is written.
+    std::vector<int32_t> ids((size_t)n_triangles);
+    HIP_TRY(hipMemcpyAsync(ids.data(), material, ids.size() * sizeof(int32_t), hipMemcpyDefault, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int nm = (int)cs.desc_materials.size();
+    for (int i = 0; i < n_triangles; ++i)
+        if (ids[i] < -1 || ids[i] >= nm) { set_error("triangle %d: material %d outside [-1, %d)", first_triangle + i, ids[i], nm); return GNXR_ERR_INVALID; }
+    std::vector<int32_t> tri_material = cs.tri_material;
+    std::copy(ids.begin(), ids.end(), tri_material.begin() + first_triangle);
+    MaterialEdit e;
+    if (!compile_materials(cs.desc_materials.data(), nm, (int)cs.textures.size(), cs.sphere_material, tri_material.data(), cs.tri_own_attr.data(), (int)tri_material.size(), nullptr, &e.mt))
+        return GNXR_ERR_INVALID;
+    e.spheres = cs.spheres;
+    e.ids = ids.data(); e.first = first_triangle; e.n = n_triangles;
+    if ((rc = material_apply_all(s, e, st)) != GNXR_OK) return rc;
+    e.mt.move_to(&cs);
+    cs.tri_material = std::move(tri_material);
+    s->host->host_bvh_stale = true;
+    return GNXR_OK;
+}
+
+// test hook: what the primary's device holds per triangle, back in authoring order
+extern "C" int gnxr_scene_triangle_materials(gnxr_scene *s, int32_t *material_out, uint8_t *shade_class_out, int64_t capacity) {
+    if (!s) { set_error("null scene"); return GNXR_ERR_INVALID; }
+    const int nt = (int)s->cs.tri_material.size();
+    if (!material_out || !shade_class_out || capacity < nt) return nt;
+    std::lock_guard<std::recursive_mutex> lock(s->render_mutex);
+    int rc = s->bind();
+    if (rc) return rc;
+    DevBuf<int32_t> d_mat;
+    DevBuf<uint8_t> d_cls;
+    if ((rc = d_mat.alloc(nt)) || (rc = d_cls.alloc(nt))) return rc;
+    hipLaunchKernelGGL(matedit::k_material_gather, dim3(grid_for(nt)), dim3(refit::kB), 0, 0, (const DTri *)s->tris.p, (const unsigned char *)s->tri_class.p, nt,
+                       (const int *)s->material_authored.p, d_mat.p, d_cls.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(material_out, d_mat.p, (size_t)nt * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(shade_class_out, d_cls.p, (size_t)nt, hipMemcpyDeviceToHost));
+    return nt;
 }
 
 extern "C" int gnxr_scene_set_camera(gnxr_scene *s, const gnxr_camera *camera, int32_t camera_medium) {

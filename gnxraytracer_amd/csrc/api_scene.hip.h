@@ -118,6 +118,10 @@ struct gnxr_scene {
     DevBuf<unsigned int> upd_arrived;
     DevBuf<float> upd_xyz;
     DevBuf<int> upd_flag;
+    // gnxr_scene_update_materials / gnxr_scene_set_triangle_materials: CompiledScene::tri_material / tri_own_attr / mat_map, uploaded at the
+    // first edit (material_tables; the map is allocated last: it marks the set complete) and kept current by every edit after it
+    DevBuf<int32_t> mat_tri, mat_map;
+    DevBuf<uint8_t> mat_own;
     // gnxr_render_views_device: the host copy of st.view_cams (what the stream-ordered upload reads; both only grow)
     std::vector<DCamera> h_view_cams;
 
@@ -131,11 +135,11 @@ struct gnxr_scene {
         HIP_TRY(hipMemcpy(cs.nodes4.data(), nodes4.p, cs.nodes4.size() * sizeof(DNode4), hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(cs.tris.data(), tris.p, cs.tris.size() * sizeof(DTri), hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(cs.leaf_boxes.data(), leaf_boxes.p, cs.leaf_boxes.size() * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(cs.tri_class.data(), tri_class.p, cs.tri_class.size(), hipMemcpyDeviceToHost));   // (a material edit rewrites it on the device)
         if (host->host_order_stale) {
             HIP_TRY(hipMemcpy(cs.corner_vertex.data(), upd_corner.p, cs.corner_vertex.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
             HIP_TRY(hipMemcpy(cs.node_parent.data(), upd_parent.p, cs.node_parent.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
             HIP_TRY(hipMemcpy(cs.node4_src.data(), upd_node4_src.p, cs.node4_src.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(cs.tri_class.data(), tri_class.p, cs.tri_class.size(), hipMemcpyDeviceToHost));
             if (!cs.tri_media.empty()) HIP_TRY(hipMemcpy(cs.tri_media.data(), tri_media.p, cs.tri_media.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
             if (!cs.tri_uv.empty()) HIP_TRY(hipMemcpy(cs.tri_uv.data(), tri_uv.p, cs.tri_uv.size() * sizeof(float), hipMemcpyDeviceToHost));
             if (!cs.tri_n.empty()) HIP_TRY(hipMemcpy(cs.tri_n.data(), tri_n.p, cs.tri_n.size() * sizeof(float), hipMemcpyDeviceToHost));

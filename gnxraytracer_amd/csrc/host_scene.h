@@ -71,6 +71,13 @@ struct CompiledScene {
     std::vector<float> tri_s;                  // the same for TriangleMesh::s (shading tangents)
     std::vector<float> aov_albedo;             // feature buffers: float4 per AUTHORED material, gnxr_material_albedo's rgb + the bits of kd_texture
     std::vector<int32_t> material_authored;    // per entry of `materials` (the attribute copies included): the authored material index
+    // material edits (gnxr_scene_update_materials / gnxr_scene_set_triangle_materials): what compile_materials reads, in AUTHORING order and
+    // therefore valid whatever leaf order the tree has; the two per-triangle tables go to the device at the first edit
+    std::vector<gnxr_material> desc_materials;   // gnxr_scene_desc::materials
+    std::vector<int32_t> tri_material;           // gnxr_scene_desc::tri_material
+    std::vector<uint8_t> tri_own_attr;           // per authored triangle: 1 = uvs other than the defaults, normals or tangents of its own
+    std::vector<int32_t> sphere_material;        // gnxr_sphere::material (DSphere::material is -1 for a GNXR_MAT_NONE material)
+    std::vector<int32_t> mat_map;                // 4 per authored material: internal index (-1: no BSDF), its attribute copy (-1: none), shade class, 0
     std::vector<DLight> lights;
     std::vector<int32_t> infinite_lights;
     // sampler
@@ -107,6 +114,21 @@ struct HlbvhNode { float b[6]; int32_t child[2]; int32_t axis, first, n; };   //
 typedef bool (*HlbvhBuildFn)(const float *prim_bounds6, const float *centroids3, int n, const float lo[3], const float hi[3],
                              std::vector<HlbvhNode> *nodes, int *root, uint32_t *prims_sorted);
 bool compile_scene(const gnxr_scene_desc *d, CompiledScene *out, HlbvhBuildFn hlbvh_build = nullptr);
+// The materials section of compile_scene, which gnxr_scene_create and the material edits share: the internal material tables (one record per
+// authored material, then one attribute copy per material that a triangle with uvs, normals or tangents of its own uses, numbered in the
+// order `visit` -- n_triangles authored indices, null = authoring order -- meets them), the feature buffers' albedo table, the way back
+// to the authored index and mat_map.  Validates as compile_scene does (texture references, textured materials on spheres, unknown types);
+// false (error set) leaves *mt half-written and nothing else touched.
+struct MaterialTables {
+    std::vector<DMaterial> materials, materials_single;
+    std::vector<float> aov_albedo;
+    std::vector<int32_t> material_authored, mat_map;
+    void move_to(CompiledScene *cs);
+};
+bool compile_materials(const gnxr_material *mats, int n_materials, int n_textures, const std::vector<int32_t> &sphere_material, const int32_t *tri_material,
+                       const uint8_t *tri_own_attr, int n_triangles, const int32_t *visit, MaterialTables *mt);
+// one triangle's DTri::material and tri_class byte from mat_map (k_material_tris, material_kernel.hip.h, is the device's form)
+void triangle_material(const int32_t *mat_map, int32_t authored, uint8_t own_attr, int32_t *material, uint8_t *shade_class);
 // after a refit: the root box of the binary BVH (lo.xyz hi.xyz) -> world_bound (grown by the spheres), the environment light's bounding
 // sphere and the distant lights' radius, computed as compile_scene computes them
 void refit_world_bound(CompiledScene *cs, const float root6[6]);

@@ -925,6 +925,74 @@ static bool build_textures(const gnxr_scene_desc *d, CompiledScene *cs) {
     return true;
 }
 
+// ------------------------------------------------------------------ materials
+static bool material_textures_ok(const gnxr_material &m, int index, int n_textures) {
+    if (m.kd_texture > n_textures || m.ks_texture > n_textures || m.kd_texture < 0 || m.ks_texture < 0) { set_error("material %d: texture reference out of range", index); return false; }
+    return true;
+}
+static bool sphere_material_ok(const gnxr_material *mats, int n_materials, int m, int sphere) {
+    if (m >= 0 && m < n_materials && (mats[m].kd_texture || mats[m].ks_texture)) { set_error("sphere %d: image-textured materials are supported on triangles only", sphere); return false; }
+    return true;
+}
+
+void MaterialTables::move_to(CompiledScene *cs) {
+    cs->materials = std::move(materials); cs->materials_single = std::move(materials_single);
+    cs->aov_albedo = std::move(aov_albedo); cs->material_authored = std::move(material_authored); cs->mat_map = std::move(mat_map);
+}
+
+bool compile_materials(const gnxr_material *mats, int n_materials, int n_textures, const std::vector<int32_t> &sphere_material, const int32_t *tri_material,
+                       const uint8_t *tri_own_attr, int n_triangles, const int32_t *visit, MaterialTables *mt) {
+    for (int i = 0; i < n_materials; ++i) if (!material_textures_ok(mats[i], i, n_textures)) return false;
+    for (size_t i = 0; i < sphere_material.size(); ++i) if (!sphere_material_ok(mats, n_materials, sphere_material[i], (int)i)) return false;
+    mt->materials.resize(std::max(1, n_materials));
+    memset(mt->materials.data(), 0, sizeof(DMaterial) * mt->materials.size());
+    for (int i = 0; i < n_materials; ++i) if (!compile_material(mats[i], &mt->materials[i])) return false;
+    mt->materials_single = mt->materials;   // ComputeScatteringFunctions(..., allowMultipleLobes = false): differs for smooth glass only
+    for (int i = 0; i < n_materials; ++i) if (!compile_material(mats[i], &mt->materials_single[i], false)) return false;
+    mt->mat_map.assign(4 * (size_t)std::max(1, n_materials), 0);
+    for (int i = 0; i < n_materials; ++i) {
+        mt->mat_map[4 * (size_t)i] = mats[i].type == GNXR_MAT_NONE ? -1 : i;   // no BSDF: medium boundary
+        mt->mat_map[4 * (size_t)i + 1] = -1;
+        mt->mat_map[4 * (size_t)i + 2] = mt->materials[i].shade_class;
+    }
+    // A triangle whose uvs are not the GetUVs defaults or that has normals gets a COPY of its material with shade class 3 (the general
+    // shade queue, which reads the attribute tables and derives dpdu / dpdv, the shading frame and dndu / dndv from them); everything
+    // else stays on the kernels with the defaults folded in.
+    for (int k = 0; k < n_triangles; ++k) {
+        const int prim = visit ? visit[k] : k, m = tri_material[prim];
+        if (m < 0 || !tri_own_attr[prim] || mt->mat_map[4 * (size_t)m] < 0 || mt->mat_map[4 * (size_t)m + 1] >= 0) continue;
+        mt->mat_map[4 * (size_t)m + 1] = (int32_t)mt->materials.size();
+        DMaterial c = mt->materials[m], cs_ = mt->materials_single[m];
+        c.shade_class = cs_.shade_class = 3;
+        c.has_attr = cs_.has_attr = 1;
+        mt->materials.push_back(c);
+        mt->materials_single.push_back(cs_);
+    }
+    // feature buffers (gnxr_render_aov_device): one albedo per AUTHORED material (w: the bits of kd_texture, so that the device knows
+    // where to look the colour up instead) and the way back from an internal material -- the attribute copies above included -- to the
+    // authored index the ids channel reports
+    mt->aov_albedo.assign((size_t)std::max(1, n_materials) * 4, 0.f);
+    for (int i = 0; i < n_materials; ++i) {
+        if (!material_albedo(mats[i], &mt->aov_albedo[(size_t)i * 4])) { set_error("unknown material type %d", mats[i].type); return false; }
+        memcpy(&mt->aov_albedo[(size_t)i * 4 + 3], &mats[i].kd_texture, 4);
+    }
+    mt->material_authored.assign(mt->materials.size(), 0);
+    for (int i = 0; i < n_materials; ++i) {
+        mt->material_authored[i] = i;
+        if (mt->mat_map[4 * (size_t)i + 1] >= 0) mt->material_authored[mt->mat_map[4 * (size_t)i + 1]] = i;
+    }
+    return true;
+}
+
+void triangle_material(const int32_t *mat_map, int32_t authored, uint8_t own_attr, int32_t *material, uint8_t *shade_class) {
+    *material = authored; *shade_class = 0;
+    if (authored < 0) return;
+    const int32_t *e = mat_map + 4 * (size_t)authored;
+    if (e[0] < 0) { *material = -1; return; }
+    *material = own_attr ? e[1] : e[0];
+    *shade_class = (uint8_t)(own_attr ? 3 : e[2]);
+}
+
 // ------------------------------------------------------------------ compile
 bool compile_scene(const gnxr_scene_desc *d, CompiledScene *cs, HlbvhBuildFn hlbvh_build) {
     if (!d || d->abi_version != GNXR_ABI_VERSION) { set_error("scene description ABI version mismatch"); return false; }
@@ -938,16 +1006,11 @@ bool compile_scene(const gnxr_scene_desc *d, CompiledScene *cs, HlbvhBuildFn hlb
         set_error("scene description: a table has a count but no data");
         return false;
     }
-    for (int i = 0; i < d->n_materials; ++i)
-        if (d->materials[i].kd_texture > d->n_textures || d->materials[i].ks_texture > d->n_textures || d->materials[i].kd_texture < 0 || d->materials[i].ks_texture < 0) {
-            set_error("material %d: texture reference out of range", i);
-            return false;
-        }
+    // (compile_materials applies these two checks again, for the edits; creation keeps them here as well so that a bad reference is refused
+    // before the textures and the tree are built and the order in which errors are reported stays what it was)
+    for (int i = 0; i < d->n_materials; ++i) if (!material_textures_ok(d->materials[i], i, d->n_textures)) return false;
     if (!build_textures(d, cs)) return false;
-    for (int i = 0; i < d->n_spheres; ++i) {
-        const int m = d->spheres[i].material;
-        if (m >= 0 && m < d->n_materials && (d->materials[m].kd_texture || d->materials[m].ks_texture)) { set_error("sphere %d: image-textured materials are supported on triangles only", i); return false; }
-    }
+    for (int i = 0; i < d->n_spheres; ++i) if (!sphere_material_ok(d->materials, d->n_materials, d->spheres[i].material, i)) return false;
     for (int i = 0; i < 3 * d->n_triangles; ++i)
         if (d->indices[i] < 0 || d->indices[i] >= d->n_vertices) { set_error("triangle index out of range"); return false; }
     for (int i = 0; i < d->n_triangles; ++i) {
@@ -1022,6 +1085,7 @@ bool compile_scene(const gnxr_scene_desc *d, CompiledScene *cs, HlbvhBuildFn hlb
     cs->world_bound.hi = Vec3(cs->nodes[0].hi0, cs->nodes[0].hi1, cs->nodes[0].hi2);
     // ---- spheres (outside the BVH)
     cs->spheres.assign(std::max(1, d->n_spheres), DSphere());
+    cs->sphere_material.assign(d->n_spheres, -1);
     for (int i = 0; i < d->n_spheres; ++i) {
         const gnxr_sphere &sp = d->spheres[i];
         DSphere &ds = cs->spheres[i];
@@ -1032,6 +1096,7 @@ bool compile_scene(const gnxr_scene_desc *d, CompiledScene *cs, HlbvhBuildFn hlb
         memcpy(ds.c, sp.center, 12);
         ds.r = sp.radius;
         ds.material = (sp.material >= 0 && d->materials[sp.material].type == GNXR_MAT_NONE) ? -1 : sp.material;
+        cs->sphere_material[i] = sp.material;
         ds.med_in = sp.medium_inside; ds.med_out = sp.medium_outside;
         ds.prim = d->n_triangles + i;
     }
@@ -1066,23 +1131,16 @@ bool compile_scene(const gnxr_scene_desc *d, CompiledScene *cs, HlbvhBuildFn hlb
                 if (!(lo_v == n.lo[a]) || !(hi_v == hi[a])) cs->leaf1_from_verts = 0;
             }
         }
-    // ---- materials
-    cs->materials.resize(std::max(1, d->n_materials));
-    memset(cs->materials.data(), 0, sizeof(DMaterial) * cs->materials.size());
-    for (int i = 0; i < d->n_materials; ++i) if (!compile_material(d->materials[i], &cs->materials[i])) return false;
-    cs->materials_single = cs->materials;   // ComputeScatteringFunctions(..., allowMultipleLobes = false): differs for smooth glass only
-    for (int i = 0; i < d->n_materials; ++i) if (!compile_material(d->materials[i], &cs->materials_single[i], false)) return false;
-    // ---- per-corner uvs and shading normals (TriangleMesh::uv / ::n).  A triangle whose uvs are not the GetUVs defaults or that has
-    // normals gets a COPY of its material with shade class 3 (the general shade queue, which reads the attribute tables and derives
-    // dpdu / dpdv, the shading frame and dndu / dndv from them); everything else stays on the kernels with the defaults folded in.
+    // ---- per-corner uvs and shading normals (TriangleMesh::uv / ::n) into leaf order, and per AUTHORED triangle whether it has any of its
+    // own: uvs that are not the GetUVs defaults, normals or tangents (compile_materials gives such a triangle a copy of its material)
     cs->tri_uv.clear();
     cs->tri_n.clear();
     cs->tri_s.clear();
+    cs->tri_own_attr.assign(d->n_triangles, 0);
     if (d->tri_uv || d->tri_n || d->tri_s) {
         if (d->tri_uv) cs->tri_uv.assign((size_t)d->n_triangles * 8, 0.f);
         if (d->tri_n) cs->tri_n.assign((size_t)d->n_triangles * 12, 0.f);
         if (d->tri_s) cs->tri_s.assign((size_t)d->n_triangles * 12, 0.f);
-        std::vector<int> attr_copy(d->n_materials, -1);
         const float def[6] = {0, 0, 1, 0, 1, 1}, zero9[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
         for (int li = 0; li < d->n_triangles; ++li) {
             const int prim = cs->tris[li].prim;
@@ -1106,37 +1164,25 @@ bool compile_scene(const gnxr_scene_desc *d, CompiledScene *cs, HlbvhBuildFn hlb
                 if (hasS && d->tri_light[prim] >= 0) { set_error("triangle %d: per-vertex tangents on an emissive triangle are not supported", prim); return false; }
                 custom = custom || hasS;
             }
-            DTri &t = cs->tris[li];
-            if (t.material < 0 || !custom) continue;
-            if (attr_copy[t.material] < 0) {
-                attr_copy[t.material] = (int)cs->materials.size();
-                DMaterial m = cs->materials[t.material], ms = cs->materials_single[t.material];
-                m.shade_class = ms.shade_class = 3;
-                m.has_attr = ms.has_attr = 1;
-                cs->materials.push_back(m);
-                cs->materials_single.push_back(ms);
-            }
-            t.material = attr_copy[t.material];
+            cs->tri_own_attr[prim] = custom ? 1 : 0;
         }
     }
-    // ---- feature buffers (gnxr_render_aov_device): one albedo per AUTHORED material (w: the bits of kd_texture, so that the device knows
-    // where to look the colour up instead) and the way back from an internal material -- the attribute copies above included -- to the
-    // authored index the ids channel reports
-    cs->aov_albedo.assign((size_t)std::max(1, d->n_materials) * 4, 0.f);
-    for (int i = 0; i < d->n_materials; ++i) {
-        if (!material_albedo(d->materials[i], &cs->aov_albedo[(size_t)i * 4])) { set_error("unknown material type %d", d->materials[i].type); return false; }
-        memcpy(&cs->aov_albedo[(size_t)i * 4 + 3], &d->materials[i].kd_texture, 4);
-    }
-    cs->material_authored.assign(cs->materials.size(), 0);
-    for (int i = 0; i < d->n_materials; ++i) cs->material_authored[i] = i;
-    for (int li = 0; li < d->n_triangles; ++li) {
-        const int m = cs->tris[li].material, authored = d->tri_material[cs->tris[li].prim];
-        if (m >= 0) cs->material_authored[m] = authored;
+    // ---- materials: the tables (compile_materials; the attribute copies numbered in leaf order) and every triangle's share of them
+    cs->desc_materials.assign(d->materials, d->materials + d->n_materials);
+    cs->tri_material.assign(d->tri_material, d->tri_material + d->n_triangles);
+    {
+        std::vector<int32_t> leaf_order(d->n_triangles);
+        for (int li = 0; li < d->n_triangles; ++li) leaf_order[li] = cs->tris[li].prim;
+        MaterialTables mt;
+        if (!compile_materials(cs->desc_materials.data(), d->n_materials, d->n_textures, cs->sphere_material, cs->tri_material.data(), cs->tri_own_attr.data(), d->n_triangles,
+                               leaf_order.data(), &mt))
+            return false;
+        mt.move_to(cs);
     }
     cs->tri_class.assign(d->n_triangles, 0);
     for (int li = 0; li < d->n_triangles; ++li) {
-        const int m = cs->tris[li].material;
-        if (m >= 0) cs->tri_class[li] = (uint8_t)cs->materials[m].shade_class;
+        const int prim = cs->tris[li].prim;
+        triangle_material(cs->mat_map.data(), cs->tri_material[prim], cs->tri_own_attr[prim], &cs->tris[li].material, &cs->tri_class[li]);
     }
     // ---- lights
     cs->lights.resize(std::max(1, d->n_lights));

@@ -424,6 +424,31 @@ int gnxr_scene_update_lights(gnxr_scene *scene, int32_t first_light, int32_t n_l
  * reference's HLBVH build does not terminate (coincident treelet centroids, a leaf over 65535 primitives), GNXR_ERR_UNSUPPORTED for a
  * tree deeper than the 64-entry traversal stack, GNXR_ERR_OOM. */
 int gnxr_scene_rebuild_bvh(gnxr_scene *scene, void *hip_stream);
+/* Replace material records [first_material, first_material + n_materials) of the scene's material list (the numbering of
+ * gnxr_scene_desc.materials) by materials[0 .. n_materials).  Every field may change, the type included: MATTE -> GLASS changes which shade
+ * kernels the next render launches, a BSDF material -> GNXR_MAT_NONE turns its triangles (and spheres) into medium boundaries, and back;
+ * kd_texture / ks_texture may name any texture the scene was created with.  The number of materials and the set of textures are fixed.
+ * Afterwards every result of the handle -- renders of all integrators, gnxr_li_device, gnxr_render_views_device, gnxr_render_aov_device,
+ * gnxr_bsdf_device, the ray queries, the ray counters of gnxr_stats -- is bit for bit that of a scene created from the same description
+ * carrying the edited records (tree aside: it keeps its topology).  The records are validated as gnxr_scene_create validates them
+ * (unknown type, texture reference beyond n_textures, image textures on other than MATTE / PLASTIC or on a sphere's material) and
+ * compiled into a copy first: GNXR_ERR_INVALID leaves the scene exactly as it was, also for a null scene (before any device is touched),
+ * a null materials with n_materials > 0 or a range outside the scene's materials.  n_materials == 0 is a no-op.  The call takes the
+ * handle's render lock, writes every device of the scene -- the material tables, then one kernel over the triangles, which hold their
+ * material's internal index and shade class -- and returns when all hold the edit; a failed upload puts the old state back on the devices
+ * already written.  The BVH, lights, light-selection table, textures, media and the path state of gnxr_render_reserve are not touched. */
+int gnxr_scene_update_materials(gnxr_scene *scene, int32_t first_material, int32_t n_materials, const gnxr_material *materials);
+/* Replace tri_material[first_triangle, first_triangle + n_triangles) (triangles in authoring order, the numbering of
+ * gnxr_scene_desc.tri_material) by material[0 .. n_triangles): values in [-1, n_materials), -1 == no material.  material may be host
+ * memory or device memory of the scene's (first) device; the read is ordered after what hip_stream holds (NULL: the null stream) and the
+ * kernel runs on that stream.  The ids cross to the host (4 bytes per edited triangle) and are validated there before anything is
+ * written.  Emissive triangles may change material.  Contract, error codes, locking and what stays untouched are those of
+ * gnxr_scene_update_materials; GNXR_ERR_INVALID also for an id out of range. */
+int gnxr_scene_set_triangle_materials(gnxr_scene *scene, int32_t first_triangle, int32_t n_triangles, const int32_t *material, void *hip_stream);
+/* Test hook: per triangle in authoring order, read from the scene's first device, the authored material index the triangle currently
+ * shows (-1 where it has no BSDF) and its shade-class byte.  Returns the number of triangles (or a negative gnxr_status); the arrays are
+ * filled when both are given and capacity allows. */
+int gnxr_scene_triangle_materials(gnxr_scene *scene, int32_t *material_out, uint8_t *shade_class_out, int64_t capacity);
 /* Replace the camera (and the medium it sits in, -1 == none) for later renders; same checks as gnxr_scene_create. */
 int gnxr_scene_set_camera(gnxr_scene *scene, const gnxr_camera *camera, int32_t camera_medium);
 
