@@ -115,6 +115,14 @@ int gnxr_debug_trace_stats(unsigned long long *out16, int reset) {   // 24 slots
     return GNXR_OK;
 }
 #endif
+#ifdef GX_TAIL_STAMP
+// development builds only (-DGX_TAIL_STAMP): what of the k_trace4 launches lay behind the end of their work lists (g_tail, trace_kernel.hip.h)
+int gnxr_debug_tail_stamp(unsigned long long *out12, int reset) {
+    if (hipMemcpyFromSymbol(out12, HIP_SYMBOL(g_tail), 12 * sizeof(unsigned long long)) != hipSuccess) return GNXR_ERR_INVALID;
+    if (reset) { unsigned long long z[12] = {~0ull, 0ull, ~0ull, 0ull}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_tail), z, sizeof(z)); }
+    return GNXR_OK;
+}
+#endif
 
 // device side of gnxr_scene_create: everything compile_scene produced goes to the copy's (bound) device (an each_copy callable)
 static int upload_scene(gnxr_scene *s, size_t) {

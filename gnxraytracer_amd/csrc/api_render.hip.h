@@ -351,7 +351,7 @@ struct RenderRun {
 // (device-driven loop: w.n_closest / w.n_nee are upper bounds that size the launch, the kernel reads the counts through
 // w.n_closest_dev / w.n_nee_dev, and the rays are counted on the device: count_rays = false)
 void RenderRun::launch_trace(TraceWork w, int n_sh, int n_mis, bool count_rays) {
-    long long total = (long long)w.n_closest + 2ll * w.n_nee;
+    long long total = (long long)w.n_closest + w.n_nee;   // one work item per continuation ray and per NEE vertex (TraceWork)
     if (total <= 0) return;
     w.order = nullptr;
     // (binning the rays of a launch by kind / octant / origin cell with a radix sort was measured in round 2 and lost -- 57.6 - 62.0 ms against

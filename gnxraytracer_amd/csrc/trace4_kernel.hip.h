@@ -19,6 +19,16 @@
 //     misses, and 55 % of all node visits go to those 64 nodes;
 //   * the traversal stack is LDS-only when the tree's worst case fits (template SPILL = false): no address-space branch per push / pop;
 //   * node addresses are a uniform base + 32-bit offsets.
+// The work list of a render launch is [n_closest continuation rays | n_nee NEE vertices] (TraceWork): ONE item per vertex.  A batch of vertex items
+// sets the shadow rays up and parks them; the lanes whose record also has a MIS ray (flags bit 1) remember it in a spare bit of `pk`, the pool
+// stays on the batch, and when the ready queue next runs empty -- before the pool moves on -- those lanes re-read their queue entries, load the
+// MIS records and park the MIS rays as a batch of their own: never more than 64 records in the queue, no register, no LDS.  (Until this
+// change a vertex was two items, and the MIS items formed a range of their own at the end of the list: with one small light a few percent
+// of them held a ray; the others cost a queue read, three record gathers and a near-empty set-up batch each.)
+// What the scheme costs: every batch of vertex items that holds at least one MIS lane pays a second wave-wide set-up (two ballots, a second
+// read of q_nee by the owing lanes, a fence), and only after its shadow rays have all been drawn from the queue -- where most vertices have
+// both rays that doubles the set-up batches of the NEE range (the parent's MIS batches were full ones there); and the ballot over `pk` that
+// finds owing lanes runs at every refill that finds the queue empty, in the continuation range too.  Measured: profiles/README.md.
 // Q selects where the rays come from and where results go: the render's path records (kT4Render), or caller-supplied rays of a batched
 // query (kT4QueryClosest / kT4QueryAny, query_kernel.hip.h).  The walk between the two is the same code.
 #pragma once
@@ -76,11 +86,16 @@ __global__ void GX_T4_BOUNDS k_trace4(DScene sc, typename Trace4Src<Q>::type pa,
     const int lane = __lane_id();
     lds_int *const rq = (lds_int *)&smem[lds_entries * kBlock + (threadIdx.x >> 6) * kRayQueue];   // this wave's records: rq[field * kRqStride + slot]
     trace_work_counts(w);
-    const unsigned total = (unsigned)w.n_closest + 2u * (unsigned)w.n_nee;
+    const unsigned total = (unsigned)w.n_closest + (unsigned)w.n_nee;   // [continuation rays | NEE vertices]
     chunk = trace_chunk(total, chunk);
     const ChunkPlan plan = chunk_plan(total, (unsigned)chunk);
     const unsigned nWaves = gridDim.x * (kBlock / 64u), waveId = blockIdx.x * (kBlock / 64u) + (threadIdx.x >> 6);
     bool firstFetch = true;   // wave-uniform
+#ifdef GX_TAIL_STAMP
+    const unsigned tailFrom = total;   // the stamped point: the end of the work list
+    bool tailSeen = false;             // wave-uniform: this wave has stamped it
+    if (Q == kT4Render && waveId == 0 && lane == 0) atomicMin(&g_tail[2], (unsigned long long)wall_clock64());
+#endif
     const DTri *__restrict__ tris = sc.tris;
     const char *__restrict__ nb = reinterpret_cast<const char *>(sc.nodes4);
     typedef float f4v __attribute__((ext_vector_type(4)));
@@ -117,6 +132,9 @@ __global__ void GX_T4_BOUNDS k_trace4(DScene sc, typename Trace4Src<Q>::type pa,
     // per-lane ray state
     bool live = false;
     int pk = 0, path = -1;   // pk: kind (bits 0-1: 0 continuation, 1 shadow, 2 MIS) | kz << 2 (Triangle.cpp:91) | done << 4 | exact << 5 | first hit ends the walk << 6 | the staged leaf is in progress (its box is decided) << 7
+    // Bit 8 of pk (kMisOwed) does not belong to the lane's ray but to the lane as a set-up slot: the vertex item this lane set up in the last
+    // batch has a MIS ray that is still to be set up.  The kernel has no register to spare, scalar or vector, and this bit costs none.
+    constexpr int kMisOwed = 256;
     V3 ro, inv;
     float Sx = 0, Sy = 0, tMax = 0;
     unsigned oNX = 0, oNY = 16, oNZ = 32;   // byte offset of the near plane of each axis inside a DNode4 (far = 48 | 80 | 112 - near ... see below)
@@ -133,7 +151,7 @@ __global__ void GX_T4_BOUNDS k_trace4(DScene sc, typename Trace4Src<Q>::type pa,
         ro = V3(q[0 * kRqStride], q[1 * kRqStride], q[2 * kRqStride]); tMax = q[3 * kRqStride];
         inv = V3(q[4 * kRqStride], q[5 * kRqStride], q[6 * kRqStride]); Sx = q[7 * kRqStride];
         Sy = q[8 * kRqStride];
-        pk = __float_as_int(q[9 * kRqStride]);
+        pk = (pk & kMisOwed) | __float_as_int(q[9 * kRqStride]);
         path = __float_as_int(q[10 * kRqStride]);
         hitLeaf = SPH ? rq[slot + 11 * kRqStride] : -1;
         const int neg0 = inv.x < 0, neg1 = inv.y < 0, neg2 = inv.z < 0;
@@ -188,7 +206,9 @@ __global__ void GX_T4_BOUNDS k_trace4(DScene sc, typename Trace4Src<Q>::type pa,
         const unsigned long long needMask = __ballot(need);
         if (needMask) {
             if (rqCount == 0) {
-                if (poolCount == 0 && !exhausted) {
+                // the last batch left MIS rays behind: they are set up (as a batch of their own) before the pool moves on or new work is fetched
+                const bool misPass = Q == kT4Render && __ballot((pk & kMisOwed) != 0) != 0;
+                if (!misPass && poolCount == 0 && !exhausted) {
                     // the cursor counts chunks (chunk_plan / chunk_range, trace_kernel.hip.h); a wave's FIRST chunk is its own number -- no
                     // atomic: 5120 waves asking at once at the start of a launch queue up behind one address for ~60 us
                     unsigned v = waveId;
@@ -198,14 +218,22 @@ __global__ void GX_T4_BOUNDS k_trace4(DScene sc, typename Trace4Src<Q>::type pa,
                     }
                     firstFetch = false;
                     if (!chunk_range(plan, v, total, &poolBase, &poolCount)) { exhausted = true; poolCount = 0; }
+#ifdef GX_TAIL_STAMP
+                    if (Q == kT4Render && !tailSeen && (exhausted || poolBase + poolCount >= tailFrom)) {
+                        tailSeen = true;
+                        if (lane == 0) atomicMin(&g_tail[0], (unsigned long long)wall_clock64());
+                    }
+#endif
                 }
-                if (poolCount > 0) {
-                    // ---- batch set-up: every lane prepares one work item (the ray-only part of Bounds3::IntersectP and Triangle::Intersect)
+                if (misPass || poolCount > 0) {
+                    // ---- batch set-up: every lane prepares one ray (the ray-only part of Bounds3::IntersectP and Triangle::Intersect) -- of the
+                    // next `take` work items, or (misPass) the MIS rays of the vertex items of the previous batch, over which the pool has
+                    // not moved on yet: lane l has item poolBase + l in both
                     const unsigned take = min(poolCount, (unsigned)kRayQueue);
-                    bool valid = false;
+                    bool valid = false, wantMis = false;
                     float4 r0 = make_float4(0, 0, 0, 0), r1 = r0, r2 = r0;
                     int sphHit = -1;
-                    if ((unsigned)lane < take) {
+                    if (misPass ? (pk & kMisOwed) != 0 : (unsigned)lane < take) {
                         unsigned i = poolBase + (unsigned)lane;
                         if (w.order) i = w.order[i];
                         float4 o4, d4;
@@ -222,24 +250,21 @@ __global__ void GX_T4_BOUNDS k_trace4(DScene sc, typename Trace4Src<Q>::type pa,
                             o4 = pa.ray_o[(size_t)path_ * kRS]; d4 = pa.ray_d[(size_t)path_ * kRS];
                             tMax_ = o4.w;
                         } else {
-                            // NEE work items: first all shadow rays, then all MIS rays
-                            const unsigned e = i - (unsigned)w.n_closest;
-                            const bool isShadow = e < (unsigned)w.n_nee;
-                            path_ = w.q_nee[isShadow ? e : e - (unsigned)w.n_nee];
-                            // PathIntegrator launches (w.vis: one record per path, every record array has an entry for it): the record's flags and
-                            // its ray are loaded together -- one memory round trip after the queue read, not two; a record without the ray has
-                            // stale floats there, which are dropped.  Other integrators size the MIS arrays by what they use: flags first.
-                            const bool together = w.vis != nullptr;
-                            if (isShadow) {
+                            // one work item per NEE vertex.  Its set-up loads the shadow record, whose flags say which rays the vertex spawned: bit 0
+                            // the shadow ray (set up here), bit 1 the MIS ray.  The MIS records are read by the lanes that have one only -- the
+                            // direction k_shade sampled from the BSDF hits the sampled light at a few percent of the vertices of a scene with
+                            // one small light -- in the batch that follows (misPass): a second round trip for the batches that hold such a lane,
+                            // none for the others.  (The MIS arrays of integrators without w.vis are sized by what they use: nothing else reads them.)
+                            path_ = w.q_nee[i - (unsigned)w.n_closest];
+                            if (!misPass) {
                                 kind_ = 1; any_ = 1;
                                 o4 = pa.sh_o[(size_t)path_ * kRS]; d4 = pa.sh_d[(size_t)path_ * kRS]; tMax_ = o4.w;
-                                valid = (__float_as_int(d4.w) & 1) != 0;     // else: this vertex spawned no shadow ray
+                                const int nflags = __float_as_int(d4.w);
+                                valid = (nflags & 1) != 0;     // else: this vertex spawned no shadow ray
+                                wantMis = (nflags & 2) != 0;
                             } else {
                                 kind_ = 2;
-                                const int nflags = __float_as_int(pa.sh_d[(size_t)path_ * kRS].w);
-                                valid = (nflags & 2) != 0;
-                                if (together || valid) { o4 = pa.mis_o[(size_t)path_ * kRS]; d4 = pa.mis_d[(size_t)path_ * kRS]; }
-                                else { o4 = make_float4(0, 0, 0, 0); d4 = o4; }
+                                o4 = pa.mis_o[(size_t)path_ * kRS]; d4 = pa.mis_d[(size_t)path_ * kRS];
                                 tMax_ = GX_INF;
                                 // a MIS ray that expects to escape (an infinite light was sampled) asks "is there any hit at all": with tMax = inf
                                 // the closest-hit walk and the any-hit walk visit the same nodes up to the first accepted triangle, and that
@@ -279,9 +304,17 @@ __global__ void GX_T4_BOUNDS k_trace4(DScene sc, typename Trace4Src<Q>::type pa,
                     }
                     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the records are read by other lanes of this wave
                     rqCount = (unsigned)__popcll(vm); rqHead = 0;
-                    poolBase += take; poolCount -= take;
+                    bool advance = true;
+                    if (Q == kT4Render) {
+                        // the vertex items of this batch that also have a MIS ray: their lanes remember it (kMisOwed), and the pool stays on the
+                        // batch; when the queue has run empty those lanes read their queue entries again and set the MIS rays up
+                        if (misPass) pk &= ~kMisOwed;
+                        else if (wantMis) pk |= kMisOwed;
+                        advance = misPass || __ballot(wantMis) == 0;
+                    }
+                    if (advance) { poolBase += take; poolCount -= take; }
                     GX_STAT(7, 1);
-                    GX_STAT(8, take);
+                    GX_STAT(8, misPass ? rqCount : take);
                 }
             }
             if (rqCount > 0) {
@@ -295,7 +328,7 @@ __global__ void GX_T4_BOUNDS k_trace4(DScene sc, typename Trace4Src<Q>::type pa,
         GX_TICK(11);
         const unsigned long long liveMask = __ballot(live);
         if (liveMask == 0) {
-            if (exhausted && rqCount == 0 && poolCount == 0) break;
+            if (exhausted && rqCount == 0 && poolCount == 0) break;   // (poolCount > 0 while a batch still owes its MIS rays)
             continue;   // nothing was ready this round: fetch / set up on the next iteration
         }
 
@@ -487,6 +520,21 @@ __global__ void GX_T4_BOUNDS k_trace4(DScene sc, typename Trace4Src<Q>::type pa,
         atomicAdd(&ctr->retests, (unsigned long long)cntRetests);
         atomicAdd(&ctr->nodes_global, (unsigned long long)cntNodesGlobal);
     }
+#ifdef GX_TAIL_STAMP
+    if (Q == kT4Render && lane == 0) {
+        atomicMax(&g_tail[1], (unsigned long long)wall_clock64());
+        __threadfence();
+        if (atomicAdd(&g_tail[3], 1ull) == (unsigned long long)nWaves - 1ull) {   // the last wave of the launch
+            __threadfence();
+            const unsigned long long tEnd = atomicExch(&g_tail[1], 0ull), tCross = atomicExch(&g_tail[0], ~0ull), tStart = atomicExch(&g_tail[2], ~0ull);
+            atomicExch(&g_tail[3], 0ull);
+            const unsigned long long behind = tEnd > tCross ? tEnd - tCross : 0ull, all = tEnd > tStart ? tEnd - tStart : 0ull;
+            const int o = total >= (1u << 24) ? 8 : 4;
+            g_tail[o] += behind; g_tail[o + 1] += all; g_tail[o + 2] += 1ull; g_tail[o + 3] += total;
+            if (o == 8) { g_tail[4] += behind; g_tail[5] += all; g_tail[6] += 1ull; g_tail[7] += total; }
+        }
+    }
+#endif
 }
 
 }  // namespace gnxr

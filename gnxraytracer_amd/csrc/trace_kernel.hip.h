@@ -5,6 +5,8 @@
 //   kind 2  MIS ray               closest hit  -> mis_o[path].w = 1 if it found what the light sample expects
 //   (PathIntegrator launches pass TraceWork::vis and get both results as bytes of one word per path instead)
 //                                                                                         (Integrator.cpp:193-203)
+// Work items (TraceWork): one per continuation ray, then one per NEE vertex -- the lane that takes a vertex traces its shadow ray and
+// then, when the record's flags say there is one, its MIS ray, without taking a new item in between.
 //
 // CDNA4 structure (this is where the time goes, so it is shaped for wave64 rather than for one ray):
 //   * persistent waves: a wave pulls CHUNK rays at a time from one global cursor (one atomic per CHUNK
@@ -26,7 +28,9 @@ namespace gnxr {
 
 struct TraceWork {
     const int *q_closest; int n_closest;   // path slots (nullptr == identity)
-    const int *q_nee; int n_nee;           // paths with an NEE record: two work items each (shadow ray, MIS ray)
+    const int *q_nee; int n_nee;           // paths with an NEE record: ONE work item each, after the n_closest continuation items (a launch has
+                                           // n_closest + n_nee items).  The item's set-up reads the flags of the shadow record: bit 0 = the vertex
+                                           // has a shadow ray, bit 1 = it has a MIS ray too, which only then costs a read of the MIS records
     const unsigned *order;                 // nullptr, or a permutation of the work items: position in the launch -> work item (a caller-supplied ordering; unused by the library itself)
     unsigned char *vis;                    // nullptr: visibility results go to sh_o[path].w / mis_o[path].w (float 1 / 0).  Otherwise 4 bytes per path:
                                            // [0] shadow ray unoccluded, [1] MIS ray found what the light sample expects (written here), [2] the record's
@@ -52,15 +56,22 @@ GX_DEV int trace_chunk(unsigned total, int chunk_max) {
 // 64-ray batch of each other instead of within a 512-ray chunk (~0.15 ms per launch: nothing for a 265 M-ray launch, 3 - 4 % of the 25 M-ray
 // launches of small sub-passes).  Sizing the request from a fresh read of the cursor was tried first and lost badly (trace +67 %: the extra
 // load of the contended line); this form costs no memory operation beyond the one atomic.
+// Tuning switches of the tail (tools/build_variant.sh + tests/dev_ab.py): items per wave handed out in small chunks / of them in 128-item chunks.
+#ifndef GX_CHUNK_TAIL
+#define GX_CHUNK_TAIL 384
+#endif
+#ifndef GX_CHUNK_MID
+#define GX_CHUNK_MID 256
+#endif
 struct ChunkPlan { unsigned c, big, k1, mid_end, k2; };
 GX_DEV ChunkPlan chunk_plan(unsigned total, unsigned c) {
     const unsigned waves = gridDim.x * (blockDim.x / 64u);
     ChunkPlan p;
     p.c = c;
-    const unsigned tail = waves * 384u;
+    const unsigned tail = waves * (unsigned)GX_CHUNK_TAIL;
     p.big = (c > 128u && total > tail) ? (total - tail) / c * c : 0u;
     p.k1 = p.big / c;
-    const unsigned mid = min(total - p.big, waves * 256u) / 128u * 128u;
+    const unsigned mid = min(total - p.big, waves * (unsigned)GX_CHUNK_MID) / 128u * 128u;
     p.mid_end = p.big + mid;
     p.k2 = mid / 128u;
     return p;
@@ -93,9 +104,6 @@ constexpr int kTraceChunk = 512;   // most rays a wave takes per global atomic (
 #define GX_SPECULATE 1
 #endif
 constexpr bool kSpeculate = GX_SPECULATE != 0;
-#ifndef GX_NEE_INTERLEAVED
-#define GX_NEE_INTERLEAVED 0
-#endif
 constexpr int kRefillMin = GX_REFILL_MIN;   // refill only when at least this many lanes are idle (or none is live)
 constexpr int kTraceLeaveMul = GX_TRACE_LEAVE_MUL, kTraceLeaveDiv = GX_TRACE_LEAVE_DIV;   // leave phase A when searching <= live * MUL / DIV
 
@@ -186,6 +194,15 @@ static __device__ unsigned long long g_trace_stats[24];
 #define GX_STAT(i, v) do {} while (0)
 #endif
 
+#ifdef GX_TAIL_STAMP
+// development builds only (-DGX_TAIL_STAMP, tests/dev_tail_stamp.py): how much of a k_trace4 launch lies behind the moment the cursor hands out
+// the last work item -- the drain.  Per launch: [0] the earliest time (100 MHz wall clock) at which a wave's fetch reached the end of the
+// list, [1] the latest exit of a wave, [2] the start of wave 0, [3] waves that have left; the last wave to leave adds the launch to
+// [4] ticks behind the end of the list, [5] ticks of the launch, [6] launches, [7] work items ([8..11]: the same four over the launches of
+// 2^24 items and more, where a wave takes many chunks), and clears [0..3].
+static __device__ unsigned long long g_tail[12] = {~0ull, 0ull, ~0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
+#endif
+
 // COUNT: count nodes / triangles (profiling).  WIDE: traverse the collapsed 4-wide tree (sc.nodes4) instead of the
 // reference's binary nodes; the counting runs use WIDE = false so that the counts are those of the reference traversal.
 // SPH: the scene has spheres (a separate instantiation keeps their registers out of the triangle-only kernel).
@@ -199,7 +216,7 @@ __global__ void __launch_bounds__(kBlock) k_trace(DScene sc, PathArrays pa, Trac
     stack.spill = (global_int *)(spill + (size_t)blockIdx.x * kBlock + threadIdx.x);
     const int lane = __lane_id();
     trace_work_counts(w);
-    const unsigned total = (unsigned)w.n_closest + 2u * (unsigned)w.n_nee;
+    const unsigned total = (unsigned)w.n_closest + (unsigned)w.n_nee;   // [continuation rays | NEE vertices]
     chunk = trace_chunk(total, chunk);
     const float4 *__restrict__ nodes = sc.nodes;
     const DTri *__restrict__ tris = sc.tris;
@@ -209,6 +226,7 @@ __global__ void __launch_bounds__(kBlock) k_trace(DScene sc, PathArrays pa, Trac
 
     // per-lane ray state
     int item = -1, kind = 0, path = -1;
+    int misPath = -1;   // >= 0: the path whose MIS ray this lane traces once its shadow ray has ended
     V3 ro, rd, invDir;
     RayShear shear;
     RayOctant oct = ray_octant(0, 0, 0);
@@ -224,47 +242,53 @@ __global__ void __launch_bounds__(kBlock) k_trace(DScene sc, PathArrays pa, Trac
         GX_STAT(0, 1);
         // ---------------- refill idle lanes from the wave pool ----------------
         bool need = item < 0;
-        unsigned long long needMask = __ballot(need);
-        if (kRefillMin > 1 && __popcll(needMask) < kRefillMin && needMask != ~0ull) needMask = 0;   // batch the refills
-        if (needMask) {
+        const bool second = need && misPath >= 0;   // the lane's vertex item still has its MIS ray to trace: no new item for it
+        const unsigned long long secondMask = __ballot(second);
+        unsigned long long needMask = __ballot(need && !second);
+        if (kRefillMin > 1 && __popcll(needMask) < kRefillMin && (needMask | secondMask) != ~0ull) needMask = 0;   // batch the refills
+        if (needMask | secondMask) {
             GX_STAT(7, 1);
-            GX_STAT(8, __popcll(needMask));
-            if (poolCount == 0 && !exhausted) {
+            GX_STAT(8, __popcll(needMask | secondMask));
+            if (needMask && poolCount == 0 && !exhausted) {
                 unsigned base = 0;
                 if (lane == 0) base = atomicAdd(cursor, (unsigned)chunk);
                 base = __shfl(base, 0);
                 if (base >= total) exhausted = true;
                 else { poolBase = base; poolCount = min((unsigned)chunk, total - base); }
             }
-            if (poolCount > 0) {
+            {
                 unsigned rank = (unsigned)__popcll(needMask & ((1ull << lane) - 1ull));
                 unsigned take = min(poolCount, (unsigned)__popcll(needMask));
-                if (need && rank < take) {
-                    unsigned i = poolBase + rank;
-                    if (w.order) i = w.order[i];
-                    item = (int)i;
+                if (second || (need && rank < take)) {
                     float4 o4, d4;
-                    if (i < (unsigned)w.n_closest) {
-                        kind = 0;
-                        path = w.q_closest ? w.q_closest[i] : (int)i;
-                        o4 = pa.ray_o[(size_t)path * kRS]; d4 = pa.ray_d[(size_t)path * kRS];
-                        tMax = o4.w;
-                    } else {
-                        // NEE work items: first all shadow rays, then all MIS rays (a wave then holds rays of one kind that
-                        // start from neighbouring vertices and -- the shadow rays -- all head for the same few lights)
-                        unsigned e = i - (unsigned)w.n_closest;
-                        const bool isShadow = GX_NEE_INTERLEAVED ? (e & 1u) == 0 : e < (unsigned)w.n_nee;
-                        path = w.q_nee[GX_NEE_INTERLEAVED ? (e >> 1) : (isShadow ? e : e - (unsigned)w.n_nee)];
-                        int nflags = __float_as_int(pa.sh_d[(size_t)path * kRS].w);
-                        if (isShadow) {
-                            kind = 1;
-                            if (nflags & 1) { o4 = pa.sh_o[(size_t)path * kRS]; d4 = pa.sh_d[(size_t)path * kRS]; tMax = o4.w; }
-                            else item = -1;     // this vertex spawned no shadow ray
+                    bool mis = second;
+                    if (second) { path = misPath; item = 0; }
+                    else {
+                        unsigned i = poolBase + rank;
+                        if (w.order) i = w.order[i];
+                        item = (int)i;
+                        if (i < (unsigned)w.n_closest) {
+                            kind = 0;
+                            path = w.q_closest ? w.q_closest[i] : (int)i;
+                            o4 = pa.ray_o[(size_t)path * kRS]; d4 = pa.ray_d[(size_t)path * kRS];
+                            tMax = o4.w;
                         } else {
-                            kind = 2;
-                            if (nflags & 2) { o4 = pa.mis_o[(size_t)path * kRS]; d4 = pa.mis_d[(size_t)path * kRS]; expect = __float_as_int(o4.w); tMax = GX_INF; }
-                            else item = -1;
+                            // one work item per NEE vertex: the flags of its shadow record say which rays it spawned.  The lane traces the shadow ray
+                            // (bit 0) first and then, without taking a new item, the MIS ray (bit 1)
+                            path = w.q_nee[i - (unsigned)w.n_closest];
+                            const int nflags = __float_as_int(pa.sh_d[(size_t)path * kRS].w);
+                            if (nflags & 1) {
+                                kind = 1;
+                                o4 = pa.sh_o[(size_t)path * kRS]; d4 = pa.sh_d[(size_t)path * kRS]; tMax = o4.w;
+                                if (nflags & 2) misPath = path;
+                            }
+                            else if (nflags & 2) mis = true;
+                            else item = -1;     // this vertex spawned no ray
                         }
+                    }
+                    if (mis) {
+                        kind = 2; misPath = -1;
+                        o4 = pa.mis_o[(size_t)path * kRS]; d4 = pa.mis_d[(size_t)path * kRS]; expect = __float_as_int(o4.w); tMax = GX_INF;
                     }
                     if (item >= 0) {
                         ro = V3(o4.x, o4.y, o4.z); rd = V3(d4.x, d4.y, d4.z);
