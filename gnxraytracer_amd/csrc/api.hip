@@ -35,6 +35,10 @@ GX_WHITTED_INSTANCES(X)
 #define X(M, L, ST, T) extern template GX_VOL_SIGNATURE(M, L, ST, T)
 GX_VOL_INSTANCES(X)
 #undef X
+// compiled in inst_shade_kinds.hip
+#define X(M, L) extern template GX_SHADE_KIND_SIGNATURE(M, L)
+GX_SHADE_KIND_INSTANCES(X)
+#undef X
 // compiled in inst_shade_query.hip
 extern template GX_BSDF_QUERY_SIGNATURE(LM_ALL)
 extern template GX_LIGHT_SAMPLE_QUERY_SIGNATURE(LT_ALL)

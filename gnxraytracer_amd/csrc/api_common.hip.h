@@ -93,6 +93,12 @@ struct Knobs {
     static int volmedia_step_cap() { return env_set("GNXR_VOLMEDIA_STEP_CAP") ? std::max(0, env_int("GNXR_VOLMEDIA_STEP_CAP", 0)) : 64; }
     // GNXR_NO_ESCAPE_QUEUE: set = escaped rays share the shade queues of the material classes (default unset).  Per call (render)
     static bool no_escape_queue() { return env_set("GNXR_NO_ESCAPE_QUEUE"); }
+    // GNXR_NO_MATERIAL_QUEUES: set = all class-1 (glossy) materials share one shade queue and k_shade<LM_GLOSSY>, whatever their kind (default
+    // unset: a queue and a narrow kernel per kind where the four queues allow, plan_shade_queues).  Per call (render)
+    static bool no_material_queues() { return env_set("GNXR_NO_MATERIAL_QUEUES"); }
+    // GNXR_NO_NARROW_SHADE: set = the queues of the kinds launch k_shade<LM_GLOSSY> instead of their narrow kernels (experiment: the split
+    // without the specialisation; default unset).  Per call (render)
+    static bool no_narrow_shade() { return env_set("GNXR_NO_NARROW_SHADE"); }
     // GNXR_HOST_LIGHT_GRID: set = the spatial light table is built on the host (default unset).  Per call (ensure_grid)
     static bool host_light_grid() { return env_set("GNXR_HOST_LIGHT_GRID"); }
     // GNXR_BINARY_BVH: set = the scene renders on the binary tree, never the 4-wide one (default unset).  Per call (scene creation)

@@ -68,6 +68,8 @@ struct RenderPlan {
     int class_mask;                             // bit c: a material of shade class c is present
     bool area_only, area_env_only;              // the light set (selects the shade kernels' LT_* specialisation)
     bool escape_queue;                          // escaped continuation rays get shade queue 3 to themselves
+    int queue_kernel[4];                        // PathIntegrator: the kernel behind each of the four shade queues (SHADE_Q_*, plan_shade_queues)
+    unsigned kind_queue;                        // byte k: the shade queue of the class-1 materials of kind k (k_compact<COMPACT_HITCLASS>)
     bool caller_rays;                           // RaySource: no image
     int n_views;                                // ViewSource: views of the call, else 0
     int local_rows, npix;
@@ -81,6 +83,38 @@ struct RenderPlan {
     int nsamples() const { return p.spp_end - p.spp_begin; }
     int size_passes(size_t slots_held, bool have_mem, size_t free_b);
 };
+
+// What a shade queue of the PathIntegrator launches (RenderRun::shade_stage)
+enum ShadeQueueKernel { SHADE_Q_NONE = 0, SHADE_Q_DIFFUSE, SHADE_Q_GLOSSY, SHADE_Q_CONDUCTOR, SHADE_Q_ROUGH_DIELECTRIC, SHADE_Q_ALL, SHADE_Q_TEX, SHADE_Q_ESCAPE };
+
+// The four shade queues of the binning pass.  Queue c belongs to shade class c (0 diffuse, 1 glossy, 2 any lobe, 3 image textures -- or,
+// without them, escaped rays).  The class-1 materials come in kinds (material_kind): where the queues that the scene leaves free suffice,
+// every kind present gets a queue and the kernel compiled for it -- a wave then holds lanes of one material kind, and the conductor and
+// rough-dielectric kernels carry none of the other's code.  Needed are class 0, the kinds present, class 2 and class 3 / the escape queue
+// if present; beyond four, all class-1 materials share queue 1 and k_shade<LM_GLOSSY>.  Sphere hits get their class from the traversal
+// kernels (pclass), which know no kinds: a scene with spheres keeps the shared queue.
+static void plan_shade_queues(const CompiledScene &cs, RenderPlan *pl) {
+    int *qk = pl->queue_kernel;
+    qk[0] = SHADE_Q_DIFFUSE;
+    qk[1] = (pl->class_mask & 2) ? SHADE_Q_GLOSSY : SHADE_Q_NONE;
+    qk[2] = (pl->class_mask & 4) ? SHADE_Q_ALL : SHADE_Q_NONE;
+    qk[3] = (pl->class_mask & 8) ? SHADE_Q_TEX : (pl->escape_queue ? SHADE_Q_ESCAPE : SHADE_Q_NONE);
+    pl->kind_queue = 0x01010101u;
+    int kinds = 0, n_kinds = 0;
+    for (const DMaterial &m : cs.materials) if (m.shade_class == 1) kinds |= 1 << material_kind(m);
+    for (int k = 0; k < MATERIAL_KINDS; ++k) n_kinds += (kinds >> k) & 1;
+    const int n_free = 1 + (qk[2] == SHADE_Q_NONE ? 1 : 0) + (qk[3] == SHADE_Q_NONE ? 1 : 0);
+    if (!pl->path_int() || cs.n_spheres > 0 || (kinds & ~1) == 0 || n_kinds > n_free || Knobs::no_material_queues()) return;
+    const bool narrow = !Knobs::no_narrow_shade();
+    pl->kind_queue = 0;
+    for (int k = 0, q = 1; k < MATERIAL_KINDS; ++k) {
+        if (!((kinds >> k) & 1)) { pl->kind_queue |= 1u << (8 * k); continue; }   // (no triangle has this kind)
+        while (q < 3 && qk[q] != SHADE_Q_NONE && !(q == 1 && qk[1] == SHADE_Q_GLOSSY)) ++q;   // (n_kinds <= n_free: a free queue exists)
+        qk[q] = !narrow ? SHADE_Q_GLOSSY : (k == MATERIAL_KIND_CONDUCTOR ? SHADE_Q_CONDUCTOR : (k == MATERIAL_KIND_ROUGH_DIELECTRIC ? SHADE_Q_ROUGH_DIELECTRIC : SHADE_Q_GLOSSY));
+        pl->kind_queue |= (unsigned)q << (8 * k);
+        ++q;
+    }
+}
 
 // The plan rules that tests/test_full_scale.py restates
 static const long long kSubPassPaths = 64ll << 20;                          // PathIntegrator: paths of an automatic sub-pass
@@ -146,6 +180,7 @@ static int plan_render(const CompiledScene &cs, const gnxr_render_params *pin, c
     }
     // escaped continuation rays of a scene with infinite lights get shade queue 3 to themselves when no image-textured material claims it
     pl.escape_queue = pl.path_int() && !pl.textured_scene && !cs.infinite_lights.empty() && !Knobs::no_escape_queue();
+    plan_shade_queues(cs, &pl);
     pl.caller_rays = src != nullptr;
     pl.n_views = views ? views->n_views : 0;
     pl.local_rows = count_local_rows(&p);
@@ -340,7 +375,7 @@ struct RenderRun {
 
     void launch_trace(TraceWork w, int n_sh, int n_mis, bool count_rays = true);
     void compact(int mode, const int *qin, int nin, const unsigned char *keys, int nout, int nscatter, unsigned int *totals, int *o0, int *o1, int *o2, int *o3 = nullptr, int split = 0,
-                 const unsigned *n_dev = nullptr);
+                 const unsigned *n_dev = nullptr, unsigned kind_queue = 0x01010101u);   // kind_queue: HITCLASS only (RenderPlan::kind_queue)
     int shade_stage(const int *q_in, int n, int *q_out, const unsigned *n_dev);
     void raygen(const PathArrays &at, long long u0, int kk, unsigned char *medium_keys);
     void resolve(const PathArrays &at, long long u0, int kk);
@@ -389,7 +424,7 @@ void RenderRun::launch_trace(TraceWork w, int n_sh, int n_mis, bool count_rays) 
 // stream compaction (compact_kernel.hip.h): one launch, one pass over the queue
 // (n_dev: the item count lives on the device; `nin` then bounds it and sizes the launch)
 void RenderRun::compact(int mode, const int *qin, int nin, const unsigned char *keys, int nout, int nscatter, unsigned int *totals, int *o0, int *o1, int *o2, int *o3, int split,
-                        const unsigned *n_dev) {
+                        const unsigned *n_dev, unsigned kind_queue) {
     const int tiles = (nin + kCompactTile - 1) / kCompactTile;
     const int g = std::max(1, std::min(tiles, g_num_cus * kCompactBlocksPerCu));
     // every compaction of the handle has a sequence number of its own; when the 30 bits of a descriptor's tag run out, start over on cleared descriptors
@@ -403,7 +438,7 @@ void RenderRun::compact(int mode, const int *qin, int nin, const unsigned char *
     const bool hitclass = mode == COMPACT_HITCLASS;
     const int *hit = hitclass ? (const int *)st.hit.p : nullptr;
     const unsigned char *cls = hitclass ? (const unsigned char *)s->tri_class.p : nullptr;
-#define GX_COMPACT(M, N, NS) hipLaunchKernelGGL((k_compact<M, N, NS>), dim3(g), dim3(kCompactBlock), 0, stream, qin, nin, keys, cs, totals, o0, o1, o2, o3, hit, cls, split, n_dev, dctr)
+#define GX_COMPACT(M, N, NS) hipLaunchKernelGGL((k_compact<M, N, NS>), dim3(g), dim3(kCompactBlock), 0, stream, qin, nin, keys, cs, totals, o0, o1, o2, o3, hit, cls, kind_queue, split, n_dev, dctr)
     if (mode == COMPACT_FLAGS) {
         // a fifth count: the paths that continue AND live in the lower half of the state arrays (slot < split)
         if (nout == 5) { if (nscatter == 3) GX_COMPACT(COMPACT_FLAGS, 5, 3); else GX_COMPACT(COMPACT_FLAGS, 5, 2); }
@@ -426,11 +461,10 @@ static int compact_stalled(const Counters &c) {
 // Returns the status of the fork / join of the class streams; the launches themselves are checked once per loop turn (run_path_loop).
 int RenderRun::shade_stage(const int *q_in, int n, int *q_out, const unsigned *n_dev) {
     if (timing) timer.begin(2, stream);
-    const int class_mask = pl.class_mask;
-    const bool escape_queue = pl.escape_queue;
-    // bin the paths by the shade specialisation of the material they hit (pclass written by k_trace)
-    const int n_classes = ((class_mask & 8) || escape_queue) ? 4 : 3;   // image-textured materials -- or, without them, escaped rays -- have a shade queue of their own
-    compact(COMPACT_HITCLASS, q_in, n, st.pclass.p, n_classes, n_classes, &dctr->q_class[0], st.queue_c0.p, st.queue_c1.p, st.queue_c2.p, st.queue_c3.p, 0, n_dev);
+    const int *qk = pl.queue_kernel;
+    // bin the paths by the shade queue of the material they hit (plan_shade_queues; pclass written by k_trace for misses and sphere hits)
+    const int n_classes = qk[3] != SHADE_Q_NONE ? 4 : 3;   // image-textured materials, escaped rays or a material kind have shade queue 3
+    compact(COMPACT_HITCLASS, q_in, n, st.pclass.p, n_classes, n_classes, &dctr->q_class[0], st.queue_c0.p, st.queue_c1.p, st.queue_c2.p, st.queue_c3.p, 0, n_dev, pl.kind_queue);
     int *qc[4] = {st.queue_c0.p, st.queue_c1.p, st.queue_c2.p, st.queue_c3.p};
     // 32 blocks per CU: of a k_shade grid only 2 - 3 blocks per CU are resident at a time (168 - 256 registers), and many short blocks
     // balance the end of the launch better than few long ones (8 / 16 / 32 / 64 / 128 / 1024 per CU: shade 171.4 / 167.1 / 165.7 / 165.4 /
@@ -447,10 +481,12 @@ int RenderRun::shade_stage(const int *q_in, int n, int *q_out, const unsigned *n
     const size_t slds = (sdims > 0 ? ((((size_t)snperm * 2 + 15) & ~(size_t)15) + (size_t)sdims * 32) : 0) + (size_t)lmats * sizeof(DMaterial) + (size_t)llights * sizeof(DLight);
     // the class kernels work on disjoint paths: with three or more of them (cfg 4: diffuse, glossy, Disney, escaped rays) classes 1 - 3 run on
     // two auxiliary streams beside class 0, so that the blocks of one fill the thinning end of another (fork / join with events): cfg 4 shade
-    // -4 %; with two kernels of similar size (cfg 3) the same costs 1.5 %, so they stay in line (profiles/r03_ab_shade_streams_*.log;
-    // GNXR_SHADE_STREAMS = 0 / 1 forces either)
+    // -4 %; with two kernels of similar size (cfg 3 with one glossy queue) the same costs 1.5 %, so they stay in line
+    // (profiles/r03_ab_shade_streams_*.log; GNXR_SHADE_STREAMS = 0 / 1 forces either).  cfg 3 with a queue per material kind has three: forked
+    // 5170 against 5151 Mrays/s in line (profiles/README.md, "One shade queue per kind of glossy material"), so the rule covers it as it stands
     const int shade_streams = Knobs::shade_streams();
-    const int n_class_kernels = 1 + ((class_mask & 2) ? 1 : 0) + ((class_mask & 4) ? 1 : 0) + (((class_mask & 8) || escape_queue) ? 1 : 0);
+    int n_class_kernels = 0;
+    for (int q = 0; q < 4; ++q) n_class_kernels += qk[q] != SHADE_Q_NONE ? 1 : 0;
     const bool fork = (shade_streams < 0 ? n_class_kernels >= 3 : (shade_streams != 0 && n_class_kernels >= 2)) && s->aux_stream[0] && s->aux_stream[1];
     hipStream_t cst[4] = {stream, stream, stream, stream};
     if (fork) {
@@ -463,39 +499,44 @@ int RenderRun::shade_stage(const int *q_in, int n, int *q_out, const unsigned *n
 #define GX_SHADE_K(K, C) hipLaunchKernelGGL(K, g, b, slds, cst[C], sc, r, pa, (const int *)qc[C], (const unsigned int *)&dctr->q_class[C], sdims, snperm, lmats, llights)
 #define GX_SHADE(LMV, LTV, C) do { if (spheres) GX_SHADE_K((k_shade<LMV, LTV, true>), C); else GX_SHADE_K((k_shade<LMV, LTV, false>), C); } while (0)
 #define GX_SHADE_TEX(LTV) do { if (spheres) GX_SHADE_K((k_shade<LM_ALL, LTV, true, true>), 3); else GX_SHADE_K((k_shade<LM_ALL, LTV, false, true>), 3); } while (0)
-    if (area_only) {
-        GX_SHADE(LM_DIFFUSE, LT_AREA, 0);
-        if (class_mask & 2) GX_SHADE(LM_GLOSSY, LT_AREA, 1);
-        if (class_mask & 4) GX_SHADE(LM_ALL, LT_AREA, 2);
-        if (class_mask & 8) GX_SHADE_TEX(LT_AREA);
-    } else if (area_env_only && !spheres && !(class_mask & 8)) {
-        // BASELINE config 4's light set (area lights + one InfiniteAreaLight): without the delta-light and sky-box code
-#define GX_SHADE_AE(LMV, C) GX_SHADE_K((k_shade<LMV, LT_AREA | LT_ENV, false>), C)
-        GX_SHADE_AE(LM_DIFFUSE, 0);
-        if (class_mask & 2) GX_SHADE_AE(LM_GLOSSY, 1);
-        if (class_mask & 4) GX_SHADE_AE(LM_ALL, 2);
-#undef GX_SHADE_AE
-    } else {
-        GX_SHADE(LM_DIFFUSE, LT_ALL, 0);
-        if (class_mask & 2) GX_SHADE(LM_GLOSSY, LT_ALL, 1);
-        if (class_mask & 4) GX_SHADE(LM_ALL, LT_ALL, 2);
-        if (class_mask & 8) GX_SHADE_TEX(LT_ALL);
+    // BASELINE config 4's light set (area lights + one InfiniteAreaLight) has kernels without the delta-light and sky-box code
+    const int light_set = area_only ? 0 : ((area_env_only && !spheres && !(pl.class_mask & 8)) ? 1 : 2);
+#define GX_SHADE_LM(LMV, C) do { \
+        if (light_set == 0) GX_SHADE(LMV, LT_AREA, C); \
+        else if (light_set == 1) GX_SHADE_K((k_shade<LMV, LT_AREA | LT_ENV, false>), C); \
+        else GX_SHADE(LMV, LT_ALL, C); } while (0)
+    // (the narrow kernels exist without spheres only: plan_shade_queues gives a scene with spheres no queue per kind)
+#define GX_SHADE_NARROW(LMV, C) do { \
+        if (light_set == 0) GX_SHADE_K((k_shade<LMV, LT_AREA, false>), C); \
+        else if (light_set == 1) GX_SHADE_K((k_shade<LMV, LT_AREA | LT_ENV, false>), C); \
+        else GX_SHADE_K((k_shade<LMV, LT_ALL, false>), C); } while (0)
+    for (int q = 0; q < 4; ++q) {
+        switch (qk[q]) {
+        case SHADE_Q_DIFFUSE: GX_SHADE_LM(LM_DIFFUSE, q); break;
+        case SHADE_Q_GLOSSY: GX_SHADE_LM(LM_GLOSSY, q); break;
+        case SHADE_Q_CONDUCTOR: GX_SHADE_NARROW(LM_CONDUCTOR, q); break;
+        case SHADE_Q_ROUGH_DIELECTRIC: GX_SHADE_NARROW(LM_ROUGH_DIELECTRIC, q); break;
+        case SHADE_Q_ALL: GX_SHADE_LM(LM_ALL, q); break;
+        case SHADE_Q_TEX: if (light_set == 0) GX_SHADE_TEX(LT_AREA); else GX_SHADE_TEX(LT_ALL); break;
+        case SHADE_Q_ESCAPE:
+            if (area_env_only) hipLaunchKernelGGL((k_shade_escape<LT_AREA | LT_ENV>), g, b, 0, cst[q], sc, pa, (const int *)qc[q], (const unsigned int *)&dctr->q_class[q]);
+            else hipLaunchKernelGGL((k_shade_escape<LT_ALL>), g, b, 0, cst[q], sc, pa, (const int *)qc[q], (const unsigned int *)&dctr->q_class[q]);
+            break;
+        default: continue;
+        }
+        ++launches;
     }
+#undef GX_SHADE_NARROW
+#undef GX_SHADE_LM
 #undef GX_SHADE_TEX
 #undef GX_SHADE
 #undef GX_SHADE_K
-    if (escape_queue) {
-        if (area_env_only) hipLaunchKernelGGL((k_shade_escape<LT_AREA | LT_ENV>), g, b, 0, cst[3], sc, pa, (const int *)qc[3], (const unsigned int *)&dctr->q_class[3]);
-        else hipLaunchKernelGGL((k_shade_escape<LT_ALL>), g, b, 0, cst[3], sc, pa, (const int *)qc[3], (const unsigned int *)&dctr->q_class[3]);
-        ++launches;
-    }
     if (fork) {
         HIP_TRY(hipEventRecord(s->ev_join[0], s->aux_stream[0]));
         HIP_TRY(hipEventRecord(s->ev_join[1], s->aux_stream[1]));
         HIP_TRY(hipStreamWaitEvent(stream, s->ev_join[0], 0));
         HIP_TRY(hipStreamWaitEvent(stream, s->ev_join[1], 0));
     }
-    launches += 1 + ((class_mask & 2) ? 1 : 0) + ((class_mask & 4) ? 1 : 0) + ((class_mask & 8) ? 1 : 0);
     // next-vertex queue + NEE queue from the per-path flags; totals also count shadow and MIS rays
     compact(COMPACT_FLAGS, q_in, n, st.pflags.p, 4, 2, &dctr->q_next, q_out, st.queue_nee.p, nullptr, nullptr, 0, n_dev);
     if (timing) timer.end(stream);

@@ -11,7 +11,10 @@
 //   mode CLASS    : predicate o = (keys[path] == o)       (VolPath: the state of the path)
 //   mode HITCLASS : as CLASS, with the key of a path whose ray hit a triangle looked up here (tri_class[hit[path]]); keys[path] (pclass) is
 //                   written by the traversal kernels for misses and sphere hits only, so that their retire step has no dependent gather.
-//                   Nothing else reads pclass, so the class of a triangle hit is no longer written back to it.
+//                   Nothing else reads pclass, so the class of a triangle hit is no longer written back to it.  The byte holds the shade
+//                   class and, above it, the kind of a class-1 material (gnxr_device_types.h MATERIAL_KIND_*); the render plan's table
+//                   `kind_queue` (one byte per kind) names the shade queue of each kind: o = class == 1 ? kind_queue[kind] : class.
+//                   (pclass holds plain classes: sphere hits go to queue 1, and the plan gives a scene with spheres no other glossy queue.)
 //
 // What a block does per tile (kCompactTile consecutive queue entries, kCompactChunks per thread;
 // a wave holds kCompactSpan consecutive entries, 64 per chunk, so that every load instruction is coalesced):
@@ -55,6 +58,7 @@
 // tools/kernel_regs.py report of this build -- re-run it after a compiler change.
 #pragma once
 #include "device_math.h"
+#include "gnxr_device_types.h"
 
 namespace gnxr {
 
@@ -63,6 +67,11 @@ enum CompactMode { COMPACT_FLAGS = 0, COMPACT_CLASS = 1, COMPACT_HITCLASS = 2 };
 
 template <int MODE>
 GX_DEV bool compact_pred(unsigned key, int o) { return MODE == COMPACT_FLAGS ? ((key >> o) & 1u) != 0 : key == (unsigned)o; }
+// HITCLASS: the shade queue of a key byte (shade class | kind << kClassKeyKindShift); kind_queue: byte k = the queue of class-1 kind k
+GX_DEV unsigned compact_class_queue(unsigned key, unsigned kind_queue) {
+    const unsigned cls = key & (unsigned)kClassKeyClassMask;
+    return cls == 1u ? (kind_queue >> ((key >> kClassKeyKindShift) * 8u)) & 0xffu : cls;
+}
 
 constexpr int kCompactChunks = 32;   // entries per thread: one bit each in a 32-bit predicate mask
 constexpr int kCompactTile = kCompactBlock * kCompactChunks;
@@ -92,7 +101,7 @@ struct CompactScratch {
 template <int MODE, int NOUT, int NSCATTER>
 __global__ void __launch_bounds__(kCompactBlock) k_compact(const int *__restrict__ q_in, int n, const unsigned char *__restrict__ keys, CompactScratch cs,
                                                            unsigned int *totals, int *out0, int *out1, int *out2, int *out3, const int *__restrict__ hit,
-                                                           const unsigned char *__restrict__ tri_class, int split, const unsigned *n_dev, Counters *ctr) {
+                                                           const unsigned char *__restrict__ tri_class, unsigned kind_queue, int split, const unsigned *n_dev, Counters *ctr) {
     __shared__ unsigned int wtot[NOUT][kCompactWaves];   // counts per wave of the tile
     __shared__ unsigned int s_excl[NOUT];
     __shared__ unsigned int s_ticket;
@@ -135,7 +144,7 @@ __global__ void __launch_bounds__(kCompactBlock) k_compact(const int *__restrict
 #pragma unroll
                 for (int j = 0; j < kCompactGather; ++j) h[j] = path[c0 + j] >= 0 ? hit[path[c0 + j]] : -1;
 #pragma unroll
-                for (int j = 0; j < kCompactGather; ++j) key[j] = path[c0 + j] < 0 ? 0xffu : (h[j] >= 0 ? (unsigned)tri_class[h[j]] : (unsigned)keys[path[c0 + j]]);
+                for (int j = 0; j < kCompactGather; ++j) key[j] = path[c0 + j] < 0 ? 0xffu : (h[j] >= 0 ? compact_class_queue((unsigned)tri_class[h[j]], kind_queue) : (unsigned)keys[path[c0 + j]]);
             } else {
 #pragma unroll
                 for (int j = 0; j < kCompactGather; ++j) key[j] = path[c0 + j] >= 0 ? (unsigned)keys[path[c0 + j]] : 0xffu;

@@ -88,6 +88,15 @@ constexpr uint32_t LM_DIFFUSE = lobe_bit(LOBE_LAMBERT) | lobe_bit(LOBE_OREN);
 constexpr uint32_t LM_GLOSSY = LM_DIFFUSE | lobe_bit(LOBE_SPEC_REFL) | lobe_bit(LOBE_SPEC_TRANS) | lobe_bit(LOBE_FRESNEL_SPEC) | lobe_bit(LOBE_MICRO_REFL) |
                                lobe_bit(LOBE_MICRO_TRANS) | fresnel_bit(FRESNEL_NOOP) | fresnel_bit(FRESNEL_DIELECTRIC) | fresnel_bit(FRESNEL_CONDUCTOR);
 constexpr uint32_t LM_ALL = 0xffffffffu;
+// The two kinds of glossy (class-1) material with a shade queue and a kernel of their own (material_kind, scene_compile.cpp; the plan:
+// plan_shade_queues): Metal -- ONE microfacet reflection lobe with the conductor Fresnel term -- and rough Glass -- microfacet reflection and
+// transmission with the dielectric term.  Neither has a lobe with Disney's G term.
+constexpr uint32_t LM_CONDUCTOR = lobe_bit(LOBE_MICRO_REFL) | fresnel_bit(FRESNEL_CONDUCTOR);
+constexpr uint32_t LM_ROUGH_DIELECTRIC = lobe_bit(LOBE_MICRO_REFL) | lobe_bit(LOBE_MICRO_TRANS) | fresnel_bit(FRESNEL_DIELECTRIC);
+// masks whose only lobes are the microfacet pair: the BxDF defaults (cosine-weighted Sample_f / Pdf) are never reached
+constexpr bool lm_micro_only(uint32_t lm) { return (lm & 0xffffu & ~(lobe_bit(LOBE_MICRO_REFL) | lobe_bit(LOBE_MICRO_TRANS))) == 0; }
+// which of the pair a lobe is: known at compile time where the mask has no transmission lobe
+#define GX_MICRO_IS_REFL(l) (!GX_HAS_LOBE(LOBE_MICRO_TRANS) || (l).kind == LOBE_MICRO_REFL)
 
 template <uint32_t LM>
 GX_DEV Spec fresnel_eval(const DLobe &l, float cosI) {
@@ -191,7 +200,7 @@ GX_DEV Spec lobe_f(const DLobe &l, V3 wo, V3 wi) {
     // half vector and the Fresnel argument are lobe-specific, D, G and F are evaluated once for whichever lobe a lane holds
     // (rough glass puts both lobes into one wave).
     case LOBE_MICRO_REFL: case LOBE_MICRO_TRANS: if (GX_HAS_LOBE(LOBE_MICRO_REFL) || GX_HAS_LOBE(LOBE_MICRO_TRANS)) {
-        const bool refl = l.kind == LOBE_MICRO_REFL;
+        const bool refl = GX_MICRO_IS_REFL(l);
         float cosThetaO, cosThetaI, eta = 1, cosArg;
         V3 wh;
         if (refl) {
@@ -276,7 +285,7 @@ GX_DEV float lobe_pdf(const DLobe &l, V3 wo, V3 wi) {
     case LOBE_LAMBERT_TRANS: if (GX_HAS_LOBE(LOBE_LAMBERT_TRANS)) return !same_hemisphere(wo, wi) ? abs_cos_theta(wi) * GX_INV_PI : 0.f; break;
     // MicrofacetReflection::Pdf (Reflection.cpp:216-221) / MicrofacetTransmission::Pdf (:262-276): one distribution->Pdf call
     case LOBE_MICRO_REFL: case LOBE_MICRO_TRANS: if (GX_HAS_LOBE(LOBE_MICRO_REFL) || GX_HAS_LOBE(LOBE_MICRO_TRANS)) {
-        const bool refl = l.kind == LOBE_MICRO_REFL;
+        const bool refl = GX_MICRO_IS_REFL(l);
         V3 wh;
         float scale;
         if (refl) {
@@ -307,6 +316,7 @@ GX_DEV float lobe_pdf(const DLobe &l, V3 wo, V3 wi) {
     break;
     default: break;
     }
+    if (lm_micro_only(LM)) return 0.f;
     return same_hemisphere(wo, wi) ? abs_cos_theta(wi) * GX_INV_PI : 0.f;  // BxDF::Pdf
 }
 
@@ -358,7 +368,7 @@ GX_DEV Spec lobe_sample(const DLobe &l, V3 wo, V3 *wi, float u0, float u1, float
         if (wo.z == 0) return Spec(0.f);
         V3 wh = tr_sample_wh(l.alphax, l.alphay, wo, u0, u1);
         if (dot(wo, wh) < 0) return Spec(0.f);
-        if (l.kind == LOBE_MICRO_REFL) {
+        if (GX_MICRO_IS_REFL(l)) {
             *wi = reflect(wo, wh);
             if (!same_hemisphere(wo, *wi)) return Spec(0.f);
             *pdf = tr_pdf(l.alphax, l.alphay, wo, wh) / (4 * dot(wo, wh));
@@ -396,6 +406,7 @@ GX_DEV Spec lobe_sample(const DLobe &l, V3 wo, V3 *wi, float u0, float u1, float
     break;
     default: break;
     }
+    if (lm_micro_only(LM)) return Spec(0.f);
     // BxDF::Sample_f, Reflection.cpp:394-401
     *wi = cosine_sample_hemisphere(u0, u1);
     if (wo.z < 0) wi->z *= -1;
@@ -421,8 +432,9 @@ struct Bsdf {
     // The diffuse class (LM_DIFFUSE) holds materials of at most ONE lobe, a Lambert or Oren-Nayar reflection (compile_material): lobe
     // counting, choice and the sums over "the other lobes" of Reflection.cpp:440-563 reduce to that lobe -- same arithmetic, without the
     // loops over mat->lobes[i].type (each a dependent table read).
-    static constexpr bool kSingle = (LM == LM_DIFFUSE);
-    static constexpr int kSingleType = BSDF_REFLECTION | BSDF_DIFFUSE;
+    // The conductor kind (LM_CONDUCTOR) holds materials of EXACTLY one lobe, a glossy reflection: the same reduction.
+    static constexpr bool kSingle = (LM == LM_DIFFUSE || LM == LM_CONDUCTOR);
+    static constexpr int kSingleType = BSDF_REFLECTION | (LM == LM_CONDUCTOR ? BSDF_GLOSSY : BSDF_DIFFUSE);
     GX_DEV Spec f(V3 woW, V3 wiW, int flags) const {
         V3 wi = to_local(wiW), wo = to_local(woW);
         if (wo.z == 0) return Spec(0.f);

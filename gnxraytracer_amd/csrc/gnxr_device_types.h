@@ -82,6 +82,11 @@ struct DMaterial {
     int32_t has_attr;        // copy of a material for triangles with uvs / shading normals of their own (DTexTables::tri_uv, tri_n); shade class 3
     DLobe lobes[8];
 };
+// The kind of a class-1 material (material_kind, scene_compile.cpp): which narrow glossy kernel covers it.  The per-triangle key byte that
+// the binning pass gathers (tri_class[]) is shade class | kind << kClassKeyKindShift; the render plan maps kinds to shade queues.
+enum : int32_t { MATERIAL_KIND_OTHER = 0, MATERIAL_KIND_CONDUCTOR = 1, MATERIAL_KIND_ROUGH_DIELECTRIC = 2, MATERIAL_KINDS = 4 };
+constexpr int kClassKeyKindShift = 2;
+constexpr int kClassKeyClassMask = 3;
 
 // ---- image textures: ImageTexture + UVMapping2D + MIPMap (textures/ImageTexture.h, core/Texture.cpp:163-175, core/MIPMap.h) ----
 struct DTexture {

@@ -51,7 +51,7 @@ struct CompiledScene {
     std::vector<DTri> tris;              // leaf order
     std::vector<float> leaf_boxes;       // 8 floats per leaf-order triangle, valid at the first triangle of each leaf: the leaf's LinearBVHNode bounds (lo.xyz hi.x | hi.yz 0 0)
     int leaf1_from_verts = 0;            // every one-triangle leaf's bounds == min / max of its triangle's vertices (checked in compile_scene)
-    std::vector<uint8_t> tri_class;      // per leaf-order triangle: DMaterial::shade_class of its material (0 for null materials): the class the binning pass gives a path that hit it
+    std::vector<uint8_t> tri_class;      // per leaf-order triangle: the key the binning pass gives a path that hit it: DMaterial::shade_class of its material (0 for null materials) | material_kind() << kClassKeyKindShift
     std::vector<int32_t> leaf_of_prim;   // authoring index -> leaf index
     int bvh_max_depth = 0;
     Box3 world_bound;
@@ -77,7 +77,7 @@ struct CompiledScene {
     std::vector<int32_t> tri_material;           // gnxr_scene_desc::tri_material
     std::vector<uint8_t> tri_own_attr;           // per authored triangle: 1 = uvs other than the defaults, normals or tangents of its own
     std::vector<int32_t> sphere_material;        // gnxr_sphere::material (DSphere::material is -1 for a GNXR_MAT_NONE material)
-    std::vector<int32_t> mat_map;                // 4 per authored material: internal index (-1: no BSDF), its attribute copy (-1: none), shade class, 0
+    std::vector<int32_t> mat_map;                // 4 per authored material: internal index (-1: no BSDF), its attribute copy (-1: none), shade class, kind (material_kind)
     std::vector<DLight> lights;
     std::vector<int32_t> infinite_lights;
     // sampler
@@ -128,7 +128,9 @@ struct MaterialTables {
 bool compile_materials(const gnxr_material *mats, int n_materials, int n_textures, const std::vector<int32_t> &sphere_material, const int32_t *tri_material,
                        const uint8_t *tri_own_attr, int n_triangles, const int32_t *visit, MaterialTables *mt);
 // one triangle's DTri::material and tri_class byte from mat_map (k_material_tris, material_kernel.hip.h, is the device's form)
-void triangle_material(const int32_t *mat_map, int32_t authored, uint8_t own_attr, int32_t *material, uint8_t *shade_class);
+void triangle_material(const int32_t *mat_map, int32_t authored, uint8_t own_attr, int32_t *material, uint8_t *class_key);
+// MATERIAL_KIND_* of a compiled material: non-zero for the class-1 materials that a narrow glossy kernel covers (conductor, rough dielectric)
+int material_kind(const DMaterial &m);
 // after a refit: the root box of the binary BVH (lo.xyz hi.xyz) -> world_bound (grown by the spheres), the environment light's bounding
 // sphere and the distant lights' radius, computed as compile_scene computes them
 void refit_world_bound(CompiledScene *cs, const float root6[6]);

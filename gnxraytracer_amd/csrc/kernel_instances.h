@@ -1,5 +1,5 @@
-// kernel_instances.h -- the instantiations of the two largest kernel templates, k_whitted_step and k_vol_step, are compiled in
-// translation units of their own (inst_whitted.hip, inst_whitted_tex.hip, inst_vol.hip) so that the device compilations run side by side;
+// kernel_instances.h -- the instantiations of the two largest kernel templates, k_whitted_step and k_vol_step, and the k_shade kernels of the
+// glossy material kinds are compiled in translation units of their own (inst_whitted.hip, inst_whitted_tex.hip, inst_vol.hip, inst_shade_kinds.hip) so that the device compilations run side by side;
 // api.hip sees them as `extern template`.  X(...) receives the template arguments of one instantiation.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -18,6 +18,12 @@
 #define GX_VS_LT(X, M, T) GX_VS_ST(X, M, LT_AREA, T) GX_VS_ST(X, M, LT_ALL, T)
 #define GX_VOL_INSTANCES(X) GX_VS_LT(X, LM_DIFFUSE, false) GX_VS_LT(X, LM_GLOSSY, false) GX_VS_LT(X, LM_ALL, false) GX_VS_LT(X, LM_ALL, true)
 
+// k_shade for the two kinds of glossy material, for the light sets shade_stage launches without spheres
+#define GX_SK_LT(X, M) X(M, LT_AREA) X(M, LT_AREA | LT_ENV) X(M, LT_ALL)
+#define GX_SHADE_KIND_INSTANCES(X) GX_SK_LT(X, LM_CONDUCTOR) GX_SK_LT(X, LM_ROUGH_DIELECTRIC)
+
+#define GX_SHADE_KIND_SIGNATURE(M, L) \
+    __global__ void gnxr::k_shade<M, L, false, false>(gnxr::DScene, gnxr::DRender, gnxr::PathArrays, const int *, const unsigned int *, int, int, int, int);
 #define GX_WHITTED_SIGNATURE(M, L, S, T) \
     __global__ void gnxr::k_whitted_step<M, L, S, T>(gnxr::DScene, gnxr::DRender, gnxr::PathArrays, gnxr::WhittedArrays, const int *, int, unsigned long long *);
 #define GX_VOL_SIGNATURE(M, L, ST, T) \

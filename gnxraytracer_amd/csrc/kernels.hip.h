@@ -100,7 +100,7 @@ struct DScene {
     const float4 *nodes4;   // DNode4[] as 8 float4 each
     int root4;
     const DTri *tris;
-    const unsigned char *tri_class;   // shade class of each leaf-order triangle's material (CompiledScene::tri_class)
+    const unsigned char *tri_class;   // key byte of each leaf-order triangle: shade class | kind << kClassKeyKindShift of its material (CompiledScene::tri_class)
     const float4 *leaf_box;   // 2 float4 per leaf-order triangle: bounds of the leaf that starts there (CompiledScene::leaf_boxes)
     int leaf1_from_verts;     // every one-triangle leaf's bounds equal the min / max of its vertices (checked by the scene compiler): no table read for them
     const DSphere *spheres;   // tested before the BVH; hit code -2 - index
@@ -445,7 +445,9 @@ static __device__ unsigned long long g_shade_stats[16];
 #ifndef GX_SHADE_W_TEX
 #define GX_SHADE_W_TEX 3
 #endif
-template <uint32_t LM> constexpr int shade_min_waves() { return LM == LM_DIFFUSE ? GX_SHADE_W_DIFFUSE : (LM == LM_GLOSSY ? GX_SHADE_W_GLOSSY : GX_SHADE_W_ALL); }
+template <uint32_t LM> constexpr int shade_min_waves() {   // (the kinds of the glossy class -- LM_CONDUCTOR, LM_ROUGH_DIELECTRIC -- as the class)
+    return LM == LM_DIFFUSE ? GX_SHADE_W_DIFFUSE : ((LM == LM_GLOSSY || LM == LM_CONDUCTOR || LM == LM_ROUGH_DIELECTRIC) ? GX_SHADE_W_GLOSSY : GX_SHADE_W_ALL);
+}
 template <uint32_t LM, int LT, bool SPH, bool TEX = false>
 __global__ void __launch_bounds__(kBlock, (TEX ? GX_SHADE_W_TEX : shade_min_waves<LM>())) k_shade(DScene sc, DRender r, PathArrays pa, const int *__restrict__ queue, const unsigned int *n_dev, int lds_dims, int lds_nperm, int lds_mats, int lds_lights) {
     extern __shared__ int shade_smem[];   // the Halton tables of dimensions [0, lds_dims): device_sampler.h LdsSampler | the scene's DMaterial[] | DLight[]

@@ -2,8 +2,9 @@
 // material tables, which is held in LEAF order (DTri::material, tri_class[]), rewritten from tables held in AUTHORING order.  After
 // gnxr_scene_rebuild_bvh the leaf order exists only on the device, so the way from one order to the other is DTri::prim, read here.
 //
-//   k_material_tris     every leaf-order triangle: material word and class byte from its authored material and its own-attributes byte
-//   k_material_gather   the inverse (test hook): per authored triangle the authored material it shows and its class byte
+//   k_material_tris     every leaf-order triangle: material word and key byte (shade class | kind << kClassKeyKindShift) from its authored
+//                       material and its own-attributes byte
+//   k_material_gather   the inverse (test hook): per authored triangle the authored material it shows and its shade class
 //
 // The arithmetic is triangle_material's (scene_compile.cpp), which gnxr_scene_create applies on the host.
 #pragma once
@@ -15,7 +16,7 @@
 namespace gnxr {
 namespace matedit {
 
-// tri_material / own_attr: per authored triangle; mat_map: per authored material (internal index or -1, attribute copy or -1, shade class, 0).
+// tri_material / own_attr: per authored triangle; mat_map: per authored material (internal index or -1, attribute copy or -1, shade class, kind).
 // Writes 4 bytes of the triangle's second row and one byte of tri_class: plain stores, every element by one lane.  The ids in tri_material
 // were validated on the host ([-1, n_materials)), so mat_map is indexed without a further test.
 static __global__ void __launch_bounds__(refit::kB) k_material_tris(DTri *__restrict__ tris, unsigned char *__restrict__ tri_class, int n_tris,
@@ -30,7 +31,7 @@ static __global__ void __launch_bounds__(refit::kB) k_material_tris(DTri *__rest
             const int4 e = mat_map[authored];
             const bool own = own_attr[prim] != 0;
             material = e.x < 0 ? -1 : (own ? e.y : e.x);
-            cls = e.x < 0 ? 0 : (own ? 3 : e.z);
+            cls = e.x < 0 ? 0 : (own ? 3 : (e.z | (e.w << kClassKeyKindShift)));
         }
         tris[li].material = material;
         tri_class[li] = (unsigned char)cls;
@@ -46,7 +47,7 @@ static __global__ void __launch_bounds__(refit::kB) k_material_gather(const DTri
         if ((unsigned)prim >= (unsigned)n_tris) continue;   // bounds guard: prim is a store index here
         const int m = tris[li].material;
         material_out[prim] = m >= 0 ? authored[m] : -1;
-        class_out[prim] = tri_class[li];
+        class_out[prim] = tri_class[li] & kClassKeyClassMask;
     }
 }
 

@@ -439,6 +439,22 @@ static bool compile_material(const gnxr_material &m, DMaterial *out, bool allowM
     return true;
 }
 
+// The kind of a class-1 material: which narrow glossy kernel (device_bsdf.h LM_CONDUCTOR / LM_ROUGH_DIELECTRIC) covers it.  A pure function of
+// the compiled material, like the class.  1 conductor: exactly one lobe, a microfacet reflection with the conductor Fresnel term (Metal).
+// 2 rough dielectric: microfacet reflection / transmission lobes with the dielectric Fresnel term only (rough Glass; Plastic has a Lambert
+// lobe and smooth Glass specular lobes).  0: everything else, and every material of another class.
+int material_kind(const DMaterial &m) {
+    if (m.shade_class != 1 || m.n_lobes < 1) return MATERIAL_KIND_OTHER;
+    bool conductor = m.n_lobes == 1, dielectric = true;
+    for (int i = 0; i < m.n_lobes; ++i) {
+        const DLobe &l = m.lobes[i];
+        if (l.disney_g) return MATERIAL_KIND_OTHER;
+        if (!(l.kind == LOBE_MICRO_REFL && l.fresnel == FRESNEL_CONDUCTOR)) conductor = false;
+        if (!((l.kind == LOBE_MICRO_REFL || l.kind == LOBE_MICRO_TRANS) && l.fresnel == FRESNEL_DIELECTRIC)) dielectric = false;
+    }
+    return conductor ? MATERIAL_KIND_CONDUCTOR : (dielectric ? MATERIAL_KIND_ROUGH_DIELECTRIC : MATERIAL_KIND_OTHER);
+}
+
 // ------------------------------------------------------------------ sampler tables
 namespace {
 struct Pcg32 {  // core/RNG.h:30-110
@@ -954,6 +970,7 @@ bool compile_materials(const gnxr_material *mats, int n_materials, int n_texture
         mt->mat_map[4 * (size_t)i] = mats[i].type == GNXR_MAT_NONE ? -1 : i;   // no BSDF: medium boundary
         mt->mat_map[4 * (size_t)i + 1] = -1;
         mt->mat_map[4 * (size_t)i + 2] = mt->materials[i].shade_class;
+        mt->mat_map[4 * (size_t)i + 3] = material_kind(mt->materials[i]);
     }
     // A triangle whose uvs are not the GetUVs defaults or that has normals gets a COPY of its material with shade class 3 (the general
     // shade queue, which reads the attribute tables and derives dpdu / dpdv, the shading frame and dndu / dndv from them); everything
@@ -984,13 +1001,13 @@ bool compile_materials(const gnxr_material *mats, int n_materials, int n_texture
     return true;
 }
 
-void triangle_material(const int32_t *mat_map, int32_t authored, uint8_t own_attr, int32_t *material, uint8_t *shade_class) {
-    *material = authored; *shade_class = 0;
+void triangle_material(const int32_t *mat_map, int32_t authored, uint8_t own_attr, int32_t *material, uint8_t *class_key) {
+    *material = authored; *class_key = 0;
     if (authored < 0) return;
     const int32_t *e = mat_map + 4 * (size_t)authored;
     if (e[0] < 0) { *material = -1; return; }
     *material = own_attr ? e[1] : e[0];
-    *shade_class = (uint8_t)(own_attr ? 3 : e[2]);
+    *class_key = (uint8_t)(own_attr ? 3 : (e[2] | (e[3] << kClassKeyKindShift)));   // (the attribute copy is class 3: no kind)
 }
 
 // ------------------------------------------------------------------ compile
