@@ -332,6 +332,12 @@ class Scene:
         self.n_triangles = int(d.n_triangles)
         self.n_vertices = int(d.n_vertices)
         self.device = _device
+        self._env_light = None   # a copy of the INFINITE light's record (update_environment keeps it current)
+        for i in range(int(d.n_lights)):
+            if d.lights[i].type == _abi.LIGHT_INFINITE:
+                self._env_light = Light()
+                C.memmove(C.byref(self._env_light), C.byref(d.lights[i]), C.sizeof(Light))
+                break
         _check(lib().gnxr_scene_create(C.byref(d), C.byref(self._h)))
 
     def close(self):
@@ -439,6 +445,66 @@ class Scene:
         holds."""
         handle = _stream_handle("rebuild_bvh", stream)
         _check(lib().gnxr_scene_rebuild_bvh(self._h, C.c_void_p(handle or None)))
+
+    def update_environment(self, rgb=None, le=None, light_to_world=None, n_samples=None, stream=None):
+        """Replace or rotate the environment map of the scene's INFINITE light (gnxr_scene_update_environment).  rgb: the new map, an
+        (h, w, 3) float32 numpy array (host memory) or a contiguous float32 (h, w, 3) torch tensor on the scene's device (read on `stream`,
+        by default the current torch stream); its size may differ from the old map's.  le, light_to_world (16 floats, row-major) and
+        n_samples replace those fields of the light's record; omitted ones keep their current values.  The tables are rebuilt on the
+        device and every later result is that of a scene created with this map and record.  rgb=None only rotates (or changes
+        n_samples): le must then stay as it is (GnxrError otherwise: the raw map is not retained, send it again)."""
+        rec = Light()
+        if self._env_light is not None:
+            C.memmove(C.byref(rec), C.byref(self._env_light), C.sizeof(Light))
+        else:   # (the library refuses a scene without an INFINITE light)
+            rec.type, rec.tri, rec.n_samples = _abi.LIGHT_INFINITE, -1, 1
+            rec.le[:] = [1.0, 1.0, 1.0]
+            rec.light_to_world[:] = [1.0 if i % 5 == 0 else 0.0 for i in range(16)]
+        if le is not None:
+            rec.le[:] = [float(x) for x in le]
+        if light_to_world is not None:
+            rec.light_to_world[:] = [float(x) for x in np.asarray(light_to_world, dtype=np.float32).reshape(16)]
+        if n_samples is not None:
+            rec.n_samples = int(n_samples)
+        ptr, w, h = None, 0, 0
+        if rgb is None:
+            pass
+        elif isinstance(rgb, np.ndarray):
+            if rgb.dtype != np.float32 or rgb.ndim != 3 or rgb.shape[2] != 3:
+                raise ValueError(f"update_environment: expected a float32 array of shape (h, w, 3), got {rgb.dtype} {rgb.shape}")
+            rgb = np.ascontiguousarray(rgb)
+            ptr, h, w = rgb.ctypes.data, rgb.shape[0], rgb.shape[1]
+        elif type(rgb).__module__.split(".")[0] == "torch":
+            import torch
+            if not (isinstance(rgb, torch.Tensor) and rgb.is_cuda and rgb.device.index == self.device and rgb.dtype == torch.float32 and
+                    rgb.dim() == 3 and rgb.shape[2] == 3 and rgb.is_contiguous()):
+                raise ValueError(f"update_environment: expected a contiguous float32 (h, w, 3) tensor on cuda:{self.device}, got "
+                                 f"{getattr(rgb, 'dtype', None)} {tuple(getattr(rgb, 'shape', ()))} on {getattr(rgb, 'device', None)}")
+            ptr, h, w = rgb.data_ptr(), int(rgb.shape[0]), int(rgb.shape[1])
+            if stream is None:
+                stream = torch.cuda.current_stream(rgb.device)
+        else:
+            raise ValueError(f"update_environment: expected a numpy array, a torch tensor or None, got {type(rgb).__name__}")
+        stream = _stream_handle("update_environment", stream)
+        _check(lib().gnxr_scene_update_environment(self._h, C.byref(rec), C.c_void_p(ptr) if rgb is not None else None, int(w), int(h), C.c_void_p(stream or None)))
+        self._env_light = rec
+
+    ENV_TABLES = (("env_texels4", np.float32), ("env_cond_func", np.float32), ("env_cond_cdf", np.float32), ("env_cond_int", np.float32),
+                  ("env_marg_func", np.float32), ("env_marg_cdf", np.float32), ("env_marg_guide", np.uint16), ("env_cond_guide", np.uint16),
+                  ("env", np.uint32), ("env_power_lookup", np.float32))
+
+    def env_tables(self):
+        """Test hook: the environment tables of the first device (gnxr_scene_env_tables) as a dict of flat arrays: the eight tables, the
+        DEnv record renders are given ("env", as uint32 words) and the Power lookup; empty arrays for a scene without an INFINITE light."""
+        out = {}
+        for which, (name, dtype) in enumerate(self.ENV_TABLES):
+            n = C.c_int64(0)
+            _check(lib().gnxr_scene_env_tables(self._h, which, None, 0, C.byref(n)))
+            a = np.zeros(n.value // np.dtype(dtype).itemsize, dtype)
+            if n.value:
+                _check(lib().gnxr_scene_env_tables(self._h, which, C.c_void_p(a.ctypes.data), n.value, C.byref(n)))
+            out[name] = a
+        return out
 
     def set_camera(self, eye=(0, 0, 5), look=(0, 0, 0), up=(0, 1, 0), fov=90.0, lens_radius=0.0, focal_distance=3.0, orthographic=False, medium=-1):
         """The camera of SceneBuilder.set_camera (and the medium it sits in, -1 == none) for later renders."""

@@ -147,6 +147,8 @@ PROTOTYPES = {
     "gnxr_scene_update_vertices_ex": (C.c_int, [VP, i32, i32, VP, u32, VP]),   # ..., flags (UPDATE_MOVE_LIGHTS), hipStream_t
     "gnxr_scene_update_lights": (C.c_int, [VP, i32, i32, P(Light)]),
     "gnxr_scene_rebuild_bvh": (C.c_int, [VP, VP]),   # scene, hipStream_t
+    "gnxr_scene_update_environment": (C.c_int, [VP, P(Light), VP, i32, i32, VP]),   # scene, record, host or device fp32 map (or NULL), width, height, hipStream_t
+    "gnxr_scene_env_tables": (C.c_int, [VP, i32, VP, i64, P(i64)]),   # scene, which, out, capacity in bytes, size in bytes
     "gnxr_scene_update_materials": (C.c_int, [VP, i32, i32, P(Material)]),
     "gnxr_scene_set_triangle_materials": (C.c_int, [VP, i32, i32, VP, VP]),   # scene, first, n, host or device int32 ids, hipStream_t
     "gnxr_scene_triangle_materials": (C.c_int, [VP, P(i32), P(C.c_uint8), C.c_int64]),

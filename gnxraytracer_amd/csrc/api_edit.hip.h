@@ -118,7 +118,7 @@ extern "C" int gnxr_scene_update_vertices(gnxr_scene *s, int32_t first_vertex, i
 // The new records of lights [first, first + n): nothing of the scene is touched before every one of them has passed.  What a record may
 // change: AREA_TRI le / two_sided / n_samples (its triangle stays; corners, area and normal come from the vertices the scene holds NOW,
 // which cs.lights carries: gnxr_scene_update_vertices_ex and gnxr_scene_rebuild_bvh keep that copy current); POINT / SPOT / DISTANT
-// everything; SKYBOX centre and radius; INFINITE nothing (its importance tables and texels are not rebuilt here).
+// everything; SKYBOX centre and radius; INFINITE nothing (its importance tables and texels are rebuilt by gnxr_scene_update_environment).
 static int build_light_update(const CompiledScene &cs, int first, int n, const gnxr_light *in, std::vector<DLight> *lights, std::vector<gnxr_light> *desc) {
     *lights = cs.lights;
     *desc = cs.desc_lights;
@@ -127,7 +127,7 @@ static int build_light_update(const CompiledScene &cs, int first, int n, const g
         const gnxr_light &was = cs.desc_lights[i], &l = in[k];
         if (l.type != was.type) { set_error("light %d: the type of a light cannot change in place (%d -> %d)", i, was.type, l.type); return GNXR_ERR_UNSUPPORTED; }
         if (l.type == GNXR_LIGHT_INFINITE) {
-            if (memcmp(&l, &was, sizeof(gnxr_light)) != 0) { set_error("light %d: an INFINITE light cannot change in place (its tables are built by gnxr_scene_create)", i); return GNXR_ERR_UNSUPPORTED; }
+            if (memcmp(&l, &was, sizeof(gnxr_light)) != 0) { set_error("light %d: an INFINITE light does not change through gnxr_scene_update_lights (gnxr_scene_update_environment rebuilds its tables)", i); return GNXR_ERR_UNSUPPORTED; }
             continue;
         }
         Vec3 corners[3];

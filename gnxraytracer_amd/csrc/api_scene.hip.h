@@ -47,6 +47,8 @@ struct SceneHost {
     CompiledScene cs;
     bool host_bvh_stale = false;     // after an update cs.nodes / nodes4 / tris / leaf_boxes lag the primary's device until sync_host_bvh()
     bool host_order_stale = false;   // after gnxr_scene_rebuild_bvh the host copies of what is held in leaf or node order lag too (the upd_* tables are current)
+    bool host_env_stale = false;     // after gnxr_scene_update_environment cs.env_texels / env_texels4 / env_cond_* / env_marg_* lag the devices until sync_host_env()
+    std::mutex env_mutex;            // sync_host_env may be reached from the worker of any copy (ensure_grid)
 };
 
 struct gnxr_scene {
@@ -150,6 +152,23 @@ struct gnxr_scene {
         host->host_bvh_stale = false;
         return GNXR_OK;
     }
+    // the host copies of the environment tables, downloaded on demand after gnxr_scene_update_environment (their one reader is the
+    // host-built spatial light table: build_light_grid).  Every copy holds the same tables: the (bound) device of this one is read.
+    int sync_host_env() {
+        std::lock_guard<std::mutex> lock(host->env_mutex);
+        if (!host->host_env_stale) return GNXR_OK;
+        const size_t nt = (size_t)cs.env.w * cs.env.h, W2 = cs.env.dw, H2 = cs.env.dh;
+        cs.env_texels4.resize(4 * nt); cs.env_texels.resize(3 * nt);
+        cs.env_cond_func.resize(W2 * H2); cs.env_cond_cdf.resize((W2 + 1) * H2); cs.env_cond_int.resize(H2);
+        cs.env_marg_func.resize(H2); cs.env_marg_cdf.resize(H2 + 1);
+        cs.env_marg_guide.resize(kEnvGuideMarg + 1); cs.env_cond_guide.resize(H2 * (kEnvGuideCond + 1));
+#define DOWN(field) HIP_TRY(hipMemcpy(cs.field.data(), field.p, cs.field.size() * sizeof(cs.field[0]), hipMemcpyDeviceToHost));
+        DOWN(env_texels4) DOWN(env_cond_func) DOWN(env_cond_cdf) DOWN(env_cond_int) DOWN(env_marg_func) DOWN(env_marg_cdf) DOWN(env_marg_guide) DOWN(env_cond_guide)
+#undef DOWN
+        for (size_t i = 0; i < nt; ++i) { cs.env_texels[3 * i] = cs.env_texels4[4 * i]; cs.env_texels[3 * i + 1] = cs.env_texels4[4 * i + 1]; cs.env_texels[3 * i + 2] = cs.env_texels4[4 * i + 2]; }
+        host->host_env_stale = false;
+        return GNXR_OK;
+    }
     ~gnxr_scene() {
         if (h_counters) (void)hipHostFree(h_counters);
         if (h_ring) (void)hipHostFree(h_ring);
@@ -162,7 +181,8 @@ struct gnxr_scene {
 
     // the lights and the environment map: what Sample_Li / Pdf_Li / Le read, without the selection table (grid, grid_table stay zero).
     // After the scene is created only the editing calls change what is behind these pointers: gnxr_scene_update_vertices refits the world radius
-    // (cs.env, distant lights), GNXR_UPDATE_MOVE_LIGHTS moves the area lights, gnxr_scene_update_lights rewrites light records.
+    // (cs.env, distant lights), GNXR_UPDATE_MOVE_LIGHTS moves the area lights, gnxr_scene_update_lights rewrites light records,
+    // gnxr_scene_update_environment swaps in new environment tables (and cs.env with them).
     DLightTables light_tables_static() const {
         DLightTables lt = {};
         lt.lights = lights.p;
@@ -238,6 +258,8 @@ struct gnxr_scene {
                 return GNXR_ERR_UNSUPPORTED;
             }
         }
+        if (!on_device && grid.spatial && cs.has_env)   // the host's probes sample the environment tables
+            if (int src = sync_host_env()) return src;
         if (!on_device) build_light_grid(cs, strategy, &grid, &table, false);
         int rc;
         if (on_device) {

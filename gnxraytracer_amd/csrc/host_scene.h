@@ -137,6 +137,15 @@ void refit_world_bound(CompiledScene *cs, const float root6[6]);
 // one DLight from its description, as compile_scene makes it (gnxr_scene_update_lights): for AREA_TRI from the corners of its triangle and
 // its leaf index; for INFINITE the record without the environment tables; false (error set) for an unknown type
 bool compile_light(const gnxr_light &l, int index, const Vec3 corners[3], int tri_leaf, const Box3 &world_bound, DLight *out);
+// the host's share of gnxr_scene_update_environment, whose tables the device builds (env_build_kernel.hip.h): MIPMap's power-of-two size,
+// the Lanczos weights of its resample (they depend on the two sizes only), the sizes of the pyramid's levels, and InfiniteAreaLight::Power's
+// lookup over the pyramid's top levels -- top_rgba[k] holds level first_level + k as float4 texels, first_level = max(0, levels - 3) --
+// all computed by the code build_env runs for gnxr_scene_create
+struct EnvResampleWeight { int32_t first; float w[4]; };
+int env_round_up_pow2(int v);
+std::vector<EnvResampleWeight> env_resample_weights(int old_res, int new_res);
+void env_pyramid_sizes(int rx, int ry, std::vector<int> *lw, std::vector<int> *lh);
+void env_power_from_top_levels(int rx, int ry, int first_level, const std::vector<std::vector<float>> &top_rgba, float out[3]);
 DCamera make_camera(const gnxr_camera &c, int W, int H, int medium);      // camera/Perspective.cpp:114-135, core/Camera.h:54-75
 DHalton make_halton(int W, int H);                                          // samplers/HaltonSampler.cpp:33-60
 // light-selection table: dense restatement of core/LightDistribution.cpp (uniform / power / spatial)

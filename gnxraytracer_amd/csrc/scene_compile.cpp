@@ -705,6 +705,54 @@ void refit_world_bound(CompiledScene *cs, const float root6[6]) {
     }
 }
 
+// Lmap->Lookup((.5, .5), .5) of InfiniteAreaLight::Power (InfiniteAreaLight.cpp:84-89; MIPMap.h:225-242 Lookup, :244-256 triangle) over a
+// pyramid of nLevels levels of lw[i] x lh[i] texels; tx(level, s, t, c) is MIPMap::Texel (Repeat).  Only the top two or three levels are
+// read, whatever the size of the map.
+template <typename Tx>
+static void mip_power_lookup(int nLevels, const std::vector<int> &lw, const std::vector<int> &lh, const Tx &tx, float *out) {
+    auto triangle = [&](int level, float sx, float ty, float *out) {
+        level = std::min(std::max(level, 0), nLevels - 1);
+        float s_ = sx * lw[level] - 0.5f, t_ = ty * lh[level] - 0.5f;
+        int s0 = (int)std::floor(s_), t0 = (int)std::floor(t_);
+        float ds = s_ - s0, dt = t_ - t0;
+        for (int c = 0; c < 3; ++c)
+            out[c] = (1 - ds) * (1 - dt) * tx(level, s0, t0, c) + (1 - ds) * dt * tx(level, s0, t0 + 1, c) + ds * (1 - dt) * tx(level, s0 + 1, t0, c) +
+                     ds * dt * tx(level, s0 + 1, t0 + 1, c);
+    };
+    const float invLog2 = 1.442695040888963387004650940071f;
+    float level = nLevels - 1 + std::log(std::max(.5f, 1e-8f)) * invLog2;
+    if (level < 0) triangle(0, .5f, .5f, out);
+    else if (level >= nLevels - 1) { for (int c = 0; c < 3; ++c) out[c] = tx(nLevels - 1, 0, 0, c); }
+    else {
+        int iLevel = (int)std::floor(level);
+        float delta = level - iLevel, a[3], b[3];
+        triangle(iLevel, .5f, .5f, a);
+        triangle(iLevel + 1, .5f, .5f, b);
+        for (int c = 0; c < 3; ++c) out[c] = (1 - delta) * a[c] + delta * b[c];
+    }
+}
+
+// ---- the host's share of gnxr_scene_update_environment (api_env.hip.h): what depends on the sizes only, and the Power lookup over the
+// few top-level texels the device hands back
+int env_round_up_pow2(int v) { return round_up_pow2(v); }
+std::vector<EnvResampleWeight> env_resample_weights(int old_res, int new_res) {
+    std::vector<RW> wt = resample_weights(old_res, new_res);
+    std::vector<EnvResampleWeight> out(wt.size());
+    for (size_t i = 0; i < wt.size(); ++i) { out[i].first = wt[i].first; memcpy(out[i].w, wt[i].w, sizeof(out[i].w)); }
+    return out;
+}
+void env_pyramid_sizes(int rx, int ry, std::vector<int> *lw, std::vector<int> *lh) {
+    lw->assign(1, rx); lh->assign(1, ry);
+    for (int m = std::max(rx, ry); m > 1; m >>= 1) { lw->push_back(std::max(1, lw->back() / 2)); lh->push_back(std::max(1, lh->back() / 2)); }
+}
+void env_power_from_top_levels(int rx, int ry, int first_level, const std::vector<std::vector<float>> &top_rgba, float out[3]) {
+    std::vector<int> lw, lh;
+    env_pyramid_sizes(rx, ry, &lw, &lh);
+    const int nLevels = (int)lw.size();
+    auto tx = [&](int level, int s_, int t_, int c) { return top_rgba[level - first_level][((size_t)modi(t_, lh[level]) * lw[level] + modi(s_, lw[level])) * 4 + c]; };
+    mip_power_lookup(nLevels, lw, lh, tx, out);
+}
+
 // flip_y: SkyBoxLight::loadImage switches stb_image to vertically flipped loading for the whole process
 // (stbi_set_flip_vertically_on_load(true), lights/SkyBoxLight.cpp:19); an InfiniteAreaLight constructed after
 // a SkyBoxLight -- the order of ui/RenderThread.cpp:145-151 -- therefore sees its map upside down.
@@ -775,27 +823,7 @@ static void build_env(const gnxr_scene_desc *d, const gnxr_light &l, bool flip_y
                                                                       tx(i - 1, 2 * s_ + 1, 2 * t + 1, c));
             pyr.push_back(std::move(lvl)); lw.push_back(sRes); lh.push_back(tRes);
         }
-        auto triangle = [&](int level, float sx, float ty, float *out) {
-            level = std::min(std::max(level, 0), nLevels - 1);
-            float s_ = sx * lw[level] - 0.5f, t_ = ty * lh[level] - 0.5f;
-            int s0 = (int)std::floor(s_), t0 = (int)std::floor(t_);
-            float ds = s_ - s0, dt = t_ - t0;
-            for (int c = 0; c < 3; ++c)
-                out[c] = (1 - ds) * (1 - dt) * tx(level, s0, t0, c) + (1 - ds) * dt * tx(level, s0, t0 + 1, c) + ds * (1 - dt) * tx(level, s0 + 1, t0, c) +
-                         ds * dt * tx(level, s0 + 1, t0 + 1, c);
-        };
-        const float invLog2 = 1.442695040888963387004650940071f;
-        float level = nLevels - 1 + std::log(std::max(.5f, 1e-8f)) * invLog2;
-        float *out = cs->env_power_lookup;
-        if (level < 0) triangle(0, .5f, .5f, out);
-        else if (level >= nLevels - 1) { for (int c = 0; c < 3; ++c) out[c] = tx(nLevels - 1, 0, 0, c); }
-        else {
-            int iLevel = (int)std::floor(level);
-            float delta = level - iLevel, a[3], b[3];
-            triangle(iLevel, .5f, .5f, a);
-            triangle(iLevel + 1, .5f, .5f, b);
-            for (int c = 0; c < 3; ++c) out[c] = (1 - delta) * a[c] + delta * b[c];
-        }
+        mip_power_lookup(nLevels, lw, lh, tx, cs->env_power_lookup);
     }
     DEnv &e = cs->env;
     memset(&e, 0, sizeof(e));

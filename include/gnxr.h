@@ -407,12 +407,38 @@ int gnxr_scene_update_vertices_ex(gnxr_scene *scene, int32_t first_vertex, int32
  * description with those light records.  What may change: le, two_sided and n_samples of an AREA_TRI light (its corners, area and
  * normal stay those of the vertices the scene holds now, moved or not); every field of a POINT, SPOT or DISTANT light; center and
  * radius of a SKYBOX light.  GNXR_ERR_UNSUPPORTED for a record whose type differs from the light's, an AREA_TRI record whose tri
- * differs, or an INFINITE record that differs in any byte (the environment tables are built by gnxr_scene_create only);
+ * differs, or an INFINITE record that differs in any byte (the environment light changes through gnxr_scene_update_environment,
+ * which rebuilds its tables);
  * GNXR_ERR_INVALID for a null scene, a null lights with n_lights > 0 or a range outside the scene's lights.  Every refusal leaves the
  * scene exactly as it was: all records are built into a copy first.  The call takes the handle's render lock, writes the records of
  * every device of the scene and returns; the BVH, textures, tables and the path state of gnxr_render_reserve stay, the light-selection
  * table is rebuilt at the next render. */
 int gnxr_scene_update_lights(gnxr_scene *scene, int32_t first_light, int32_t n_lights, const gnxr_light *lights);
+/* Replace or rotate the environment map of the scene's INFINITE light.  `light` is the new record of that light: le, light_to_world and
+ * n_samples may change, type must be GNXR_LIGHT_INFINITE.  rgb is the new map, width * height * 3 fp32, row-major, as decoded from .hdr
+ * (the meaning of gnxr_scene_desc.env_rgb); its size may differ from the one the scene was created with.  rgb may be host memory or
+ * device memory of the scene's (first) device, told apart as gnxr_scene_update_vertices tells xyz apart; the read is ordered after what
+ * hip_stream holds (NULL: the null stream) and the build runs on that stream.  The texels (r * sqrt(r), r = le * rgb, rows flipped when a
+ * SKYBOX light precedes the INFINITE light in the light list, as at creation), their Lanczos resample to powers of two, the pyramid behind
+ * InfiniteAreaLight::Power, the 2w x 2h sampling image, its conditional and marginal distributions and the FindInterval guide tables are
+ * built on the device, on every device of the scene from the raw map, with the arithmetic gnxr_scene_create applies on the host:
+ * afterwards every result of the handle -- renders of all integrators, gnxr_li_device, gnxr_render_views_device, gnxr_render_aov_device,
+ * gnxr_light_sample_device, gnxr_light_le_device, the light-selection tables of all three strategies, the ray counters of gnxr_stats -- is
+ * bit for bit that of a scene created from the same description carrying this map and this record.
+ * rgb == NULL (width and height ignored) is a rotation-only edit: le must equal the current record's bytes, only the transforms, the
+ * light record and the light-selection table change and no kernel runs; with a changed le it is GNXR_ERR_INVALID -- send the map again,
+ * the raw map is not retained.
+ * The call takes the handle's render lock.  Each device builds into fresh buffers and no copy swaps until every copy has built, so a
+ * refused or failed call leaves the scene exactly as it was, on all devices.  It returns when every device holds the new tables.  The
+ * light-selection table is rebuilt at the next render; the BVH, materials, textures, media, sampler tables, the camera and the path state
+ * of gnxr_render_reserve stay where they are.  Besides the map, the Lanczos weights (one record per resampled row and column) and the
+ * light records go to the device; the at most 21 texels of the pyramid's top three levels and the marginal's integral come back; no table
+ * crosses the host when rgb is device memory.
+ * GNXR_ERR_INVALID, before any device is touched, for a null scene, a null light, a type other than GNXR_LIGHT_INFINITE, rgb with
+ * width <= 0 or height <= 0, a size whose guide-table entries would not fit uint16_t (2 * round_up_pow2(size) + 1 > 65535: more than
+ * 16384 texels per side) and the le rule above; GNXR_ERR_UNSUPPORTED for a scene created without an INFINITE light (the light list is
+ * fixed); GNXR_ERR_OOM. */
+int gnxr_scene_update_environment(gnxr_scene *scene, const gnxr_light *light, const float *rgb, int32_t width, int32_t height, void *hip_stream);
 /* Rebuild the triangle BVH of an existing scene over the vertices it currently holds on the device (the state after any number of
  * gnxr_scene_update_vertices calls), entirely on the device: the tree, its 4-wide form, the primitive order and everything kept in
  * that order become what gnxr_scene_create builds with bvh_split_method = GNXR_BVH_HLBVH from a description carrying those vertices,
@@ -449,6 +475,11 @@ int gnxr_scene_set_triangle_materials(gnxr_scene *scene, int32_t first_triangle,
  * shows (-1 where it has no BSDF) and its shade-class byte.  Returns the number of triangles (or a negative gnxr_status); the arrays are
  * filled when both are given and capacity allows. */
 int gnxr_scene_triangle_materials(gnxr_scene *scene, int32_t *material_out, uint8_t *shade_class_out, int64_t capacity);
+/* Test hook: one environment table as the scene's first device holds it.  which 0 .. 7: env_texels4 (float4 per level-0 texel),
+ * env_cond_func, env_cond_cdf, env_cond_int, env_marg_func, env_marg_cdf (fp32), env_marg_guide, env_cond_guide (uint16_t); 8: the DEnv
+ * record every render is given (sizes, transforms, bounding sphere, the marginal's integral); 9: the three floats of the Power lookup.
+ * *n_bytes receives the table's size (0 for a scene without an INFINITE light); out is filled when given and capacity_bytes allows. */
+int gnxr_scene_env_tables(gnxr_scene *scene, int32_t which, void *out, int64_t capacity_bytes, int64_t *n_bytes);
 /* Replace the camera (and the medium it sits in, -1 == none) for later renders; same checks as gnxr_scene_create. */
 int gnxr_scene_set_camera(gnxr_scene *scene, const gnxr_camera *camera, int32_t camera_medium);
 
