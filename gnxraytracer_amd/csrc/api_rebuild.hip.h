@@ -72,9 +72,10 @@ int rebuild_on_device(gnxr_scene *s, hipStream_t st, Rebuilt *r) {
     // ---- flatten
     DevBuf<int> par, size;
     DevBuf<unsigned int> arrived;
-    DevBuf<unsigned char> even;
+    DevBuf<unsigned char> choice, is_root4;
+    DevBuf<WideCost> cost;
     DevBuf<uint32_t> id4, sums, total;
-    if ((rc = par.alloc(cap)) || (rc = size.alloc(cap)) || (rc = arrived.alloc(cap)) || (rc = even.alloc(N)) || (rc = id4.alloc(N)) ||
+    if ((rc = par.alloc(cap)) || (rc = size.alloc(cap)) || (rc = arrived.alloc(cap)) || (rc = choice.alloc(N)) || (rc = is_root4.alloc(N)) || (rc = cost.alloc(N)) || (rc = id4.alloc(N)) ||
         (rc = sums.alloc((size_t)(N + hlbvh::kTile - 1) / hlbvh::kTile + 2)) || (rc = total.alloc(1)) || (rc = r->nodes.alloc(N)) || (rc = r->parent.alloc(N)) ||
         (rc = r->arrived.alloc(N)) || (rc = r->leaf_boxes.alloc(8 * (size_t)n)))
         return rc;
@@ -82,14 +83,21 @@ int rebuild_on_device(gnxr_scene *s, hipStream_t st, Rebuilt *r) {
     HIP_TRY(hipMemsetAsync(size.p, 0, (size_t)cap * sizeof(int), st));
     HIP_TRY(hipMemsetAsync(arrived.p, 0, (size_t)cap * sizeof(unsigned int), st));
     HIP_TRY(hipMemsetAsync(id4.p, 0, (size_t)N * sizeof(uint32_t), st));
-    HIP_TRY(hipMemsetAsync(even.p, 0, (size_t)N, st));
+    HIP_TRY(hipMemsetAsync(choice.p, 0, (size_t)N, st));
+    HIP_TRY(hipMemsetAsync(is_root4.p, 0, (size_t)N, st));
+    HIP_TRY(hipMemsetAsync(cost.p, 0, (size_t)N * sizeof(WideCost), st));
+    HIP_TRY(hipMemsetAsync(r->arrived.p, 0, (size_t)N * sizeof(unsigned int), st));
     HIP_TRY(hipMemsetAsync(r->nodes.p, 0, (size_t)N * sizeof(DNode), st));
     HIP_TRY(hipMemsetAsync(r->parent.p, 0xff, (size_t)N * sizeof(int), st));
     HIP_TRY(hipMemsetAsync(r->leaf_boxes.p, 0, 8 * (size_t)n * sizeof(float), st));
     hipLaunchKernelGGL(k_rb_parents, dim3(grid_for(cap)), dim3(kB), 0, st, (const HlbvhNode *)hb.d_nodes.p, U, cap, par.p, res.p);
     hipLaunchKernelGGL(k_rb_sizes, dim3(grid_for(U)), dim3(kB), 0, st, U, cap, (const HlbvhNode *)hb.d_nodes.p, (const int *)par.p, arrived.p, size.p, res.p);
     hipLaunchKernelGGL(k_rb_flatten, dim3(grid_for(cap)), dim3(kB), 0, st, U, cap, hb.root, N, n, (const HlbvhNode *)hb.d_nodes.p, (const int *)par.p, (const int *)size.p, r->nodes.p,
-                       r->parent.p, even.p, id4.p, r->leaf_boxes.p, res.p);
+                       r->parent.p, r->leaf_boxes.p, res.p);
+    // the cuts of the 4-wide tree (wide_collapse.h): costs bottom-up, then which nodes are DNode4s; r->arrived serves as the counters (the
+    // refit clears it before every use)
+    hipLaunchKernelGGL(k_rb_cost, dim3(grid_for(N)), dim3(kB), 0, st, N, (const DNode *)r->nodes.p, (const int *)r->parent.p, r->arrived.p, cost.p, choice.p);
+    hipLaunchKernelGGL(k_rb_cuts, dim3(grid_for(N)), dim3(kB), 0, st, N, (const DNode *)r->nodes.p, (const int *)r->parent.p, (const unsigned char *)choice.p, id4.p, is_root4.p, res.p);
     hl_scan(id4.p, N, sums.p, total.p, st);
     HIP_TRY(hipGetLastError());
     uint32_t n4 = 0;
@@ -117,7 +125,7 @@ int rebuild_on_device(gnxr_scene *s, hipStream_t st, Rebuilt *r) {
         HIP_TRY(hipMemsetAsync(placed.p, 0, (size_t)n4 * sizeof(uint32_t), st));
         HIP_TRY(hipMemsetAsync(r->nodes4.p, 0, (size_t)n4 * sizeof(DNode4), st));
         HIP_TRY(hipMemsetAsync(r->node4_src.p, 0xff, 4 * (size_t)n4 * sizeof(int32_t), st));
-        hipLaunchKernelGGL(k_rb_collapse, dim3(grid_for(N)), dim3(kB), 0, st, N, (const DNode *)r->nodes.p, (const int *)r->parent.p, (const unsigned char *)even.p,
+        hipLaunchKernelGGL(k_rb_collapse, dim3(grid_for(N)), dim3(kB), 0, st, N, (const DNode *)r->nodes.p, (const unsigned char *)choice.p, (const unsigned char *)is_root4.p,
                            (const uint32_t *)id4.p, (int)n4, tmp4.p, src_tmp.p, res.p);
         hipLaunchKernelGGL(k_rb_bfs, dim3(1), dim3(kTopNodesMax), 0, st, (const DNode4 *)tmp4.p, (int)n4, new_of.p, placed.p, res.p);
         hl_scan(placed.p, (int)n4, sums.p, nullptr, st);

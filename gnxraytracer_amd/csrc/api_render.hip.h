@@ -21,7 +21,7 @@ static TraceLaunch trace_launch(const gnxr_scene *s, bool wide, bool spheres, lo
     // global memory (LDS levels are worth more than a bigger node cache: profiles/README.md, r02 A/B table)
     const int per_cu = g_trace_blocks_per_cu;
     // besides the stack: the set-up ray records, the top-of-tree node cache and the order table
-    const size_t fixed_b = wide ? (size_t)(kRayRecDwords + (spheres ? 1 : 0)) * kRqStride * sizeof(int) + (size_t)kTopCache * 128 + 128 : 0;
+    const size_t fixed_b = wide ? (size_t)(kRayRecDwords + (spheres ? 1 : 0)) * kRqStride * sizeof(int) + (size_t)kTopCache * 128 + kOrderTableBytes : 0;
     t.lds_entries = std::min(std::min(t.entries, Knobs::trace_lds_levels()), std::max(2, (int)(((160 * 1024) / per_cu - 1024 - fixed_b) / (kBlock * sizeof(int)))));
     t.spill_needed = t.entries > t.lds_entries;
     t.lds = (size_t)t.lds_entries * kBlock * sizeof(int) + fixed_b;

@@ -4,6 +4,7 @@
 // dwordx4; per-scene tables are read-mostly and small enough (BVH of 100k triangles = 6.4 MB nodes
 // + 4.8 MB triangles) to live in the 32 MiB aggregate L2 / 256 MiB Infinity Cache.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 namespace gnxr {
@@ -18,18 +19,20 @@ struct DNode {
 };
 static_assert(sizeof(DNode) == 32, "DNode must be 32 bytes");
 
-// 4-wide node made by collapsing two levels of the binary tree (children = the grandchildren A.l A.r B.l B.r of a
-// binary node N with children A, B).  The split axes of N, A and B are kept so that the four children are visited in
-// exactly the order BVHAccel::Intersect would reach them (near child first by dirIsNeg[axis]), which keeps hit
-// records bit-identical while halving the number of dependent memory round trips per ray.  128 B = 8 dwordx4.
+// 4-wide node: the children are a cut of the binary subtree under a binary node N -- 2 to 4 binary nodes that cover N's leaves exactly
+// once, chosen so that the summed surface area of all 4-wide nodes is smallest (wide_collapse.h).  The split axes between N and the
+// cut fix, per ray octant, the order in which BVHAccel::Intersect would reach the children (near child first by dirIsNeg[axis]); the node
+// carries that order, which keeps hit records bit-identical while a ray takes well under half the dependent memory round trips.
+// 128 B = 8 dwordx4.
 struct DNode4 {
     float lox[4], loy[4], loz[4], hix[4], hiy[4], hiz[4];
     int32_t child[4];     // >= 0: DNode4 index; < 0: leaf, ~ref = first triangle | nPrims << 24; kNode4Empty: no child (box inverted)
     uint32_t order_lo, order_hi;   // visiting order per ray octant (neg0 | neg1 << 1 | neg2 << 2): byte o = 4 x 2-bit child slots, nearest first
-    int32_t axes;                  // axis0 | axisA << 2 | axisB << 4 (kept for inspection)
+    uint32_t codes;                // the same order in 4 bits per octant: shape of the cut | three near / far decisions (wide_collapse.h)
     int32_t _pad;
 };
 static_assert(sizeof(DNode4) == 128, "DNode4 must be 128 bytes");
+static_assert(offsetof(DNode4, order_lo) == 112 && offsetof(DNode4, codes) == 120, "k_trace4 reads the order tables at fixed offsets");
 constexpr int32_t kNode4Empty = 0x7ffffffe;
 constexpr int kTopNodesMax = 1024;   // DNode4[0 .. kTopNodesMax) are the top of the tree in breadth-first order (scene_compile.cpp); the traversal kernel caches a prefix of them in LDS
 constexpr int32_t kRefDone = 0x7fffffff;

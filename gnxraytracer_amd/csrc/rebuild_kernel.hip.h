@@ -7,9 +7,13 @@
 //   k_rb_sizes       nodes per subtree, bottom-up with arrival counters (the form of k_hl_fit)
 //   k_rb_flatten     `flatten`: one lane per build node walks to the root and sums what lies in front of it in pre-order (1 for a
 //                    first child, 1 + size(first subtree) for a second child), which is its index in DNode[]; writes DNode,
-//                    node_parent, leaf_boxes, the depth's parity and the maximum depth
-//   k_rb_collapse    `collapse`: a binary interior node at even depth is a DNode4; its depth-first number is the exclusive scan of that
-//                    flag over pre-order (scan kernels of hlbvh_build.hip.h); one lane per DNode4 fills it and sums the stack need
+//                    node_parent, leaf_boxes and the maximum depth
+//   k_rb_cost        `collapse`, pass 1: the costs T(X, 1..4) of wide_collapse.h and every node's decisions, bottom-up with arrival
+//                    counters (the form of k_refit_fit)
+//   k_rb_cuts        pass 2: one lane per binary interior node replays the decisions along its own root path (at most the tree's depth
+//                    steps) and learns whether it is the root of a DNode4; sums the stack need on the way
+//   k_rb_collapse    pass 3: a DNode4's depth-first number is the exclusive scan of that flag over pre-order (scan kernels of
+//                    hlbvh_build.hip.h); one lane per DNode4 fills it from its cut (wide_cut, the function the host uses)
 //   k_rb_bfs         the breadth-first order of the first kTopNodesMax 4-wide nodes: one block, level by level over a queue in LDS
 //   k_rb_renumber    DNode4[] in its final order (top block breadth-first, the rest depth-first), child indices remapped, node4_src
 //   k_rb_permute     everything held in leaf order follows the new primitive order
@@ -24,6 +28,7 @@
 #include "gnxr_device_types.h"
 #include "host_scene.h"
 #include "refit_kernel.hip.h"
+#include "wide_collapse.h"
 
 namespace gnxr {
 namespace rebuild {
@@ -102,10 +107,10 @@ static __global__ void __launch_bounds__(kB) k_rb_sizes(int U, int cap, const Hl
     }
 }
 
-// n_nodes = 2 U - 1.  leaf_boxes is zero on entry.  is4: 1 where the node becomes a DNode4 (scanned in place afterwards).
+// n_nodes = 2 U - 1.  leaf_boxes is zero on entry.
 static __global__ void __launch_bounds__(kB) k_rb_flatten(int U, int cap, int root, int n_nodes, int n_tris, const HlbvhNode *__restrict__ nodes, const int *__restrict__ par,
-                                                         const int *__restrict__ size, DNode *__restrict__ out, int *__restrict__ node_parent, unsigned char *__restrict__ even,
-                                                         uint32_t *__restrict__ is4, float *__restrict__ leaf_boxes, int *__restrict__ res) {
+                                                         const int *__restrict__ size, DNode *__restrict__ out, int *__restrict__ node_parent, float *__restrict__ leaf_boxes,
+                                                         int *__restrict__ res) {
     int max_depth = 0;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < cap; i += gridDim.x * blockDim.x) {
         const HlbvhNode nd = nodes[i];
@@ -135,8 +140,6 @@ static __global__ void __launch_bounds__(kB) k_rb_flatten(int U, int cap, int ro
         }
         out[pre] = d;
         node_parent[pre] = depth == 0 ? -1 : pre - first_delta;
-        even[pre] = (depth & 1) == 0 ? 1 : 0;
-        is4[pre] = (!leaf && (depth & 1) == 0) ? 1u : 0u;
         max_depth = max(max_depth, depth);
     }
     for (int o = 32; o > 0; o >>= 1) max_depth = max(max_depth, __shfl_xor(max_depth, o));
@@ -145,68 +148,100 @@ static __global__ void __launch_bounds__(kB) k_rb_flatten(int U, int cap, int ro
 
 __device__ __forceinline__ bool rb_is_leaf(const DNode &n) { return (n.meta & 0xffffu) != 0; }
 __device__ __forceinline__ int32_t rb_leaf_ref(const DNode &n) { return ~(int32_t)((uint32_t)n.offset | ((n.meta & 0x7fu) << 24)); }
-// children a DNode4 made from binary node b has: one per leaf child, two per interior child
-__device__ __forceinline__ int rb_nchild(const DNode *__restrict__ bn, int b) { return (rb_is_leaf(bn[b + 1]) ? 1 : 2) + (rb_is_leaf(bn[bn[b].offset]) ? 1 : 2); }
+// One lane per leaf of the binary tree climbs: the first child to arrive at a parent leaves, the second computes the parent's costs from the
+// two children's (k_refit_fit's scheme, fences and agent-scope loads included).  `arrived` is zero on entry.
+__device__ __forceinline__ WideCost rb_load_cost(const WideCost *c) {
+    WideCost r;
+    for (int k = 0; k < 4; ++k) r.t[k] = __hip_atomic_load(&c->t[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return r;
+}
+static __global__ void __launch_bounds__(kB) k_rb_cost(int n_nodes, const DNode *__restrict__ bn, const int *__restrict__ node_parent, unsigned int *__restrict__ arrived,
+                                                      WideCost *cost, unsigned char *__restrict__ choice) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_nodes; i += gridDim.x * blockDim.x) {
+        if (!rb_is_leaf(bn[i])) continue;
+        cost[i] = wide_cost_leaf();
+        int p = node_parent[i];
+        while (p >= 0) {
+            __threadfence();
+            if (atomicAdd(&arrived[p], 1u) == 0u) break;
+            __threadfence();
+            const DNode X = bn[p];
+            if (X.offset <= p + 1 || X.offset >= n_nodes) break;   // (not a pre-order tree: k_rb_flatten has raised the error flag)
+            const WideCost a = rb_load_cost(cost + p + 1), b = rb_load_cost(cost + X.offset);
+            WideCost c;
+            choice[p] = wide_cost_interior(X, a, b, &c);
+            cost[p] = c;
+            p = node_parent[p];
+        }
+    }
+}
 
-// id4: the exclusive scan of is4 (the DNode4's number in collapse's depth-first order).  out / src are in that order.
-static __global__ void __launch_bounds__(kB) k_rb_collapse(int n_nodes, const DNode *__restrict__ bn, const int *__restrict__ node_parent, const unsigned char *__restrict__ even,
-                                                          const uint32_t *__restrict__ id4, int n4, DNode4 *__restrict__ out, int *__restrict__ src, int *__restrict__ res) {
+// is4 / root4: 1 where the node becomes a DNode4 (is4 is scanned in place afterwards).  Both are zero on entry.
+static __global__ void __launch_bounds__(kB) k_rb_cuts(int n_nodes, const DNode *__restrict__ bn, const int *__restrict__ node_parent, const unsigned char *__restrict__ choice,
+                                                      uint32_t *__restrict__ is4, unsigned char *__restrict__ root4, int *__restrict__ res) {
     int need = 1;
     for (int bi = blockIdx.x * blockDim.x + threadIdx.x; bi < n_nodes; bi += gridDim.x * blockDim.x) {
-        const DNode N = bn[bi];
-        if (rb_is_leaf(N) || !even[bi]) continue;
-        const int me = (int)id4[bi];
-        if (me < 0 || me >= n4) { res[R_ERROR] = 1; continue; }
-        DNode4 d;
-        for (int k = 0; k < 4; ++k) {   // absent children: inverted boxes, which fail every slab test
-            d.child[k] = kNode4Empty;
-            d.lox[k] = d.loy[k] = d.loz[k] = __builtin_inff();
-            d.hix[k] = d.hiy[k] = d.hiz[k] = -__builtin_inff();
+        if (rb_is_leaf(bn[bi])) continue;
+        // the way up: which child each node of the root path is (bit s: the step taken from depth s)
+        unsigned long long second = 0ull;
+        int depth = 0, c = bi;
+        bool deep = false;
+        for (int p = node_parent[c]; p >= 0; p = node_parent[c]) {
+            if (depth == 64) { deep = true; break; }
+            second = (second << 1) | (bn[p].offset == c ? 1ull : 0ull);
+            ++depth; c = p;
         }
-        d._pad = 0;
-        const int axis0 = (int)(N.meta >> 16);
-        int axisAB[2] = {0, 0};
-        int grand[4] = {-1, -1, -1, -1};
-        const int AB[2] = {bi + 1, N.offset};
-        for (int h = 0; h < 2; ++h) {
-            const DNode x = bn[AB[h]];
-            if (rb_is_leaf(x)) grand[2 * h] = AB[h];
-            else { grand[2 * h] = AB[h] + 1; grand[2 * h + 1] = x.offset; axisAB[h] = (int)(x.meta >> 16); }
+        if (deep) continue;   // deeper than any tree the host accepts (R_MAX_DEPTH): the call fails on that
+        if (c != 0) { res[R_ERROR] = 1; continue; }
+        // the way down: `slots` is the number of child slots the node shares among its leaves; 1: the node is a child slot, and being
+        // interior (every node of the path is) the root of a DNode4 that leaves k - 1 references on the stack while its first child is walked
+        int cur = 0, slots = 1, below = 0;
+        bool is_root = false;
+        for (int s = 0;; ++s) {
+            is_root = slots == 1;
+            if (is_root) { slots = wide_best_k(choice[cur]); below += slots - 1; }
+            if (s == depth) break;
+            const int a = wide_split(choice[cur], slots);
+            const bool sec = (second >> s) & 1ull;
+            slots = sec ? slots - a : a;
+            cur = sec ? bn[cur].offset : cur + 1;
+            if (cur <= 0 || cur >= n_nodes) break;   // (not a pre-order tree: caught below)
         }
-        const int axisA = axisAB[0], axisB = axisAB[1];
-        uint32_t table[2] = {0u, 0u};
-        for (int oct = 0; oct < 8; ++oct) {
-            const int n0 = (oct >> axis0) & 1, nA = (oct >> axisA) & 1, nB = (oct >> axisB) & 1;
-            const int base0 = n0 ? 2 : 0, base1 = 2 - base0;
-            const int sw0 = n0 ? nB : nA, sw1 = n0 ? nA : nB;
-            const uint32_t byte = (uint32_t)((base0 + sw0) | ((base0 + 1 - sw0) << 2) | ((base1 + sw1) << 4) | ((base1 + 1 - sw1) << 6));
-            table[oct >> 2] |= byte << (8 * (oct & 3));
-        }
-        d.order_lo = table[0]; d.order_hi = table[1];
-        d.axes = axis0 | (axisA << 2) | (axisB << 4);
-        for (int k = 0; k < 4; ++k) {
-            src[4 * (size_t)me + k] = grand[k];
-            if (grand[k] < 0) continue;
-            const DNode g = bn[grand[k]];
-            d.lox[k] = g.lo[0]; d.loy[k] = g.lo[1]; d.loz[k] = g.lo[2];
-            d.hix[k] = g.hi0; d.hiy[k] = g.hi1; d.hiz[k] = g.hi2;
-            d.child[k] = rb_is_leaf(g) ? rb_leaf_ref(g) : (int32_t)id4[grand[k]];
-        }
-        out[me] = d;
-        // a node can leave nchild - 1 references on the stack while its first child is traversed: summed over the node and its ancestors
-        int below = 0, a = bi;
-        for (int steps = 0;; ++steps) {
-            if (steps > n_nodes) { res[R_ERROR] = 1; break; }
-            below += rb_nchild(bn, a) - 1;
-            const int p = node_parent[a];
-            if (p < 0) break;
-            a = node_parent[p];
-            if (a < 0) { res[R_ERROR] = 1; break; }
-        }
-        need = max(need, below + 1);
+        if (cur != bi) { res[R_ERROR] = 1; continue; }
+        if (is_root) { is4[bi] = 1u; root4[bi] = 1; need = max(need, below + 1); }
     }
     for (int o = 32; o > 0; o >>= 1) need = max(need, __shfl_xor(need, o));
     if ((threadIdx.x & 63) == 0) atomicMax(&res[R_STACK4_NEED], need);
+}
+
+// id4: the exclusive scan of is4 (the DNode4's number in collapse's depth-first order).  out / src are in that order.
+static __global__ void __launch_bounds__(kB) k_rb_collapse(int n_nodes, const DNode *__restrict__ bn, const unsigned char *__restrict__ choice, const unsigned char *__restrict__ root4,
+                                                          const uint32_t *__restrict__ id4, int n4, DNode4 *__restrict__ out, int *__restrict__ src, int *__restrict__ res) {
+    for (int bi = blockIdx.x * blockDim.x + threadIdx.x; bi < n_nodes; bi += gridDim.x * blockDim.x) {
+        if (!root4[bi]) continue;
+        const int me = (int)id4[bi];
+        if (me < 0 || me >= n4) { res[R_ERROR] = 1; continue; }
+        const WideCut cut = wide_cut(bn, choice, bi);
+        DNode4 d;
+        d.order_lo = cut.order_lo; d.order_hi = cut.order_hi; d.codes = cut.codes;
+        d._pad = 0;
+        for (int k = 0; k < 4; ++k) {
+            const int g = cut.slot[k];
+            src[4 * (size_t)me + k] = g;
+            if (g < 0) {   // absent children: inverted boxes, which fail every slab test
+                d.child[k] = kNode4Empty;
+                d.lox[k] = d.loy[k] = d.loz[k] = __builtin_inff();
+                d.hix[k] = d.hiy[k] = d.hiz[k] = -__builtin_inff();
+                continue;
+            }
+            if (g >= n_nodes) { res[R_ERROR] = 1; d.child[k] = kNode4Empty; continue; }
+            const DNode G = bn[g];
+            d.lox[k] = G.lo[0]; d.loy[k] = G.lo[1]; d.loz[k] = G.lo[2];
+            d.hix[k] = G.hi0; d.hiy[k] = G.hi1; d.hiz[k] = G.hi2;
+            d.child[k] = rb_is_leaf(G) ? rb_leaf_ref(G) : (int32_t)id4[g];
+        }
+        out[me] = d;
+    }
 }
 
 // One block of kTopNodesMax threads.  new_of is -1 and placed 0 on entry; the first min(n4, kTopNodesMax) nodes of the breadth-first order

@@ -12,6 +12,7 @@
 #include <thread>
 
 #include "host_scene.h"
+#include "wide_collapse.h"
 
 namespace gnxr {
 
@@ -151,63 +152,68 @@ static int flatten(const std::vector<BuildNode> &bn, int node, std::vector<DNode
 
 // ------------------------------------------------------------------ BVH4 collapse
 namespace {
-inline bool is_leaf(const DNode &n) { return (n.meta & 0xffffu) != 0; }
 inline int32_t leaf_ref(const DNode &n) { return ~(int32_t)((uint32_t)n.offset | ((n.meta & 0x7fu) << 24)); }
 
-// returns a child reference for binary node `bi`; interior nodes become DNode4s (pre-order).  src receives, 4 per DNode4, the binary node
-// each child slot copies its box from (-1 for an absent child): the refit refills the slots from the refitted binary tree.
-int32_t collapse(const std::vector<DNode> &bn, int bi, std::vector<DNode4> &out, std::vector<int32_t> &src, int depthStack, int *needStack) {
-    const DNode &N = bn[bi];
-    if (is_leaf(N)) return leaf_ref(N);
-    int me = (int)out.size();
-    out.push_back(DNode4());
-    src.insert(src.end(), 4, -1);
-    DNode4 d;
-    memset(&d, 0, sizeof(d));
-    for (int k = 0; k < 4; ++k) d.child[k] = kNode4Empty;
-    int axis0 = (int)(N.meta >> 16), axisA = 0, axisB = 0;
-    int A = bi + 1, B = N.offset;
-    int grand[4] = {-1, -1, -1, -1};
-    auto group = [&](int X, int base, int *axisOut) {
-        const DNode &x = bn[X];
-        if (is_leaf(x)) { grand[base] = X; *axisOut = 0; }
-        else { grand[base] = X + 1; grand[base + 1] = x.offset; *axisOut = (int)(x.meta >> 16); }
-    };
-    group(A, 0, &axisA);
-    group(B, 2, &axisB);
-    // order in which BVHAccel::Intersect reaches the four grandchildren for each ray octant: the near child of N first
-    // (dirIsNeg[axis0]), inside each half the near grandchild first (dirIsNeg[axisA] / dirIsNeg[axisB])
-    uint64_t table = 0;
-    for (int oct = 0; oct < 8; ++oct) {
-        int neg[3] = {oct & 1, (oct >> 1) & 1, (oct >> 2) & 1};
-        int n0 = neg[axis0], nA = neg[axisA], nB = neg[axisB];
-        int base0 = n0 ? 2 : 0, base1 = 2 - base0;
-        int sw0 = n0 ? nB : nA, sw1 = n0 ? nA : nB;
-        int order[4] = {base0 + sw0, base0 + 1 - sw0, base1 + sw1, base1 + 1 - sw1};
-        uint64_t byte = (uint64_t)(order[0] | (order[1] << 2) | (order[2] << 4) | (order[3] << 6));
-        table |= byte << (8 * oct);
+// The 4-wide tree over the binary tree `bn` (pre-order): which nodes become DNode4s and what their children are is decided by
+// wide_collapse.h (minimum summed surface area of the DNode4 roots).  Three passes over the array, the ones the device rebuild makes
+// (rebuild_kernel.hip.h): costs bottom-up (children lie behind their parent), the roots of the cuts top-down, then one DNode4 per root,
+// numbered in pre-order of the binary tree.  src receives, 4 per DNode4, the binary node each child slot copies its box from (-1 for an
+// absent child): the refit refills the slots from the refitted binary tree.  Returns the root reference.
+int32_t collapse(const std::vector<DNode> &bn, std::vector<DNode4> &out, std::vector<int32_t> &src, int *needStack) {
+    const size_t n = bn.size();
+    if (wide_is_leaf(bn[0])) return leaf_ref(bn[0]);
+    std::vector<WideCost> cost(n);
+    std::vector<uint8_t> choice(n, 0);
+    for (size_t i = n; i-- > 0;) {
+        if (wide_is_leaf(bn[i])) cost[i] = wide_cost_leaf();
+        else choice[i] = wide_cost_interior(bn[i], cost[i + 1], cost[bn[i].offset], &cost[i]);
     }
-    d.order_lo = (uint32_t)table; d.order_hi = (uint32_t)(table >> 32);
-    d.axes = axis0 | (axisA << 2) | (axisB << 4);
-    for (int k = 0; k < 4; ++k) {   // absent children: inverted boxes, which fail every slab test
-        d.lox[k] = d.loy[k] = d.loz[k] = std::numeric_limits<float>::infinity();
-        d.hix[k] = d.hiy[k] = d.hiz[k] = -std::numeric_limits<float>::infinity();
+    // slots[i]: the slots binary node i shares among its leaves (1: it is a child slot, and a DNode4 of its own if interior);
+    // below[i]: references the DNode4s above i leave on the stack while the walk is inside i
+    std::vector<uint8_t> slots(n, 0);
+    std::vector<int32_t> below(n, 0), id4(n, -1);
+    slots[0] = 1;
+    int32_t n4 = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (wide_is_leaf(bn[i])) continue;
+        int k = slots[i];
+        if (k == 1) {
+            k = wide_best_k(choice[i]);
+            id4[i] = n4++;
+            // a node can leave k - 1 references on the stack while its first child is being traversed
+            below[i] += k - 1;
+            *needStack = std::max(*needStack, below[i] + 1);
+        }
+        const int a = wide_split(choice[i], k);
+        const size_t A = i + 1, B = (size_t)bn[i].offset;
+        slots[A] = (uint8_t)a; slots[B] = (uint8_t)(k - a);
+        below[A] = below[B] = below[i];
     }
-    int nchild = 0;
-    for (int k = 0; k < 4; ++k) if (grand[k] >= 0) ++nchild;
-    // a node can leave nchild-1 references on the stack while its first child is being traversed
-    int below = depthStack + nchild - 1;
-    *needStack = std::max(*needStack, below + 1);
-    for (int k = 0; k < 4; ++k) {
-        if (grand[k] < 0) continue;
-        const DNode &g = bn[grand[k]];
-        d.lox[k] = g.lo[0]; d.loy[k] = g.lo[1]; d.loz[k] = g.lo[2];
-        d.hix[k] = g.hi0; d.hiy[k] = g.hi1; d.hiz[k] = g.hi2;
-        src[4 * (size_t)me + k] = grand[k];
-        d.child[k] = collapse(bn, grand[k], out, src, below, needStack);
+    out.assign((size_t)n4, DNode4());
+    src.assign(4 * (size_t)n4, -1);
+    for (size_t i = 0; i < n; ++i) {
+        if (id4[i] < 0) continue;
+        const WideCut cut = wide_cut(bn.data(), choice.data(), (int)i);
+        DNode4 d;
+        memset(&d, 0, sizeof(d));
+        d.order_lo = cut.order_lo; d.order_hi = cut.order_hi; d.codes = cut.codes;
+        for (int k = 0; k < 4; ++k) {
+            const int g = cut.slot[k];
+            if (g < 0) {   // absent children: inverted boxes, which fail every slab test
+                d.child[k] = kNode4Empty;
+                d.lox[k] = d.loy[k] = d.loz[k] = std::numeric_limits<float>::infinity();
+                d.hix[k] = d.hiy[k] = d.hiz[k] = -std::numeric_limits<float>::infinity();
+                continue;
+            }
+            const DNode &G = bn[g];
+            d.lox[k] = G.lo[0]; d.loy[k] = G.lo[1]; d.loz[k] = G.lo[2];
+            d.hix[k] = G.hi0; d.hiy[k] = G.hi1; d.hiz[k] = G.hi2;
+            src[4 * (size_t)id4[i] + k] = g;
+            d.child[k] = wide_is_leaf(G) ? leaf_ref(G) : id4[g];
+        }
+        out[id4[i]] = d;
     }
-    out[me] = d;
-    return me;
+    return 0;
 }
 }  // namespace
 
@@ -1078,6 +1084,8 @@ bool compile_scene(const gnxr_scene_desc *d, CompiledScene *cs, HlbvhBuildFn hlb
     bb.method = d->bvh_split_method;
     int root = d->bvh_split_method == GNXR_BVH_HLBVH ? bb.build_hlbvh(hlbvh_build) : bb.build(0, d->n_triangles);
     if (root < 0) return false;
+    for (const BuildNode &b : bb.nodes)   // (the HLBVH stage checks its own leaves; a host build reaches this with coincident centroids)
+        if (b.n > 0xffff) { set_error("a BVH leaf of %d primitives does not fit LinearBVHNode's 16-bit primitive count", b.n); return false; }
     cs->nodes.clear();
     cs->nodes.reserve(bb.nodes.size());
     cs->bvh_max_depth = 0;
@@ -1085,7 +1093,7 @@ bool compile_scene(const gnxr_scene_desc *d, CompiledScene *cs, HlbvhBuildFn hlb
     cs->nodes4.clear();
     cs->node4_src.clear();
     cs->stack4_need = 1;
-    cs->root4 = collapse(cs->nodes, 0, cs->nodes4, cs->node4_src, 0, &cs->stack4_need);
+    cs->root4 = collapse(cs->nodes, cs->nodes4, cs->node4_src, &cs->stack4_need);
     if (cs->nodes4.empty()) { cs->nodes4.push_back(DNode4()); cs->node4_src.assign(4, -1); }
     else if (cs->root4 >= 0) {
         // Renumber the 4-wide nodes: the top of the tree in breadth-first order (indices [0, kTopNodes): what the traversal kernel keeps in

@@ -34,21 +34,24 @@
 #pragma once
 #include "kernels.hip.h"
 #include "query_kernel.hip.h"
+#include "wide_collapse.h"
 
 namespace gnxr {
 
-// Hit children in visiting order.  The order byte of a node for one ray octant (4 x 2-bit child slots, nearest first) is one of 8
-// patterns, fixed by three bits: which half (children 0,1 or 2,3) comes first and whether each half is swapped (scene_compile.cpp:
-// collapse) -- bit 1 of slot 0, bit 0 of slot 0, bit 0 of slot 2.  order_entry(code, hitMask) = the slots that are hit, nearest first,
-// 2 bits each from bit 0 (their number is the mask's population count).  The 128 entries live in LDS (filled at kernel start).
+// Hit children in visiting order.  The order byte of a node for one ray octant (4 x 2-bit child slots, nearest first) is one of 16
+// patterns, named by the node's 4-bit code for that octant: the shape of the cut the children are (balanced or chain) and three near / far
+// decisions (wide_collapse.h).  order_entry(code, hitMask) = the slots that are hit, nearest first, 2 bits each from bit 0 (their number
+// is the mask's population count).  The 256 entries live in LDS (filled at kernel start).
 GX_DEV unsigned order_entry(unsigned code, unsigned hm) {
-    const unsigned base0 = (code & 4u) ? 2u : 0u, sw0 = (code >> 1) & 1u, sw1 = code & 1u, base1 = 2u - base0;
-    const unsigned ord[4] = {base0 + sw0, base0 + 1u - sw0, base1 + sw1, base1 + 1u - sw1};
+    const unsigned byte = wide_order_byte(code);
     unsigned e = 0, n = 0;
-    for (int i = 0; i < 4; ++i)
-        if ((hm >> ord[i]) & 1u) { e |= ord[i] << (2u * n); ++n; }
+    for (int i = 0; i < 4; ++i) {
+        const unsigned slot = (byte >> (2 * i)) & 3u;
+        if ((hm >> slot) & 1u) { e |= slot << (2u * n); ++n; }
+    }
     return e;
 }
+constexpr int kOrderTableBytes = 256;
 #ifndef GX_T4_CACHE
 #define GX_T4_CACHE 64
 #endif
@@ -77,7 +80,7 @@ GX_DEV int trace4_lds_dwords_per_thread(bool sph) { return kRayRecDwords + (sph 
 template <bool COUNT, bool SPH, bool SPILL, int Q = kT4Render>
 __global__ void GX_T4_BOUNDS k_trace4(DScene sc, typename Trace4Src<Q>::type pa, TraceWork w, unsigned int *cursor, Counters *ctr, int lds_entries, int *spill, int chunk, int n_top) {
     // LDS: [lds_entries * kBlock] stack columns | [(11 | 12) * kRqStride] ray records (SoA: field * kRqStride + wave * kRayQueue + slot) |
-    //      [8 * kTopCache float4] top-of-tree nodes, SoA by plane (plane * kTopCache + node: conflict-free across nodes) | [128 B] order table
+    //      [8 * kTopCache float4] top-of-tree nodes, SoA by plane (plane * kTopCache + node: conflict-free across nodes) | [kOrderTableBytes] order table
     extern __shared__ int smem[];
     typedef __attribute__((address_space(3))) float lds_float;
     lds_int *const stk = (lds_int *)&smem[threadIdx.x];
@@ -108,7 +111,7 @@ __global__ void GX_T4_BOUNDS k_trace4(DScene sc, typename Trace4Src<Q>::type pa,
         // these few nodes (tests/dev_stats.py): from LDS they cost a ds_read instead.
         const f4v *gn = reinterpret_cast<const f4v *>(sc.nodes4);
         for (int i = threadIdx.x; i < n_top * 8; i += kBlock) topN[(i & 7) * kTopCache + (i >> 3)] = gn[i];
-        if (threadIdx.x < 128) lut[threadIdx.x] = (unsigned char)order_entry(threadIdx.x >> 4, threadIdx.x & 15u);
+        if (threadIdx.x < kOrderTableBytes) lut[threadIdx.x] = (unsigned char)order_entry(threadIdx.x >> 4, threadIdx.x & 15u);
         __syncthreads();
     }
 
@@ -138,7 +141,7 @@ __global__ void GX_T4_BOUNDS k_trace4(DScene sc, typename Trace4Src<Q>::type pa,
     V3 ro, inv;
     float Sx = 0, Sy = 0, tMax = 0;
     unsigned oNX = 0, oNY = 16, oNZ = 32;   // byte offset of the near plane of each axis inside a DNode4 (far = 48 | 80 | 112 - near ... see below)
-    unsigned ordShift = 0;                  // bit offset of this octant's byte in the node's 64-bit order table
+    unsigned ordShift = 0;                  // bit offset of this octant's 4-bit code in the node's `codes`
     int cur = -1, toVisit = 0, leafOff = 0, leafN = 0, hitLeaf = -1;
     uint32_t cntNodes = 0, cntTris = 0, cntRetests = 0, cntNodesGlobal = 0;
 #ifdef GX_TRACE_STATS
@@ -156,7 +159,7 @@ __global__ void GX_T4_BOUNDS k_trace4(DScene sc, typename Trace4Src<Q>::type pa,
         hitLeaf = SPH ? rq[slot + 11 * kRqStride] : -1;
         const int neg0 = inv.x < 0, neg1 = inv.y < 0, neg2 = inv.z < 0;
         oNX = neg0 ? 48u : 0u; oNY = neg1 ? 64u : 16u; oNZ = neg2 ? 80u : 32u;   // lox 0 loy 16 loz 32 hix 48 hiy 64 hiz 80
-        ordShift = 8u * (unsigned)(neg0 | (neg1 << 1) | (neg2 << 2));
+        ordShift = 4u * (unsigned)(neg0 | (neg1 << 1) | (neg2 << 2));
         cur = ((pk >> 4) & 1) ? -1 : sc.root4; toVisit = 0; leafN = 0;
         live = true;
     };
@@ -376,22 +379,21 @@ __global__ void GX_T4_BOUNDS k_trace4(DScene sc, typename Trace4Src<Q>::type pa,
                 // ---- one 4-wide step: test the four children (Bounds3::IntersectP per box), continue with the first one hit in the
                 // reference's visiting order, push the others farthest first
                 f4v nX, fX, nY, fY, nZ, fZ, cf;
-                uint2 tb;
+                unsigned codes;
                 if (cur < n_top) {   // top of the tree: from the block's LDS copy
                     const lds_f4 *L = topN + cur;
                     nX = L[(oNX >> 4) * kTopCache]; fX = L[((48u - oNX) >> 4) * kTopCache];
                     nY = L[(oNY >> 4) * kTopCache]; fY = L[((80u - oNY) >> 4) * kTopCache];
                     nZ = L[(oNZ >> 4) * kTopCache]; fZ = L[((112u - oNZ) >> 4) * kTopCache];
                     cf = L[6 * kTopCache];
-                    const f4v t7 = L[7 * kTopCache];
-                    tb = make_uint2(__float_as_uint(t7.x), __float_as_uint(t7.y));
+                    codes = __float_as_uint(L[7 * kTopCache].z);
                 } else {
                     if (COUNT) cntNodesGlobal++;
                     const unsigned off = (unsigned)cur << 7;
 #define GX_LD4(o) (*reinterpret_cast<const f4v *>(nb + (unsigned)(off + (o))))
                     nX = GX_LD4(oNX); fX = GX_LD4(48u - oNX); nY = GX_LD4(oNY); fY = GX_LD4(80u - oNY); nZ = GX_LD4(oNZ); fZ = GX_LD4(112u - oNZ);
                     cf = GX_LD4(96u);
-                    tb = *reinterpret_cast<const uint2 *>(nb + (unsigned)(off + 112u));
+                    codes = *reinterpret_cast<const unsigned *>(nb + (unsigned)(off + 120u));
 #undef GX_LD4
                 }
                 const float k = 1 + 2 * GX_GAMMA(3);
@@ -431,8 +433,7 @@ __global__ void GX_T4_BOUNDS k_trace4(DScene sc, typename Trace4Src<Q>::type pa,
                 int next;
                 if (hitMask == 0) next = (toVisit == 0) ? -1 : pop(toVisit);
                 else {
-                    const unsigned word = (ordShift >= 32u ? tb.y : tb.x) >> (ordShift & 31u);   // this octant's order byte in the low bits
-                    const unsigned e = lut[((word & 3u) << 5) | (word & 16u) | hitMask];               // (slot0 bit 1, slot0 bit 0, slot2 bit 0, hit mask)
+                    const unsigned e = lut[(((codes >> ordShift) & 15u) << 4) | hitMask];   // (this octant's code, hit mask)
                     const int n = __popc(hitMask);
                     const int c0 = __float_as_int(cf.x), c1 = __float_as_int(cf.y), c2 = __float_as_int(cf.z), c3 = __float_as_int(cf.w);
                     auto child = [&](unsigned s) -> int { const int lo = (s & 1u) ? c1 : c0, hi = (s & 1u) ? c3 : c2; return (s & 2u) ? hi : lo; };
@@ -489,7 +490,9 @@ __global__ void GX_T4_BOUNDS k_trace4(DScene sc, typename Trace4Src<Q>::type pa,
                 shear.Sx = Sx; shear.Sy = Sy; shear.Sz = kz == 0 ? inv.x : (kz == 1 ? inv.y : inv.z);
                 V3 p0, p1, p2;
                 load_tri(tris, leafOff, &p0, &p1, &p2);
-                if (COUNT) cntTris++;
+#ifndef GX_COUNT_TRI_TESTS   // the counter is the triangles LOADED (what the byte model of bench.py charges), box-culled one-triangle leaves included;
+                if (COUNT) cntTris++;   // -DGX_COUNT_TRI_TESTS (development builds) counts the triangles TESTED: the same number for every collapse of one binary tree
+#endif
                 bool inBox = true;
                 if (fromVerts) {
                     const float4 b0 = make_float4(fminf(fminf(p0.x, p1.x), p2.x), fminf(fminf(p0.y, p1.y), p2.y), fminf(fminf(p0.z, p1.z), p2.z), fmaxf(fmaxf(p0.x, p1.x), p2.x));
@@ -497,6 +500,9 @@ __global__ void GX_T4_BOUNDS k_trace4(DScene sc, typename Trace4Src<Q>::type pa,
                     inBox = slab_test(b0, b1, ro, inv, neg, tMax);
                 }
                 more = leafN > 1;
+#ifdef GX_COUNT_TRI_TESTS
+                if (COUNT && inBox) cntTris++;
+#endif
                 TriHit h;
                 if (inBox && tri_test_sheared(p0, p1, p2, ro, shear, tMax, &h)) {
                     hitLeaf = leafOff;

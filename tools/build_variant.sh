@@ -10,9 +10,9 @@ cd $ROOT/gnxraytracer_amd/csrc
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-slp-vectorize -fno-unroll-loops -Wall -Wno-unused-variable -Wno-unused-function"
 OBJS=""
 if [ -n "$ALLTU" ]; then
-  for f in inst_whitted_tex inst_whitted inst_vol inst_shade_query inst_aov; do /opt/rocm/bin/hipcc $FLAGS $@ -c $f.hip -o $ROOT/build/${f}_$NAME.o & OBJS="$OBJS $ROOT/build/${f}_$NAME.o"; done
+  for f in inst_whitted_tex inst_whitted inst_vol inst_shade_query inst_shade_kinds inst_aov; do /opt/rocm/bin/hipcc $FLAGS $@ -c $f.hip -o $ROOT/build/${f}_$NAME.o & OBJS="$OBJS $ROOT/build/${f}_$NAME.o"; done
 else
-  OBJS="$ROOT/build/inst_whitted_tex.o $ROOT/build/inst_whitted.o $ROOT/build/inst_vol.o $ROOT/build/inst_shade_query.o $ROOT/build/inst_aov.o"
+  OBJS="$ROOT/build/inst_whitted_tex.o $ROOT/build/inst_whitted.o $ROOT/build/inst_vol.o $ROOT/build/inst_shade_query.o $ROOT/build/inst_shade_kinds.o $ROOT/build/inst_aov.o"
 fi
 /opt/rocm/bin/hipcc $FLAGS $@ -c api.hip -o $ROOT/build/api_$NAME.o
 wait
