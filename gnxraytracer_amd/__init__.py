@@ -506,6 +506,91 @@ class Scene:
             out[name] = a
         return out
 
+    def update_media(self, media, density=None, first_medium=0, stream=None):
+        """Replace media [first_medium, first_medium + len(media)) of the scene's medium list by `media` (gnxr Medium records, or one
+        record): coefficients, g, medium_to_world, the grid resolution and the type may all change (gnxr_scene_update_media).  density:
+        one array per GRID record of the call, in record order (a list, or the array itself when there is one such record); each a
+        float32 numpy array (host memory) or a contiguous float32 torch tensor on the scene's device, of shape (nz, ny, nx) or flat with
+        nx * ny * nz entries.  The records' density_offset is set here.  Host arrays are packed and sent in ONE call, which takes all
+        records or none.  Torch tensors are read where they lie, on `stream` (by default the current torch stream): no tensor is
+        concatenated or copied, so the records go one call each, in order (a GRID record with its tensor, a HOMOGENEOUS one alone) --
+        a record the library refuses leaves the earlier ones applied.  (The C call itself takes several device grids at once, as one
+        packed allocation with the offsets in the records; this method does not offer that form: a caller who needs several device grids
+        to change together calls gnxr_scene_update_media through lib().)  density=None changes coefficients only: every GRID record must then
+        name a medium that is GRID now, with the same resolution, whose grid stays.  Afterwards the scene renders as one created with
+        these media and grids; a refused call raises GnxrError and leaves the scene as it was."""
+        media = [media] if isinstance(media, Medium) else list(media)
+        for m in media:
+            if not isinstance(m, Medium):
+                raise ValueError(f"update_media: media must be gnxr Medium records, got {type(m).__name__}")
+        recs = (Medium * max(len(media), 1))()
+        for k, m in enumerate(media):
+            C.memmove(C.byref(recs[k]), C.byref(m), C.sizeof(Medium))
+        if density is None:
+            handle = _stream_handle("update_media", stream)
+            _check(lib().gnxr_scene_update_media(self._h, int(first_medium), len(media), recs, None, C.c_void_p(handle or None)))
+            return
+        is_torch = lambda x: type(x).__module__.split(".")[0] == "torch"
+        grids = [density] if isinstance(density, np.ndarray) or is_torch(density) else density
+        if not isinstance(grids, (list, tuple)):
+            raise ValueError(f"update_media: expected a numpy array, a torch tensor, a list of them or None, got {type(density).__name__}")
+        grid_recs = [k for k, m in enumerate(media) if m.type == _abi.MEDIUM_GRID]
+        if len(grids) != len(grid_recs):
+            raise ValueError(f"update_media: {len(grids)} density arrays for {len(grid_recs)} GRID records")
+        on_device = [is_torch(g) for g in grids]
+        if any(on_device) and not all(on_device):
+            raise ValueError("update_media: density arrays must be all numpy arrays or all torch tensors")
+        for g, k in zip(grids, grid_recs):
+            nx, ny, nz = recs[k].nx, recs[k].ny, recs[k].nz
+            shapes = ((nz, ny, nx), (nx * ny * nz,))
+            if isinstance(g, np.ndarray):
+                if g.dtype != np.float32 or tuple(g.shape) not in shapes:
+                    raise ValueError(f"update_media: expected a float32 array of shape {shapes[0]} or {shapes[1]}, got {g.dtype} {g.shape}")
+            elif is_torch(g):
+                import torch
+                if not (isinstance(g, torch.Tensor) and g.is_cuda and g.device.index == self.device and g.dtype == torch.float32 and
+                        tuple(g.shape) in shapes and g.is_contiguous()):
+                    raise ValueError(f"update_media: expected a contiguous float32 {shapes[0]} or {shapes[1]} tensor on cuda:{self.device}, got "
+                                     f"{getattr(g, 'dtype', None)} {tuple(getattr(g, 'shape', ()))} on {getattr(g, 'device', None)}")
+            else:
+                raise ValueError(f"update_media: expected a numpy array or a torch tensor, got {type(g).__name__}")
+        if not any(on_device):   # host memory: one packed array, one call
+            offsets = np.cumsum([0] + [g.size for g in grids])
+            packed = np.concatenate([np.ascontiguousarray(g).reshape(-1) for g in grids]) if grids else np.zeros(1, np.float32)
+            for k, off in zip(grid_recs, offsets):
+                recs[k].density_offset = int(off)
+            handle = _stream_handle("update_media", stream)
+            _check(lib().gnxr_scene_update_media(self._h, int(first_medium), len(media), recs, C.c_void_p(packed.ctypes.data), C.c_void_p(handle or None)))
+            return
+        import torch
+        if stream is None:
+            stream = torch.cuda.current_stream(grids[0].device)
+        handle = _stream_handle("update_media", stream)
+        tensor_of = dict(zip(grid_recs, grids))
+        for k in range(len(media)):
+            one = (Medium * 1)()
+            C.memmove(C.byref(one[0]), C.byref(recs[k]), C.sizeof(Medium))
+            one[0].density_offset = 0
+            ptr = tensor_of[k].data_ptr() if k in tensor_of else None
+            _check(lib().gnxr_scene_update_media(self._h, int(first_medium) + k, 1, one, C.c_void_p(ptr) if ptr else None, C.c_void_p(handle or None)))
+
+    def media_tables(self):
+        """Test hook: the medium tables of the first device (gnxr_scene_media_tables): {"records": the device's medium records as uint32
+        words, (n_media, 32), density_offset written as 0; "grids": one flat float32 array per medium, empty for a HOMOGENEOUS one}."""
+        n = C.c_int64(0)
+        _check(lib().gnxr_scene_media_tables(self._h, 0, 0, None, 0, C.byref(n)))
+        records = np.zeros((n.value // _abi.DMEDIUM_BYTES, _abi.DMEDIUM_BYTES // 4), np.uint32)
+        if n.value:
+            _check(lib().gnxr_scene_media_tables(self._h, 0, 0, C.c_void_p(records.ctypes.data), n.value, C.byref(n)))
+        grids = []
+        for i in range(len(records)):
+            _check(lib().gnxr_scene_media_tables(self._h, 1, i, None, 0, C.byref(n)))
+            g = np.zeros(n.value // 4, np.float32)
+            if n.value:
+                _check(lib().gnxr_scene_media_tables(self._h, 1, i, C.c_void_p(g.ctypes.data), n.value, C.byref(n)))
+            grids.append(g)
+        return {"records": records, "grids": grids}
+
     def set_camera(self, eye=(0, 0, 5), look=(0, 0, 0), up=(0, 1, 0), fov=90.0, lens_radius=0.0, focal_distance=3.0, orthographic=False, medium=-1):
         """The camera of SceneBuilder.set_camera (and the medium it sits in, -1 == none) for later renders."""
         cam = camera(eye, look, up, fov, lens_radius, focal_distance, orthographic)

@@ -96,7 +96,7 @@ struct CompiledScene {
     // media
     std::vector<gnxr_medium> media;
     std::vector<DMedium> dmedia;
-    std::vector<float> grid_density;
+    std::vector<float> grid_density;     // read by the upload at creation only; cleared by the first gnxr_scene_update_media (the devices hold the grids, dmedia their offsets)
     std::vector<DSphere> spheres;
     int n_spheres = 0;
     std::vector<int32_t> tri_media;      // leaf order, (inside, outside) per triangle; empty when no triangle is a medium boundary
@@ -137,6 +137,10 @@ void refit_world_bound(CompiledScene *cs, const float root6[6]);
 // one DLight from its description, as compile_scene makes it (gnxr_scene_update_lights): for AREA_TRI from the corners of its triangle and
 // its leaf index; for INFINITE the record without the environment tables; false (error set) for an unknown type
 bool compile_light(const gnxr_light &l, int index, const Vec3 corners[3], int tri_leaf, const Box3 &world_bound, DLight *out);
+// one DMedium from its description and, for a GRID medium, the maximum of its grid (GridDensityMedium.h:28-31: the fold from +0 over
+// std::max), as compile_scene makes it (gnxr_scene_update_media): sigma_t, w2m = Inverse(medium_to_world), inv_max_density = 1 / max_density.
+// density_offset is left 0: where the grid sits is the caller's.  false (error set) for an unknown type or an empty grid
+bool compile_medium(const gnxr_medium &m, int index, float max_density, DMedium *out);
 // the host's share of gnxr_scene_update_environment, whose tables the device builds (env_build_kernel.hip.h): MIPMap's power-of-two size,
 // the Lanczos weights of its resample (they depend on the two sizes only), the sizes of the pyramid's levels, and InfiniteAreaLight::Power's
 // lookup over the pyramid's top levels -- top_rgba[k] holds level first_level + k as float4 texels, first_level = max(0, levels - 3) --

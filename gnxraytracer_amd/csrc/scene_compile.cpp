@@ -1044,6 +1044,23 @@ void triangle_material(const int32_t *mat_map, int32_t authored, uint8_t own_att
     *class_key = (uint8_t)(own_attr ? 3 : (e[2] | (e[3] << kClassKeyKindShift)));   // (the attribute copy is class 3: no kind)
 }
 
+bool compile_medium(const gnxr_medium &m, int index, float max_density, DMedium *out) {
+    DMedium &dm = *out;
+    memset(&dm, 0, sizeof(dm));
+    dm.type = m.type; dm.nx = m.nx; dm.ny = m.ny; dm.nz = m.nz; dm.g = m.g;
+    memcpy(dm.sigma_a, m.sigma_a, 12); memcpy(dm.sigma_s, m.sigma_s, 12);
+    dm.sigma_t = m.sigma_a[0] + m.sigma_s[0];
+    if (m.type == GNXR_MEDIUM_GRID) {
+        if (m.nx <= 0 || m.ny <= 0 || m.nz <= 0) { set_error("medium %d: empty density grid", index); return false; }
+        Mat4 m2w;
+        for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) m2w.m[r][c] = m.medium_to_world[4 * r + c];
+        Mat4 inv = inverse(m2w);   // Transform(Matrix4x4) -> mInv = Inverse(m), Transform.h:110-112
+        for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) dm.w2m[4 * r + c] = inv.m[r][c];
+        dm.inv_max_density = 1 / max_density;
+    } else if (m.type != GNXR_MEDIUM_HOMOGENEOUS) { set_error("medium %d: unknown type %d", index, m.type); return false; }
+    return true;
+}
+
 // ------------------------------------------------------------------ compile
 bool compile_scene(const gnxr_scene_desc *d, CompiledScene *cs, HlbvhBuildFn hlbvh_build) {
     if (!d || d->abi_version != GNXR_ABI_VERSION) { set_error("scene description ABI version mismatch"); return false; }
@@ -1284,23 +1301,17 @@ bool compile_scene(const gnxr_scene_desc *d, CompiledScene *cs, HlbvhBuildFn hlb
     for (size_t i = 0; i < cs->media.size(); ++i) {
         const gnxr_medium &m = cs->media[i];
         DMedium &dm = cs->dmedia[i];
-        memset(&dm, 0, sizeof(dm));
-        dm.type = m.type; dm.nx = m.nx; dm.ny = m.ny; dm.nz = m.nz; dm.g = m.g;
-        memcpy(dm.sigma_a, m.sigma_a, 12); memcpy(dm.sigma_s, m.sigma_s, 12);
-        dm.sigma_t = m.sigma_a[0] + m.sigma_s[0];
-        if (m.type == GNXR_MEDIUM_GRID) {
-            if (m.nx <= 0 || m.ny <= 0 || m.nz <= 0) { set_error("medium %d: empty density grid", (int)i); return false; }
-            Mat4 m2w;
-            for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) m2w.m[r][c] = m.medium_to_world[4 * r + c];
-            Mat4 inv = inverse(m2w);   // Transform(Matrix4x4) -> mInv = Inverse(m), Transform.h:110-112
-            for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) dm.w2m[4 * r + c] = inv.m[r][c];
-            float maxDensity = 0;   // GridDensityMedium.h:28-31
+        const bool grid = m.type == GNXR_MEDIUM_GRID && m.nx > 0 && m.ny > 0 && m.nz > 0;   // (anything else is compile_medium's to refuse)
+        float maxDensity = 0;   // GridDensityMedium.h:28-31
+        if (grid) {
             const float *dd = cs->grid_density.data() + m.density_offset;
             for (int64_t k = 0; k < (int64_t)m.nx * m.ny * m.nz; ++k) maxDensity = std::max(maxDensity, dd[k]);
-            dm.inv_max_density = 1 / maxDensity;
+        }
+        if (!compile_medium(m, (int)i, maxDensity, &dm)) return false;
+        if (grid) {
             if (m.density_offset + (int64_t)m.nx * m.ny * m.nz >= (1ll << 31)) { set_error("medium %d: density grid too large", (int)i); return false; }
             dm.density_offset = (int32_t)m.density_offset;
-        } else if (m.type != GNXR_MEDIUM_HOMOGENEOUS) { set_error("medium %d: unknown type %d", (int)i, m.type); return false; }
+        }
     }
     cs->tri_media.clear();
     if (d->tri_medium_inside && d->tri_medium_outside) {

@@ -480,6 +480,37 @@ int gnxr_scene_triangle_materials(gnxr_scene *scene, int32_t *material_out, uint
  * record every render is given (sizes, transforms, bounding sphere, the marginal's integral); 9: the three floats of the Power lookup.
  * *n_bytes receives the table's size (0 for a scene without an INFINITE light); out is filled when given and capacity_bytes allows. */
 int gnxr_scene_env_tables(gnxr_scene *scene, int32_t which, void *out, int64_t capacity_bytes, int64_t *n_bytes);
+/* Replace medium records [first_medium, first_medium + n_media) of the scene's medium list (the numbering of gnxr_scene_desc.media) by
+ * media[0 .. n_media).  Every field may change: sigma_a, sigma_s, g, medium_to_world, the grid resolution and the type (HOMOGENEOUS <->
+ * GRID).  The number of media and the medium interfaces of triangles and spheres are fixed.  density is the source of the new grids:
+ * each GRID record's density_offset indexes into it (the meaning of gnxr_scene_desc.grid_density, local to this call; fp32, x fastest;
+ * ranges of two records may overlap or coincide).  density may be host memory or device memory of the scene's (first) device, told apart
+ * as gnxr_scene_update_vertices tells xyz apart; the read is ordered after what hip_stream holds (NULL: the null stream) and the kernel
+ * runs on that stream.  Each new grid is copied into a fresh packed grid buffer by one kernel that finds its maximum -- the fold from +0
+ * of GridDensityMedium.h:28-31, which skips NaNs and never yields -0 -- in the same pass; grids of media the call leaves alone are copied
+ * device to device.  Afterwards every result of the handle -- renders of all integrators, gnxr_li_device, gnxr_render_views_device,
+ * gnxr_render_aov_device, the queries, the ray counters and media_segments of gnxr_stats -- is bit for bit that of a scene created from
+ * the same description carrying these media and grids (tree aside).
+ * density == NULL is a coefficients-only edit: every GRID record of the call must name a medium that is GRID now, with the same nx, ny,
+ * nz; its grid and its maximum stay, its density_offset is ignored and no kernel runs.
+ * The call takes the handle's render lock.  Records are validated and compiled into a copy first, each device builds into a fresh buffer
+ * and no copy swaps until every copy has built, so a refused or failed call leaves the scene exactly as it was, on all devices.  It
+ * returns when every device holds the edit.  The BVH, materials, lights, the light-selection table, textures, environment tables, sampler
+ * tables, the camera (its medium index included) and the path state of gnxr_render_reserve stay where they are.  Besides the grids the
+ * medium records go to the device; one float per new grid (its maximum) comes back; no grid crosses the host when density is device
+ * memory.
+ * GNXR_ERR_INVALID, before any device is touched, for a null scene, a null media with n_media > 0, a range outside the scene's media, an
+ * unknown type, nx, ny or nz <= 0 on a GRID record, a density_offset that is negative or 2^60 or more with density != NULL, the density == NULL rule above,
+ * grids whose packed total (every grid starts 16-byte aligned) would reach 2^31 floats, and a density in device memory of a device other
+ * than the scene's first; GNXR_ERR_UNSUPPORTED for a scene created without media (the medium list is fixed); GNXR_ERR_OOM.  n_media == 0
+ * is a no-op. */
+int gnxr_scene_update_media(gnxr_scene *scene, int32_t first_medium, int32_t n_media, const gnxr_medium *media, const float *density, void *hip_stream);
+/* Test hook, read from the scene's first device.  which 0: the device's medium records of all media (`medium` ignored; 32 words per
+ * medium: type, nx, ny, nz, sigma_a, g, sigma_s, sigma_t, the world-to-medium matrix, 1 / the grid's maximum, then density_offset --
+ * written as 0: where a grid sits in the library's buffer is layout, not result -- and padding); which 1: the nx * ny * nz floats of
+ * grid `medium`, read through its record's offset (size 0 for a HOMOGENEOUS medium).  *n_bytes receives the size; out is filled when
+ * given and capacity_bytes allows.  GNXR_ERR_INVALID for null arguments, which outside {0, 1} or, with which 1, a medium outside the list. */
+int gnxr_scene_media_tables(gnxr_scene *scene, int32_t which, int32_t medium, void *out, int64_t capacity_bytes, int64_t *n_bytes);
 /* Replace the camera (and the medium it sits in, -1 == none) for later renders; same checks as gnxr_scene_create. */
 int gnxr_scene_set_camera(gnxr_scene *scene, const gnxr_camera *camera, int32_t camera_medium);
 
