@@ -338,6 +338,12 @@ class Scene:
                 self._env_light = Light()
                 C.memmove(C.byref(self._env_light), C.byref(d.lights[i]), C.sizeof(Light))
                 break
+        self._textures = []      # copies of the Texture records, texel_offset zeroed (update_textures keeps them current)
+        for i in range(int(d.n_textures)):
+            t = Texture()
+            C.memmove(C.byref(t), C.byref(d.textures[i]), C.sizeof(Texture))
+            t.texel_offset = 0
+            self._textures.append(t)
         _check(lib().gnxr_scene_create(C.byref(d), C.byref(self._h)))
 
     def close(self):
@@ -590,6 +596,124 @@ class Scene:
                 _check(lib().gnxr_scene_media_tables(self._h, 1, i, C.c_void_p(g.ctypes.data), n.value, C.byref(n)))
             grids.append(g)
         return {"records": records, "grids": grids}
+
+    TEXTURE_PARAMS = ("su", "sv", "du", "dv", "trilinear", "max_aniso", "wrap", "scale", "gamma")
+
+    def update_textures(self, images=None, first_texture=0, params=None, stream=None):
+        """Replace image textures [first_texture, first_texture + n) of the scene's texture list (gnxr_scene_update_textures).  images:
+        one array per replaced texture (a list, or the array itself when there is one): each an (h, w, 3) float32 numpy array (host
+        memory) or a contiguous float32 (h, w, 3) torch tensor on the scene's device, decoded texels with row 0 the top row; the size may
+        differ from the old texture's.  params: per texture a dict of the keywords of SceneBuilder.add_image_texture (su, sv, du, dv,
+        trilinear, max_aniso, wrap, scale, gamma), or one dict when there is one texture; omitted keys keep the texture's current
+        value.  The Scene keeps a copy of every record, as created and as edited.  Host arrays are packed and sent in ONE call, which
+        takes all textures or none.  Torch tensors are read where they lie, on `stream` (by default the current torch stream): no tensor
+        is concatenated or copied, so the textures go one call each, in order -- a texture the library refuses leaves the earlier ones
+        applied.  (The C call itself takes several device textures at once, as one packed allocation with the offsets in the records;
+        this method does not offer that form: a caller who needs several device textures to change together calls
+        gnxr_scene_update_textures through lib().)  images=None changes parameters only: su, sv, du, dv, max_aniso and trilinear; wrap,
+        gamma and scale are baked into the texels and must then stay as they are (GnxrError otherwise: send the image).  The pyramids are
+        built on the device and every later result is that of a scene created with these textures; a refused call raises GnxrError and
+        leaves the scene as it was."""
+        is_torch = lambda x: type(x).__module__.split(".")[0] == "torch"
+        if images is None:
+            imgs = None
+        elif isinstance(images, np.ndarray) or is_torch(images):
+            imgs = [images]
+        elif isinstance(images, (list, tuple)):
+            imgs = list(images)
+        else:
+            raise ValueError(f"update_textures: expected a numpy array, a torch tensor, a list of them or None, got {type(images).__name__}")
+        if params is None:
+            plist = None
+        elif isinstance(params, dict):
+            plist = [params]
+        elif isinstance(params, (list, tuple)):
+            plist = list(params)
+        else:
+            raise ValueError(f"update_textures: params must be a dict, a list of dicts or None, got {type(params).__name__}")
+        if imgs is None and plist is None:
+            raise ValueError("update_textures: neither images nor params given")
+        n = len(imgs) if imgs is not None else len(plist)
+        if plist is not None and len(plist) != n:
+            raise ValueError(f"update_textures: {len(plist)} parameter dicts for {n} images")
+        first_texture = int(first_texture)
+        if first_texture < 0 or first_texture + n > len(self._textures):
+            raise ValueError(f"update_textures: textures [{first_texture}, {first_texture + n}) outside the scene's {len(self._textures)} textures")
+        recs = (Texture * max(n, 1))()
+        for k in range(n):
+            C.memmove(C.byref(recs[k]), C.byref(self._textures[first_texture + k]), C.sizeof(Texture))
+            for key, v in ((plist[k] or {}) if plist is not None else {}).items():
+                if key not in self.TEXTURE_PARAMS:
+                    raise ValueError(f"update_textures: unknown texture parameter {key!r} (expected one of {', '.join(self.TEXTURE_PARAMS)})")
+                if key == "wrap":
+                    if v not in ("repeat", "black", "clamp"):
+                        raise ValueError(f"update_textures: wrap must be 'repeat', 'black' or 'clamp', got {v!r}")
+                    recs[k].wrap = {"repeat": 0, "black": 1, "clamp": 2}[v]
+                elif key in ("trilinear", "gamma"):
+                    setattr(recs[k], key, int(bool(v)))
+                else:
+                    setattr(recs[k], key, float(v))
+        on_device = [is_torch(g) for g in imgs] if imgs is not None else []
+        if any(on_device) and not all(on_device):
+            raise ValueError("update_textures: images must be all numpy arrays or all torch tensors")
+        for k, g in enumerate(imgs or []):
+            if isinstance(g, np.ndarray):
+                if g.dtype != np.float32 or g.ndim != 3 or g.shape[2] != 3 or g.shape[0] < 1 or g.shape[1] < 1:
+                    raise ValueError(f"update_textures: expected a float32 array of shape (h, w, 3), got {g.dtype} {g.shape}")
+            elif is_torch(g):
+                import torch
+                if not (isinstance(g, torch.Tensor) and g.is_cuda and g.device.index == self.device and g.dtype == torch.float32 and
+                        g.dim() == 3 and g.shape[2] == 3 and g.shape[0] >= 1 and g.shape[1] >= 1 and g.is_contiguous()):
+                    raise ValueError(f"update_textures: expected a contiguous float32 (h, w, 3) tensor on cuda:{self.device}, got "
+                                     f"{getattr(g, 'dtype', None)} {tuple(getattr(g, 'shape', ()))} on {getattr(g, 'device', None)}")
+            else:
+                raise ValueError(f"update_textures: expected a numpy array or a torch tensor, got {type(g).__name__}")
+            recs[k].height, recs[k].width = int(g.shape[0]), int(g.shape[1])
+
+        def keep(k):
+            C.memmove(C.byref(self._textures[first_texture + k]), C.byref(recs[k]), C.sizeof(Texture))
+            self._textures[first_texture + k].texel_offset = 0
+
+        if imgs is None or not any(on_device):   # parameters only, or host memory: one packed array, one call
+            packed = None
+            if imgs:
+                offsets = np.cumsum([0] + [g.size for g in imgs])
+                packed = np.concatenate([np.ascontiguousarray(g).reshape(-1) for g in imgs])
+                for k in range(n):
+                    recs[k].texel_offset = int(offsets[k])
+            handle = _stream_handle("update_textures", stream)
+            _check(lib().gnxr_scene_update_textures(self._h, first_texture, n, recs, C.c_void_p(packed.ctypes.data) if packed is not None else None,
+                                                    C.c_void_p(handle or None)))
+            for k in range(n):
+                keep(k)
+            return
+        import torch
+        if stream is None:
+            stream = torch.cuda.current_stream(imgs[0].device)
+        handle = _stream_handle("update_textures", stream)
+        for k in range(n):
+            one = (Texture * 1)()
+            C.memmove(C.byref(one[0]), C.byref(recs[k]), C.sizeof(Texture))
+            one[0].texel_offset = 0
+            _check(lib().gnxr_scene_update_textures(self._h, first_texture + k, 1, one, C.c_void_p(imgs[k].data_ptr()), C.c_void_p(handle or None)))
+            keep(k)
+
+    def texture_tables(self):
+        """Test hook: the texture tables of the first device (gnxr_scene_texture_tables): {"records": the device's texture records as
+        uint32 words, (n_textures, 28); "texels": one flat float32 array per texture, the float4 (rgb_) texels of all its levels}."""
+        n = C.c_int64(0)
+        _check(lib().gnxr_scene_texture_tables(self._h, 0, 0, None, 0, C.byref(n)))
+        records = np.zeros((n.value // _abi.DTEXTURE_BYTES, _abi.DTEXTURE_BYTES // 4), np.uint32)
+        if n.value:
+            _check(lib().gnxr_scene_texture_tables(self._h, 0, 0, C.c_void_p(records.ctypes.data), n.value, C.byref(n)))
+        texels = []
+        for i in range(len(records)):
+            _check(lib().gnxr_scene_texture_tables(self._h, 1, i, None, 0, C.byref(n)))
+            t = np.zeros(n.value // 4, np.float32)
+            if n.value:
+                _check(lib().gnxr_scene_texture_tables(self._h, 1, i, C.c_void_p(t.ctypes.data), n.value, C.byref(n)))
+            texels.append(t)
+        return {"records": records, "texels": texels}
 
     def set_camera(self, eye=(0, 0, 5), look=(0, 0, 0), up=(0, 1, 0), fov=90.0, lens_radius=0.0, focal_distance=3.0, orthographic=False, medium=-1):
         """The camera of SceneBuilder.set_camera (and the medium it sits in, -1 == none) for later renders."""

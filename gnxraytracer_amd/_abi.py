@@ -19,6 +19,7 @@ DIRECT_SAMPLE_ALL, DIRECT_SAMPLE_ONE = 0, 1
 LIGHTS_SPATIAL, LIGHTS_UNIFORM, LIGHTS_POWER = 0, 1, 2
 MEDIUM_HOMOGENEOUS, MEDIUM_GRID = 1, 2
 DMEDIUM_BYTES = 128   # one record of gnxr_scene_media_tables(which = 0): sizeof(DMedium), csrc/gnxr_device_types.h
+DTEXTURE_BYTES = 112   # one record of gnxr_scene_texture_tables(which = 0): sizeof(DTexture), csrc/gnxr_device_types.h
 # flags of gnxr_scene_update_vertices_ex
 UPDATE_MOVE_LIGHTS = 1
 
@@ -152,6 +153,8 @@ PROTOTYPES = {
     "gnxr_scene_env_tables": (C.c_int, [VP, i32, VP, i64, P(i64)]),   # scene, which, out, capacity in bytes, size in bytes
     "gnxr_scene_update_media": (C.c_int, [VP, i32, i32, P(Medium), VP, VP]),   # scene, first, n, records, host or device fp32 grids (or NULL), hipStream_t
     "gnxr_scene_media_tables": (C.c_int, [VP, i32, i32, VP, i64, P(i64)]),   # scene, which, medium, out, capacity in bytes, size in bytes
+    "gnxr_scene_update_textures": (C.c_int, [VP, i32, i32, P(Texture), VP, VP]),   # scene, first, n, records, host or device fp32 texels (or NULL), hipStream_t
+    "gnxr_scene_texture_tables": (C.c_int, [VP, i32, i32, VP, i64, P(i64)]),   # scene, which, texture, out, capacity in bytes, size in bytes
     "gnxr_scene_update_materials": (C.c_int, [VP, i32, i32, P(Material)]),
     "gnxr_scene_set_triangle_materials": (C.c_int, [VP, i32, i32, VP, VP]),   # scene, first, n, host or device int32 ids, hipStream_t
     "gnxr_scene_triangle_materials": (C.c_int, [VP, P(i32), P(C.c_uint8), C.c_int64]),

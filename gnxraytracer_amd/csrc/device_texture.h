@@ -6,7 +6,8 @@
 //   camera offset rays, ScaleDifferentials           camera/Perspective.cpp:86-110, core/Geometry.h:874-880, core/Integrator.cpp:283
 //   SpecularReflect / SpecularTransmit differentials core/Integrator.cpp:335-354, 376-436
 // The pyramid (y flip, convertIn, Lanczos resample, box filter) and the EWA weight table are built on the host
-// (scene_compile.cpp build_textures).  PathIntegrator slices the camera RayDifferential to a Ray (PathIntegrator.cpp:67), so
+// (scene_compile.cpp build_textures) when the scene is created; gnxr_scene_update_textures builds the same pyramid on the
+// device (texture_build_kernel.hip.h).  PathIntegrator slices the camera RayDifferential to a Ray (PathIntegrator.cpp:67), so
 // under Path every lookup is unfiltered (zero differentials); VolPath filters at the camera ray's first surface vertex;
 // Whitted / DirectLighting carry the differentials along their specular chains.
 #pragma once

@@ -64,7 +64,8 @@ struct CompiledScene {
     std::vector<DMaterial> materials;
     std::vector<DMaterial> materials_single;   // allowMultipleLobes == false (Whitted)
     std::vector<DTexture> textures;            // image textures: parameters + level offsets into tex_texels
-    std::vector<float> tex_texels;             // float4 (rgb_) per texel, all levels of all textures
+    std::vector<float> tex_texels;             // float4 (rgb_) per texel, all levels of all textures; read by the upload at creation only, cleared by the first gnxr_scene_update_textures with texels (the devices hold them, `textures` their offsets)
+    std::vector<gnxr_texture> desc_textures;   // gnxr_scene_desc::textures with texel_offset zeroed (the raw texels are not retained): what a parameters-only texture edit compares against
     std::vector<float> ewa_lut;                // MIPMap::weightLut
     std::vector<float> tri_uv;                 // empty, or 8 floats per leaf-order triangle: (u,v) x 3 corners + pad
     std::vector<float> tri_n;                  // empty, or 12 floats per leaf-order triangle: 3 shading normals + pad (zeros == none)
@@ -150,6 +151,10 @@ int env_round_up_pow2(int v);
 std::vector<EnvResampleWeight> env_resample_weights(int old_res, int new_res);
 void env_pyramid_sizes(int rx, int ry, std::vector<int> *lw, std::vector<int> *lh);
 void env_power_from_top_levels(int rx, int ry, int first_level, const std::vector<std::vector<float>> &top_rgba, float out[3]);
+// one DTexture from its description, as build_textures makes it (gnxr_scene_update_textures, whose pyramid the device builds): the
+// power-of-two size, the number of levels and the mapping; level_offset counts from `first_texel`, the levels following each other
+// without padding.  *n_texels receives the texels of all levels.  false (error set) for a size <= 0, an unknown wrap or more than 16 levels
+bool compile_texture(const gnxr_texture &t, int index, int64_t first_texel, DTexture *out, int64_t *n_texels);
 DCamera make_camera(const gnxr_camera &c, int W, int H, int medium);      // camera/Perspective.cpp:114-135, core/Camera.h:54-75
 DHalton make_halton(int W, int H);                                          // samplers/HaltonSampler.cpp:33-60
 // light-selection table: dense restatement of core/LightDistribution.cpp (uniform / power / spatial)

@@ -8,6 +8,7 @@
 //   camera         camera/Perspective.cpp:114-135 + core/Camera.h:54-75
 //   env light      MIPMap level 0 + Distribution2D (lights/InfiniteAreaLight.cpp:12-82, core/MIPMap.h:85-198)
 // Pure host code.
+#include <chrono>
 #include <cstdio>
 #include <thread>
 
@@ -887,7 +888,7 @@ static float inverse_gamma_correct(float value) {   // core/GNXRayTracer.h:367-3
     return std::pow((value + 0.055f) * 1.f / 1.055f, (float)2.4f);
 }
 static bool build_textures(const gnxr_scene_desc *d, CompiledScene *cs) {
-    cs->textures.clear(); cs->tex_texels.clear(); cs->ewa_lut.clear();
+    cs->textures.clear(); cs->tex_texels.clear(); cs->ewa_lut.clear(); cs->desc_textures.clear();
     if (d->n_textures <= 0) return true;
     if (!d->textures || !d->texels) { set_error("textures without texel data"); return false; }
     cs->ewa_lut.resize(128);
@@ -971,7 +972,31 @@ static bool build_textures(const gnxr_scene_desc *d, CompiledScene *cs) {
             prev.swap(cur); pw = sRes; ph = tRes;
         }
         cs->textures.push_back(dt);
+        cs->desc_textures.push_back(t);
+        cs->desc_textures.back().texel_offset = 0;
     }
+    return true;
+}
+bool compile_texture(const gnxr_texture &t, int index, int64_t first_texel, DTexture *out, int64_t *n_texels) {
+    if (t.width <= 0 || t.height <= 0) { set_error("texture %d: invalid size %d x %d", index, t.width, t.height); return false; }
+    if (t.wrap < GNXR_WRAP_REPEAT || t.wrap > GNXR_WRAP_CLAMP) { set_error("texture %d: unknown wrap mode %d", index, t.wrap); return false; }
+    if (t.width > 32768 || t.height > 32768) { set_error("texture %d: more than 16 MIP levels", index); return false; }   // (before the rounding, which overflows above 2^30)
+    int rx = t.width, ry = t.height;
+    if ((rx & (rx - 1)) || (ry & (ry - 1))) { rx = round_up_pow2(rx); ry = round_up_pow2(ry); }
+    DTexture dt;
+    memset(&dt, 0, sizeof(dt));
+    dt.w0 = rx; dt.h0 = ry; dt.wrap = t.wrap; dt.trilinear = t.trilinear; dt.max_aniso = t.max_aniso;
+    dt.su = t.su; dt.sv = t.sv; dt.du = t.du; dt.dv = t.dv;
+    int nLevels = 1;
+    for (int m = std::max(rx, ry); m > 1; m >>= 1) ++nLevels;
+    dt.n_levels = nLevels;
+    int64_t at = first_texel;
+    for (int i = 0, w = rx, h = ry; i < nLevels; ++i, w = std::max(1, w / 2), h = std::max(1, h / 2)) {
+        dt.level_offset[i] = (int32_t)at;   // (the caller refuses a packed total of 2^31 texels or more)
+        at += (int64_t)w * h;
+    }
+    *out = dt;
+    *n_texels = at - first_texel;
     return true;
 }
 
@@ -1077,7 +1102,13 @@ bool compile_scene(const gnxr_scene_desc *d, CompiledScene *cs, HlbvhBuildFn hlb
     // (compile_materials applies these two checks again, for the edits; creation keeps them here as well so that a bad reference is refused
     // before the textures and the tree are built and the order in which errors are reported stays what it was)
     for (int i = 0; i < d->n_materials; ++i) if (!material_textures_ok(d->materials[i], i, d->n_textures)) return false;
-    if (!build_textures(d, cs)) return false;
+    {   // GNXR_VERBOSE: the host's time in the pyramids (tests/dev_texture_update_time.py reads the line)
+        const auto t0 = std::chrono::steady_clock::now();
+        if (!build_textures(d, cs)) return false;
+        if (d->n_textures > 0 && getenv("GNXR_VERBOSE"))
+            fprintf(stderr, "[gnxr] build_textures: %d textures, %zu texels, %.3f ms on the host\n", d->n_textures, cs->tex_texels.size() / 4,
+                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    }
     for (int i = 0; i < d->n_spheres; ++i) if (!sphere_material_ok(d->materials, d->n_materials, d->spheres[i].material, i)) return false;
     for (int i = 0; i < 3 * d->n_triangles; ++i)
         if (d->indices[i] < 0 || d->indices[i] >= d->n_vertices) { set_error("triangle index out of range"); return false; }

@@ -453,7 +453,7 @@ int gnxr_scene_rebuild_bvh(gnxr_scene *scene, void *hip_stream);
 /* Replace material records [first_material, first_material + n_materials) of the scene's material list (the numbering of
  * gnxr_scene_desc.materials) by materials[0 .. n_materials).  Every field may change, the type included: MATTE -> GLASS changes which shade
  * kernels the next render launches, a BSDF material -> GNXR_MAT_NONE turns its triangles (and spheres) into medium boundaries, and back;
- * kd_texture / ks_texture may name any texture the scene was created with.  The number of materials and the set of textures are fixed.
+ * kd_texture / ks_texture may name any texture the scene was created with.  The number of materials and the number of textures are fixed.
  * Afterwards every result of the handle -- renders of all integrators, gnxr_li_device, gnxr_render_views_device, gnxr_render_aov_device,
  * gnxr_bsdf_device, the ray queries, the ray counters of gnxr_stats -- is bit for bit that of a scene created from the same description
  * carrying the edited records (tree aside: it keeps its topology).  The records are validated as gnxr_scene_create validates them
@@ -511,6 +511,43 @@ int gnxr_scene_update_media(gnxr_scene *scene, int32_t first_medium, int32_t n_m
  * grid `medium`, read through its record's offset (size 0 for a HOMOGENEOUS medium).  *n_bytes receives the size; out is filled when
  * given and capacity_bytes allows.  GNXR_ERR_INVALID for null arguments, which outside {0, 1} or, with which 1, a medium outside the list. */
 int gnxr_scene_media_tables(gnxr_scene *scene, int32_t which, int32_t medium, void *out, int64_t capacity_bytes, int64_t *n_bytes);
+/* Replace texture records [first_texture, first_texture + n_textures) of the scene's texture list (the numbering of
+ * gnxr_scene_desc.textures) by textures[0 .. n_textures).  Every field may change: width, height, the mapping (su, sv, du, dv),
+ * max_aniso, scale, trilinear, wrap, gamma -- and with them the padded size and the number of MIP levels.  The number of textures is
+ * fixed, and so is which material references which texture (gnxr_scene_update_materials changes that).  texels is the source: each
+ * record's texel_offset indexes into it (the meaning of gnxr_scene_desc.texels, local to this call: RGB fp32, width * height * 3, row 0
+ * the TOP row; ranges of two records may overlap or coincide).  texels may be host memory or device memory of the scene's (first)
+ * device, told apart as gnxr_scene_update_media tells density apart; the read is ordered after what hip_stream holds (NULL: the null
+ * stream) and the kernels run on that stream.  The pyramid is built on the device as gnxr_scene_create builds it on the host -- y flip,
+ * convertIn (scale, inverse gamma), the Lanczos resample to powers of two under the wrap mode, the clamp, the box-filtered levels through
+ * MIPMap::Texel -- into a fresh packed texel buffer (textures in index order, levels 0 .. n - 1 of each in order, no padding); textures
+ * the call leaves alone are copied device to device.  Afterwards every result of the handle -- renders of all integrators,
+ * gnxr_li_device, gnxr_render_views_device, gnxr_render_aov_device, gnxr_bsdf_device with and without differentials, the ray counters of
+ * gnxr_stats -- is bit for bit that of a scene created from the same description carrying these records and texels (tree aside), and
+ * the device's texture records and texels are byte for byte that scene's.  Texels are finite: NaN and infinite values are outside what
+ * is pinned.
+ * texels == NULL is a parameters-only edit: su, sv, du, dv, max_aniso and trilinear may change; width, height, wrap, gamma and scale are
+ * baked into the texels and must equal the texture's current values (GNXR_ERR_INVALID otherwise: send the texels); texel_offset is
+ * ignored, no kernel runs and only the texture records are written.
+ * The call takes the handle's render lock.  Records are validated and compiled into a copy first, each device builds into a fresh buffer
+ * and no copy swaps until every copy has built; the texture records and the address of the new buffer are written last and the old ones
+ * put back if that fails, so a refused or failed call leaves the scene exactly as it was, on all devices.  It returns when every device
+ * holds the edit.  The EWA weight table, the BVH, the materials and their shade classes, lights, the light-selection table, media,
+ * environment tables, sampler tables, the camera and the path state of gnxr_render_reserve stay where they are.  Besides the texels the
+ * Lanczos weights of a resampled texture and the texture records go to the device; nothing comes back, and no texel crosses the host
+ * when texels is device memory.
+ * GNXR_ERR_INVALID, before any device is touched, for a null scene, a null textures with n_textures > 0, a range outside the scene's
+ * textures, width or height <= 0, an unknown wrap, more than 16 MIP levels (a side above 32768), a texel_offset that is negative or 2^60
+ * or more with texels != NULL, the texels == NULL rule above, a packed total of 2^31 texels or more, and texels in device memory of a
+ * device other than the scene's first; GNXR_ERR_UNSUPPORTED for a scene created without textures (the texture list is fixed);
+ * GNXR_ERR_OOM.  n_textures == 0 is a no-op. */
+int gnxr_scene_update_textures(gnxr_scene *scene, int32_t first_texture, int32_t n_textures, const gnxr_texture *textures, const float *texels, void *hip_stream);
+/* Test hook, read from the scene's first device.  which 0: the device's texture records of all textures (`texture` ignored; 28 words per
+ * texture: n_levels, the padded w0 and h0, wrap, trilinear, max_aniso, su, sv, du, dv, the first texel of each of 16 levels in the
+ * packed buffer, two words of padding); which 1: the float4 (rgb_) texels of all levels of texture `texture`, level after level, each
+ * read through its record's offset.  *n_bytes receives the size; out is filled when given and capacity_bytes allows.  GNXR_ERR_INVALID
+ * for null arguments, which outside {0, 1} or, with which 1, a texture outside the list. */
+int gnxr_scene_texture_tables(gnxr_scene *scene, int32_t which, int32_t texture, void *out, int64_t capacity_bytes, int64_t *n_bytes);
 /* Replace the camera (and the medium it sits in, -1 == none) for later renders; same checks as gnxr_scene_create. */
 int gnxr_scene_set_camera(gnxr_scene *scene, const gnxr_camera *camera, int32_t camera_medium);
 
