@@ -42,6 +42,9 @@ GX_VOL_INSTANCES(X)
 #define X(M, L) extern template GX_SHADE_KIND_SIGNATURE(M, L)
 GX_SHADE_KIND_INSTANCES(X)
 #undef X
+#define X(M, L, S) extern template GX_SHADE_MIS_SIGNATURE(M, L, S)
+GX_SHADE_MIS_INSTANCES(X)
+#undef X
 // compiled in inst_shade_query.hip
 extern template GX_BSDF_QUERY_SIGNATURE(LM_ALL)
 extern template GX_LIGHT_SAMPLE_QUERY_SIGNATURE(LT_ALL)

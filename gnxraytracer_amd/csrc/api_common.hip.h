@@ -99,6 +99,16 @@ struct Knobs {
     // GNXR_NO_NARROW_SHADE: set = the queues of the kinds launch k_shade<LM_GLOSSY> instead of their narrow kernels (experiment: the split
     // without the specialisation; default unset).  Per call (render)
     static bool no_narrow_shade() { return env_set("GNXR_NO_NARROW_SHADE"); }
+    // GNXR_NO_MIS_DEFER: set = a scene lit by area lights alone is shaded by k_shade<LM, LT_AREA> as every other scene, not by the kernels with
+    // the MIS half of EstimateDirect reordered (SM_DIR_FIRST / SM_DEFER; same image and counts bit for bit: the A/B and test switch; default
+    // unset).  Per call (render)
+    static bool no_mis_defer() { return env_set("GNXR_NO_MIS_DEFER"); }
+    // GNXR_MIS_DEFER_STEP: 1 = direction first only (SM_DIR_FIRST), 2 = and the rare vertices deferred to a list per wave (SM_DEFER)
+    // (experiment: each step's A/B; default 2).  Per call (render)
+    static int mis_defer_step() { const int v = env_int("GNXR_MIS_DEFER_STEP", 2); return v == 1 ? 1 : 2; }
+    // GNXR_MIS_DEFER_DRAIN_AT: entries of a wave's list at which the wave drains it between two vertices, 1 .. 64 (default 64; small values
+    // let tests reach the drains inside the loop).  Per call (render)
+    static int mis_defer_drain_at() { return std::max(1, std::min(64, env_int("GNXR_MIS_DEFER_DRAIN_AT", 64))); }
     // GNXR_HOST_LIGHT_GRID: set = the spatial light table is built on the host (default unset).  Per call (ensure_grid)
     static bool host_light_grid() { return env_set("GNXR_HOST_LIGHT_GRID"); }
     // GNXR_BINARY_BVH: set = the scene renders on the binary tree, never the 4-wide one (default unset).  Per call (scene creation)

@@ -362,6 +362,8 @@ struct RenderRun {
     // counting: bit 1 = on the reference's binary tree, bit 2 = on the timed (4-wide) walk + the medium kernel's tracking steps
     const bool timing = (g_profiling & 1) != 0, count_wide = (g_profiling & 4) != 0, counting = (g_profiling & 2) != 0 && !count_wide;
     bool spheres;
+    // shade_stage, where the lights are all area lights: 0 = k_shade<LM, LT_AREA>, 1 = SM_DIR_FIRST, 2 = SM_DEFER; the list's drain threshold
+    const int mis_mode = Knobs::no_mis_defer() ? 0 : Knobs::mis_defer_step(), mis_drain_at = Knobs::mis_defer_drain_at();
     bool list_media = false;   // VolPath with caller rays (each names a medium) or views in different media: raygen marks the slots that start inside one
     int n_lights, n_scene_media;
     unsigned long long rays_closest = 0, rays_any = 0, rays_mis = 0, media_segments = 0;
@@ -456,6 +458,8 @@ static int compact_stalled(const Counters &c) {
     return GNXR_ERR_RUNTIME;
 }
 
+constexpr size_t kShadeLdsBudget = 52 * 1024;   // LDS of a k_shade block that runs three to a CU (160 KB; the rest is allocation slack)
+
 // PathIntegrator::Li at the vertices the last trace found: class binning, one k_shade per class, queue compaction.  What they spawned is
 // counted on the device.  `n` bounds the number of queued paths (it sizes the launches); the count itself is read through n_dev.
 // Returns the status of the fork / join of the class streams; the launches themselves are checked once per loop turn (run_path_loop).
@@ -496,18 +500,32 @@ int RenderRun::shade_stage(const int *q_in, int n, int *q_out, const unsigned *n
         cst[1] = s->aux_stream[0]; cst[2] = s->aux_stream[1]; cst[3] = s->aux_stream[1];
     }
     const bool area_only = pl.area_only, area_env_only = pl.area_env_only;
-#define GX_SHADE_K(K, C) hipLaunchKernelGGL(K, g, b, slds, cst[C], sc, r, pa, (const int *)qc[C], (const unsigned int *)&dctr->q_class[C], sdims, snperm, lmats, llights)
+#define GX_SHADE_KA(K, C, LDS, LL) hipLaunchKernelGGL(K, g, b, LDS, cst[C], sc, r, pa, (const int *)qc[C], (const unsigned int *)&dctr->q_class[C], sdims, snperm, lmats, LL)
+#define GX_SHADE_K(K, C) GX_SHADE_KA(K, C, slds, llights)
 #define GX_SHADE(LMV, LTV, C) do { if (spheres) GX_SHADE_K((k_shade<LMV, LTV, true>), C); else GX_SHADE_K((k_shade<LMV, LTV, false>), C); } while (0)
+    // area lights only: the kernels with the MIS half of EstimateDirect reordered (mis_step, above; 0: k_shade<LM, LT_AREA>, the same bits)
+#define GX_SHADE_AREA_S(LMV, SPHV, C) do { \
+        if (mis_step == 2) GX_SHADE_KA((k_shade<LMV, LT_AREA | SM_DEFER, SPHV>), C, slds_mis, llights_mis); \
+        else if (mis_step == 1) GX_SHADE_K((k_shade<LMV, LT_AREA | SM_DIR_FIRST, SPHV>), C); \
+        else GX_SHADE_K((k_shade<LMV, LT_AREA, SPHV>), C); } while (0)
+#define GX_SHADE_AREA(LMV, C) do { if (spheres) GX_SHADE_AREA_S(LMV, true, C); else GX_SHADE_AREA_S(LMV, false, C); } while (0)
 #define GX_SHADE_TEX(LTV) do { if (spheres) GX_SHADE_K((k_shade<LM_ALL, LTV, true, true>), 3); else GX_SHADE_K((k_shade<LM_ALL, LTV, false, true>), 3); } while (0)
     // BASELINE config 4's light set (area lights + one InfiniteAreaLight) has kernels without the delta-light and sky-box code
     const int light_set = area_only ? 0 : ((area_env_only && !spheres && !(pl.class_mask & 8)) ? 1 : 2);
+    // Area lights alone: the MIS half of EstimateDirect direction first (k_shade's SM_DIR_FIRST), and its rare vertices on a list per wave in
+    // LDS (SM_DEFER) where the lists fit beside the tables: three blocks per CU share 160 KB, so a block has kShadeLdsBudget.  Where they
+    // do not (more than a handful of materials in LDS) the plan falls back to SM_DIR_FIRST.
+    int mis_step = light_set == 0 ? mis_mode : 0;
+    const size_t slds_mis = slds + (size_t)(kBlock / 64) * ((size_t)kMisEntryWords * kMisCap + 1) * sizeof(int);
+    const int llights_mis = llights | (std::min(mis_drain_at, kMisCap) << 8);
+    if (mis_step == 2 && slds_mis > kShadeLdsBudget) mis_step = 1;
 #define GX_SHADE_LM(LMV, C) do { \
-        if (light_set == 0) GX_SHADE(LMV, LT_AREA, C); \
+        if (light_set == 0) GX_SHADE_AREA(LMV, C); \
         else if (light_set == 1) GX_SHADE_K((k_shade<LMV, LT_AREA | LT_ENV, false>), C); \
         else GX_SHADE(LMV, LT_ALL, C); } while (0)
     // (the narrow kernels exist without spheres only: plan_shade_queues gives a scene with spheres no queue per kind)
 #define GX_SHADE_NARROW(LMV, C) do { \
-        if (light_set == 0) GX_SHADE_K((k_shade<LMV, LT_AREA, false>), C); \
+        if (light_set == 0) GX_SHADE_AREA_S(LMV, false, C); \
         else if (light_set == 1) GX_SHADE_K((k_shade<LMV, LT_AREA | LT_ENV, false>), C); \
         else GX_SHADE_K((k_shade<LMV, LT_ALL, false>), C); } while (0)
     for (int q = 0; q < 4; ++q) {
@@ -529,8 +547,11 @@ int RenderRun::shade_stage(const int *q_in, int n, int *q_out, const unsigned *n
 #undef GX_SHADE_NARROW
 #undef GX_SHADE_LM
 #undef GX_SHADE_TEX
+#undef GX_SHADE_AREA
+#undef GX_SHADE_AREA_S
 #undef GX_SHADE
 #undef GX_SHADE_K
+#undef GX_SHADE_KA
     if (fork) {
         HIP_TRY(hipEventRecord(s->ev_join[0], s->aux_stream[0]));
         HIP_TRY(hipEventRecord(s->ev_join[1], s->aux_stream[1]));

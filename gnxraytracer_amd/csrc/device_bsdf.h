@@ -414,6 +414,54 @@ GX_DEV Spec lobe_sample(const DLobe &l, V3 wo, V3 *wi, float u0, float u1, float
     return need_f ? lobe_f<LM>(l, wo, *wi) : Spec(0.f);
 }
 
+// The direction part of lobe_sample for a non-specular lobe: *wi as lobe_sample leaves it (the same inlined functions on the same operands,
+// so the same bits), without the pdf and f.  False where lobe_sample returns before it has a direction; true does not say that its pdf is
+// non-zero -- the caller that needs to know runs lobe_sample.  A specular lobe has no direction part (false).
+template <uint32_t LM>
+GX_DEV bool lobe_dir(const DLobe &l, V3 wo, V3 *wi, float u0, float u1) {
+    switch (l.kind) {
+    case LOBE_SPEC_REFL: case LOBE_SPEC_TRANS: case LOBE_FRESNEL_SPEC: return false;
+    case LOBE_MICRO_REFL: case LOBE_MICRO_TRANS: if (GX_HAS_LOBE(LOBE_MICRO_REFL) || GX_HAS_LOBE(LOBE_MICRO_TRANS)) {
+        if (wo.z == 0) return false;
+        V3 wh = tr_sample_wh(l.alphax, l.alphay, wo, u0, u1);
+        if (dot(wo, wh) < 0) return false;
+        if (GX_MICRO_IS_REFL(l)) {
+            *wi = reflect(wo, wh);
+            return same_hemisphere(wo, *wi);
+        }
+        const bool up = cos_theta(wo) > 0;
+        float eta = (up ? l.etaA : l.etaB) / (up ? l.etaB : l.etaA);
+        return refract(wo, wh, eta, wi);
+    }
+    break;
+    case LOBE_LAMBERT_TRANS: if (GX_HAS_LOBE(LOBE_LAMBERT_TRANS)) {
+        *wi = cosine_sample_hemisphere(u0, u1);
+        if (wo.z > 0) wi->z *= -1;
+        return true;
+    }
+    break;
+    case LOBE_DISNEY_CLEARCOAT: if (GX_HAS_LOBE(LOBE_DISNEY_CLEARCOAT)) {
+        if (wo.z == 0) return false;
+        float alpha2 = l.gloss * l.gloss;
+        float cosTheta = gx_sqrt(fmaxf(0.f, (1 - gx_pow(alpha2, 1 - u0)) / (1 - alpha2)));
+        float sinTheta = gx_sqrt(fmaxf(0.f, 1 - cosTheta * cosTheta));
+        float phi = 2 * GX_PI * u1;
+        float sinPhi, cosPhi;
+        gx_sincos(phi, &sinPhi, &cosPhi);
+        V3 wh(sinTheta * cosPhi, sinTheta * sinPhi, cosTheta);
+        if (!same_hemisphere(wo, wh)) wh = -wh;
+        *wi = reflect(wo, wh);
+        return same_hemisphere(wo, *wi);
+    }
+    break;
+    default: break;
+    }
+    if (lm_micro_only(LM)) return false;
+    *wi = cosine_sample_hemisphere(u0, u1);
+    if (wo.z < 0) wi->z *= -1;
+    return true;
+}
+
 // ---- BSDF container, Reflection.h:102-154 + Reflection.cpp:440-563 ----
 template <uint32_t LM>
 struct Bsdf {
@@ -473,6 +521,28 @@ struct Bsdf {
             if (matches(l.type, flags)) { ++matching; p += lobe_pdf<LM>(l, wo, wi); }
         }
         return matching > 0 ? p / matching : 0.f;
+    }
+    // The direction part of sample_f for `flags` without BSDF_SPECULAR: the lobe choice, lobe_dir and to_world -- *wiW has the bits sample_f
+    // gives it.  False where sample_f returns black before it has a direction; true does not say that its pdf and f are non-zero.  For the
+    // callers that can decide from the direction alone whether they need f and the pdf (k_shade with SM_DIR_FIRST / SM_DEFER: light_pdf of the MIS half).
+    GX_DEV bool sample_dir(V3 woW, V3 *wiW, float u0, float u1, int flags) const {
+        V3 wi, wo = to_local(woW);
+        if (kSingle) {
+            if (mat->n_lobes == 0 || !matches(kSingleType, flags) || wo.z == 0) return false;
+            if (!lobe_dir<LM>(mat->lobes[0], wo, &wi, fminf(u0 * 1 - 0, GX_ONE_MINUS_EPS), u1)) return false;
+        } else {
+            const int matching = num_components(flags);
+            if (matching == 0) return false;
+            int comp = min((int)floorf(u0 * matching), matching - 1);   // the lobe choice of sample_f
+            int which = -1, count = comp;
+            for (int i = 0; i < mat->n_lobes; ++i)
+                if (matches(mat->lobes[i].type, flags) && count-- == 0) { which = i; break; }
+            float ur0 = fminf(u0 * matching - comp, GX_ONE_MINUS_EPS);
+            if (wo.z == 0) return false;
+            if (!lobe_dir<LM>(mat->lobes[which], wo, &wi, ur0, u1)) return false;
+        }
+        *wiW = to_world(wi);
+        return true;
     }
     GX_DEV Spec sample_f(V3 woW, V3 *wiW, float u0, float u1, float *pdf, int flags, int *sampledType) const {
         if (kSingle) {   // matchingComps == 1: comp = 0, uRemapped = min(u[0] * 1 - 0, OneMinusEpsilon), no other lobes' pdfs, f = that lobe's f if it reflects

@@ -1,5 +1,5 @@
-// kernel_instances.h -- the instantiations of the two largest kernel templates, k_whitted_step and k_vol_step, and the k_shade kernels of the
-// glossy material kinds are compiled in translation units of their own (inst_whitted.hip, inst_whitted_tex.hip, inst_vol.hip, inst_shade_kinds.hip) so that the device compilations run side by side;
+// kernel_instances.h -- the instantiations of the two largest kernel templates, k_whitted_step and k_vol_step, the k_shade kernels of the
+// glossy material kinds and of the reordered MIS half are compiled in translation units of their own (inst_whitted.hip, inst_whitted_tex.hip, inst_vol.hip, inst_shade_kinds.hip) so that the device compilations run side by side;
 // api.hip sees them as `extern template`.  X(...) receives the template arguments of one instantiation.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -22,6 +22,13 @@
 #define GX_SK_LT(X, M) X(M, LT_AREA) X(M, LT_AREA | LT_ENV) X(M, LT_ALL)
 #define GX_SHADE_KIND_INSTANCES(X) GX_SK_LT(X, LM_CONDUCTOR) GX_SK_LT(X, LM_ROUGH_DIELECTRIC)
 
+// k_shade with the MIS half reordered (SM_DIR_FIRST, SM_DEFER; area lights only): every material class with and without spheres, the two kinds without
+#define GX_SM_LM(X, L) X(LM_DIFFUSE, L, false) X(LM_DIFFUSE, L, true) X(LM_GLOSSY, L, false) X(LM_GLOSSY, L, true) X(LM_ALL, L, false) X(LM_ALL, L, true) \
+    X(LM_CONDUCTOR, L, false) X(LM_ROUGH_DIELECTRIC, L, false)
+#define GX_SHADE_MIS_INSTANCES(X) GX_SM_LM(X, LT_AREA | SM_DIR_FIRST) GX_SM_LM(X, LT_AREA | SM_DEFER)
+
+#define GX_SHADE_MIS_SIGNATURE(M, L, S) \
+    __global__ void gnxr::k_shade<M, L, S, false>(gnxr::DScene, gnxr::DRender, gnxr::PathArrays, const int *, const unsigned int *, int, int, int, int);
 #define GX_SHADE_KIND_SIGNATURE(M, L) \
     __global__ void gnxr::k_shade<M, L, false, false>(gnxr::DScene, gnxr::DRender, gnxr::PathArrays, const int *, const unsigned int *, int, int, int, int);
 #define GX_WHITTED_SIGNATURE(M, L, S, T) \

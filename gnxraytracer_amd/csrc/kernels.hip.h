@@ -448,8 +448,80 @@ static __device__ unsigned long long g_shade_stats[16];
 template <uint32_t LM> constexpr int shade_min_waves() {   // (the kinds of the glossy class -- LM_CONDUCTOR, LM_ROUGH_DIELECTRIC -- as the class)
     return LM == LM_DIFFUSE ? GX_SHADE_W_DIFFUSE : ((LM == LM_GLOSSY || LM == LM_CONDUCTOR || LM == LM_ROUGH_DIELECTRIC) ? GX_SHADE_W_GLOSSY : GX_SHADE_W_ALL);
 }
-template <uint32_t LM, int LT, bool SPH, bool TEX = false>
+constexpr int kMisEntryWords = 27, kMisCap = 64;   // the SM_DEFER list: words of an entry (mis_drain_entry) and entries of a wave's list
+// SM_DEFER of k_shade (below): one entry of a wave's list of deferred vertices -- word w of entry e is list[w * cap + e], so the lanes of a wave
+// read and write neighbouring words (cap = kMisCap).  It holds what the MIS half of EstimateDirect reads, and what its stores need of the light half:
+//   0 path | 1 material | 2-4 wo | 5-6 the two BSDF sample values | 7-9 ns | 10-12 ng | 13-15 ss | 16-18 ts | 19-21 p | 22-24 pError | 25 light
+//   26 bit 0: the light half wrote a shadow ray (nflags & 1), bit 1: beta is finite, bit 2: the path goes on (written at the end of the vertex)
+// mis_drain_entry runs the MIS half for one entry: the statements of k_shade's own, on the same operands (the entry holds them bit for bit).
+// The main pass has written the vertex as one without MIS ray; where there is one after all this adds the MIS record and rewrites the three
+// words that say so: the flags in sh_d.w, nee_vis[path] and pflags[path].  The main pass's stores to those words come from another lane of
+// this wave in an earlier loop turn; the wavefront fences around the list keep them first.
+template <uint32_t LM>
+GX_DEV void mis_drain_entry(const int *e, const DMaterial *mats, const DLightTables &ltab, const PathArrays &pa) {
+    constexpr int cap = kMisCap;
+#define GX_MF(w) __int_as_float(e[(w) * cap])
+    const int path = e[0], lightNum = e[25 * cap], bits = e[26 * cap];
+    Bsdf<LM> bsdf;
+    bsdf.mat = mats + e[1 * cap];
+    const V3 woN(GX_MF(2), GX_MF(3), GX_MF(4));
+    const float us0 = GX_MF(5), us1 = GX_MF(6);
+    bsdf.ns = V3(GX_MF(7), GX_MF(8), GX_MF(9)); bsdf.ng = V3(GX_MF(10), GX_MF(11), GX_MF(12));
+    bsdf.ss = V3(GX_MF(13), GX_MF(14), GX_MF(15)); bsdf.ts = V3(GX_MF(16), GX_MF(17), GX_MF(18));
+    const V3 p(GX_MF(19), GX_MF(20), GX_MF(21)), pError(GX_MF(22), GX_MF(23), GX_MF(24));
+#undef GX_MF
+    const int bsdfFlags = BSDF_ALL & ~BSDF_SPECULAR;
+    float scatteringPdf = 0;
+    V3 wi2;
+    int sampledType;
+    Spec f = bsdf.sample_f(woN, &wi2, us0, us1, &scatteringPdf, bsdfFlags, &sampledType);
+    f = f * absdot(wi2, bsdf.ns);
+    bool sampledSpecular = (sampledType & BSDF_SPECULAR) != 0;
+    if (!f.is_black() && scatteringPdf > 0) {
+        float weight = 1;
+        bool skip = false;
+        if (!sampledSpecular) {
+            float lightPdf = light_pdf<LT_AREA>(ltab, lightNum, p, pError, bsdf.ng, wi2);
+            if (lightPdf == 0) skip = true;  // `return Ld`
+            else weight = power_heuristic(scatteringPdf, lightPdf);
+        }
+        if (!skip) {
+            const DLight &lt = ltab.lights[lightNum];
+            V3 mo = offset_ray_origin(p, pError, bsdf.ng, wi2);
+            V3 lp0(lt.p0[0], lt.p0[1], lt.p0[2]), lp1(lt.p1[0], lt.p1[1], lt.p1[2]), lp2(lt.p2[0], lt.p2[1], lt.p2[2]);
+            V3 ln = normalize(cross(lp0 - lp2, lp1 - lp2));  // lightIsect.n
+            Spec Li2 = area_L(lt, ln, -wi2);
+            const int expect = lt.tri_leaf;
+            Spec Y(0.f);
+            if (!Li2.is_black()) Y = f * Li2 * Spec(1.f) * weight / scatteringPdf;
+            const int nflags = (bits & 1) | 2;
+            pa.mis_o[(size_t)path * kRS] = make_float4(mo.x, mo.y, mo.z, __int_as_float(expect));
+            pa.mis_d[(size_t)path * kRS] = make_float4(wi2.x, wi2.y, wi2.z, 0.f);
+            pa.mis_Y[path] = make_float4(Y.r, Y.g, Y.b, 0.f);
+            pa.sh_d[(size_t)path * kRS].w = __int_as_float(nflags);
+            pa.nee_vis[path] = ((unsigned)nflags | ((bits & 2) ? 0u : 0x80u)) << 16;
+            pa.pflags[path] = (unsigned char)(((bits >> 2) & 1) | 2 | ((bits & 1) ? 4 : 0) | 8);
+        }
+    }
+}
+
+// LTM = the light-type set LT (device_lights.h LT_*) | how the MIS half of EstimateDirect is ordered, MD (bits above LT_ALL: the kernels of the
+// other orders keep the name k_shade, and a kernel without the bits is the kernel it was):
+//   0               as the reference writes it -- bsdf.sample_f, then light_pdf, which drops the vertex where it is 0
+//   SM_DIR_FIRST    direction first: bsdf.sample_dir, light_pdf of that direction, and the code of 0 only in the lanes where it is not 0
+//   SM_DEFER        direction first, and the lanes where it is not 0 -- 3.6 % of the vertices of cfg 3, under one small area light -- put what that code
+//                   reads on a list of their wave in LDS; the wave runs the code once for a whole list (mis_drain_entry)
+// Both for LT_AREA without TEX only: an infinite light's Pdf_Li is never 0, so the other light sets have nothing to skip.  Same image and
+// counts, bit for bit ("The MIS half, direction first").
+constexpr int SM_DIR_FIRST = 16, SM_DEFER = 32;
+template <uint32_t LM, int LTM, bool SPH, bool TEX = false>
 __global__ void __launch_bounds__(kBlock, (TEX ? GX_SHADE_W_TEX : shade_min_waves<LM>())) k_shade(DScene sc, DRender r, PathArrays pa, const int *__restrict__ queue, const unsigned int *n_dev, int lds_dims, int lds_nperm, int lds_mats, int lds_lights) {
+    constexpr int LT = LTM & LT_ALL, MD = LTM >> 4;   // MD: 0, 1 = SM_DIR_FIRST, 2 = SM_DEFER
+    static_assert(MD == 0 || (LT == LT_AREA && !TEX && MD <= 2), "the MIS half is reordered for area lights without image textures only");
+    // SM_DEFER: lds_lights carries the list's drain threshold (1 .. kMisCap) in bits 8 - 15
+    constexpr int misCap = kMisCap;
+    const int misDrainAt = MD == 2 ? (lds_lights >> 8) & 0xff : 0;
+    if (MD == 2) lds_lights &= 0xff;
     extern __shared__ int shade_smem[];   // the Halton tables of dimensions [0, lds_dims): device_sampler.h LdsSampler | the scene's DMaterial[] | DLight[]
     const int n = (int)*n_dev;
     if (blockIdx.x * blockDim.x >= (unsigned)n) return;   // this block has no item: skip the table fill
@@ -488,9 +560,36 @@ __global__ void __launch_bounds__(kBlock, (TEX ? GX_SHADE_W_TEX : shade_min_wave
     int pathCur_ = i < n ? queue[i] : -1;
     int leafCur_ = pathCur_ >= 0 ? pa.hit[pathCur_] : -1;
     int pathNext_ = (long long)i + stride_ < n ? queue[i + stride_] : -1;
-    for (; i < n; i += stride_) {
+    // SM_DEFER: this wave's list (the words of mis_drain_entry, above) and, behind it, its fill count -- in LDS because the vertices that append sit in
+    // divergent code, where a count in a register would no longer be the wave's
+    int *const misList = shade_smem + (MD != 2 ? 0 : (lds_sampler_bytes(lds_nperm, lds_dims) >> 2) + (lds_mats > 0 ? lds_mats * (int)(sizeof(DMaterial) / 4) : 0) +
+                                                     lds_lights * (int)(sizeof(DLight) / 4) + (int)(threadIdx.x >> 6) * (kMisEntryWords * misCap + 1));
+    int *const misFill = misList + kMisEntryWords * misCap;
+    if (MD == 2) {
+        if ((threadIdx.x & 63) == 0) *misFill = 0;
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    }
+    for (; MD == 2 || i < n; i += stride_) {
         bool survive = false, wantNee = false, wantShadow = false, wantMis = false;
         int path = -1;
+        int misSlot = -1, misBits = 0;   // SM_DEFER: this vertex's entry, and bits 0 - 1 of its word 26
+        if (MD == 2) {
+            // a loop turn of the wave, not of the lane: a lane whose items are done stays for the drains.  The list is drained between two
+            // vertices once it holds misDrainAt entries, and when no lane has an item left -- every lane takes one entry
+            const bool act_ = i < n;
+            const bool anyAct_ = __ballot(act_) != 0;
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the entries and the main pass's stores of the earlier turns come first
+            const int fill_ = *misFill;
+            if (fill_ > 0 && (fill_ >= misDrainAt || !anyAct_)) {
+                if ((int)(threadIdx.x & 63) < fill_) mis_drain_entry<LM>(misList + (threadIdx.x & 63), mats, ltab, pa);
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // all reads of the list precede the next appends
+                if ((threadIdx.x & 63) == 0) *misFill = 0;
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                GX_STICK(12);  // SM_DEFER: drains
+            }
+            if (!anyAct_) break;
+            if (!act_) { i = n - stride_; continue; }
+        }
         GX_STICK(9);
         const int leafNext_ = pathNext_ >= 0 ? pa.hit[pathNext_] : -1;
         const int pathNext2_ = (long long)i + 2ll * stride_ < n ? queue[i + 2 * stride_] : -1;
@@ -557,6 +656,14 @@ __global__ void __launch_bounds__(kBlock, (TEX ? GX_SHADE_W_TEX : shade_min_wave
                             V3 so, sd, mo, wi2;
                             Spec X(0.f), Y(0.f);
                             int expect = -1;
+                            // (SM_DIR_FIRST asks ahead of the light half, where fewer values are live: less scratch in the glossy kernels;
+                            // SM_DEFER below, where the entry's operands are at hand -- an area light is no delta light)
+                            bool misLaneEarly_ = true;
+                            if (MD == 1) {
+                                V3 wd;
+                                misLaneEarly_ = bsdf.sample_dir(woN, &wd, us0, us1, bsdfFlags) && light_pdf<LT>(ltab, lightNum, sp.p, sp.pError, sp.n, wd) != 0;
+                                GX_STICK(11);  // direction of the MIS half + its light_pdf
+                            }
                             LightSample ls = light_sample<LT>(ltab, lightNum, sp.p, ul0, ul1);
                             GX_STICK(4);   // light_sample
                             float scatteringPdf = 0;
@@ -572,7 +679,46 @@ __global__ void __launch_bounds__(kBlock, (TEX ? GX_SHADE_W_TEX : shade_min_wave
                                 }
                             }
                             GX_STICK(5);   // BSDF f / pdf towards the light sample, shadow ray
-                            if (!light_is_delta<LT>(ltab.lights[lightNum])) {
+                            // MD 1, 2: `return Ld` of the reference depends on the sampled direction alone -- bsdfFlags has no BSDF_SPECULAR, so
+                            // light_pdf is always asked, and a vertex whose light_pdf is 0 needs neither f nor the pdf.  sample_dir gives the
+                            // direction sample_f gives (same functions, same operands, no contraction: same bits) and light_pdf is a pure
+                            // function, so the lanes that go on are exactly the lanes whose MIS ray exists -- plus those sample_f itself
+                            // drops (f black, pdf 0), which it still drops below.  With one small area light that is a few vertices in a hundred, and
+                            // a wave without such a lane branches over the evaluation.
+                            bool misLane = !light_is_delta<LT>(ltab.lights[lightNum]);
+                            if (MD == 1) misLane = misLaneEarly_;
+                            if (MD == 2 && misLane) {
+                                V3 wd;
+                                misLane = bsdf.sample_dir(woN, &wd, us0, us1, bsdfFlags) && light_pdf<LT>(ltab, lightNum, sp.p, sp.pError, sp.n, wd) != 0;
+                                GX_STICK(11);  // direction of the MIS half + its light_pdf
+                            }
+                            if (MD == 2) {
+                                // SM_DEFER: those lanes append an entry instead (slots from ballot and popcount; a lane the list has no room
+                                // for goes on below as with SM_DIR_FIRST).  This code is divergent: the ballot sees the lanes that are here.
+                                const unsigned long long hm_ = __ballot(misLane);
+                                if (hm_ != 0) {
+                                    const int lane_ = (int)(threadIdx.x & 63), base_ = *misFill;
+                                    const int slot_ = base_ + __popcll(hm_ & ((1ull << lane_) - 1ull));
+                                    if (misLane && slot_ < misCap) {
+                                        int *e_ = misList + slot_;
+#define GX_ME(w, v) e_[(w) * misCap] = (v)
+#define GX_MEF(w, v) e_[(w) * misCap] = __float_as_int(v)
+                                        GX_ME(0, path); GX_ME(1, triMat); GX_MEF(2, woN.x); GX_MEF(3, woN.y); GX_MEF(4, woN.z); GX_MEF(5, us0); GX_MEF(6, us1);
+                                        GX_MEF(7, sp.ns.x); GX_MEF(8, sp.ns.y); GX_MEF(9, sp.ns.z); GX_MEF(10, sp.n.x); GX_MEF(11, sp.n.y); GX_MEF(12, sp.n.z);
+                                        GX_MEF(13, sp.ss.x); GX_MEF(14, sp.ss.y); GX_MEF(15, sp.ss.z); GX_MEF(16, sp.ts.x); GX_MEF(17, sp.ts.y); GX_MEF(18, sp.ts.z);
+                                        GX_MEF(19, sp.p.x); GX_MEF(20, sp.p.y); GX_MEF(21, sp.p.z); GX_MEF(22, sp.pError.x); GX_MEF(23, sp.pError.y); GX_MEF(24, sp.pError.z);
+                                        GX_ME(25, lightNum);
+#undef GX_MEF
+#undef GX_ME
+                                        misSlot = slot_;
+                                        misLane = false;
+                                    }
+                                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // every lane here has read the count
+                                    if (lane_ == __ffsll((long long)hm_) - 1) *misFill = min(base_ + __popcll(hm_), misCap);
+                                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                                }
+                            }
+                            if (misLane) {
                                 int sampledType;
                                 Spec f = bsdf.sample_f(woN, &wi2, us0, us1, &scatteringPdf, bsdfFlags, &sampledType);
                                 f = f * absdot(wi2, sp.ns);
@@ -607,7 +753,9 @@ __global__ void __launch_bounds__(kBlock, (TEX ? GX_SHADE_W_TEX : shade_min_wave
                                 }
                             }
                             GX_STICK(7);   // light_pdf + MIS record
-                            if (nflags) {
+                            // (SM_DEFER: a deferred vertex gets its record even where the light half left nothing, nflags 0 -- all but the
+                            // MIS part and the three words mis_drain_entry rewrites if the MIS ray exists; without it nothing reads the record)
+                            if (nflags || (MD == 2 && misSlot >= 0)) {
                                 pa.sh_o[(size_t)path * kRS] = make_float4(so.x, so.y, so.z, 1 - GX_SHADOW_EPS);
                                 pa.sh_d[(size_t)path * kRS] = make_float4(sd.x, sd.y, sd.z, __int_as_float(nflags));
                                 pa.sh_X[(size_t)path * kRS] = make_float4(X.r, X.g, X.b, lightPdfSel);
@@ -621,7 +769,8 @@ __global__ void __launch_bounds__(kBlock, (TEX ? GX_SHADE_W_TEX : shade_min_wave
                                 // the reference's L += beta * 0 would poison the pixel, and so must this)
                                 const bool betaFinite = __builtin_isfinite(beta.r) && __builtin_isfinite(beta.g) && __builtin_isfinite(beta.b);
                                 pa.nee_vis[path] = ((unsigned)nflags | (betaFinite ? 0u : 0x80u)) << 16;
-                                wantNee = true;
+                                wantNee = MD == 2 ? nflags != 0 : true;
+                                if (MD == 2) misBits = (nflags & 1) | (betaFinite ? 2 : 0);
                                 wantShadow = (nflags & 1) != 0;
                                 wantMis = (nflags & 2) != 0;
                             }
@@ -662,6 +811,7 @@ __global__ void __launch_bounds__(kBlock, (TEX ? GX_SHADE_W_TEX : shade_min_wave
             GX_STICK(10);  // continuation: 2 Halton values, BSDF sample_f, Russian roulette, state stores
         }
         pa.pflags[path] = (unsigned char)((survive ? 1 : 0) | (wantNee ? 2 : 0) | (wantShadow ? 4 : 0) | (wantMis ? 8 : 0));
+        if (MD == 2 && misSlot >= 0) misList[26 * misCap + misSlot] = misBits | (survive ? 4 : 0);   // `survive` is known: the entry is complete
         pathCur_ = pathNext_; leafCur_ = leafNext_; pathNext_ = pathNext2_;
     }
 #ifdef GX_SHADE_STATS
