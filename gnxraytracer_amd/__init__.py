@@ -452,6 +452,75 @@ class Scene:
         handle = _stream_handle("rebuild_bvh", stream)
         _check(lib().gnxr_scene_rebuild_bvh(self._h, C.c_void_p(handle or None)))
 
+    def set_geometry(self, vertices, indices, tri_material, tri_light=None, medium_inside=None, medium_outside=None, uv=None, normals=None,
+                     tangents=None, stream=None):
+        """Replace the scene's triangle mesh (gnxr_scene_set_geometry): float32 (nv, 3) vertices in world space, int32 (nt, 3) indices,
+        int32 (nt,) tri_material (or one integer for all triangles; -1 == no material), and optionally int32 (nt,) tri_light (required
+        when the scene has area lights: each must be named by exactly one triangle), int32 (nt,) medium_inside and medium_outside (both
+        or neither), float32 (nt, 6) uv, (nt, 9) normals and (nt, 9) tangents in the description's layout.  The arrays are ALL numpy
+        arrays or ALL contiguous torch tensors on the scene's device; tensors are read where they lie, on `stream` (default: torch's
+        current stream).  Afterwards the scene gives the results of a new Scene with this mesh and an HLBVH tree; materials, lights'
+        parameters, textures, media, environment, camera and the reserved path state are kept.  Malformed arguments raise ValueError
+        before the library is called; a refusal raises GnxrError and leaves the scene as it was."""
+        import numbers
+        name = "set_geometry"
+        on_device = not isinstance(vertices, np.ndarray)
+        if on_device:
+            if type(vertices).__module__.split(".")[0] != "torch":
+                raise ValueError(f"{name}: vertices: expected a numpy array or a torch tensor, got {type(vertices).__name__}")
+            import torch
+            if stream is None and isinstance(vertices, torch.Tensor) and vertices.is_cuda:
+                stream = torch.cuda.current_stream(vertices.device)
+        handle = _stream_handle(name, stream)
+
+        def arr(what, x, kind, cols, rows):
+            """a checked array and its address"""
+            shape = (rows, cols) if cols else (rows,)
+            want = f"{kind} array of shape ({'n' if rows is None else rows}{', %d' % cols if cols else ''})"
+            if on_device:
+                dt = torch.float32 if kind == "float32" else torch.int32
+                ok = (isinstance(x, torch.Tensor) and x.is_cuda and x.device.index == self.device and x.dtype == dt and x.dim() == len(shape) and x.is_contiguous())
+                if not ok or x.shape[0] < 1 or tuple(x.shape[1:]) != shape[1:] or (rows is not None and x.shape[0] != rows):
+                    raise ValueError(f"{name}: {what}: expected a contiguous {want} on cuda:{self.device} (all arrays tensors there, or all numpy), got "
+                                     f"{type(x).__name__} {getattr(x, 'dtype', None)} {tuple(getattr(x, 'shape', ()))} on {getattr(x, 'device', None)}")
+                return x, x.data_ptr()
+            dt = np.float32 if kind == "float32" else np.int32
+            ok = isinstance(x, np.ndarray) and x.dtype == dt and x.ndim == len(shape)
+            if not ok or x.shape[0] < 1 or tuple(x.shape[1:]) != shape[1:] or (rows is not None and x.shape[0] != rows):
+                raise ValueError(f"{name}: {what}: expected a {want} in host memory (all arrays numpy, or all tensors on the scene's device), got "
+                                 f"{type(x).__name__} {getattr(x, 'dtype', None)} {tuple(getattr(x, 'shape', ()))}")
+            x = np.ascontiguousarray(x)
+            return x, x.ctypes.data
+
+        keep = []
+        g = _abi.Geometry()
+        g.struct_size = C.sizeof(_abi.Geometry)
+        v, g.vertices = arr("vertices", vertices, "float32", 3, None)
+        idx, g.indices = arr("indices", indices, "int32", 3, None)
+        nt = int(idx.shape[0])
+        if isinstance(tri_material, numbers.Integral) and not isinstance(tri_material, bool):
+            if on_device:   # filled on the stream the call reads on
+                ts = stream if hasattr(stream, "cuda_stream") else torch.cuda.ExternalStream(handle, device=v.device)
+                with torch.cuda.stream(ts):
+                    tri_material = torch.full((nt,), int(tri_material), dtype=torch.int32, device=v.device)
+            else:
+                tri_material = np.full(nt, int(tri_material), np.int32)
+        keep += [v, idx]
+        for field, what, x, kind, cols, required in (("tri_material", "tri_material", tri_material, "int32", 0, True), ("tri_light", "tri_light", tri_light, "int32", 0, False),
+                                                     ("tri_medium_inside", "medium_inside", medium_inside, "int32", 0, False),
+                                                     ("tri_medium_outside", "medium_outside", medium_outside, "int32", 0, False), ("tri_uv", "uv", uv, "float32", 6, False),
+                                                     ("tri_n", "normals", normals, "float32", 9, False), ("tri_s", "tangents", tangents, "float32", 9, False)):
+            if x is None and not required:
+                continue
+            a, ptr = arr(what, x, kind, cols, nt)
+            keep.append(a)
+            setattr(g, field, ptr)
+        if (medium_inside is None) != (medium_outside is None):
+            raise ValueError(f"{name}: medium_inside and medium_outside come together or not at all")
+        g.n_vertices, g.n_triangles = int(v.shape[0]), nt
+        _check(lib().gnxr_scene_set_geometry(self._h, C.byref(g), C.c_void_p(handle or None)))
+        self.n_triangles, self.n_vertices = nt, int(v.shape[0])
+
     def update_environment(self, rgb=None, le=None, light_to_world=None, n_samples=None, stream=None):
         """Replace or rotate the environment map of the scene's INFINITE light (gnxr_scene_update_environment).  rgb: the new map, an
         (h, w, 3) float32 numpy array (host memory) or a contiguous float32 (h, w, 3) torch tensor on the scene's device (read on `stream`,

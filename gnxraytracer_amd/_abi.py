@@ -128,6 +128,12 @@ class LightResult(C.Structure):
     _fields_ = [("Li", f32 * 3), ("pdf", f32), ("wi", f32 * 3), ("pdf_li", f32), ("pdf_select", f32), ("p_light", f32 * 3)]
 
 
+class Geometry(C.Structure):   # gnxr_geometry: the arrays are host or device addresses (not in gnxr_abi_sizeof's list: it carries struct_size)
+    _fields_ = [("struct_size", i32), ("n_vertices", i32), ("n_triangles", i32), ("_pad", i32),
+                ("vertices", C.c_void_p), ("indices", C.c_void_p), ("tri_material", C.c_void_p), ("tri_light", C.c_void_p),
+                ("tri_medium_inside", C.c_void_p), ("tri_medium_outside", C.c_void_p), ("tri_uv", C.c_void_p), ("tri_n", C.c_void_p), ("tri_s", C.c_void_p)]
+
+
 P = C.POINTER
 VP = C.c_void_p
 
@@ -149,6 +155,7 @@ PROTOTYPES = {
     "gnxr_scene_update_vertices_ex": (C.c_int, [VP, i32, i32, VP, u32, VP]),   # ..., flags (UPDATE_MOVE_LIGHTS), hipStream_t
     "gnxr_scene_update_lights": (C.c_int, [VP, i32, i32, P(Light)]),
     "gnxr_scene_rebuild_bvh": (C.c_int, [VP, VP]),   # scene, hipStream_t
+    "gnxr_scene_set_geometry": (C.c_int, [VP, P(Geometry), VP]),   # scene, record of host or device arrays, hipStream_t
     "gnxr_scene_update_environment": (C.c_int, [VP, P(Light), VP, i32, i32, VP]),   # scene, record, host or device fp32 map (or NULL), width, height, hipStream_t
     "gnxr_scene_env_tables": (C.c_int, [VP, i32, VP, i64, P(i64)]),   # scene, which, out, capacity in bytes, size in bytes
     "gnxr_scene_update_media": (C.c_int, [VP, i32, i32, P(Medium), VP, VP]),   # scene, first, n, records, host or device fp32 grids (or NULL), hipStream_t

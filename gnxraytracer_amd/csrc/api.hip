@@ -20,6 +20,7 @@
 #include "refit_kernel.hip.h"
 #include "material_kernel.hip.h"
 #include "rebuild_kernel.hip.h"
+#include "geometry_kernel.hip.h"
 #include "env_build_kernel.hip.h"
 #include "media_kernel.hip.h"
 #include "texture_build_kernel.hip.h"
@@ -288,6 +289,7 @@ int gnxr_trace_any(gnxr_scene *s, const gnxr_ray *rays, int64_t n, uint8_t *occl
 
 #include "api_edit.hip.h"
 #include "api_rebuild.hip.h"
+#include "api_geometry.hip.h"
 #include "api_env.hip.h"
 #include "api_media.hip.h"
 #include "api_textures.hip.h"

@@ -34,14 +34,40 @@ struct Rebuilt {
     }
 };
 
-// the tree over the vertices `s` holds on its (bound) device, into `r`; nothing of `s` changes
-int rebuild_on_device(gnxr_scene *s, hipStream_t st, Rebuilt *r) {
+// What a rebuild reads: the per-triangle tables of n triangles on the (bound) device, in any order that DTri::prim numbers 0 .. n - 1 --
+// the scene's own in leaf order (rebuild_source_of), or gnxr_scene_set_geometry's in authoring order (api_geometry.hip.h).  Absent tables
+// are null.  lights: the scene's DLight records with tri_leaf counting rows of `tris`; refit_lights: the AREA_TRI records take corners, area
+// and normal from their triangles (k_refit_lights) instead of keeping them.
+struct RebuildSource {
+    int n = 0;
+    const DTri *tris = nullptr;
+    const uint8_t *tri_class = nullptr;
+    const int32_t *corner = nullptr, *tri_media = nullptr;
+    const float *tri_uv = nullptr, *tri_n = nullptr, *tri_s = nullptr;
+    const DLight *lights = nullptr;
+    bool refit_lights = false;
+};
+// the tables `s` holds (the refit's corner table goes to the device first; after a rebuild the device copy is the current one)
+int rebuild_source_of(gnxr_scene *s, RebuildSource *src) {
+    const CompiledScene &cs = s->cs;
+    if (int rc = refit_tables(s)) return rc;
+    src->n = (int)cs.tris.size();
+    src->tris = s->tris.p; src->tri_class = s->tri_class.p; src->corner = s->upd_corner.p;
+    src->tri_media = cs.tri_media.empty() ? nullptr : s->tri_media.p;
+    src->tri_uv = cs.tri_uv.empty() ? nullptr : s->tri_uv.p;
+    src->tri_n = cs.tri_n.empty() ? nullptr : s->tri_n.p;
+    src->tri_s = cs.tri_s.empty() ? nullptr : s->tri_s.p;
+    src->lights = s->lights.p;
+    return GNXR_OK;
+}
+
+// the tree over the triangles of `src` on the (bound) device of `s`, into `r`; nothing of `s` changes
+int rebuild_on_device(gnxr_scene *s, const RebuildSource &src, hipStream_t st, Rebuilt *r) {
     using namespace rebuild;
     const CompiledScene &cs = s->cs;
-    const int n = (int)cs.tris.size();
+    const int n = src.n;
     const int n_lights = (int)cs.desc_lights.size();
     int rc;
-    if ((rc = refit_tables(s)) != GNXR_OK) return rc;   // corner_vertex on the device (after a rebuild the device copy is the current one)
     const auto fetch = [&](void *dst, const void *src, size_t bytes) -> hipError_t {
         hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st);
         return e == hipSuccess ? hipStreamSynchronize(st) : e;
@@ -60,7 +86,7 @@ int rebuild_on_device(gnxr_scene *s, hipStream_t st, Rebuilt *r) {
     HIP_TRY(hipMemcpyAsync(cb.p, h_cb, sizeof(h_cb), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(res.p, h_res, sizeof(h_res), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(old_of_prim.p, 0xff, (size_t)n * sizeof(int), st));
-    hipLaunchKernelGGL(k_rb_prims, dim3(grid_for(n)), dim3(kB), 0, st, (const DTri *)s->tris.p, n, pb.p, cen.p, old_of_prim.p, cb.p, res.p);
+    hipLaunchKernelGGL(k_rb_prims, dim3(grid_for(n)), dim3(kB), 0, st, src.tris, n, pb.p, cen.p, old_of_prim.p, cb.p, res.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(fetch(h_cb, cb.p, sizeof(h_cb)));
     float lo[3], hi[3];
@@ -135,24 +161,23 @@ int rebuild_on_device(gnxr_scene *s, hipStream_t st, Rebuilt *r) {
         r->root4 = 0;   // the root is the first node of the breadth-first block
     }
     // ---- everything held in leaf order
-    const bool has_media = !cs.tri_media.empty(), has_uv = !cs.tri_uv.empty(), has_n = !cs.tri_n.empty(), has_s = !cs.tri_s.empty();
+    const bool has_media = src.tri_media != nullptr, has_uv = src.tri_uv != nullptr, has_n = src.tri_n != nullptr, has_s = src.tri_s != nullptr;
     if ((rc = r->tris.alloc(n)) || (rc = r->tri_class.alloc(n)) || (rc = r->corner.alloc(3 * (size_t)n)) || (has_media && (rc = r->tri_media.alloc(2 * (size_t)n))) ||
         (has_uv && (rc = r->tri_uv.alloc(8 * (size_t)n))) || (has_n && (rc = r->tri_n.alloc(12 * (size_t)n))) || (has_s && (rc = r->tri_s.alloc(12 * (size_t)n))) ||
         (rc = r->lights.alloc(cs.lights.size())))
         return rc;
     LeafTables lt;
-    lt.tris = s->tris.p; lt.tri_class = s->tri_class.p; lt.corner = s->upd_corner.p;
-    lt.tri_media = has_media ? reinterpret_cast<const int2 *>(s->tri_media.p) : nullptr;
-    lt.tri_uv = has_uv ? reinterpret_cast<const float4 *>(s->tri_uv.p) : nullptr;
-    lt.tri_n = has_n ? reinterpret_cast<const float4 *>(s->tri_n.p) : nullptr;
-    lt.tri_s = has_s ? reinterpret_cast<const float4 *>(s->tri_s.p) : nullptr;
+    lt.tris = src.tris; lt.tri_class = src.tri_class; lt.corner = src.corner;
+    lt.tri_media = reinterpret_cast<const int2 *>(src.tri_media);
+    lt.tri_uv = reinterpret_cast<const float4 *>(src.tri_uv); lt.tri_n = reinterpret_cast<const float4 *>(src.tri_n); lt.tri_s = reinterpret_cast<const float4 *>(src.tri_s);
     lt.tris_out = r->tris.p; lt.tri_class_out = r->tri_class.p; lt.corner_out = r->corner.p;
     lt.tri_media_out = reinterpret_cast<int2 *>(r->tri_media.p);
     lt.tri_uv_out = reinterpret_cast<float4 *>(r->tri_uv.p); lt.tri_n_out = reinterpret_cast<float4 *>(r->tri_n.p); lt.tri_s_out = reinterpret_cast<float4 *>(r->tri_s.p);
     HIP_TRY(hipMemsetAsync(new_of_old.p, 0xff, (size_t)n * sizeof(int), st));
     hipLaunchKernelGGL(k_rb_permute, dim3(grid_for(n)), dim3(kB), 0, st, n, hb.prims, (const int *)old_of_prim.p, lt, new_of_old.p, res.p);
-    HIP_TRY(hipMemcpyAsync(r->lights.p, s->lights.p, cs.lights.size() * sizeof(DLight), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(r->lights.p, src.lights, cs.lights.size() * sizeof(DLight), hipMemcpyDeviceToDevice, st));
     if (n_lights > 0) hipLaunchKernelGGL(k_rb_lights, dim3(grid_for(n_lights)), dim3(kB), 0, st, r->lights.p, n_lights, n, (const int *)new_of_old.p, res.p);
+    if (n_lights > 0 && src.refit_lights) hipLaunchKernelGGL(refit::k_refit_lights, dim3(grid_for(n_lights)), dim3(refit::kB), 0, st, r->lights.p, n_lights, (const DTri *)r->tris.p, n);
     hipLaunchKernelGGL(k_rb_leafcheck, dim3(grid_for(N)), dim3(kB), 0, st, N, (const DNode *)r->nodes.p, (const DTri *)r->tris.p, n, res.p);
     HIP_TRY(hipGetLastError());
     r->h_lights.resize(cs.lights.size());
@@ -213,7 +238,12 @@ extern "C" int gnxr_scene_rebuild_bvh(gnxr_scene *s, void *hip_stream) {
     if (rc) return rc;
     // 1. every device builds into fresh buffers (the primary on the caller's stream), and all must have built the same tree
     std::vector<Rebuilt> built(s->n_copies());
-    if ((rc = s->each_copy([&](gnxr_scene *c, size_t i) { return rebuild_on_device(c, i == 0 ? (hipStream_t)hip_stream : nullptr, &built[i]); }))) return rc;
+    if ((rc = s->each_copy([&](gnxr_scene *c, size_t i) -> int {
+            RebuildSource src;
+            if (int rc_ = rebuild_source_of(c, &src)) return rc_;
+            return rebuild_on_device(c, src, i == 0 ? (hipStream_t)hip_stream : nullptr, &built[i]);
+        })))
+        return rc;
     for (size_t i = 1; i < built.size(); ++i)
         if (!built[i].same_tree(built[0])) { set_error("BVH rebuild: the devices disagree (internal error)"); return GNXR_ERR_RUNTIME; }
     // 2. the only writes that can still fail; a failure points every record back at the tables the scene holds

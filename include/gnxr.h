@@ -450,6 +450,53 @@ int gnxr_scene_update_environment(gnxr_scene *scene, const gnxr_light *light, co
  * reference's HLBVH build does not terminate (coincident treelet centroids, a leaf over 65535 primitives), GNXR_ERR_UNSUPPORTED for a
  * tree deeper than the 64-entry traversal stack, GNXR_ERR_OOM. */
 int gnxr_scene_rebuild_bvh(gnxr_scene *scene, void *hip_stream);
+/* Replace the triangle mesh of an existing scene: vertex count, triangle count, index array and every per-triangle array may change.  The
+ * fields mean what the fields of the same names mean in gnxr_scene_desc.  The arrays are either ALL host memory or ALL device memory of
+ * the scene's first device (a mix, or another device: GNXR_ERR_INVALID); they are read on hip_stream (NULL: the null stream), ordered
+ * after what the caller queued there, and the call returns -- it synchronises, as gnxr_scene_rebuild_bvh does -- once every device of
+ * the scene has been switched over.  struct_size must be sizeof(gnxr_geometry) (the record is not part of gnxr_abi_sizeof's list).
+ *
+ * After a successful call every observable result -- renders of all integrators, the ray queries, gnxr_li_device, the shading queries,
+ * gnxr_render_views_device, gnxr_render_aov_device, gnxr_scene_bvh, gnxr_scene_bvh4, gnxr_scene_info, the light-selection tables -- is
+ * bit for bit that of a scene created with gnxr_scene_create from the same description with the geometry fields replaced by *g,
+ * gnxr_light::tri taken from tri_light and bvh_split_method = GNXR_BVH_HLBVH (binary bounds up to the sign of a zero).  Kept: materials,
+ * textures, environment tables, media, spheres, camera, sampler tables, the path state of gnxr_render_reserve, and the light list's
+ * length, types and parameters.  What follows the new mesh: primitive ids (gnxr_hit.prim, the ids feature buffer, a sphere's
+ * n_triangles + index), the world bound and with it the environment light's bounding sphere and the distant lights' radius, the
+ * light-selection table (rebuilt at the next render), the traversal stack and the choice of the traversal kernel.  Later edits
+ * (gnxr_scene_update_vertices[_ex], gnxr_scene_rebuild_bvh, gnxr_scene_set_triangle_materials, gnxr_scene_update_materials,
+ * gnxr_scene_update_lights) work on the new mesh.
+ *
+ * Lights: tri_light must name every AREA_TRI light of the scene on exactly one triangle and no other light; the records' corners, area,
+ * normal and triangle reference are recomputed on the device, le / two_sided / n_samples stay.  Normals or tangents on an emissive
+ * triangle are refused, as at creation.
+ *
+ * One pass over the triangles on the device validates the arrays and builds the scene's tables in authoring order (an index out of range
+ * is reported, never dereferenced); the tree is then built by the stages of gnxr_scene_rebuild_bvh.  Of the mesh only tri_material and
+ * one byte per triangle (has uvs, normals or tangents of its own) cross to the host, where the material tables are compiled; vertex and
+ * index data stay on the first device (further devices of gnxr_init_devices are fed through the host).
+ *
+ * Every refusal is found before anything of the scene changes.  GNXR_ERR_INVALID: a null scene or record or a wrong struct_size (before
+ * any device is touched); n_vertices < 1 or n_triangles < 1; a null vertices / indices / tri_material, a null tri_light in a scene with
+ * AREA_TRI lights; only one of the two medium arrays; arrays on mixed sides or on another device; an index outside [0, n_vertices); a
+ * material outside [-1, n_materials); a medium outside [-1, n_media); a tri_light entry that is neither -1 nor an AREA_TRI light, a
+ * light named twice or not at all; what gnxr_scene_update_materials refuses; non-finite centroids or more than 65535 primitives on one
+ * Morton code.  GNXR_ERR_UNSUPPORTED: a tree deeper than the 64-entry traversal stack.  GNXR_ERR_OOM. */
+typedef struct gnxr_geometry {
+    int32_t struct_size;               /* sizeof(gnxr_geometry): the binding's self-check */
+    int32_t n_vertices, n_triangles;
+    int32_t _pad;
+    const float   *vertices;           /* n_vertices * 3, world space                         */
+    const int32_t *indices;            /* n_triangles * 3                                     */
+    const int32_t *tri_material;       /* n_triangles, -1 == null material                    */
+    const int32_t *tri_light;          /* n_triangles or NULL (allowed only if no AREA_TRI light) */
+    const int32_t *tri_medium_inside;  /* n_triangles or NULL; both or neither                */
+    const int32_t *tri_medium_outside;
+    const float   *tri_uv;             /* n_triangles * 6 or NULL                             */
+    const float   *tri_n;              /* n_triangles * 9 or NULL                             */
+    const float   *tri_s;              /* n_triangles * 9 or NULL                             */
+} gnxr_geometry;
+int gnxr_scene_set_geometry(gnxr_scene *scene, const gnxr_geometry *g, void *hip_stream);
 /* Replace material records [first_material, first_material + n_materials) of the scene's material list (the numbering of
  * gnxr_scene_desc.materials) by materials[0 .. n_materials).  Every field may change, the type included: MATTE -> GLASS changes which shade
  * kernels the next render launches, a BSDF material -> GNXR_MAT_NONE turns its triangles (and spheres) into medium boundaries, and back;
