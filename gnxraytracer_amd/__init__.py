@@ -331,6 +331,7 @@ class Scene:
         d = builder_or_desc.desc() if isinstance(builder_or_desc, SceneBuilder) else builder_or_desc
         self.n_triangles = int(d.n_triangles)
         self.n_vertices = int(d.n_vertices)
+        self.n_lights = int(d.n_lights)   # (set_lights keeps it current)
         self.device = _device
         self._env_light = None   # a copy of the INFINITE light's record (update_environment keeps it current)
         for i in range(int(d.n_lights)):
@@ -399,6 +400,44 @@ class Scene:
                 raise ValueError(f"update_lights: lights must be gnxr Light records, got {type(l).__name__}")
         arr = (Light * max(len(lights), 1))(*lights)
         _check(lib().gnxr_scene_update_lights(self._h, int(first_light), len(lights), arr))
+
+    def set_lights(self, lights, stream=None):
+        """Replace the scene's light list by `lights` (a list of gnxr Light records, possibly empty): lights may be added, removed and
+        retyped, and other triangles may become emissive (gnxr_scene_set_lights).  An AREA_TRI record names its triangle in authoring
+        order (`tri`), no two the same one; its corners, area and normal come from the vertices the scene holds now.  The INFINITE
+        record, if the scene has one, must be in the list unchanged (update_environment changes it).  Afterwards every result is that of
+        a scene created with this list; tree, materials, textures, media, environment tables and the reserved path state are kept.
+        `stream`: None (the null stream), a torch.cuda.Stream or a hipStream_t as a non-negative integer.  Anything that is not a Light
+        raises ValueError before the library is called; a refusal raises GnxrError and leaves the scene as it was."""
+        lights = list(lights)
+        for l in lights:
+            if not isinstance(l, Light):
+                raise ValueError(f"set_lights: lights must be gnxr Light records, got {type(l).__name__}")
+        handle = _stream_handle("set_lights", stream)
+        arr = (Light * max(len(lights), 1))()
+        for k, l in enumerate(lights):
+            C.memmove(C.byref(arr[k]), C.byref(l), C.sizeof(Light))
+        _check(lib().gnxr_scene_set_lights(self._h, arr if lights else None, len(lights), C.c_void_p(handle or None)))
+        self.n_lights = len(lights)
+        self._env_light = None
+        for l in lights:
+            if l.type == _abi.LIGHT_INFINITE:
+                self._env_light = Light()
+                C.memmove(C.byref(self._env_light), C.byref(l), C.sizeof(Light))
+                break
+
+    def light_tables(self):
+        """Test hook: the light tables of the first device (gnxr_scene_light_tables): (the device's light records as uint32 words,
+        (n_lights, 28); per triangle in authoring order the light it is, int32 (n_triangles,), -1 == none)."""
+        out = []
+        for which, dtype, cols in ((0, np.uint32, _abi.DLIGHT_BYTES // 4), (1, np.int32, 0)):
+            n = C.c_int64(0)
+            _check(lib().gnxr_scene_light_tables(self._h, which, None, 0, C.byref(n)))
+            a = np.zeros(n.value // 4, dtype)
+            if n.value:
+                _check(lib().gnxr_scene_light_tables(self._h, which, C.c_void_p(a.ctypes.data), n.value, C.byref(n)))
+            out.append(a.reshape(-1, cols) if cols else a)
+        return tuple(out)
 
     def update_materials(self, materials, first_material=0):
         """Replace materials [first_material, first_material + len(materials)) of the scene's material list by `materials` (gnxr Material

@@ -19,6 +19,7 @@ DIRECT_SAMPLE_ALL, DIRECT_SAMPLE_ONE = 0, 1
 LIGHTS_SPATIAL, LIGHTS_UNIFORM, LIGHTS_POWER = 0, 1, 2
 MEDIUM_HOMOGENEOUS, MEDIUM_GRID = 1, 2
 DMEDIUM_BYTES = 128   # one record of gnxr_scene_media_tables(which = 0): sizeof(DMedium), csrc/gnxr_device_types.h
+DLIGHT_BYTES = 112   # one record of gnxr_scene_light_tables(which = 0): sizeof(DLight), csrc/gnxr_device_types.h
 DTEXTURE_BYTES = 112   # one record of gnxr_scene_texture_tables(which = 0): sizeof(DTexture), csrc/gnxr_device_types.h
 # flags of gnxr_scene_update_vertices_ex
 UPDATE_MOVE_LIGHTS = 1
@@ -154,6 +155,8 @@ PROTOTYPES = {
     "gnxr_scene_update_vertices": (C.c_int, [VP, i32, i32, VP, VP]),   # xyz: host or device address
     "gnxr_scene_update_vertices_ex": (C.c_int, [VP, i32, i32, VP, u32, VP]),   # ..., flags (UPDATE_MOVE_LIGHTS), hipStream_t
     "gnxr_scene_update_lights": (C.c_int, [VP, i32, i32, P(Light)]),
+    "gnxr_scene_set_lights": (C.c_int, [VP, P(Light), i32, VP]),   # scene, records, count, hipStream_t
+    "gnxr_scene_light_tables": (C.c_int, [VP, i32, VP, i64, P(i64)]),   # scene, which, out, capacity in bytes, size in bytes
     "gnxr_scene_rebuild_bvh": (C.c_int, [VP, VP]),   # scene, hipStream_t
     "gnxr_scene_set_geometry": (C.c_int, [VP, P(Geometry), VP]),   # scene, record of host or device arrays, hipStream_t
     "gnxr_scene_update_environment": (C.c_int, [VP, P(Light), VP, i32, i32, VP]),   # scene, record, host or device fp32 map (or NULL), width, height, hipStream_t

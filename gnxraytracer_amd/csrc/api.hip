@@ -1,7 +1,7 @@
 // api.hip -- C ABI of libgnxr.so (include/gnxr.h): one translation unit.  This file keeps initialisation, scene creation, the render entry
 // points and the host-memory probes; the rest lives in the api_*.hip.h headers included below (shared pieces, gnxr_scene, the HLBVH build
 // driver, the peak probes, the front end of the calls on device memory, the render path, the editing calls, the in-place BVH rebuild, the
-// environment light's rebuild, the media edit, the texture edit, the entry points on device memory).  One process drives one GPU (gnxr_init), or several behind every handle (gnxr_init_devices).
+// light list's replacement, the environment light's rebuild, the media edit, the texture edit, the entry points on device memory).  One process drives one GPU (gnxr_init), or several behind every handle (gnxr_init_devices).
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -21,6 +21,7 @@
 #include "material_kernel.hip.h"
 #include "rebuild_kernel.hip.h"
 #include "geometry_kernel.hip.h"
+#include "lights_kernel.hip.h"
 #include "env_build_kernel.hip.h"
 #include "media_kernel.hip.h"
 #include "texture_build_kernel.hip.h"
@@ -290,6 +291,7 @@ int gnxr_trace_any(gnxr_scene *s, const gnxr_ray *rays, int64_t n, uint8_t *occl
 #include "api_edit.hip.h"
 #include "api_rebuild.hip.h"
 #include "api_geometry.hip.h"
+#include "api_lights.hip.h"
 #include "api_env.hip.h"
 #include "api_media.hip.h"
 #include "api_textures.hip.h"

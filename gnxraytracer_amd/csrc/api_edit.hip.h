@@ -125,7 +125,7 @@ static int build_light_update(const CompiledScene &cs, int first, int n, const g
     for (int k = 0; k < n; ++k) {
         const int i = first + k;
         const gnxr_light &was = cs.desc_lights[i], &l = in[k];
-        if (l.type != was.type) { set_error("light %d: the type of a light cannot change in place (%d -> %d)", i, was.type, l.type); return GNXR_ERR_UNSUPPORTED; }
+        if (l.type != was.type) { set_error("light %d: the type of a light cannot change in place (%d -> %d); gnxr_scene_set_lights replaces the list", i, was.type, l.type); return GNXR_ERR_UNSUPPORTED; }
         if (l.type == GNXR_LIGHT_INFINITE) {
             if (memcmp(&l, &was, sizeof(gnxr_light)) != 0) { set_error("light %d: an INFINITE light does not change through gnxr_scene_update_lights (gnxr_scene_update_environment rebuilds its tables)", i); return GNXR_ERR_UNSUPPORTED; }
             continue;
@@ -133,7 +133,7 @@ static int build_light_update(const CompiledScene &cs, int first, int n, const g
         Vec3 corners[3];
         int tri_leaf = -1;
         if (l.type == GNXR_LIGHT_AREA_TRI) {
-            if (l.tri != was.tri) { set_error("light %d: the triangle of an area light cannot change in place (%d -> %d)", i, was.tri, l.tri); return GNXR_ERR_UNSUPPORTED; }
+            if (l.tri != was.tri) { set_error("light %d: the triangle of an area light cannot change in place (%d -> %d); gnxr_scene_set_lights replaces the list", i, was.tri, l.tri); return GNXR_ERR_UNSUPPORTED; }
             const DLight &cur = cs.lights[i];
             tri_leaf = cur.tri_leaf;
             corners[0] = Vec3(cur.p0[0], cur.p0[1], cur.p0[2]); corners[1] = Vec3(cur.p1[0], cur.p1[1], cur.p1[2]); corners[2] = Vec3(cur.p2[0], cur.p2[1], cur.p2[2]);
@@ -147,7 +147,7 @@ static int build_light_update(const CompiledScene &cs, int first, int n, const g
 extern "C" int gnxr_scene_update_lights(gnxr_scene *s, int32_t first_light, int32_t n_lights, const gnxr_light *lights) {
     if (!s) { set_error("null scene"); return GNXR_ERR_INVALID; }
     if (n_lights > 0 && !lights) { set_error("null light array"); return GNXR_ERR_INVALID; }
-    const int64_t have = (int64_t)s->cs.desc_lights.size();   // (the number of lights never changes)
+    const int64_t have = (int64_t)s->cs.desc_lights.size();   // (the live count: gnxr_scene_set_lights changes it)
     if (first_light < 0 || n_lights < 0 || (int64_t)first_light + n_lights > have) {
         set_error("light range [%d, %lld) outside the scene's %lld lights", first_light, (long long)first_light + n_lights, (long long)have);
         return GNXR_ERR_INVALID;

@@ -114,7 +114,7 @@ extern "C" int gnxr_scene_update_environment(gnxr_scene *s, const gnxr_light *li
     int idx = -1;
     for (size_t i = 0; i < cs.desc_lights.size() && idx < 0; ++i)
         if (cs.desc_lights[i].type == GNXR_LIGHT_INFINITE) idx = (int)i;
-    if (idx < 0 || !cs.has_env) { set_error("the scene was created without an INFINITE light (the light list of a scene is fixed)"); return GNXR_ERR_UNSUPPORTED; }
+    if (idx < 0 || !cs.has_env) { set_error("the scene has no INFINITE light, and neither this call nor gnxr_scene_set_lights adds one: create the scene with it"); return GNXR_ERR_UNSUPPORTED; }
     if (!rgb && memcmp(light->le, cs.desc_lights[idx].le, sizeof(light->le)) != 0) {
         set_error("le of the environment light changes its texels: send the map again (the raw map is not retained)");
         return GNXR_ERR_INVALID;

@@ -182,7 +182,8 @@ struct gnxr_scene {
     // the lights and the environment map: what Sample_Li / Pdf_Li / Le read, without the selection table (grid, grid_table stay zero).
     // After the scene is created only the editing calls change what is behind these pointers: gnxr_scene_update_vertices refits the world radius
     // (cs.env, distant lights), GNXR_UPDATE_MOVE_LIGHTS moves the area lights, gnxr_scene_update_lights rewrites light records,
-    // gnxr_scene_update_environment swaps in new environment tables (and cs.env with them).
+    // gnxr_scene_update_environment swaps in new environment tables (and cs.env with them), gnxr_scene_set_lights swaps in another list
+    // (lights, infinite; the counts are read from the host scene here, at every call).
     DLightTables light_tables_static() const {
         DLightTables lt = {};
         lt.lights = lights.p;

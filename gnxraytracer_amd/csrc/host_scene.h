@@ -138,6 +138,13 @@ void refit_world_bound(CompiledScene *cs, const float root6[6]);
 // one DLight from its description, as compile_scene makes it (gnxr_scene_update_lights): for AREA_TRI from the corners of its triangle and
 // its leaf index; for INFINITE the record without the environment tables; false (error set) for an unknown type
 bool compile_light(const gnxr_light &l, int index, const Vec3 corners[3], int tri_leaf, const Box3 &world_bound, DLight *out);
+// A whole new light list for a live scene (gnxr_scene_set_lights), checked and compiled before anything of the scene is touched: recs gets
+// max(1, n) records as compile_scene makes them, except that an AREA_TRI record carries its AUTHORED triangle in tri_leaf and blank corners
+// (the device binds it to its leaf-order triangle and computes the rest: lights_kernel.hip.h, k_refit_lights); infinite the indices of the
+// INFINITE and SKYBOX records; light_of_prim per authored triangle the light that names it or -1.  Returns GNXR_OK, GNXR_ERR_INVALID (a
+// triangle out of range or named twice, an unknown type) or GNXR_ERR_UNSUPPORTED (an INFINITE record added, dropped, changed in any byte or
+// moved across a SKYBOX record: its tables are gnxr_scene_update_environment's), with the error set.
+int compile_light_list(const CompiledScene &cs, const gnxr_light *in, int n, std::vector<DLight> *recs, std::vector<int32_t> *infinite, std::vector<int32_t> *light_of_prim);
 // one DMedium from its description and, for a GRID medium, the maximum of its grid (GridDensityMedium.h:28-31: the fold from +0 over
 // std::max), as compile_scene makes it (gnxr_scene_update_media): sigma_t, w2m = Inverse(medium_to_world), inv_max_density = 1 / max_density.
 // density_offset is left 0: where the grid sits is the caller's.  false (error set) for an unknown type or an empty grid

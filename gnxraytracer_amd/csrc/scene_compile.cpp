@@ -700,6 +700,52 @@ bool compile_light(const gnxr_light &l, int index, const Vec3 corners[3], int tr
     return true;
 }
 
+// The light list of gnxr_scene_set_lights: compile_scene's lights section without the environment tables, for a scene that exists.
+int compile_light_list(const CompiledScene &cs, const gnxr_light *in, int n, std::vector<DLight> *recs, std::vector<int32_t> *infinite, std::vector<int32_t> *light_of_prim) {
+    const int nt = (int)cs.tri_material.size();
+    recs->resize((size_t)std::max(1, n));
+    memset(recs->data(), 0, sizeof(DLight) * recs->size());
+    infinite->clear();
+    light_of_prim->assign((size_t)nt, -1);
+    // the INFINITE light the scene has, and whether a SKYBOX light precedes it (build_env's flip_y: the texels the devices hold were made with it)
+    int cur_env = -1;
+    bool cur_sky = false;
+    for (size_t i = 0; i < cs.desc_lights.size() && cur_env < 0; ++i) {
+        if (cs.desc_lights[i].type == GNXR_LIGHT_INFINITE) cur_env = (int)i;
+        else if (cs.desc_lights[i].type == GNXR_LIGHT_SKYBOX) cur_sky = true;
+    }
+    if (cur_env < 0) cur_sky = false;
+    int new_env = -1;
+    bool sky = false;
+    const Vec3 blank[3] = {Vec3(0, 0, 0), Vec3(0, 0, 0), Vec3(0, 0, 0)};
+    for (int i = 0; i < n; ++i) {
+        const gnxr_light &l = in[i];
+        int tri = -1;
+        if (l.type == GNXR_LIGHT_AREA_TRI) {
+            if (l.tri < 0 || l.tri >= nt) { set_error("light %d: triangle %d outside the scene's %d triangles", i, l.tri, nt); return GNXR_ERR_INVALID; }
+            if ((*light_of_prim)[l.tri] >= 0) { set_error("light %d: triangle %d is already the triangle of light %d", i, l.tri, (*light_of_prim)[l.tri]); return GNXR_ERR_INVALID; }
+            (*light_of_prim)[l.tri] = i;
+            tri = l.tri;
+        } else if (l.type == GNXR_LIGHT_INFINITE) {
+            const char *how = "gnxr_scene_update_environment replaces or rotates the map of a scene created with an INFINITE light; gnxr_scene_set_lights keeps that light as it is";
+            if (cur_env < 0) { set_error("light %d: the scene has no INFINITE light and none can be added: its tables are not built here (%s)", i, how); return GNXR_ERR_UNSUPPORTED; }
+            if (new_env >= 0) { set_error("light %d: a second INFINITE light (light %d is one); only one is supported (%s)", i, new_env, how); return GNXR_ERR_UNSUPPORTED; }
+            if (memcmp(&l, &cs.desc_lights[cur_env], sizeof(gnxr_light)) != 0) { set_error("light %d: the INFINITE record differs from the scene's (%s)", i, how); return GNXR_ERR_UNSUPPORTED; }
+            if (sky != cur_sky) { set_error("light %d: whether a SKYBOX light precedes the INFINITE light decides the row order of its texels and cannot change (%s)", i, how); return GNXR_ERR_UNSUPPORTED; }
+            new_env = i;
+        } else if (l.type == GNXR_LIGHT_SKYBOX) {
+            sky = true;
+        }
+        if (!compile_light(l, i, blank, tri, cs.world_bound, &(*recs)[i])) return GNXR_ERR_INVALID;
+        if (l.type == GNXR_LIGHT_INFINITE || l.type == GNXR_LIGHT_SKYBOX) infinite->push_back(i);
+    }
+    if (cur_env >= 0 && new_env < 0) {
+        set_error("the new list drops the scene's INFINITE light: its tables are not released here (gnxr_scene_update_environment changes that light; a scene without it is a new scene)");
+        return GNXR_ERR_UNSUPPORTED;
+    }
+    return GNXR_OK;
+}
+
 void refit_world_bound(CompiledScene *cs, const float root6[6]) {
     cs->world_bound = Box3();
     cs->world_bound.lo = Vec3(root6[0], root6[1], root6[2]);
@@ -1474,7 +1520,7 @@ void build_light_grid(const CompiledScene &cs, int strategy, DLightGrid *grid, s
     grid->nvox[0] = grid->nvox[1] = grid->nvox[2] = 1;
     memcpy(grid->lo, &cs.world_bound.lo, 12);
     memcpy(grid->hi, &cs.world_bound.hi, 12);
-    if (nl == 0) { table->assign(1, 0.f); return; }
+    if (nl == 0) { table->assign(grid->stride, 0.f); return; }   // one blank record of the stride the grid announces (gnxr_light_grid_table copies that many floats)
     auto write_dist = [&](const float *func, float *dst) {
         std::vector<float> cdf(nl + 1);
         float funcInt;

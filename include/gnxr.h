@@ -407,13 +407,42 @@ int gnxr_scene_update_vertices_ex(gnxr_scene *scene, int32_t first_vertex, int32
  * description with those light records.  What may change: le, two_sided and n_samples of an AREA_TRI light (its corners, area and
  * normal stay those of the vertices the scene holds now, moved or not); every field of a POINT, SPOT or DISTANT light; center and
  * radius of a SKYBOX light.  GNXR_ERR_UNSUPPORTED for a record whose type differs from the light's, an AREA_TRI record whose tri
- * differs, or an INFINITE record that differs in any byte (the environment light changes through gnxr_scene_update_environment,
+ * differs (gnxr_scene_set_lights replaces the list), or an INFINITE record that differs in any byte (the environment light changes through gnxr_scene_update_environment,
  * which rebuilds its tables);
  * GNXR_ERR_INVALID for a null scene, a null lights with n_lights > 0 or a range outside the scene's lights.  Every refusal leaves the
  * scene exactly as it was: all records are built into a copy first.  The call takes the handle's render lock, writes the records of
  * every device of the scene and returns; the BVH, textures, tables and the path state of gnxr_render_reserve stay, the light-selection
  * table is rebuilt at the next render. */
 int gnxr_scene_update_lights(gnxr_scene *scene, int32_t first_light, int32_t n_lights, const gnxr_light *lights);
+/* Replace the scene's light list by lights[0 .. n_lights) (host memory): lights may be added, removed and retyped, and which triangles
+ * are emissive may change.  n_lights == 0 is allowed (lights may then be NULL).  Afterwards every result of the handle -- renders of all
+ * integrators, the ray counters, gnxr_li_device, gnxr_light_sample_device, gnxr_light_le_device, the feature buffers, the light-selection
+ * tables of all three strategies -- is bit for bit that of a scene created from the same description with this light list and the
+ * tri_light array that matches it.  Kept: the tree, materials, textures, media, the environment tables, the camera and the path state of
+ * gnxr_render_reserve.
+ * AREA_TRI: tri is a triangle of the mesh the scene holds now, in authoring order, [0, n_triangles); no two lights may name the same one.
+ * le, two_sided and n_samples come from the record; corners, area and normal from the vertices the scene holds now, computed on the
+ * device as gnxr_scene_update_vertices_ex computes them.  Triangles no light names stop being emissive.  A triangle with per-vertex
+ * normals or tangents cannot be emissive, as at creation.  POINT / SPOT / DISTANT / SKYBOX records are compiled against the current world
+ * bound, as gnxr_scene_update_lights compiles them.  INFINITE: its tables are not rebuilt here, so the new list must hold exactly as many
+ * INFINITE records as the scene has (0 or 1), byte-identical to the current one; its index may move, but whether a SKYBOX record precedes
+ * it may not (that decides the row order of its texels).  Anything else is GNXR_ERR_UNSUPPORTED: gnxr_scene_update_environment changes
+ * that light.
+ * GNXR_ERR_INVALID: a null scene, n_lights < 0, a null lights with n_lights > 0 (all before any device is touched); an unknown type; tri
+ * out of range or named twice; normals or tangents on a triangle made emissive.  GNXR_ERR_OOM.  Every record is checked before anything is
+ * written, and a call that fails later puts DTri::light -- the one table written in place -- back on every device: a refused or failed
+ * call leaves the scene as it was.  Limits that depend on an integrator (DirectLighting's and Whitted's 256 samples per vertex, the
+ * spatial table's memory) are checked by the render that meets them, as for a created scene.
+ * The AREA_TRI records are bound to their triangles on the device, on hip_stream (NULL: the null stream), in whatever leaf order the tree
+ * has: no tree or triangle table crosses to the host.  The call takes the handle's render lock and returns when every device of the scene
+ * holds the new list; the light-selection table is rebuilt at the next render.  To change the mesh and its emissive triangles together:
+ * gnxr_scene_set_lights with the non-area lights only, gnxr_scene_set_geometry with tri_light NULL or all -1, gnxr_scene_set_lights with
+ * the full list on the new triangles (three calls, not atomic: renders in between see fewer lights). */
+int gnxr_scene_set_lights(gnxr_scene *scene, const gnxr_light *lights, int32_t n_lights, void *hip_stream);
+/* Test hook: what the first device holds.  which 0: the light records, 112 bytes (28 words) each, n_lights of them; which 1: per triangle
+ * in authoring order the light it is (int32, -1: none).  *n_bytes receives the size; the table is copied when out is not NULL and
+ * capacity_bytes suffices. */
+int gnxr_scene_light_tables(gnxr_scene *scene, int32_t which, void *out, int64_t capacity_bytes, int64_t *n_bytes);
 /* Replace or rotate the environment map of the scene's INFINITE light.  `light` is the new record of that light: le, light_to_world and
  * n_samples may change, type must be GNXR_LIGHT_INFINITE.  rgb is the new map, width * height * 3 fp32, row-major, as decoded from .hdr
  * (the meaning of gnxr_scene_desc.env_rgb); its size may differ from the one the scene was created with.  rgb may be host memory or
@@ -436,8 +465,8 @@ int gnxr_scene_update_lights(gnxr_scene *scene, int32_t first_light, int32_t n_l
  * crosses the host when rgb is device memory.
  * GNXR_ERR_INVALID, before any device is touched, for a null scene, a null light, a type other than GNXR_LIGHT_INFINITE, rgb with
  * width <= 0 or height <= 0, a size whose guide-table entries would not fit uint16_t (2 * round_up_pow2(size) + 1 > 65535: more than
- * 16384 texels per side) and the le rule above; GNXR_ERR_UNSUPPORTED for a scene created without an INFINITE light (the light list is
- * fixed); GNXR_ERR_OOM. */
+ * 16384 texels per side) and the le rule above; GNXR_ERR_UNSUPPORTED for a scene without an INFINITE light (neither this call nor
+ * gnxr_scene_set_lights adds one); GNXR_ERR_OOM. */
 int gnxr_scene_update_environment(gnxr_scene *scene, const gnxr_light *light, const float *rgb, int32_t width, int32_t height, void *hip_stream);
 /* Rebuild the triangle BVH of an existing scene over the vertices it currently holds on the device (the state after any number of
  * gnxr_scene_update_vertices calls), entirely on the device: the tree, its 4-wide form, the primitive order and everything kept in
