@@ -1169,6 +1169,47 @@ class PathIntegrator:
         _check(lib().gnxr_render_views_device(scene._h, C.byref(p), cams, med, V, C.c_void_p(out.data_ptr() or None), C.c_void_p(stream or None), C.byref(st)))
         return out, stats_dict(st)
 
+    def RenderAdaptive(self, scene, width, height, spp, threshold, min_spp=16, step_spp=16, floor=0.01, guard=1, out=None, count_out=None, stream=None, **kw):
+        """Integrator::Render to a noise threshold (gnxr_render_adaptive_device): every pixel takes min_spp samples, then max(step_spp, n // 8)
+        more per round (n: what it has) while it -- or a pixel within `guard` pixels of it -- is noisy, up to the budget `spp`.  Sample s of a pixel is Render's.  A
+        pixel is noisy while e > threshold * (m + floor * n): e = the rgb sum of |S - 2 A| (S: its sum of Li over all n samples, A: over the
+        even ones), m = Sr + Sg + Sb.  Returns (image, count, stats): the float32 [H, W, 4] tensor of S / n (`out` when given), the int32
+        [H, W] tensor of n (`count_out` when given), both on the scene's device, and the stats dict of a render extended by `rounds`,
+        `samples` (the sum of n) and `pixels_at_budget`.  With min_spp == spp the image is Render's bit for bit.  Runs on `stream` (by
+        default torch's current stream) and returns once the outputs are written.  The other keyword arguments are Render's, without the
+        sample range and the shard fields; samples_per_pass = paths per sub-pass of a round, as for Li."""
+        import math
+        import torch
+        width, height, spp, min_spp, step_spp, guard = int(width), int(height), int(spp), int(min_spp), int(step_spp), int(guard)
+        threshold, floor = float(threshold), float(floor)
+        if width <= 0 or height <= 0:
+            raise ValueError(f"RenderAdaptive: invalid image size {width} x {height}")
+        if spp < 1 or not 1 <= min_spp <= spp:
+            raise ValueError(f"RenderAdaptive: spp >= 1 and min_spp in [1, spp] are required, got spp = {spp}, min_spp = {min_spp}")
+        if step_spp < 1:
+            raise ValueError(f"RenderAdaptive: step_spp must be at least 1, got {step_spp}")
+        if not 0 <= guard <= 8:
+            raise ValueError(f"RenderAdaptive: guard must lie in [0, 8], got {guard}")
+        if math.isnan(threshold) or threshold < 0 or math.isnan(floor) or floor < 0:
+            raise ValueError(f"RenderAdaptive: threshold and floor must be numbers >= 0, got {threshold} and {floor}")
+        unknown = [k for k in kw if k not in ("samples_per_pass", "passes_in_flight")]
+        if unknown:
+            raise ValueError(f"RenderAdaptive: unexpected arguments {unknown} (samples_per_pass, passes_in_flight)")
+        device = torch.device("cuda", scene.device)
+        hstream, tstream = _stream_pair(stream, device)
+        with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensors to the stream that writes them)
+            out = _out_tensor("RenderAdaptive: out", out, (height, width, 4), torch.float32, device)
+            count_out = _out_tensor("RenderAdaptive: count_out", count_out, (height, width), torch.int32, device)
+        p = self.params(width, height, spp, **kw)
+        ap = _abi.AdaptiveParams(C.sizeof(_abi.AdaptiveParams), min_spp, step_spp, guard, threshold, floor)
+        info = _abi.AdaptiveInfo(C.sizeof(_abi.AdaptiveInfo), 0, 0, 0)
+        st = Stats()
+        _check(lib().gnxr_render_adaptive_device(scene._h, C.byref(p), C.byref(ap), C.c_void_p(out.data_ptr() or None), C.c_void_p(count_out.data_ptr() or None),
+                                                 C.c_void_p(hstream or None), C.byref(st), C.byref(info)))
+        stats = stats_dict(st)
+        stats.update(rounds=info.rounds, samples=info.samples, pixels_at_budget=info.pixels_at_budget)
+        return out, count_out, stats
+
     AOV_CHANNELS = ("albedo", "normal", "shading_normal", "depth", "ids")
 
     def RenderAOV(self, scene, width, height, spp, cameras=None, media=None, channels=AOV_CHANNELS, out=None, stream=None, **kw):

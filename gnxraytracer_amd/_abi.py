@@ -135,6 +135,14 @@ class Geometry(C.Structure):   # gnxr_geometry: the arrays are host or device ad
                 ("tri_medium_inside", C.c_void_p), ("tri_medium_outside", C.c_void_p), ("tri_uv", C.c_void_p), ("tri_n", C.c_void_p), ("tri_s", C.c_void_p)]
 
 
+class AdaptiveParams(C.Structure):   # gnxr_adaptive_params (carries struct_size: not in gnxr_abi_sizeof's list)
+    _fields_ = [("struct_size", i32), ("min_spp", i32), ("step_spp", i32), ("guard", i32), ("threshold", f32), ("floor", f32)]
+
+
+class AdaptiveInfo(C.Structure):   # gnxr_adaptive_info (carries struct_size)
+    _fields_ = [("struct_size", i32), ("rounds", i32), ("samples", i64), ("pixels_at_budget", i64)]
+
+
 P = C.POINTER
 VP = C.c_void_p
 
@@ -179,6 +187,7 @@ PROTOTYPES = {
     "gnxr_li_device": (C.c_int, [VP, P(RenderParams), VP, VP, i64, VP, VP, P(Stats)]),   # device addresses + hipStream_t
     "gnxr_render_views_device": (C.c_int, [VP, P(RenderParams), P(Camera), P(i32), i32, VP, VP, P(Stats)]),   # cameras, media: host; images: device
     "gnxr_render_aov_device": (C.c_int, [VP, P(RenderParams), P(Camera), P(i32), i32, P(AovBuffers), VP, P(Stats)]),   # cameras, media: host; buffers: device
+    "gnxr_render_adaptive_device": (C.c_int, [VP, P(RenderParams), P(AdaptiveParams), VP, VP, VP, P(Stats), P(AdaptiveInfo)]),   # image, counts: device; hipStream_t
     "gnxr_material_albedo": (C.c_int, [P(Material), P(f32)]),
     "gnxr_camera_rays_device": (C.c_int, [P(Camera), i32, i32, i32, VP, VP, VP, i64, VP, VP, VP]),   # device addresses + hipStream_t
     "gnxr_bsdf_device": (C.c_int, [VP, VP, VP, VP, VP, i64, i32, VP, VP]),   # device addresses + hipStream_t

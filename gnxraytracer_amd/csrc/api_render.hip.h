@@ -56,6 +56,26 @@ struct ViewSource {
     int n_views;
 };
 
+// gnxr_render_adaptive_device: the pixels of render_one's loops when they stop at different sample counts (adaptive_kernel.hip.h,
+// api_adaptive.hip.h).  The call works in rounds; the unit of work of a round is one path (as for caller rays), path j of a round being
+// sample n0 + j / n_active of active pixel j % n_active, and a finished chunk is added to the per-pixel sums in chunk order.
+struct PixelListSource {
+    gnxr_adaptive_params ap;
+    int32_t *count_out;           // device memory, (H, W) int32, or nullptr
+    PixelRound round;             // the round in progress (run_adaptive)
+    int rounds;                   // what the call did (run_adaptive): rounds, samples over all pixels, pixels that reached spp
+    long long samples, at_budget;
+};
+
+// The schedule: samples a round gives every active pixel that has taken n0 so far.  Round 0 takes min_spp; a later round step_spp, or an
+// eighth of what the pixel has (rounded down) where that is more, cut at the budget.  The growing steps keep the number of rounds
+// logarithmic in spp / step_spp -- every round ends with a drain of the path loop ("Adaptive sampling") -- and a late decision
+// comes at most 12.5 % of a pixel's samples after the point where a fixed step would have taken it.
+constexpr int kAdaptiveGrowth = 8;
+static int adaptive_round_samples(const gnxr_adaptive_params &ap, int spp, int n0) {
+    return n0 == 0 ? ap.min_spp : std::min(std::max(ap.step_spp, n0 / kAdaptiveGrowth), spp - n0);
+}
+
 // ---- the launch plan ----
 // What render_one decides before it allocates or enqueues anything.  plan_render() fills the part that needs no device (it runs before the
 // handle is locked), RenderPlan::size_passes() the pass sizes, which depend on the free device memory (after the bind and the light grid).
@@ -72,6 +92,7 @@ struct RenderPlan {
     unsigned kind_queue;                        // byte k: the shade queue of the class-1 materials of kind k (k_compact<COMPACT_HITCLASS>)
     bool caller_rays;                           // RaySource: no image
     int n_views;                                // ViewSource: views of the call, else 0
+    bool pixel_list;                            // PixelListSource: rounds over lists of pixels; a unit is one path, unit_end the paths of the largest round
     int local_rows, npix;
     long long unit, unit_begin, unit_end;       // the unit of work the loops cut into passes: one sample of every pixel (npix paths), or one caller ray
     int spill_entries;                          // deepest traversal stack either BVH layout can need (sizes trace_spill)
@@ -123,7 +144,7 @@ static const double kStateFreeFraction = 0.45;                              // o
 static const unsigned long long kStateCapBytes = 150ull * 1000 * 1000 * 1000;   // never more path state than this
 
 // Validates the parameters and derives what follows from them and the scene alone.  No device is touched.
-static int plan_render(const CompiledScene &cs, const gnxr_render_params *pin, const RaySource *src, const ViewSource *views, RenderPlan *out) {
+static int plan_render(const CompiledScene &cs, const gnxr_render_params *pin, const RaySource *src, const ViewSource *views, const PixelListSource *pix, RenderPlan *out) {
     RenderPlan &pl = *out;
     gnxr_render_params &p = pl.p;
     p = *pin;
@@ -167,6 +188,12 @@ static int plan_render(const CompiledScene &cs, const gnxr_render_params *pin, c
         set_error("Li for caller rays: Whitted, DirectLighting and VolPath need camera ray differentials on scenes with image textures");
         return GNXR_ERR_UNSUPPORTED;
     }
+    if (pix && pl.textured_scene && (pl.whitted || pl.volpath)) {
+        // (their shade kernels find the camera's ray differentials through slot % npix: whitted_kernel.hip.h / vol_kernel.hip.h; the slots
+        // of a round hold a list of pixels.  PathIntegrator drops the differentials)
+        set_error("adaptive: Whitted, DirectLighting and VolPath take the pixel of a path from its slot on scenes with image textures; PathIntegrator renders them");
+        return GNXR_ERR_UNSUPPORTED;
+    }
     if (views && pl.textured_scene && pl.volpath) {
         // (k_vol_step recomputes the camera's offset rays at the first surface from DRender::cam, vol_kernel.hip.h: the one camera read
         // inside a shade kernel.  Whitted / DirectLighting store them per path at raygen, PathIntegrator drops them: both render views)
@@ -185,9 +212,16 @@ static int plan_render(const CompiledScene &cs, const gnxr_render_params *pin, c
     pl.n_views = views ? views->n_views : 0;
     pl.local_rows = count_local_rows(&p);
     pl.npix = views ? views->n_views * p.width * p.height : pl.local_rows * p.width;
-    pl.unit = src ? 1 : pl.npix;
-    pl.unit_begin = src ? 0 : p.spp_begin;
+    pl.pixel_list = pix != nullptr;
+    pl.unit = (src || pix) ? 1 : pl.npix;
+    pl.unit_begin = (src || pix) ? 0 : p.spp_begin;
     pl.unit_end = src ? src->n : p.spp_end;
+    // the largest round: the one with the most samples, with no pixel stopped yet (run_adaptive rewrites unit_end for every round)
+    if (pix) {
+        int most = 0;
+        for (int n0 = 0; n0 < p.spp;) { const int ns = adaptive_round_samples(pix->ap, p.spp, n0); most = std::max(most, ns); n0 += ns; }
+        pl.unit_end = (long long)pl.npix * most;
+    }
     pl.spill_entries = std::max(cs.stack4_need + 1, cs.bvh_max_depth + 2);
     pl.k = pl.in_flight = 0;
     pl.half = pl.cap = pl.nrec = 0;
@@ -198,6 +232,20 @@ static int plan_render(const CompiledScene &cs, const gnxr_render_params *pin, c
 // 32-bit work indices.  slots_held: path slots this handle already owns; free_b: free device memory (have_mem: the query succeeded).
 int RenderPlan::size_passes(size_t slots_held, bool have_mem, size_t free_b) {
     const long long n_units = unit_end - unit_begin;
+    if (pixel_list && p.samples_per_pass <= 0) {
+        // Rounds of pixel lists, auto: plan the render these parameters describe (a unit = one sample of every pixel) and live in its
+        // slots -- what gnxr_render_reserve allocates for that render then holds every round.  A round that fits them is ONE sub-pass:
+        // a round ends with a drain whatever its cut, and every staggered start only adds loop turns to it (measured: DESIGN.md,
+        // "Adaptive sampling").  A larger round (min_spp near spp) takes the render's own sub-passes.
+        RenderPlan rp = *this;
+        rp.pixel_list = false; rp.unit = npix; rp.unit_begin = 0; rp.unit_end = p.spp;
+        if (int rc = rp.size_passes(slots_held, have_mem, free_b)) return rc;
+        const bool fits = n_units <= (long long)rp.cap;
+        k = fits ? (int)n_units : (int)rp.half;
+        in_flight = fits ? 1 : (int)std::min<long long>(rp.in_flight, (n_units + k - 1) / k);
+        half = (size_t)k; cap = (size_t)in_flight * half; nrec = rp.nrec;   // (cap <= rp.cap: the render's index checks cover it)
+        return GNXR_OK;
+    }
     k = p.samples_per_pass;
     if (k <= 0) {
         // auto.  PathIntegrator: sub-passes of ~64 M paths, four of them in flight (below) -- launches stay thick because they mix the
@@ -223,6 +271,9 @@ int RenderPlan::size_passes(size_t slots_held, bool have_mem, size_t free_b) {
         const int n_subs = (int)std::min<long long>(kMaxRegions, (n_units + k - 1) / k);
         in_flight = p.passes_in_flight > 0 ? p.passes_in_flight : (Knobs::regions() > 0 ? Knobs::regions() : 4);
         in_flight = std::max(1, std::min(std::min(in_flight, kMaxRegions), n_subs));
+        // pixel lists with samples_per_pass = paths per sub-pass: never more slots than one pass of the render that takes the number as
+        // samples per pixel (gnxr_render_reserve with the same parameters)
+        if (pixel_list && p.samples_per_pass > 0) in_flight = (int)std::max<long long>(1, std::min<long long>(in_flight, (long long)npix * std::min(p.samples_per_pass, p.spp) / k));
         for (; in_flight > 1; --in_flight) {
             const unsigned long long want = (unsigned long long)in_flight * half, held = (unsigned long long)slots_held;
             const bool idx_ok = want < (1ull << 31) && want * 3ull < (1ull << 32);
@@ -276,7 +327,8 @@ int RenderState::reserve(const RenderPlan &pl) {
     // global part of k_trace's traversal stacks (the deepest walk either BVH layout can need), sized for a full grid
     if ((rc = trace_spill.alloc((size_t)g_num_cus * g_trace_blocks_per_cu * kBlock * (size_t)pl.spill_entries)) != GNXR_OK) return rc;
     if (!pl.caller_rays && (rc = accum.alloc(pl.npix)) != GNXR_OK) return rc;
-    const size_t max_tiles = (cap + kCompactTile - 1) / kCompactTile;
+    // (pixel lists: the compaction that lists the next round's pixels runs over the image)
+    const size_t max_tiles = (std::max(cap, pl.pixel_list ? (size_t)pl.npix : (size_t)0) + kCompactTile - 1) / kCompactTile;
     if (tile_desc.n < kCompactMaxOut * max_tiles || !tile_desc.p) {   // fresh memory: every descriptor "not ready" (tag 0 belongs to no compaction)
         if ((rc = tile_desc.alloc(kCompactMaxOut * max_tiles)) != GNXR_OK) return rc;
         HIP_TRY(hipMemset(tile_desc.p, 0, tile_desc.n * sizeof(unsigned long long)));
@@ -348,9 +400,10 @@ struct RenderRun {
     gnxr_scene *s;
     RenderState &st;
     hipStream_t stream;
-    const RenderPlan &pl;
+    const RenderPlan &pl;       // (a PixelListSource's rounds: run_adaptive sets unit_begin / unit_end of this plan before each run of the loops)
     const RaySource *src;
     const ViewSource *views;
+    const PixelListSource *pix;
     DScene sc;
     DRender r;
     PathArrays pa;
@@ -370,8 +423,9 @@ struct RenderRun {
     unsigned long long new_paths = 0;   // PathIntegrator: camera rays started (their count is known to the host; the other rays are counted on the device)
     unsigned int launches = 0, passes = 0, loop_iterations = 0;
 
-    RenderRun(gnxr_scene *scene, hipStream_t stream_, const RenderPlan &plan, const RaySource *src_, const ViewSource *views_, const DScene &sc_, const DRender &r_)
-        : s(scene), st(scene->st), stream(stream_), pl(plan), src(src_), views(views_), sc(sc_), r(r_), pa(st.path_arrays()), va(st.vol_arrays()),
+    RenderRun(gnxr_scene *scene, hipStream_t stream_, const RenderPlan &plan, const RaySource *src_, const ViewSource *views_, const PixelListSource *pix_, const DScene &sc_,
+              const DRender &r_)
+        : s(scene), st(scene->st), stream(stream_), pl(plan), src(src_), views(views_), pix(pix_), sc(sc_), r(r_), pa(st.path_arrays()), va(st.vol_arrays()),
           wa(st.whitted_arrays(plan, (int)scene->cs.desc_lights.size())), mt(scene->media_tables()), dctr(scene->counters.p), spheres(scene->cs.n_spheres > 0),
           n_lights((int)scene->cs.desc_lights.size()), n_scene_media((int)scene->cs.media.size()) {}
 
@@ -568,13 +622,15 @@ int RenderRun::shade_stage(const int *q_in, int n, int *q_out, const unsigned *n
 // [u0, u0 + kk) in the slots of `at`, and hand the radiance of a finished (sub-)pass -- L by slot -- to the image or to the caller.
 void RenderRun::raygen(const PathArrays &at, long long u0, int kk, unsigned char *medium_keys) {
     const int n_new = (int)(pl.unit * kk);
-    if (views) hipLaunchKernelGGL(k_raygen_views, dim3(grid_for(n_new)), dim3(kBlock), 0, stream, sc, r, (const DCamera *)st.view_cams.p, at, n_new, (int)u0, medium_keys);
+    if (pix) hipLaunchKernelGGL(k_raygen_pixels, dim3(grid_for(n_new)), dim3(kBlock), 0, stream, sc, r, at, pix->round, n_new, u0);
+    else if (views) hipLaunchKernelGGL(k_raygen_views, dim3(grid_for(n_new)), dim3(kBlock), 0, stream, sc, r, (const DCamera *)st.view_cams.p, at, n_new, (int)u0, medium_keys);
     else if (!src) hipLaunchKernelGGL(k_raygen, dim3(grid_for(n_new)), dim3(kBlock), 0, stream, sc, r, at, n_new, (int)u0);
     else hipLaunchKernelGGL(k_raygen_rays, dim3(grid_for(n_new)), dim3(kBlock), 0, stream, sc, r, at, reinterpret_cast<const float4 *>(src->rays + u0),
                             reinterpret_cast<const int4 *>(src->samples + u0), n_new, n_scene_media, medium_keys, dctr, u0);
 }
 void RenderRun::resolve(const PathArrays &at, long long u0, int kk) {
-    if (!src) hipLaunchKernelGGL(k_resolve, dim3(grid_for(r.npix)), dim3(kBlock), 0, stream, at, st.accum.p, r.npix, kk);
+    if (pix) hipLaunchKernelGGL(k_adaptive_accum, dim3(grid_for(pix->round.n_active)), dim3(kBlock), 0, stream, (const float4 *)at.L, pix->round, kk, u0, st.accum.p, st.ad_A.p);
+    else if (!src) hipLaunchKernelGGL(k_resolve, dim3(grid_for(r.npix)), dim3(kBlock), 0, stream, at, st.accum.p, r.npix, kk);
     else hipLaunchKernelGGL(k_store_li, dim3(grid_for(kk)), dim3(kBlock), 0, stream, (const float4 *)at.L, reinterpret_cast<const int4 *>(src->samples + u0), r,
                             n_scene_media, kk, reinterpret_cast<float4 *>(src->L) + u0);
 }
@@ -940,11 +996,14 @@ static void fill_stats(const RenderRun &run, double seconds_render, double secon
 // reserve_only: stop after the allocations (gnxr_render_reserve).
 // src != nullptr: Li for the caller's rays instead (gnxr_li_device); `d_rgba_out` is then unused.
 // views != nullptr: the views' cameras instead of the scene's (gnxr_render_views_device); `d_rgba_out` holds n_views images.
+// pix != nullptr: rounds over lists of pixels instead of passes over the image (gnxr_render_adaptive_device, run_adaptive).
+static int run_adaptive(RenderRun &run, RenderPlan &pl, PixelListSource &pix, void *d_rgba_out);
+static void adaptive_stats(const PixelListSource &pix, gnxr_stats *stats);
 static int render_one(gnxr_scene *s, const gnxr_render_params *pin, void *d_rgba_out, void *hip_stream, gnxr_stats *stats, bool reserve_only = false,
-                      const RaySource *src = nullptr, const ViewSource *views = nullptr) {
+                      const RaySource *src = nullptr, const ViewSource *views = nullptr, PixelListSource *pix = nullptr) {
     if (!s || !pin || (!d_rgba_out && !src)) { set_error("null argument"); return GNXR_ERR_INVALID; }
     RenderPlan pl;
-    int rc = plan_render(s->cs, pin, src, views, &pl);
+    int rc = plan_render(s->cs, pin, src, views, pix, &pl);
     if (rc) return rc;
     const gnxr_render_params &p = pl.p;
     std::lock_guard<std::recursive_mutex> lock(s->render_mutex);
@@ -978,9 +1037,11 @@ static int render_one(gnxr_scene *s, const gnxr_render_params *pin, void *d_rgba
         if ((rc = pl.size_passes(s->st.L.n, have_mem, free_b)) != GNXR_OK) return rc;
     }
     if ((rc = s->st.reserve(pl)) != GNXR_OK) return rc;
+    if (pix && (rc = s->st.reserve_adaptive(pl)) != GNXR_OK) return rc;
+    if (pix && !s->h_ad_count && hipHostMalloc((void **)&s->h_ad_count, sizeof(unsigned int)) != hipSuccess) { s->h_ad_count = nullptr; set_error("hipHostMalloc failed"); return GNXR_ERR_OOM; }
     if (reserve_only) { if (stats) memset(stats, 0, sizeof(*stats)); return GNXR_OK; }
 
-    RenderRun run(s, stream, pl, src, views, sc, r);
+    RenderRun run(s, stream, pl, src, views, pix, sc, r);
     run.list_media = pl.volpath && (src || views_mixed_media);
     // (stream-ordered: the table is read by this call's raygen kernels only, and the call returns after the stream has drained)
     if (views) HIP_TRY(hipMemcpyAsync(s->st.view_cams.p, s->h_view_cams.data(), (size_t)views->n_views * sizeof(DCamera), hipMemcpyHostToDevice, stream));
@@ -991,8 +1052,9 @@ static int render_one(gnxr_scene *s, const gnxr_render_params *pin, void *d_rgba
     HIP_TRY(hipEventCreate(&ev.a));
     HIP_TRY(hipEventCreate(&ev.b));
     HIP_TRY(hipEventRecord(ev.a, stream));
-    if ((rc = pl.path_int() ? run_path_loop(run) : run_passes(run)) != GNXR_OK) return rc;
-    if (!src) {
+    if (pix) { if ((rc = run_adaptive(run, pl, *pix, d_rgba_out)) != GNXR_OK) return rc; }
+    else if ((rc = pl.path_int() ? run_path_loop(run) : run_passes(run)) != GNXR_OK) return rc;
+    if (!src && !pix) {
         hipLaunchKernelGGL(k_finish, dim3(grid_for(r.npix)), dim3(kBlock), 0, stream, r, (const float4 *)s->st.accum.p, (float4 *)d_rgba_out);
         ++run.launches;
     }
@@ -1005,6 +1067,7 @@ static int render_one(gnxr_scene *s, const gnxr_render_params *pin, void *d_rgba
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
     if (stats) fill_stats(run, ms * 1e-3, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(), stats);
+    if (stats && pix) adaptive_stats(*pix, stats);
     if (src && s->h_counters->li_bad) {
         set_error("gnxr_li_device: sample record %llu is out of range (px in [0, %d), py in [0, %d), s in [0, %d), medium in [-1, %d)); its L is (0, 0, 0, 0)",
                   ~s->h_counters->li_bad, p.width, p.height, p.spp, run.n_scene_media);

@@ -31,8 +31,16 @@ struct RenderState {
     DevBuf<float> wh_pdf;
     DevBuf<int> wh_rec;
     DevBuf<DCamera> view_cams;   // gnxr_render_views_device: the DCamera record of every view
+    // gnxr_render_adaptive_device (adaptive_kernel.hip.h): per pixel the sums over the even samples (the sums over all samples and the count
+    // live in accum), the two state bytes and the two list entries; the totals of the compaction that lists a round's pixels.  Allocated
+    // by the first adaptive call of a size (reserve_adaptive), 26 bytes per pixel; other renders never touch them.
+    DevBuf<float4> ad_A;
+    DevBuf<unsigned char> ad_state[2];
+    DevBuf<int> ad_list[2];
+    DevBuf<unsigned int> ad_totals;
 
     int reserve(const RenderPlan &pl);
+    int reserve_adaptive(const RenderPlan &pl);
     static unsigned long long state_bytes(const RenderPlan &pl);
     // the kernels' views of the arrays
     PathArrays path_arrays();
@@ -84,6 +92,7 @@ struct gnxr_scene {
     DevBuf<float4> out;        // gnxr_render: the image on the device
     DevBuf<Counters> counters;
     Counters *h_counters = nullptr;  // pinned
+    unsigned int *h_ad_count = nullptr;   // pinned: the size of an adaptive call's next round (run_adaptive), allocated by the first such call
     // the device-driven PathIntegrator loop: lagging copies of the counters (pinned ring, one event per slot) -- the host reads them
     // without ever waiting for the iteration it has just enqueued
     // k_shade runs one kernel per material class; the classes are independent, so they go to different streams and fill each other's ends
@@ -171,6 +180,7 @@ struct gnxr_scene {
     }
     ~gnxr_scene() {
         if (h_counters) (void)hipHostFree(h_counters);
+        if (h_ad_count) (void)hipHostFree(h_ad_count);
         if (h_ring) (void)hipHostFree(h_ring);
         if (h_stage) (void)hipHostFree(h_stage);
         for (hipEvent_t e : ring_ev) if (e) (void)hipEventDestroy(e);

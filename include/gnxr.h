@@ -640,7 +640,10 @@ int gnxr_render_device(gnxr_scene *scene, const gnxr_render_params *params, void
 
 /* Allocates, on every device of the handle, the path state a render with these parameters needs, without rendering anything: the
  * first gnxr_render / gnxr_render_device call with them then runs at its steady-state speed (the reference has no counterpart: its
- * per-thread MemoryArena grows inside Render, core/Integrator.cpp:262).  State buffers only ever grow; they are released with the scene. */
+ * per-thread MemoryArena grows inside Render, core/Integrator.cpp:262).  State buffers only ever grow; they are released with the scene.
+ * It covers the path state of gnxr_render_adaptive_device with the same parameters too, but not that call's 26 bytes per pixel of
+ * its own (sums over the even samples, state bytes, lists) nor its pinned count word: the first adaptive call of a size allocates
+ * them inside the call -- run one small-budget adaptive call up front where the first frame must not allocate. */
 int gnxr_render_reserve(gnxr_scene *scene, const gnxr_render_params *params);
 
 /* -- Aggregate seam (replaces Scene::Intersect / Scene::IntersectP), batched ------------ */
@@ -773,6 +776,49 @@ typedef struct gnxr_aov_buffers {   /* device pointers; NULL = channel not wante
 int gnxr_render_aov_device(gnxr_scene *scene, const gnxr_render_params *params, const gnxr_camera *cameras, const int32_t *camera_media,
                            int32_t n_views, const gnxr_aov_buffers *out, void *hip_stream, gnxr_stats *stats);
 int gnxr_material_albedo(const gnxr_material *m, float rgb[3]);
+
+/* -- Adaptive sampling on device memory: render to a noise threshold, per-pixel sample counts ------------------------------
+ * gnxr_render_adaptive_device renders the scene's camera like gnxr_render_device, but lets every pixel stop as soon as its two
+ * half estimates agree.  params->spp is the sample budget and the samplesPerPixel of the HaltonSampler: sample s of pixel (x, y)
+ * is the camera sample of gnxr_render_device -- the same Halton index, camera ray and Li.
+ * Per pixel: S = rgb fp32 sums of Li over its samples s = 0, 1, 2, ... in that order from +0 (what a render accumulates), A = the
+ * same sums over the even s only, n = samples taken, active = true.  Round 0 gives every pixel samples [0, min_spp); each later
+ * round gives every active pixel, which has n samples, its next max(step_spp, n / 8) samples (integer division), cut at spp: the
+ * steps grow with n once n exceeds 8 step_spp, so that the number of rounds -- each ends with a drain of the device -- stays
+ * logarithmic in spp / step_spp, and a late decision comes at most an eighth of a pixel's samples late.  After a round every pixel that was active in it computes,
+ * in single fp32 operations in the written order (no fused multiply-add, no division, no square root):
+ *     e = (|Sr - (Ar + Ar)| + |Sg - (Ag + Ag)|) + |Sb - (Ab + Ab)|
+ *     m = (Sr + Sg) + Sb
+ *     bound = threshold * (m + floor * (float)n)
+ *     noisy = !(e <= bound)                                   (a NaN keeps the pixel sampling)
+ * and then active' = active && n < spp && (some pixel q with |qx - x| <= guard and |qy - y| <= guard inside the image has
+ * active_q && noisy_q).  A pixel that has stopped never restarts; the call ends when no pixel is active.  Note that threshold = 0
+ * still stops a pixel whose e is exactly 0.
+ * Outputs (device memory): d_rgba_out, (H, W, 4) fp32 in the layout of gnxr_render_device, pixel = (Sr / (float)n, Sg / (float)n,
+ * Sb / (float)n, 1); d_count_out, (H, W) int32 = n, may be NULL.  With min_spp == spp the image and the ray counters are those of
+ * gnxr_render_device bit for bit.  info (host memory, required): rounds run, samples = the sum of n, pixels_at_budget = pixels with
+ * n == spp.  stats is filled as by a render: camera_samples = the sum of n, the ray counters are the sums over all rounds.
+ * Of params: spp_begin and spp_end must be 0; shard_index 0, shard_count and shard_rows 0 or 1; samples_per_pass = PATHS per
+ * sub-pass of a round, as for gnxr_li_device (0 = auto: a round is one sub-pass while it fits the path state of a render with these params, else that render's sub-passes);
+ * passes_in_flight keeps its meaning; the results depend on neither.  All four integrators are supported; on a scene with image
+ * textures PathIntegrator is supported, Whitted, DirectLighting and VolPath return GNXR_ERR_UNSUPPORTED (their shade kernels
+ * find the camera's ray differentials through the slot of a path, as for gnxr_li_device).
+ * Memory: 42 bytes per pixel of state (S and n, A, two state bytes, two list entries), of which 26 are allocated by the handle's
+ * first adaptive call of a size; nothing grows with width*height*spp.  Path state comes from the handle's buffers, sized for the
+ * largest round, and never exceeds what gnxr_render_reserve allocates for the same gnxr_render_params.  The host reads one
+ * 4-byte count per round (the size of the next round) and nothing else.
+ * Locking, ordering and device selection as for gnxr_render_views_device: one render per handle at a time, queued after what
+ * hip_stream holds, back when the outputs are written; with gnxr_init_devices the call runs on the copy of the scene on the
+ * device that holds d_rgba_out.
+ * GNXR_ERR_INVALID, before anything is queued (the outputs stay untouched): a null scene, params, adaptive, d_rgba_out or info; a
+ * struct_size other than sizeof of its record; an output that is not device memory, on a device without a copy of the scene, on
+ * another device than the other, or misaligned (16 bytes for d_rgba_out, 4 for d_count_out); invalid params or shard fields;
+ * min_spp outside [1, spp], step_spp < 1, guard outside [0, 8], threshold or floor negative or NaN.
+ * The two records carry struct_size, like gnxr_geometry; they are not part of gnxr_abi_sizeof's list.                          */
+typedef struct gnxr_adaptive_params { int32_t struct_size, min_spp, step_spp, guard; float threshold, floor; } gnxr_adaptive_params;
+typedef struct gnxr_adaptive_info { int32_t struct_size, rounds; int64_t samples; int64_t pixels_at_budget; } gnxr_adaptive_info;
+int gnxr_render_adaptive_device(gnxr_scene *scene, const gnxr_render_params *params, const gnxr_adaptive_params *adaptive, void *d_rgba_out,
+                                int32_t *d_count_out, void *hip_stream, gnxr_stats *stats, gnxr_adaptive_info *info);
 
 /* -- Shading queries on device memory: the pieces an integrator is made of, batched -------------------------------------
  * Same conventions as the device calls of the Aggregate seam: every array is device memory of one device that holds a copy of the
