@@ -1256,6 +1256,43 @@ class PathIntegrator:
                                             C.byref(st)))
         return res, stats_dict(st)
 
+    def RenderDenoised(self, scene, width, height, spp, cameras=None, media=None, normal="shading_normal", stream=None, **denoise_kw):
+        """A render at a low sample count, filtered on the device: the two halves [0, spp/2) and [spp/2, spp) of the samples (RenderViews
+        when `cameras` are given, else gnxr_render_device through the scene's own camera), RenderAOV over all samples for albedo, the
+        normal channel `normal` ("shading_normal" or "normal") and depth, then denoise(half_a, half_b, albedo, normal, depth), all on
+        `stream` (by default torch's current stream).  spp must be even and at least 2.  Returns (image, stats): the float32 tensor
+        (H, W, 4) -- (V, H, W, 4) with cameras -- and the field-wise sum of the two renders' stats dicts plus "aov", the dict of the
+        RenderAOV call.  The other keyword arguments are denoise's (iterations, the sigmas, out)."""
+        import torch
+        spp = int(spp)
+        if spp < 2 or spp % 2:
+            raise ValueError(f"RenderDenoised: spp must be even and at least 2 (the two halves are the variance estimate), got {spp}")
+        if normal not in ("shading_normal", "normal"):
+            raise ValueError(f"RenderDenoised: normal must be 'shading_normal' or 'normal', got {normal!r}")
+        if cameras is None and media is not None:
+            raise ValueError("RenderDenoised: media goes with cameras; the scene's own camera sits in the scene's camera medium")
+        unknown = [k for k in denoise_kw if k not in ("iterations", "sigma_color", "sigma_normal", "sigma_depth", "out")]
+        if unknown:
+            raise ValueError(f"RenderDenoised: unexpected arguments {unknown} (iterations, sigma_color, sigma_normal, sigma_depth, out)")
+        cameras, media, width, height = _view_args("RenderDenoised", cameras, media, width, height)
+        device = torch.device("cuda", scene.device)
+        hstream, tstream = _stream_pair(stream, device)
+        halves, stats = [], []
+        for lo, hi in ((0, spp // 2), (spp // 2, spp)):
+            if cameras is not None:
+                img, st = self.RenderViews(scene, cameras, width, height, spp, media=media, stream=tstream, spp_begin=lo, spp_end=hi)
+            else:
+                with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensor to the stream that writes it)
+                    img = torch.zeros((height, width, 4), dtype=torch.float32, device=device)
+                st = self.RenderDevice(scene, img.data_ptr(), width, height, spp, stream=hstream, spp_begin=lo, spp_end=hi)
+            halves.append(img)
+            stats.append(st)
+        aov, aov_stats = self.RenderAOV(scene, width, height, spp, cameras=cameras, media=media, channels=("albedo", normal, "depth"), stream=tstream)
+        image = denoise(halves[0], halves[1], albedo=aov["albedo"], normal=aov[normal], depth=aov["depth"], stream=tstream, **denoise_kw)
+        total = {k: stats[0][k] + stats[1][k] for k in stats[0]}
+        total["aov"] = aov_stats
+        return image, total
+
     def Render(self, scene, width, height, spp, **kw):
         """Integrator::Render: returns (float32 image [H, W, 4], stats dict)."""
         p = self.params(width, height, spp, **kw)
@@ -1353,6 +1390,47 @@ def camera_rays_device(camera, width, height, px, py, s, medium=-1, stream=None)
                                          C.c_void_p(s.data_ptr() or None), n, C.c_void_p(rays.data_ptr() or None), C.c_void_p(samples.data_ptr() or None),
                                          C.c_void_p(st or None)))
     return rays, samples
+
+
+def denoise(color, color_b=None, albedo=None, normal=None, depth=None, iterations=5, sigma_color=4.0, sigma_normal=0.25, sigma_depth=0.01, out=None, stream=None):
+    """The edge-avoiding a-trous filter on device memory (gnxr_denoise_device; the definition, operation by operation: include/gnxr.h).
+    `color`: a contiguous float32 tensor (H, W, 4) or (V, H, W, 4) on a GPU -- the image, or with `color_b` the first of two shares of
+    it (renders of the sample ranges [0, N/2) and [N/2, N) of spp = N: they add up to the image and their difference estimates its
+    variance, which then steers the colour weight).  Guides, all optional and of color's shape and device: `albedo` (rgb + coverage:
+    the image is divided by it before and multiplied after), `normal` (either normal channel of RenderAOV), `depth` ((H, W) or
+    (V, H, W)).  `iterations` in [1, 8]: iteration i filters with a 5 x 5 kernel at distance 2^i.  A sigma of 0 switches its term off.
+    Returns the filtered float32 tensor of color's shape: `out` when given, which may be `color` or `color_b` but no guide.  Queued on
+    `stream` (by default torch's current stream); the call does not wait for the GPU.  Malformed arguments raise ValueError."""
+    import math
+    import torch
+    if not (isinstance(color, torch.Tensor) and color.is_cuda and color.dtype == torch.float32 and color.dim() in (3, 4) and color.shape[-1] == 4 and color.is_contiguous()):
+        raise ValueError(f"denoise: color must be a contiguous float32 (H, W, 4) or (V, H, W, 4) tensor on a GPU, got "
+                         f"{type(color).__name__} {getattr(color, 'dtype', None)} {tuple(getattr(color, 'shape', ()))} on {getattr(color, 'device', None)}")
+    shape = tuple(color.shape)
+    for what, x, want in (("color_b", color_b, shape), ("albedo", albedo, shape), ("normal", normal, shape), ("depth", depth, shape[:-1])):
+        if x is not None and not (isinstance(x, torch.Tensor) and x.device == color.device and x.dtype == torch.float32 and tuple(x.shape) == want and x.is_contiguous()):
+            raise ValueError(f"denoise: {what} must be a contiguous float32 tensor of shape {want} on {color.device}, got "
+                             f"{type(x).__name__} {getattr(x, 'dtype', None)} {tuple(getattr(x, 'shape', ()))} on {getattr(x, 'device', None)}")
+    H, W = shape[-3], shape[-2]
+    V = shape[0] if len(shape) == 4 else 1
+    if H < 1 or W < 1:
+        raise ValueError(f"denoise: invalid image size {W} x {H}")
+    iterations = int(iterations)
+    if not 1 <= iterations <= 8:
+        raise ValueError(f"denoise: iterations must lie in [1, 8], got {iterations}")
+    sigmas = [float(sigma_color), float(sigma_normal), float(sigma_depth)]
+    if any(math.isnan(s) or s < 0 for s in sigmas):
+        raise ValueError(f"denoise: the sigmas must be numbers >= 0, got {sigmas}")
+    hstream, tstream = _stream_pair(stream, color.device)
+    with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensor to the stream that writes it)
+        out = _out_tensor("denoise: out", out, shape, torch.float32, color.device)
+    if V == 0:
+        return out
+    ptr = lambda x: C.c_void_p(x.data_ptr() or None) if x is not None else None
+    p = _abi.DenoiseParams(C.sizeof(_abi.DenoiseParams), W, H, V, iterations, *sigmas)
+    bufs = _abi.DenoiseBuffers(C.sizeof(_abi.DenoiseBuffers), 0, ptr(color), ptr(color_b), ptr(albedo), ptr(normal), ptr(depth))
+    _check(lib().gnxr_denoise_device(C.byref(p), C.byref(bufs), ptr(out), C.c_void_p(hstream or None)))
+    return out
 
 
 def save_png(path, rgba8):

@@ -143,6 +143,16 @@ class AdaptiveInfo(C.Structure):   # gnxr_adaptive_info (carries struct_size)
     _fields_ = [("struct_size", i32), ("rounds", i32), ("samples", i64), ("pixels_at_budget", i64)]
 
 
+class DenoiseParams(C.Structure):   # gnxr_denoise_params (carries struct_size)
+    _fields_ = [("struct_size", i32), ("width", i32), ("height", i32), ("n_views", i32), ("iterations", i32),
+                ("sigma_color", f32), ("sigma_normal", f32), ("sigma_depth", f32)]
+
+
+class DenoiseBuffers(C.Structure):   # gnxr_denoise_buffers (carries struct_size): device addresses, NULL = not given
+    _fields_ = [("struct_size", i32), ("_pad", i32), ("d_color", C.c_void_p), ("d_color_b", C.c_void_p), ("d_albedo", C.c_void_p),
+                ("d_normal", C.c_void_p), ("d_depth", C.c_void_p)]
+
+
 P = C.POINTER
 VP = C.c_void_p
 
@@ -188,6 +198,7 @@ PROTOTYPES = {
     "gnxr_render_views_device": (C.c_int, [VP, P(RenderParams), P(Camera), P(i32), i32, VP, VP, P(Stats)]),   # cameras, media: host; images: device
     "gnxr_render_aov_device": (C.c_int, [VP, P(RenderParams), P(Camera), P(i32), i32, P(AovBuffers), VP, P(Stats)]),   # cameras, media: host; buffers: device
     "gnxr_render_adaptive_device": (C.c_int, [VP, P(RenderParams), P(AdaptiveParams), VP, VP, VP, P(Stats), P(AdaptiveInfo)]),   # image, counts: device; hipStream_t
+    "gnxr_denoise_device": (C.c_int, [P(DenoiseParams), P(DenoiseBuffers), VP, VP]),   # buffers, image: device; hipStream_t
     "gnxr_material_albedo": (C.c_int, [P(Material), P(f32)]),
     "gnxr_camera_rays_device": (C.c_int, [P(Camera), i32, i32, i32, VP, VP, VP, i64, VP, VP, VP]),   # device addresses + hipStream_t
     "gnxr_bsdf_device": (C.c_int, [VP, VP, VP, VP, VP, i64, i32, VP, VP]),   # device addresses + hipStream_t

@@ -820,6 +820,61 @@ typedef struct gnxr_adaptive_info { int32_t struct_size, rounds; int64_t samples
 int gnxr_render_adaptive_device(gnxr_scene *scene, const gnxr_render_params *params, const gnxr_adaptive_params *adaptive, void *d_rgba_out,
                                 int32_t *d_count_out, void *hip_stream, gnxr_stats *stats, gnxr_adaptive_info *info);
 
+/* -- Edge-aware image denoiser on device memory, guided by the feature buffers ----------------------------------------------
+ * gnxr_denoise_device filters n_views images of width x height pixels with an edge-avoiding a-trous wavelet filter (Dammertz et al.
+ * 2010) whose colour weight is the variance-guided one of SVGF, the variance estimated from two independent half renders.  It is a
+ * pure image operation: no scene handle; the device is the one that holds d_color (as gnxr_camera_rays_device finds it); the work is
+ * queued on hip_stream after what the stream holds and the call returns without waiting for the GPU; scratch, 48 bytes per pixel
+ * (two ping-pong work records and one guide record), comes from the stream-ordered allocator.  d_rgba_out may be d_color or
+ * d_color_b (in place: the same address); it may not overlap a share at any other offset, nor a guide.  n_views == 0 is a no-op.  Image v of a buffer sits at v*width*height*stride,
+ * pixel (x, y) at x + y*width; no tap crosses from one view into another.
+ * "Shares": d_color alone is the image.  With d_color_b the two are the shares of the image that two renders of disjoint sample
+ * ranges return (spp_begin / spp_end: samples [0, N/2) and [N/2, N) of spp = N): they add up to the image, and with equal halves
+ * (a - b)^2 estimates the variance of the mean.
+ * The definition.  Every operation is a single fp32 operation in the written order (no fused multiply-add; division and sqrt are
+ * IEEE); expf is glibc's (the bits of gnxr_eval_libm, fn = 1).  lum(x) = (0.212671f*x.r + 0.715160f*x.g) + 0.072169f*x.b.
+ *   Prepare, per pixel:
+ *     div_c = max(albedo_c + (1 - coverage), 1/1024) per channel (t > 1/1024 ? t : 1/1024: a NaN gives 1/1024), or 1 without
+ *             d_albedo -- a missed sample counts as albedo 1, so an environment background is not divided away
+ *     with d_color_b:     c_c = (a_c + b_c) / div_c;   d = lum(a / div) - lum(b / div);   v = d * d
+ *     without:            c_c = a_c / div_c;   v = 0
+ *     a pixel with a non-finite c_c or v is INVALID, its work record (0, 0, 0, -1); otherwise the record is (c.r, c.g, c.b, v).
+ *     The guide record is (n.x, n.y, n.z, depth), zeros for absent guides.
+ *   Host constants: inv_sn = 1 / (sigma_normal * sigma_normal), inv_sc = 1 / (sigma_color * sigma_color).  A sigma of 0 or an absent
+ *     guide switches that term off (the term is +0).
+ *   Iteration i = 0 .. iterations-1, step s = 2^i, per pixel p of view v:
+ *     the colour term is used when sigma_color > 0.  With d_color_b: vbar_p = (sum g*v_q) / (sum g) over the valid in-image pixels
+ *     q of the 3 x 3 window at distance 1 (dy outer -1..1, dx inner -1..1; g = 1/4 at the centre, 1/8 at the edges, 1/16 at the
+ *     corners; 0 when the window has no valid pixel) and inv_c = 1 / (sigma_color * sqrt(vbar_p) + 1e-6f).  With d_depth and
+ *     sigma_depth > 0: inv_z = 1 / ((sigma_depth * (float)s) * z_p + 1e-20f).
+ *     Taps in the order dy = -2..2 outer, dx = -2..2 inner, q = p + s*(dx, dy); a tap outside the image of view v or on an invalid q
+ *     is skipped; h = k[|dy|] * k[|dx|] with k = {3/8, 1/4, 1/16}.  x_c is 0 when p is invalid, else
+ *       with d_color_b:   x_c = |lum(c_p) - lum(c_q)| * inv_c
+ *       without:          dc = c_p - c_q;  x_c = ((dc.r*dc.r + dc.g*dc.g) + dc.b*dc.b) * (inv_sc * 4^i)
+ *       dn = n_p - n_q;   x_n = ((dn.x*dn.x + dn.y*dn.y) + dn.z*dn.z) * inv_sn
+ *       x_z = |z_p - z_q| * inv_z
+ *       w = h * expf(-((x_c + x_n) + x_z))
+ *     A tap with !(w > 0) is skipped (NaN included).  Otherwise, from +0: sum_c += w * c_q per channel; sum_w += w;
+ *     sum_v += (w*w) * v_q.  If sum_w > 0: c' = sum_c / sum_w, v' = sum_v / (sum_w*sum_w) and the pixel is valid from here on;
+ *     otherwise its record is kept as it is.
+ *   Output: out.rgb = c * div; out.w = d_color.w of that pixel; a pixel that is still invalid gets a.rgb (a.rgb + b.rgb with a
+ *     second image), unchanged.
+ * GNXR_ERR_INVALID, before anything is queued (the output stays untouched): a null params, in, d_color or d_rgba_out; a struct_size
+ * other than sizeof of its record; width or height < 1, n_views < 0; iterations outside [1, 8]; a negative or NaN sigma; a pointer
+ * that is not device memory or is on another device than d_color; a four-float buffer that is not 16-byte aligned, a d_depth that
+ * is not 4-byte aligned; d_rgba_out overlapping a guide, or a share at another address than its own; n_views*width*height beyond the limit of gnxr_render_views_device.
+ * The two records carry struct_size; they are not part of gnxr_abi_sizeof's list.                                               */
+typedef struct gnxr_denoise_params { int32_t struct_size, width, height, n_views, iterations;
+                                     float sigma_color, sigma_normal, sigma_depth; } gnxr_denoise_params;
+typedef struct gnxr_denoise_buffers { int32_t struct_size, pad;
+    const float *d_color;    /* V*H*W*4, required: the image, or the first of two shares of it            */
+    const float *d_color_b;  /* V*H*W*4 or NULL: the second share (an independent estimate, see above)    */
+    const float *d_albedo;   /* V*H*W*4 or NULL: rgb + coverage, the layout of gnxr_aov_buffers.d_albedo  */
+    const float *d_normal;   /* V*H*W*4 or NULL: either normal channel of gnxr_aov_buffers                */
+    const float *d_depth;    /* V*H*W   or NULL                                                           */
+} gnxr_denoise_buffers;
+int gnxr_denoise_device(const gnxr_denoise_params *params, const gnxr_denoise_buffers *in, float *d_rgba_out, void *hip_stream);
+
 /* -- Shading queries on device memory: the pieces an integrator is made of, batched -------------------------------------
  * Same conventions as the device calls of the Aggregate seam: every array is device memory of one device that holds a copy of the
  * scene, the work is queued on hip_stream (NULL: the null stream) after what the caller queued there, scratch comes from the
