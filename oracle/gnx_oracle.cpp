@@ -199,17 +199,24 @@ void gnxo_primes(int32_t *primes, int32_t *sums) {
 }
 
 // ---- BSDF probe: build the BSDF at a hit of ray (o,d) and evaluate / sample it ----
-// out layout per query (16 floats): f[3], pdf, sample_f[3], sample_pdf, wi[3], sampledType, nComponents, hit, 0, 0
-// flags: BxDFType in the low byte; bits 8.. = 1000 * eps of synthetic ray differentials (0: none; texture-filter probe)
-int gnxo_bsdf_probe(gnxo_scene *s, const gnxr_ray *rays, const float *wiW, const float *u2, int64_t n, int flagsIn, float *out) {
-    const Scene &scene = s->scene;
-    const int flags = flagsIn & 0xff;
-    const float diffEps = (float)(flagsIn >> 8) / 1000.f;
+// out layout per query (16 floats): f[3], pdf, sample_f[3], sample_pdf, wi[3], sampledType, nComponents, hit, dudx, dvdy
+// diffEps > 0: synthetic offset rays (same origin, directions nudged by diffEps along x / y), what oracle/ref_driver.cpp builds.
+// `diffs`: null, or 12 floats per query: rxOrigin, rxDirection, ryOrigin, ryDirection (the rows of Scene.bsdf(..., differentials=)).
+// `branch`: null, or one mask per query (TEXB_* / DIFFB_* of o_texture.h) of the paths ComputeDifferentials and the lookup of the hit
+// material's Kd image texture took; 0 for a miss or a null material, the DIFFB_* bits alone for a material without a Kd image.
+static void bsdfProbe(const Scene &scene, const gnxr_ray *rays, const float *wiW, const float *u2, int64_t n, int flags, float diffEps,
+                      const float *diffs, float *out, uint32_t *branch) {
     for (int64_t i = 0; i < n; ++i) {
         float *o = out + 16 * i;
         for (int k = 0; k < 16; ++k) o[k] = 0;
+        if (branch) branch[i] = 0;
         Ray r(V3(rays[i].o[0], rays[i].o[1], rays[i].o[2]), V3(rays[i].d[0], rays[i].d[1], rays[i].d[2]), rays[i].tmax);
-        if (diffEps > 0) {
+        if (diffs) {
+            const float *q = diffs + 12 * i;
+            r.hasDifferentials = true;
+            r.rxOrigin = V3(q[0], q[1], q[2]); r.rxDirection = V3(q[3], q[4], q[5]);
+            r.ryOrigin = V3(q[6], q[7], q[8]); r.ryDirection = V3(q[9], q[10], q[11]);
+        } else if (diffEps > 0) {
             r.hasDifferentials = true;
             r.rxOrigin = r.ryOrigin = r.o;
             r.rxDirection = r.d + V3(diffEps, 0, 0);
@@ -218,7 +225,21 @@ int gnxo_bsdf_probe(gnxo_scene *s, const gnxr_ray *rays, const float *wiW, const
         SurfaceInteraction isect;
         if (!scene.Intersect(r, &isect)) continue;
         BSDF bsdf;
-        if (!ComputeScatteringFunctions(scene, r, &isect, true, &bsdf)) continue;
+        uint32_t mask = 0;
+        TexTrace() = branch ? &mask : nullptr;      // ComputeDifferentials reports here; the lookups below are traced separately
+        bool has = ComputeScatteringFunctions(scene, r, &isect, true, &bsdf);
+        TexTrace() = nullptr;
+        if (!has) continue;
+        if (branch) {
+            mask &= 0xffff0000u;                    // Plastic looks up Kd and Ks: keep ComputeDifferentials' bits, trace Kd alone
+            const gnxr_material &m = scene.materials[scene.triMaterial[isect.prim]];
+            if ((m.type == GNXR_MAT_MATTE || m.type == GNXR_MAT_PLASTIC) && m.kd_texture > 0) {
+                TexTrace() = &mask;
+                (void)scene.textures[m.kd_texture - 1].Evaluate(isect.uv, isect.dudx, isect.dvdx, isect.dudy, isect.dvdy);
+                TexTrace() = nullptr;
+            }
+            branch[i] = mask;
+        }
         o[13] = 1; o[14] = isect.dudx; o[15] = isect.dvdy;
         V3 wi(wiW[3 * i], wiW[3 * i + 1], wiW[3 * i + 2]);
         Spec f = bsdf.f(isect.wo, wi, flags);
@@ -230,6 +251,17 @@ int gnxo_bsdf_probe(gnxo_scene *s, const gnxr_ray *rays, const float *wiW, const
         o[4] = sf[0]; o[5] = sf[1]; o[6] = sf[2]; o[7] = pdf;
         o[8] = wis.x; o[9] = wis.y; o[10] = wis.z; o[11] = (float)st; o[12] = (float)bsdf.NumComponents(flags);
     }
+}
+// flagsIn: BxDFType in the low byte; bits 8.. = 1000 * eps of the synthetic offset rays (0: none)
+int gnxo_bsdf_probe(gnxo_scene *s, const gnxr_ray *rays, const float *wiW, const float *u2, int64_t n, int flagsIn, float *out) {
+    bsdfProbe(s->scene, rays, wiW, u2, n, flagsIn & 0xff, (float)(flagsIn >> 8) / 1000.f, nullptr, out, nullptr);
+    return 0;
+}
+// The same probe with the caller's offset rays (diffs == null: none) and, when `branch` is given, the per-probe branch report.
+int gnxo_bsdf_probe_diff(gnxo_scene *s, const gnxr_ray *rays, const float *wiW, const float *u2, const float *diffs, int64_t n, int flags, float *out,
+                         uint32_t *branch) {
+    if (!s || n < 0 || flags < 0 || flags > 31) return -1;
+    bsdfProbe(s->scene, rays, wiW, u2, n, flags, 0.f, diffs, out, branch);
     return 0;
 }
 

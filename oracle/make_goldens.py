@@ -16,6 +16,7 @@ What each fixture pins:
   bsdf_zoo.npz   BSDF::f / Pdf / Sample_f for one material of each kind
   light_*.npz    DiffuseAreaLight / InfiniteAreaLight / SkyBoxLight Sample_Li / Pdf_Li / Le
   render_*.npz   images + ray counts of the restated Render/Li loop running on the reference's classes
+  texture_filter.npz + tex_filter_*.hdr   ImageTexture::Evaluate / MIPMap::Lookup over filters x wrap modes x shapes x footprints
   reference_assets.npz + *.xz / *.bz2   the reference's Resources/ inputs of tests/test_reference_assets.py and its answers on them
 """
 import os
@@ -234,6 +235,7 @@ def main():
     delta_goldens()
     ortho_goldens()
     hlbvh_goldens()
+    texture_filter_goldens()
     # cfg 2 at full size: the counts the survey recorded from the COMPLETE reference
     img, cnt = render(cornell_path, 256, 256, 64)
     checksum = float(img[..., :3].astype(np.float64).sum())
@@ -423,6 +425,52 @@ def hlbvh_goldens():
          order=np.frombuffer(raw[4 + nn * 36:], np.int32).copy())
 
 
+# ---------------------------------------------------------------- 19: the texture-filter sweep (tests/test_texture_filter.py)
+TEXTURE_FILTER_EPS = (1e-5, 1e-3, 0.02, 0.2, 0.7)
+TEXTURE_FILTER_PROBES, TEXTURE_FILTER_MISSES = 256, 16     # per quad (and eps value: every eps value runs the same rays)
+
+
+def filter_image(w, h, seed):
+    """Seeded smooth colour plus a few isolated texels far above it (one in a corner and one on an edge, where the wrap modes show)
+    and one black texel; a 1x1 image is its colour alone."""
+    rng = np.random.default_rng([77, seed])
+    y, x = np.mgrid[0:h, 0:w].astype(np.float64)
+    ph = rng.uniform(0, 2 * np.pi, 3)
+    img = np.stack([0.45 + 0.3 * np.sin(5.1 * x / w + 2.3 * y / h + ph[0]), 0.4 + 0.3 * np.cos(2.2 * x / w - 4.7 * y / h + ph[1]),
+                    0.5 + 0.35 * np.sin(3.9 * (x / w + y / h) + ph[2])], -1)
+    if w * h > 1:
+        img[0, 0] = (6.0, 0.5, 0.25)
+        img[h - 1, w // 2] = (0.25, 5.0, 0.5)
+        img[h // 2, w - 1] = (0.5, 0.25, 4.0)
+        img[h // 2, w // 3] = 0.0
+        for _ in range(max(1, w * h // 64)):
+            img[rng.integers(0, h), rng.integers(0, w)] = rng.uniform(2.0, 8.0, 3)
+    return img.astype(np.float32)
+
+
+def texture_filter_goldens():
+    """ImageTexture::Evaluate of the compiled reference over filters x wrap modes x image shapes x footprints: scenes.TEXTURE_FILTER_QUADS
+    probed with rays aimed at chosen uv targets under chosen incidence angles (scenes.texture_filter_probes), the driver's synthetic
+    offset rays at five sizes, BSDF flags 31, all 16 columns of every probe.  out[i, e] is probe i under TEXTURE_FILTER_EPS[e]."""
+    for k, (name, (w, h)) in enumerate(scenes.TEXTURE_FILTER_IMAGES.items()):
+        write_rgbe(scenes.texture_filter_image_path(name, G), filter_image(w, h, k))
+    b = scenes.texture_filter_scene("sweep", G)
+    path = scene_file(b, "texture_filter")
+    parts = [scenes.texture_filter_probes(q, TEXTURE_FILTER_PROBES, 1, TEXTURE_FILTER_MISSES) for q in range(len(scenes.TEXTURE_FILTER_QUADS))]
+    rays, wi, u = (np.ascontiguousarray(np.concatenate([p[k] for p in parts])) for k in range(3))
+    quad = np.repeat(np.arange(len(parts)), TEXTURE_FILTER_PROBES + TEXTURE_FILTER_MISSES).astype(np.int32)
+    eps = np.array(TEXTURE_FILTER_EPS, np.float32)
+    blob = rays.tobytes() + wi.tobytes() + u.tobytes()
+    out = np.stack([np.frombuffer(ol.run_ref(path, "bsdf", blob, [31, repr(float(e))]), np.float32).reshape(-1, 16) for e in eps], 1)
+    osc = ol.OracleScene(b)
+    for k, e in enumerate(eps):
+        o = osc.bsdf_probe_diff(rays, wi, u, scenes.synthetic_differentials(rays, e), 31)
+        same = (o.view(np.uint32) == out[:, k].view(np.uint32)) | (np.isnan(o) & np.isnan(out[:, k]))
+        print("texture_filter eps", float(e), "valid", int((out[:, k, 13] == 1).sum()), "of", len(rays), "oracle identical rows", int(same.all(1).sum()))
+    save("texture_filter.npz", rays=rays, wi=wi, u=u, quad=quad, eps=eps, out=np.ascontiguousarray(out))
+    print("texture_filter.npz", os.path.getsize(os.path.join(G, "texture_filter.npz")), "bytes")
+
+
 # ---------------------------------------------------------------- 18: the reference's Resources/ inputs (tests/test_reference_assets.py)
 def sha256_bits(a):
     import hashlib
@@ -531,5 +579,7 @@ if __name__ == "__main__":
         ortho_goldens()
     elif sys.argv[1:] == ["hlbvh"]:      # only section 17
         hlbvh_goldens()
+    elif sys.argv[1:] == ["texture_filter"]:   # only section 19
+        texture_filter_goldens()
     else:
         main()

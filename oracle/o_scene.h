@@ -64,30 +64,32 @@ struct SurfaceInteraction : Interaction {
     }
     void ComputeDifferentials(const Ray &ray) {
         bool ok = ray.hasDifferentials;
+        if (!ok) TexMark(DIFFB_NONE);
         if (ok) {
             Float d = Dot(n, V3(p.x, p.y, p.z));
             Float tx = -(Dot(n, ray.rxOrigin) - d) / Dot(n, ray.rxDirection);
             Float ty = 0;
-            if (std::isinf(tx) || std::isnan(tx)) ok = false;
+            if (std::isinf(tx) || std::isnan(tx)) { TexMark(DIFFB_TX_FAIL); ok = false; }
             V3 px, py;
             if (ok) {
                 px = ray.rxOrigin + tx * ray.rxDirection;
                 ty = -(Dot(n, ray.ryOrigin) - d) / Dot(n, ray.ryDirection);
-                if (std::isinf(ty) || std::isnan(ty)) ok = false;
+                if (std::isinf(ty) || std::isnan(ty)) { TexMark(DIFFB_TY_FAIL); ok = false; }
             }
             if (ok) {
                 py = ray.ryOrigin + ty * ray.ryDirection;
                 dpdx = px - p;
                 dpdy = py - p;
                 int dim[2];
-                if (std::abs(n.x) > std::abs(n.y) && std::abs(n.x) > std::abs(n.z)) { dim[0] = 1; dim[1] = 2; }
-                else if (std::abs(n.y) > std::abs(n.z)) { dim[0] = 0; dim[1] = 2; }
-                else { dim[0] = 0; dim[1] = 1; }
+                if (std::abs(n.x) > std::abs(n.y) && std::abs(n.x) > std::abs(n.z)) { dim[0] = 1; dim[1] = 2; TexMark(DIFFB_AXES_YZ); }
+                else if (std::abs(n.y) > std::abs(n.z)) { dim[0] = 0; dim[1] = 2; TexMark(DIFFB_AXES_XZ); }
+                else { dim[0] = 0; dim[1] = 1; TexMark(DIFFB_AXES_XY); }
                 Float A[2][2] = {{dpdu[dim[0]], dpdv[dim[0]]}, {dpdu[dim[1]], dpdv[dim[1]]}};
                 Float Bx[2] = {px[dim[0]] - p[dim[0]], px[dim[1]] - p[dim[1]]};
                 Float By[2] = {py[dim[0]] - p[dim[0]], py[dim[1]] - p[dim[1]]};
-                if (!SolveLinearSystem2x2(A, Bx, &dudx, &dvdx)) dudx = dvdx = 0;
-                if (!SolveLinearSystem2x2(A, By, &dudy, &dvdy)) dudy = dvdy = 0;
+                if (!SolveLinearSystem2x2(A, Bx, &dudx, &dvdx)) { TexMark(DIFFB_SOLVE_X_FAIL); dudx = dvdx = 0; }
+                if (!SolveLinearSystem2x2(A, By, &dudy, &dvdy)) { TexMark(DIFFB_SOLVE_Y_FAIL); dudy = dvdy = 0; }
+                TexMark(DIFFB_SOLVED);
                 return;
             }
         }

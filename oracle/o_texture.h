@@ -29,6 +29,33 @@ inline int Log2Int(uint32_t v) { return 31 - __builtin_clz(v); }
 inline Float Log2(Float x) { const Float invLog2 = 1.442695040888963387004650940071; return std::log(x) * invLog2; }
 inline int ModI(int a, int b) { int r = a - (a / b) * b; return (r < 0) ? r + b : r; }
 
+// Branch report of gnxo_bsdf_probe_diff (tests/test_texture_filter.py): while TexTrace() points at a mask, the lookup below ORs in
+// the bit of every path it takes.  The bits come from the control flow of the lookup itself; nothing is decided a second time.
+enum : uint32_t {
+    TEXB_TRI_BELOW = 1u << 0,     // Lookup(st, width): level < 0 -> triangle(0)
+    TEXB_TRI_TOP = 1u << 1,       // level >= Levels() - 1 -> the top texel
+    TEXB_TRI_LERP = 1u << 2,      // the lerp of two levels
+    TEXB_EWA_SWAP = 1u << 3,      // dst0 was the shorter axis
+    TEXB_EWA_CLAMPED = 1u << 4,   // maxAnisotropy rescaled the minor axis
+    TEXB_EWA_MINOR0 = 1u << 5,    // minorLength == 0 -> triangle(0)
+    TEXB_EWA_LOD0 = 1u << 6,      // lod clamped to 0
+    TEXB_EWA_PAST = 1u << 7,      // EWA(ilod + 1) with ilod + 1 >= Levels() -> the top texel
+    TEXB_WRAP = 1u << 8,          // Texel(): the wrap mode changed an index (Repeat, Clamp) or returned black (Black)
+    TEXB_EWA_LERP = 1u << 9,      // the lerp of two EWA levels was reached
+    // SurfaceInteraction::ComputeDifferentials (o_scene.h): which return, which axis pair
+    DIFFB_NONE = 1u << 16,        // the ray has no differentials
+    DIFFB_TX_FAIL = 1u << 17,     // tx infinite or NaN
+    DIFFB_TY_FAIL = 1u << 18,     // ty infinite or NaN
+    DIFFB_SOLVED = 1u << 19,      // the regular return
+    DIFFB_SOLVE_X_FAIL = 1u << 20,   // SolveLinearSystem2x2 refused the x system
+    DIFFB_SOLVE_Y_FAIL = 1u << 21,   // ... the y system
+    DIFFB_AXES_YZ = 1u << 22,     // |n.x| largest: dim = {1, 2}
+    DIFFB_AXES_XZ = 1u << 23,     // |n.y| larger than |n.z|: dim = {0, 2}
+    DIFFB_AXES_XY = 1u << 24,     // otherwise: dim = {0, 1}
+};
+inline uint32_t *&TexTrace() { static thread_local uint32_t *p = nullptr; return p; }
+inline void TexMark(uint32_t bit) { if (uint32_t *p = TexTrace()) *p |= bit; }
+
 // MIPMap<RGBSpectrum>, core/MIPMap.h:41-337.  The InfiniteAreaLight uses (doTrilinear = false, Repeat) and only the
 // width-0 Lookup; ImageTexture uses the (st, dst0, dst1) Lookup: trilinear or EWA.
 struct MIPMapRGB {
@@ -122,11 +149,13 @@ struct MIPMapRGB {
     int Levels() const { return (int)pyramid.size(); }
     const Spec &Texel(int level, int s, int t) const {   // MIPMap.h:203-223
         static const Spec black(0.f);
+        const int sIn = s, tIn = t;
         switch (wrapMode) {
         case GNXR_WRAP_REPEAT: s = ModI(s, lw[level]); t = ModI(t, lh[level]); break;
         case GNXR_WRAP_CLAMP: s = Clamp(s, 0, lw[level] - 1); t = Clamp(t, 0, lh[level] - 1); break;
-        default: if (s < 0 || s >= lw[level] || t < 0 || t >= lh[level]) return black; break;
+        default: if (s < 0 || s >= lw[level] || t < 0 || t >= lh[level]) { TexMark(TEXB_WRAP); return black; } break;
         }
+        if (s != sIn || t != tIn) TexMark(TEXB_WRAP);
         return pyramid[level][(size_t)t * lw[level] + s];
     }
     Spec triangle(int level, const P2 &st) const {
@@ -144,22 +173,26 @@ struct MIPMapRGB {
             Float width = std::max(std::max(std::abs(dst0.x), std::abs(dst0.y)), std::max(std::abs(dst1.x), std::abs(dst1.y)));
             return Lookup(st, width);
         }
-        if (dst0.x * dst0.x + dst0.y * dst0.y < dst1.x * dst1.x + dst1.y * dst1.y) std::swap(dst0, dst1);
+        if (dst0.x * dst0.x + dst0.y * dst0.y < dst1.x * dst1.x + dst1.y * dst1.y) { TexMark(TEXB_EWA_SWAP); std::swap(dst0, dst1); }
         Float majorLength = std::sqrt(dst0.x * dst0.x + dst0.y * dst0.y);
         Float minorLength = std::sqrt(dst1.x * dst1.x + dst1.y * dst1.y);
         if (minorLength * maxAnisotropy < majorLength && minorLength > 0) {
             Float scale = majorLength / (minorLength * maxAnisotropy);
             dst1.x *= scale; dst1.y *= scale;
             minorLength *= scale;
+            TexMark(TEXB_EWA_CLAMPED);
         }
-        if (minorLength == 0) return triangle(0, st);
-        Float lod = std::max((Float)0, Levels() - (Float)1 + Log2(minorLength));
+        if (minorLength == 0) { TexMark(TEXB_EWA_MINOR0); return triangle(0, st); }
+        const Float unclamped = Levels() - (Float)1 + Log2(minorLength);
+        Float lod = std::max((Float)0, unclamped);
+        if (!((Float)0 < unclamped)) TexMark(TEXB_EWA_LOD0);   // std::max returned its first argument
         int ilod = std::floor(lod);
+        TexMark(TEXB_EWA_LERP);
         return Lerp(lod - ilod, EWA(ilod, st, dst0, dst1), EWA(ilod + 1, st, dst0, dst1));
     }
     // MIPMap.h:288-334
     Spec EWA(int level, P2 st, P2 dst0, P2 dst1) const {
-        if (level >= Levels()) return Texel(Levels() - 1, 0, 0);
+        if (level >= Levels()) { TexMark(TEXB_EWA_PAST); return Texel(Levels() - 1, 0, 0); }
         st.x = st.x * lw[level] - 0.5f;
         st.y = st.y * lh[level] - 0.5f;
         dst0.x *= lw[level]; dst0.y *= lh[level];
@@ -196,9 +229,10 @@ struct MIPMapRGB {
     }
     Spec Lookup(const P2 &st, Float width = 0.f) const {
         Float level = Levels() - 1 + Log2(std::max(width, (Float)1e-8));
-        if (level < 0) return triangle(0, st);
-        else if (level >= Levels() - 1) return Texel(Levels() - 1, 0, 0);
+        if (level < 0) { TexMark(TEXB_TRI_BELOW); return triangle(0, st); }
+        else if (level >= Levels() - 1) { TexMark(TEXB_TRI_TOP); return Texel(Levels() - 1, 0, 0); }
         else {
+            TexMark(TEXB_TRI_LERP);
             int iLevel = std::floor(level);
             Float delta = level - iLevel;
             return Lerp(delta, triangle(iLevel, st), triangle(iLevel + 1, st));

@@ -43,6 +43,7 @@ def olib():
         L.gnxo_perm_table.restype = i64
         L.gnxo_primes.argtypes = [P(i32), P(i32)]
         L.gnxo_bsdf_probe.argtypes = [VP, P(_abi.Ray), P(f32), P(f32), i64, C.c_int, P(f32)]
+        L.gnxo_bsdf_probe_diff.argtypes = [VP, P(_abi.Ray), P(f32), P(f32), P(f32), i64, C.c_int, P(f32), P(C.c_uint32)]
         L.gnxo_light_probe.argtypes = [VP, C.c_int, C.c_int, P(f32), P(f32), P(f32), P(f32), i64, P(f32)]
         L.gnxo_light_le.argtypes = [VP, C.c_int, P(_abi.Ray), i64, P(f32)]
         L.gnxo_framebuffer_update.argtypes = [P(f32), P(f32), i32, i32, i32, P(u8)]
@@ -53,6 +54,13 @@ def olib():
 
 def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+# bits of OracleScene.bsdf_probe_diff(..., branch=True): the enum of oracle/o_texture.h
+TEXB = {"tri_below": 1 << 0, "tri_top": 1 << 1, "tri_lerp": 1 << 2, "ewa_swap": 1 << 3, "ewa_clamped": 1 << 4, "ewa_minor0": 1 << 5, "ewa_lod0": 1 << 6,
+        "ewa_past": 1 << 7, "wrap": 1 << 8, "ewa_lerp": 1 << 9}
+DIFFB = {"none": 1 << 16, "tx_fail": 1 << 17, "ty_fail": 1 << 18, "solved": 1 << 19, "solve_x_fail": 1 << 20, "solve_y_fail": 1 << 21,
+         "axes_yz": 1 << 22, "axes_xz": 1 << 23, "axes_xy": 1 << 24}
 
 
 class OracleScene:
@@ -117,6 +125,25 @@ class OracleScene:
         out = np.zeros((len(rays), 16), np.float32)
         olib().gnxo_bsdf_probe(self._h, rays.ctypes.data_as(C.POINTER(_abi.Ray)), _fp(wi), _fp(u), len(rays), flags, _fp(out))
         return out
+
+    def bsdf_probe_diff(self, rays, wi, u, diffs=None, flags=31, branch=False):
+        """bsdf_probe with the caller's offset rays: `diffs` is None or the (n, 12) rows Scene.bsdf takes as differentials= (rxOrigin,
+        rxDirection, ryOrigin, ryDirection).  branch=True also returns one uint32 mask per probe (the TEXB / DIFFB constants below): which
+        paths ComputeDifferentials and the lookup of the hit material's Kd image texture took."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        wi = np.ascontiguousarray(wi, np.float32)
+        u = np.ascontiguousarray(u, np.float32)
+        out = np.zeros((len(rays), 16), np.float32)
+        dp = None
+        if diffs is not None:
+            diffs = np.ascontiguousarray(diffs, np.float32)
+            assert diffs.shape == (len(rays), 12), diffs.shape
+            dp = _fp(diffs)
+        mask = np.zeros(len(rays), np.uint32) if branch else None
+        rc = olib().gnxo_bsdf_probe_diff(self._h, rays.ctypes.data_as(C.POINTER(_abi.Ray)), _fp(wi), _fp(u), dp, len(rays), int(flags), _fp(out),
+                                         mask.ctypes.data_as(C.POINTER(C.c_uint32)) if branch else None)
+        assert rc == 0
+        return (out, mask) if branch else out
 
     def light_probe(self, light, refP, refN, u, wiQ, strategy=_abi.LIGHTS_UNIFORM):
         refP, refN, u, wiQ = (np.ascontiguousarray(a, np.float32) for a in (refP, refN, u, wiQ))

@@ -461,3 +461,132 @@ def delta_cornell(medium_ball=True):
         v, t, uv, n = uv_sphere_mesh((0.2, -1.4, 0.9), 0.7, 6, 8)
         b.add_mesh(v, t, -1, medium_inside=med, medium_outside=-1)
     return b
+
+
+# ---------------------------------------------------------------- the texture-filter sweep (tests/test_texture_filter.py)
+# images of the sweep, tests/golden/tex_filter_<name>.hdr (written by oracle/make_goldens.py texture_filter_goldens): (w, h)
+TEXTURE_FILTER_IMAGES = {"16x16": (16, 16), "64x4": (64, 4), "5x3": (5, 3), "33x17": (33, 17), "1x1": (1, 1)}
+UV_UNIT, UV_WIDE = (0.0, 1.0), (-1.5, 2.5)
+# one flat quad per row, each with a material of its own: Matte (sigma 0: f = Kd / pi shows the texture value) whose Kd is the image
+# texture `kd`; `ks` makes it a Plastic with a second texture.  uv: the range both coordinates run over across the quad.  half: half the
+# edge length; "tiny" is so small under so many uv repeats that dpdu / dpdv give SolveLinearSystem2x2 a determinant below 1e-10.
+TEXTURE_FILTER_QUADS = [
+    dict(name="ewa_repeat", uv=UV_WIDE, kd=dict(image="16x16", wrap="repeat", max_aniso=8.0)),
+    dict(name="ewa_black", uv=UV_WIDE, kd=dict(image="16x16", wrap="black", max_aniso=8.0)),
+    dict(name="ewa_clamp", uv=UV_WIDE, kd=dict(image="33x17", wrap="clamp", max_aniso=8.0)),
+    dict(name="ewa_repeat_aniso1", uv=UV_WIDE, kd=dict(image="64x4", wrap="repeat", max_aniso=1.0)),
+    dict(name="ewa_repeat_aniso16", uv=UV_UNIT, kd=dict(image="33x17", wrap="repeat", max_aniso=16.0)),
+    dict(name="tri_repeat", uv=UV_WIDE, kd=dict(image="64x4", wrap="repeat", trilinear=True)),
+    dict(name="tri_black", uv=UV_WIDE, kd=dict(image="33x17", wrap="black", trilinear=True)),
+    dict(name="tri_clamp", uv=UV_WIDE, kd=dict(image="16x16", wrap="clamp", trilinear=True)),
+    dict(name="ewa_mapped", uv=UV_UNIT, kd=dict(image="16x16", wrap="repeat", max_aniso=8.0, su=7.0, sv=0.5, du=-3.25, dv=-0.75)),
+    dict(name="tri_gamma_scale", uv=UV_WIDE, kd=dict(image="5x3", wrap="clamp", trilinear=True, gamma=True, scale=0.8)),
+    dict(name="ewa_black_5x3", uv=UV_UNIT, kd=dict(image="5x3", wrap="black", max_aniso=8.0)),
+    dict(name="ewa_1x1", uv=UV_UNIT, kd=dict(image="1x1", wrap="repeat", max_aniso=8.0)),
+    dict(name="tri_black_1x1", uv=UV_WIDE, kd=dict(image="1x1", wrap="black", trilinear=True)),
+    dict(name="plastic", uv=UV_WIDE, kd=dict(image="64x4", wrap="clamp", max_aniso=8.0), ks=dict(image="5x3", wrap="repeat", trilinear=True)),
+    dict(name="tiny", uv=(0.0, 1000.0), half=0.002, kd=dict(image="16x16", wrap="repeat", max_aniso=8.0)),
+]
+# (e1, e2) of the quads, taken in turn: the normal e1 x e2 runs along z, x and y (the three axis pairs of ComputeDifferentials) and
+# along two tilted directions
+_TF_FRAMES = [((1, 0, 0), (0, 1, 0)), ((0, 1, 0), (0, 0, 1)), ((0, 0, 1), (1, 0, 0)), ((0.8, 0.0, -0.6), (0.36, 0.8, 0.48)), ((0.0, 0.6, 0.8), (1.0, 0.0, 0.0))]
+TEXTURE_FILTER_UPDATED_QUAD = 0   # case "updated": this quad's texture is the 33x17 image under Clamp instead of 16x16 under Repeat
+TEXTURE_FILTER_UPDATED = dict(image="33x17", wrap="clamp", max_aniso=8.0)
+
+
+def texture_filter_image_path(name, golden_dir=None):
+    return os.path.join(golden_dir or os.path.join(ROOT, "tests", "golden"), f"tex_filter_{name}.hdr")
+
+
+def texture_filter_quad(i):
+    """(centre, e1, e2, half, (uv_lo, uv_hi)) of quad i: the quads lie 12 units apart along x, far enough that a probe ray, which
+    starts within 1.5 units of its target, meets no other quad first"""
+    q = TEXTURE_FILTER_QUADS[i]
+    e1, e2 = (np.array(v, np.float64) for v in _TF_FRAMES[i % len(_TF_FRAMES)])
+    return np.array([12.0 * i, 0.0, 0.0]), e1, e2, float(q.get("half", 1.0)), q["uv"]
+
+
+def texture_filter_scene(case="sweep", golden_dir=None):
+    """The scene of the texture-filter sweep: TEXTURE_FILTER_QUADS, no lights (the probes evaluate BSDFs only).  case "sweep" is what
+    the reference fixture was recorded on; "updated" is the same scene with the texture of quad TEXTURE_FILTER_UPDATED_QUAD replaced,
+    what Scene.update_textures must turn a "sweep" scene into.  Texture i of quad j is texture_filter_texture_index(j)."""
+    assert case in ("sweep", "updated"), case
+    b = gx.SceneBuilder()
+    for i, q in enumerate(TEXTURE_FILTER_QUADS):
+        c, e1, e2, half, (lo, hi) = texture_filter_quad(i)
+        kd = dict(TEXTURE_FILTER_UPDATED if case == "updated" and i == TEXTURE_FILTER_UPDATED_QUAD else q["kd"])
+        t = b.add_image_texture(texture_filter_image_path(kd.pop("image"), golden_dir), **kd)
+        if "ks" in q:
+            ks = dict(q["ks"])
+            m = b.add_material(type=gx._abi.MAT_PLASTIC, kd=(0.5, 0.5, 0.5), ks=(0.5, 0.5, 0.5), urough=0.1, remap_roughness=1)
+            b.set_material_texture(m, "ks", b.add_image_texture(texture_filter_image_path(ks.pop("image"), golden_dir), **ks))
+        else:
+            m = b.MatteMaterial(WHITE, 0.0)
+        b.set_material_texture(m, "kd", t)
+        v = np.array([c - half * e1 - half * e2, c + half * e1 - half * e2, c + half * e1 + half * e2, c - half * e1 + half * e2], np.float32)
+        b.add_mesh(v, np.array([[0, 1, 2], [0, 2, 3]], np.int32), m, uv=[[lo, lo], [hi, lo], [hi, hi], [lo, hi]])
+    return b
+
+
+def texture_filter_texture_index(quad):
+    """index of quad `quad`'s Kd texture in the scene's texture list (a Plastic quad adds two)"""
+    return quad + sum(1 for q in TEXTURE_FILTER_QUADS[:quad] if "ks" in q)
+
+
+TEXTURE_FILTER_COSINES = (1.0, 0.5, 0.1, 0.02)
+
+
+def texture_filter_probes(quad, n, seed, n_miss=0):
+    """n + n_miss BSDF probes built for quad `quad`: (rays, wi, u).  Each of the first n rays is aimed at a seeded uv target -- half of
+    them uniform over the quad, half within one texel of an image border (st = 0 or 1 in u, in v or in both, where the quad's uv range
+    reaches it) -- from 1 to 1.5 units away, under an incidence cosine from TEXTURE_FILTER_COSINES (the grazing ones stretch the
+    footprint) at a seeded azimuth; a quarter arrives from behind the quad.  wi lies on the side of wo, so that the Lambert lobe
+    shows Kd, and takes one of four directions, u one of four samples: the sampling columns of the results then repeat.  The last
+    n_miss rays point away from the quad and hit nothing."""
+    rng = np.random.default_rng([20261019, seed, quad])
+    q = TEXTURE_FILTER_QUADS[quad]
+    c, e1, e2, half, (lo, hi) = texture_filter_quad(quad)
+    nrm = np.cross(e1, e2)
+    kd = q["kd"]
+    w, h = TEXTURE_FILTER_IMAGES[kd["image"]]
+    su, sv, du, dv = kd.get("su", 1.0), kd.get("sv", 1.0), kd.get("du", 0.0), kd.get("dv", 0.0)
+    m = n + n_miss
+    uv = rng.uniform(lo, hi, (m, 2))
+    mode = rng.integers(0, 6, m)          # 0-2: uniform; 3: a border in u; 4: in v; 5: in both
+    for axis, (s_, d_, res) in enumerate(((su, du, w), (sv, dv, h))):
+        near = (mode == 3 + axis) | (mode == 5)
+        st = np.floor(s_ * uv[:, axis] + d_) + rng.integers(0, 2, m) + rng.uniform(-1.0, 1.0, m) / res   # a border of the tile the target lay in
+        cand = (st - d_) / s_
+        ok = near & (cand > lo) & (cand < hi)
+        uv[ok, axis] = cand[ok]
+    pad = 1e-3 * (hi - lo)
+    uv = np.clip(uv, lo + pad, hi - pad)
+    a = (uv - lo) / (hi - lo) * 2.0 - 1.0
+    p = c + half * (a[:, 0:1] * e1 + a[:, 1:2] * e2)
+    cos = np.array(TEXTURE_FILTER_COSINES)[rng.integers(0, 4, m)]
+    phi = rng.uniform(0, 2 * np.pi, m)
+    side = np.where(rng.integers(0, 4, m) == 0, -1.0, 1.0)
+    sin = np.sqrt(1.0 - cos * cos)
+    wo = side[:, None] * cos[:, None] * nrm + sin[:, None] * (np.cos(phi)[:, None] * e1 + np.sin(phi)[:, None] * e2)
+    dist = rng.uniform(1.0, 1.5, m)
+    o = p + wo * dist[:, None]
+    d = -wo
+    d[n:] = wo[n:]                        # the misses leave the quad behind them
+    rays = gx.make_rays(o.astype(np.float32), d.astype(np.float32), np.inf)
+    k = rng.integers(0, 4, m)
+    ct, ph = np.array([0.9, 0.6, 0.3, 0.75])[k], np.array([0.3, 2.0, 4.1, 5.5])[k]
+    stt = np.sqrt(1.0 - ct * ct)
+    wi = side[:, None] * ct[:, None] * nrm + stt[:, None] * (np.cos(ph)[:, None] * e1 + np.sin(ph)[:, None] * e2)
+    u = np.array([[0.12, 0.7], [0.55, 0.31], [0.83, 0.9], [0.4, 0.05]], np.float32)[rng.integers(0, 4, m)]
+    return rays, np.ascontiguousarray(wi, np.float32), np.ascontiguousarray(u, np.float32)
+
+
+def synthetic_differentials(rays, eps):
+    """the offset rays oracle/ref_driver.cpp's `bsdf` command builds for diffEps = eps: rx / ryOrigin = o, rxDirection = d + (eps, 0, 0),
+    ryDirection = d + (0, eps, 0), in float32: (n, 12) rows for Scene.bsdf(differentials=) and OracleScene.bsdf_probe_diff"""
+    eps = np.float32(eps)
+    o, d = rays[:, 0:3], rays[:, 4:7]
+    rxd, ryd = d.copy(), d.copy()
+    rxd[:, 0] = d[:, 0] + eps
+    ryd[:, 1] = d[:, 1] + eps
+    return np.ascontiguousarray(np.concatenate([o, rxd, o, ryd], 1), np.float32)

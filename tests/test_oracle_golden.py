@@ -225,6 +225,24 @@ def test_smooth_normal_images(name, gx):
     assert (st["rays_closest"], st["rays_any"]) == tuple(int(v) for v in g[name + "_rays"])
     assert biteq(img, g[name])
 
+def test_texture_filter_sweep():
+    """ImageTexture::Evaluate / MIPMap::Lookup of the compiled reference over EWA and trilinear x Repeat / Black / Clamp x images of
+    16x16, 64x4, 5x3, 33x17 and 1x1 texels x five footprint sizes (scenes.TEXTURE_FILTER_QUADS, oracle/make_goldens.py
+    texture_filter_goldens): the oracle reproduces every record bit for bit, through gnxo_bsdf_probe_diff given the offset rays the
+    reference's driver builds from its float diffEps.  tests/test_texture_filter.py counts which branches these probes take."""
+    g = golden("texture_filter.npz")
+    rays, wi, u, out = g["rays"], g["wi"], g["u"], g["out"]
+    assert out.dtype == np.float32 and out.shape == (len(rays), len(g["eps"]), 16) and len(g["eps"]) == 5
+    osc = ol.OracleScene(scenes.texture_filter_scene("sweep"))
+    for k, eps in enumerate(g["eps"]):
+        o = osc.bsdf_probe_diff(rays, wi, u, scenes.synthetic_differentials(rays, eps), 31)
+        assert o.shape == out[:, k].shape and biteq(o, out[:, k]), float(eps)
+        assert (out[:, k, 13] == 1).mean() >= 0.25
+    # the footprints matter: the five eps values give five different answers on most valid probes
+    valid = out[:, 0, 13] == 1
+    assert (np.array([len(np.unique(out[i, :, 0:3].view(np.uint32), axis=0)) for i in np.nonzero(valid)[0]]) >= 3).mean() > 0.5
+
+
 DELTA_CASES = ["path_spatial", "path_power", "path_uniform", "whitted", "direct_all", "direct_one", "volpath"]
 
 
