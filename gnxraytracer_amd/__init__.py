@@ -1293,6 +1293,44 @@ class PathIntegrator:
         total["aov"] = aov_stats
         return image, total
 
+    def RenderFiltered(self, scene, width, height, spp, filter, cameras=None, media=None, accum=None, resume=False, out=None, stream=None, **kw):
+        """Integrator::Render through a film with a pixel reconstruction filter (gnxr_render_filtered_device; the definition, operation by
+        operation: include/gnxr.h): every sample is weighted into all pixels within the filter's radius of its film position, a pixel
+        being the weighted sum over the weight sum.  `filter`: film_filter(...).  `cameras`: gnxr Camera records (camera()), or None for
+        the scene's own camera, which also drops the leading V; `media`: one medium index per camera or None.  `accum`: a float32
+        (H, W, 4) / (V, H, W, 4) tensor of (Sr, Sg, Sb, Wt) on the scene's device to accumulate into -- zeroed first unless `resume` --
+        or None for an accumulator inside the library.  Returns (image, stats): the resolved float32 tensor (H, W, 4) / (V, H, W, 4)
+        (`out` when given), and the stats dict of a render.  A render over spp_begin..spp_end followed by a resumed one over the next
+        range leaves the bits of one render over both.  Runs on `stream` (by default torch's current stream) and returns once the
+        outputs are written.  The other keyword arguments are Render's, without the shard fields."""
+        import torch
+        if not isinstance(filter, _abi.FilmFilter):
+            raise ValueError(f"RenderFiltered: filter must be a film_filter(...) record, got {type(filter).__name__}")
+        if cameras is None and media is not None:
+            raise ValueError("RenderFiltered: media goes with cameras; the scene's own camera sits in the scene's camera medium")
+        cameras, media, width, height = _view_args("RenderFiltered", cameras, media, width, height)
+        if resume and accum is None:
+            raise ValueError("RenderFiltered: resume continues an accumulator: pass the tensor of the earlier call as accum")
+        unknown = [k for k in kw if k not in ("spp_begin", "spp_end", "samples_per_pass", "passes_in_flight")]
+        if unknown:
+            raise ValueError(f"RenderFiltered: unexpected arguments {unknown} (spp_begin, spp_end, samples_per_pass, passes_in_flight)")
+        V = len(cameras) if cameras is not None else 1
+        lead = (V,) if cameras is not None else ()
+        device = torch.device("cuda", scene.device)
+        hstream, tstream = _stream_pair(stream, device)
+        if accum is not None:
+            _out_tensor("RenderFiltered: accum", accum, lead + (height, width, 4), torch.float32, device)
+        with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensor to the stream that writes it)
+            out = _out_tensor("RenderFiltered: out", out, lead + (height, width, 4), torch.float32, device)
+        p = self.params(width, height, spp, **kw)
+        cams = (Camera * V)(*cameras) if cameras else None
+        med = (C.c_int32 * V)(*media) if media else None
+        st = Stats()
+        _check(lib().gnxr_render_filtered_device(scene._h, C.byref(p), C.byref(filter), cams, med, V, C.c_void_p(out.data_ptr() or None),
+                                                 C.c_void_p(accum.data_ptr() or None) if accum is not None else None, _abi.FILM_CONTINUE if resume else 0,
+                                                 C.c_void_p(hstream or None), C.byref(st)))
+        return out, stats_dict(st)
+
     def Render(self, scene, width, height, spp, **kw):
         """Integrator::Render: returns (float32 image [H, W, 4], stats dict)."""
         p = self.params(width, height, spp, **kw)
@@ -1430,6 +1468,114 @@ def denoise(color, color_b=None, albedo=None, normal=None, depth=None, iteration
     p = _abi.DenoiseParams(C.sizeof(_abi.DenoiseParams), W, H, V, iterations, *sigmas)
     bufs = _abi.DenoiseBuffers(C.sizeof(_abi.DenoiseBuffers), 0, ptr(color), ptr(color_b), ptr(albedo), ptr(normal), ptr(depth))
     _check(lib().gnxr_denoise_device(C.byref(p), C.byref(bufs), ptr(out), C.c_void_p(hstream or None)))
+    return out
+
+
+FILM_FILTER_KINDS = {"box": _abi.FILTER_BOX, "triangle": _abi.FILTER_TRIANGLE, "gaussian": _abi.FILTER_GAUSSIAN, "mitchell": _abi.FILTER_MITCHELL,
+                     "table": _abi.FILTER_TABLE}
+
+
+def film_filter(kind, radius, alpha=2.0, B=1 / 3, C=1 / 3, table=None):
+    """A pixel reconstruction filter of the film (gnxr_film_filter): `kind` is "box", "triangle", "gaussian" (falloff `alpha`), "mitchell"
+    (`B`, `C`) or "table" (`table`: 256 values, row y of 16 entries at y*16, entry (x, y) weighing a sample (x + 0.5) / 16 of the radius
+    away in x and likewise in y); `radius`: a number or (radius_x, radius_y), each in [0.5, 4] pixels.  Returns the record film_add,
+    film_filter_table and integrator.RenderFiltered take.  Malformed arguments raise ValueError."""
+    import ctypes
+    import math
+    if kind not in FILM_FILTER_KINDS:
+        raise ValueError(f"film_filter: kind must be one of {tuple(FILM_FILTER_KINDS)}, got {kind!r}")
+    try:
+        rx, ry = (float(radius), float(radius)) if np.ndim(radius) == 0 else (float(radius[0]), float(radius[1]))
+        if np.ndim(radius) != 0 and len(radius) != 2:
+            raise TypeError
+    except (TypeError, ValueError, IndexError):
+        raise ValueError(f"film_filter: radius must be a number or a pair of numbers, got {radius!r}") from None
+    if not (0.5 <= rx <= 4.0 and 0.5 <= ry <= 4.0):   # (a NaN fails)
+        raise ValueError(f"film_filter: the radii must lie in [0.5, 4], got {rx} x {ry}")
+    a, b = (float(alpha), 0.0) if kind == "gaussian" else ((float(B), float(C)) if kind == "mitchell" else (0.0, 0.0))
+    if math.isnan(a) or math.isnan(b):
+        raise ValueError(f"film_filter: the parameters of a {kind} filter must be numbers, got {a} and {b}")
+    tab = None
+    if kind == "table":
+        if table is None:
+            raise ValueError("film_filter: kind 'table' needs table = 256 values")
+        tab = np.ascontiguousarray(table, dtype=np.float32).reshape(-1)
+        if tab.size != 256:
+            raise ValueError(f"film_filter: table must hold 256 values (16 x 16), got {tab.size}")
+    elif table is not None:
+        raise ValueError(f"film_filter: table goes with kind 'table', not {kind!r}")
+    f = _abi.FilmFilter(ctypes.sizeof(_abi.FilmFilter), FILM_FILTER_KINDS[kind], rx, ry, a, b,
+                        tab.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if tab is not None else None)
+    f._table = tab   # the record points into it
+    return f
+
+
+def _film_record(name, f):
+    if not isinstance(f, _abi.FilmFilter):
+        raise ValueError(f"{name}: expected a film_filter(...) record, got {type(f).__name__}")
+    return f
+
+
+def film_filter_table(f):
+    """The 16 x 16 table of weights the film builds from the record `f` (gnxr_film_filter_table, host code: needs no GPU): a float32
+    (16, 16) numpy array, entry [y, x] = the filter at ((x + 0.5) * radius_x / 16, (y + 0.5) * radius_y / 16)."""
+    _film_record("film_filter_table", f)
+    out = np.zeros((16, 16), dtype=np.float32)
+    _check(lib().gnxr_film_filter_table(C.byref(f), out.ctypes.data_as(C.POINTER(C.c_float))))
+    return out
+
+
+def _film_accum_shape(name, accum):
+    import torch
+    if not (isinstance(accum, torch.Tensor) and accum.is_cuda and accum.dtype == torch.float32 and accum.dim() in (3, 4) and accum.shape[-1] == 4 and accum.is_contiguous()):
+        raise ValueError(f"{name}: accum must be a contiguous float32 (H, W, 4) or (V, H, W, 4) tensor on a GPU, got "
+                         f"{type(accum).__name__} {getattr(accum, 'dtype', None)} {tuple(getattr(accum, 'shape', ()))} on {getattr(accum, 'device', None)}")
+    shape = tuple(accum.shape)
+    H, W = shape[-3], shape[-2]
+    V = shape[0] if len(shape) == 4 else 1
+    if H < 1 or W < 1:
+        raise ValueError(f"{name}: invalid image size {W} x {H}")
+    return shape, V, H, W
+
+
+def film_add(f, L, offsets, accum, stream=None):
+    """Adds layers of samples to a film accumulator on device memory (gnxr_film_add_device): `accum` is a contiguous float32 tensor
+    (H, W, 4) or (V, H, W, 4) of (Sr, Sg, Sb, Wt), `L` (n, *accum.shape) holds the sample of layer j that belongs to each pixel (w is
+    ignored) and `offsets` (n, *accum.shape[:-1], 2) its film offset (ux, uy) inside that pixel; a sample with an offset outside [0, 1]
+    adds nothing.  Every sample is weighted by the filter `f` (film_filter) into the pixels of its view within the radius of its
+    position, layer by layer in the order include/gnxr.h defines.  Returns accum.  Queued on `stream` (by default torch's current
+    stream); the call does not wait for the GPU.  Malformed arguments raise ValueError."""
+    import torch
+    _film_record("film_add", f)
+    shape, V, H, W = _film_accum_shape("film_add", accum)
+    ok = lambda x, tail: isinstance(x, torch.Tensor) and x.device == accum.device and x.dtype == torch.float32 and x.dim() == len(shape) + 1 and tuple(x.shape[1:]) == tail and x.is_contiguous()
+    if not ok(L, shape):
+        raise ValueError(f"film_add: L must be a contiguous float32 tensor of shape (n, {', '.join(map(str, shape))}) on {accum.device}, got "
+                         f"{type(L).__name__} {getattr(L, 'dtype', None)} {tuple(getattr(L, 'shape', ()))} on {getattr(L, 'device', None)}")
+    if not ok(offsets, shape[:-1] + (2,)) or offsets.shape[0] != L.shape[0]:
+        raise ValueError(f"film_add: offsets must be a contiguous float32 tensor of shape ({L.shape[0]}, {', '.join(map(str, shape[:-1]))}, 2) on {accum.device}, got "
+                         f"{type(offsets).__name__} {getattr(offsets, 'dtype', None)} {tuple(getattr(offsets, 'shape', ()))} on {getattr(offsets, 'device', None)}")
+    n = L.shape[0]
+    if V == 0 or n == 0:
+        return accum
+    hstream, _ = _stream_pair(stream, accum.device)
+    _check(lib().gnxr_film_add_device(C.byref(f), W, H, V, n, C.c_void_p(L.data_ptr() or None), C.c_void_p(offsets.data_ptr() or None), C.c_void_p(accum.data_ptr() or None),
+                                      C.c_void_p(hstream or None)))
+    return accum
+
+
+def film_resolve(accum, out=None, stream=None):
+    """The image of a film accumulator (gnxr_film_resolve_device): per pixel (Sr / Wt, Sg / Wt, Sb / Wt, 1), a channel being 0 where Wt is 0
+    or the quotient is negative.  `accum`: as for film_add.  Returns the float32 tensor of accum's shape: `out` when given, which may
+    be `accum` itself.  Queued on `stream` (by default torch's current stream); the call does not wait for the GPU."""
+    import torch
+    shape, V, H, W = _film_accum_shape("film_resolve", accum)
+    hstream, tstream = _stream_pair(stream, accum.device)
+    with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensor to the stream that writes it)
+        out = _out_tensor("film_resolve: out", out, shape, torch.float32, accum.device)
+    if V == 0:
+        return out
+    _check(lib().gnxr_film_resolve_device(W, H, V, C.c_void_p(accum.data_ptr() or None), C.c_void_p(out.data_ptr() or None), C.c_void_p(hstream or None)))
     return out
 
 

@@ -153,6 +153,14 @@ class DenoiseBuffers(C.Structure):   # gnxr_denoise_buffers (carries struct_size
                 ("d_normal", C.c_void_p), ("d_depth", C.c_void_p)]
 
 
+class FilmFilter(C.Structure):   # gnxr_film_filter (carries struct_size): table is host memory, 256 floats, or NULL
+    _fields_ = [("struct_size", i32), ("kind", i32), ("radius_x", f32), ("radius_y", f32), ("a", f32), ("b", f32), ("table", C.POINTER(f32))]
+
+
+# kind of gnxr_film_filter / flags of gnxr_render_filtered_device
+FILTER_BOX, FILTER_TRIANGLE, FILTER_GAUSSIAN, FILTER_MITCHELL, FILTER_TABLE = range(5)
+FILM_CONTINUE = 1
+
 P = C.POINTER
 VP = C.c_void_p
 
@@ -199,6 +207,10 @@ PROTOTYPES = {
     "gnxr_render_aov_device": (C.c_int, [VP, P(RenderParams), P(Camera), P(i32), i32, P(AovBuffers), VP, P(Stats)]),   # cameras, media: host; buffers: device
     "gnxr_render_adaptive_device": (C.c_int, [VP, P(RenderParams), P(AdaptiveParams), VP, VP, VP, P(Stats), P(AdaptiveInfo)]),   # image, counts: device; hipStream_t
     "gnxr_denoise_device": (C.c_int, [P(DenoiseParams), P(DenoiseBuffers), VP, VP]),   # buffers, image: device; hipStream_t
+    "gnxr_film_filter_table": (C.c_int, [P(FilmFilter), P(f32)]),   # host: record -> the 16 x 16 table
+    "gnxr_film_add_device": (C.c_int, [P(FilmFilter), i32, i32, i32, i32, VP, VP, VP, VP]),   # width, height, views, layers; L, offsets, accum: device; hipStream_t
+    "gnxr_film_resolve_device": (C.c_int, [i32, i32, i32, VP, VP, VP]),   # width, height, views; accum, image: device; hipStream_t
+    "gnxr_render_filtered_device": (C.c_int, [VP, P(RenderParams), P(FilmFilter), P(Camera), P(i32), i32, VP, VP, u32, VP, P(Stats)]),   # cameras, media: host; image, accum: device; flags
     "gnxr_material_albedo": (C.c_int, [P(Material), P(f32)]),
     "gnxr_camera_rays_device": (C.c_int, [P(Camera), i32, i32, i32, VP, VP, VP, i64, VP, VP, VP]),   # device addresses + hipStream_t
     "gnxr_bsdf_device": (C.c_int, [VP, VP, VP, VP, VP, i64, i32, VP, VP]),   # device addresses + hipStream_t

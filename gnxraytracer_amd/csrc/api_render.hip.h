@@ -56,6 +56,28 @@ struct ViewSource {
     int n_views;
 };
 
+// gnxr_render_filtered_device: the film that takes the place of k_resolve / k_finish (film_kernel.hip.h).  A finished sub-pass is added to the
+// accumulator layer by layer -- a sample's film offset is recomputed from its Halton index while its tile is staged, so the path state
+// does not grow -- and the image is resolved from the accumulator at the end.
+struct FilmSource {
+    FilmFilter f;
+    FilmTable tab;
+    float4 *accum;                // device memory, (npix, 4): the caller's accumulator, or nullptr: the handle's (RenderState::accum)
+    bool keep;                    // the caller's accumulator continues (GNXR_FILM_CONTINUE); else it is zeroed first
+};
+
+static FilmImage film_image(int W, int H, int n_views) {
+    FilmImage im;
+    im.W = W; im.H = H;
+    im.npix = (long long)n_views * W * H;
+    im.tiles_x = (W + kFilmTile - 1) / kFilmTile;
+    im.tiles_y = (H + kFilmTile - 1) / kFilmTile;
+    im.n_tiles = (long long)n_views * im.tiles_y * im.tiles_x;
+    return im;
+}
+// blocks of a k_film_add launch: one per tile while the device has room for them (a block's LDS, ~15 KB, lets ten share a CU)
+static int film_grid(const FilmImage &im) { return grid_for(im.n_tiles * kBlock, 32); }
+
 // gnxr_render_adaptive_device: the pixels of render_one's loops when they stop at different sample counts (adaptive_kernel.hip.h,
 // api_adaptive.hip.h).  The call works in rounds; the unit of work of a round is one path (as for caller rays), path j of a round being
 // sample n0 + j / n_active of active pixel j % n_active, and a finished chunk is added to the per-pixel sums in chunk order.
@@ -404,6 +426,8 @@ struct RenderRun {
     const RaySource *src;
     const ViewSource *views;
     const PixelListSource *pix;
+    const FilmSource *film = nullptr;   // set by render_one after construction
+    float4 *film_accum = nullptr;
     DScene sc;
     DRender r;
     PathArrays pa;
@@ -630,6 +654,10 @@ void RenderRun::raygen(const PathArrays &at, long long u0, int kk, unsigned char
 }
 void RenderRun::resolve(const PathArrays &at, long long u0, int kk) {
     if (pix) hipLaunchKernelGGL(k_adaptive_accum, dim3(grid_for(pix->round.n_active)), dim3(kBlock), 0, stream, (const float4 *)at.L, pix->round, kk, u0, st.accum.p, st.ad_A.p);
+    else if (film) {   // layer j of the sub-pass: sample u0 + j of every pixel (slot = j * npix + pixel, as k_resolve reads it)
+        const FilmImage im = film_image(r.W, r.H, std::max(1, pl.n_views));
+        hipLaunchKernelGGL(k_film_add<true>, dim3(film_grid(im)), dim3(kBlock), 0, stream, im, film->f, film->tab, (const float4 *)at.L, (const float2 *)nullptr, sc.st, (int)u0, kk, film_accum);
+    }
     else if (!src) hipLaunchKernelGGL(k_resolve, dim3(grid_for(r.npix)), dim3(kBlock), 0, stream, at, st.accum.p, r.npix, kk);
     else hipLaunchKernelGGL(k_store_li, dim3(grid_for(kk)), dim3(kBlock), 0, stream, (const float4 *)at.L, reinterpret_cast<const int4 *>(src->samples + u0), r,
                             n_scene_media, kk, reinterpret_cast<float4 *>(src->L) + u0);
@@ -1000,8 +1028,8 @@ static void fill_stats(const RenderRun &run, double seconds_render, double secon
 static int run_adaptive(RenderRun &run, RenderPlan &pl, PixelListSource &pix, void *d_rgba_out);
 static void adaptive_stats(const PixelListSource &pix, gnxr_stats *stats);
 static int render_one(gnxr_scene *s, const gnxr_render_params *pin, void *d_rgba_out, void *hip_stream, gnxr_stats *stats, bool reserve_only = false,
-                      const RaySource *src = nullptr, const ViewSource *views = nullptr, PixelListSource *pix = nullptr) {
-    if (!s || !pin || (!d_rgba_out && !src)) { set_error("null argument"); return GNXR_ERR_INVALID; }
+                      const RaySource *src = nullptr, const ViewSource *views = nullptr, PixelListSource *pix = nullptr, const FilmSource *film = nullptr) {
+    if (!s || !pin || (!d_rgba_out && !src && !(film && film->accum))) { set_error("null argument"); return GNXR_ERR_INVALID; }
     RenderPlan pl;
     int rc = plan_render(s->cs, pin, src, views, pix, &pl);
     if (rc) return rc;
@@ -1043,9 +1071,12 @@ static int render_one(gnxr_scene *s, const gnxr_render_params *pin, void *d_rgba
 
     RenderRun run(s, stream, pl, src, views, pix, sc, r);
     run.list_media = pl.volpath && (src || views_mixed_media);
+    run.film = film;
+    run.film_accum = film && film->accum ? film->accum : s->st.accum.p;
     // (stream-ordered: the table is read by this call's raygen kernels only, and the call returns after the stream has drained)
     if (views) HIP_TRY(hipMemcpyAsync(s->st.view_cams.p, s->h_view_cams.data(), (size_t)views->n_views * sizeof(DCamera), hipMemcpyHostToDevice, stream));
     if (!src) HIP_TRY(hipMemsetAsync(s->st.accum.p, 0, sizeof(float4) * r.npix, stream));
+    if (film && film->accum && !film->keep) HIP_TRY(hipMemsetAsync(film->accum, 0, sizeof(float4) * r.npix, stream));
     HIP_TRY(hipMemsetAsync(run.dctr, 0, sizeof(Counters), stream));
     HIP_TRY(hipMemsetAsync(s->st.compact_ticket.p, 0, 2 * sizeof(unsigned int), stream));   // once per render; from pass to pass k_compact zeroes its successor's counter
     EventPair ev;
@@ -1054,7 +1085,9 @@ static int render_one(gnxr_scene *s, const gnxr_render_params *pin, void *d_rgba
     HIP_TRY(hipEventRecord(ev.a, stream));
     if (pix) { if ((rc = run_adaptive(run, pl, *pix, d_rgba_out)) != GNXR_OK) return rc; }
     else if ((rc = pl.path_int() ? run_path_loop(run) : run_passes(run)) != GNXR_OK) return rc;
-    if (!src && !pix) {
+    if (film) {
+        if (d_rgba_out) { hipLaunchKernelGGL(k_film_resolve, dim3(grid_for(r.npix)), dim3(kBlock), 0, stream, (const float4 *)run.film_accum, (long long)r.npix, (float4 *)d_rgba_out); ++run.launches; }
+    } else if (!src && !pix) {
         hipLaunchKernelGGL(k_finish, dim3(grid_for(r.npix)), dim3(kBlock), 0, stream, r, (const float4 *)s->st.accum.p, (float4 *)d_rgba_out);
         ++run.launches;
     }

@@ -875,6 +875,84 @@ typedef struct gnxr_denoise_buffers { int32_t struct_size, pad;
 } gnxr_denoise_buffers;
 int gnxr_denoise_device(const gnxr_denoise_params *params, const gnxr_denoise_buffers *in, float *d_rgba_out, void *hip_stream);
 
+/* -- Film: pixel reconstruction filters for renders on device memory ---------------------------------------------------------
+ * gnxr_render_device forms a pixel as the unweighted mean of its own samples.  The film forms it as pbrt-v3's Film does
+ * (Film::AddSample / WriteImage): every sample is weighted into all pixels within the filter's radius of its position on the film,
+ * a pixel being the weighted sum over the weight sum.  It is defined here operation by operation in fp32, with an order of
+ * accumulation, so that a restatement reproduces it bit for bit.  Every operation is a single fp32 operation in the written order
+ * (no fused multiply-add; division is IEEE).
+ *
+ * The filter record.  kind: GNXR_FILTER_BOX, _TRIANGLE, _GAUSSIAN (a = alpha), _MITCHELL (a = B, b = C) or _TABLE (table = 256 floats
+ * in host memory, read during the call); radius_x, radius_y in [0.5, 4].  The record carries struct_size and is not part of
+ * gnxr_abi_sizeof's list.
+ *
+ * The filter table.  gnxr_film_filter_table (host, needs no device) is the single definition of the 16 x 16 table every other call
+ * of this block builds from the record: out[y*16 + x] = Evaluate(px, py) with px = (((float)x + 0.5f) * radius_x) / 16.f and py
+ * likewise (rx = radius_x, ry = radius_y):
+ *   BOX       1
+ *   TRIANGLE  max(0, rx - |px|) * max(0, ry - |py|)
+ *   GAUSSIAN  G(px, expX) * G(py, expY);  G(d, e) = max(0.f, expf(((-a) * d) * d) - e);  expX = expf(((-a) * rx) * rx), expY likewise
+ *             (GaussianFilter.h:16-32); expf is the host C library's
+ *   MITCHELL  M(px / rx) * M(py / ry) with pbrt-v3's Mitchell1D, written out:
+ *               x = |2.f * t|
+ *               x > 1:  ((((((-B - 6.f*C) * x) * x) * x + (((6.f*B + 30.f*C) * x) * x)) + ((-12.f*B - 48.f*C) * x)) + (8.f*B + 24.f*C)) * (1.f / 6.f)
+ *               else:   (((((12.f - 9.f*B) - 6.f*C) * x) * x) * x + ((((-18.f + 12.f*B) + 6.f*C) * x) * x) + (6.f - 2.f*B)) * (1.f / 6.f)
+ *             (sums left to right; in the second form: (cubic + quadratic) + constant)
+ *   TABLE     a copy of the caller's 256 values
+ *
+ * Adding samples.  gnxr_film_add_device adds n_layers layers of samples to an accumulator; all three arrays are device memory of
+ * one device.  With npix = n_views*width*height and pixel lp = v*width*height + x + y*width:
+ *   d_L        (n_layers, npix, 4) fp32: the sample of layer j that belongs to pixel lp at (j*npix + lp)*4; w is ignored
+ *   d_offsets  (n_layers, npix, 2) fp32: its film offset (ux, uy) inside that pixel
+ *   d_accum    (npix, 4) fp32, read and written: (Sr, Sg, Sb, Wt)
+ * For layer j ascending, then source row qy ascending, then source column qx ascending, a sample with both offsets in [0, 1] has
+ *     dx = ((float)qx + ux) - 0.5f;   x0 = (int)ceilf(dx - rx);   x1 = (int)floorf(dx + rx) + 1;        the same in y
+ * and every pixel (x, y) of the same view with x0 <= x < x1 and y0 <= y < y1 inside the image receives
+ *     fx = fabsf(((float)x - dx) * (1.f / rx) * 16.f)   (left to right);   ifx = min((int)floorf(fx), 15);      ify likewise
+ *     w = table[ify*16 + ifx];   S.c = S.c + L.c * w   (the product rounded, then the sum);   Wt = Wt + w
+ * A sample with an offset outside [0, 1], or NaN, adds nothing.  A destination pixel receives its contributions in the order
+ * (j, qy, qx) ascending: that order is the definition, and because j is outermost it does not depend on how layers are batched.
+ * Nothing crosses from one view into another.  The work is queued on hip_stream and the call does not wait for the GPU; the
+ * device is the one that holds d_accum.  n_views == 0 and n_layers == 0 are no-ops.
+ *
+ * Resolving.  gnxr_film_resolve_device writes pixel lp of d_rgba_out as (c(Sr), c(Sg), c(Sb), 1): c(S) = 0 where Wt == 0, otherwise
+ * t = S / Wt, replaced by 0 where t < 0 (a NaN stays).  A division, not pbrt's multiplication by the reciprocal, so that the box
+ * case below meets gnxr_render_device.  d_rgba_out may be d_accum.  Queued on hip_stream, like the add.
+ *
+ * Rendering through the film.  gnxr_render_filtered_device is gnxr_render_views_device with this film in place of the unweighted
+ * mean.  cameras == NULL with n_views == 1 means the scene's own camera and camera medium, as for gnxr_render_aov_device.  One layer is
+ * added per sample s of [spp_begin, spp_end) in ascending order: for pixel (x, y) its L is the Li that gnxr_render_device adds for
+ * that sample, and (ux, uy) are dimensions 0 and 1 of its Halton sample (gnxr_sample_halton; the film position camera_ray() shoots
+ * through).  d_accum == NULL uses an internal accumulator, zeroed first; otherwise the call accumulates into the caller's
+ * (npix, 4) buffer, which is zeroed first unless flags has GNXR_FILM_CONTINUE.  d_rgba_out (n_views images, resolved) may be NULL
+ * when d_accum is given; at least one of the two is required.  samples_per_pass and passes_in_flight keep their meaning and the
+ * result depends on neither.  shard_index must be 0, shard_count and shard_rows 0 or 1: a filter reads its neighbours' samples, so a
+ * caller who shards splits the views.  All four integrators; the support matrix is gnxr_render_device's for the scene's own camera
+ * and gnxr_render_views_device's with cameras.  Locking, stream ordering and the choice of the device are as for
+ * gnxr_render_views_device; the call returns when the outputs are written.  n_views == 0 is a no-op.
+ *
+ * What follows from the definition:
+ *   - a call over [0, a) followed by a call over [a, b) with GNXR_FILM_CONTINUE leaves the bits of one call over [0, b); the same
+ *     holds for gnxr_film_add_device split by layers;
+ *   - with BOX and radius 0.5 every weight is 1, and a pixel whose Wt == (float)spp carries gnxr_render_device's bits;
+ *   - pbrt's window lets a sample with an offset of exactly 0 also reach the pixel below or left of it, and a sample whose qx + ux
+ *     rounds to qx + 1 the pixel above or right of it: those receivers differ from gnxr_render_device.
+ *
+ * GNXR_ERR_INVALID, before anything is queued (the outputs stay untouched): a null or mis-sized filter record; an unknown kind; a
+ * radius outside [0.5, 4] or NaN; a NULL table with TABLE; buffers that are null, not device memory, on different devices, on a
+ * device without a copy of the scene, or not 16-byte aligned (8 for d_offsets); width or height < 1, negative n_views or n_layers;
+ * unknown flag bits; the limits and parameter rules of gnxr_render_views_device.                                                 */
+enum { GNXR_FILTER_BOX = 0, GNXR_FILTER_TRIANGLE = 1, GNXR_FILTER_GAUSSIAN = 2, GNXR_FILTER_MITCHELL = 3, GNXR_FILTER_TABLE = 4 };
+#define GNXR_FILM_CONTINUE 1u   /* flags of gnxr_render_filtered_device: keep what d_accum holds */
+typedef struct gnxr_film_filter { int32_t struct_size, kind; float radius_x, radius_y, a, b; const float *table; } gnxr_film_filter;
+int gnxr_film_filter_table(const gnxr_film_filter *filter, float out[256]);
+int gnxr_film_add_device(const gnxr_film_filter *filter, int32_t width, int32_t height, int32_t n_views, int32_t n_layers, const float *d_L,
+                         const float *d_offsets, float *d_accum, void *hip_stream);
+int gnxr_film_resolve_device(int32_t width, int32_t height, int32_t n_views, const float *d_accum, float *d_rgba_out, void *hip_stream);
+int gnxr_render_filtered_device(gnxr_scene *scene, const gnxr_render_params *params, const gnxr_film_filter *filter, const gnxr_camera *cameras,
+                                const int32_t *camera_media, int32_t n_views, void *d_rgba_out, float *d_accum, uint32_t flags, void *hip_stream,
+                                gnxr_stats *stats);
+
 /* -- Shading queries on device memory: the pieces an integrator is made of, batched -------------------------------------
  * Same conventions as the device calls of the Aggregate seam: every array is device memory of one device that holds a copy of the
  * scene, the work is queued on hip_stream (NULL: the null stream) after what the caller queued there, scratch comes from the
