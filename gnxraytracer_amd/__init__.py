@@ -359,6 +359,12 @@ class Scene:
         _check(lib().gnxr_scene_info(self._h, C.byref(n), C.byref(dmax), C.byref(nv)))
         return {"bvh_nodes": n.value, "bvh_max_depth": dmax.value, "light_voxels": nv.value}
 
+    def nee_apply_counts(self):
+        """gnxr_scene_nee_apply_counts: (light estimates the last PathIntegrator render added inside its traversal launches, by the pass after them)."""
+        t, w = C.c_uint64(), C.c_uint64()
+        _check(lib().gnxr_scene_nee_apply_counts(self._h, C.byref(t), C.byref(w)))
+        return int(t.value), int(w.value)
+
     # editing between frames (gnxr_scene_update_vertices / gnxr_scene_set_camera)
     def update_vertices(self, xyz, first_vertex=0, stream=None, move_lights=False):
         """Move vertices [first_vertex, first_vertex + len(xyz)) of the description's vertex array to xyz (world space, (n, 3) float32):

@@ -198,6 +198,7 @@ PROTOTYPES = {
     "gnxr_render": (C.c_int, [VP, P(RenderParams), P(f32), P(Stats)]),
     "gnxr_render_device": (C.c_int, [VP, P(RenderParams), VP, VP, P(Stats)]),
     "gnxr_render_reserve": (C.c_int, [VP, P(RenderParams)]),
+    "gnxr_scene_nee_apply_counts": (C.c_int, [VP, P(u64), P(u64)]),
     "gnxr_trace_closest": (C.c_int, [VP, P(Ray), i64, P(Hit)]),
     "gnxr_trace_any": (C.c_int, [VP, P(Ray), i64, P(u8)]),
     "gnxr_trace_closest_device": (C.c_int, [VP, VP, i64, VP, VP]),   # device addresses + hipStream_t

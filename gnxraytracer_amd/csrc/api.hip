@@ -204,6 +204,21 @@ int gnxr_scene_info(const gnxr_scene *s, int32_t *n_nodes, int32_t *max_depth, i
     return GNXR_OK;
 }
 
+// Who added the light estimates of the handle's last PathIntegrator render (Counters::nee_applied_*), summed over its devices.  A call of
+// its own: gnxr_stats keeps its layout.
+int gnxr_scene_nee_apply_counts(gnxr_scene *s, uint64_t *in_trace, uint64_t *by_sweep) {
+    if (!s) { set_error("null argument"); return GNXR_ERR_INVALID; }
+    std::lock_guard<std::recursive_mutex> lock(s->render_mutex);
+    uint64_t t = 0, w = 0;
+    for (size_t i = 0; i <= s->replicas.size(); ++i) {
+        const Counters *c = s->copy(i)->h_counters;
+        if (c) { t += c->nee_applied_trace; w += c->nee_applied_sweep; }
+    }
+    if (in_trace) *in_trace = t;
+    if (by_sweep) *by_sweep = w;
+    return GNXR_OK;
+}
+
 int gnxr_render_device(gnxr_scene *s, const gnxr_render_params *pin, void *d_rgba_out, void *hip_stream, gnxr_stats *stats) {
     return render_sharded(s, pin, d_rgba_out, hip_stream, stats);
 }

@@ -109,6 +109,9 @@ struct Knobs {
     // GNXR_MIS_DEFER_DRAIN_AT: entries of a wave's list at which the wave drains it between two vertices, 1 .. 64 (default 64; small values
     // let tests reach the drains inside the loop).  Per call (render)
     static int mis_defer_drain_at() { return std::max(1, std::min(64, env_int("GNXR_MIS_DEFER_DRAIN_AT", 64))); }
+    // GNXR_NO_TRACE_NEE_APPLY: set = k_trace4 adds no light estimates in its set-up batches; k_nee_combine adds them all after the launch (same
+    // image and counts bit for bit: the A/B and test switch; default unset).  Per call (render)
+    static bool no_trace_nee_apply() { return env_set("GNXR_NO_TRACE_NEE_APPLY"); }
     // GNXR_HOST_LIGHT_GRID: set = the spatial light table is built on the host (default unset).  Per call (ensure_grid)
     static bool host_light_grid() { return env_set("GNXR_HOST_LIGHT_GRID"); }
     // GNXR_BINARY_BVH: set = the scene renders on the binary tree, never the 4-wide one (default unset).  Per call (scene creation)

@@ -707,6 +707,7 @@ static int run_path_loop(RenderRun &run) {
     const int stagger = Knobs::pipe_cut() >= 0 ? Knobs::pipe_cut() : std::max(1, (pl.p.max_depth + 2 + lag + R - 1) / R);
     int *qbuf[2] = {st.queue_a.p, st.queue_b.p};
     int in_idx = 0;
+    const int nee_in_trace = Knobs::no_trace_nee_apply() ? 0 : 1;   // TraceWork::nee_in_trace
     const unsigned *cnt_ptr = &dctr->n_queue;  // where the count of the queue in flight lives on the device (k_loop_tail / k_queue_merge write it)
     size_t next_sub = 0, done_subs = 0;
     int iter = 0, last_start = -(1 << 20), newest_seen = -1;
@@ -792,12 +793,12 @@ static int run_path_loop(RenderRun &run) {
         // C. continuation rays (and new camera rays), shadow and MIS rays of the vertices just shaded; then their light estimates
         if (any_active || start) {
             TraceWork tw{qbuf[trace_idx], (int)n_trace_upper, st.queue_nee.p, any_active ? (int)n_upper : 0, nullptr, reinterpret_cast<unsigned char *>(st.nee_vis.p), cnt_ptr,
-                         any_active ? (const unsigned *)&dctr->q_nee : nullptr};
+                         any_active ? (const unsigned *)&dctr->q_nee : nullptr, nee_in_trace};
             run.launch_trace(tw, 0, 0, false);
             if (any_active) {
                 if (run.timing) run.timer.begin(1, stream);
                 hipLaunchKernelGGL(k_nee_combine, dim3(grid_for(n_upper)), dim3(kBlock), 0, stream, run.pa, (const int *)st.queue_nee.p, (int)n_upper, reinterpret_cast<const unsigned char *>(st.nee_vis.p),
-                                   (const unsigned *)&dctr->q_nee);
+                                   (const unsigned *)&dctr->q_nee, &dctr->nee_applied_sweep);   // the sweep: every vertex k_trace4 has not added itself
                 if (run.timing) run.timer.end(stream);
                 ++run.launches;
             }

@@ -52,7 +52,8 @@ struct PathArrays {
     float4 *mis_o;    // [4] MIS ray origin, w: expected leaf triangle (int bits; -1 == expects a miss)
     float4 *mis_d;    // [4] MIS ray direction
     float4 *mis_Y;    // f*Li*w/scatteringPdf if the expectation holds (plain array)
-    unsigned int *nee_vis;   // PathIntegrator: per path [0] shadow ray unoccluded, [1] MIS ray found what it expects (bytes written by k_trace), [2] record flags (k_shade)
+    unsigned int *nee_vis;   // PathIntegrator: per path [0] shadow ray unoccluded, [1] MIS ray found what it expects (bytes written by k_trace: bit 0; k_trace4 adds
+                             // bit 1 = traced), [2] record flags (k_shade: the whole word, so the other bytes start at 0), [3] 1 = the light estimate is in L (TraceWork::vis)
     // bind the record fields to the five groups
     __host__ __device__ void bind_records(float4 *const g[kRecGroups]) {
         ray_o = g[0]; ray_d = g[0] + 1; beta = g[1]; meta = reinterpret_cast<uint2 *>(g[1] + 1);
@@ -93,6 +94,7 @@ struct Counters {
     unsigned long long rays_continue, rays_shadow, rays_mis;   // summed over the iterations: continuation rays of surviving paths, shadow rays, MIS rays
     unsigned long long li_bad;                      // gnxr_li_device: ~index of the first sample record out of range (0: none; li_kernel.hip.h)
     unsigned int compact_stall;                     // k_compact: a look-back reached its poll cap (never in a correct run; the host reports GNXR_ERR_RUNTIME)
+    unsigned long long nee_applied_trace, nee_applied_sweep;   // NEE vertices whose light estimate was added by k_trace4's set-up batches / by k_nee_combine (one atomic per wave)
 };
 
 struct DScene {

@@ -29,6 +29,14 @@
 // read of q_nee by the owing lanes, a fence), and only after its shadow rays have all been drawn from the queue -- where most vertices have
 // both rays that doubles the set-up batches of the NEE range (the parent's MIS batches were full ones there); and the ballot over `pk` that
 // finds owing lanes runs at every refill that finds the queue empty, in the continuation range too.  Measured: profiles/README.md.
+// Light estimates inside the launch (TraceWork::nee_in_trace): a set-up batch of the NEE range also looks, lane by lane, at the vertex items this
+// wave set up kNeeLag = 128 items earlier in the chunk it owns.  retire_ray marks a traced ray in bit 1 of its result byte; a vertex whose rays
+// are all back gets L += beta * Ld right there (nee_apply, the function k_nee_combine calls) and byte 3 of its word set, and k_nee_combine, which
+// still runs after the launch, adds the others: the last 128 items of every chunk, the 128- and 64-item chunks of the tail, the vertices with
+// a ray still under way.  Every lane is on in a set-up batch and the wave waits for dependent loads there anyway; the three loads of the
+// lagging vertex (queue entry, word, records) are issued between the set-up's own.  An item has one owner and its rays are only ever taken by
+// lanes of the wave that parked them, so nobody else touches the vertex's word or its L during the launch; a workgroup-scope fence before the
+// word is read makes the wave's own retire stores visible (same CU, same L1).  Measured: profiles/README.md.
 // Q selects where the rays come from and where results go: the render's path records (kT4Render), or caller-supplied rays of a batched
 // query (kT4QueryClosest / kT4QueryAny, query_kernel.hip.h).  The walk between the two is the same code.
 #pragma once
@@ -62,6 +70,17 @@ constexpr int kRayRecDwords = 11;        // LDS record of a set-up ray: o.xyz tM
 #endif
 constexpr int kRayQueue = GX_T4_RQ;      // set-up rays a wave parks in LDS per batch (32 frees LDS for 6 more stack levels but halves the set-up's lane use: slower)
 constexpr int kRqStride = (kBlock / 64) * kRayQueue;   // dwords per record field per block
+#ifndef GX_T4_NEE_LAG
+#define GX_T4_NEE_LAG 128
+#endif
+constexpr int kNeeLag = GX_T4_NEE_LAG;   // a set-up batch adds the light estimates of the vertex items the wave set up this many items earlier (whole batches: the lagging items are behind the pool)
+#ifndef GX_T4_NEE_TAIL
+#define GX_T4_NEE_TAIL 0   // 1: a round over the last kNeeLag items of a chunk when it runs out (measured: more vertices in the kernel, no faster; profiles/README.md)
+#endif
+#ifndef GX_T4_NEE_BESIDE
+#define GX_T4_NEE_BESIDE 0   // 1: the lagging vertex's sh_X / nbeta / L are loaded beside its word, not under the test of it
+#endif
+static_assert(kNeeLag >= 64 && kNeeLag % 64 == 0, "the lagging items must lie behind the batch that is being set up");
 GX_DEV int trace4_lds_dwords_per_thread(bool sph) { return kRayRecDwords + (sph ? 1 : 0); }
 
 // COUNT: count node steps / triangle tests / leaf re-tests.  SPH: the scene has spheres.  SPILL: the traversal stack may outgrow its LDS part.
@@ -131,6 +150,7 @@ __global__ void GX_T4_BOUNDS k_trace4(DScene sc, typename Trace4Src<Q>::type pa,
     unsigned poolBase = 0, poolCount = 0;   // wave-uniform: the chunk of work items this wave owns
     bool exhausted = false;                 // wave-uniform: the global cursor ran past `total`
     unsigned rqHead = 0, rqCount = 0;       // wave-uniform: set-up rays waiting in LDS
+    unsigned nNeeApplied = 0;               // wave-uniform: light estimates this wave has added (Counters::nee_applied_trace)
 
     // per-lane ray state
     bool live = false;
@@ -185,15 +205,37 @@ __global__ void GX_T4_BOUNDS k_trace4(DScene sc, typename Trace4Src<Q>::type pa,
             }
         }
         else if (kind == 1) {
-            if (w.vis) w.vis[4 * (size_t)path] = hitLeaf == -1 ? 1 : 0;
+            // (bit 1 of a result byte: this ray has been traced -- what the set-up batch that adds light estimates waits for, nee_ready)
+            if (w.vis) w.vis[4 * (size_t)path] = hitLeaf == -1 ? 3 : 2;
             else reinterpret_cast<float *>(&pa.sh_o[(size_t)path * kRS])[3] = hitLeaf == -1 ? 1.f : 0.f;
         } else {
             const int expect = __float_as_int(pa.mis_o[(size_t)path * kRS].w);   // the leaf triangle the light sample expects (-1: nothing), written by k_shade
             bool ok = (expect >= 0) ? (hitLeaf == expect) : (hitLeaf == -1);
-            if (w.vis) w.vis[4 * (size_t)path + 1] = ok ? 1 : 0;
+            if (w.vis) w.vis[4 * (size_t)path + 1] = ok ? 3 : 2;
             else reinterpret_cast<float *>(&pa.mis_o[(size_t)path * kRS])[3] = ok ? 1.f : 0.f;
         }
         live = false;
+    };
+    // One round of light estimates: lane l looks at work item first + l where that lies in [lo, hi) -- vertex items this wave has set up
+    // and nobody else touches -- and adds the estimate of a vertex whose rays are all back (nee_ready), marking it; the others are left
+    // to k_nee_combine.  (first may have wrapped below 0: such lanes fail the test against hi.)
+    auto nee_round = [&](unsigned first, unsigned lo, unsigned hi) {
+        if constexpr (Q == kT4Render) {
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // this wave's retire stores have landed (the CU's L1 serves its own stores)
+            const unsigned j = first + (unsigned)lane;
+            bool did = false;
+            if (j >= lo && j < hi) {
+                const int p = w.q_nee[j - (unsigned)w.n_closest];
+                unsigned *vw = reinterpret_cast<unsigned *>(w.vis) + p;
+                const unsigned v = __hip_atomic_load(vw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                if (nee_ready(v)) {
+                    nee_apply(pa, p, v);
+                    reinterpret_cast<unsigned char *>(vw)[3] = 1;
+                    did = true;
+                }
+            }
+            nNeeApplied += (unsigned)__popcll(__ballot(did));
+        }
     };
 #ifdef GX_TRACE_STATS
 #define GX_TICK(i) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); GX_STAT(i, t_ - tick_); tick_ = t_; } while (0)
@@ -212,6 +254,16 @@ __global__ void GX_T4_BOUNDS k_trace4(DScene sc, typename Trace4Src<Q>::type pa,
                 // the last batch left MIS rays behind: they are set up (as a batch of their own) before the pool moves on or new work is fetched
                 const bool misPass = Q == kT4Render && __ballot((pk & kMisOwed) != 0) != 0;
                 if (!misPass && poolCount == 0 && !exhausted) {
+#if GX_T4_NEE_TAIL
+                    // the chunk that has just run out: its last kNeeLag items have had no set-up batch behind them.  Their rays have all been
+                    // drawn from the queue, most of the older ones are back: one round per 64 of them before the wave asks for more work
+                    if (Q == kT4Render && !firstFetch && w.nee_in_trace && w.vis && !w.order && poolBase > (unsigned)w.n_closest) {
+                        const unsigned len = poolBase <= plan.big ? plan.c : (poolBase <= plan.mid_end ? 128u : (poolBase - 1u - plan.mid_end) % 64u + 1u);
+                        const unsigned lo = max(poolBase - len, (unsigned)w.n_closest);
+                        for (unsigned back = (unsigned)kNeeLag; back >= 64u; back -= 64u)
+                            if (poolBase - lo + 64u > back) nee_round(poolBase - back, lo, poolBase);
+                    }
+#endif
                     // the cursor counts chunks (chunk_plan / chunk_range, trace_kernel.hip.h); a wave's FIRST chunk is its own number -- no
                     // atomic: 5120 waves asking at once at the start of a launch queue up behind one address for ~60 us
                     unsigned v = waveId;
@@ -233,15 +285,31 @@ __global__ void GX_T4_BOUNDS k_trace4(DScene sc, typename Trace4Src<Q>::type pa,
                     // next `take` work items, or (misPass) the MIS rays of the vertex items of the previous batch, over which the pool has
                     // not moved on yet: lane l has item poolBase + l in both
                     const unsigned take = min(poolCount, (unsigned)kRayQueue);
+                    // ---- light estimates of the vertices this wave set up kNeeLag items earlier in this chunk: lane l looks at item
+                    // poolBase + l - kNeeLag.  Their rays were parked by this wave and taken by its lanes alone, so no other wave touches the
+                    // vertex's word or its L; where all its rays are back (nee_ready) the lane adds the estimate and marks the vertex, the others
+                    // are left to k_nee_combine.  The chunk's first item follows from its end and the plan (chunk_range): the kernel has no
+                    // register for it.  The three dependent loads ride on the set-up's own: the queue entry is asked for here, the vertex's
+                    // word once the set-up's records are in, and the estimate is added after the set-up's arithmetic.
+                    int neeP = -1;   // the lagging vertex's path
+                    bool neeOn = false;   // wave-uniform: this batch has lagging items
+                    if constexpr (Q == kT4Render) {
+                        const unsigned chunkEnd = poolBase + poolCount;
+                        // (a 64-item chunk, the only kind that can be cut short by the end of the list, never has a lagging item of its own)
+                        const unsigned chunkLen = chunkEnd <= plan.big ? plan.c : (chunkEnd <= plan.mid_end ? 128u : 0u);
+                        const unsigned lo = max(chunkEnd - chunkLen, (unsigned)w.n_closest) + (unsigned)kNeeLag;   // first position whose lagging item is a vertex of this chunk
+                        neeOn = !misPass && w.nee_in_trace && w.vis && !w.order && poolBase + 63u >= lo;
+                        if (neeOn && poolBase + (unsigned)lane >= lo) neeP = w.q_nee[poolBase + (unsigned)lane - (unsigned)kNeeLag - (unsigned)w.n_closest];
+                    }
                     bool valid = false, wantMis = false;
                     float4 r0 = make_float4(0, 0, 0, 0), r1 = r0, r2 = r0;
                     int sphHit = -1;
+                    float4 o4 = make_float4(0, 0, 0, 0), d4 = o4;
+                    int kind_ = 0, path_ = 0, any_ = 0;
+                    float tMax_ = 0.f;
                     if (misPass ? (pk & kMisOwed) != 0 : (unsigned)lane < take) {
                         unsigned i = poolBase + (unsigned)lane;
                         if (w.order) i = w.order[i];
-                        float4 o4, d4;
-                        int kind_ = 0, path_, any_ = 0;
-                        float tMax_;
                         valid = true;
                         if constexpr (Q != kT4Render) {   // a query: the caller's gnxr_ray i, one kind for the whole launch
                             path_ = (int)i;
@@ -275,6 +343,23 @@ __global__ void GX_T4_BOUNDS k_trace4(DScene sc, typename Trace4Src<Q>::type pa,
                                 any_ = __float_as_int(o4.w) < 0 ? 1 : 0;
                             }
                         }
+                    }
+                    unsigned neeV = 0;   // the lagging vertex's word
+#if GX_T4_NEE_BESIDE
+                    float4 neeX = make_float4(0, 0, 0, 0), neeB = neeX, neeL = neeX;   // ... and its records, asked for beside the word (one dependent level less, bytes for the vertices that add nothing)
+#endif
+                    if constexpr (Q == kT4Render) {
+                        if (neeOn) {
+                            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // this wave's retire stores have landed (the CU's L1 serves its own stores)
+                            if (neeP >= 0) {
+                                neeV = __hip_atomic_load(reinterpret_cast<unsigned *>(w.vis) + neeP, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+#if GX_T4_NEE_BESIDE
+                                neeX = pa.sh_X[(size_t)neeP * kRS]; neeB = pa.nbeta[(size_t)neeP * kRS]; neeL = pa.L[neeP];
+#endif
+                            }
+                        }
+                    }
+                    {
                         if (valid) {
                             const V3 o(o4.x, o4.y, o4.z), d(d4.x, d4.y, d4.z);
                             const V3 iv(1.f / d.x, 1.f / d.y, 1.f / d.z);          // BVHAccel.cpp:657
@@ -307,6 +392,20 @@ __global__ void GX_T4_BOUNDS k_trace4(DScene sc, typename Trace4Src<Q>::type pa,
                     }
                     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the records are read by other lanes of this wave
                     rqCount = (unsigned)__popcll(vm); rqHead = 0;
+                    if constexpr (Q == kT4Render) {
+                        if (neeOn) {
+                            const bool did = neeP >= 0 && nee_ready(neeV);
+                            if (did) {
+#if GX_T4_NEE_BESIDE
+                                if (nee_adds(neeV)) pa.L[neeP] = nee_sum(pa, neeP, neeV, neeX, neeB, neeL);
+#else
+                                nee_apply(pa, neeP, neeV);
+#endif
+                                reinterpret_cast<unsigned char *>(w.vis)[4 * (size_t)neeP + 3] = 1;
+                            }
+                            nNeeApplied += (unsigned)__popcll(__ballot(did));
+                        }
+                    }
                     bool advance = true;
                     if (Q == kT4Render) {
                         // the vertex items of this batch that also have a MIS ray: their lanes remember it (kMisOwed), and the pool stays on the
@@ -520,6 +619,7 @@ __global__ void GX_T4_BOUNDS k_trace4(DScene sc, typename Trace4Src<Q>::type pa,
 #ifdef GX_TRACE_STATS
     if (lane == 0) for (int i = 0; i < 24; ++i) if (st_[i]) atomicAdd(&g_trace_stats[i], st_[i]);
 #endif
+    if (Q == kT4Render && nNeeApplied != 0 && lane == 0) atomicAdd(&ctr->nee_applied_trace, (unsigned long long)nNeeApplied);
     if (COUNT) {
         atomicAdd(&ctr->nodes, (unsigned long long)cntNodes);
         atomicAdd(&ctr->tris, (unsigned long long)cntTris);

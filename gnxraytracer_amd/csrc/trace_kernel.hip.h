@@ -33,10 +33,13 @@ struct TraceWork {
                                            // has a shadow ray, bit 1 = it has a MIS ray too, which only then costs a read of the MIS records
     const unsigned *order;                 // nullptr, or a permutation of the work items: position in the launch -> work item (a caller-supplied ordering; unused by the library itself)
     unsigned char *vis;                    // nullptr: visibility results go to sh_o[path].w / mis_o[path].w (float 1 / 0).  Otherwise 4 bytes per path:
-                                           // [0] shadow ray unoccluded, [1] MIS ray found what the light sample expects (written here), [2] the record's
-                                           // flags (written by k_shade) -- k_nee_combine then reads one word instead of three float4
+                                           // [0] shadow ray unoccluded, [1] MIS ray found what the light sample expects (written here: bit 0 the result;
+                                           // k_trace4 also sets bit 1, "this ray has been traced"), [2] the record's flags (written by k_shade, which
+                                           // zeroes the other three bytes), [3] 1 once the vertex's light estimate has been added to L (nee_apply)
+                                           // -- k_nee_combine then reads one word instead of three float4
     const unsigned *n_closest_dev, *n_nee_dev;   // nullptr, or where the two counts live on the device (the device-driven path loop: the host never reads
                                            // them; n_closest / n_nee then only bound the launch)
+    int nee_in_trace;                      // k_trace4 with `vis` and without `order`: add the light estimates of traced vertices in later set-up batches (0: all by k_nee_combine)
 };
 // the counts a traversal kernel works on: the device-side ones when the launch carries them
 GX_DEV void trace_work_counts(TraceWork &w) {
@@ -447,27 +450,58 @@ __global__ void __launch_bounds__(kBlock) k_trace(DScene sc, PathArrays pa, Trac
 // two visibility results of the vertex are known.  Pure streaming: per NEE vertex one word of flags + results (TraceWork::vis), X, Y when
 // the vertex has a MIS ray, beta and L (72 B read, 16 B written; the first version read the three float4 that carried flags and results
 // in their w lanes: 128 B).
-static __global__ void __launch_bounds__(kBlock) k_nee_combine(PathArrays pa, const int *__restrict__ queue, int n, const unsigned char *__restrict__ vis, const unsigned *n_dev = nullptr) {
+//
+// Who adds a vertex: k_trace4 itself, in a later set-up batch of the wave that traced the vertex's rays (trace4_kernel.hip.h), where it can --
+// it then stores 1 into byte 3 of the vertex's word -- and k_nee_combine, the sweep after the launch, every vertex whose byte 3 is still 0.
+// Both call nee_apply (or, where the records are loaded ahead of the test, its two halves nee_adds and nee_sum), so a vertex is added once, by
+// the same statements, whoever gets to it.
+// `v` is the vertex's word (TraceWork::vis): the results are bit 0 of bytes 0 and 1, the record's flags byte 2.
+//
+// nee_adds: the skip rule.  false: neither ray arrived (the light sample is occluded and the BSDF sample missed the light): Ld = 0, and L + beta * (0 / pdf) == L bit
+// for bit when beta is finite (k_shade says so in bit 7 of the flags; pdf > 0) -- a third to a half of the vertices; their three
+// records and L are not touched
+GX_DEV bool nee_adds(unsigned v) {
+    const unsigned flags = (v >> 16) & 0xffu;
+    return (flags & 0x80u) || ((flags & 1u) && (v & 1u)) || ((flags & 2u) && ((v >> 8) & 1u));
+}
+// the new L of a vertex that adds: X4 = sh_X, nb = nbeta, L4 = L of the path (mis_Y is read here, where the MIS ray arrived)
+GX_DEV float4 nee_sum(const PathArrays &pa, int path, unsigned v, const float4 &X4, const float4 &nb, const float4 &L4) {
+    const int flags = (int)((v >> 16) & 0xffu);
+    Spec Ld(0.f);
+    if ((flags & 1) && (v & 1u)) Ld = Ld + Spec(X4.x, X4.y, X4.z);
+    if ((flags & 2) && ((v >> 8) & 1u)) {
+        float4 Y4 = pa.mis_Y[path];
+        Spec Y(Y4.x, Y4.y, Y4.z);
+        if (!Y.is_black()) Ld = Ld + Y;
+    }
+    Spec add = Spec(nb.x, nb.y, nb.z) * (Ld / X4.w);
+    return make_float4(L4.x + add.r, L4.y + add.g, L4.z + add.b, 0.f);
+}
+GX_DEV void nee_apply(const PathArrays &pa, int path, unsigned v) {
+    if (!nee_adds(v)) return;
+    const float4 X4 = pa.sh_X[(size_t)path * kRS], nb = pa.nbeta[(size_t)path * kRS], L4 = pa.L[path];
+    pa.L[path] = nee_sum(pa, path, v, X4, nb, L4);
+}
+// every ray the record's flags name has been traced (bit 1 of its result byte, k_trace4's retire_ray) and nobody has added the vertex yet
+GX_DEV bool nee_ready(unsigned v) {
+    const unsigned flags = v >> 16;
+    return (!(flags & 1u) || (v & 2u)) && (!(flags & 2u) || (v & 0x200u)) && (v >> 24) == 0;
+}
+
+static __global__ void __launch_bounds__(kBlock) k_nee_combine(PathArrays pa, const int *__restrict__ queue, int n, const unsigned char *__restrict__ vis, const unsigned *n_dev = nullptr,
+                                                               unsigned long long *n_applied = nullptr) {
     if (n_dev) n = (int)*n_dev;
+    unsigned mine = 0;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         int path = queue[i];
         const unsigned v = reinterpret_cast<const unsigned *>(vis)[path];
-        const int flags = (int)((v >> 16) & 0xffu);
-        // neither ray arrived (the light sample is occluded and the BSDF sample missed the light): Ld = 0, and L + beta * (0 / pdf) == L bit
-        // for bit when beta is finite (k_shade says so in bit 7 of the flags; pdf > 0) -- a third to a half of the vertices; their three
-        // records and L are not touched
-        if (!(flags & 0x80) && !(((flags & 1) && (v & 0xffu)) || ((flags & 2) && ((v >> 8) & 0xffu)))) continue;
-        float4 X4 = pa.sh_X[(size_t)path * kRS];
-        Spec Ld(0.f);
-        if ((flags & 1) && (v & 0xffu)) Ld = Ld + Spec(X4.x, X4.y, X4.z);
-        if ((flags & 2) && ((v >> 8) & 0xffu)) {
-            float4 Y4 = pa.mis_Y[path];
-            Spec Y(Y4.x, Y4.y, Y4.z);
-            if (!Y.is_black()) Ld = Ld + Y;
-        }
-        float4 nb = pa.nbeta[(size_t)path * kRS], L4 = pa.L[path];
-        Spec add = Spec(nb.x, nb.y, nb.z) * (Ld / X4.w);
-        pa.L[path] = make_float4(L4.x + add.r, L4.y + add.g, L4.z + add.b, 0.f);
+        if (v >> 24) continue;   // added inside the trace launch
+        nee_apply(pa, path, v);
+        ++mine;
+    }
+    if (n_applied) {   // Counters::nee_applied_sweep: one atomic per wave
+        for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o);
+        if (__lane_id() == 0 && mine) atomicAdd(n_applied, (unsigned long long)mine);
     }
 }
 

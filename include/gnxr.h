@@ -646,6 +646,11 @@ int gnxr_render_device(gnxr_scene *scene, const gnxr_render_params *params, void
  * them inside the call -- run one small-budget adaptive call up front where the first frame must not allocate. */
 int gnxr_render_reserve(gnxr_scene *scene, const gnxr_render_params *params);
 
+/* Diagnostics of the handle's last PathIntegrator render: how many light-sampling vertices had their estimate added to the path's radiance
+ * inside the traversal launch that traced their rays, and how many by the pass after it.  The two sum to the vertices the render queued;
+ * with GNXR_NO_TRACE_NEE_APPLY set in the environment the first is 0.  Either pointer may be NULL.  (Not part of gnxr_stats: its layout is fixed.) */
+int gnxr_scene_nee_apply_counts(gnxr_scene *scene, uint64_t *in_trace, uint64_t *by_sweep);
+
 /* -- Aggregate seam (replaces Scene::Intersect / Scene::IntersectP), batched ------------ */
 int gnxr_trace_closest(gnxr_scene *scene, const gnxr_ray *rays, int64_t n, gnxr_hit *hits);
 int gnxr_trace_any(gnxr_scene *scene, const gnxr_ray *rays, int64_t n, uint8_t *occluded);
