@@ -1337,6 +1337,35 @@ class PathIntegrator:
                                                  C.c_void_p(hstream or None), C.byref(st)))
         return out, stats_dict(st)
 
+    def BakeLightmap(self, scene, lm_uv, width, height, spp, dilate=2, flip=False, medium=-1, out=None, stream=None, **kw):
+        """A lightmap of the scene (gnxr_bake_lightmap_device; the definition, operation by operation: include/gnxr.h): the irradiance
+        that arrives at the scene's triangles, in the (width, height) atlas of `lm_uv` -- a contiguous float32 (n_triangles, 6) tensor on
+        the scene's device, (u0 v0 u1 v1 u2 v2) per triangle in authoring order.  Per covered texel: pi times the mean over `spp`
+        samples of this integrator's Li along cosine-distributed rays off the surface (bake_texels, surface_rays and Li, summed in sample
+        order), alpha 1; empty texels are 0; then `dilate` gutter passes (bake_dilate).  `flip` bakes the back side, `medium` is the
+        medium the rays start in.  Returns (float32 tensor [H, W, 4] -- `out` when given --, stats dict with camera_samples = covered
+        texels * spp).  The live scene is read: a bake after an edit sees it.  Runs on `stream` (by default torch's current stream) and
+        returns once the lightmap is written.  Keyword arguments: samples_per_pass (paths per sub-batch), passes_in_flight."""
+        import torch
+        width, height = int(width), int(height)
+        if width <= 0 or height <= 0:
+            raise ValueError(f"BakeLightmap: invalid atlas size {width} x {height}")
+        if int(dilate) < 0:
+            raise ValueError(f"BakeLightmap: dilate must be >= 0, got {dilate}")
+        unknown = [k for k in kw if k not in ("samples_per_pass", "passes_in_flight")]
+        if unknown:
+            raise ValueError(f"BakeLightmap: unexpected arguments {unknown} (samples_per_pass, passes_in_flight)")
+        _bake_uv("BakeLightmap", scene, lm_uv)
+        hstream, tstream = _stream_pair(stream, lm_uv.device)
+        with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensor to the stream that writes it)
+            out = _out_tensor("BakeLightmap: out", out, (height, width, 4), torch.float32, lm_uv.device)
+        p = self.params(width, height, spp, **kw)
+        bp = _abi.BakeParams(C.sizeof(_abi.BakeParams), _abi.BAKE_FLIP_NORMALS if flip else 0, int(dilate), int(medium))
+        st = Stats()
+        _check(lib().gnxr_bake_lightmap_device(scene._h, C.byref(p), C.byref(bp), C.c_void_p(lm_uv.data_ptr() or None), C.c_void_p(out.data_ptr() or None),
+                                               C.c_void_p(hstream or None), C.byref(st)))
+        return out, stats_dict(st)
+
     def Render(self, scene, width, height, spp, **kw):
         """Integrator::Render: returns (float32 image [H, W, 4], stats dict)."""
         p = self.params(width, height, spp, **kw)
@@ -1582,6 +1611,91 @@ def film_resolve(accum, out=None, stream=None):
     if V == 0:
         return out
     _check(lib().gnxr_film_resolve_device(W, H, V, C.c_void_p(accum.data_ptr() or None), C.c_void_p(out.data_ptr() or None), C.c_void_p(hstream or None)))
+    return out
+
+
+def _bake_uv(name, scene, lm_uv):
+    """the lightmap uv set of the baking calls: a contiguous float32 (n_triangles, 6) tensor on the scene's device"""
+    import torch
+    scene._device_tensor(f"{name}: lm_uv", lm_uv, torch.float32, 6)
+    if lm_uv.shape[0] != scene.n_triangles:
+        raise ValueError(f"{name}: lm_uv has {lm_uv.shape[0]} rows for {scene.n_triangles} triangles")
+    return lm_uv
+
+
+def bake_texels(scene, lm_uv, width, height, out=None, stream=None):
+    """Atlas rasterisation on the GPU (gnxr_bake_texels_device; the definition: include/gnxr.h): `lm_uv` is a contiguous float32
+    (n_triangles, 6) tensor on the scene's device, (u0 v0 u1 v1 u2 v2) per triangle in authoring order.  Returns (tri, bary): the int32
+    (H, W) tensor of the lowest triangle that covers each texel centre (-1: none; both windings, inclusive edges) and the float32
+    (H, W, 2) tensor of its barycentrics (b1, b2) there.  `out`: a (tri, bary) pair to write into.  Queued on `stream` (by default
+    torch's current stream); the call does not wait for the GPU."""
+    import torch
+    width, height = int(width), int(height)
+    if width <= 0 or height <= 0:
+        raise ValueError(f"bake_texels: invalid atlas size {width} x {height}")
+    _bake_uv("bake_texels", scene, lm_uv)
+    hstream, tstream = _stream_pair(stream, lm_uv.device)
+    out_tri, out_bary = out if out is not None else (None, None)
+    with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensors to the stream that writes them)
+        tri = _out_tensor("bake_texels: out[0]", out_tri, (height, width), torch.int32, lm_uv.device)
+        bary = _out_tensor("bake_texels: out[1]", out_bary, (height, width, 2), torch.float32, lm_uv.device)
+    _check(lib().gnxr_bake_texels_device(scene._h, C.c_void_p(lm_uv.data_ptr() or None), width, height, C.c_void_p(tri.data_ptr() or None),
+                                         C.c_void_p(bary.data_ptr() or None), C.c_void_p(hstream or None)))
+    return tri, bary
+
+
+def surface_rays(scene, tri, bary, px, py, s, width, height, flip=False, medium=-1, out=None, stream=None):
+    """Rays off the scene's surfaces on the GPU (gnxr_surface_rays_device), the texture-space sibling of camera_rays_device: record i is
+    the point with barycentrics bary[i] = (b1, b2) on triangle tri[i] (authoring order, current vertices) and sample s[i] of pixel
+    (px[i], py[i]) of a HaltonSampler over (width, height).  tri, px, py, s: contiguous int32 (n,) tensors, bary: float32 (n, 2), all on
+    the scene's device.  Returns (rays [n, 8] float32 in the gnxr_ray layout, samples [n, 4] int32 = px, py, s, medium, pn [n, 8] float32 =
+    position, 0, normal, 0): rays leave cosine-distributed about the geometric normal (negated with `flip`), drawn from Halton dimensions
+    3 and 4, from an origin offset by the point's error bound; rays and samples are what integrator.Li takes.  `out`: a (rays, samples,
+    pn) triple to write into.  A degenerate triangle gives zero rows; a triangle, pixel or sample out of range raises GnxrError after the
+    others are finished, its rows are 0.  Queued on `stream` (by default torch's current stream)."""
+    import torch
+    scene._device_tensor("surface_rays: tri", tri, torch.int32, 0)
+    n = tri.shape[0]
+    scene._device_tensor("surface_rays: bary", bary, torch.float32, 2)
+    for what, x in (("px", px), ("py", py), ("s", s)):
+        scene._device_tensor(f"surface_rays: {what}", x, torch.int32, 0)
+        if x.shape[0] != n:
+            raise ValueError(f"surface_rays: {what} has {x.shape[0]} entries for {n} triangles")
+    if bary.shape[0] != n:
+        raise ValueError(f"surface_rays: bary has {bary.shape[0]} rows for {n} triangles")
+    hstream, tstream = _stream_pair(stream, tri.device)
+    o_rays, o_samples, o_pn = out if out is not None else (None, None, None)
+    with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensors to the stream that writes them)
+        rays = _out_tensor("surface_rays: out[0]", o_rays, (n, 8), torch.float32, tri.device)
+        samples = _out_tensor("surface_rays: out[1]", o_samples, (n, 4), torch.int32, tri.device)
+        pn = _out_tensor("surface_rays: out[2]", o_pn, (n, 8), torch.float32, tri.device)
+    ptr = lambda x: C.c_void_p(x.data_ptr() or None)
+    _check(lib().gnxr_surface_rays_device(scene._h, int(width), int(height), ptr(tri), ptr(bary), ptr(px), ptr(py), ptr(s), n, _abi.BAKE_FLIP_NORMALS if flip else 0,
+                                          int(medium), ptr(rays), ptr(samples), ptr(pn), C.c_void_p(hstream or None)))
+    return rays, samples, pn
+
+
+def bake_dilate(img, iterations, out=None, stream=None):
+    """Gutter dilation of a lightmap on the GPU (gnxr_bake_dilate_device; the definition: include/gnxr.h): `img` is a contiguous float32
+    (H, W, 4) tensor whose alpha is coverage.  Each of `iterations` passes gives every texel that is not filled yet and has filled
+    8-neighbours the mean of their rgb; alpha is never changed.  Returns the dilated tensor: `out` when given, which may be `img` (in
+    place).  Queued on `stream` (by default torch's current stream); the call does not wait for the GPU."""
+    import torch
+    if not (isinstance(img, torch.Tensor) and img.is_cuda and img.dtype == torch.float32 and img.dim() == 3 and img.shape[-1] == 4 and img.is_contiguous()):
+        raise ValueError(f"bake_dilate: img must be a contiguous float32 (H, W, 4) tensor on a GPU, got "
+                         f"{type(img).__name__} {getattr(img, 'dtype', None)} {tuple(getattr(img, 'shape', ()))} on {getattr(img, 'device', None)}")
+    H, W = img.shape[0], img.shape[1]
+    if H < 1 or W < 1:
+        raise ValueError(f"bake_dilate: invalid image size {W} x {H}")
+    iterations = int(iterations)
+    if iterations < 0:
+        raise ValueError(f"bake_dilate: iterations must be >= 0, got {iterations}")
+    hstream, tstream = _stream_pair(stream, img.device)
+    with torch.cuda.stream(tstream):
+        out = _out_tensor("bake_dilate: out", out, tuple(img.shape), torch.float32, img.device)
+        if out.data_ptr() != img.data_ptr():
+            out.copy_(img)
+    _check(lib().gnxr_bake_dilate_device(W, H, iterations, C.c_void_p(out.data_ptr() or None), C.c_void_p(hstream or None)))
     return out
 
 

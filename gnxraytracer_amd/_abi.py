@@ -157,6 +157,12 @@ class FilmFilter(C.Structure):   # gnxr_film_filter (carries struct_size): table
     _fields_ = [("struct_size", i32), ("kind", i32), ("radius_x", f32), ("radius_y", f32), ("a", f32), ("b", f32), ("table", C.POINTER(f32))]
 
 
+class BakeParams(C.Structure):   # gnxr_bake_params (carries struct_size: not in gnxr_abi_sizeof's list)
+    _fields_ = [("struct_size", i32), ("flags", u32), ("dilate", i32), ("medium", i32)]
+
+
+BAKE_FLIP_NORMALS = 1   # flags of gnxr_surface_rays_device / gnxr_bake_params
+
 # kind of gnxr_film_filter / flags of gnxr_render_filtered_device
 FILTER_BOX, FILTER_TRIANGLE, FILTER_GAUSSIAN, FILTER_MITCHELL, FILTER_TABLE = range(5)
 FILM_CONTINUE = 1
@@ -212,6 +218,10 @@ PROTOTYPES = {
     "gnxr_film_add_device": (C.c_int, [P(FilmFilter), i32, i32, i32, i32, VP, VP, VP, VP]),   # width, height, views, layers; L, offsets, accum: device; hipStream_t
     "gnxr_film_resolve_device": (C.c_int, [i32, i32, i32, VP, VP, VP]),   # width, height, views; accum, image: device; hipStream_t
     "gnxr_render_filtered_device": (C.c_int, [VP, P(RenderParams), P(FilmFilter), P(Camera), P(i32), i32, VP, VP, u32, VP, P(Stats)]),   # cameras, media: host; image, accum: device; flags
+    "gnxr_bake_texels_device": (C.c_int, [VP, VP, i32, i32, VP, VP, VP]),   # scene; lightmap uvs: device; width, height; tri, bary: device; hipStream_t
+    "gnxr_surface_rays_device": (C.c_int, [VP, i32, i32, VP, VP, VP, VP, VP, i64, u32, i32, VP, VP, VP, VP]),   # scene, width, height; tri, bary, px, py, s; n, flags, medium; rays, samples, pn; hipStream_t
+    "gnxr_bake_dilate_device": (C.c_int, [i32, i32, i32, VP, VP]),   # width, height, iterations; image: device; hipStream_t
+    "gnxr_bake_lightmap_device": (C.c_int, [VP, P(RenderParams), P(BakeParams), VP, VP, VP, P(Stats)]),   # lightmap uvs, image: device; hipStream_t
     "gnxr_material_albedo": (C.c_int, [P(Material), P(f32)]),
     "gnxr_camera_rays_device": (C.c_int, [P(Camera), i32, i32, i32, VP, VP, VP, i64, VP, VP, VP]),   # device addresses + hipStream_t
     "gnxr_bsdf_device": (C.c_int, [VP, VP, VP, VP, VP, i64, i32, VP, VP]),   # device addresses + hipStream_t

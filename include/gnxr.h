@@ -958,6 +958,80 @@ int gnxr_render_filtered_device(gnxr_scene *scene, const gnxr_render_params *par
                                 const int32_t *camera_media, int32_t n_views, void *d_rgba_out, float *d_accum, uint32_t flags, void *hip_stream,
                                 gnxr_stats *stats);
 
+/* -- Lightmap baking: texture-space irradiance through Li, on device memory ----------------------------------------------------
+ * A bake computes the light that arrives at the scene's triangles into a uv atlas (a lightmap) instead of a camera image.  It is
+ * the texture-space front end of gnxr_li_device: gnxr_bake_texels_device rasterises the atlas, gnxr_surface_rays_device turns
+ * (triangle, barycentrics, pixel, sample) into the rays and sample records gnxr_li_device takes, gnxr_bake_dilate_device fills the
+ * gutters, and gnxr_bake_lightmap_device is the three of them around Li with an ordered reduction.  Everything is defined here
+ * operation by operation in fp32 (single operations in the written order, no fused multiply-add, IEEE division and square root), so
+ * that a restatement reproduces it bit for bit.  All arrays are device memory of one device that holds a copy of the scene (for
+ * gnxr_bake_dilate_device: of one device); the work is queued on hip_stream after what the caller queued there, and scratch comes
+ * from the stream-ordered allocator.  Triangles are named by their authoring index; spheres cannot be baked.
+ *
+ * Atlas rasterisation.  d_tri_lm_uv holds n_triangles * 6 floats, (u0 v0 u1 v1 u2 v2) per triangle in authoring order: a lightmap
+ * uv set of the caller's (not the scene's tri_uv).  With E(a, b, c) = (b.u - a.u) * (c.v - a.v) - (b.v - a.v) * (c.u - a.u):
+ *   area = E(p0, p1, p2);  a triangle with area == 0, a non-finite area or a non-finite uv covers nothing
+ *   texel (x, y), row 0 at v near 0, has the centre P = (cu, cv) = (((float)x + 0.5f) / (float)W, ((float)y + 0.5f) / (float)H)
+ *   wa = E(p1, p2, P), wb = E(p2, p0, P), wc = E(p0, p1, P)
+ *   P is covered when min(u) <= cu <= max(u) and min(v) <= cv <= max(v) over the three corners (fp32 comparisons; implied by the
+ *   edge tests in exact arithmetic, stated so that the result never depends on which texels an implementation visits), and
+ *   wa, wb, wc are all >= 0 (area > 0) or all <= 0 (area < 0): both windings bake, edges are inclusive
+ * d_texel_tri[x + y*W] is the LOWEST index among the triangles that cover the centre, -1 where none does; d_texel_bary (may be
+ * NULL) holds (b1, b2) = (wb / area, wc / area) of that triangle, (0, 0) where the texel is empty (b0 = wa / area = 1 - b1 - b2 up
+ * to rounding is not stored).  uv outside [0, 1]^2 is simply outside the atlas.  The result does not depend on launch order.
+ * d_tri_lm_uv and d_texel_tri 4-byte aligned, d_texel_bary 8-byte aligned; at most 2^30 texels.  Does not wait for the GPU.
+ *
+ * Surface rays.  For record i -- triangle d_tri[i], barycentrics (b1, b2) = d_bary[2i .. 2i+1], pixel (d_px[i], d_py[i]) and
+ * sample d_s[i] of a HaltonSampler over [0, width) x [0, height) --
+ *   p0, p1, p2 = the scene's CURRENT world-space vertices of the triangle (a bake after gnxr_scene_update_vertices or
+ *   gnxr_scene_set_geometry sees the edit);  b0 = 1.f - b1 - b2
+ *   p = b0*p0 + b1*p1 + b2*p2,  pError = gamma(7) * (|b0*p0| + |b1*p1| + |b2*p2|) per component,  n = Normalize(Cross(p0 - p2, p1 - p2)):
+ *   the values Triangle::Intersect gives a hit with these barycentrics (gnxr_hit.n before any flip by shading normals); n is
+ *   negated when flags has GNXR_BAKE_FLIP_NORMALS
+ *   (u0, u1) = dimensions 3 and 4 of that Halton sample (gnxr_sample_halton): the pLens pair, which Li never draws and a pinhole
+ *   camera skips, so the direction is decorrelated from everything Li draws from dimension 5 on
+ *   w = CosineSampleHemisphere(u0, u1) (core/Sampling.h:140-145);  CoordinateSystem(n, &s, &t) (core/Geometry.h:988-995)
+ *   d = (s * w.x + t * w.y) + n * w.z per component;  o = OffsetRayOrigin(p, pError, n, d) (core/Geometry.h:1408-1422)
+ * d_rays[i] = (o, tmax = +inf, d, _pad = 0), d_samples[i] = {px, py, s, medium}: the two arrays gnxr_li_device takes; d_pn (may be
+ * NULL) receives (p, 0, n, 0), 8 floats per record, n as flipped.  A degenerate triangle (zero world-space area) gets a zeroed ray,
+ * sample and d_pn record and is no error.  A triangle outside [0, n_triangles), a pixel outside the image or s < 0 gets zeroed
+ * records too; the other records are finished and the call returns GNXR_ERR_INVALID naming the first such record (the contract of
+ * gnxr_camera_rays_device: the call waits for its own kernel).  d_rays, d_samples, d_pn 16-byte aligned, d_bary 8, the int arrays 4.
+ * medium in [-1, n_media).  n == 0 is a no-op.  The call takes its turn with renders and edits on the copy of the scene it runs on.
+ *
+ * Dilation.  d_rgba is a width*height*4 fp32 image whose alpha is coverage; a texel starts out filled when alpha > 0.  Each of
+ * `iterations` passes reads the previous pass's image and fill flags only: a texel that is not filled and has at least one filled
+ * 8-neighbour inside the image takes rgb = (sum of the filled neighbours' rgb, added from 0 in (dy, dx) ascending order, dy
+ * outermost) / (float)count and becomes filled.  Alpha is never changed, so a dilated texel stays distinguishable from a baked
+ * one.  In place; d_rgba 16-byte aligned; iterations == 0 is a no-op.  Does not wait for the GPU.
+ *
+ * The bake.  params is the gnxr_render_params of Li: width, height = the atlas, spp = samples per texel; max_depth, rr_threshold,
+ * the integrator and the strategies mean what they mean for gnxr_li_device; spp_begin, spp_end and shard_index must be 0,
+ * shard_count and shard_rows 0 or 1.  For every covered texel (x, y) of the rasterisation and s in [0, spp), L_s is the Li of
+ * gnxr_li_device along the surface ray of (tri, bary, px = x, py = y, s) with bake->flags and bake->medium; the texel is
+ *   rgb = ((0 + L_0 + L_1 + ...) / (float)spp) * pi   (pi = 3.14159265358979323846f; sums in sample order, as Render sums),  alpha = 1
+ * an empty texel is (0, 0, 0, 0), and bake->dilate dilation passes follow.  The result is the incident irradiance on the side n
+ * points to; a triangle's own emission is not added.  A texel on a degenerate triangle receives L_s = 0.  The call runs in
+ * sub-batches of samples through the front end of gnxr_li_device: samples_per_pass is the number of paths per sub-batch and per
+ * sub-pass of Li (0 = auto), scratch for rays, sample records and L is bounded by a sub-batch, and the output depends on neither.
+ * Locking, stream ordering, the choice of the device and stats (sums over the sub-batches; camera_samples = covered texels * spp)
+ * follow gnxr_li_device, and the call returns when the lightmap is written.  GNXR_ERR_UNSUPPORTED: what gnxr_li_device refuses
+ * (Whitted, DirectLighting or VolPath on a scene with image textures; spp beyond the 32-bit Halton indices).  GNXR_ERR_INVALID,
+ * before anything is queued (the output stays untouched): null arguments, arrays that are not device memory, on a device without
+ * a copy of the scene, on different devices or misaligned (d_rgba_out: 16 bytes), width or height < 1 or more than 2^30 texels,
+ * invalid params, dilate < 0, unknown flag bits, medium outside [-1, n_media), struct_size != sizeof(gnxr_bake_params).
+ * gnxr_bake_params carries struct_size, like gnxr_geometry; it is not part of gnxr_abi_sizeof's list.                            */
+#define GNXR_BAKE_FLIP_NORMALS 1u   /* flags of gnxr_surface_rays_device and gnxr_bake_params: bake the back side */
+typedef struct gnxr_bake_params { int32_t struct_size; uint32_t flags; int32_t dilate, medium; } gnxr_bake_params;
+int gnxr_bake_texels_device(gnxr_scene *scene, const float *d_tri_lm_uv, int32_t width, int32_t height, int32_t *d_texel_tri, float *d_texel_bary,
+                            void *hip_stream);
+int gnxr_surface_rays_device(gnxr_scene *scene, int32_t width, int32_t height, const int32_t *d_tri, const float *d_bary, const int32_t *d_px,
+                             const int32_t *d_py, const int32_t *d_s, int64_t n, uint32_t flags, int32_t medium, gnxr_ray *d_rays,
+                             gnxr_li_sample *d_samples, float *d_pn, void *hip_stream);
+int gnxr_bake_dilate_device(int32_t width, int32_t height, int32_t iterations, float *d_rgba, void *hip_stream);
+int gnxr_bake_lightmap_device(gnxr_scene *scene, const gnxr_render_params *params, const gnxr_bake_params *bake, const float *d_tri_lm_uv,
+                              void *d_rgba_out, void *hip_stream, gnxr_stats *stats);
+
 /* -- Shading queries on device memory: the pieces an integrator is made of, batched -------------------------------------
  * Same conventions as the device calls of the Aggregate seam: every array is device memory of one device that holds a copy of the
  * scene, the work is queued on hip_stream (NULL: the null stream) after what the caller queued there, scratch comes from the
