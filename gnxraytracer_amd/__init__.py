@@ -1366,6 +1366,40 @@ class PathIntegrator:
                                                C.c_void_p(hstream or None), C.byref(st)))
         return out, stats_dict(st)
 
+    def BakeLightProbes(self, scene, positions, spp, width=None, height=None, medium=-1, out=None, stream=None, **kw):
+        """Light probes of the scene (gnxr_bake_lightprobes_device; the definition, operation by operation: include/gnxr.h): the radiance
+        that arrives at `positions` -- a contiguous float32 (n_probes, 3) tensor on the scene's device --, projected on the nine real
+        spherical harmonics of bands 0 to 2.  Per probe: 4 pi times the mean over `spp` samples of this integrator's Li along uniformly
+        distributed rays (lightprobe_rays and Li) times the basis (sh_project).  (width, height) is the virtual grid of pixels whose
+        Halton sequences the probes use, probe k being pixel (k % width, k // width); by default width = min(n_probes, 1024) and
+        height = ceil(n_probes / width).  `medium` is the medium the rays start in.  Returns (float32 tensor [n_probes, 9, 4] -- `out`
+        when given --, stats dict with camera_samples = n_probes * spp): slot j = (r, g, b, 0), what sh_irradiance takes.  The live
+        scene is read: a bake after an edit sees it.  Runs on `stream` (by default torch's current stream) and returns once the
+        coefficients are written.  Keyword arguments: samples_per_pass (paths per sub-batch), passes_in_flight."""
+        import torch
+        scene._device_tensor("BakeLightProbes: positions", positions, torch.float32, 3)
+        n = positions.shape[0]
+        if width is None:
+            width = max(1, min(n, 1024))
+        width = int(width)
+        if height is None:
+            height = max(1, -(-n // width)) if width > 0 else 0
+        height = int(height)
+        if width <= 0 or height <= 0 or width * height < n:
+            raise ValueError(f"BakeLightProbes: the {width} x {height} grid of pixels does not hold {n} probes")
+        unknown = [k for k in kw if k not in ("samples_per_pass", "passes_in_flight")]
+        if unknown:
+            raise ValueError(f"BakeLightProbes: unexpected arguments {unknown} (samples_per_pass, passes_in_flight)")
+        hstream, tstream = _stream_pair(stream, positions.device)
+        with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensor to the stream that writes it)
+            out = _out_tensor("BakeLightProbes: out", out, (n, 9, 4), torch.float32, positions.device)
+        p = self.params(width, height, spp, **kw)
+        pp = _abi.LightprobeParams(C.sizeof(_abi.LightprobeParams), 0, int(medium))
+        st = Stats()
+        _check(lib().gnxr_bake_lightprobes_device(scene._h, C.byref(p), C.byref(pp), C.c_void_p(positions.data_ptr() or None), n, C.c_void_p(out.data_ptr() or None),
+                                                  C.c_void_p(hstream or None), C.byref(st)))
+        return out, stats_dict(st)
+
     def Render(self, scene, width, height, spp, **kw):
         """Integrator::Render: returns (float32 image [H, W, 4], stats dict)."""
         p = self.params(width, height, spp, **kw)
@@ -1696,6 +1730,94 @@ def bake_dilate(img, iterations, out=None, stream=None):
         if out.data_ptr() != img.data_ptr():
             out.copy_(img)
     _check(lib().gnxr_bake_dilate_device(W, H, iterations, C.c_void_p(out.data_ptr() or None), C.c_void_p(hstream or None)))
+    return out
+
+
+def _gpu_tensor(what, x, dtype, tail, device=None):
+    """an argument of the light-probe calls that take no scene: a contiguous `dtype` tensor (n, *tail) on a GPU (on `device` when given)"""
+    import torch
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and (device is None or x.device == device) and x.dtype == dtype and x.dim() == 1 + len(tail) and
+            tuple(x.shape[1:]) == tuple(tail) and x.is_contiguous()):
+        raise ValueError(f"{what}: expected a contiguous {dtype} (n{''.join(', %d' % c for c in tail)}) tensor on {device or 'a GPU'}, got "
+                         f"{type(x).__name__} {getattr(x, 'dtype', None)} {tuple(getattr(x, 'shape', ()))} on {getattr(x, 'device', None)}")
+    return x
+
+
+def lightprobe_rays(scene, pos, px, py, s, width, height, medium=-1, out=None, stream=None):
+    """Rays from points in free space on the GPU (gnxr_lightprobe_rays_device), the sibling of surface_rays: record i starts at pos[i] and
+    takes sample s[i] of pixel (px[i], py[i]) of a HaltonSampler over (width, height).  pos: a contiguous float32 (n, 3) tensor, px, py,
+    s: int32 (n,), all on the scene's device.  Returns (rays [n, 8] float32 in the gnxr_ray layout, samples [n, 4] int32 = px, py, s,
+    medium): directions are uniform over the sphere, drawn from Halton dimensions 3 and 4; the two arrays are what integrator.Li takes.
+    `out`: a (rays, samples) pair to write into.  A non-finite position, a pixel outside the image or s < 0 raises GnxrError after the
+    others are finished, its rows are 0.  Queued on `stream` (by default torch's current stream)."""
+    import torch
+    scene._device_tensor("lightprobe_rays: pos", pos, torch.float32, 3)
+    n = pos.shape[0]
+    for what, x in (("px", px), ("py", py), ("s", s)):
+        scene._device_tensor(f"lightprobe_rays: {what}", x, torch.int32, 0)
+        if x.shape[0] != n:
+            raise ValueError(f"lightprobe_rays: {what} has {x.shape[0]} entries for {n} positions")
+    width, height = int(width), int(height)
+    if width <= 0 or height <= 0:
+        raise ValueError(f"lightprobe_rays: invalid image size {width} x {height}")
+    hstream, tstream = _stream_pair(stream, pos.device)
+    o_rays, o_samples = out if out is not None else (None, None)
+    with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensors to the stream that writes them)
+        rays = _out_tensor("lightprobe_rays: out[0]", o_rays, (n, 8), torch.float32, pos.device)
+        samples = _out_tensor("lightprobe_rays: out[1]", o_samples, (n, 4), torch.int32, pos.device)
+    ptr = lambda x: C.c_void_p(x.data_ptr() or None)
+    _check(lib().gnxr_lightprobe_rays_device(scene._h, width, height, ptr(pos), ptr(px), ptr(py), ptr(s), n, int(medium), ptr(rays), ptr(samples), C.c_void_p(hstream or None)))
+    return rays, samples
+
+
+def sh_project(rays, L, n_probes, out=None, accumulate=False, stream=None):
+    """Projects radiance samples on the nine real spherical harmonics of bands 0 to 2 on the GPU (gnxr_sh_project_device; the basis and the
+    order of the sum: include/gnxr.h).  `rays` (n, 8) float32 in the gnxr_ray layout -- only the directions are read -- and `L` (n, 4)
+    float32 are contiguous tensors on one GPU in probe-major order: n = n_probes * n_samples, row k * n_samples + s is sample s of probe k.
+    Returns the float32 (n_probes, 9, 4) tensor of sums, slot j = (sum r, sum g, sum b, 0) of L * Y_j: `out` when given.  With
+    `accumulate` the sums continue from what `out` holds: the samples of a probe may then come in several calls, whole blocks of 64 in
+    every call but the last.  Queued on `stream` (by default torch's current stream); the call does not wait for the GPU."""
+    import torch
+    _gpu_tensor("sh_project: rays", rays, torch.float32, (8,))
+    _gpu_tensor("sh_project: L", L, torch.float32, (4,), rays.device)
+    n_probes = int(n_probes)
+    n = rays.shape[0]
+    if L.shape[0] != n:
+        raise ValueError(f"sh_project: L has {L.shape[0]} rows for {n} rays")
+    if n_probes < 0 or (n_probes == 0 and n != 0) or (n_probes > 0 and n % n_probes != 0):
+        raise ValueError(f"sh_project: {n} records are no whole number of samples for each of {n_probes} probes")
+    if accumulate and out is None:
+        raise ValueError("sh_project: accumulate continues the sums of an earlier call: pass its tensor as out")
+    hstream, tstream = _stream_pair(stream, rays.device)
+    with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensor to the stream that writes it)
+        out = _out_tensor("sh_project: out", out, (n_probes, 9, 4), torch.float32, rays.device)
+    if n_probes == 0:
+        return out
+    ptr = lambda x: C.c_void_p(x.data_ptr() or None)
+    _check(lib().gnxr_sh_project_device(ptr(rays), ptr(L), n_probes, n // n_probes, ptr(out), _abi.SH_CONTINUE if accumulate else 0, C.c_void_p(hstream or None)))
+    return out
+
+
+def sh_irradiance(sh, probe, normals, out=None, stream=None):
+    """Irradiance from light probes on the GPU (gnxr_sh_irradiance_device; the definition: include/gnxr.h): `sh` is a contiguous float32
+    (n_probes, 9, 4) tensor of coefficients (BakeLightProbes), `probe` an int32 (n,) tensor of probe indices and `normals` a float32
+    (n, 3) tensor of unit normals, all on one GPU.  Returns the float32 (n, 4) tensor (E r, E g, E b, 1) of the irradiance that probe
+    probe[i] gives a surface facing normals[i]: `out` when given.  A probe index out of range raises GnxrError after the others are
+    finished, its row is 0.  Queued on `stream` (by default torch's current stream)."""
+    import torch
+    _gpu_tensor("sh_irradiance: sh", sh, torch.float32, (9, 4))
+    _gpu_tensor("sh_irradiance: probe", probe, torch.int32, (), sh.device)
+    _gpu_tensor("sh_irradiance: normals", normals, torch.float32, (3,), sh.device)
+    n = probe.shape[0]
+    if normals.shape[0] != n:
+        raise ValueError(f"sh_irradiance: normals has {normals.shape[0]} rows for {n} probe indices")
+    hstream, tstream = _stream_pair(stream, sh.device)
+    with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensor to the stream that writes it)
+        out = _out_tensor("sh_irradiance: out", out, (n, 4), torch.float32, sh.device)
+    if n == 0:
+        return out
+    ptr = lambda x: C.c_void_p(x.data_ptr() or None)
+    _check(lib().gnxr_sh_irradiance_device(ptr(sh), sh.shape[0], ptr(probe), ptr(normals), n, ptr(out), C.c_void_p(hstream or None)))
     return out
 
 

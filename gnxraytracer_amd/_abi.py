@@ -163,6 +163,13 @@ class BakeParams(C.Structure):   # gnxr_bake_params (carries struct_size: not in
 
 BAKE_FLIP_NORMALS = 1   # flags of gnxr_surface_rays_device / gnxr_bake_params
 
+
+class LightprobeParams(C.Structure):   # gnxr_lightprobe_params (carries struct_size: not in gnxr_abi_sizeof's list)
+    _fields_ = [("struct_size", i32), ("flags", u32), ("medium", i32)]
+
+
+SH_CONTINUE = 1   # flags of gnxr_sh_project_device
+
 # kind of gnxr_film_filter / flags of gnxr_render_filtered_device
 FILTER_BOX, FILTER_TRIANGLE, FILTER_GAUSSIAN, FILTER_MITCHELL, FILTER_TABLE = range(5)
 FILM_CONTINUE = 1
@@ -222,6 +229,10 @@ PROTOTYPES = {
     "gnxr_surface_rays_device": (C.c_int, [VP, i32, i32, VP, VP, VP, VP, VP, i64, u32, i32, VP, VP, VP, VP]),   # scene, width, height; tri, bary, px, py, s; n, flags, medium; rays, samples, pn; hipStream_t
     "gnxr_bake_dilate_device": (C.c_int, [i32, i32, i32, VP, VP]),   # width, height, iterations; image: device; hipStream_t
     "gnxr_bake_lightmap_device": (C.c_int, [VP, P(RenderParams), P(BakeParams), VP, VP, VP, P(Stats)]),   # lightmap uvs, image: device; hipStream_t
+    "gnxr_lightprobe_rays_device": (C.c_int, [VP, i32, i32, VP, VP, VP, VP, i64, i32, VP, VP, VP]),   # scene, width, height; pos, px, py, s; n, medium; rays, samples; hipStream_t
+    "gnxr_sh_project_device": (C.c_int, [VP, VP, i32, i64, VP, u32, VP]),   # rays, L: device; n_probes, n_samples; sums: device; flags; hipStream_t
+    "gnxr_bake_lightprobes_device": (C.c_int, [VP, P(RenderParams), P(LightprobeParams), VP, i32, VP, VP, P(Stats)]),   # positions; n_probes; coefficients: device; hipStream_t
+    "gnxr_sh_irradiance_device": (C.c_int, [VP, i32, VP, VP, i64, VP, VP]),   # coefficients; n_probes; probe, normals; n; E: device; hipStream_t
     "gnxr_material_albedo": (C.c_int, [P(Material), P(f32)]),
     "gnxr_camera_rays_device": (C.c_int, [P(Camera), i32, i32, i32, VP, VP, VP, i64, VP, VP, VP]),   # device addresses + hipStream_t
     "gnxr_bsdf_device": (C.c_int, [VP, VP, VP, VP, VP, i64, i32, VP, VP]),   # device addresses + hipStream_t

@@ -33,6 +33,7 @@
 #include "denoise_kernel.hip.h"
 #include "film_kernel.hip.h"
 #include "bake_kernel.hip.h"
+#include "lightprobe_kernel.hip.h"
 #include "kernel_instances.h"
 
 using namespace gnxr;
@@ -320,6 +321,7 @@ int gnxr_trace_any(gnxr_scene *s, const gnxr_ray *rays, int64_t n, uint8_t *occl
 #include "api_denoise.hip.h"
 #include "api_film.hip.h"
 #include "api_bake.hip.h"
+#include "api_lightprobe.hip.h"
 
 extern "C" {
 

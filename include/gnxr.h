@@ -1032,6 +1032,83 @@ int gnxr_bake_dilate_device(int32_t width, int32_t height, int32_t iterations, f
 int gnxr_bake_lightmap_device(gnxr_scene *scene, const gnxr_render_params *params, const gnxr_bake_params *bake, const float *d_tri_lm_uv,
                               void *d_rgba_out, void *hip_stream, gnxr_stats *stats);
 
+/* -- Light probes: L2 spherical-harmonic radiance at points in free space, on device memory ---------------------------------------
+ * The other half of baked lighting: what a lightmap is for static, unwrapped surfaces a light probe is for everything that moves
+ * through the scene.  A probe holds the incident radiance at a point, projected on the nine real spherical harmonics of bands 0
+ * to 2, and gives the irradiance for any normal.  gnxr_lightprobe_rays_device turns (position, pixel, sample) into the rays and
+ * sample records gnxr_li_device takes, gnxr_sh_project_device reduces (direction, L) pairs to coefficient sums in a defined order,
+ * gnxr_sh_irradiance_device evaluates, and gnxr_bake_lightprobes_device is the first two around Li.  The conventions are those of
+ * the lightmap section: single fp32 operations in the written order, no fused multiply-add, IEEE division and square root, sinf
+ * and cosf the library's (gnxr_eval_libm); device memory of one device, work queued on hip_stream, scratch from the stream-ordered
+ * allocator.
+ *
+ * The basis.  For a direction (x, y, z), slot j of a probe belongs to
+ *   Y_0 = 0.282095f            Y_1 = 0.488603f*y           Y_2 = 0.488603f*z                          Y_3 = 0.488603f*x
+ *   Y_4 = 1.092548f*(x*y)      Y_5 = 1.092548f*(y*z)       Y_6 = 0.315392f*((3.f*(z*z)) - 1.f)       Y_7 = 1.092548f*(x*z)
+ *   Y_8 = 0.546274f*((x*x) - (y*y))
+ * A probe is 9 float4, slot j = (r, g, b, 0).
+ *
+ * Probe rays.  For record i -- position d_pos[3i .. 3i+2], pixel (d_px[i], d_py[i]) and sample d_s[i] of a HaltonSampler over
+ * [0, width) x [0, height) --
+ *   (u0, u1) = dimensions 3 and 4 of that Halton sample (gnxr_sample_halton): the pLens pair, as for surface rays
+ *   d = UniformSampleSphere(u0, u1) (core/Sampling.cpp:72-77):  z = 1.f - 2.f*u0,  r = sqrt(max(0.f, 1.f - z*z)),
+ *   phi = (2.f*Pi)*u1 (Pi = 3.14159265358979323846f),  d = (r*cosf(phi), r*sinf(phi), z)
+ * d_rays[i] = (o = the position, tmax = +inf, d, _pad = 0), d_samples[i] = {px, py, s, medium}.  A record with a non-finite
+ * position, a pixel outside the image or s < 0 gets a zeroed ray and sample; the other records are finished and the call returns
+ * GNXR_ERR_INVALID naming the first such record (the contract of gnxr_camera_rays_device: the call waits for its own kernel).
+ * d_rays and d_samples 16-byte aligned, the others 4.  The scene gives the sampler tables and the range of medium, [-1, n_media).
+ * n == 0 is a no-op.
+ *
+ * Projection.  d_rays (only d is read) and d_L (float4 per record, w ignored) hold n_probes * n_samples records in PROBE-MAJOR
+ * order: record k*n_samples + s is sample s of probe k.  The term of sample s in slot j and channel c is L_s.c * Y_j(d_s).  The
+ * sum is defined for a wave of 64 lanes:
+ *   samples are cut into blocks of 64 consecutive samples; in block b, lane l holds the term of sample 64*b + l, or +0.0f when
+ *   that sample is past n_samples
+ *   for m = 32, 16, 8, 4, 2, 1 in this order every lane replaces its value by v[l] + v[l ^ m]; the block sum is lane 0's value
+ *   (fp32 addition is commutative: every lane ends with the same bits)
+ *   sum = (...((start + block_0) + block_1) + ...), in increasing block order; start = 0.0f, or what d_sh_sum holds when flags
+ *   has GNXR_SH_CONTINUE
+ * d_sh_sum[9k + j] = (sum_r, sum_g, sum_b, 0).  A caller who continues -- the samples of a probe spread over several calls --
+ * passes whole blocks (n_samples a multiple of 64) in every call but the last: then the calls give the bits of one call over all
+ * samples.  n_samples == 0 leaves start (0 without the flag).  All three arrays 16-byte aligned and on one device, which the
+ * call runs on (no scene).  n_probes == 0 is a no-op.  Does not wait for the GPU.
+ *
+ * The bake.  params is the gnxr_render_params of Li: spp = samples per probe; width x height is a virtual grid of pixels whose
+ * Halton sequences the probes use, and must hold n_probes pixels: probe k is pixel (k % width, k / width).  max_depth,
+ * rr_threshold, the integrator and the strategies mean what they mean for gnxr_li_device; spp_begin, spp_end and shard_index must
+ * be 0, shard_count and shard_rows 0 or 1.  For probe k at d_positions[3k .. 3k+2] and s in [0, spp), L_s is the Li of
+ * gnxr_li_device along the probe ray of (position, px, py, s) with probe_params->medium, and
+ *   d_sh_out[9k + j].rgb = (sum * 12.566370614359172f) / (float)spp,  w = 0,  sum = the projection's sum over all spp samples
+ * (12.566370614359172f = 4 pi = 1 / the density of the directions).  A probe with a non-finite position gets zeros.  The call
+ * runs in sub-batches -- ranges of probes, or ranges of whole blocks of one probe's samples -- through the front end of
+ * gnxr_li_device: samples_per_pass is the number of paths per sub-batch (at least one block) and per sub-pass of Li (0 = auto),
+ * scratch for rays, sample records and L is bounded by a sub-batch, and the output depends on neither: block sums are added one
+ * after another however the samples are cut.  Locking, stream ordering, the choice of the device and stats (sums over the
+ * sub-batches; camera_samples = n_probes * spp) follow gnxr_bake_lightmap_device, and the call returns when the coefficients are
+ * written.  GNXR_ERR_UNSUPPORTED: what gnxr_li_device refuses.  GNXR_ERR_INVALID, before anything is queued (the output stays
+ * untouched): null arguments, arrays that are not device memory, on a device without a copy of the scene, on different devices
+ * or misaligned (d_positions: 4 bytes, d_sh_out: 16), n_probes < 0 or more than 2^27, a grid with fewer than n_probes pixels,
+ * invalid params, flag bits (none is defined), medium outside [-1, n_media), struct_size != sizeof(gnxr_lightprobe_params).
+ * n_probes == 0 is a no-op.  gnxr_lightprobe_params carries struct_size; it is not part of gnxr_abi_sizeof's list.
+ *
+ * Evaluation.  For record i with probe k = d_probe[i], coefficients c_j = d_sh[9k + j] and normal n = d_normals[3i .. 3i+2] (unit
+ * length is the caller's business), per channel c
+ *   E.c = ((((A0*(c_0.c*Y_0) + A1*(c_1.c*Y_1)) + A1*(c_2.c*Y_2)) + A1*(c_3.c*Y_3)) + A2*(c_4.c*Y_4)) + ... + A2*(c_8.c*Y_8)
+ * left to right, Y_j = Y_j(n), A0 = 3.14159265f, A1 = 2.09439510f, A2 = 0.78539816f (the cosine lobe's band factors), and
+ * d_E[i] = (E.r, E.g, E.b, 1).  A probe index outside [0, n_probes) gives a zeroed record; the others are finished and the call
+ * returns GNXR_ERR_INVALID naming the first such record (it waits for its own kernel).  d_sh and d_E 16-byte aligned, d_probe and
+ * d_normals 4; all on one device, which the call runs on (no scene).  n == 0 is a no-op.                                        */
+#define GNXR_SH_CONTINUE 1u   /* flags of gnxr_sh_project_device: add to what d_sh_sum holds */
+typedef struct gnxr_lightprobe_params { int32_t struct_size; uint32_t flags; int32_t medium; } gnxr_lightprobe_params;
+int gnxr_lightprobe_rays_device(gnxr_scene *scene, int32_t width, int32_t height, const float *d_pos, const int32_t *d_px, const int32_t *d_py,
+                                const int32_t *d_s, int64_t n, int32_t medium, gnxr_ray *d_rays, gnxr_li_sample *d_samples, void *hip_stream);
+int gnxr_sh_project_device(const gnxr_ray *d_rays, const float *d_L, int32_t n_probes, int64_t n_samples, float *d_sh_sum, uint32_t flags,
+                           void *hip_stream);
+int gnxr_bake_lightprobes_device(gnxr_scene *scene, const gnxr_render_params *params, const gnxr_lightprobe_params *probe_params,
+                                 const float *d_positions, int32_t n_probes, void *d_sh_out, void *hip_stream, gnxr_stats *stats);
+int gnxr_sh_irradiance_device(const float *d_sh, int32_t n_probes, const int32_t *d_probe, const float *d_normals, int64_t n, float *d_E,
+                              void *hip_stream);
+
 /* -- Shading queries on device memory: the pieces an integrator is made of, batched -------------------------------------
  * Same conventions as the device calls of the Aggregate seam: every array is device memory of one device that holds a copy of the
  * scene, the work is queued on hip_stream (NULL: the null stream) after what the caller queued there, scratch comes from the
