@@ -17,6 +17,8 @@ What each fixture pins:
   light_*.npz    DiffuseAreaLight / InfiniteAreaLight / SkyBoxLight Sample_Li / Pdf_Li / Le
   render_*.npz   images + ray counts of the restated Render/Li loop running on the reference's classes
   texture_filter.npz + tex_filter_*.hdr   ImageTexture::Evaluate / MIPMap::Lookup over filters x wrap modes x shapes x footprints
+  bsdf_grid_*.npz   BSDF::f / Pdf / Sample_f across the materials' parameter space (scenes.MATERIAL_GRID), aimed probes
+  light_delta.npz   PointLight / SpotLight / DistantLight Sample_Li / Pdf_Li across cone shapes and transforms, probes on the cone edges
   reference_assets.npz + *.xz / *.bz2   the reference's Resources/ inputs of tests/test_reference_assets.py and its answers on them
 """
 import os
@@ -236,6 +238,8 @@ def main():
     ortho_goldens()
     hlbvh_goldens()
     texture_filter_goldens()
+    material_grid_goldens()
+    light_delta_goldens()
     # cfg 2 at full size: the counts the survey recorded from the COMPLETE reference
     img, cnt = render(cornell_path, 256, 256, 64)
     checksum = float(img[..., :3].astype(np.float64).sum())
@@ -471,6 +475,54 @@ def texture_filter_goldens():
     print("texture_filter.npz", os.path.getsize(os.path.join(G, "texture_filter.npz")), "bytes")
 
 
+# ---------------------------------------------------------------- 20: the material grid and the delta-light grid
+def same_bits(a, b):
+    return (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))
+
+
+def material_grid_goldens():
+    """BSDF::f / Pdf / Sample_f of the compiled reference on scenes.MATERIAL_GRID: one quad per point of the materials' parameter space,
+    scenes.MATERIAL_GRID_PROBES aimed probes each (scenes.material_grid_probes: grazing incidence, wi on the mirror and the refraction
+    axis, the edges of u), under the flag sets of scenes.MATERIAL_GRID_FLAGS.  One file per group of material families
+    (scenes.MATERIAL_GRID_FILES), inputs stored beside the 16 output columns."""
+    b = scenes.material_grid()
+    path = scene_file(b, "material_grid")
+    parts = [scenes.material_grid_probes(i, scenes.MATERIAL_GRID_PROBES, scenes.MATERIAL_GRID_SEED) for i in range(len(scenes.MATERIAL_GRID))]
+    rays, wi, u = (np.ascontiguousarray(np.concatenate([p[k] for p in parts])) for k in range(3))
+    material = np.repeat(np.arange(len(parts)), scenes.MATERIAL_GRID_PROBES).astype(np.int32)
+    blob = rays.tobytes() + wi.tobytes() + u.tobytes()
+    osc = ol.OracleScene(b)
+    outs = {}
+    for flags in scenes.MATERIAL_GRID_FLAGS:
+        r = np.frombuffer(ol.run_ref(path, "bsdf", blob, [flags]), np.float32).reshape(-1, 16).copy()
+        same = same_bits(osc.bsdf_probe(rays, wi, u, flags), r)
+        print("material grid flags", flags, "valid", int((r[:, 13] == 1).sum()), "of", len(r), "oracle identical rows", int(same.all(1).sum()))
+        outs[f"out_{flags}"] = r
+    for fname, families in scenes.MATERIAL_GRID_FILES.items():
+        sel = np.array([scenes.MATERIAL_GRID[m]["family"] in families for m in material])
+        save(fname, rays=rays[sel], wi=wi[sel], u=u[sel], material=material[sel], **{k: v[sel] for k, v in outs.items()})
+        print(fname, os.path.getsize(os.path.join(G, fname)), "bytes")
+
+
+def light_delta_goldens():
+    """PointLight / SpotLight / DistantLight::Sample_Li and Pdf_Li of the compiled reference on scenes.delta_grid(): the 12 columns of the
+    `light` command for scenes.DELTA_GRID_PROBES reference points per light, aimed at the cone edges (scenes.delta_grid_probes).  out[k]
+    belongs to light first + k of the scene; refN, u and wiQ are the same for every light."""
+    b, first = scenes.delta_grid()
+    path = scene_file(b, "delta_grid")
+    osc = ol.OracleScene(b)
+    refP, out = [], []
+    for k, l in enumerate(scenes.DELTA_GRID):
+        p, n, u, wq = scenes.delta_grid_probes(k, scenes.DELTA_GRID_PROBES, 1)
+        r = np.frombuffer(ol.run_ref(path, "light", p.tobytes() + n.tobytes() + u.tobytes() + wq.tobytes(), [first + k]), np.float32).reshape(-1, 12).copy()
+        keep = [c for c in range(12) if c != 8]
+        same = same_bits(osc.light_probe(first + k, p, n, u, wq)[:, keep], r[:, keep])
+        print("light_delta", l["name"], "Li > 0 on", int((r[:, :3] > 0).any(1).sum()), "of", len(r), "oracle identical rows (without column 8)", int(same.all(1).sum()))
+        refP.append(p); out.append(r)
+    save("light_delta.npz", refP=np.stack(refP), refN=n, u=u, wiQ=wq, out=np.stack(out), first_light=np.int32(first))
+    print("light_delta.npz", os.path.getsize(os.path.join(G, "light_delta.npz")), "bytes")
+
+
 # ---------------------------------------------------------------- 18: the reference's Resources/ inputs (tests/test_reference_assets.py)
 def sha256_bits(a):
     import hashlib
@@ -581,5 +633,8 @@ if __name__ == "__main__":
         hlbvh_goldens()
     elif sys.argv[1:] == ["texture_filter"]:   # only section 19
         texture_filter_goldens()
+    elif sys.argv[1:] == ["material_grid"]:    # only section 20
+        material_grid_goldens()
+        light_delta_goldens()
     else:
         main()

@@ -261,6 +261,46 @@ def test_env_and_skybox_reference_goldens(gpu):
     assert (le.cpu().numpy() == 0).all()
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("flags", scenes.MATERIAL_GRID_FLAGS)
+def test_bsdf_material_grid_goldens(gpu, flags):
+    """The materials' parameter space (scenes.MATERIAL_GRID: every branch of compile_material) under aimed probes -- grazing incidence, wi
+    on the mirror and the refraction axis, the edges of u --, whole records against the compiled reference.  The reference's NaN records
+    (rough transmission at eta == 1) must come back as NaN.  tests/test_material_grid.py states what the fixture must show."""
+    g = scenes.material_grid_golden()
+    want = g[f"out_{flags}"]
+    got = dbsdf(gpu.Scene(scenes.material_grid()), g["rays"], g["wi"], g["u"], flags)
+    assert got.shape == want.shape == (len(scenes.MATERIAL_GRID) * scenes.MATERIAL_GRID_PROBES, 16) and (want[:, 13] == 1).all()
+    bad = {}
+    for i, name in enumerate(scenes.MATERIAL_GRID_NAMES):
+        s = g["material"] == i
+        if not biteq(got[s], want[s]):
+            bad[name] = mismatch(got[s], want[s])
+    assert not bad, (flags, bad)
+
+
+@pytest.mark.gpu
+def test_delta_light_grid_goldens(gpu):
+    """Point, spot and distant lights across cone shapes and transforms (scenes.DELTA_GRID), reference points on the cone edges and on the
+    light itself, under the uniform strategy.  Column 8 (the selection pdf) is not produced by the reference; P1 (columns 9 to 11) is
+    compared where the reference's pdf is > 0, as for the environment lights."""
+    g = golden("light_delta.npz")
+    b, first = scenes.delta_grid()
+    scene = gpu.Scene(b)
+    assert int(g["first_light"]) == first and len(g["out"]) == len(scenes.DELTA_GRID)
+    bad = {}
+    for k, l in enumerate(scenes.DELTA_GRID):
+        r = g["out"][k]
+        o = dlight(scene, first + k, g["refP"][k], g["refN"], g["u"], g["wiQ"], gpu._abi.LIGHTS_UNIFORM)
+        pdf_pos = r[:, 3] > 0
+        assert o.shape == r.shape and pdf_pos.mean() > 0.9
+        if not biteq(o[:, :8], r[:, :8]):
+            bad[l["name"]] = mismatch(o[:, :8], r[:, :8])
+        elif not biteq(o[pdf_pos, 9:], r[pdf_pos, 9:]):
+            bad[l["name"]] = "P1: " + mismatch(o[pdf_pos, 9:], r[pdf_pos, 9:])
+    assert not bad, bad
+
+
 # ---------------------------------------------------------------- GPU: against the oracle, where no golden exists
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", ["glass_sphere", "textured", "smooth"])
