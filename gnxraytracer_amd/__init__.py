@@ -333,6 +333,8 @@ class Scene:
         self.n_vertices = int(d.n_vertices)
         self.n_lights = int(d.n_lights)   # (set_lights keeps it current)
         self.device = _device
+        self.camera = Camera()   # a copy of the scene's own camera record (set_camera keeps it current)
+        C.memmove(C.byref(self.camera), C.byref(d.camera), C.sizeof(Camera))
         self._env_light = None   # a copy of the INFINITE light's record (update_environment keeps it current)
         for i in range(int(d.n_lights)):
             if d.lights[i].type == _abi.LIGHT_INFINITE:
@@ -833,6 +835,7 @@ class Scene:
         """The camera of SceneBuilder.set_camera (and the medium it sits in, -1 == none) for later renders."""
         cam = camera(eye, look, up, fov, lens_radius, focal_distance, orthographic)
         _check(lib().gnxr_scene_set_camera(self._h, C.byref(cam), int(medium)))
+        self.camera = cam
 
     # Aggregate seam: Scene::Intersect / IntersectP, batched
     def bvh(self):
@@ -988,6 +991,54 @@ class Scene:
         n, out, st, _ = self._query_args("light_le", [("rays", rays, torch.float32, 8)], out, 3, stream)
         _check(lib().gnxr_light_le_device(self._h, int(light), C.c_void_p(rays.data_ptr() or None), n, C.c_void_p(out.data_ptr() or None), C.c_void_p(st or None)))
         return out
+
+    MOTION_CHANNELS = ("motion", "guide", "prim")
+
+    def motion(self, width, height, prev_cameras, cameras=None, prev_vertices=None, out=None, stream=None):
+        """A pixel-centre G-buffer and where each pixel's surface point was one frame ago (gnxr_motion_device; the definition, operation
+        by operation: include/gnxr.h).  `prev_cameras`: the gnxr Camera records (camera()) of the previous frame, one per view -- a single
+        record will do for one view.  `cameras`: this frame's records, or None for the scene's own camera, which also drops the leading
+        V.  `prev_vertices`: None (nothing but the camera moved), or a contiguous float32 (n_vertices, 3) tensor on the scene's device:
+        the vertex array the scene held one frame ago, in update_vertices' layout.  Returns a dict of torch tensors on the scene's
+        device: "motion" (V, H, W, 4) float32 = (x', y', t', flag) -- the raster position on the previous frame's film, the distance
+        the previous frame's guide holds there if it saw the same point, 1 when both are usable --, "guide" (V, H, W, 4) float32 =
+        (n.x, n.y, n.z, t) of the hit through the pixel centre and "prim" (V, H, W) int32 = its primitive, -1 on a miss.  `out`: a dict
+        with preallocated tensors for some or all of them.  Runs on `stream` (by default torch's current stream) and returns once the
+        buffers are written.  Malformed arguments raise ValueError."""
+        import torch
+        if isinstance(prev_cameras, Camera):
+            prev_cameras = [prev_cameras]
+        if prev_cameras is None:
+            raise ValueError("motion: prev_cameras is required (the cameras of the previous frame)")
+        prev_cameras, _, _, _ = _view_args("motion: prev_cameras", prev_cameras, None, width, height)
+        cameras, _, width, height = _view_args("motion", cameras, None, width, height)
+        V = len(cameras) if cameras is not None else 1
+        if len(prev_cameras) != V:
+            raise ValueError(f"motion: {len(prev_cameras)} previous cameras for {V} view{'s' if V != 1 else ''}")
+        if prev_vertices is not None:
+            self._device_tensor("motion: prev_vertices", prev_vertices, torch.float32, 3)
+            if prev_vertices.shape[0] != self.n_vertices:
+                raise ValueError(f"motion: prev_vertices has {prev_vertices.shape[0]} rows, the scene has {self.n_vertices} vertices")
+        out = dict(out) if out is not None else {}
+        extra = [c for c in out if c not in self.MOTION_CHANNELS]
+        if extra:
+            raise ValueError(f"motion: out holds {extra}; the channels are {self.MOTION_CHANNELS}")
+        device = torch.device("cuda", self.device)
+        lead = (V,) if cameras is not None else ()
+        hstream, tstream = _stream_pair(stream, device)
+        res = {}
+        with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensors to the stream that writes them)
+            for c in self.MOTION_CHANNELS:
+                res[c] = _out_tensor(f"motion: out[{c!r}]", out.get(c), lead + (height, width) + (() if c == "prim" else (4,)), torch.int32 if c == "prim" else torch.float32, device)
+        if V == 0:
+            return res
+        ptr = lambda x: C.c_void_p(x.data_ptr() or None)
+        p = _abi.MotionParams(C.sizeof(_abi.MotionParams), width, height, V)
+        bufs = _abi.MotionBuffers(C.sizeof(_abi.MotionBuffers), 0, ptr(res["motion"]), ptr(res["guide"]), ptr(res["prim"]))
+        cams = (Camera * V)(*cameras) if cameras else None
+        prev = (Camera * V)(*prev_cameras)
+        _check(lib().gnxr_motion_device(self._h, C.byref(p), cams, prev, ptr(prev_vertices) if prev_vertices is not None else None, C.byref(bufs), C.c_void_p(hstream or None)))
+        return res
 
 
 RayHits = collections.namedtuple("RayHits", "hits prim t bary n")
@@ -1819,6 +1870,149 @@ def sh_irradiance(sh, probe, normals, out=None, stream=None):
     ptr = lambda x: C.c_void_p(x.data_ptr() or None)
     _check(lib().gnxr_sh_irradiance_device(ptr(sh), sh.shape[0], ptr(probe), ptr(normals), n, ptr(out), C.c_void_p(hstream or None)))
     return out
+
+
+def camera_matrices(camera, width, height):
+    """gnxr_camera_matrices (host, needs no GPU): {"r2c", "c2w", "w2r"} as (4, 4) float32 arrays -- RasterToCamera and CameraToWorld as every
+    kernel's camera record holds them for `camera` (camera()) over a (width, height) film, and WorldToRaster, the product of the forward
+    matrices they are made of: the single definition of the matrix Scene.motion projects with."""
+    if not isinstance(camera, Camera):
+        raise ValueError(f"camera_matrices: camera must be a gnxr Camera record (camera(...)), got {type(camera).__name__}")
+    m = {k: np.zeros((4, 4), dtype=np.float32) for k in ("r2c", "c2w", "w2r")}
+    fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+    _check(lib().gnxr_camera_matrices(C.byref(camera), int(width), int(height), fp(m["r2c"]), fp(m["c2w"]), fp(m["w2r"])))
+    return m
+
+
+def temporal_accumulate(color, motion, guide, prim, history=None, max_history=32, depth_tol=0.05, normal_cos=0.9, out=None, stream=None):
+    """Blends a frame into its reprojected history on the GPU (gnxr_temporal_accumulate_device; the definition, operation by operation:
+    include/gnxr.h).  `color`: this frame's image, a contiguous float32 tensor (H, W, 4) or (V, H, W, 4) on a GPU; `motion`, `guide`
+    (color's shape) and `prim` (int32, color's shape without the 4): this frame's channels of Scene.motion.  `history`: None (the first
+    frame, or after a reset) or the dict an earlier call returned.  A history tap counts when it shows the same primitive at the expected
+    depth (within depth_tol, relative) under a similar normal (cosine at least normal_cos); the history length stops at max_history, so
+    that an old frame's weight decays.  Returns the next history, a dict {"color": the accumulated image, "stat": (m1, m2, N, var) per
+    pixel -- the moments of the luminance, the history length, the variance --, "guide": guide, "prim": prim}.  `out`: a dict with
+    preallocated "color" and / or "stat" tensors, which may overlap no input.  After set_geometry, set_lights or a material edit the
+    caller starts over with history=None.  Queued on `stream` (by default torch's current stream); the call does not wait for the GPU.
+    Malformed arguments raise ValueError."""
+    import math
+    import torch
+    if not (isinstance(color, torch.Tensor) and color.is_cuda and color.dtype == torch.float32 and color.dim() in (3, 4) and color.shape[-1] == 4 and color.is_contiguous()):
+        raise ValueError(f"temporal_accumulate: color must be a contiguous float32 (H, W, 4) or (V, H, W, 4) tensor on a GPU, got "
+                         f"{type(color).__name__} {getattr(color, 'dtype', None)} {tuple(getattr(color, 'shape', ()))} on {getattr(color, 'device', None)}")
+    shape = tuple(color.shape)
+
+    def layout(what, x, prim_like):
+        want, dtype = (shape[:-1], torch.int32) if prim_like else (shape, torch.float32)
+        if not (isinstance(x, torch.Tensor) and x.device == color.device and x.dtype == dtype and tuple(x.shape) == want and x.is_contiguous()):
+            raise ValueError(f"temporal_accumulate: {what} must be a contiguous {dtype} tensor of shape {want} on {color.device}, got "
+                             f"{type(x).__name__} {getattr(x, 'dtype', None)} {tuple(getattr(x, 'shape', ()))} on {getattr(x, 'device', None)}")
+        return x
+
+    layout("motion", motion, False); layout("guide", guide, False); layout("prim", prim, True)
+    if history is not None:
+        if not isinstance(history, dict) or sorted(history) != ["color", "guide", "prim", "stat"]:
+            raise ValueError("temporal_accumulate: history must be None or a dict with 'color', 'stat', 'guide' and 'prim' (what an earlier call returned)")
+        for k in ("color", "stat", "guide", "prim"):
+            layout(f"history[{k!r}]", history[k], k == "prim")
+    H, W = shape[-3], shape[-2]
+    V = shape[0] if len(shape) == 4 else 1
+    if H < 1 or W < 1:
+        raise ValueError(f"temporal_accumulate: invalid image size {W} x {H}")
+    max_history, depth_tol, normal_cos = int(max_history), float(depth_tol), float(normal_cos)
+    if max_history < 1:
+        raise ValueError(f"temporal_accumulate: max_history must be at least 1, got {max_history}")
+    if math.isnan(depth_tol) or depth_tol < 0 or math.isnan(normal_cos):
+        raise ValueError(f"temporal_accumulate: depth_tol must be a number >= 0 and normal_cos a number, got {depth_tol} and {normal_cos}")
+    out = dict(out) if out is not None else {}
+    extra = [k for k in out if k not in ("color", "stat")]
+    if extra:
+        raise ValueError(f"temporal_accumulate: out holds {extra}; the outputs are 'color' and 'stat'")
+    hstream, tstream = _stream_pair(stream, color.device)
+    with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensors to the stream that writes them)
+        o_color = _out_tensor("temporal_accumulate: out['color']", out.get("color"), shape, torch.float32, color.device)
+        o_stat = _out_tensor("temporal_accumulate: out['stat']", out.get("stat"), shape, torch.float32, color.device)
+    res = {"color": o_color, "stat": o_stat, "guide": guide, "prim": prim}
+    if V == 0:
+        return res
+    ptr = lambda x: C.c_void_p(x.data_ptr() or None)
+    h = history or {}
+    hptr = lambda k: ptr(h[k]) if h else None
+    p = _abi.TemporalParams(C.sizeof(_abi.TemporalParams), W, H, V, max_history, depth_tol, normal_cos)
+    bufs = _abi.TemporalBuffers(C.sizeof(_abi.TemporalBuffers), 0, ptr(color), ptr(motion), ptr(guide), ptr(prim), hptr("color"), hptr("stat"), hptr("guide"), hptr("prim"),
+                                ptr(o_color), ptr(o_stat))
+    _check(lib().gnxr_temporal_accumulate_device(C.byref(p), C.byref(bufs), C.c_void_p(hstream or None)))
+    return res
+
+
+_denoise = denoise   # (TemporalAccumulator.frame has an argument of that name)
+
+
+class TemporalAccumulator:
+    """A frame loop with history: renders a low-spp frame, finds where every pixel was one frame ago and blends the frame into what the
+    earlier frames left there -- the composition integrator.RenderDevice -> Scene.motion -> temporal_accumulate (-> denoise), nothing
+    more: its result equals that chain of public calls on bits.
+
+        acc = TemporalAccumulator(PathIntegrator(5), scene, 1920, 1080, spp=4)
+        for cam in orbit:
+            frame = acc.frame(cam, denoise=True)      # frame["denoised"], frame["color"], frame["stat"][..., 2] = history length
+
+    Frame k renders the samples [(k mod max_history) * spp, + spp) of a sampler with samplesPerPixel = max_history * spp (spp_begin /
+    spp_end), so consecutive frames are independent estimates, and multiplies the rgb of that share by (float)max_history: the frame's own
+    estimate.  The other keyword arguments are temporal_accumulate's (depth_tol, normal_cos).  The accumulator detects no edit: after
+    Scene.set_geometry, set_lights or a material edit the caller calls reset(); moved vertices are handed to frame() as prev_vertices."""
+
+    def __init__(self, integrator, scene, width, height, spp, max_history=32, **accumulate_kw):
+        width, height, spp, max_history = int(width), int(height), int(spp), int(max_history)
+        if width <= 0 or height <= 0:
+            raise ValueError(f"TemporalAccumulator: invalid image size {width} x {height}")
+        if spp < 1 or max_history < 1:
+            raise ValueError(f"TemporalAccumulator: spp and max_history must be at least 1, got {spp} and {max_history}")
+        unknown = [k for k in accumulate_kw if k not in ("depth_tol", "normal_cos")]
+        if unknown:
+            raise ValueError(f"TemporalAccumulator: unexpected arguments {unknown} (depth_tol, normal_cos)")
+        self.integrator, self.scene, self.width, self.height, self.spp, self.max_history = integrator, scene, width, height, spp, max_history
+        self.accumulate_kw = dict(accumulate_kw)
+        self.reset()
+
+    def reset(self):
+        """Forget the history: the next frame starts from its own samples alone."""
+        self.history = None
+        self.prev_camera = None
+        self.k = 0
+
+    def frame(self, camera=None, prev_vertices=None, denoise=False, stream=None):
+        """One frame.  `camera`: None keeps the scene's camera; a gnxr Camera record (camera()) is set with Scene.set_camera first (outside
+        any medium).  `prev_vertices`: what Scene.motion takes, when vertices moved since the last frame.  `denoise`: also pass the
+        accumulated colour through denoise() as a single share, guided by this frame's normals and depths.  Returns the history dict of
+        temporal_accumulate ("color", "stat", "guide", "prim") with "motion" added, and "denoised" with denoise=True.  Runs on `stream`
+        (by default torch's current stream)."""
+        import torch
+        scene, W, H, M = self.scene, self.width, self.height, self.max_history
+        if camera is not None:
+            if not isinstance(camera, Camera):
+                raise ValueError(f"TemporalAccumulator.frame: camera must be a gnxr Camera record (camera(...)), got {type(camera).__name__}")
+            scene.set_camera(tuple(camera.eye), tuple(camera.look), tuple(camera.up), camera.fov_deg, camera.lens_radius, camera.focal_distance, bool(camera.orthographic))
+        cam = Camera()
+        C.memmove(C.byref(cam), C.byref(scene.camera), C.sizeof(Camera))
+        device = torch.device("cuda", scene.device)
+        hstream, tstream = _stream_pair(stream, device)
+        with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensor to the stream that writes it)
+            img = torch.zeros((H, W, 4), dtype=torch.float32, device=device)
+        lo = (self.k % M) * self.spp
+        self.integrator.RenderDevice(scene, img.data_ptr(), W, H, M * self.spp, stream=hstream, spp_begin=lo, spp_end=lo + self.spp)
+        with torch.cuda.stream(tstream):
+            img[..., :3] *= float(M)
+        mo = scene.motion(W, H, self.prev_camera if self.prev_camera is not None else cam, prev_vertices=prev_vertices, stream=tstream)
+        res = temporal_accumulate(img, mo["motion"], mo["guide"], mo["prim"], history=self.history, max_history=M, stream=tstream, **self.accumulate_kw)
+        self.history, self.prev_camera = res, cam
+        self.k += 1
+        res = dict(res, motion=mo["motion"])
+        if denoise:
+            with torch.cuda.stream(tstream):
+                depth = mo["guide"][..., 3].contiguous()
+            res["denoised"] = _denoise(res["color"], normal=mo["guide"], depth=depth, stream=tstream)
+        return res
 
 
 def save_png(path, rgba8):

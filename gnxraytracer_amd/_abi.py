@@ -170,6 +170,25 @@ class LightprobeParams(C.Structure):   # gnxr_lightprobe_params (carries struct_
 
 SH_CONTINUE = 1   # flags of gnxr_sh_project_device
 
+
+class MotionParams(C.Structure):   # gnxr_motion_params (carries struct_size: not in gnxr_abi_sizeof's list)
+    _fields_ = [("struct_size", i32), ("width", i32), ("height", i32), ("n_views", i32)]
+
+
+class MotionBuffers(C.Structure):   # gnxr_motion_buffers (carries struct_size): device addresses, NULL = channel not wanted
+    _fields_ = [("struct_size", i32), ("_pad", i32), ("d_motion", C.c_void_p), ("d_guide", C.c_void_p), ("d_prim", C.c_void_p)]
+
+
+class TemporalParams(C.Structure):   # gnxr_temporal_params (carries struct_size)
+    _fields_ = [("struct_size", i32), ("width", i32), ("height", i32), ("n_views", i32), ("max_history", i32), ("depth_tol", f32), ("normal_cos", f32)]
+
+
+class TemporalBuffers(C.Structure):   # gnxr_temporal_buffers (carries struct_size): device addresses; the history is all set or all NULL
+    _fields_ = [("struct_size", i32), ("_pad", i32), ("d_color", C.c_void_p), ("d_motion", C.c_void_p), ("d_guide", C.c_void_p), ("d_prim", C.c_void_p),
+                ("d_hist_color", C.c_void_p), ("d_hist_stat", C.c_void_p), ("d_hist_guide", C.c_void_p), ("d_hist_prim", C.c_void_p),
+                ("d_out_color", C.c_void_p), ("d_out_stat", C.c_void_p)]
+
+
 # kind of gnxr_film_filter / flags of gnxr_render_filtered_device
 FILTER_BOX, FILTER_TRIANGLE, FILTER_GAUSSIAN, FILTER_MITCHELL, FILTER_TABLE = range(5)
 FILM_CONTINUE = 1
@@ -233,6 +252,9 @@ PROTOTYPES = {
     "gnxr_sh_project_device": (C.c_int, [VP, VP, i32, i64, VP, u32, VP]),   # rays, L: device; n_probes, n_samples; sums: device; flags; hipStream_t
     "gnxr_bake_lightprobes_device": (C.c_int, [VP, P(RenderParams), P(LightprobeParams), VP, i32, VP, VP, P(Stats)]),   # positions; n_probes; coefficients: device; hipStream_t
     "gnxr_sh_irradiance_device": (C.c_int, [VP, i32, VP, VP, i64, VP, VP]),   # coefficients; n_probes; probe, normals; n; E: device; hipStream_t
+    "gnxr_camera_matrices": (C.c_int, [P(Camera), i32, i32, P(f32), P(f32), P(f32)]),   # host: r2c, c2w, w2r (16 floats each, any may be NULL)
+    "gnxr_motion_device": (C.c_int, [VP, P(MotionParams), P(Camera), P(Camera), VP, P(MotionBuffers), VP]),   # cameras, previous cameras: host; previous vertices: device; hipStream_t
+    "gnxr_temporal_accumulate_device": (C.c_int, [P(TemporalParams), P(TemporalBuffers), VP]),   # buffers: device; hipStream_t
     "gnxr_material_albedo": (C.c_int, [P(Material), P(f32)]),
     "gnxr_camera_rays_device": (C.c_int, [P(Camera), i32, i32, i32, VP, VP, VP, i64, VP, VP, VP]),   # device addresses + hipStream_t
     "gnxr_bsdf_device": (C.c_int, [VP, VP, VP, VP, VP, i64, i32, VP, VP]),   # device addresses + hipStream_t

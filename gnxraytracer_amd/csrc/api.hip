@@ -34,6 +34,7 @@
 #include "film_kernel.hip.h"
 #include "bake_kernel.hip.h"
 #include "lightprobe_kernel.hip.h"
+#include "temporal_kernel.hip.h"
 #include "kernel_instances.h"
 
 using namespace gnxr;
@@ -322,6 +323,7 @@ int gnxr_trace_any(gnxr_scene *s, const gnxr_ray *rays, int64_t n, uint8_t *occl
 #include "api_film.hip.h"
 #include "api_bake.hip.h"
 #include "api_lightprobe.hip.h"
+#include "api_temporal.hip.h"
 
 extern "C" {
 

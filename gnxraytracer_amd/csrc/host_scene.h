@@ -163,6 +163,7 @@ void env_power_from_top_levels(int rx, int ry, int first_level, const std::vecto
 // without padding.  *n_texels receives the texels of all levels.  false (error set) for a size <= 0, an unknown wrap or more than 16 levels
 bool compile_texture(const gnxr_texture &t, int index, int64_t first_texel, DTexture *out, int64_t *n_texels);
 DCamera make_camera(const gnxr_camera &c, int W, int H, int medium);      // camera/Perspective.cpp:114-135, core/Camera.h:54-75
+void camera_world_to_raster(const gnxr_camera &c, int W, int H, float w2r[16]);   // (s2r * c2s) * lookat of make_camera's factors
 DHalton make_halton(int W, int H);                                          // samplers/HaltonSampler.cpp:33-60
 // light-selection table: dense restatement of core/LightDistribution.cpp (uniform / power / spatial)
 void build_light_grid(const CompiledScene &cs, int strategy, DLightGrid *grid, std::vector<float> *table, bool layout_only = false);

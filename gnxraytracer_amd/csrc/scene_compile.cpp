@@ -553,11 +553,10 @@ float host_radical_inverse(const CompiledScene &cs, int baseIndex, uint64_t a) {
 }
 
 // ------------------------------------------------------------------ camera / halton
-DCamera make_camera(const gnxr_camera &c, int W, int H, int medium) {
-    DCamera d;
-    memset(&d, 0, sizeof(d));
+// the three transforms a camera over a W x H film is made of: WorldToCamera (lookat), CameraToScreen, ScreenToRaster
+struct CameraXf { Xf lookat, c2s, s2r; };
+static CameraXf camera_transforms(const gnxr_camera &c, int W, int H) {
     Xf lookat = look_at(Vec3(c.eye[0], c.eye[1], c.eye[2]), Vec3(c.look[0], c.look[1], c.look[2]), Vec3(c.up[0], c.up[1], c.up[2]));
-    Mat4 c2w = lookat.inv;  // Camera2WorldStart = Inverse(lookat), RenderThread.cpp:65
     float frame = (float)W / (float)H;
     float sxmin, sxmax, symin, symax;
     if (frame > 1.f) { sxmin = -frame; sxmax = frame; symin = -1.f; symax = 1.f; }
@@ -570,7 +569,15 @@ DCamera make_camera(const gnxr_camera &c, int W, int H, int medium) {
     // (Orthographic.h:18, Transform.cpp:282-285)
     Xf c2s = c.orthographic ? xmul(scale(1, 1, 1 / (10.f - 0.f)), translate(Vec3(0, 0, -0.f))) : perspective(c.fov_deg, 1e-2f, 1000.f);
     Xf s2r = xmul(xmul(scale((float)W, (float)H, 1), scale(1 / (sxmax - sxmin), 1 / (symin - symax), 1)), translate(Vec3(-sxmin, -symax, 0)));
-    Xf r2c = xmul(xinverse(c2s), xinverse(s2r));
+    return {lookat, c2s, s2r};
+}
+
+DCamera make_camera(const gnxr_camera &c, int W, int H, int medium) {
+    DCamera d;
+    memset(&d, 0, sizeof(d));
+    const CameraXf x = camera_transforms(c, W, H);
+    Mat4 c2w = x.lookat.inv;  // Camera2WorldStart = Inverse(lookat), RenderThread.cpp:65
+    Xf r2c = xmul(xinverse(x.c2s), xinverse(x.s2r));
     memcpy(d.r2c, r2c.m.m, 64);
     memcpy(d.c2w, c2w.m, 64);
     d.lens_radius = c.lens_radius;
@@ -578,6 +585,13 @@ DCamera make_camera(const gnxr_camera &c, int W, int H, int medium) {
     d.medium = medium;
     d.ortho = c.orthographic ? 1 : 0;
     return d;
+}
+
+// WorldToRaster = (ScreenToRaster * CameraToScreen) * WorldToCamera: the forward matrices of make_camera's factors (gnxr_camera_matrices)
+void camera_world_to_raster(const gnxr_camera &c, int W, int H, float w2r[16]) {
+    const CameraXf x = camera_transforms(c, W, H);
+    const Xf m = xmul(xmul(x.s2r, x.c2s), x.lookat);
+    memcpy(w2r, m.m.m, 64);
 }
 
 static int64_t mod64(int64_t a, int64_t b) { int64_t r = a - (a / b) * b; return r < 0 ? r + b : r; }
@@ -1619,5 +1633,15 @@ void light_grid_probes(const CompiledScene &cs, float *ri /* [5][128] */) {
 extern "C" int gnxr_material_albedo(const gnxr_material *m, float rgb[3]) {
     if (!m || !rgb) { gnxr::set_error("null argument"); return GNXR_ERR_INVALID; }
     if (!gnxr::material_albedo(*m, rgb)) { gnxr::set_error("unknown material type %d", m->type); return GNXR_ERR_INVALID; }
+    return GNXR_OK;
+}
+
+extern "C" int gnxr_camera_matrices(const gnxr_camera *camera, int32_t width, int32_t height, float r2c[16], float c2w[16], float w2r[16]) {
+    if (!camera) { gnxr::set_error("camera matrices: null camera"); return GNXR_ERR_INVALID; }
+    if (width < 1 || height < 1) { gnxr::set_error("camera matrices: invalid image size %d x %d", width, height); return GNXR_ERR_INVALID; }
+    const gnxr::DCamera d = gnxr::make_camera(*camera, width, height, -1);
+    if (r2c) memcpy(r2c, d.r2c, 64);
+    if (c2w) memcpy(c2w, d.c2w, 64);
+    if (w2r) gnxr::camera_world_to_raster(*camera, width, height, w2r);
     return GNXR_OK;
 }

@@ -1109,6 +1109,98 @@ int gnxr_bake_lightprobes_device(gnxr_scene *scene, const gnxr_render_params *pa
 int gnxr_sh_irradiance_device(const float *d_sh, int32_t n_probes, const int32_t *d_probe, const float *d_normals, int64_t n, float *d_E,
                               void *hip_stream);
 
+/* -- Temporal accumulation: motion vectors and reprojected frame history, on device memory ------------------------------------------
+ * What an interactive caller puts between its renderer and its spatial filter: where was this pixel's surface point on the previous
+ * frame's film (gnxr_motion_device), is the history there still the same surface, and a blend of the new frame into the history that
+ * survives the test (gnxr_temporal_accumulate_device).  Every operation is a single fp32 operation in the written order (no fused
+ * multiply-add; division and sqrt are IEEE).  lum(x) = (0.212671f*x.r + 0.715160f*x.g) + 0.072169f*x.b, the denoiser's.  Raster
+ * convention: the centre of pixel (x, y) is (x + 0.5, y + 0.5).  Image v of a buffer sits at v*width*height*stride, pixel (x, y) at
+ * x + y*width.
+ *
+ * gnxr_camera_matrices (host, needs no device).  r2c (RasterToCamera) and c2w (CameraToWorld) are the matrices every kernel's camera
+ * record holds for this camera over a width x height film; w2r is WorldToRaster = (ScreenToRaster * CameraToScreen) * WorldToCamera,
+ * the product of the FORWARD fp32 matrices of the same three transforms r2c and c2w are made of (Transform::operator*: each entry
+ * ((a0*b0 + a1*b1) + a2*b2) + a3*b3), not an inverse of r2c and c2w.  Row-major.  It is the single definition of w2r, as
+ * gnxr_material_albedo is of the albedo: the kernels and the tests take the matrix from here.  Any output pointer may be NULL.
+ * GNXR_ERR_INVALID: a null camera, width or height < 1.
+ *
+ * gnxr_motion_device: a pixel-centre G-buffer and where each pixel was one frame ago.  cameras: n_views records in host memory, or
+ * NULL with n_views == 1 for the scene's own camera; prev_cameras (host memory, n_views records, required): the cameras of the
+ * previous frame.  d_prev_vertices: NULL, or device memory of n_vertices*3 floats, the world-space vertex array the scene held one
+ * frame ago in the layout of gnxr_scene_update_vertices.  For view v and pixel (x, y):
+ *   Ray.  (o, d) by exactly the operations of the camera ray of a render for the film sample (fx, fy) = (0.5, 0.5), lens_radius
+ *     taken as 0 whatever the camera says, tmax = +inf; no sampler table is read.
+ *   Hit.  The bits of gnxr_trace_closest_device on that ray (the same front end, the same 4-wide walk; spheres included).
+ *     d_guide = (hit.n, hit.t), (0, 0, 0, 0) on a miss; d_prim = hit.prim.
+ *   Position one frame ago.  P = o + t*d per component (one multiply, one add).
+ *     triangle hit with d_prev_vertices:  P' = (b0*q0 + b1*q1) + b2*q2 per component, qi the previous position of corner i of the
+ *                                         hit triangle
+ *     sphere hit, or no d_prev_vertices:  P' = P
+ *     miss, perspective camera:           P' = E' + d, E' = (c2w'[3], c2w'[7], c2w'[11]) the previous camera's position (a direction
+ *                                         keeps its place on the film under translation)
+ *     miss, orthographic camera:          P' = o
+ *     (the kind of the miss is that of the view's camera, the kind of the expected depth below that of prev_cameras[v])
+ *   Projection.  With m = w2r of prev_cameras[v]:  xr = (m[0]*X + m[1]*Y) + (m[2]*Z + m[3]), and yr, zr, w the same from rows 1, 2
+ *     and 3.  If w == 1, (x', y') = (xr, yr); otherwise (x', y') = (xr / w, yr / w).
+ *   Expected previous depth.  Miss: t' = 0.  Perspective: e = P' - E', t' = sqrt((e.x*e.x + e.y*e.y) + e.z*e.z).  Orthographic:
+ *     t' = zr * 10.f (this undoes Orthographic(0, 10)).
+ *   d_motion = (x', y', t', 1.0f) when w > 0 and x', y', t' are all finite; otherwise (0, 0, 0, 0).
+ * Locking, stream ordering and the choice of the scene copy under gnxr_init_devices are those of gnxr_render_aov_device; scratch is
+ * one ray per pixel from the stream-ordered allocator, which also holds the hit's leaf code (and the corner -> vertex table of the
+ * refit, uploaded once per scene, when d_prev_vertices is given); the call returns when the buffers are written.  n_views == 0 is a no-op.
+ * GNXR_ERR_INVALID, before anything is queued: a null scene, params, prev_cameras or out; a struct_size other than sizeof of its
+ * record; width or height < 1, n_views < 0; all channels NULL; null cameras with n_views > 1; a channel or d_prev_vertices that is
+ * not device memory or is on a device without a copy of the scene; d_motion or d_guide not 16-byte aligned, d_prim or
+ * d_prev_vertices not 4-byte aligned; n_views*width*height beyond the limit of gnxr_render_views_device.
+ *
+ * gnxr_temporal_accumulate_device: validate, gather and blend; a pure image operation, no scene.  A stat record is (m1, m2, N, var):
+ * first and second moment of the luminance, the history length as a float, the variance.  The history of the next frame is
+ * (d_out_color, d_out_stat, this frame's d_guide, this frame's d_prim): the caller swaps.  Per pixel p = (x, y) of view v:
+ *   c = d_color[p].rgb;  out.w = d_color[p].w;  l = lum(c);  cur_ok: the three channels of c are finite.
+ *   Gather (skipped without history or when d_motion[p].w == 0).  (x', y', t') = d_motion[p].xyz.
+ *     fx = x' - 0.5f, fy = y' - 0.5f.  Snap: if |fx - rintf(fx)| <= 1/256 then fx = rintf(fx), the same for fy (a static camera and
+ *     scene are a single-tap copy, stable on bits).  Range, in float, before any conversion to int: no taps unless fx >= -1 &&
+ *     fx < (float)W && fy >= -1 && fy < (float)H (NaN, inf and 1e30 give no taps).  x0 = floorf(fx), ax = fx - x0, the same in y.
+ *     Taps in the order (i, j) = (0,0), (1,0), (0,1), (1,1), q = (x0 + i, y0 + j) inside view v (no tap crosses into another view),
+ *     b = (i ? ax : 1 - ax) * (j ? ay : 1 - ay).  A tap counts iff b > 0, q is inside the image, hist_stat[q].z > 0,
+ *     hist_prim[q] == prim[p], hist_color[q].rgb and hist_stat[q].xy are finite and, when prim[p] >= 0,
+ *     |hist_guide[q].w - t'| <= depth_tol * t' and ((n_p.x*n_q.x + n_p.y*n_q.y) + n_p.z*n_q.z) >= normal_cos (n_p = d_guide[p].xyz,
+ *     n_q = hist_guide[q].xyz; a NaN fails either comparison).  From +0, over the taps that count: sw += b; sc += b * hc per
+ *     channel; s1 += b * m1_q; s2 += b * m2_q; sN += b * N_q.  History exists iff sw > 0; then H = sc / sw, M1 = s1 / sw,
+ *     M2 = s2 / sw, N = sN / sw.
+ *   Blend.  var(m1, m2) = m2 - m1*m1, taken as 0 unless it is > 0.
+ *     history and cur_ok:   N' = min(N + 1, (float)max_history); alpha = 1 / N'; out_c = H_c + alpha * (c_c - H_c);
+ *                           m1' = M1 + alpha * (l - M1); m2' = M2 + alpha * (l*l - M2); stat (m1', m2', N', var(m1', m2'))
+ *     no history, cur_ok:   out = c, stat (l, l*l, 1, 0)
+ *     history, not cur_ok:  out = H, stat (M1, M2, N, var(M1, M2))
+ *     neither:              out.rgb = 0, stat (0, 0, 0, 0)
+ * The device is the one that holds d_color; the work is queued on hip_stream and the call returns without waiting for the GPU, as
+ * gnxr_denoise_device; no scratch.  n_views == 0 is a no-op.  GNXR_ERR_INVALID, before anything is queued: a null params, io or
+ * required pointer; a struct_size other than sizeof of its record; some but not all history pointers; width or height < 1,
+ * n_views < 0; max_history < 1; a negative or NaN depth_tol, a NaN normal_cos; a pointer that is not device memory or is on another
+ * device than d_color; a four-float buffer not 16-byte aligned, d_prim or d_hist_prim not 4-byte aligned; an output that overlaps
+ * an input or the other output (the gather reads neighbours); n_views*width*height beyond the limit of gnxr_render_views_device.
+ * A caller resets its history (passes NULL history once) after an edit that changes what a primitive id means or how surfaces
+ * shade: new geometry, new lights, new materials.  The records carry struct_size; they are not part of gnxr_abi_sizeof's list.  */
+int gnxr_camera_matrices(const gnxr_camera *camera, int32_t width, int32_t height, float r2c[16], float c2w[16], float w2r[16]);
+typedef struct gnxr_motion_params  { int32_t struct_size, width, height, n_views; } gnxr_motion_params;
+typedef struct gnxr_motion_buffers { int32_t struct_size, pad;
+    float   *d_motion;  /* V*H*W*4: (x', y', t', flag)                       */
+    float   *d_guide;   /* V*H*W*4: (n.x, n.y, n.z, t) of the centre hit     */
+    int32_t *d_prim;    /* V*H*W  : gnxr_hit.prim of the centre hit, -1 miss */
+} gnxr_motion_buffers;  /* NULL = channel not wanted; not all three NULL     */
+int gnxr_motion_device(gnxr_scene *scene, const gnxr_motion_params *params, const gnxr_camera *cameras, const gnxr_camera *prev_cameras,
+                       const float *d_prev_vertices, const gnxr_motion_buffers *out, void *hip_stream);
+typedef struct gnxr_temporal_params { int32_t struct_size, width, height, n_views, max_history;
+                                      float depth_tol, normal_cos; } gnxr_temporal_params;
+typedef struct gnxr_temporal_buffers { int32_t struct_size, pad;
+    const float *d_color;                                     /* V*H*W*4, required: this frame's image                       */
+    const float *d_motion, *d_guide; const int32_t *d_prim;   /* required: this frame's, from gnxr_motion_device             */
+    const float *d_hist_color, *d_hist_stat, *d_hist_guide; const int32_t *d_hist_prim;   /* all four, or all NULL (first frame) */
+    float *d_out_color, *d_out_stat;                          /* V*H*W*4 each, required                                      */
+} gnxr_temporal_buffers;
+int gnxr_temporal_accumulate_device(const gnxr_temporal_params *params, const gnxr_temporal_buffers *io, void *hip_stream);
+
 /* -- Shading queries on device memory: the pieces an integrator is made of, batched -------------------------------------
  * Same conventions as the device calls of the Aggregate seam: every array is device memory of one device that holds a copy of the
  * scene, the work is queued on hip_stream (NULL: the null stream) after what the caller queued there, scratch comes from the
