@@ -2015,6 +2015,180 @@ class TemporalAccumulator:
         return res
 
 
+def _display_image(name, color):
+    """`color` of the display calls, checked: (shape, V, H, W)"""
+    import torch
+    if not (isinstance(color, torch.Tensor) and color.is_cuda and color.dtype == torch.float32 and color.dim() in (3, 4) and color.shape[-1] == 4 and color.is_contiguous()):
+        raise ValueError(f"{name}: color must be a contiguous float32 (H, W, 4) or (V, H, W, 4) tensor on a GPU, got "
+                         f"{type(color).__name__} {getattr(color, 'dtype', None)} {tuple(getattr(color, 'shape', ()))} on {getattr(color, 'device', None)}")
+    shape = tuple(color.shape)
+    H, W = shape[-3], shape[-2]
+    if H < 1 or W < 1:
+        raise ValueError(f"{name}: invalid image size {W} x {H}")
+    return shape, (shape[0] if len(shape) == 4 else 1), H, W
+
+
+def _min_log2(name, min_log2):
+    min_log2 = int(min_log2)
+    if not -126 <= min_log2 <= 111:
+        raise ValueError(f"{name}: min_log2 must lie in [-126, 111], got {min_log2}")
+    return min_log2
+
+
+def luminance_histogram(color, min_log2=-12, out=None, stream=None):
+    """Log-luminance histogram of an image on the GPU (gnxr_luminance_histogram_device; the definition: include/gnxr.h).  `color`: a
+    contiguous float32 tensor (H, W, 4) or (V, H, W, 4) on a GPU.  Returns an int32 tensor (V, 260) -- `out` when given --: per view 256
+    bins, sixteen per octave over [2^min_log2, 2^(min_log2 + 16)), then the pixels below the range (zero and negative ones among them),
+    above it, not finite, and a 0.  The counts are exact: the bin comes from the bit pattern of the luminance.  Queued on `stream` (by
+    default torch's current stream); the call does not wait for the GPU.  Malformed arguments raise ValueError."""
+    import torch
+    shape, V, H, W = _display_image("luminance_histogram", color)
+    min_log2 = _min_log2("luminance_histogram", min_log2)
+    hstream, tstream = _stream_pair(stream, color.device)
+    with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensor to the stream that writes it)
+        out = _out_tensor("luminance_histogram: out", out, (V, _abi.HISTOGRAM_WORDS), torch.int32, color.device)
+    if V == 0:
+        return out
+    p = _abi.HistogramParams(C.sizeof(_abi.HistogramParams), W, H, V, min_log2)
+    _check(lib().gnxr_luminance_histogram_device(C.byref(p), C.c_void_p(color.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(hstream or None)))
+    return out
+
+
+def auto_exposure(hist, prev=None, key=0.18, low=0.5, high=0.95, rate=1.0, min_exposure=2 ** -8, max_exposure=2 ** 8, min_log2=-12, out=None, stream=None):
+    """The exposure a luminance histogram meters, adapted over time, computed on the GPU (gnxr_exposure_device; the definition, operation
+    by operation: include/gnxr.h).  `hist`: the int32 (V, 260) tensor of luminance_histogram, taken with the same min_log2.  The pixels
+    between the quantiles `low` and `high` of the in-range luminances are averaged in log2, and the target exposure puts that average on
+    `key`, clamped to [min_exposure, max_exposure].  `prev`: None, or the tensor an earlier call returned: the exposure then moves from
+    its previous value towards the target by the fraction `rate`; a black frame holds the previous value.  Returns a float32 (V, 4)
+    tensor -- `out` when given, which may be `prev` (in place) --: per view (exposure, target, the metered log2 luminance, the weight
+    it was metered from).  tonemap takes the tensor as its exposure: the value never visits the host.  Queued on `stream` (by default
+    torch's current stream); the call does not wait for the GPU.  Malformed arguments raise ValueError."""
+    import math
+    import torch
+    if not (isinstance(hist, torch.Tensor) and hist.is_cuda and hist.dtype == torch.int32 and hist.dim() == 2 and hist.shape[1] == _abi.HISTOGRAM_WORDS and hist.is_contiguous()):
+        raise ValueError(f"auto_exposure: hist must be a contiguous int32 (V, {_abi.HISTOGRAM_WORDS}) tensor on a GPU (luminance_histogram), got "
+                         f"{type(hist).__name__} {getattr(hist, 'dtype', None)} {tuple(getattr(hist, 'shape', ()))} on {getattr(hist, 'device', None)}")
+    V = hist.shape[0]
+    if prev is not None and not (isinstance(prev, torch.Tensor) and prev.device == hist.device and prev.dtype == torch.float32 and tuple(prev.shape) == (V, 4) and prev.is_contiguous()):
+        raise ValueError(f"auto_exposure: prev must be None or a contiguous float32 ({V}, 4) tensor on {hist.device}, got "
+                         f"{type(prev).__name__} {getattr(prev, 'dtype', None)} {tuple(getattr(prev, 'shape', ()))} on {getattr(prev, 'device', None)}")
+    min_log2 = _min_log2("auto_exposure", min_log2)
+    key, low, high, rate, min_exposure, max_exposure = (float(x) for x in (key, low, high, rate, min_exposure, max_exposure))
+    if not all(math.isfinite(x) for x in (key, low, high, rate, min_exposure, max_exposure)):
+        raise ValueError("auto_exposure: key, low, high, rate, min_exposure and max_exposure must be finite")
+    if not (0 <= low < high <= 1):
+        raise ValueError(f"auto_exposure: 0 <= low < high <= 1 is required, got {low} and {high}")
+    if not (key > 0 and 0 < rate <= 1 and 0 < min_exposure <= max_exposure):
+        raise ValueError(f"auto_exposure: key > 0, 0 < rate <= 1 and 0 < min_exposure <= max_exposure are required, got {key}, {rate}, {min_exposure} and {max_exposure}")
+    hstream, tstream = _stream_pair(stream, hist.device)
+    with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensor to the stream that writes it)
+        out = _out_tensor("auto_exposure: out", out, (V, 4), torch.float32, hist.device)
+    if V == 0:
+        return out
+    p = _abi.ExposureParams(C.sizeof(_abi.ExposureParams), V, min_log2, 0, key, low, high, rate, min_exposure, max_exposure)
+    _check(lib().gnxr_exposure_device(C.byref(p), C.c_void_p(hist.data_ptr()), C.c_void_p(prev.data_ptr()) if prev is not None else None, C.c_void_p(out.data_ptr()),
+                                      C.c_void_p(hstream or None)))
+    return out
+
+
+TONEMAP_CURVES = {"linear": _abi.TONEMAP_LINEAR, "reference": _abi.TONEMAP_REFERENCE, "reinhard": _abi.TONEMAP_REINHARD, "aces": _abi.TONEMAP_ACES}
+
+
+def tonemap(color, exposure=1.0, curve="aces", white=4.0, srgb=True, round=True, out=None, stream=None):
+    """From a linear float image to bytes on the GPU (gnxr_tonemap_device; the definition, operation by operation: include/gnxr.h): every
+    colour channel times the exposure, through `curve` -- "linear", "reference" (FrameBuffer's 1 - exp(-4x)), "reinhard" (extended, with
+    the white point `white`) or "aces" (Narkowicz's fit) --, clamped to [0, 1], sRGB-encoded with `srgb`, then rounded to the nearest
+    byte (`round`) or truncated, as FrameBuffer does.  `color`: a contiguous float32 tensor (H, W, 4) or (V, H, W, 4) on a GPU;
+    `exposure`: a number, or the float32 (V, 4) tensor of auto_exposure, read on the device.  Returns a uint8 tensor of color's shape
+    -- `out` when given --, alpha 255; save_png takes a view of it after .cpu().numpy().  Queued on `stream` (by default torch's current
+    stream); the call does not wait for the GPU.  Malformed arguments raise ValueError."""
+    import math
+    import torch
+    shape, V, H, W = _display_image("tonemap", color)
+    if curve not in TONEMAP_CURVES:
+        raise ValueError(f"tonemap: curve must be one of {sorted(TONEMAP_CURVES)}, got {curve!r}")
+    white = float(white)
+    if not 1e-3 <= white <= 65504:
+        raise ValueError(f"tonemap: white must lie in [1e-3, 65504], got {white}")
+    d_exposure, e = None, 1.0
+    if isinstance(exposure, torch.Tensor):
+        if not (exposure.device == color.device and exposure.dtype == torch.float32 and tuple(exposure.shape) == (V, 4) and exposure.is_contiguous()):
+            raise ValueError(f"tonemap: an exposure tensor must be a contiguous float32 ({V}, 4) tensor on {color.device} (auto_exposure), got "
+                             f"{exposure.dtype} {tuple(exposure.shape)} on {exposure.device}")
+        d_exposure = exposure
+    else:
+        try:
+            e = float(exposure)
+        except (TypeError, ValueError):
+            raise ValueError(f"tonemap: exposure must be a number or the tensor of auto_exposure, got {type(exposure).__name__}") from None
+        if not (math.isfinite(e) and e >= 0):
+            raise ValueError(f"tonemap: exposure must be finite and >= 0, got {e}")
+    hstream, tstream = _stream_pair(stream, color.device)
+    with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensor to the stream that writes it)
+        out = _out_tensor("tonemap: out", out, shape, torch.uint8, color.device)
+    if V == 0:
+        return out
+    flags = (_abi.TONEMAP_SRGB if srgb else 0) | (_abi.TONEMAP_ROUND if round else 0)
+    p = _abi.TonemapParams(C.sizeof(_abi.TonemapParams), W, H, V, TONEMAP_CURVES[curve], flags, e, white)
+    _check(lib().gnxr_tonemap_device(C.byref(p), C.c_void_p(color.data_ptr()), C.c_void_p(d_exposure.data_ptr()) if d_exposure is not None else None,
+                                     C.c_void_p(out.data_ptr()), C.c_void_p(hstream or None)))
+    return out
+
+
+class Display:
+    """The display stage of a frame loop: luminance_histogram -> auto_exposure -> tonemap, with the exposure record kept on the device
+    between frames and updated in place -- nothing more: its result equals that chain of public calls on bits, and no frame waits for
+    the GPU.
+
+        acc = TemporalAccumulator(PathIntegrator(5), scene, 1920, 1080, spp=4)
+        display = Display(1920, 1080, rate=0.1)
+        for cam in orbit:
+            shown = display.present(acc.frame(cam, denoise=True)["denoised"])      # shown["rgba8"]: (1080, 1920, 4) uint8
+
+    The keyword arguments are those of the three calls: min_log2; key, low, high, rate, min_exposure, max_exposure; curve, white, srgb,
+    round.  The first frame after the construction or a reset() takes its target exposure at once."""
+
+    _HIST, _EXPOSURE, _TONEMAP = ("min_log2",), ("key", "low", "high", "rate", "min_exposure", "max_exposure"), ("curve", "white", "srgb", "round")
+
+    def __init__(self, width, height, n_views=1, **kw):
+        width, height, n_views = int(width), int(height), int(n_views)
+        if width <= 0 or height <= 0 or n_views < 1:
+            raise ValueError(f"Display: invalid size {n_views} x {width} x {height}")
+        unknown = [k for k in kw if k not in self._HIST + self._EXPOSURE + self._TONEMAP]
+        if unknown:
+            raise ValueError(f"Display: unexpected arguments {unknown} ({', '.join(self._HIST + self._EXPOSURE + self._TONEMAP)})")
+        self.width, self.height, self.n_views = width, height, n_views
+        self.min_log2 = _min_log2("Display", kw.get("min_log2", -12))
+        self.exposure_kw = {k: kw[k] for k in self._EXPOSURE if k in kw}
+        self.tonemap_kw = {k: kw[k] for k in self._TONEMAP if k in kw}
+        self._hist = self._record = None
+        self.reset()
+
+    def reset(self):
+        """Forget the exposure: the next frame takes its target at once."""
+        self.has_exposure = False
+
+    def present(self, color, stream=None):
+        """One frame.  `color`: a contiguous float32 tensor (V, H, W, 4), or (H, W, 4) with n_views == 1, on a GPU.  Returns {"rgba8": the
+        uint8 tensor of color's shape, "exposure": the float32 (V, 4) record of auto_exposure, "hist": the int32 (V, 260) histogram};
+        "exposure" and "hist" are the Display's own tensors, which the next frame overwrites.  Runs on `stream` (by default torch's
+        current stream)."""
+        import torch
+        shape, V, H, W = _display_image("Display.present", color)
+        if (V, H, W) != (self.n_views, self.height, self.width):
+            raise ValueError(f"Display.present: color is {V} x {H} x {W}, the display {self.n_views} x {self.height} x {self.width}")
+        hstream, tstream = _stream_pair(stream, color.device)
+        if self._hist is None or self._hist.device != color.device:
+            with torch.cuda.stream(tstream):
+                self._hist = torch.empty((V, _abi.HISTOGRAM_WORDS), dtype=torch.int32, device=color.device)
+                self._record = torch.empty((V, 4), dtype=torch.float32, device=color.device)
+            self.has_exposure = False
+        hist = luminance_histogram(color, min_log2=self.min_log2, out=self._hist, stream=tstream)
+        rec = auto_exposure(hist, prev=self._record if self.has_exposure else None, min_log2=self.min_log2, out=self._record, stream=tstream, **self.exposure_kw)
+        self.has_exposure = True
+        return {"rgba8": tonemap(color, exposure=rec, stream=tstream, **self.tonemap_kw), "exposure": rec, "hist": hist}
+
+
 def save_png(path, rgba8):
     """FrameBuffer::saveToFile (ui/FrameBuffer.cpp:6-9): rgba8 is a [H, W, 4] uint8 array."""
     rgba8 = np.ascontiguousarray(rgba8, dtype=np.uint8)

@@ -189,6 +189,23 @@ class TemporalBuffers(C.Structure):   # gnxr_temporal_buffers (carries struct_si
                 ("d_out_color", C.c_void_p), ("d_out_stat", C.c_void_p)]
 
 
+class HistogramParams(C.Structure):   # gnxr_histogram_params (carries struct_size: not in gnxr_abi_sizeof's list)
+    _fields_ = [("struct_size", i32), ("width", i32), ("height", i32), ("n_views", i32), ("min_log2", i32)]
+
+
+class ExposureParams(C.Structure):   # gnxr_exposure_params (carries struct_size)
+    _fields_ = [("struct_size", i32), ("n_views", i32), ("min_log2", i32), ("_pad", i32), ("key", f32), ("low", f32), ("high", f32), ("rate", f32),
+                ("min_exposure", f32), ("max_exposure", f32)]
+
+
+class TonemapParams(C.Structure):   # gnxr_tonemap_params (carries struct_size)
+    _fields_ = [("struct_size", i32), ("width", i32), ("height", i32), ("n_views", i32), ("curve", i32), ("flags", u32), ("exposure", f32), ("white", f32)]
+
+
+HISTOGRAM_WORDS = 260   # uint32 per view of gnxr_luminance_histogram_device: 256 bins, below, above, not finite, 0
+TONEMAP_LINEAR, TONEMAP_REFERENCE, TONEMAP_REINHARD, TONEMAP_ACES = range(4)   # curve of gnxr_tonemap_params
+TONEMAP_SRGB, TONEMAP_ROUND = 1, 2   # flags of gnxr_tonemap_params
+
 # kind of gnxr_film_filter / flags of gnxr_render_filtered_device
 FILTER_BOX, FILTER_TRIANGLE, FILTER_GAUSSIAN, FILTER_MITCHELL, FILTER_TABLE = range(5)
 FILM_CONTINUE = 1
@@ -255,6 +272,9 @@ PROTOTYPES = {
     "gnxr_camera_matrices": (C.c_int, [P(Camera), i32, i32, P(f32), P(f32), P(f32)]),   # host: r2c, c2w, w2r (16 floats each, any may be NULL)
     "gnxr_motion_device": (C.c_int, [VP, P(MotionParams), P(Camera), P(Camera), VP, P(MotionBuffers), VP]),   # cameras, previous cameras: host; previous vertices: device; hipStream_t
     "gnxr_temporal_accumulate_device": (C.c_int, [P(TemporalParams), P(TemporalBuffers), VP]),   # buffers: device; hipStream_t
+    "gnxr_luminance_histogram_device": (C.c_int, [P(HistogramParams), VP, VP, VP]),   # image, histogram: device; hipStream_t
+    "gnxr_exposure_device": (C.c_int, [P(ExposureParams), VP, VP, VP, VP]),   # histogram, previous records (or NULL), records: device; hipStream_t
+    "gnxr_tonemap_device": (C.c_int, [P(TonemapParams), VP, VP, VP, VP]),   # image, exposure records (or NULL), RGBA8: device; hipStream_t
     "gnxr_material_albedo": (C.c_int, [P(Material), P(f32)]),
     "gnxr_camera_rays_device": (C.c_int, [P(Camera), i32, i32, i32, VP, VP, VP, i64, VP, VP, VP]),   # device addresses + hipStream_t
     "gnxr_bsdf_device": (C.c_int, [VP, VP, VP, VP, VP, i64, i32, VP, VP]),   # device addresses + hipStream_t

@@ -35,6 +35,7 @@
 #include "bake_kernel.hip.h"
 #include "lightprobe_kernel.hip.h"
 #include "temporal_kernel.hip.h"
+#include "display_kernel.hip.h"
 #include "kernel_instances.h"
 
 using namespace gnxr;
@@ -324,6 +325,7 @@ int gnxr_trace_any(gnxr_scene *s, const gnxr_ray *rays, int64_t n, uint8_t *occl
 #include "api_bake.hip.h"
 #include "api_lightprobe.hip.h"
 #include "api_temporal.hip.h"
+#include "api_display.hip.h"
 
 extern "C" {
 

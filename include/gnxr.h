@@ -1201,6 +1201,81 @@ typedef struct gnxr_temporal_buffers { int32_t struct_size, pad;
 } gnxr_temporal_buffers;
 int gnxr_temporal_accumulate_device(const gnxr_temporal_params *params, const gnxr_temporal_buffers *io, void *hip_stream);
 
+/* -- Display stage: auto-exposure, tone map and sRGB RGBA8, on device memory -----------------------------------------------------
+ * The last link of a frame pipeline (render -> motion -> accumulate -> denoise -> display): from a linear float RGBA image in device
+ * memory to bytes a window or a PNG takes, with an exposure that follows the scene and never leaves the device.  Three pure image
+ * operations, no scene.  Every operation is a single fp32 operation in the written order (no fused multiply-add; division is IEEE);
+ * expf and powf are the library's (gnxr_eval_libm: glibc's bits).  lum(x) = (0.212671f*x.r + 0.715160f*x.g) + 0.072169f*x.b, the
+ * denoiser's.  Image v of a buffer sits at v*width*height*stride.  gnxr_framebuffer_update (host memory, one view, the reference
+ * UI's constants) stays what it is.
+ *
+ * Common to the three calls.  The device is the one that holds the image (gnxr_exposure_device: the histogram); the work is queued
+ * on hip_stream and the call returns without waiting for the GPU; no scratch.  n_views == 0 is a no-op.  GNXR_ERR_INVALID, before
+ * anything is queued: a null params or required pointer; a struct_size other than sizeof of the record; width or height < 1,
+ * n_views < 0; a parameter outside the range given below; a pointer that is not device memory, is on another device than the first
+ * array, or whose extent runs past the end of its allocation; a four-float buffer, a histogram or an exposure record not 16-byte
+ * aligned, an RGBA8 plane not 4-byte aligned; an output that overlaps an input (one exception: in-place exposure);
+ * n_views*width*height beyond the limit of gnxr_render_views_device.  The records carry struct_size; they are not part of
+ * gnxr_abi_sizeof's list.
+ *
+ * gnxr_luminance_histogram_device: a log-luminance histogram from the bit pattern of the luminance.  Integers only: the result is
+ * exact and does not depend on the order in which pixels are counted.  min_log2 in [-126, 111].  d_hist: GNXR_HISTOGRAM_WORDS = 260
+ * uint32 per view, overwritten (zeroed on the stream first).  Per pixel, l = lum(d_rgba[p].rgb), bits = the word of l:
+ *   exponent field all ones (NaN, +-inf)                         hist[258]++
+ *   otherwise !(l > 0) (0, -0, negatives)                        hist[256]++
+ *   otherwise k = (int)(bits >> 19) - ((min_log2 + 127) << 4):   k < 0: hist[256]++ (subnormals too);  k > 255: hist[257]++;
+ *                                                                else hist[k]++
+ *   hist[259] stays 0.
+ * Sixteen bins per octave over [2^min_log2, 2^(min_log2 + 16)): bin k covers a sixteenth of an octave's mantissa range, and its
+ * coordinate min_log2 + (k + 0.5)/16 is a piecewise-linear log2, within -0.12 / +0.03 stop of the true one (the price of a histogram
+ * without libm).  With min_log2 = -12: 2^-12 -> bin 0, 0.18 -> 151, 1.0 -> 192, the float below 16 -> 255, 16.0 -> above.
+ *
+ * gnxr_exposure_device: the exposure the histogram meters, adapted over time.  d_exposure: one float4 per view, (exposure, target,
+ * L, kept weight).  d_prev_exposure: NULL, or the same layout; it may BE d_exposure (in place) but may not overlap it at an offset.
+ * Refused unless 0 <= low < high <= 1, key > 0, 0 < rate <= 1, 0 < min_exposure <= max_exposure, every float finite, min_log2 in
+ * [-126, 111].  Per view, sequentially -- the order is the definition:
+ *   total = (float)(hist[0] + ... + hist[255], as integers);  skip = total*low;  keep = total*high - skip;  sw = sx = +0
+ *   for k = 0 .. 255:  c = (float)hist[k];  s = fminf(c, skip);  c -= s;  skip -= s;
+ *                      t = fminf(c, keep);  keep -= t;  sw += t;  sx += t * ((float)k + 0.5f)
+ *   prev = d_prev_exposure ? d_prev_exposure[4v] : 0;  prev_ok: prev > 0 and finite
+ *   sw > 0:  m = sx / sw;  L = (float)min_log2 + m * 0.0625f;
+ *            target = fminf(fmaxf(key * powf(2.0f, -L), min_exposure), max_exposure)
+ *   else:    L = 0;  target = prev_ok ? prev : 1.0f            (black, or everything out of range: hold)
+ *   exposure = prev_ok ? prev + (target - prev) * rate : target
+ *   d_exposure[4v ..] = (exposure, target, L, sw)
+ * (the pixels between the quantiles low and high of the in-range luminances are averaged in log2; key / 2^L puts that average on
+ * key.)
+ *
+ * gnxr_tonemap_device: exposure, curve, sRGB encoding, bytes.  curve: one of GNXR_TONEMAP_*; flags: GNXR_TONEMAP_SRGB |
+ * GNXR_TONEMAP_ROUND, no other bit; exposure finite and >= 0; white in [1e-3, 65504] (read by REINHARD only, validated always).
+ * d_exposure: NULL -- E = params.exposure -- or the float4-per-view record of gnxr_exposure_device -- E = d_exposure[4v], read on
+ * the device.  d_rgba8_out: 4 bytes per pixel; it overlaps neither d_rgba nor d_exposure.  Per pixel and colour channel:
+ *   x = in * E;  if !(x > 0) x = 0;  x = fminf(x, 65504.f)                        (NaN, negatives -> 0; +inf -> 65504)
+ *   LINEAR     y = x
+ *   REFERENCE  y = 1.0f - expf(-x / 0.25f)                                         (FrameBuffer::update_f_u_c's curve)
+ *   REINHARD   y = (x * (1.0f + x / (white*white))) / (1.0f + x)
+ *   ACES       y = (x * (2.51f*x + 0.03f)) / (x * (2.43f*x + 0.59f) + 0.14f)
+ *   y = fminf(fmaxf(y, 0.f), 1.f)
+ *   SRGB set   z = y <= 0.0031308f ? 12.92f*y : 1.055f * powf(y, 1.f/2.4f) - 0.055f   (GammaCorrect, core/GNXRayTracer.h:360)
+ *      unset   z = y
+ *   ROUND set  byte = (uint8)(z*255.f + 0.5f);  unset  byte = (uint8)(z*255.f)          (truncation is FrameBuffer's)
+ * Alpha is 255; a pixel is the 32-bit word R | G<<8 | B<<16 | A<<24.  With REFERENCE, no flag and E = 1 the bytes are those of
+ * gnxr_framebuffer_update(zeros, frame, 1) on a finite non-negative frame.                                                       */
+#define GNXR_HISTOGRAM_WORDS 260
+enum { GNXR_TONEMAP_LINEAR = 0, GNXR_TONEMAP_REFERENCE = 1, GNXR_TONEMAP_REINHARD = 2, GNXR_TONEMAP_ACES = 3 };   /* curve */
+#define GNXR_TONEMAP_SRGB  1u   /* flags of gnxr_tonemap_device: encode with the sRGB transfer function */
+#define GNXR_TONEMAP_ROUND 2u   /*                               round to the nearest byte instead of truncating */
+typedef struct gnxr_histogram_params { int32_t struct_size, width, height, n_views, min_log2; } gnxr_histogram_params;
+typedef struct gnxr_exposure_params { int32_t struct_size, n_views, min_log2, pad;
+                                      float key, low, high, rate, min_exposure, max_exposure; } gnxr_exposure_params;
+typedef struct gnxr_tonemap_params { int32_t struct_size, width, height, n_views, curve; uint32_t flags;
+                                     float exposure, white; } gnxr_tonemap_params;
+int gnxr_luminance_histogram_device(const gnxr_histogram_params *params, const float *d_rgba, uint32_t *d_hist, void *hip_stream);
+int gnxr_exposure_device(const gnxr_exposure_params *params, const uint32_t *d_hist, const float *d_prev_exposure, float *d_exposure,
+                         void *hip_stream);
+int gnxr_tonemap_device(const gnxr_tonemap_params *params, const float *d_rgba, const float *d_exposure, uint8_t *d_rgba8_out,
+                        void *hip_stream);
+
 /* -- Shading queries on device memory: the pieces an integrator is made of, batched -------------------------------------
  * Same conventions as the device calls of the Aggregate seam: every array is device memory of one device that holds a copy of the
  * scene, the work is queued on hip_stream (NULL: the null stream) after what the caller queued there, scratch comes from the
