@@ -491,6 +491,72 @@ class Scene:
             _check(rc)
         return mat, cls
 
+    def update_attributes(self, uv=None, normals=None, tangents=None, first_triangle=0, stream=None):
+        """Replace per-corner attributes of triangles [first_triangle, first_triangle + n) (authoring order) of a live scene
+        (gnxr_scene_update_attributes): float32 (n, 6) uv, (n, 9) normals and (n, 9) tangents in the description's layout, None = leave that
+        table as it is.  The arrays are ALL numpy arrays (host memory) or ALL contiguous torch tensors on the scene's device, read where
+        they lie on `stream` (by default torch's current stream).  Afterwards every result is that of a scene created with these
+        attributes.  Malformed arguments raise ValueError before the library is called; a refusal -- a table the scene was created
+        without, a triangle that would gain or lose attributes of its own, normals or tangents on an emissive triangle -- raises
+        GnxrError and leaves the scene as it was."""
+        name = "update_attributes"
+        given = [(what, x, cols) for what, x, cols in (("uv", uv, 6), ("normals", normals, 9), ("tangents", tangents, 9)) if x is not None]
+        if not given:
+            raise ValueError(f"{name}: none of uv, normals, tangents given")
+        on_device = not isinstance(given[0][1], np.ndarray)
+        if on_device:
+            if type(given[0][1]).__module__.split(".")[0] != "torch":
+                raise ValueError(f"{name}: {given[0][0]}: expected a numpy array or a torch tensor, got {type(given[0][1]).__name__}")
+            import torch
+            if stream is None and isinstance(given[0][1], torch.Tensor) and given[0][1].is_cuda:
+                stream = torch.cuda.current_stream(given[0][1].device)
+        handle = _stream_handle(name, stream)
+        ptrs, keep, n = {}, [], None
+        for what, x, cols in given:
+            if on_device:
+                ok = (isinstance(x, torch.Tensor) and x.is_cuda and x.device.index == self.device and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == cols and
+                      x.is_contiguous())
+                if not ok:
+                    raise ValueError(f"{name}: {what}: expected a contiguous float32 (n, {cols}) tensor on cuda:{self.device} (all arrays tensors there, or all numpy), got "
+                                     f"{type(x).__name__} {getattr(x, 'dtype', None)} {tuple(getattr(x, 'shape', ()))} on {getattr(x, 'device', None)}")
+                ptrs[what] = x.data_ptr()
+            else:
+                if not (isinstance(x, np.ndarray) and x.dtype == np.float32 and x.ndim == 2 and x.shape[1] == cols):
+                    raise ValueError(f"{name}: {what}: expected a float32 array of shape (n, {cols}) in host memory (all arrays numpy, or all tensors on the scene's device), got "
+                                     f"{type(x).__name__} {getattr(x, 'dtype', None)} {tuple(getattr(x, 'shape', ()))}")
+                x = np.ascontiguousarray(x)
+                ptrs[what] = x.ctypes.data
+            keep.append(x)
+            if n is not None and x.shape[0] != n:
+                raise ValueError(f"{name}: {what} has {x.shape[0]} rows, {given[0][0]} has {n}")
+            n = int(x.shape[0])
+        vp = lambda what: C.c_void_p(ptrs.get(what) or None)
+        _check(lib().gnxr_scene_update_attributes(self._h, int(first_triangle), n, vp("uv"), vp("normals"), vp("tangents"), C.c_void_p(handle or None)))
+
+    def triangle_attributes(self):
+        """Test hook: the per-corner attributes the first device holds, in authoring order (gnxr_scene_triangle_attributes):
+        (uv (n, 6), normals (n, 9), tangents (n, 9)) float32, None for a table the scene does not have."""
+        out = []
+        for which, cols in ((0, 6), (1, 9), (2, 9)):
+            n = C.c_int64(0)
+            _check(lib().gnxr_scene_triangle_attributes(self._h, which, None, 0, C.byref(n)))
+            if n.value == 0:
+                out.append(None)
+                continue
+            a = np.zeros(n.value, np.float32)
+            _check(lib().gnxr_scene_triangle_attributes(self._h, which, a.ctypes.data_as(C.POINTER(C.c_float)), n.value, C.byref(n)))
+            out.append(a.reshape(-1, cols))
+        return tuple(out)
+
+    def recompute_normals(self, flip=False, stream=None):
+        """Shading normals of the smooth triangles (those whose normal row is not all zero) from the vertices the scene holds now
+        (gnxr_scene_recompute_normals; the definition, operation by operation: include/gnxr.h): area-weighted sums of face normals over
+        the triangles that share a vertex index, normalised; flat triangles, uvs and tangents are untouched.  flip=True negates every
+        face normal.  A scene without per-corner normals is left as it is.  `stream`: None (the null stream), a torch.cuda.Stream or a
+        hipStream_t as a non-negative integer."""
+        handle = _stream_handle("recompute_normals", stream)
+        _check(lib().gnxr_scene_recompute_normals(self._h, _abi.NORMALS_FLIP if flip else 0, C.c_void_p(handle or None)))
+
     def rebuild_bvh(self, stream=None):
         """Rebuild the BVH on the device over the vertices the scene holds now (after update_vertices): the HLBVH tree a new Scene over
         those vertices would get, with materials, textures, tables and the reserved path state kept.  `stream`: None (the null stream),
@@ -2013,6 +2079,85 @@ class TemporalAccumulator:
                 depth = mo["guide"][..., 3].contiguous()
             res["denoised"] = _denoise(res["color"], normal=mo["guide"], depth=depth, stream=tstream)
         return res
+
+
+def skin_vertices(rest, bone_index, bone_weight, bones, morph_delta=None, morph_weight=None, out=None, stream=None):
+    """Linear-blend skinning with blend shapes on the GPU (gnxr_skin_vertices_device; the definition, operation by operation:
+    include/gnxr.h).  All arguments are contiguous torch tensors on one GPU: `rest` (V, 3) float32, `bone_index` (V, 4) int32,
+    `bone_weight` (V, 4) float32 (used as given, never normalised; a slot with weight 0 is skipped and its index ignored), `bones`
+    (B, 3, 4) or (B, 12) float32, row-major 3x4 matrices to world space, and optionally `morph_delta` (M, V, 3) float32 with
+    `morph_weight` (M,) float32.  Returns the (V, 3) float32 positions (`out` when given; it must not overlap an input), which
+    Scene.update_vertices takes as they are.  A bone index outside [0, B) in a used slot raises GnxrError.  Queued on `stream` (by default
+    torch's current stream)."""
+    import torch
+    name = "skin_vertices"
+    _gpu_tensor(f"{name}: rest", rest, torch.float32, (3,))
+    dev, V = rest.device, rest.shape[0]
+    _gpu_tensor(f"{name}: bone_index", bone_index, torch.int32, (4,), dev)
+    _gpu_tensor(f"{name}: bone_weight", bone_weight, torch.float32, (4,), dev)
+    if isinstance(bones, torch.Tensor) and bones.dim() == 3:
+        _gpu_tensor(f"{name}: bones", bones, torch.float32, (3, 4), dev)
+    else:
+        _gpu_tensor(f"{name}: bones", bones, torch.float32, (12,), dev)
+    if bone_index.shape[0] != V or bone_weight.shape[0] != V:
+        raise ValueError(f"{name}: {V} rest positions, {bone_index.shape[0]} index rows, {bone_weight.shape[0]} weight rows")
+    if bones.shape[0] < 1:
+        raise ValueError(f"{name}: at least one bone is required")
+    if (morph_delta is None) != (morph_weight is None):
+        raise ValueError(f"{name}: morph_delta and morph_weight come together or not at all")
+    M = 0
+    if morph_delta is not None:
+        _gpu_tensor(f"{name}: morph_delta", morph_delta, torch.float32, (V, 3), dev)
+        _gpu_tensor(f"{name}: morph_weight", morph_weight, torch.float32, (), dev)
+        M = morph_delta.shape[0]
+        if morph_weight.shape[0] != M:
+            raise ValueError(f"{name}: {M} morph targets, {morph_weight.shape[0]} weights")
+    hstream, tstream = _stream_pair(stream, dev)
+    with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensor to the stream that writes it)
+        res = _out_tensor(f"{name}: out", out, (V, 3), torch.float32, dev)
+    ptr = lambda x: C.c_void_p(x.data_ptr() or None)
+    p = _abi.SkinParams(C.sizeof(_abi.SkinParams), V, int(bones.shape[0]), M)
+    _check(lib().gnxr_skin_vertices_device(C.byref(p), ptr(rest), ptr(bone_index), ptr(bone_weight), ptr(bones), ptr(morph_delta) if M else None,
+                                           ptr(morph_weight) if M else None, ptr(res), C.c_void_p(hstream or None)))
+    return res
+
+
+class SkinnedMesh:
+    """The per-frame loop of a skinned mesh in a live scene, made of the public calls and nothing else: skin_vertices ->
+    Scene.update_vertices -> Scene.recompute_normals.
+
+    `vertices`: the description's whole vertex array, (n_vertices, 3) float32 (numpy or a tensor); `rest`, `bone_index`, `bone_weight`
+    (and `morph_delta`): skin_vertices' arguments for vertices [first_vertex, first_vertex + len(rest)), tensors on the scene's device.
+    The object keeps two whole-scene vertex tensors on the device, the current and the previous frame's -- the layout
+    Scene.motion(prev_vertices=) and TemporalAccumulator.frame(prev_vertices=) take.  move_lights: pass it on to update_vertices;
+    normals=False leaves the shading normals alone (a flat-shaded mesh)."""
+
+    def __init__(self, scene, vertices, rest, bone_index, bone_weight, first_vertex=0, morph_delta=None, move_lights=False, normals=True):
+        import torch
+        device = torch.device("cuda", scene.device)
+        v = torch.as_tensor(vertices, dtype=torch.float32).to(device).contiguous()
+        if v.dim() != 2 or v.shape[1] != 3 or v.shape[0] != scene.n_vertices:
+            raise ValueError(f"SkinnedMesh: vertices: expected (n_vertices = {scene.n_vertices}, 3), got {tuple(v.shape)}")
+        first_vertex = int(first_vertex)
+        if first_vertex < 0 or first_vertex + rest.shape[0] > scene.n_vertices:
+            raise ValueError(f"SkinnedMesh: vertices [{first_vertex}, {first_vertex + rest.shape[0]}) outside the scene's {scene.n_vertices}")
+        self.scene, self.first_vertex, self.move_lights, self.normals = scene, first_vertex, bool(move_lights), bool(normals)
+        self.rest, self.bone_index, self.bone_weight, self.morph_delta = rest, bone_index, bone_weight, morph_delta
+        self.vertices, self.prev_vertices = v.clone(), v.clone()
+
+    def pose(self, bones, morph_weight=None, flip=False, stream=None):
+        """One frame: the two vertex tensors swap, the range is skinned into the current one, the scene takes it (update_vertices, then
+        recompute_normals unless normals=False).  Returns the previous frame's whole vertex tensor."""
+        import torch
+        self.vertices, self.prev_vertices = self.prev_vertices, self.vertices
+        _, tstream = _stream_pair(stream, self.vertices.device)
+        n = self.rest.shape[0]
+        moved = self.vertices[self.first_vertex:self.first_vertex + n]   # (rows of a contiguous tensor: contiguous)
+        skin_vertices(self.rest, self.bone_index, self.bone_weight, bones, self.morph_delta, morph_weight if self.morph_delta is not None else None, out=moved, stream=tstream)
+        self.scene.update_vertices(moved, first_vertex=self.first_vertex, stream=tstream, move_lights=self.move_lights)
+        if self.normals:
+            self.scene.recompute_normals(flip=flip, stream=tstream)
+        return self.prev_vertices
 
 
 def _display_image(name, color):

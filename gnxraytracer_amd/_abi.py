@@ -206,6 +206,12 @@ HISTOGRAM_WORDS = 260   # uint32 per view of gnxr_luminance_histogram_device: 25
 TONEMAP_LINEAR, TONEMAP_REFERENCE, TONEMAP_REINHARD, TONEMAP_ACES = range(4)   # curve of gnxr_tonemap_params
 TONEMAP_SRGB, TONEMAP_ROUND = 1, 2   # flags of gnxr_tonemap_params
 
+class SkinParams(C.Structure):   # gnxr_skin_params (carries struct_size: not in gnxr_abi_sizeof's list)
+    _fields_ = [("struct_size", i32), ("n_vertices", i32), ("n_bones", i32), ("n_morphs", i32)]
+
+
+NORMALS_FLIP = 1   # flags of gnxr_scene_recompute_normals
+
 # kind of gnxr_film_filter / flags of gnxr_render_filtered_device
 FILTER_BOX, FILTER_TRIANGLE, FILTER_GAUSSIAN, FILTER_MITCHELL, FILTER_TABLE = range(5)
 FILM_CONTINUE = 1
@@ -275,6 +281,10 @@ PROTOTYPES = {
     "gnxr_luminance_histogram_device": (C.c_int, [P(HistogramParams), VP, VP, VP]),   # image, histogram: device; hipStream_t
     "gnxr_exposure_device": (C.c_int, [P(ExposureParams), VP, VP, VP, VP]),   # histogram, previous records (or NULL), records: device; hipStream_t
     "gnxr_tonemap_device": (C.c_int, [P(TonemapParams), VP, VP, VP, VP]),   # image, exposure records (or NULL), RGBA8: device; hipStream_t
+    "gnxr_scene_update_attributes": (C.c_int, [VP, i32, i32, VP, VP, VP, VP]),   # scene, first, n, host or device fp32 uv / normal / tangent rows (or NULL), hipStream_t
+    "gnxr_scene_triangle_attributes": (C.c_int, [VP, i32, P(f32), i64, P(i64)]),   # scene, which, out, capacity in floats, size in floats
+    "gnxr_scene_recompute_normals": (C.c_int, [VP, u32, VP]),   # scene, flags (NORMALS_FLIP), hipStream_t
+    "gnxr_skin_vertices_device": (C.c_int, [P(SkinParams), VP, VP, VP, VP, VP, VP, VP, VP]),   # rest, bone index, bone weight, bones, morph deltas, morph weights, out: device; hipStream_t
     "gnxr_material_albedo": (C.c_int, [P(Material), P(f32)]),
     "gnxr_camera_rays_device": (C.c_int, [P(Camera), i32, i32, i32, VP, VP, VP, i64, VP, VP, VP]),   # device addresses + hipStream_t
     "gnxr_bsdf_device": (C.c_int, [VP, VP, VP, VP, VP, i64, i32, VP, VP]),   # device addresses + hipStream_t

@@ -215,7 +215,7 @@ void geometry_commit_host(gnxr_scene *s, const gnxr_geometry &g, GeomHost &hh, R
     refit_world_bound(&cs, hh.root6);   // Scene::WorldBound, the environment light's bounding sphere, the delta lights' radius (in cs.lights: refit_world uploads them)
 }
 // ... then every copy: pointer swaps; the tables of the old mesh that the new one lacks go, as do the material edits' authoring-order
-// tables (material_tables uploads the new ones at the next edit)
+// tables (material_tables uploads the new ones at the next edit) and the vertex -> corner table of gnxr_scene_recompute_normals
 void geometry_commit_copy(gnxr_scene *s, Rebuilt &r) {
     const bool has_media = r.tri_media.p, has_uv = r.tri_uv.p, has_n = r.tri_n.p, has_s = r.tri_s.p;   // (asked before the swaps)
     rebuild_commit_copy(s, r);
@@ -224,6 +224,7 @@ void geometry_commit_copy(gnxr_scene *s, Rebuilt &r) {
     if (!has_n) s->tri_n.release();
     if (!has_s) s->tri_s.release();
     s->mat_map.release(); s->mat_tri.release(); s->mat_own.release();
+    s->adj_offsets.release(); s->adj_corners.release();   // the normals' adjacency follows the index array (api_deform.hip.h builds the new one at the next call)
 }
 
 }  // namespace

@@ -55,6 +55,7 @@ struct SceneHost {
     CompiledScene cs;
     bool host_bvh_stale = false;     // after an update cs.nodes / nodes4 / tris / leaf_boxes lag the primary's device until sync_host_bvh()
     bool host_order_stale = false;   // after gnxr_scene_rebuild_bvh the host copies of what is held in leaf or node order lag too (the upd_* tables are current)
+    bool host_attr_stale = false;    // after gnxr_scene_update_attributes / gnxr_scene_recompute_normals cs.tri_uv / tri_n / tri_s lag the primary's device until sync_host_bvh() (with host_bvh_stale)
     bool host_env_stale = false;     // after gnxr_scene_update_environment cs.env_texels / env_texels4 / env_cond_* / env_marg_* lag the devices until sync_host_env()
     std::mutex env_mutex;            // sync_host_env may be reached from the worker of any copy (ensure_grid)
 };
@@ -133,6 +134,12 @@ struct gnxr_scene {
     // first edit (material_tables; the map is allocated last: it marks the set complete) and kept current by every edit after it
     DevBuf<int32_t> mat_tri, mat_map;
     DevBuf<uint8_t> mat_own;
+    // gnxr_scene_recompute_normals (api_deform.hip.h): the vertex -> corner table (CSR over authored corner ids 3 t + k, built at the first call
+    // of a topology, released by gnxr_scene_set_geometry), the per-call face normals (per authored triangle) and vertex sums; and the
+    // refusal flag of gnxr_scene_update_attributes
+    DevBuf<uint32_t> adj_offsets, adj_corners;
+    DevBuf<float4> nrm_face, nrm_vsum;
+    DevBuf<int> attr_flag;
     // gnxr_render_views_device: the host copy of st.view_cams (what the stream-ordered upload reads; both only grow)
     std::vector<DCamera> h_view_cams;
 
@@ -157,6 +164,13 @@ struct gnxr_scene {
             if (!cs.tri_s.empty()) HIP_TRY(hipMemcpy(cs.tri_s.data(), tri_s.p, cs.tri_s.size() * sizeof(float), hipMemcpyDeviceToHost));
             for (size_t li = 0; li < cs.tris.size(); ++li) cs.leaf_of_prim[cs.tris[li].prim] = (int32_t)li;
             host->host_order_stale = false;
+            host->host_attr_stale = false;
+        }
+        if (host->host_attr_stale) {
+            if (!cs.tri_uv.empty()) HIP_TRY(hipMemcpy(cs.tri_uv.data(), tri_uv.p, cs.tri_uv.size() * sizeof(float), hipMemcpyDeviceToHost));
+            if (!cs.tri_n.empty()) HIP_TRY(hipMemcpy(cs.tri_n.data(), tri_n.p, cs.tri_n.size() * sizeof(float), hipMemcpyDeviceToHost));
+            if (!cs.tri_s.empty()) HIP_TRY(hipMemcpy(cs.tri_s.data(), tri_s.p, cs.tri_s.size() * sizeof(float), hipMemcpyDeviceToHost));
+            host->host_attr_stale = false;
         }
         host->host_bvh_stale = false;
         return GNXR_OK;

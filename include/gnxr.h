@@ -384,7 +384,8 @@ int gnxr_scene_info(const gnxr_scene *scene, int32_t *n_bvh_nodes, int32_t *bvh_
  * device memory of the scene's (first) device; the read is ordered after work already queued on hip_stream (NULL: the null
  * stream), and the refit runs on that stream.  The BVH keeps its topology and primitive order; its boxes are refitted on the
  * device (exactly the LinearBVHNode bounds that topology has over the new vertices).  Returns when every device of the scene
- * holds the new geometry.  Per-corner uvs / shading normals / tangents, spheres, materials and lights are unchanged; what depends
+ * holds the new geometry.  Per-corner uvs / shading normals / tangents, spheres, materials and lights are unchanged (a smooth mesh
+ * gets normals for its new shape from gnxr_scene_recompute_normals, or rows of the caller's from gnxr_scene_update_attributes); what depends
  * on the world bound (environment and distant lights, the light-selection table) follows it.  GNXR_ERR_UNSUPPORTED (scene
  * untouched) if a vertex of an emissive (AREA_TRI) triangle would change value: area lights move through
  * gnxr_scene_update_vertices_ex with GNXR_UPDATE_MOVE_LIGHTS.  GNXR_ERR_INVALID for a null scene, a null xyz with
@@ -1275,6 +1276,63 @@ int gnxr_exposure_device(const gnxr_exposure_params *params, const uint32_t *d_h
                          void *hip_stream);
 int gnxr_tonemap_device(const gnxr_tonemap_params *params, const float *d_rgba, const float *d_exposure, uint8_t *d_rgba8_out,
                         void *hip_stream);
+
+/* -- Deforming smooth meshes in place: pose -> moved vertices -> refit -> shading normals ---------------------------------
+ * gnxr_skin_vertices_device makes the moved vertices, gnxr_scene_update_vertices[_ex] takes them (it accepts device memory) and
+ * refits the tree, gnxr_scene_recompute_normals gives the smooth triangles the normals of the new shape, and
+ * gnxr_scene_update_attributes replaces per-corner rows with the caller's own.  Every arithmetic step below is ONE rounded fp32
+ * operation: nothing is contracted into a fused multiply-add, divisions and square roots are correctly rounded, and sums run in the
+ * stated order, so a restatement in fp32 that follows the text reproduces the results bit for bit (tests/deform_reference.py).
+ *
+ * gnxr_scene_update_attributes: rows [first_triangle, first_triangle + n_triangles) of the scene's per-corner tables become the
+ * caller's.  Triangles are in authoring numbering (gnxr_scene_desc.indices); tri_uv has 6 floats per triangle, tri_n and tri_s 9,
+ * in the layout of gnxr_scene_desc; a NULL array leaves that table as it is.  The arrays are all host memory or all device memory of
+ * the scene's first device (the rule of gnxr_scene_set_geometry); reads are ordered after work already queued on hip_stream, and the
+ * call returns when every device of the scene holds the new rows.  Afterwards every result is, bit for bit, that of a scene created
+ * with these attributes (the tree is the one the handle has); re-sending the rows a scene holds changes nothing.  Refusals are all
+ * detected before anything is written and leave the scene untouched.  GNXR_ERR_INVALID: a null scene, a range outside the scene's
+ * triangles, all three arrays NULL with n_triangles > 0, arrays on mixed sides or on another device.  GNXR_ERR_UNSUPPORTED: an array
+ * whose table the scene was created without; a triangle whose own-attribute status would change -- it has attributes of its own when
+ * its uvs differ in any bit from the defaults (0,0) (1,0) (1,1) or its normal or tangent row has any bit set, which selects its
+ * material copy and shade class and is therefore topology (gnxr_scene_set_geometry changes it); a normal or tangent row with a bit
+ * set on an emissive triangle (refused at creation as well).
+ *
+ * gnxr_scene_triangle_attributes (test hook): the rows the first device holds, in authoring order and unpadded; which = 0 uvs
+ * (6 floats per triangle), 1 normals, 2 tangents (9).  *n_floats receives the size of the table (0: the scene has none); the rows
+ * are written when out is not NULL and capacity_floats >= *n_floats.
+ *
+ * gnxr_scene_recompute_normals: shading normals from the vertices the scene holds now.  S = the triangles whose tri_n row has any
+ * bit set when the call starts (the smooth triangles); the others take no part and are not written.  For t in S with corners p0, p1,
+ * p2 (the positions the scene holds): a = p1 - p0, b = p2 - p0, F_t = (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x), each
+ * product rounded, then the difference; F_t is not normalised, so faces weigh in by their area.  With GNXR_NORMALS_FLIP every
+ * component of F_t is negated.  For a vertex index v, N_v = the sum of F_t over the corners of triangles in S that name v, starting
+ * from +0, in ascending authoring triangle number and, within a triangle, ascending corner (a triangle that names v twice adds twice).
+ * Triangles share a normal where they share a vertex INDEX; duplicated vertices make a crease.  For each corner of t in S, with N the
+ * sum of its vertex: l2 = (N.x N.x + N.y N.y) + N.z N.z; if l2 is finite and > 0 the corner's normal becomes N / sqrt(l2) (three
+ * divisions by the one rounded root), otherwise the corner keeps the normal it had.  So no row becomes zero and no triangle's
+ * own-attribute status changes.  tri_s and tri_uv are not touched (the shading frame is orthogonalised against the normal at every
+ * hit).  The vertex -> corner table behind N_v is built on the device at the first call and kept until gnxr_scene_set_geometry
+ * replaces the mesh; gnxr_scene_rebuild_bvh leaves it valid.  Every device of the scene computes the same bits; the call returns when
+ * all hold them.  GNXR_ERR_INVALID for a null scene or unknown flag bits; a scene without tri_n is a successful no-op.
+ *
+ * gnxr_skin_vertices_device: linear-blend skinning with blend shapes on device memory, no scene involved.  Per vertex v:
+ * q = d_rest[v]; for m = 0 .. n_morphs - 1 in order, q = q + w_m * d_morph_delta[m][v] per component (w_m = d_morph_weight[m]; one
+ * multiply, one add).  P = (0, 0, 0); for slot k = 0 .. 3 in order, with w = d_bone_weight[v][k]: a slot with w == 0 is skipped and its
+ * index is not looked at; otherwise, with the row-major 3x4 matrix m of bone d_bone_index[v][k], T.x = ((m00 q.x + m01 q.y) + m02 q.z)
+ * + m03 and likewise T.y, T.z, and P = P + w * T per component.  d_out[v] = P.  Weights are used as given (never normalised).  All
+ * arrays are device memory of one device, validated as gnxr_temporal_accumulate_device validates its buffers; d_bone_index,
+ * d_bone_weight and d_bones are 16-byte aligned (their rows are read whole), the others 4-byte; d_out overlaps no input;
+ * d_morph_delta and d_morph_weight may be NULL when n_morphs == 0.  An index outside [0, n_bones) in a slot with a non-zero weight
+ * is never dereferenced: the call returns GNXR_ERR_INVALID with the contents of d_out unspecified.  The work is queued on hip_stream;
+ * the call waits for its status word only.  d_out can go straight into gnxr_scene_update_vertices. */
+#define GNXR_NORMALS_FLIP 1u   /* flags of gnxr_scene_recompute_normals */
+typedef struct gnxr_skin_params { int32_t struct_size, n_vertices, n_bones, n_morphs; } gnxr_skin_params;
+int gnxr_scene_update_attributes(gnxr_scene *scene, int32_t first_triangle, int32_t n_triangles, const float *tri_uv, const float *tri_n,
+                                 const float *tri_s, void *hip_stream);
+int gnxr_scene_triangle_attributes(gnxr_scene *scene, int32_t which, float *out, int64_t capacity_floats, int64_t *n_floats);
+int gnxr_scene_recompute_normals(gnxr_scene *scene, uint32_t flags, void *hip_stream);
+int gnxr_skin_vertices_device(const gnxr_skin_params *params, const float *d_rest, const int32_t *d_bone_index, const float *d_bone_weight,
+                              const float *d_bones, const float *d_morph_delta, const float *d_morph_weight, float *d_out, void *hip_stream);
 
 /* -- Shading queries on device memory: the pieces an integrator is made of, batched -------------------------------------
  * Same conventions as the device calls of the Aggregate seam: every array is device memory of one device that holds a copy of the
