@@ -418,41 +418,20 @@ int gnxr_camera_rays_device(const gnxr_camera *cam, int32_t camera_medium, int32
     if (int rc = ensure_device()) return rc;
     const QueryArg args[] = {{d_px, (size_t)n * 4, "d_px"}, {d_py, (size_t)n * 4, "d_py"}, {d_s, (size_t)n * 4, "d_s"}, {d_rays, (size_t)n * sizeof(gnxr_ray), "d_rays"},
                              {d_samples, (size_t)n * sizeof(gnxr_li_sample), "d_samples"}};
-    int device = -1;
-    for (const QueryArg &a : args) {
-        hipPointerAttribute_t at;
-        const hipError_t e = hipPointerGetAttributes(&at, a.p);
-        (void)hipGetLastError();
-        if (e != hipSuccess || at.type != hipMemoryTypeDevice) { set_error("%s is not device memory (host arrays go through gnxr_camera_rays)", a.what); return GNXR_ERR_INVALID; }
-        if (device >= 0 && at.device != device) { set_error("%s and %s live on different devices", args[0].what, a.what); return GNXR_ERR_INVALID; }
-        device = at.device;
-        hipDeviceptr_t base = nullptr;
-        size_t size = 0;
-        if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)a.p) == hipSuccess && base && (const char *)a.p + a.bytes > (const char *)base + size) {
-            set_error("%s: %zu bytes from %p run past the end of its allocation (%zu bytes from %p)", a.what, a.bytes, a.p, size, (void *)base);
-            return GNXR_ERR_INVALID;
-        }
-        (void)hipGetLastError();
-    }
     DeviceCall call;
-    if (int rc = call.bind(device)) return rc;
+    if (int rc = call.bind("", args, " (host arrays go through gnxr_camera_rays)")) return rc;
     DSamplerTables st;
-    if (int rc = device_probe_tables(device, &st)) return rc;
+    if (int rc = device_probe_tables(call.device, &st)) return rc;
     st.h = make_halton(width, height);
     const DCamera dc = make_camera(*cam, width, height, camera_medium);
     hipStream_t stream = (hipStream_t)hip_stream;
-    StreamScratch scratch;
-    HIP_TRY(scratch.alloc(sizeof(unsigned long long), stream));
-    unsigned long long *d_bad = reinterpret_cast<unsigned long long *>(scratch.p), bad = 0;
-    hipError_t e = hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_camera_rays, dim3(grid_for(n)), dim3(kBlock), 0, stream, st, dc, (int)width, (int)height, (const int *)d_px, (const int *)d_py, (const int *)d_s,
-                           (long long)n, reinterpret_cast<float4 *>(d_rays), reinterpret_cast<int4 *>(d_samples), d_bad);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);   // only the status word has to come back: the records are on the stream
-    HIP_TRY(e);
+    StatusWord status;
+    unsigned long long bad = 0;
+    if (int rc = status.alloc(stream)) return rc;
+    hipLaunchKernelGGL(k_camera_rays, dim3(grid_for(n)), dim3(kBlock), 0, stream, st, dc, (int)width, (int)height, (const int *)d_px, (const int *)d_py, (const int *)d_s,
+                       (long long)n, reinterpret_cast<float4 *>(d_rays), reinterpret_cast<int4 *>(d_samples), status.d);
+    HIP_TRY(hipGetLastError());
+    if (int rc = status.fetch(&bad)) return rc;
     if (bad) {
         set_error("gnxr_camera_rays_device: record %llu is out of range (px in [0, %d), py in [0, %d), s >= 0); its ray and sample are 0", (unsigned long long)~bad, width, height);
         return GNXR_ERR_INVALID;

@@ -21,7 +21,7 @@ int gnxr_render_aov_device(gnxr_scene *s, const gnxr_render_params *p, const gnx
     if ((((uintptr_t)out->d_depth | (uintptr_t)out->d_ids) & 3u) != 0) { set_error("d_depth and d_ids must be 4-byte aligned"); return GNXR_ERR_INVALID; }
     // a sample slot is sample * (n_views * W * H) + pixel, traced by the kernel of the views call: its limit
     long long total = 0;
-    if (int rc = check_view_pixels(*p, n_views, "feature buffers", &total)) return rc;
+    if (int rc = check_view_pixels(p->width, p->height, n_views, "feature buffers", &total)) return rc;
     if (!cameras) camera_media = nullptr;   // the scene's own camera sits in the scene's camera medium
     if (int rc = check_view_media(s, camera_media, n_views, "feature buffers")) return rc;
     if (n_views == 0) { if (stats) memset(stats, 0, sizeof(*stats)); return GNXR_OK; }

@@ -143,20 +143,9 @@ int gnxr_bake_dilate_device(int32_t width, int32_t height, int32_t iterations, f
     if (int rc = bake_atlas_ok("gnxr_bake_dilate_device", width, height)) return rc;
     if (((uintptr_t)d_rgba & 15u) != 0) { set_error("gnxr_bake_dilate_device: d_rgba is not 16-byte aligned"); return GNXR_ERR_INVALID; }
     if (int rc = ensure_device()) return rc;
-    const size_t bytes = (size_t)width * height * sizeof(float4);
-    hipPointerAttribute_t at;
-    const hipError_t e = hipPointerGetAttributes(&at, d_rgba);
-    (void)hipGetLastError();
-    if (e != hipSuccess || at.type != hipMemoryTypeDevice) { set_error("gnxr_bake_dilate_device: d_rgba is not device memory"); return GNXR_ERR_INVALID; }
-    hipDeviceptr_t base = nullptr;
-    size_t size_b = 0;
-    if (hipMemGetAddressRange(&base, &size_b, (hipDeviceptr_t)d_rgba) == hipSuccess && base && (const char *)d_rgba + bytes > (const char *)base + size_b) {
-        set_error("gnxr_bake_dilate_device: d_rgba: %zu bytes from %p run past the end of its allocation (%zu bytes from %p)", bytes, (void *)d_rgba, size_b, (void *)base);
-        return GNXR_ERR_INVALID;
-    }
-    (void)hipGetLastError();
+    const QueryArg args[] = {{d_rgba, (size_t)width * height * sizeof(float4), "d_rgba"}};
     DeviceCall call;
-    if (int rc = call.bind(at.device)) return rc;
+    if (int rc = call.bind("gnxr_bake_dilate_device", args)) return rc;
     return bake_dilate((float4 *)d_rgba, width, height, iterations, (hipStream_t)hip_stream);
 }
 

@@ -220,35 +220,14 @@ int gnxr_skin_vertices_device(const gnxr_skin_params *p, const float *d_rest, co
     const int kArgs = 7;   // the output comes last
     const QueryArg args[kArgs] = {{d_rest, V * 12, "d_rest"}, {d_bone_index, V * 16, "d_bone_index"}, {d_bone_weight, V * 16, "d_bone_weight"}, {d_bones, B * 48, "d_bones"},
                                   {M ? d_morph_delta : nullptr, M * V * 12, "d_morph_delta"}, {M ? d_morph_weight : nullptr, M * 4, "d_morph_weight"}, {d_out, V * 12, "d_out"}};
-    for (int i = 0; i < kArgs; ++i) {
-        const unsigned align = i >= 1 && i <= 3 ? 16u : 4u;   // the 16-byte rows: four indices, four weights, a matrix row
-        if (((uintptr_t)args[i].p & (align - 1)) != 0) { set_error("skin vertices: %s is not %u-byte aligned", args[i].what, align); return GNXR_ERR_INVALID; }
-    }
+    const unsigned align[kArgs] = {4u, 16u, 16u, 16u, 4u, 4u, 4u};   // the 16-byte rows: four indices, four weights, a matrix row
+    if (int rc = check_aligned("skin vertices", args, align, kArgs)) return rc;
     if (V == 0) return GNXR_OK;
-    for (int i = 0; i < kArgs - 1; ++i) {
-        const char *g = (const char *)args[i].p, *w = (const char *)d_out;
-        if (g && g < w + args[kArgs - 1].bytes && w < g + args[i].bytes) { set_error("skin vertices: d_out overlaps %s", args[i].what); return GNXR_ERR_INVALID; }
-    }
+    for (int i = 0; i < kArgs - 1; ++i)
+        if (ranges_overlap(args[i], args[kArgs - 1])) { set_error("skin vertices: d_out overlaps %s", args[i].what); return GNXR_ERR_INVALID; }
     if (int rc = ensure_device()) return rc;
-    int device = -1;
-    for (const QueryArg &a : args) {
-        if (!a.p) continue;
-        hipPointerAttribute_t at;
-        const hipError_t e = hipPointerGetAttributes(&at, a.p);
-        (void)hipGetLastError();
-        if (e != hipSuccess || at.type != hipMemoryTypeDevice) { set_error("skin vertices: %s is not device memory", a.what); return GNXR_ERR_INVALID; }
-        if (device >= 0 && at.device != device) { set_error("skin vertices: %s and %s live on different devices", args[0].what, a.what); return GNXR_ERR_INVALID; }
-        device = at.device;
-        hipDeviceptr_t base = nullptr;
-        size_t size_b = 0;
-        if (hipMemGetAddressRange(&base, &size_b, (hipDeviceptr_t)a.p) == hipSuccess && base && (const char *)a.p + a.bytes > (const char *)base + size_b) {
-            set_error("skin vertices: %s: %zu bytes from %p run past the end of its allocation (%zu bytes from %p)", a.what, a.bytes, a.p, size_b, (void *)base);
-            return GNXR_ERR_INVALID;
-        }
-        (void)hipGetLastError();
-    }
     DeviceCall call;
-    if (int rc = call.bind(device)) return rc;
+    if (int rc = call.bind("skin vertices", args)) return rc;
     hipStream_t st = (hipStream_t)hip_stream;
     StreamScratch scratch;   // the bad-index flag
     HIP_TRY(scratch.alloc(sizeof(int), st));

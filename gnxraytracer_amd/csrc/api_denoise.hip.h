@@ -1,6 +1,6 @@
 // api_denoise.hip.h -- gnxr_denoise_device: the edge-avoiding a-trous filter on device memory, guided by the feature buffers (the
-// definition: include/gnxr.h; the kernels: denoise_kernel.hip.h).  No scene: the device is the one that holds d_color, as for
-// gnxr_camera_rays_device.  Part of api.hip's translation unit.
+// definition: include/gnxr.h; the kernels: denoise_kernel.hip.h).  No scene: the device is the one that holds the arrays
+// (DeviceCall::bind(name, args), api_device_call.hip.h).  Part of api.hip's translation unit.
 #pragma once
 
 template <bool B, bool N, bool Z>
@@ -25,47 +25,24 @@ int gnxr_denoise_device(const gnxr_denoise_params *p, const gnxr_denoise_buffers
     if (p->width < 1 || p->height < 1 || p->n_views < 0) { set_error("denoise: width and height >= 1 and n_views >= 0 are required"); return GNXR_ERR_INVALID; }
     if (p->iterations < 1 || p->iterations > 8) { set_error("denoise: iterations = %d is outside [1, 8]", p->iterations); return GNXR_ERR_INVALID; }
     if (!(p->sigma_color >= 0.f) || !(p->sigma_normal >= 0.f) || !(p->sigma_depth >= 0.f)) { set_error("denoise: the sigmas must be >= 0 (no NaN)"); return GNXR_ERR_INVALID; }
-    gnxr_render_params size;
-    memset(&size, 0, sizeof(size));
-    size.width = p->width; size.height = p->height;
     long long npix = 0;
-    if (int rc = check_view_pixels(size, p->n_views, "denoise", &npix)) return rc;
+    if (int rc = check_view_pixels(p->width, p->height, p->n_views, "denoise", &npix)) return rc;
     const size_t n4 = (size_t)npix * sizeof(float4), n1 = (size_t)npix * sizeof(float);
     const QueryArg args[] = {{in->d_color, n4, "d_color"}, {in->d_color_b, n4, "d_color_b"}, {in->d_albedo, n4, "d_albedo"}, {in->d_normal, n4, "d_normal"},
                              {in->d_depth, n1, "d_depth"}, {d_rgba_out, n4, "d_rgba_out"}};
-    for (int i = 0; i < 6; ++i) {
-        const unsigned align = i == 4 ? 4u : 16u;   // d_depth: one float per pixel
-        if (((uintptr_t)args[i].p & (align - 1)) != 0) { set_error("denoise: %s is not %u-byte aligned", args[i].what, align); return GNXR_ERR_INVALID; }
-    }
+    const unsigned align[] = {16u, 16u, 16u, 16u, 4u, 16u};   // d_depth: one float per pixel
+    if (int rc = check_aligned("denoise", args, align, 6)) return rc;
     if (npix == 0) return GNXR_OK;
     for (int i = 0; i < 5; ++i) {   // the output may BE a colour share (every lane reads its own pixel before it writes it); it overlaps nothing else
-        const char *g = (const char *)args[i].p, *o = (const char *)d_rgba_out;
-        if (i < 2 && g == o) continue;
-        if (g && g < o + n4 && o < g + args[i].bytes) {
+        if (i < 2 && args[i].p == (const void *)d_rgba_out) continue;
+        if (ranges_overlap(args[i], args[5])) {
             set_error(i < 2 ? "denoise: d_rgba_out overlaps %s at an offset (in place means the same address)" : "denoise: d_rgba_out overlaps %s", args[i].what);
             return GNXR_ERR_INVALID;
         }
     }
     if (int rc = ensure_device()) return rc;
-    int device = -1;
-    for (const QueryArg &a : args) {
-        if (!a.p) continue;
-        hipPointerAttribute_t at;
-        const hipError_t e = hipPointerGetAttributes(&at, a.p);
-        (void)hipGetLastError();
-        if (e != hipSuccess || at.type != hipMemoryTypeDevice) { set_error("denoise: %s is not device memory", a.what); return GNXR_ERR_INVALID; }
-        if (device >= 0 && at.device != device) { set_error("denoise: %s and %s live on different devices", args[0].what, a.what); return GNXR_ERR_INVALID; }
-        device = at.device;
-        hipDeviceptr_t base = nullptr;
-        size_t size_b = 0;
-        if (hipMemGetAddressRange(&base, &size_b, (hipDeviceptr_t)a.p) == hipSuccess && base && (const char *)a.p + a.bytes > (const char *)base + size_b) {
-            set_error("denoise: %s: %zu bytes from %p run past the end of its allocation (%zu bytes from %p)", a.what, a.bytes, a.p, size_b, (void *)base);
-            return GNXR_ERR_INVALID;
-        }
-        (void)hipGetLastError();
-    }
     DeviceCall call;
-    if (int rc = call.bind(device)) return rc;
+    if (int rc = call.bind("denoise", args)) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
     StreamScratch scratch;   // two ping-pong work records and one guide record per pixel
     HIP_TRY(scratch.alloc(3 * n4, stream));

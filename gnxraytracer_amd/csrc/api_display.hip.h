@@ -1,42 +1,8 @@
 // api_display.hip.h -- the display stage on device memory: gnxr_luminance_histogram_device, gnxr_exposure_device and gnxr_tonemap_device
-// (validate, queue, return: pure image operations on the device that holds the image, as gnxr_temporal_accumulate_device).  The
-// definition: include/gnxr.h; the kernels: display_kernel.hip.h.  Part of api.hip's translation unit.
+// (validate, queue, return: pure image operations on the device that holds the image).  Once its parameters have passed, each call
+// checks overlap, then alignment, returns for an empty call and only then asks the runtime where its arrays live (the pieces:
+// api_device_call.hip.h).  The definition: include/gnxr.h; the kernels: display_kernel.hip.h.  Part of api.hip's translation unit.
 #pragma once
-
-// What the three calls share once their parameters have passed: alignment (align[i] bytes for args[i]), nothing to do for an empty
-// call (*empty), then -- the first step that needs the runtime -- every array is device memory of one device and ends inside its
-// allocation; that device is bound.
-static int display_bind(const char *name, const QueryArg *args, const unsigned *align, int n_args, bool nothing_to_do, bool *empty, DeviceCall *call) {
-    for (int i = 0; i < n_args; ++i)
-        if (((uintptr_t)args[i].p & (align[i] - 1)) != 0) { set_error("%s: %s is not %u-byte aligned", name, args[i].what, align[i]); return GNXR_ERR_INVALID; }
-    *empty = nothing_to_do;
-    if (nothing_to_do) return GNXR_OK;
-    if (int rc = ensure_device()) return rc;
-    int device = -1;
-    for (int i = 0; i < n_args; ++i) {
-        const QueryArg &a = args[i];
-        if (!a.p) continue;
-        hipPointerAttribute_t at;
-        const hipError_t e = hipPointerGetAttributes(&at, a.p);
-        (void)hipGetLastError();
-        if (e != hipSuccess || at.type != hipMemoryTypeDevice) { set_error("%s: %s is not device memory", name, a.what); return GNXR_ERR_INVALID; }
-        if (device >= 0 && at.device != device) { set_error("%s: %s and %s live on different devices", name, args[0].what, a.what); return GNXR_ERR_INVALID; }
-        device = at.device;
-        hipDeviceptr_t base = nullptr;
-        size_t size_b = 0;
-        if (hipMemGetAddressRange(&base, &size_b, (hipDeviceptr_t)a.p) == hipSuccess && base && (const char *)a.p + a.bytes > (const char *)base + size_b) {
-            set_error("%s: %s: %zu bytes from %p run past the end of its allocation (%zu bytes from %p)", name, a.what, a.bytes, a.p, size_b, (void *)base);
-            return GNXR_ERR_INVALID;
-        }
-        (void)hipGetLastError();
-    }
-    return call->bind(device);
-}
-
-static bool display_overlap(const QueryArg &a, const QueryArg &b) {
-    const char *x = (const char *)a.p, *y = (const char *)b.p;
-    return x && y && x < y + b.bytes && y < x + a.bytes;
-}
 
 static bool display_is_finite(float x) { return x - x == 0.f; }
 
@@ -58,19 +24,17 @@ int gnxr_luminance_histogram_device(const gnxr_histogram_params *p, const float 
     if (p->struct_size != (int32_t)sizeof(gnxr_histogram_params)) { set_error("%s: struct_size must be sizeof(gnxr_histogram_params) = %zu", name, sizeof(gnxr_histogram_params)); return GNXR_ERR_INVALID; }
     if (p->width < 1 || p->height < 1 || p->n_views < 0) { set_error("%s: width and height >= 1 and n_views >= 0 are required", name); return GNXR_ERR_INVALID; }
     if (p->min_log2 < -126 || p->min_log2 > 111) { set_error("%s: min_log2 = %d is outside [-126, 111]", name, p->min_log2); return GNXR_ERR_INVALID; }
-    gnxr_render_params size;
-    memset(&size, 0, sizeof(size));
-    size.width = p->width; size.height = p->height;
     long long npix = 0;
-    if (int rc = check_view_pixels(size, p->n_views, name, &npix)) return rc;
+    if (int rc = check_view_pixels(p->width, p->height, p->n_views, name, &npix)) return rc;
     const size_t hist_bytes = (size_t)p->n_views * kHistWords * sizeof(uint32_t);
     const QueryArg args[] = {{d_rgba, (size_t)npix * sizeof(float4), "d_rgba"}, {d_hist, hist_bytes, "d_hist"}};
     const unsigned align[] = {16u, 16u};
-    if (npix > 0 && display_overlap(args[0], args[1])) { set_error("%s: d_hist overlaps d_rgba", name); return GNXR_ERR_INVALID; }
+    if (npix > 0 && ranges_overlap(args[0], args[1])) { set_error("%s: d_hist overlaps d_rgba", name); return GNXR_ERR_INVALID; }
+    if (int rc = check_aligned(name, args, align, 2)) return rc;
+    if (npix == 0) return GNXR_OK;
+    if (int rc = ensure_device()) return rc;
     DeviceCall call;
-    bool empty = false;
-    if (int rc = display_bind(name, args, align, 2, npix == 0, &empty, &call)) return rc;
-    if (empty) return GNXR_OK;
+    if (int rc = call.bind(name, args)) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
     HIP_TRY(hipMemsetAsync(d_hist, 0, hist_bytes, stream));
     const int bias = (p->min_log2 + 127) << 4;
@@ -100,16 +64,17 @@ int gnxr_exposure_device(const gnxr_exposure_params *p, const uint32_t *d_hist, 
     const QueryArg args[] = {{d_hist, (size_t)p->n_views * kHistWords * sizeof(uint32_t), "d_hist"}, {d_prev_exposure, rec_bytes, "d_prev_exposure"}, {d_exposure, rec_bytes, "d_exposure"}};
     const unsigned align[] = {16u, 16u, 16u};
     if (p->n_views > 0) {
-        if (display_overlap(args[2], args[0])) { set_error("%s: d_exposure overlaps d_hist", name); return GNXR_ERR_INVALID; }
-        if ((const void *)d_prev_exposure != (const void *)d_exposure && display_overlap(args[2], args[1])) {
+        if (ranges_overlap(args[2], args[0])) { set_error("%s: d_exposure overlaps d_hist", name); return GNXR_ERR_INVALID; }
+        if ((const void *)d_prev_exposure != (const void *)d_exposure && ranges_overlap(args[2], args[1])) {
             set_error("%s: d_exposure overlaps d_prev_exposure at an offset (in place means the same address)", name);
             return GNXR_ERR_INVALID;
         }
     }
+    if (int rc = check_aligned(name, args, align, 3)) return rc;
+    if (p->n_views == 0) return GNXR_OK;
+    if (int rc = ensure_device()) return rc;
     DeviceCall call;
-    bool empty = false;
-    if (int rc = display_bind(name, args, align, 3, p->n_views == 0, &empty, &call)) return rc;
-    if (empty) return GNXR_OK;
+    if (int rc = call.bind(name, args)) return rc;
     ExposureParams ep;
     ep.min_log2 = p->min_log2;
     ep.key = p->key; ep.low = p->low; ep.high = p->high; ep.rate = p->rate; ep.min_exposure = p->min_exposure; ep.max_exposure = p->max_exposure;
@@ -128,22 +93,20 @@ int gnxr_tonemap_device(const gnxr_tonemap_params *p, const float *d_rgba, const
     if ((p->flags & ~(uint32_t)(GNXR_TONEMAP_SRGB | GNXR_TONEMAP_ROUND)) != 0) { set_error("%s: flags = 0x%x holds unknown bits", name, p->flags); return GNXR_ERR_INVALID; }
     if (!display_is_finite(p->exposure) || !(p->exposure >= 0.f)) { set_error("%s: exposure = %g must be finite and >= 0", name, p->exposure); return GNXR_ERR_INVALID; }
     if (!(p->white >= 1e-3f && p->white <= 65504.f)) { set_error("%s: white = %g is outside [1e-3, 65504]", name, p->white); return GNXR_ERR_INVALID; }
-    gnxr_render_params size;
-    memset(&size, 0, sizeof(size));
-    size.width = p->width; size.height = p->height;
     long long npix = 0;
-    if (int rc = check_view_pixels(size, p->n_views, name, &npix)) return rc;
+    if (int rc = check_view_pixels(p->width, p->height, p->n_views, name, &npix)) return rc;
     const QueryArg args[] = {{d_rgba, (size_t)npix * sizeof(float4), "d_rgba"}, {d_exposure, (size_t)p->n_views * sizeof(float4), "d_exposure"},
                              {d_rgba8_out, (size_t)npix * 4, "d_rgba8_out"}};
     const unsigned align[] = {16u, 16u, 4u};
     if (npix > 0) {
         for (int i = 0; i < 2; ++i)
-            if (display_overlap(args[2], args[i])) { set_error("%s: d_rgba8_out overlaps %s", name, args[i].what); return GNXR_ERR_INVALID; }
+            if (ranges_overlap(args[2], args[i])) { set_error("%s: d_rgba8_out overlaps %s", name, args[i].what); return GNXR_ERR_INVALID; }
     }
+    if (int rc = check_aligned(name, args, align, 3)) return rc;
+    if (npix == 0) return GNXR_OK;
+    if (int rc = ensure_device()) return rc;
     DeviceCall call;
-    bool empty = false;
-    if (int rc = display_bind(name, args, align, 3, npix == 0, &empty, &call)) return rc;
-    if (empty) return GNXR_OK;
+    if (int rc = call.bind(name, args)) return rc;
     const bool srgb = (p->flags & GNXR_TONEMAP_SRGB) != 0;
     const int round = (p->flags & GNXR_TONEMAP_ROUND) ? 1 : 0, grid = grid_for(npix), wh = p->width * p->height;
     const float ww = p->white * p->white;

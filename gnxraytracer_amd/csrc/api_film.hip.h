@@ -62,38 +62,19 @@ static void film_make(const gnxr_film_filter &f, FilmFilter *ff, FilmTable *tab)
     ff->hx = std::min(kFilmMaxHalo, (int)ceilf(f.radius_x + 0.5f)); ff->hy = std::min(kFilmMaxHalo, (int)ceilf(f.radius_y + 0.5f));
     film_table(f, tab->v);
 }
-// The arrays of a film call without a scene: all given, aligned, device memory of one device (-> *device) and inside their allocations
-static int film_check_buffers(const char *call, const QueryArg *args, const unsigned *align, int n_args, int *device) {
+// The arrays of a film call without a scene: each given and aligned, then -- the first step that needs the runtime -- all on one device,
+// which `dc` binds
+static int film_check_buffers(const char *call, const QueryArg *args, const unsigned *align, int n_args, DeviceCall *dc) {
     for (int i = 0; i < n_args; ++i) {
         if (!args[i].p) { set_error("%s: %s is null", call, args[i].what); return GNXR_ERR_INVALID; }
-        if (((uintptr_t)args[i].p & (align[i] - 1)) != 0) { set_error("%s: %s is not %u-byte aligned", call, args[i].what, align[i]); return GNXR_ERR_INVALID; }
+        if (int rc = check_aligned(call, args + i, align + i, 1)) return rc;
     }
     if (int rc = ensure_device()) return rc;
-    *device = -1;
-    for (int i = 0; i < n_args; ++i) {
-        const QueryArg &a = args[i];
-        hipPointerAttribute_t at;
-        const hipError_t e = hipPointerGetAttributes(&at, a.p);
-        (void)hipGetLastError();
-        if (e != hipSuccess || at.type != hipMemoryTypeDevice) { set_error("%s: %s is not device memory", call, a.what); return GNXR_ERR_INVALID; }
-        if (*device >= 0 && at.device != *device) { set_error("%s: %s and %s live on different devices", call, args[0].what, a.what); return GNXR_ERR_INVALID; }
-        *device = at.device;
-        hipDeviceptr_t base = nullptr;
-        size_t size_b = 0;
-        if (hipMemGetAddressRange(&base, &size_b, (hipDeviceptr_t)a.p) == hipSuccess && base && (const char *)a.p + a.bytes > (const char *)base + size_b) {
-            set_error("%s: %s: %zu bytes from %p run past the end of its allocation (%zu bytes from %p)", call, a.what, a.bytes, a.p, size_b, (void *)base);
-            return GNXR_ERR_INVALID;
-        }
-        (void)hipGetLastError();
-    }
-    return GNXR_OK;
+    return dc->bind(call, args, n_args);
 }
 static int film_check_size(const char *call, int32_t width, int32_t height, int32_t n_views, long long *npix) {
     if (width < 1 || height < 1 || n_views < 0) { set_error("%s: width and height >= 1 and n_views >= 0 are required", call); return GNXR_ERR_INVALID; }
-    gnxr_render_params size;
-    memset(&size, 0, sizeof(size));
-    size.width = width; size.height = height;
-    return check_view_pixels(size, n_views, call, npix);
+    return check_view_pixels(width, height, n_views, call, npix);
 }
 
 extern "C" {
@@ -115,14 +96,10 @@ int gnxr_film_add_device(const gnxr_film_filter *filter, int32_t width, int32_t 
     const size_t n = (size_t)n_layers * (size_t)npix;
     const QueryArg args[] = {{d_accum, (size_t)npix * sizeof(float4), "d_accum"}, {d_L, n * sizeof(float4), "d_L"}, {d_offsets, n * sizeof(float2), "d_offsets"}};
     const unsigned align[] = {16u, 16u, 8u};
-    int device = -1;
-    if (int rc = film_check_buffers("film_add", args, align, 3, &device)) return rc;
-    for (int i = 1; i < 3; ++i) {   // the accumulator is read and written while the samples are read
-        const char *g = (const char *)args[i].p, *o = (const char *)d_accum;
-        if (g < o + args[0].bytes && o < g + args[i].bytes) { set_error("film_add: d_accum overlaps %s", args[i].what); return GNXR_ERR_INVALID; }
-    }
     DeviceCall call;
-    if (int rc = call.bind(device)) return rc;
+    if (int rc = film_check_buffers("film_add", args, align, 3, &call)) return rc;
+    for (int i = 1; i < 3; ++i)   // the accumulator is read and written while the samples are read
+        if (ranges_overlap(args[0], args[i])) { set_error("film_add: d_accum overlaps %s", args[i].what); return GNXR_ERR_INVALID; }
     FilmFilter ff;
     FilmTable tab;
     film_make(*filter, &ff, &tab);
@@ -142,14 +119,12 @@ int gnxr_film_resolve_device(int32_t width, int32_t height, int32_t n_views, con
     const size_t n4 = (size_t)npix * sizeof(float4);
     const QueryArg args[] = {{d_accum, n4, "d_accum"}, {d_rgba_out, n4, "d_rgba_out"}};
     const unsigned align[] = {16u, 16u};
-    int device = -1;
-    if (int rc = film_check_buffers("film_resolve", args, align, 2, &device)) return rc;
-    {   // in place means the same address
-        const char *g = (const char *)d_accum, *o = (const char *)d_rgba_out;
-        if (g != o && g < o + n4 && o < g + n4) { set_error("film_resolve: d_rgba_out overlaps d_accum at an offset (in place means the same address)"); return GNXR_ERR_INVALID; }
-    }
     DeviceCall call;
-    if (int rc = call.bind(device)) return rc;
+    if (int rc = film_check_buffers("film_resolve", args, align, 2, &call)) return rc;
+    if ((const void *)d_accum != (const void *)d_rgba_out && ranges_overlap(args[0], args[1])) {
+        set_error("film_resolve: d_rgba_out overlaps d_accum at an offset (in place means the same address)");
+        return GNXR_ERR_INVALID;
+    }
     hipLaunchKernelGGL(k_film_resolve, dim3(grid_for(npix)), dim3(kBlock), 0, (hipStream_t)hip_stream, (const float4 *)d_accum, npix, (float4 *)d_rgba_out);
     HIP_TRY(hipGetLastError());
     return GNXR_OK;
@@ -168,16 +143,13 @@ int gnxr_render_filtered_device(gnxr_scene *s, const gnxr_render_params *p, cons
     if (!d_rgba_out && !d_accum) { set_error("render_filtered: d_rgba_out and d_accum are both null"); return GNXR_ERR_INVALID; }
     if ((((uintptr_t)d_rgba_out | (uintptr_t)d_accum) & 15u) != 0) { set_error("render_filtered: d_rgba_out and d_accum must be 16-byte aligned"); return GNXR_ERR_INVALID; }
     long long total = 0;
-    if (int rc = check_view_pixels(*p, n_views, "render_filtered", &total)) return rc;
+    if (int rc = check_view_pixels(p->width, p->height, n_views, "render_filtered", &total)) return rc;
     if (int rc = ensure_device()) return rc;
     if (!cameras) camera_media = nullptr;   // the scene's own camera sits in the scene's camera medium
     if (int rc = check_view_media(s, camera_media, n_views, "render_filtered")) return rc;
     const size_t n4 = (size_t)total * sizeof(float4);
-    if (d_rgba_out && d_accum) {
-        const char *g = (const char *)d_accum, *o = (const char *)d_rgba_out;
-        if (g < o + n4 && o < g + n4) { set_error("render_filtered: d_rgba_out overlaps d_accum"); return GNXR_ERR_INVALID; }
-    }
     const QueryArg args[] = {{d_rgba_out, n4, "d_rgba_out"}, {d_accum, n4, "d_accum"}};
+    if (ranges_overlap(args[0], args[1])) { set_error("render_filtered: d_rgba_out overlaps d_accum"); return GNXR_ERR_INVALID; }
     DeviceCall call;
     if (int rc = call.bind(s, args)) return rc;
     gnxr_render_params pp = *p;

@@ -9,38 +9,8 @@
 static const long long kLightprobeMaxProbes = 1ll << 27;
 static const int kShBlock = 64;   // samples of a block of the projection's sum: the width of a wave
 
-// The device that holds every listed array of a call without a scene (-1 and the error set otherwise); the extents are checked against the
-// allocations whenever the runtime reports them.
-static int lightprobe_arrays_device(const char *call, const QueryArg *args, int n_args) {
-    int device = -1;
-    for (int i = 0; i < n_args; ++i) {
-        const QueryArg &a = args[i];
-        hipPointerAttribute_t at;
-        const hipError_t e = hipPointerGetAttributes(&at, a.p);
-        (void)hipGetLastError();
-        if (e != hipSuccess || at.type != hipMemoryTypeDevice) { set_error("%s: %s is not device memory", call, a.what); return -1; }
-        if (device >= 0 && at.device != device) { set_error("%s: %s and %s live on different devices", call, args[0].what, a.what); return -1; }
-        device = at.device;
-        hipDeviceptr_t base = nullptr;
-        size_t size = 0;
-        if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)a.p) == hipSuccess && base && (const char *)a.p + a.bytes > (const char *)base + size) {
-            set_error("%s: %s: %zu bytes from %p run past the end of its allocation (%zu bytes from %p)", call, a.what, a.bytes, a.p, size, (void *)base);
-            return -1;
-        }
-        (void)hipGetLastError();
-    }
-    return device;
-}
-
 // a wave per probe, as many blocks as the probes need or the device holds
 static int sh_project_grid(long long n_probes) { return grid_for(n_probes * 64); }
-
-// the status word of a kernel that flags records: back on the host once the kernel has run (only the word is waited for)
-static int lightprobe_status(unsigned long long *d_bad, hipStream_t stream, unsigned long long *bad) {
-    HIP_TRY(hipMemcpyAsync(bad, d_bad, sizeof(*bad), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    return GNXR_OK;
-}
 
 extern "C" {
 
@@ -64,14 +34,13 @@ int gnxr_lightprobe_rays_device(gnxr_scene *s, int32_t width, int32_t height, co
     if (int rc = call.bind(s, args)) return rc;
     gnxr_scene *r = call.r;   // the sampler tables never change after the scene is created: no lock
     hipStream_t stream = (hipStream_t)hip_stream;
-    StreamScratch scratch;
-    HIP_TRY(scratch.alloc(sizeof(unsigned long long), stream));
-    unsigned long long *d_bad = reinterpret_cast<unsigned long long *>(scratch.p), bad = 0;
-    HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), stream));
+    StatusWord status;
+    unsigned long long bad = 0;
+    if (int rc = status.alloc(stream)) return rc;
     hipLaunchKernelGGL(k_lightprobe_rays, dim3(grid_for(n)), dim3(kBlock), 0, stream, bake_sampler_tables(r, width, height), (int)width, (int)height, d_pos, (const int *)d_px,
-                       (const int *)d_py, (const int *)d_s, (long long)n, (int)medium, reinterpret_cast<float4 *>(d_rays), reinterpret_cast<int4 *>(d_samples), d_bad);
+                       (const int *)d_py, (const int *)d_s, (long long)n, (int)medium, reinterpret_cast<float4 *>(d_rays), reinterpret_cast<int4 *>(d_samples), status.d);
     HIP_TRY(hipGetLastError());
-    if (int rc = lightprobe_status(d_bad, stream, &bad)) return rc;
+    if (int rc = status.fetch(&bad)) return rc;
     if (bad) {
         set_error("gnxr_lightprobe_rays_device: record %llu is out of range (a finite position, px in [0, %d), py in [0, %d), s >= 0); its ray and sample are 0",
                   (unsigned long long)~bad, width, height);
@@ -90,10 +59,8 @@ int gnxr_sh_project_device(const gnxr_ray *d_rays, const float *d_L, int32_t n_p
     if (int rc = ensure_device()) return rc;
     const size_t n = (size_t)n_probes * (size_t)n_samples;
     const QueryArg args[] = {{d_sh_sum, (size_t)n_probes * 9 * sizeof(float4), "d_sh_sum"}, {d_rays, n * sizeof(gnxr_ray), "d_rays"}, {d_L, n * sizeof(float4), "d_L"}};
-    const int device = lightprobe_arrays_device("gnxr_sh_project_device", args, n_samples > 0 ? 3 : 1);
-    if (device < 0) return GNXR_ERR_INVALID;
     DeviceCall call;
-    if (int rc = call.bind(device)) return rc;
+    if (int rc = call.bind("gnxr_sh_project_device", args, n_samples > 0 ? 3 : 1)) return rc;
     hipLaunchKernelGGL(k_sh_project, dim3(sh_project_grid(n_probes)), dim3(kBlock), 0, (hipStream_t)hip_stream, reinterpret_cast<const float4 *>(d_rays),
                        reinterpret_cast<const float4 *>(d_L), (int)n_probes, (long long)n_samples, (int)((flags & GNXR_SH_CONTINUE) != 0), reinterpret_cast<float4 *>(d_sh_sum));
     HIP_TRY(hipGetLastError());
@@ -111,19 +78,16 @@ int gnxr_sh_irradiance_device(const float *d_sh, int32_t n_probes, const int32_t
     if (int rc = ensure_device()) return rc;
     const QueryArg args[] = {{d_E, (size_t)n * sizeof(float4), "d_E"}, {d_probe, (size_t)n * 4, "d_probe"}, {d_normals, (size_t)n * 12, "d_normals"},
                              {d_sh, (size_t)n_probes * 9 * sizeof(float4), "d_sh"}};
-    const int device = lightprobe_arrays_device("gnxr_sh_irradiance_device", args, n_probes > 0 ? 4 : 3);
-    if (device < 0) return GNXR_ERR_INVALID;
     DeviceCall call;
-    if (int rc = call.bind(device)) return rc;
+    if (int rc = call.bind("gnxr_sh_irradiance_device", args, n_probes > 0 ? 4 : 3)) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
-    StreamScratch scratch;
-    HIP_TRY(scratch.alloc(sizeof(unsigned long long), stream));
-    unsigned long long *d_bad = reinterpret_cast<unsigned long long *>(scratch.p), bad = 0;
-    HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), stream));
+    StatusWord status;
+    unsigned long long bad = 0;
+    if (int rc = status.alloc(stream)) return rc;
     hipLaunchKernelGGL(k_sh_irradiance, dim3(grid_for(n)), dim3(kBlock), 0, stream, reinterpret_cast<const float4 *>(d_sh), (int)n_probes, (const int *)d_probe, d_normals,
-                       (long long)n, reinterpret_cast<float4 *>(d_E), d_bad);
+                       (long long)n, reinterpret_cast<float4 *>(d_E), status.d);
     HIP_TRY(hipGetLastError());
-    if (int rc = lightprobe_status(d_bad, stream, &bad)) return rc;
+    if (int rc = status.fetch(&bad)) return rc;
     if (bad) {
         set_error("gnxr_sh_irradiance_device: record %llu names a probe outside [0, %d); its irradiance is 0", (unsigned long long)~bad, n_probes);
         return GNXR_ERR_INVALID;

@@ -129,7 +129,7 @@ int gnxr_render_views_device(gnxr_scene *s, const gnxr_render_params *p, const g
     if (n_views == 0) { if (stats) memset(stats, 0, sizeof(*stats)); return GNXR_OK; }
     if (!d_rgba_out || ((uintptr_t)d_rgba_out & 15u) != 0) { set_error("d_rgba_out is null or not 16-byte aligned"); return GNXR_ERR_INVALID; }
     long long total = 0;
-    if (int rc = check_view_pixels(*p, n_views, "views", &total)) return rc;
+    if (int rc = check_view_pixels(p->width, p->height, n_views, "views", &total)) return rc;
     if (int rc = ensure_device()) return rc;
     if (int rc = check_view_media(s, camera_media, n_views, "views")) return rc;
     const QueryArg args[] = {{d_rgba_out, (size_t)total * sizeof(float4), "d_rgba_out"}};
@@ -208,18 +208,13 @@ int gnxr_light_sample_device(gnxr_scene *s, const float *d_queries, int64_t n, i
     hipStream_t st = (hipStream_t)hip_stream;
     DLightTables lt;
     if ((rc = query_light_tables(r, strategy, &lt)) != GNXR_OK) return rc;
-    StreamScratch scratch;
-    HIP_TRY(scratch.alloc(sizeof(unsigned long long), st));
-    unsigned long long *d_bad = reinterpret_cast<unsigned long long *>(scratch.p), bad = 0;
-    hipError_t e = hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), st);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL((k_light_sample_query<LT_ALL>), dim3(grid_for(n)), dim3(kBlock), 0, st, lt, reinterpret_cast<const float4 *>(d_queries), (long long)n,
-                           reinterpret_cast<float4 *>(d_out), d_bad);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);   // the status has to come back
-    HIP_TRY(e);
+    StatusWord status;
+    unsigned long long bad = 0;
+    if ((rc = status.alloc(st)) != GNXR_OK) return rc;
+    hipLaunchKernelGGL((k_light_sample_query<LT_ALL>), dim3(grid_for(n)), dim3(kBlock), 0, st, lt, reinterpret_cast<const float4 *>(d_queries), (long long)n,
+                       reinterpret_cast<float4 *>(d_out), status.d);
+    HIP_TRY(hipGetLastError());
+    if ((rc = status.fetch(&bad)) != GNXR_OK) return rc;
     if (bad) {
         set_error("gnxr_light_sample_device: query %llu names a light outside [0, %d); its record is 0", (unsigned long long)~bad, lt.n_lights);
         return GNXR_ERR_INVALID;

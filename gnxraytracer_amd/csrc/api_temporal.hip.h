@@ -1,6 +1,6 @@
 // api_temporal.hip.h -- temporal accumulation on device memory: gnxr_motion_device (a pixel-centre G-buffer and where each pixel was one frame
 // ago; around closest_hit_codes, the front end of the feature buffers) and gnxr_temporal_accumulate_device (validate, gather and blend: a
-// pure image operation on the device that holds d_color, as gnxr_denoise_device).  The definition: include/gnxr.h; the kernels:
+// pure image operation on the device that holds its arrays, found by api_device_call.hip.h's walk).  The definition: include/gnxr.h; the kernels:
 // temporal_kernel.hip.h; gnxr_camera_matrices lives with make_camera (scene_compile.cpp).  Part of api.hip's translation unit.
 #pragma once
 
@@ -18,11 +18,8 @@ int gnxr_motion_device(gnxr_scene *s, const gnxr_motion_params *p, const gnxr_ca
     if (!out->d_motion && !out->d_guide && !out->d_prim) { set_error("motion: no channel requested"); return GNXR_ERR_INVALID; }
     if ((((uintptr_t)out->d_motion | (uintptr_t)out->d_guide) & 15u) != 0) { set_error("motion: d_motion and d_guide must be 16-byte aligned"); return GNXR_ERR_INVALID; }
     if ((((uintptr_t)out->d_prim | (uintptr_t)d_prev_vertices) & 3u) != 0) { set_error("motion: d_prim and d_prev_vertices must be 4-byte aligned"); return GNXR_ERR_INVALID; }
-    gnxr_render_params size;
-    memset(&size, 0, sizeof(size));
-    size.width = p->width; size.height = p->height;
     long long total = 0;
-    if (int rc = check_view_pixels(size, p->n_views, "motion", &total)) return rc;
+    if (int rc = check_view_pixels(p->width, p->height, p->n_views, "motion", &total)) return rc;
     if (p->n_views == 0) return GNXR_OK;
     if (int rc = ensure_device()) return rc;
     const size_t npx = (size_t)total;
@@ -97,47 +94,22 @@ int gnxr_temporal_accumulate_device(const gnxr_temporal_params *p, const gnxr_te
     if (p->width < 1 || p->height < 1 || p->n_views < 0) { set_error("temporal accumulate: width and height >= 1 and n_views >= 0 are required"); return GNXR_ERR_INVALID; }
     if (p->max_history < 1) { set_error("temporal accumulate: max_history = %d is below 1", p->max_history); return GNXR_ERR_INVALID; }
     if (!(p->depth_tol >= 0.f) || p->normal_cos != p->normal_cos) { set_error("temporal accumulate: depth_tol must be >= 0 and normal_cos a number (no NaN)"); return GNXR_ERR_INVALID; }
-    gnxr_render_params size;
-    memset(&size, 0, sizeof(size));
-    size.width = p->width; size.height = p->height;
     long long npix = 0;
-    if (int rc = check_view_pixels(size, p->n_views, "temporal accumulate", &npix)) return rc;
+    if (int rc = check_view_pixels(p->width, p->height, p->n_views, "temporal accumulate", &npix)) return rc;
     const size_t n4 = (size_t)npix * sizeof(float4), n1 = (size_t)npix * sizeof(int32_t);
     const int kArgs = 10, kInputs = 8;   // the two outputs come last
     const QueryArg args[kArgs] = {{io->d_color, n4, "d_color"}, {io->d_motion, n4, "d_motion"}, {io->d_guide, n4, "d_guide"}, {io->d_prim, n1, "d_prim"},
                                   {io->d_hist_color, n4, "d_hist_color"}, {io->d_hist_stat, n4, "d_hist_stat"}, {io->d_hist_guide, n4, "d_hist_guide"}, {io->d_hist_prim, n1, "d_hist_prim"},
                                   {io->d_out_color, n4, "d_out_color"}, {io->d_out_stat, n4, "d_out_stat"}};
-    for (int i = 0; i < kArgs; ++i) {
-        const unsigned align = i == 3 || i == 7 ? 4u : 16u;   // the primitive ids: one int per pixel
-        if (((uintptr_t)args[i].p & (align - 1)) != 0) { set_error("temporal accumulate: %s is not %u-byte aligned", args[i].what, align); return GNXR_ERR_INVALID; }
-    }
+    const unsigned align[kArgs] = {16u, 16u, 16u, 4u, 16u, 16u, 16u, 4u, 16u, 16u};   // the primitive ids: one int per pixel
+    if (int rc = check_aligned("temporal accumulate", args, align, kArgs)) return rc;
     if (npix == 0) return GNXR_OK;
-    for (int o = kInputs; o < kArgs; ++o) {   // the gather reads neighbours: an output overlaps no input, nor the other output
-        for (int i = 0; i < o; ++i) {
-            const char *g = (const char *)args[i].p, *w = (const char *)args[o].p;
-            if (g && g < w + args[o].bytes && w < g + args[i].bytes) { set_error("temporal accumulate: %s overlaps %s", args[o].what, args[i].what); return GNXR_ERR_INVALID; }
-        }
-    }
+    for (int o = kInputs; o < kArgs; ++o)   // the gather reads neighbours: an output overlaps no input, nor the other output
+        for (int i = 0; i < o; ++i)
+            if (ranges_overlap(args[i], args[o])) { set_error("temporal accumulate: %s overlaps %s", args[o].what, args[i].what); return GNXR_ERR_INVALID; }
     if (int rc = ensure_device()) return rc;
-    int device = -1;
-    for (const QueryArg &a : args) {
-        if (!a.p) continue;
-        hipPointerAttribute_t at;
-        const hipError_t e = hipPointerGetAttributes(&at, a.p);
-        (void)hipGetLastError();
-        if (e != hipSuccess || at.type != hipMemoryTypeDevice) { set_error("temporal accumulate: %s is not device memory", a.what); return GNXR_ERR_INVALID; }
-        if (device >= 0 && at.device != device) { set_error("temporal accumulate: %s and %s live on different devices", args[0].what, a.what); return GNXR_ERR_INVALID; }
-        device = at.device;
-        hipDeviceptr_t base = nullptr;
-        size_t size_b = 0;
-        if (hipMemGetAddressRange(&base, &size_b, (hipDeviceptr_t)a.p) == hipSuccess && base && (const char *)a.p + a.bytes > (const char *)base + size_b) {
-            set_error("temporal accumulate: %s: %zu bytes from %p run past the end of its allocation (%zu bytes from %p)", a.what, a.bytes, a.p, size_b, (void *)base);
-            return GNXR_ERR_INVALID;
-        }
-        (void)hipGetLastError();
-    }
     DeviceCall call;
-    if (int rc = call.bind(device)) return rc;
+    if (int rc = call.bind("temporal accumulate", args)) return rc;
     TemporalArrays a;
     a.color = (const float4 *)io->d_color; a.motion = (const float4 *)io->d_motion; a.guide = (const float4 *)io->d_guide; a.prim = io->d_prim;
     a.hist_color = (const float4 *)io->d_hist_color; a.hist_stat = (const float4 *)io->d_hist_stat; a.hist_guide = (const float4 *)io->d_hist_guide; a.hist_prim = io->d_hist_prim;
