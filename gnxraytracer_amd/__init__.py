@@ -23,6 +23,8 @@ import numpy as np
 
 from . import _abi
 from ._abi import (Camera, Hit, Light, LiSample, Material, Medium, Ray, RenderParams, SceneDesc, Stats, Texture)  # noqa: F401
+from ._tensors import (ANY_GPU, SOME, _addr, _arrays_on_device, _edit_stream, _expect, _got, _host_or_device, _image, _image_size, _is_tensor, _is_torch, _only_kw,  # noqa: F401
+                       _out_tensor, _outputs, _ptr, _refuse, _same_count, _stream_handle, _stream_pair)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GNXR_LIB", os.path.join(_HERE, "libgnxr.so"))   # GNXR_LIB: A/B builds during tuning
@@ -57,6 +59,9 @@ def _check(rc):
 
 def _f3(v):
     return (C.c_float * 3)(*[float(x) for x in v])
+
+
+LIGHT_STRATEGIES = {"spatial": _abi.LIGHTS_SPATIAL, "uniform": _abi.LIGHTS_UNIFORM, "power": _abi.LIGHTS_POWER}   # lightSampleStrategy by name
 
 
 def init(device_id=0):
@@ -374,28 +379,12 @@ class Scene:
         stream).  The BVH is refitted on the device with its topology kept.  Vertices of emissive triangles cannot move unless
         move_lights=True (gnxr_scene_update_vertices_ex with GNXR_UPDATE_MOVE_LIGHTS): then the area lights' records follow their
         triangles on the device."""
-        if isinstance(xyz, np.ndarray):
-            if xyz.dtype != np.float32 or xyz.ndim != 2 or xyz.shape[1] != 3:
-                raise ValueError(f"update_vertices: expected a float32 array of shape (n, 3), got {xyz.dtype} {xyz.shape}")
-            xyz = np.ascontiguousarray(xyz)
-            ptr = xyz.ctypes.data
-        elif type(xyz).__module__.split(".")[0] == "torch":
-            import torch
-            if not (isinstance(xyz, torch.Tensor) and xyz.is_cuda and xyz.device.index == self.device and xyz.dtype == torch.float32 and
-                    xyz.dim() == 2 and xyz.shape[1] == 3 and xyz.is_contiguous()):
-                raise ValueError(f"update_vertices: expected a contiguous float32 (n, 3) tensor on cuda:{self.device}, got "
-                                 f"{getattr(xyz, 'dtype', None)} {tuple(getattr(xyz, 'shape', ()))} on {getattr(xyz, 'device', None)}")
-            ptr = xyz.data_ptr()
-            if stream is None:
-                stream = torch.cuda.current_stream(xyz.device)
-        else:
-            raise ValueError(f"update_vertices: expected a numpy array or a torch tensor, got {type(xyz).__name__}")
-        stream = _stream_handle("update_vertices", stream)
+        ptr, xyz, _ = _host_or_device("update_vertices", xyz, np.float32, [(None, 3)], "(n, 3)", self.device)
+        stream = _stream_handle("update_vertices", _edit_stream(stream, xyz))
         if move_lights:
-            _check(lib().gnxr_scene_update_vertices_ex(self._h, int(first_vertex), int(xyz.shape[0]), C.c_void_p(ptr or None), _abi.UPDATE_MOVE_LIGHTS,
-                                                       C.c_void_p(stream or None)))
+            _check(lib().gnxr_scene_update_vertices_ex(self._h, int(first_vertex), int(xyz.shape[0]), _addr(ptr), _abi.UPDATE_MOVE_LIGHTS, _addr(stream)))
         else:
-            _check(lib().gnxr_scene_update_vertices(self._h, int(first_vertex), int(xyz.shape[0]), C.c_void_p(ptr or None), C.c_void_p(stream or None)))
+            _check(lib().gnxr_scene_update_vertices(self._h, int(first_vertex), int(xyz.shape[0]), _addr(ptr), _addr(stream)))
 
     def update_lights(self, lights, first_light=0):
         """Replace lights [first_light, first_light + len(lights)) of the scene's light list by `lights` (gnxr Light records, e.g. copies
@@ -425,7 +414,7 @@ class Scene:
         arr = (Light * max(len(lights), 1))()
         for k, l in enumerate(lights):
             C.memmove(C.byref(arr[k]), C.byref(l), C.sizeof(Light))
-        _check(lib().gnxr_scene_set_lights(self._h, arr if lights else None, len(lights), C.c_void_p(handle or None)))
+        _check(lib().gnxr_scene_set_lights(self._h, arr if lights else None, len(lights), _addr(handle)))
         self.n_lights = len(lights)
         self._env_light = None
         for l in lights:
@@ -463,24 +452,9 @@ class Scene:
         """Give triangles [first_triangle, first_triangle + len(ids)) (authoring order) the materials `ids`: an int32 (n,) numpy array
         (host memory) or a contiguous int32 (n,) torch tensor on the scene's device (read on `stream`, by default the current torch
         stream), values in [-1, n_materials), -1 == no material (gnxr_scene_set_triangle_materials)."""
-        if isinstance(ids, np.ndarray):
-            if ids.dtype != np.int32 or ids.ndim != 1:
-                raise ValueError(f"set_triangle_materials: expected an int32 array of shape (n,), got {ids.dtype} {ids.shape}")
-            ids = np.ascontiguousarray(ids)
-            ptr = ids.ctypes.data
-        elif type(ids).__module__.split(".")[0] == "torch":
-            import torch
-            if not (isinstance(ids, torch.Tensor) and ids.is_cuda and ids.device.index == self.device and ids.dtype == torch.int32 and
-                    ids.dim() == 1 and ids.is_contiguous()):
-                raise ValueError(f"set_triangle_materials: expected a contiguous int32 (n,) tensor on cuda:{self.device}, got "
-                                 f"{getattr(ids, 'dtype', None)} {tuple(getattr(ids, 'shape', ()))} on {getattr(ids, 'device', None)}")
-            ptr = ids.data_ptr()
-            if stream is None:
-                stream = torch.cuda.current_stream(ids.device)
-        else:
-            raise ValueError(f"set_triangle_materials: expected a numpy array or a torch tensor, got {type(ids).__name__}")
-        stream = _stream_handle("set_triangle_materials", stream)
-        _check(lib().gnxr_scene_set_triangle_materials(self._h, int(first_triangle), int(ids.shape[0]), C.c_void_p(ptr or None), C.c_void_p(stream or None)))
+        ptr, ids, _ = _host_or_device("set_triangle_materials", ids, np.int32, [(None,)], "(n,)", self.device)
+        stream = _stream_handle("set_triangle_materials", _edit_stream(stream, ids))
+        _check(lib().gnxr_scene_set_triangle_materials(self._h, int(first_triangle), int(ids.shape[0]), _addr(ptr), _addr(stream)))
 
     def triangle_materials(self):
         """Test hook: per triangle in authoring order, read from the device, (authored material index it shows or -1, shade class):
@@ -503,35 +477,16 @@ class Scene:
         given = [(what, x, cols) for what, x, cols in (("uv", uv, 6), ("normals", normals, 9), ("tangents", tangents, 9)) if x is not None]
         if not given:
             raise ValueError(f"{name}: none of uv, normals, tangents given")
-        on_device = not isinstance(given[0][1], np.ndarray)
-        if on_device:
-            if type(given[0][1]).__module__.split(".")[0] != "torch":
-                raise ValueError(f"{name}: {given[0][0]}: expected a numpy array or a torch tensor, got {type(given[0][1]).__name__}")
-            import torch
-            if stream is None and isinstance(given[0][1], torch.Tensor) and given[0][1].is_cuda:
-                stream = torch.cuda.current_stream(given[0][1].device)
-        handle = _stream_handle(name, stream)
+        on_device = _arrays_on_device(name, given[0][0], given[0][1])
+        handle = _stream_handle(name, _edit_stream(stream, given[0][1]))
         ptrs, keep, n = {}, [], None
         for what, x, cols in given:
-            if on_device:
-                ok = (isinstance(x, torch.Tensor) and x.is_cuda and x.device.index == self.device and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == cols and
-                      x.is_contiguous())
-                if not ok:
-                    raise ValueError(f"{name}: {what}: expected a contiguous float32 (n, {cols}) tensor on cuda:{self.device} (all arrays tensors there, or all numpy), got "
-                                     f"{type(x).__name__} {getattr(x, 'dtype', None)} {tuple(getattr(x, 'shape', ()))} on {getattr(x, 'device', None)}")
-                ptrs[what] = x.data_ptr()
-            else:
-                if not (isinstance(x, np.ndarray) and x.dtype == np.float32 and x.ndim == 2 and x.shape[1] == cols):
-                    raise ValueError(f"{name}: {what}: expected a float32 array of shape (n, {cols}) in host memory (all arrays numpy, or all tensors on the scene's device), got "
-                                     f"{type(x).__name__} {getattr(x, 'dtype', None)} {tuple(getattr(x, 'shape', ()))}")
-                x = np.ascontiguousarray(x)
-                ptrs[what] = x.ctypes.data
+            ptrs[what], x, _ = _host_or_device(f"{name}: {what}", x, np.float32, [(None, cols)], f"(n, {cols})", self.device, on_device)
             keep.append(x)
             if n is not None and x.shape[0] != n:
                 raise ValueError(f"{name}: {what} has {x.shape[0]} rows, {given[0][0]} has {n}")
             n = int(x.shape[0])
-        vp = lambda what: C.c_void_p(ptrs.get(what) or None)
-        _check(lib().gnxr_scene_update_attributes(self._h, int(first_triangle), n, vp("uv"), vp("normals"), vp("tangents"), C.c_void_p(handle or None)))
+        _check(lib().gnxr_scene_update_attributes(self._h, int(first_triangle), n, _addr(ptrs.get("uv")), _addr(ptrs.get("normals")), _addr(ptrs.get("tangents")), _addr(handle)))
 
     def triangle_attributes(self):
         """Test hook: the per-corner attributes the first device holds, in authoring order (gnxr_scene_triangle_attributes):
@@ -555,7 +510,7 @@ class Scene:
         face normal.  A scene without per-corner normals is left as it is.  `stream`: None (the null stream), a torch.cuda.Stream or a
         hipStream_t as a non-negative integer."""
         handle = _stream_handle("recompute_normals", stream)
-        _check(lib().gnxr_scene_recompute_normals(self._h, _abi.NORMALS_FLIP if flip else 0, C.c_void_p(handle or None)))
+        _check(lib().gnxr_scene_recompute_normals(self._h, _abi.NORMALS_FLIP if flip else 0, _addr(handle)))
 
     def rebuild_bvh(self, stream=None):
         """Rebuild the BVH on the device over the vertices the scene holds now (after update_vertices): the HLBVH tree a new Scene over
@@ -563,7 +518,7 @@ class Scene:
         a torch.cuda.Stream or a hipStream_t as a non-negative integer (TypeError / ValueError otherwise); the work is ordered after what it
         holds."""
         handle = _stream_handle("rebuild_bvh", stream)
-        _check(lib().gnxr_scene_rebuild_bvh(self._h, C.c_void_p(handle or None)))
+        _check(lib().gnxr_scene_rebuild_bvh(self._h, _addr(handle)))
 
     def set_geometry(self, vertices, indices, tri_material, tri_light=None, medium_inside=None, medium_outside=None, uv=None, normals=None,
                      tangents=None, stream=None):
@@ -577,61 +532,44 @@ class Scene:
         before the library is called; a refusal raises GnxrError and leaves the scene as it was."""
         import numbers
         name = "set_geometry"
-        on_device = not isinstance(vertices, np.ndarray)
-        if on_device:
-            if type(vertices).__module__.split(".")[0] != "torch":
-                raise ValueError(f"{name}: vertices: expected a numpy array or a torch tensor, got {type(vertices).__name__}")
-            import torch
-            if stream is None and isinstance(vertices, torch.Tensor) and vertices.is_cuda:
-                stream = torch.cuda.current_stream(vertices.device)
+        on_device = _arrays_on_device(name, "vertices", vertices)
+        stream = _edit_stream(stream, vertices)
         handle = _stream_handle(name, stream)
 
-        def arr(what, x, kind, cols, rows):
-            """a checked array and its address"""
-            shape = (rows, cols) if cols else (rows,)
-            want = f"{kind} array of shape ({'n' if rows is None else rows}{', %d' % cols if cols else ''})"
-            if on_device:
-                dt = torch.float32 if kind == "float32" else torch.int32
-                ok = (isinstance(x, torch.Tensor) and x.is_cuda and x.device.index == self.device and x.dtype == dt and x.dim() == len(shape) and x.is_contiguous())
-                if not ok or x.shape[0] < 1 or tuple(x.shape[1:]) != shape[1:] or (rows is not None and x.shape[0] != rows):
-                    raise ValueError(f"{name}: {what}: expected a contiguous {want} on cuda:{self.device} (all arrays tensors there, or all numpy), got "
-                                     f"{type(x).__name__} {getattr(x, 'dtype', None)} {tuple(getattr(x, 'shape', ()))} on {getattr(x, 'device', None)}")
-                return x, x.data_ptr()
-            dt = np.float32 if kind == "float32" else np.int32
-            ok = isinstance(x, np.ndarray) and x.dtype == dt and x.ndim == len(shape)
-            if not ok or x.shape[0] < 1 or tuple(x.shape[1:]) != shape[1:] or (rows is not None and x.shape[0] != rows):
-                raise ValueError(f"{name}: {what}: expected a {want} in host memory (all arrays numpy, or all tensors on the scene's device), got "
-                                 f"{type(x).__name__} {getattr(x, 'dtype', None)} {tuple(getattr(x, 'shape', ()))}")
-            x = np.ascontiguousarray(x)
-            return x, x.ctypes.data
+        def arr(what, x, dtype, cols, rows):
+            """a checked array and its address: at least one row, `rows` of them where that is given"""
+            text = f"({'n' if rows is None else rows}{', %d' % cols if cols else ''})"
+            address, x, _ = _host_or_device(f"{name}: {what}", x, dtype, [(rows or SOME,) + ((cols,) if cols else ())], text, self.device, on_device, tensor_text=f"array of shape {text}")
+            return x, address
 
         keep = []
         g = _abi.Geometry()
         g.struct_size = C.sizeof(_abi.Geometry)
-        v, g.vertices = arr("vertices", vertices, "float32", 3, None)
-        idx, g.indices = arr("indices", indices, "int32", 3, None)
+        v, g.vertices = arr("vertices", vertices, np.float32, 3, None)
+        idx, g.indices = arr("indices", indices, np.int32, 3, None)
         nt = int(idx.shape[0])
         if isinstance(tri_material, numbers.Integral) and not isinstance(tri_material, bool):
             if on_device:   # filled on the stream the call reads on
+                import torch
                 ts = stream if hasattr(stream, "cuda_stream") else torch.cuda.ExternalStream(handle, device=v.device)
                 with torch.cuda.stream(ts):
                     tri_material = torch.full((nt,), int(tri_material), dtype=torch.int32, device=v.device)
             else:
                 tri_material = np.full(nt, int(tri_material), np.int32)
         keep += [v, idx]
-        for field, what, x, kind, cols, required in (("tri_material", "tri_material", tri_material, "int32", 0, True), ("tri_light", "tri_light", tri_light, "int32", 0, False),
-                                                     ("tri_medium_inside", "medium_inside", medium_inside, "int32", 0, False),
-                                                     ("tri_medium_outside", "medium_outside", medium_outside, "int32", 0, False), ("tri_uv", "uv", uv, "float32", 6, False),
-                                                     ("tri_n", "normals", normals, "float32", 9, False), ("tri_s", "tangents", tangents, "float32", 9, False)):
+        for field, what, x, dtype, cols, required in (("tri_material", "tri_material", tri_material, np.int32, 0, True), ("tri_light", "tri_light", tri_light, np.int32, 0, False),
+                                                      ("tri_medium_inside", "medium_inside", medium_inside, np.int32, 0, False),
+                                                      ("tri_medium_outside", "medium_outside", medium_outside, np.int32, 0, False), ("tri_uv", "uv", uv, np.float32, 6, False),
+                                                      ("tri_n", "normals", normals, np.float32, 9, False), ("tri_s", "tangents", tangents, np.float32, 9, False)):
             if x is None and not required:
                 continue
-            a, ptr = arr(what, x, kind, cols, nt)
+            a, ptr = arr(what, x, dtype, cols, nt)
             keep.append(a)
             setattr(g, field, ptr)
         if (medium_inside is None) != (medium_outside is None):
             raise ValueError(f"{name}: medium_inside and medium_outside come together or not at all")
         g.n_vertices, g.n_triangles = int(v.shape[0]), nt
-        _check(lib().gnxr_scene_set_geometry(self._h, C.byref(g), C.c_void_p(handle or None)))
+        _check(lib().gnxr_scene_set_geometry(self._h, C.byref(g), _addr(handle)))
         self.n_triangles, self.n_vertices = nt, int(v.shape[0])
 
     def update_environment(self, rgb=None, le=None, light_to_world=None, n_samples=None, stream=None):
@@ -655,26 +593,11 @@ class Scene:
         if n_samples is not None:
             rec.n_samples = int(n_samples)
         ptr, w, h = None, 0, 0
-        if rgb is None:
-            pass
-        elif isinstance(rgb, np.ndarray):
-            if rgb.dtype != np.float32 or rgb.ndim != 3 or rgb.shape[2] != 3:
-                raise ValueError(f"update_environment: expected a float32 array of shape (h, w, 3), got {rgb.dtype} {rgb.shape}")
-            rgb = np.ascontiguousarray(rgb)
-            ptr, h, w = rgb.ctypes.data, rgb.shape[0], rgb.shape[1]
-        elif type(rgb).__module__.split(".")[0] == "torch":
-            import torch
-            if not (isinstance(rgb, torch.Tensor) and rgb.is_cuda and rgb.device.index == self.device and rgb.dtype == torch.float32 and
-                    rgb.dim() == 3 and rgb.shape[2] == 3 and rgb.is_contiguous()):
-                raise ValueError(f"update_environment: expected a contiguous float32 (h, w, 3) tensor on cuda:{self.device}, got "
-                                 f"{getattr(rgb, 'dtype', None)} {tuple(getattr(rgb, 'shape', ()))} on {getattr(rgb, 'device', None)}")
-            ptr, h, w = rgb.data_ptr(), int(rgb.shape[0]), int(rgb.shape[1])
-            if stream is None:
-                stream = torch.cuda.current_stream(rgb.device)
-        else:
-            raise ValueError(f"update_environment: expected a numpy array, a torch tensor or None, got {type(rgb).__name__}")
-        stream = _stream_handle("update_environment", stream)
-        _check(lib().gnxr_scene_update_environment(self._h, C.byref(rec), C.c_void_p(ptr) if rgb is not None else None, int(w), int(h), C.c_void_p(stream or None)))
+        if rgb is not None:
+            ptr, rgb, _ = _host_or_device("update_environment", rgb, np.float32, [(None, None, 3)], "(h, w, 3)", self.device, or_none=True)
+            h, w = rgb.shape[0], rgb.shape[1]
+        stream = _stream_handle("update_environment", _edit_stream(stream, rgb))
+        _check(lib().gnxr_scene_update_environment(self._h, C.byref(rec), _addr(ptr), int(w), int(h), _addr(stream)))
         self._env_light = rec
 
     ENV_TABLES = (("env_texels4", np.float32), ("env_cond_func", np.float32), ("env_cond_cdf", np.float32), ("env_cond_int", np.float32),
@@ -716,51 +639,37 @@ class Scene:
             C.memmove(C.byref(recs[k]), C.byref(m), C.sizeof(Medium))
         if density is None:
             handle = _stream_handle("update_media", stream)
-            _check(lib().gnxr_scene_update_media(self._h, int(first_medium), len(media), recs, None, C.c_void_p(handle or None)))
+            _check(lib().gnxr_scene_update_media(self._h, int(first_medium), len(media), recs, None, _addr(handle)))
             return
-        is_torch = lambda x: type(x).__module__.split(".")[0] == "torch"
-        grids = [density] if isinstance(density, np.ndarray) or is_torch(density) else density
+        grids = [density] if isinstance(density, np.ndarray) or _is_torch(density) else density
         if not isinstance(grids, (list, tuple)):
             raise ValueError(f"update_media: expected a numpy array, a torch tensor, a list of them or None, got {type(density).__name__}")
+        grids = list(grids)
         grid_recs = [k for k, m in enumerate(media) if m.type == _abi.MEDIUM_GRID]
         if len(grids) != len(grid_recs):
             raise ValueError(f"update_media: {len(grids)} density arrays for {len(grid_recs)} GRID records")
-        on_device = [is_torch(g) for g in grids]
+        on_device = [_is_torch(g) for g in grids]
         if any(on_device) and not all(on_device):
             raise ValueError("update_media: density arrays must be all numpy arrays or all torch tensors")
-        for g, k in zip(grids, grid_recs):
+        for i, k in enumerate(grid_recs):
             nx, ny, nz = recs[k].nx, recs[k].ny, recs[k].nz
             shapes = ((nz, ny, nx), (nx * ny * nz,))
-            if isinstance(g, np.ndarray):
-                if g.dtype != np.float32 or tuple(g.shape) not in shapes:
-                    raise ValueError(f"update_media: expected a float32 array of shape {shapes[0]} or {shapes[1]}, got {g.dtype} {g.shape}")
-            elif is_torch(g):
-                import torch
-                if not (isinstance(g, torch.Tensor) and g.is_cuda and g.device.index == self.device and g.dtype == torch.float32 and
-                        tuple(g.shape) in shapes and g.is_contiguous()):
-                    raise ValueError(f"update_media: expected a contiguous float32 {shapes[0]} or {shapes[1]} tensor on cuda:{self.device}, got "
-                                     f"{getattr(g, 'dtype', None)} {tuple(getattr(g, 'shape', ()))} on {getattr(g, 'device', None)}")
-            else:
-                raise ValueError(f"update_media: expected a numpy array or a torch tensor, got {type(g).__name__}")
+            _, grids[i], _ = _host_or_device("update_media", grids[i], np.float32, shapes, f"{shapes[0]} or {shapes[1]}", self.device)
         if not any(on_device):   # host memory: one packed array, one call
             offsets = np.cumsum([0] + [g.size for g in grids])
-            packed = np.concatenate([np.ascontiguousarray(g).reshape(-1) for g in grids]) if grids else np.zeros(1, np.float32)
+            packed = np.concatenate([g.reshape(-1) for g in grids]) if grids else np.zeros(1, np.float32)
             for k, off in zip(grid_recs, offsets):
                 recs[k].density_offset = int(off)
             handle = _stream_handle("update_media", stream)
-            _check(lib().gnxr_scene_update_media(self._h, int(first_medium), len(media), recs, C.c_void_p(packed.ctypes.data), C.c_void_p(handle or None)))
+            _check(lib().gnxr_scene_update_media(self._h, int(first_medium), len(media), recs, _addr(packed.ctypes.data), _addr(handle)))
             return
-        import torch
-        if stream is None:
-            stream = torch.cuda.current_stream(grids[0].device)
-        handle = _stream_handle("update_media", stream)
+        handle = _stream_handle("update_media", _edit_stream(stream, grids[0]))
         tensor_of = dict(zip(grid_recs, grids))
         for k in range(len(media)):
             one = (Medium * 1)()
             C.memmove(C.byref(one[0]), C.byref(recs[k]), C.sizeof(Medium))
             one[0].density_offset = 0
-            ptr = tensor_of[k].data_ptr() if k in tensor_of else None
-            _check(lib().gnxr_scene_update_media(self._h, int(first_medium) + k, 1, one, C.c_void_p(ptr) if ptr else None, C.c_void_p(handle or None)))
+            _check(lib().gnxr_scene_update_media(self._h, int(first_medium) + k, 1, one, _ptr(tensor_of.get(k)), _addr(handle)))
 
     def media_tables(self):
         """Test hook: the medium tables of the first device (gnxr_scene_media_tables): {"records": the device's medium records as uint32
@@ -796,10 +705,9 @@ class Scene:
         gamma and scale are baked into the texels and must then stay as they are (GnxrError otherwise: send the image).  The pyramids are
         built on the device and every later result is that of a scene created with these textures; a refused call raises GnxrError and
         leaves the scene as it was."""
-        is_torch = lambda x: type(x).__module__.split(".")[0] == "torch"
         if images is None:
             imgs = None
-        elif isinstance(images, np.ndarray) or is_torch(images):
+        elif isinstance(images, np.ndarray) or _is_torch(images):
             imgs = [images]
         elif isinstance(images, (list, tuple)):
             imgs = list(images)
@@ -835,22 +743,12 @@ class Scene:
                     setattr(recs[k], key, int(bool(v)))
                 else:
                     setattr(recs[k], key, float(v))
-        on_device = [is_torch(g) for g in imgs] if imgs is not None else []
+        on_device = [_is_torch(g) for g in imgs] if imgs is not None else []
         if any(on_device) and not all(on_device):
             raise ValueError("update_textures: images must be all numpy arrays or all torch tensors")
-        for k, g in enumerate(imgs or []):
-            if isinstance(g, np.ndarray):
-                if g.dtype != np.float32 or g.ndim != 3 or g.shape[2] != 3 or g.shape[0] < 1 or g.shape[1] < 1:
-                    raise ValueError(f"update_textures: expected a float32 array of shape (h, w, 3), got {g.dtype} {g.shape}")
-            elif is_torch(g):
-                import torch
-                if not (isinstance(g, torch.Tensor) and g.is_cuda and g.device.index == self.device and g.dtype == torch.float32 and
-                        g.dim() == 3 and g.shape[2] == 3 and g.shape[0] >= 1 and g.shape[1] >= 1 and g.is_contiguous()):
-                    raise ValueError(f"update_textures: expected a contiguous float32 (h, w, 3) tensor on cuda:{self.device}, got "
-                                     f"{getattr(g, 'dtype', None)} {tuple(getattr(g, 'shape', ()))} on {getattr(g, 'device', None)}")
-            else:
-                raise ValueError(f"update_textures: expected a numpy array or a torch tensor, got {type(g).__name__}")
-            recs[k].height, recs[k].width = int(g.shape[0]), int(g.shape[1])
+        for k in range(len(imgs or [])):
+            _, imgs[k], _ = _host_or_device("update_textures", imgs[k], np.float32, [(SOME, SOME, 3)], "(h, w, 3)", self.device)
+            recs[k].height, recs[k].width = int(imgs[k].shape[0]), int(imgs[k].shape[1])
 
         def keep(k):
             C.memmove(C.byref(self._textures[first_texture + k]), C.byref(recs[k]), C.sizeof(Texture))
@@ -860,24 +758,20 @@ class Scene:
             packed = None
             if imgs:
                 offsets = np.cumsum([0] + [g.size for g in imgs])
-                packed = np.concatenate([np.ascontiguousarray(g).reshape(-1) for g in imgs])
+                packed = np.concatenate([g.reshape(-1) for g in imgs])
                 for k in range(n):
                     recs[k].texel_offset = int(offsets[k])
             handle = _stream_handle("update_textures", stream)
-            _check(lib().gnxr_scene_update_textures(self._h, first_texture, n, recs, C.c_void_p(packed.ctypes.data) if packed is not None else None,
-                                                    C.c_void_p(handle or None)))
+            _check(lib().gnxr_scene_update_textures(self._h, first_texture, n, recs, _addr(packed.ctypes.data) if packed is not None else None, _addr(handle)))
             for k in range(n):
                 keep(k)
             return
-        import torch
-        if stream is None:
-            stream = torch.cuda.current_stream(imgs[0].device)
-        handle = _stream_handle("update_textures", stream)
+        handle = _stream_handle("update_textures", _edit_stream(stream, imgs[0]))
         for k in range(n):
             one = (Texture * 1)()
             C.memmove(C.byref(one[0]), C.byref(recs[k]), C.sizeof(Texture))
             one[0].texel_offset = 0
-            _check(lib().gnxr_scene_update_textures(self._h, first_texture + k, 1, one, C.c_void_p(imgs[k].data_ptr()), C.c_void_p(handle or None)))
+            _check(lib().gnxr_scene_update_textures(self._h, first_texture + k, 1, one, _ptr(imgs[k]), _addr(handle)))
             keep(k)
 
     def texture_tables(self):
@@ -946,23 +840,14 @@ class Scene:
         return occ
 
     # batched queries on device memory (gnxr_trace_closest_device / gnxr_trace_any_device)
-    def _device_tensor(self, what, x, dtype, cols):
-        import torch
-        shape = (cols,) if cols else ()
-        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.device.index == self.device and x.dtype == dtype and
-                x.dim() == 1 + len(shape) and tuple(x.shape[1:]) == shape and x.is_contiguous()):
-            raise ValueError(f"{what}: expected a contiguous {dtype} (n{''.join(', %d' % c for c in shape)}) tensor on cuda:{self.device}, got "
-                             f"{type(x).__name__} {getattr(x, 'dtype', None)} {tuple(getattr(x, 'shape', ()))} on {getattr(x, 'device', None)}")
-        return x
-
     def _query(self, name, rays, out, dtype, cols, stream):
         import torch
-        self._device_tensor(f"{name}: rays", rays, torch.float32, 8)
+        _expect(f"{name}: rays", rays, torch.float32, (8,), self.device)
         n = rays.shape[0]
         out = _out_tensor(f"{name}: out", out, (n, cols) if cols else (n,), dtype, rays.device)
         st, _ = _stream_pair(stream, rays.device)
         fn = lib().gnxr_trace_closest_device if cols else lib().gnxr_trace_any_device
-        _check(fn(self._h, C.c_void_p(rays.data_ptr() or None), n, C.c_void_p(out.data_ptr() or None), C.c_void_p(st or None)))
+        _check(fn(self._h, _ptr(rays), n, _ptr(out), _addr(st)))
         return out
 
     def intersect(self, rays, out=None, stream=None):
@@ -985,13 +870,11 @@ class Scene:
         import torch
         n = None
         for what, x, dtype, cols in args:
-            _tensor_layout(f"{name}: {what}", x, dtype, cols)
+            _expect(f"{name}: {what}", x, dtype, (cols,))
         for what, x, dtype, cols in args:
-            self._device_tensor(f"{name}: {what}", x, dtype, cols)
-            if n is None:
-                n = x.shape[0]
-            elif x.shape[0] != n:
-                raise ValueError(f"{name}: {what} has {x.shape[0]} rows for {n} {args[0][0]}")
+            _expect(f"{name}: {what}", x, dtype, (cols,), self.device)
+            n = x.shape[0] if n is None else n
+            _same_count(name, what, x.shape[0], n, args[0][0])
         out = _out_tensor(f"{name}: out", out, (n, out_cols), torch.float32, args[0][1].device)
         return (n, out) + _stream_pair(stream, args[0][1].device)
 
@@ -1012,9 +895,7 @@ class Scene:
         if not 0 <= flags <= 31:
             raise ValueError(f"bsdf: flags must be a BxDFType mask in [0, 31], got {flags}")
         n, out, st, tstream = self._query_args("bsdf", args, out, 16, stream)
-        _check(lib().gnxr_bsdf_device(self._h, C.c_void_p(rays.data_ptr() or None), C.c_void_p(wi.data_ptr() or None), C.c_void_p(u.data_ptr() or None),
-                                      C.c_void_p(differentials.data_ptr() or None) if differentials is not None else None, n, flags,
-                                      C.c_void_p(out.data_ptr() or None), C.c_void_p(st or None)))
+        _check(lib().gnxr_bsdf_device(self._h, _ptr(rays), _ptr(wi), _ptr(u), _ptr(differentials), n, flags, _ptr(out), _addr(st)))
         if n:
             with torch.cuda.stream(tstream):
                 out[:, 11:14] = out.view(torch.int32)[:, 11:14].to(torch.float32)
@@ -1029,15 +910,14 @@ class Scene:
         sampled point: the far end of the shadow ray).  A light index out of range raises GnxrError after the other queries are
         finished; its row is 0.  Queued on `stream` (default: torch's current stream); the call waits for the result's status."""
         import torch
-        names = {"spatial": _abi.LIGHTS_SPATIAL, "uniform": _abi.LIGHTS_UNIFORM, "power": _abi.LIGHTS_POWER}
-        if isinstance(strategy, bool) or strategy not in names and strategy not in names.values():
-            raise ValueError(f"sample_light: strategy must be one of {sorted(names)} or LIGHTS_SPATIAL / LIGHTS_UNIFORM / LIGHTS_POWER, got {strategy!r}")
-        strategy = names.get(strategy, strategy)
+        if isinstance(strategy, bool) or strategy not in LIGHT_STRATEGIES and strategy not in LIGHT_STRATEGIES.values():
+            raise ValueError(f"sample_light: strategy must be one of {sorted(LIGHT_STRATEGIES)} or LIGHTS_SPATIAL / LIGHTS_UNIFORM / LIGHTS_POWER, got {strategy!r}")
+        strategy = LIGHT_STRATEGIES.get(strategy, strategy)
         args = [("p", p, torch.float32, 3), ("n", n, torch.float32, 3), ("u", u, torch.float32, 2), ("wi_query", wi_query, torch.float32, 3)]
         m, out, st, tstream = self._query_args("sample_light", args, out, 12, stream)
         if isinstance(light, torch.Tensor):
             if not (light.dtype == torch.int32 and light.dim() == 1 and light.shape[0] == m and light.is_cuda and light.device == p.device):
-                raise ValueError(f"sample_light: light must be an int or an int32 ({m},) tensor on {p.device}, got {light.dtype} {tuple(light.shape)} on {light.device}")
+                raise ValueError(f"sample_light: light must be an int or an int32 ({m},) tensor on {p.device}, got {_got(light, type_name=False)}")
         elif not isinstance(light, (int, np.integer)) or isinstance(light, bool):
             raise ValueError(f"sample_light: light must be an int or an int32 tensor, got {type(light).__name__}")
         with torch.cuda.stream(tstream):   # the packed gnxr_light_sample_device queries: p, light, n, u, wi_query
@@ -1047,7 +927,7 @@ class Scene:
             q[:, 4:7] = n
             q[:, 7:9] = u
             q[:, 9:12] = wi_query
-        _check(lib().gnxr_light_sample_device(self._h, C.c_void_p(q.data_ptr() or None), m, int(strategy), C.c_void_p(out.data_ptr() or None), C.c_void_p(st or None)))
+        _check(lib().gnxr_light_sample_device(self._h, _ptr(q), m, int(strategy), _ptr(out), _addr(st)))
         return out
 
     def light_le(self, light, rays, out=None, stream=None):
@@ -1055,7 +935,7 @@ class Scene:
         (n, 3) tensor out (`out` when given); zero for lights that have no Le.  Queued on `stream`; nothing waits."""
         import torch
         n, out, st, _ = self._query_args("light_le", [("rays", rays, torch.float32, 8)], out, 3, stream)
-        _check(lib().gnxr_light_le_device(self._h, int(light), C.c_void_p(rays.data_ptr() or None), n, C.c_void_p(out.data_ptr() or None), C.c_void_p(st or None)))
+        _check(lib().gnxr_light_le_device(self._h, int(light), _ptr(rays), n, _ptr(out), _addr(st)))
         return out
 
     MOTION_CHANNELS = ("motion", "guide", "prim")
@@ -1082,7 +962,7 @@ class Scene:
         if len(prev_cameras) != V:
             raise ValueError(f"motion: {len(prev_cameras)} previous cameras for {V} view{'s' if V != 1 else ''}")
         if prev_vertices is not None:
-            self._device_tensor("motion: prev_vertices", prev_vertices, torch.float32, 3)
+            _expect("motion: prev_vertices", prev_vertices, torch.float32, (3,), self.device)
             if prev_vertices.shape[0] != self.n_vertices:
                 raise ValueError(f"motion: prev_vertices has {prev_vertices.shape[0]} rows, the scene has {self.n_vertices} vertices")
         out = dict(out) if out is not None else {}
@@ -1091,19 +971,16 @@ class Scene:
             raise ValueError(f"motion: out holds {extra}; the channels are {self.MOTION_CHANNELS}")
         device = torch.device("cuda", self.device)
         lead = (V,) if cameras is not None else ()
-        hstream, tstream = _stream_pair(stream, device)
-        res = {}
-        with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensors to the stream that writes them)
-            for c in self.MOTION_CHANNELS:
-                res[c] = _out_tensor(f"motion: out[{c!r}]", out.get(c), lead + (height, width) + (() if c == "prim" else (4,)), torch.int32 if c == "prim" else torch.float32, device)
+        hstream, _, *tensors = _outputs(stream, device, *((f"motion: out[{c!r}]", out.get(c), lead + (height, width) + (() if c == "prim" else (4,)),
+                                                           torch.int32 if c == "prim" else torch.float32) for c in self.MOTION_CHANNELS))
+        res = dict(zip(self.MOTION_CHANNELS, tensors))
         if V == 0:
             return res
-        ptr = lambda x: C.c_void_p(x.data_ptr() or None)
         p = _abi.MotionParams(C.sizeof(_abi.MotionParams), width, height, V)
-        bufs = _abi.MotionBuffers(C.sizeof(_abi.MotionBuffers), 0, ptr(res["motion"]), ptr(res["guide"]), ptr(res["prim"]))
+        bufs = _abi.MotionBuffers(C.sizeof(_abi.MotionBuffers), 0, _ptr(res["motion"]), _ptr(res["guide"]), _ptr(res["prim"]))
         cams = (Camera * V)(*cameras) if cameras else None
         prev = (Camera * V)(*prev_cameras)
-        _check(lib().gnxr_motion_device(self._h, C.byref(p), cams, prev, ptr(prev_vertices) if prev_vertices is not None else None, C.byref(bufs), C.c_void_p(hstream or None)))
+        _check(lib().gnxr_motion_device(self._h, C.byref(p), cams, prev, _ptr(prev_vertices), C.byref(bufs), _addr(hstream)))
         return res
 
 
@@ -1125,46 +1002,6 @@ def rays_tensor(o, d, tmax=float("inf")):
     return r
 
 
-def _stream_handle(what, stream):
-    """`stream` of the scene-editing calls -- None (the null stream), a torch.cuda.Stream or a hipStream_t as an integer -- as an int;
-    TypeError for anything else, ValueError for a negative handle, both before the library is reached."""
-    import numbers
-    if stream is None:
-        return 0
-    if isinstance(stream, numbers.Integral) and not isinstance(stream, bool):
-        handle = int(stream)
-    elif isinstance(getattr(stream, "cuda_stream", None), int):
-        handle = stream.cuda_stream   # a torch.cuda.Stream
-    else:
-        raise TypeError(f"{what}: stream must be None, a torch.cuda.Stream or a hipStream_t as an integer, got {type(stream).__name__}")
-    if handle < 0:
-        raise ValueError(f"{what}: a hipStream_t is not negative, got {handle}")
-    return handle
-
-
-def _stream_pair(stream, device):
-    """`stream` -- None (torch's current stream on `device`), a torch.cuda.Stream, or a hipStream_t as an int -- as the pair
-    (hipStream_t as an int, torch stream of that handle)."""
-    import torch
-    if stream is None:
-        stream = torch.cuda.current_stream(device)
-    elif isinstance(stream, int):
-        stream = torch.cuda.ExternalStream(stream, device=device)
-    return stream.cuda_stream, stream
-
-
-def _out_tensor(what, out, shape, dtype, device):
-    """The result tensor of a call on device memory: `out` when given -- it must be a contiguous `dtype` tensor of `shape` on `device`,
-    the device of the call's inputs or of its scene -- else a new one."""
-    import torch
-    if out is None:
-        return torch.empty(shape, dtype=dtype, device=device)
-    if not (isinstance(out, torch.Tensor) and out.device == device and out.dtype == dtype and tuple(out.shape) == tuple(shape) and out.is_contiguous()):
-        raise ValueError(f"{what} must be a contiguous {dtype} tensor of shape {tuple(shape)} on {device}, got "
-                         f"{type(out).__name__} {getattr(out, 'dtype', None)} {tuple(getattr(out, 'shape', ()))} on {getattr(out, 'device', None)}")
-    return out
-
-
 def _view_args(name, cameras, media, width, height):
     """The views of RenderViews / RenderAOV, checked: (list of Camera records -- None stays None --, list of media or None, width, height)"""
     if cameras is not None:
@@ -1176,19 +1013,7 @@ def _view_args(name, cameras, media, width, height):
             media = [int(m) for m in media]
             if len(media) != len(cameras):
                 raise ValueError(f"{name}: {len(media)} media for {len(cameras)} cameras")
-    width, height = int(width), int(height)
-    if width <= 0 or height <= 0:
-        raise ValueError(f"{name}: invalid image size {width} x {height}")
-    return cameras, media, width, height
-
-
-def _tensor_layout(what, x, dtype, cols):
-    """a contiguous (n, cols) tensor of `dtype` (on any device: Scene._device_tensor checks the device)"""
-    import torch
-    if not (isinstance(x, torch.Tensor) and x.dtype == dtype and x.dim() == 2 and x.shape[1] == cols and x.is_contiguous()):
-        raise ValueError(f"{what}: expected a contiguous {dtype} (n, {cols}) tensor, got "
-                         f"{type(x).__name__} {getattr(x, 'dtype', None)} {tuple(getattr(x, 'shape', ()))}")
-    return x
+    return (cameras, media) + _image_size(name, width, height)
 
 
 def li_samples(px, py, s, medium=-1):
@@ -1241,8 +1066,7 @@ class PathIntegrator:
     def __init__(self, maxDepth=5, rrThreshold=1.0, lightSampleStrategy="spatial"):
         self.maxDepth = int(maxDepth)
         self.rrThreshold = float(rrThreshold)
-        self.strategy = {"spatial": _abi.LIGHTS_SPATIAL, "uniform": _abi.LIGHTS_UNIFORM,
-                         "power": _abi.LIGHTS_POWER}.get(lightSampleStrategy, _abi.LIGHTS_SPATIAL)
+        self.strategy = LIGHT_STRATEGIES.get(lightSampleStrategy, _abi.LIGHTS_SPATIAL)
 
     def params(self, width, height, spp, spp_begin=0, spp_end=0, shard_index=0, shard_count=1, shard_rows=1,
                samples_per_pass=0, passes_in_flight=0):
@@ -1258,19 +1082,17 @@ class PathIntegrator:
         out of range raises GnxrError after the run and its row is 0.  Runs on `stream` (by default torch's current stream) and returns
         once L is written.  The other keyword arguments are Render's (samples_per_pass = paths per sub-pass, passes_in_flight)."""
         import torch
-        _tensor_layout("Li: rays", rays, torch.float32, 8)
-        _tensor_layout("Li: samples", samples, torch.int32, 4)
+        _expect("Li: rays", rays, torch.float32, (8,))
+        _expect("Li: samples", samples, torch.int32, (4,))
         n = rays.shape[0]
-        if samples.shape[0] != n:
-            raise ValueError(f"Li: {samples.shape[0]} sample records for {n} rays")
+        _same_count("Li", None, samples.shape[0], n, "rays", "sample records")
         out = _out_tensor("Li: out", out, (n, 4), torch.float32, rays.device)
-        scene._device_tensor("Li: rays", rays, torch.float32, 8)
-        scene._device_tensor("Li: samples", samples, torch.int32, 4)
+        _expect("Li: rays", rays, torch.float32, (8,), scene.device)
+        _expect("Li: samples", samples, torch.int32, (4,), scene.device)
         stream, _ = _stream_pair(stream, rays.device)
         p = self.params(width, height, spp, **kw)
         st = Stats()
-        _check(lib().gnxr_li_device(scene._h, C.byref(p), C.c_void_p(rays.data_ptr() or None), C.c_void_p(samples.data_ptr() or None), n,
-                                    C.c_void_p(out.data_ptr() or None), C.c_void_p(stream or None), C.byref(st)))
+        _check(lib().gnxr_li_device(scene._h, C.byref(p), _ptr(rays), _ptr(samples), n, _ptr(out), _addr(stream), C.byref(st)))
         return out, stats_dict(st)
 
     def RenderViews(self, scene, cameras, width, height, spp, media=None, out=None, stream=None, **kw):
@@ -1289,7 +1111,7 @@ class PathIntegrator:
         cams = (Camera * max(V, 1))(*cameras)
         med = (C.c_int32 * max(V, 1))(*media) if media is not None else None
         st = Stats()
-        _check(lib().gnxr_render_views_device(scene._h, C.byref(p), cams, med, V, C.c_void_p(out.data_ptr() or None), C.c_void_p(stream or None), C.byref(st)))
+        _check(lib().gnxr_render_views_device(scene._h, C.byref(p), cams, med, V, _ptr(out), _addr(stream), C.byref(st)))
         return out, stats_dict(st)
 
     def RenderAdaptive(self, scene, width, height, spp, threshold, min_spp=16, step_spp=16, floor=0.01, guard=1, out=None, count_out=None, stream=None, **kw):
@@ -1305,8 +1127,7 @@ class PathIntegrator:
         import torch
         width, height, spp, min_spp, step_spp, guard = int(width), int(height), int(spp), int(min_spp), int(step_spp), int(guard)
         threshold, floor = float(threshold), float(floor)
-        if width <= 0 or height <= 0:
-            raise ValueError(f"RenderAdaptive: invalid image size {width} x {height}")
+        _image_size("RenderAdaptive", width, height)
         if spp < 1 or not 1 <= min_spp <= spp:
             raise ValueError(f"RenderAdaptive: spp >= 1 and min_spp in [1, spp] are required, got spp = {spp}, min_spp = {min_spp}")
         if step_spp < 1:
@@ -1315,20 +1136,14 @@ class PathIntegrator:
             raise ValueError(f"RenderAdaptive: guard must lie in [0, 8], got {guard}")
         if math.isnan(threshold) or threshold < 0 or math.isnan(floor) or floor < 0:
             raise ValueError(f"RenderAdaptive: threshold and floor must be numbers >= 0, got {threshold} and {floor}")
-        unknown = [k for k in kw if k not in ("samples_per_pass", "passes_in_flight")]
-        if unknown:
-            raise ValueError(f"RenderAdaptive: unexpected arguments {unknown} (samples_per_pass, passes_in_flight)")
-        device = torch.device("cuda", scene.device)
-        hstream, tstream = _stream_pair(stream, device)
-        with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensors to the stream that writes them)
-            out = _out_tensor("RenderAdaptive: out", out, (height, width, 4), torch.float32, device)
-            count_out = _out_tensor("RenderAdaptive: count_out", count_out, (height, width), torch.int32, device)
+        _only_kw("RenderAdaptive", kw, ("samples_per_pass", "passes_in_flight"))
+        hstream, _, out, count_out = _outputs(stream, torch.device("cuda", scene.device), ("RenderAdaptive: out", out, (height, width, 4), torch.float32),
+                                              ("RenderAdaptive: count_out", count_out, (height, width), torch.int32))
         p = self.params(width, height, spp, **kw)
         ap = _abi.AdaptiveParams(C.sizeof(_abi.AdaptiveParams), min_spp, step_spp, guard, threshold, floor)
         info = _abi.AdaptiveInfo(C.sizeof(_abi.AdaptiveInfo), 0, 0, 0)
         st = Stats()
-        _check(lib().gnxr_render_adaptive_device(scene._h, C.byref(p), C.byref(ap), C.c_void_p(out.data_ptr() or None), C.c_void_p(count_out.data_ptr() or None),
-                                                 C.c_void_p(hstream or None), C.byref(st), C.byref(info)))
+        _check(lib().gnxr_render_adaptive_device(scene._h, C.byref(p), C.byref(ap), _ptr(out), _ptr(count_out), _addr(hstream), C.byref(st), C.byref(info)))
         stats = stats_dict(st)
         stats.update(rounds=info.rounds, samples=info.samples, pixels_at_budget=info.pixels_at_budget)
         return out, count_out, stats
@@ -1354,9 +1169,7 @@ class PathIntegrator:
             raise ValueError("RenderAOV: media goes with cameras; the scene's own camera sits in the scene's camera medium")
         cameras, media, width, height = _view_args("RenderAOV", cameras, media, width, height)
         V = len(cameras) if cameras is not None else 1
-        unknown = [k for k in kw if k not in ("spp_begin", "spp_end", "samples_per_pass")]
-        if unknown:
-            raise ValueError(f"RenderAOV: unexpected arguments {unknown} (spp_begin, spp_end, samples_per_pass)")
+        _only_kw("RenderAOV", kw, ("spp_begin", "spp_end", "samples_per_pass"))
         device = torch.device("cuda", scene.device)
         lead = (V,) if cameras is not None else ()
         shapes = {"albedo": (4,), "normal": (4,), "shading_normal": (4,), "depth": (), "ids": (2,)}
@@ -1364,19 +1177,15 @@ class PathIntegrator:
         extra = [c for c in out if c not in channels]
         if extra:
             raise ValueError(f"RenderAOV: out holds {extra}, which channels does not name")
-        hstream, tstream = _stream_pair(stream, device)
-        res = {}
-        with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensors to the stream that writes them)
-            for c in channels:
-                res[c] = _out_tensor(f"RenderAOV: out[{c!r}]", out.get(c), lead + (height, width) + shapes[c], torch.int32 if c == "ids" else torch.float32, device)
-        ptr = lambda c: C.c_void_p(res[c].data_ptr() or None) if c in res else None
-        bufs = _abi.AovBuffers(ptr("albedo"), ptr("normal"), ptr("shading_normal"), ptr("depth"), ptr("ids"))
+        hstream, _, *tensors = _outputs(stream, device, *((f"RenderAOV: out[{c!r}]", out.get(c), lead + (height, width) + shapes[c], torch.int32 if c == "ids" else torch.float32)
+                                                           for c in channels))
+        res = dict(zip(channels, tensors))
+        bufs = _abi.AovBuffers(*(_ptr(res.get(c)) for c in self.AOV_CHANNELS))
         p = self.params(width, height, spp, **kw)
         cams = (Camera * V)(*cameras) if cameras else None
         med = (C.c_int32 * V)(*media) if media else None
         st = Stats()
-        _check(lib().gnxr_render_aov_device(scene._h, C.byref(p), cams, med, V if cameras is not None else 1, C.byref(bufs), C.c_void_p(hstream or None),
-                                            C.byref(st)))
+        _check(lib().gnxr_render_aov_device(scene._h, C.byref(p), cams, med, V if cameras is not None else 1, C.byref(bufs), _addr(hstream), C.byref(st)))
         return res, stats_dict(st)
 
     def RenderDenoised(self, scene, width, height, spp, cameras=None, media=None, normal="shading_normal", stream=None, **denoise_kw):
@@ -1394,9 +1203,7 @@ class PathIntegrator:
             raise ValueError(f"RenderDenoised: normal must be 'shading_normal' or 'normal', got {normal!r}")
         if cameras is None and media is not None:
             raise ValueError("RenderDenoised: media goes with cameras; the scene's own camera sits in the scene's camera medium")
-        unknown = [k for k in denoise_kw if k not in ("iterations", "sigma_color", "sigma_normal", "sigma_depth", "out")]
-        if unknown:
-            raise ValueError(f"RenderDenoised: unexpected arguments {unknown} (iterations, sigma_color, sigma_normal, sigma_depth, out)")
+        _only_kw("RenderDenoised", denoise_kw, ("iterations", "sigma_color", "sigma_normal", "sigma_depth", "out"))
         cameras, media, width, height = _view_args("RenderDenoised", cameras, media, width, height)
         device = torch.device("cuda", scene.device)
         hstream, tstream = _stream_pair(stream, device)
@@ -1405,7 +1212,7 @@ class PathIntegrator:
             if cameras is not None:
                 img, st = self.RenderViews(scene, cameras, width, height, spp, media=media, stream=tstream, spp_begin=lo, spp_end=hi)
             else:
-                with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensor to the stream that writes it)
+                with torch.cuda.stream(tstream):
                     img = torch.zeros((height, width, 4), dtype=torch.float32, device=device)
                 st = self.RenderDevice(scene, img.data_ptr(), width, height, spp, stream=hstream, spp_begin=lo, spp_end=hi)
             halves.append(img)
@@ -1427,31 +1234,23 @@ class PathIntegrator:
         range leaves the bits of one render over both.  Runs on `stream` (by default torch's current stream) and returns once the
         outputs are written.  The other keyword arguments are Render's, without the shard fields."""
         import torch
-        if not isinstance(filter, _abi.FilmFilter):
-            raise ValueError(f"RenderFiltered: filter must be a film_filter(...) record, got {type(filter).__name__}")
+        _film_record("RenderFiltered", filter, "filter must be")
         if cameras is None and media is not None:
             raise ValueError("RenderFiltered: media goes with cameras; the scene's own camera sits in the scene's camera medium")
         cameras, media, width, height = _view_args("RenderFiltered", cameras, media, width, height)
         if resume and accum is None:
             raise ValueError("RenderFiltered: resume continues an accumulator: pass the tensor of the earlier call as accum")
-        unknown = [k for k in kw if k not in ("spp_begin", "spp_end", "samples_per_pass", "passes_in_flight")]
-        if unknown:
-            raise ValueError(f"RenderFiltered: unexpected arguments {unknown} (spp_begin, spp_end, samples_per_pass, passes_in_flight)")
+        _only_kw("RenderFiltered", kw, ("spp_begin", "spp_end", "samples_per_pass", "passes_in_flight"))
         V = len(cameras) if cameras is not None else 1
-        lead = (V,) if cameras is not None else ()
-        device = torch.device("cuda", scene.device)
-        hstream, tstream = _stream_pair(stream, device)
-        if accum is not None:
-            _out_tensor("RenderFiltered: accum", accum, lead + (height, width, 4), torch.float32, device)
-        with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensor to the stream that writes it)
-            out = _out_tensor("RenderFiltered: out", out, lead + (height, width, 4), torch.float32, device)
+        shape = ((V,) if cameras is not None else ()) + (height, width, 4)
+        given = [("RenderFiltered: accum", accum, shape, torch.float32)] if accum is not None else []   # (checked, never allocated)
+        hstream, *_, out = _outputs(stream, torch.device("cuda", scene.device), *given, ("RenderFiltered: out", out, shape, torch.float32))
         p = self.params(width, height, spp, **kw)
         cams = (Camera * V)(*cameras) if cameras else None
         med = (C.c_int32 * V)(*media) if media else None
         st = Stats()
-        _check(lib().gnxr_render_filtered_device(scene._h, C.byref(p), C.byref(filter), cams, med, V, C.c_void_p(out.data_ptr() or None),
-                                                 C.c_void_p(accum.data_ptr() or None) if accum is not None else None, _abi.FILM_CONTINUE if resume else 0,
-                                                 C.c_void_p(hstream or None), C.byref(st)))
+        _check(lib().gnxr_render_filtered_device(scene._h, C.byref(p), C.byref(filter), cams, med, V, _ptr(out), _ptr(accum), _abi.FILM_CONTINUE if resume else 0,
+                                                 _addr(hstream), C.byref(st)))
         return out, stats_dict(st)
 
     def BakeLightmap(self, scene, lm_uv, width, height, spp, dilate=2, flip=False, medium=-1, out=None, stream=None, **kw):
@@ -1464,23 +1263,16 @@ class PathIntegrator:
         texels * spp).  The live scene is read: a bake after an edit sees it.  Runs on `stream` (by default torch's current stream) and
         returns once the lightmap is written.  Keyword arguments: samples_per_pass (paths per sub-batch), passes_in_flight."""
         import torch
-        width, height = int(width), int(height)
-        if width <= 0 or height <= 0:
-            raise ValueError(f"BakeLightmap: invalid atlas size {width} x {height}")
+        width, height = _image_size("BakeLightmap", width, height, "atlas")
         if int(dilate) < 0:
             raise ValueError(f"BakeLightmap: dilate must be >= 0, got {dilate}")
-        unknown = [k for k in kw if k not in ("samples_per_pass", "passes_in_flight")]
-        if unknown:
-            raise ValueError(f"BakeLightmap: unexpected arguments {unknown} (samples_per_pass, passes_in_flight)")
+        _only_kw("BakeLightmap", kw, ("samples_per_pass", "passes_in_flight"))
         _bake_uv("BakeLightmap", scene, lm_uv)
-        hstream, tstream = _stream_pair(stream, lm_uv.device)
-        with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensor to the stream that writes it)
-            out = _out_tensor("BakeLightmap: out", out, (height, width, 4), torch.float32, lm_uv.device)
+        hstream, _, out = _outputs(stream, lm_uv.device, ("BakeLightmap: out", out, (height, width, 4), torch.float32))
         p = self.params(width, height, spp, **kw)
         bp = _abi.BakeParams(C.sizeof(_abi.BakeParams), _abi.BAKE_FLIP_NORMALS if flip else 0, int(dilate), int(medium))
         st = Stats()
-        _check(lib().gnxr_bake_lightmap_device(scene._h, C.byref(p), C.byref(bp), C.c_void_p(lm_uv.data_ptr() or None), C.c_void_p(out.data_ptr() or None),
-                                               C.c_void_p(hstream or None), C.byref(st)))
+        _check(lib().gnxr_bake_lightmap_device(scene._h, C.byref(p), C.byref(bp), _ptr(lm_uv), _ptr(out), _addr(hstream), C.byref(st)))
         return out, stats_dict(st)
 
     def BakeLightProbes(self, scene, positions, spp, width=None, height=None, medium=-1, out=None, stream=None, **kw):
@@ -1494,7 +1286,7 @@ class PathIntegrator:
         scene is read: a bake after an edit sees it.  Runs on `stream` (by default torch's current stream) and returns once the
         coefficients are written.  Keyword arguments: samples_per_pass (paths per sub-batch), passes_in_flight."""
         import torch
-        scene._device_tensor("BakeLightProbes: positions", positions, torch.float32, 3)
+        _expect("BakeLightProbes: positions", positions, torch.float32, (3,), scene.device)
         n = positions.shape[0]
         if width is None:
             width = max(1, min(n, 1024))
@@ -1504,17 +1296,12 @@ class PathIntegrator:
         height = int(height)
         if width <= 0 or height <= 0 or width * height < n:
             raise ValueError(f"BakeLightProbes: the {width} x {height} grid of pixels does not hold {n} probes")
-        unknown = [k for k in kw if k not in ("samples_per_pass", "passes_in_flight")]
-        if unknown:
-            raise ValueError(f"BakeLightProbes: unexpected arguments {unknown} (samples_per_pass, passes_in_flight)")
-        hstream, tstream = _stream_pair(stream, positions.device)
-        with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensor to the stream that writes it)
-            out = _out_tensor("BakeLightProbes: out", out, (n, 9, 4), torch.float32, positions.device)
+        _only_kw("BakeLightProbes", kw, ("samples_per_pass", "passes_in_flight"))
+        hstream, _, out = _outputs(stream, positions.device, ("BakeLightProbes: out", out, (n, 9, 4), torch.float32))
         p = self.params(width, height, spp, **kw)
         pp = _abi.LightprobeParams(C.sizeof(_abi.LightprobeParams), 0, int(medium))
         st = Stats()
-        _check(lib().gnxr_bake_lightprobes_device(scene._h, C.byref(p), C.byref(pp), C.c_void_p(positions.data_ptr() or None), n, C.c_void_p(out.data_ptr() or None),
-                                                  C.c_void_p(hstream or None), C.byref(st)))
+        _check(lib().gnxr_bake_lightprobes_device(scene._h, C.byref(p), C.byref(pp), _ptr(positions), n, _ptr(out), _addr(hstream), C.byref(st)))
         return out, stats_dict(st)
 
     def Render(self, scene, width, height, spp, **kw):
@@ -1595,24 +1382,15 @@ def camera_rays_device(camera, width, height, px, py, s, medium=-1, stream=None)
     samples [n, 4] int32 = px, py, s, medium): the two arrays integrator.Li takes.  o and d carry the bits of camera_rays.  Queued on
     `stream` (by default torch's current stream); a record outside the image or with s < 0 raises GnxrError, its row is 0."""
     import torch
-    n = None
-    for what, x in (("px", px), ("py", py), ("s", s)):
-        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.int32 and x.dim() == 1 and x.is_contiguous() and x.device == px.device):
-            raise ValueError(f"camera_rays_device: {what} must be a contiguous int32 (n,) tensor on one GPU, got "
-                             f"{type(x).__name__} {getattr(x, 'dtype', None)} {tuple(getattr(x, 'shape', ()))} on {getattr(x, 'device', None)}")
-        if n is None:
-            n = x.shape[0]
-        elif x.shape[0] != n:
-            raise ValueError(f"camera_rays_device: {what} has {x.shape[0]} entries for {n} px")
+    for what, x in (("px", px), ("py", py), ("s", s)):   # px on any GPU, the others where px is
+        if not _is_tensor(x, torch.int32, (None,), ANY_GPU if x is px else px.device):
+            _refuse(x, f"camera_rays_device: {what} must be a contiguous int32 (n,) tensor on one GPU")
+        _same_count("camera_rays_device", what, x.shape[0], px.shape[0], "px", "entries")
+    n = px.shape[0]
     if not isinstance(camera, Camera):
         raise ValueError(f"camera_rays_device: camera must be a gnxr Camera record (camera(...)), got {type(camera).__name__}")
-    st, tstream = _stream_pair(stream, px.device)
-    with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensors to the stream that writes them)
-        rays = torch.empty((n, 8), dtype=torch.float32, device=px.device)
-        samples = torch.empty((n, 4), dtype=torch.int32, device=px.device)
-    _check(lib().gnxr_camera_rays_device(C.byref(camera), int(medium), int(width), int(height), C.c_void_p(px.data_ptr() or None), C.c_void_p(py.data_ptr() or None),
-                                         C.c_void_p(s.data_ptr() or None), n, C.c_void_p(rays.data_ptr() or None), C.c_void_p(samples.data_ptr() or None),
-                                         C.c_void_p(st or None)))
+    st, _, rays, samples = _outputs(stream, px.device, ("camera_rays_device: rays", None, (n, 8), torch.float32), ("camera_rays_device: samples", None, (n, 4), torch.int32))
+    _check(lib().gnxr_camera_rays_device(C.byref(camera), int(medium), int(width), int(height), _ptr(px), _ptr(py), _ptr(s), n, _ptr(rays), _ptr(samples), _addr(st)))
     return rays, samples
 
 
@@ -1627,33 +1405,23 @@ def denoise(color, color_b=None, albedo=None, normal=None, depth=None, iteration
     `stream` (by default torch's current stream); the call does not wait for the GPU.  Malformed arguments raise ValueError."""
     import math
     import torch
-    if not (isinstance(color, torch.Tensor) and color.is_cuda and color.dtype == torch.float32 and color.dim() in (3, 4) and color.shape[-1] == 4 and color.is_contiguous()):
-        raise ValueError(f"denoise: color must be a contiguous float32 (H, W, 4) or (V, H, W, 4) tensor on a GPU, got "
-                         f"{type(color).__name__} {getattr(color, 'dtype', None)} {tuple(getattr(color, 'shape', ()))} on {getattr(color, 'device', None)}")
-    shape = tuple(color.shape)
+    shape, V, H, W = _image("denoise", "color", color, size=False)
     for what, x, want in (("color_b", color_b, shape), ("albedo", albedo, shape), ("normal", normal, shape), ("depth", depth, shape[:-1])):
-        if x is not None and not (isinstance(x, torch.Tensor) and x.device == color.device and x.dtype == torch.float32 and tuple(x.shape) == want and x.is_contiguous()):
-            raise ValueError(f"denoise: {what} must be a contiguous float32 tensor of shape {want} on {color.device}, got "
-                             f"{type(x).__name__} {getattr(x, 'dtype', None)} {tuple(getattr(x, 'shape', ()))} on {getattr(x, 'device', None)}")
-    H, W = shape[-3], shape[-2]
-    V = shape[0] if len(shape) == 4 else 1
-    if H < 1 or W < 1:
-        raise ValueError(f"denoise: invalid image size {W} x {H}")
+        if x is not None and not _is_tensor(x, torch.float32, want, color.device):
+            _refuse(x, f"denoise: {what} must be a contiguous float32 tensor of shape {want} on {color.device}")
+    _image_size("denoise", W, H)
     iterations = int(iterations)
     if not 1 <= iterations <= 8:
         raise ValueError(f"denoise: iterations must lie in [1, 8], got {iterations}")
     sigmas = [float(sigma_color), float(sigma_normal), float(sigma_depth)]
     if any(math.isnan(s) or s < 0 for s in sigmas):
         raise ValueError(f"denoise: the sigmas must be numbers >= 0, got {sigmas}")
-    hstream, tstream = _stream_pair(stream, color.device)
-    with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensor to the stream that writes it)
-        out = _out_tensor("denoise: out", out, shape, torch.float32, color.device)
+    hstream, _, out = _outputs(stream, color.device, ("denoise: out", out, shape, torch.float32))
     if V == 0:
         return out
-    ptr = lambda x: C.c_void_p(x.data_ptr() or None) if x is not None else None
     p = _abi.DenoiseParams(C.sizeof(_abi.DenoiseParams), W, H, V, iterations, *sigmas)
-    bufs = _abi.DenoiseBuffers(C.sizeof(_abi.DenoiseBuffers), 0, ptr(color), ptr(color_b), ptr(albedo), ptr(normal), ptr(depth))
-    _check(lib().gnxr_denoise_device(C.byref(p), C.byref(bufs), ptr(out), C.c_void_p(hstream or None)))
+    bufs = _abi.DenoiseBuffers(C.sizeof(_abi.DenoiseBuffers), 0, _ptr(color), _ptr(color_b), _ptr(albedo), _ptr(normal), _ptr(depth))
+    _check(lib().gnxr_denoise_device(C.byref(p), C.byref(bufs), _ptr(out), _addr(hstream)))
     return out
 
 
@@ -1696,9 +1464,9 @@ def film_filter(kind, radius, alpha=2.0, B=1 / 3, C=1 / 3, table=None):
     return f
 
 
-def _film_record(name, f):
+def _film_record(name, f, phrase="expected"):
     if not isinstance(f, _abi.FilmFilter):
-        raise ValueError(f"{name}: expected a film_filter(...) record, got {type(f).__name__}")
+        raise ValueError(f"{name}: {phrase} a film_filter(...) record, got {type(f).__name__}")
     return f
 
 
@@ -1711,19 +1479,6 @@ def film_filter_table(f):
     return out
 
 
-def _film_accum_shape(name, accum):
-    import torch
-    if not (isinstance(accum, torch.Tensor) and accum.is_cuda and accum.dtype == torch.float32 and accum.dim() in (3, 4) and accum.shape[-1] == 4 and accum.is_contiguous()):
-        raise ValueError(f"{name}: accum must be a contiguous float32 (H, W, 4) or (V, H, W, 4) tensor on a GPU, got "
-                         f"{type(accum).__name__} {getattr(accum, 'dtype', None)} {tuple(getattr(accum, 'shape', ()))} on {getattr(accum, 'device', None)}")
-    shape = tuple(accum.shape)
-    H, W = shape[-3], shape[-2]
-    V = shape[0] if len(shape) == 4 else 1
-    if H < 1 or W < 1:
-        raise ValueError(f"{name}: invalid image size {W} x {H}")
-    return shape, V, H, W
-
-
 def film_add(f, L, offsets, accum, stream=None):
     """Adds layers of samples to a film accumulator on device memory (gnxr_film_add_device): `accum` is a contiguous float32 tensor
     (H, W, 4) or (V, H, W, 4) of (Sr, Sg, Sb, Wt), `L` (n, *accum.shape) holds the sample of layer j that belongs to each pixel (w is
@@ -1733,20 +1488,16 @@ def film_add(f, L, offsets, accum, stream=None):
     stream); the call does not wait for the GPU.  Malformed arguments raise ValueError."""
     import torch
     _film_record("film_add", f)
-    shape, V, H, W = _film_accum_shape("film_add", accum)
-    ok = lambda x, tail: isinstance(x, torch.Tensor) and x.device == accum.device and x.dtype == torch.float32 and x.dim() == len(shape) + 1 and tuple(x.shape[1:]) == tail and x.is_contiguous()
-    if not ok(L, shape):
-        raise ValueError(f"film_add: L must be a contiguous float32 tensor of shape (n, {', '.join(map(str, shape))}) on {accum.device}, got "
-                         f"{type(L).__name__} {getattr(L, 'dtype', None)} {tuple(getattr(L, 'shape', ()))} on {getattr(L, 'device', None)}")
-    if not ok(offsets, shape[:-1] + (2,)) or offsets.shape[0] != L.shape[0]:
-        raise ValueError(f"film_add: offsets must be a contiguous float32 tensor of shape ({L.shape[0]}, {', '.join(map(str, shape[:-1]))}, 2) on {accum.device}, got "
-                         f"{type(offsets).__name__} {getattr(offsets, 'dtype', None)} {tuple(getattr(offsets, 'shape', ()))} on {getattr(offsets, 'device', None)}")
+    shape, V, H, W = _image("film_add", "accum", accum)
+    if not _is_tensor(L, torch.float32, (None,) + shape, accum.device):
+        _refuse(L, f"film_add: L must be a contiguous float32 tensor of shape (n, {', '.join(map(str, shape))}) on {accum.device}")
     n = L.shape[0]
+    if not _is_tensor(offsets, torch.float32, (n,) + shape[:-1] + (2,), accum.device):
+        _refuse(offsets, f"film_add: offsets must be a contiguous float32 tensor of shape ({n}, {', '.join(map(str, shape[:-1]))}, 2) on {accum.device}")
     if V == 0 or n == 0:
         return accum
     hstream, _ = _stream_pair(stream, accum.device)
-    _check(lib().gnxr_film_add_device(C.byref(f), W, H, V, n, C.c_void_p(L.data_ptr() or None), C.c_void_p(offsets.data_ptr() or None), C.c_void_p(accum.data_ptr() or None),
-                                      C.c_void_p(hstream or None)))
+    _check(lib().gnxr_film_add_device(C.byref(f), W, H, V, n, _ptr(L), _ptr(offsets), _ptr(accum), _addr(hstream)))
     return accum
 
 
@@ -1755,22 +1506,19 @@ def film_resolve(accum, out=None, stream=None):
     or the quotient is negative.  `accum`: as for film_add.  Returns the float32 tensor of accum's shape: `out` when given, which may
     be `accum` itself.  Queued on `stream` (by default torch's current stream); the call does not wait for the GPU."""
     import torch
-    shape, V, H, W = _film_accum_shape("film_resolve", accum)
-    hstream, tstream = _stream_pair(stream, accum.device)
-    with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensor to the stream that writes it)
-        out = _out_tensor("film_resolve: out", out, shape, torch.float32, accum.device)
+    shape, V, H, W = _image("film_resolve", "accum", accum)
+    hstream, _, out = _outputs(stream, accum.device, ("film_resolve: out", out, shape, torch.float32))
     if V == 0:
         return out
-    _check(lib().gnxr_film_resolve_device(W, H, V, C.c_void_p(accum.data_ptr() or None), C.c_void_p(out.data_ptr() or None), C.c_void_p(hstream or None)))
+    _check(lib().gnxr_film_resolve_device(W, H, V, _ptr(accum), _ptr(out), _addr(hstream)))
     return out
 
 
 def _bake_uv(name, scene, lm_uv):
     """the lightmap uv set of the baking calls: a contiguous float32 (n_triangles, 6) tensor on the scene's device"""
     import torch
-    scene._device_tensor(f"{name}: lm_uv", lm_uv, torch.float32, 6)
-    if lm_uv.shape[0] != scene.n_triangles:
-        raise ValueError(f"{name}: lm_uv has {lm_uv.shape[0]} rows for {scene.n_triangles} triangles")
+    _expect(f"{name}: lm_uv", lm_uv, torch.float32, (6,), scene.device)
+    _same_count(name, "lm_uv", lm_uv.shape[0], scene.n_triangles, "triangles")
     return lm_uv
 
 
@@ -1781,17 +1529,11 @@ def bake_texels(scene, lm_uv, width, height, out=None, stream=None):
     (H, W, 2) tensor of its barycentrics (b1, b2) there.  `out`: a (tri, bary) pair to write into.  Queued on `stream` (by default
     torch's current stream); the call does not wait for the GPU."""
     import torch
-    width, height = int(width), int(height)
-    if width <= 0 or height <= 0:
-        raise ValueError(f"bake_texels: invalid atlas size {width} x {height}")
+    width, height = _image_size("bake_texels", width, height, "atlas")
     _bake_uv("bake_texels", scene, lm_uv)
-    hstream, tstream = _stream_pair(stream, lm_uv.device)
     out_tri, out_bary = out if out is not None else (None, None)
-    with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensors to the stream that writes them)
-        tri = _out_tensor("bake_texels: out[0]", out_tri, (height, width), torch.int32, lm_uv.device)
-        bary = _out_tensor("bake_texels: out[1]", out_bary, (height, width, 2), torch.float32, lm_uv.device)
-    _check(lib().gnxr_bake_texels_device(scene._h, C.c_void_p(lm_uv.data_ptr() or None), width, height, C.c_void_p(tri.data_ptr() or None),
-                                         C.c_void_p(bary.data_ptr() or None), C.c_void_p(hstream or None)))
+    hstream, _, tri, bary = _outputs(stream, lm_uv.device, ("bake_texels: out[0]", out_tri, (height, width), torch.int32), ("bake_texels: out[1]", out_bary, (height, width, 2), torch.float32))
+    _check(lib().gnxr_bake_texels_device(scene._h, _ptr(lm_uv), width, height, _ptr(tri), _ptr(bary), _addr(hstream)))
     return tri, bary
 
 
@@ -1805,24 +1547,18 @@ def surface_rays(scene, tri, bary, px, py, s, width, height, flip=False, medium=
     pn) triple to write into.  A degenerate triangle gives zero rows; a triangle, pixel or sample out of range raises GnxrError after the
     others are finished, its rows are 0.  Queued on `stream` (by default torch's current stream)."""
     import torch
-    scene._device_tensor("surface_rays: tri", tri, torch.int32, 0)
+    _expect("surface_rays: tri", tri, torch.int32, (), scene.device)
     n = tri.shape[0]
-    scene._device_tensor("surface_rays: bary", bary, torch.float32, 2)
+    _expect("surface_rays: bary", bary, torch.float32, (2,), scene.device)
     for what, x in (("px", px), ("py", py), ("s", s)):
-        scene._device_tensor(f"surface_rays: {what}", x, torch.int32, 0)
-        if x.shape[0] != n:
-            raise ValueError(f"surface_rays: {what} has {x.shape[0]} entries for {n} triangles")
-    if bary.shape[0] != n:
-        raise ValueError(f"surface_rays: bary has {bary.shape[0]} rows for {n} triangles")
-    hstream, tstream = _stream_pair(stream, tri.device)
+        _expect(f"surface_rays: {what}", x, torch.int32, (), scene.device)
+        _same_count("surface_rays", what, x.shape[0], n, "triangles", "entries")
+    _same_count("surface_rays", "bary", bary.shape[0], n, "triangles")
     o_rays, o_samples, o_pn = out if out is not None else (None, None, None)
-    with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensors to the stream that writes them)
-        rays = _out_tensor("surface_rays: out[0]", o_rays, (n, 8), torch.float32, tri.device)
-        samples = _out_tensor("surface_rays: out[1]", o_samples, (n, 4), torch.int32, tri.device)
-        pn = _out_tensor("surface_rays: out[2]", o_pn, (n, 8), torch.float32, tri.device)
-    ptr = lambda x: C.c_void_p(x.data_ptr() or None)
-    _check(lib().gnxr_surface_rays_device(scene._h, int(width), int(height), ptr(tri), ptr(bary), ptr(px), ptr(py), ptr(s), n, _abi.BAKE_FLIP_NORMALS if flip else 0,
-                                          int(medium), ptr(rays), ptr(samples), ptr(pn), C.c_void_p(hstream or None)))
+    hstream, _, rays, samples, pn = _outputs(stream, tri.device, ("surface_rays: out[0]", o_rays, (n, 8), torch.float32), ("surface_rays: out[1]", o_samples, (n, 4), torch.int32),
+                                             ("surface_rays: out[2]", o_pn, (n, 8), torch.float32))
+    _check(lib().gnxr_surface_rays_device(scene._h, int(width), int(height), _ptr(tri), _ptr(bary), _ptr(px), _ptr(py), _ptr(s), n, _abi.BAKE_FLIP_NORMALS if flip else 0,
+                                          int(medium), _ptr(rays), _ptr(samples), _ptr(pn), _addr(hstream)))
     return rays, samples, pn
 
 
@@ -1832,32 +1568,18 @@ def bake_dilate(img, iterations, out=None, stream=None):
     8-neighbours the mean of their rgb; alpha is never changed.  Returns the dilated tensor: `out` when given, which may be `img` (in
     place).  Queued on `stream` (by default torch's current stream); the call does not wait for the GPU."""
     import torch
-    if not (isinstance(img, torch.Tensor) and img.is_cuda and img.dtype == torch.float32 and img.dim() == 3 and img.shape[-1] == 4 and img.is_contiguous()):
-        raise ValueError(f"bake_dilate: img must be a contiguous float32 (H, W, 4) tensor on a GPU, got "
-                         f"{type(img).__name__} {getattr(img, 'dtype', None)} {tuple(getattr(img, 'shape', ()))} on {getattr(img, 'device', None)}")
-    H, W = img.shape[0], img.shape[1]
-    if H < 1 or W < 1:
-        raise ValueError(f"bake_dilate: invalid image size {W} x {H}")
+    if not _is_tensor(img, torch.float32, (None, None, 4), ANY_GPU):
+        _refuse(img, "bake_dilate: img must be a contiguous float32 (H, W, 4) tensor on a GPU")
+    W, H = _image_size("bake_dilate", img.shape[1], img.shape[0])
     iterations = int(iterations)
     if iterations < 0:
         raise ValueError(f"bake_dilate: iterations must be >= 0, got {iterations}")
-    hstream, tstream = _stream_pair(stream, img.device)
-    with torch.cuda.stream(tstream):
-        out = _out_tensor("bake_dilate: out", out, tuple(img.shape), torch.float32, img.device)
-        if out.data_ptr() != img.data_ptr():
+    hstream, tstream, out = _outputs(stream, img.device, ("bake_dilate: out", out, tuple(img.shape), torch.float32))
+    if out.data_ptr() != img.data_ptr():
+        with torch.cuda.stream(tstream):
             out.copy_(img)
-    _check(lib().gnxr_bake_dilate_device(W, H, iterations, C.c_void_p(out.data_ptr() or None), C.c_void_p(hstream or None)))
+    _check(lib().gnxr_bake_dilate_device(W, H, iterations, _ptr(out), _addr(hstream)))
     return out
-
-
-def _gpu_tensor(what, x, dtype, tail, device=None):
-    """an argument of the light-probe calls that take no scene: a contiguous `dtype` tensor (n, *tail) on a GPU (on `device` when given)"""
-    import torch
-    if not (isinstance(x, torch.Tensor) and x.is_cuda and (device is None or x.device == device) and x.dtype == dtype and x.dim() == 1 + len(tail) and
-            tuple(x.shape[1:]) == tuple(tail) and x.is_contiguous()):
-        raise ValueError(f"{what}: expected a contiguous {dtype} (n{''.join(', %d' % c for c in tail)}) tensor on {device or 'a GPU'}, got "
-                         f"{type(x).__name__} {getattr(x, 'dtype', None)} {tuple(getattr(x, 'shape', ()))} on {getattr(x, 'device', None)}")
-    return x
 
 
 def lightprobe_rays(scene, pos, px, py, s, width, height, medium=-1, out=None, stream=None):
@@ -1868,22 +1590,15 @@ def lightprobe_rays(scene, pos, px, py, s, width, height, medium=-1, out=None, s
     `out`: a (rays, samples) pair to write into.  A non-finite position, a pixel outside the image or s < 0 raises GnxrError after the
     others are finished, its rows are 0.  Queued on `stream` (by default torch's current stream)."""
     import torch
-    scene._device_tensor("lightprobe_rays: pos", pos, torch.float32, 3)
+    _expect("lightprobe_rays: pos", pos, torch.float32, (3,), scene.device)
     n = pos.shape[0]
     for what, x in (("px", px), ("py", py), ("s", s)):
-        scene._device_tensor(f"lightprobe_rays: {what}", x, torch.int32, 0)
-        if x.shape[0] != n:
-            raise ValueError(f"lightprobe_rays: {what} has {x.shape[0]} entries for {n} positions")
-    width, height = int(width), int(height)
-    if width <= 0 or height <= 0:
-        raise ValueError(f"lightprobe_rays: invalid image size {width} x {height}")
-    hstream, tstream = _stream_pair(stream, pos.device)
+        _expect(f"lightprobe_rays: {what}", x, torch.int32, (), scene.device)
+        _same_count("lightprobe_rays", what, x.shape[0], n, "positions", "entries")
+    width, height = _image_size("lightprobe_rays", width, height)
     o_rays, o_samples = out if out is not None else (None, None)
-    with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensors to the stream that writes them)
-        rays = _out_tensor("lightprobe_rays: out[0]", o_rays, (n, 8), torch.float32, pos.device)
-        samples = _out_tensor("lightprobe_rays: out[1]", o_samples, (n, 4), torch.int32, pos.device)
-    ptr = lambda x: C.c_void_p(x.data_ptr() or None)
-    _check(lib().gnxr_lightprobe_rays_device(scene._h, width, height, ptr(pos), ptr(px), ptr(py), ptr(s), n, int(medium), ptr(rays), ptr(samples), C.c_void_p(hstream or None)))
+    hstream, _, rays, samples = _outputs(stream, pos.device, ("lightprobe_rays: out[0]", o_rays, (n, 8), torch.float32), ("lightprobe_rays: out[1]", o_samples, (n, 4), torch.int32))
+    _check(lib().gnxr_lightprobe_rays_device(scene._h, width, height, _ptr(pos), _ptr(px), _ptr(py), _ptr(s), n, int(medium), _ptr(rays), _ptr(samples), _addr(hstream)))
     return rays, samples
 
 
@@ -1895,23 +1610,19 @@ def sh_project(rays, L, n_probes, out=None, accumulate=False, stream=None):
     `accumulate` the sums continue from what `out` holds: the samples of a probe may then come in several calls, whole blocks of 64 in
     every call but the last.  Queued on `stream` (by default torch's current stream); the call does not wait for the GPU."""
     import torch
-    _gpu_tensor("sh_project: rays", rays, torch.float32, (8,))
-    _gpu_tensor("sh_project: L", L, torch.float32, (4,), rays.device)
+    _expect("sh_project: rays", rays, torch.float32, (8,), ANY_GPU)
+    _expect("sh_project: L", L, torch.float32, (4,), rays.device)
     n_probes = int(n_probes)
     n = rays.shape[0]
-    if L.shape[0] != n:
-        raise ValueError(f"sh_project: L has {L.shape[0]} rows for {n} rays")
+    _same_count("sh_project", "L", L.shape[0], n, "rays")
     if n_probes < 0 or (n_probes == 0 and n != 0) or (n_probes > 0 and n % n_probes != 0):
         raise ValueError(f"sh_project: {n} records are no whole number of samples for each of {n_probes} probes")
     if accumulate and out is None:
         raise ValueError("sh_project: accumulate continues the sums of an earlier call: pass its tensor as out")
-    hstream, tstream = _stream_pair(stream, rays.device)
-    with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensor to the stream that writes it)
-        out = _out_tensor("sh_project: out", out, (n_probes, 9, 4), torch.float32, rays.device)
+    hstream, _, out = _outputs(stream, rays.device, ("sh_project: out", out, (n_probes, 9, 4), torch.float32))
     if n_probes == 0:
         return out
-    ptr = lambda x: C.c_void_p(x.data_ptr() or None)
-    _check(lib().gnxr_sh_project_device(ptr(rays), ptr(L), n_probes, n // n_probes, ptr(out), _abi.SH_CONTINUE if accumulate else 0, C.c_void_p(hstream or None)))
+    _check(lib().gnxr_sh_project_device(_ptr(rays), _ptr(L), n_probes, n // n_probes, _ptr(out), _abi.SH_CONTINUE if accumulate else 0, _addr(hstream)))
     return out
 
 
@@ -1922,19 +1633,15 @@ def sh_irradiance(sh, probe, normals, out=None, stream=None):
     probe[i] gives a surface facing normals[i]: `out` when given.  A probe index out of range raises GnxrError after the others are
     finished, its row is 0.  Queued on `stream` (by default torch's current stream)."""
     import torch
-    _gpu_tensor("sh_irradiance: sh", sh, torch.float32, (9, 4))
-    _gpu_tensor("sh_irradiance: probe", probe, torch.int32, (), sh.device)
-    _gpu_tensor("sh_irradiance: normals", normals, torch.float32, (3,), sh.device)
+    _expect("sh_irradiance: sh", sh, torch.float32, (9, 4), ANY_GPU)
+    _expect("sh_irradiance: probe", probe, torch.int32, (), sh.device)
+    _expect("sh_irradiance: normals", normals, torch.float32, (3,), sh.device)
     n = probe.shape[0]
-    if normals.shape[0] != n:
-        raise ValueError(f"sh_irradiance: normals has {normals.shape[0]} rows for {n} probe indices")
-    hstream, tstream = _stream_pair(stream, sh.device)
-    with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensor to the stream that writes it)
-        out = _out_tensor("sh_irradiance: out", out, (n, 4), torch.float32, sh.device)
+    _same_count("sh_irradiance", "normals", normals.shape[0], n, "probe indices")
+    hstream, _, out = _outputs(stream, sh.device, ("sh_irradiance: out", out, (n, 4), torch.float32))
     if n == 0:
         return out
-    ptr = lambda x: C.c_void_p(x.data_ptr() or None)
-    _check(lib().gnxr_sh_irradiance_device(ptr(sh), sh.shape[0], ptr(probe), ptr(normals), n, ptr(out), C.c_void_p(hstream or None)))
+    _check(lib().gnxr_sh_irradiance_device(_ptr(sh), sh.shape[0], _ptr(probe), _ptr(normals), n, _ptr(out), _addr(hstream)))
     return out
 
 
@@ -1963,17 +1670,12 @@ def temporal_accumulate(color, motion, guide, prim, history=None, max_history=32
     Malformed arguments raise ValueError."""
     import math
     import torch
-    if not (isinstance(color, torch.Tensor) and color.is_cuda and color.dtype == torch.float32 and color.dim() in (3, 4) and color.shape[-1] == 4 and color.is_contiguous()):
-        raise ValueError(f"temporal_accumulate: color must be a contiguous float32 (H, W, 4) or (V, H, W, 4) tensor on a GPU, got "
-                         f"{type(color).__name__} {getattr(color, 'dtype', None)} {tuple(getattr(color, 'shape', ()))} on {getattr(color, 'device', None)}")
-    shape = tuple(color.shape)
+    shape, V, H, W = _image("temporal_accumulate", "color", color, size=False)
 
     def layout(what, x, prim_like):
         want, dtype = (shape[:-1], torch.int32) if prim_like else (shape, torch.float32)
-        if not (isinstance(x, torch.Tensor) and x.device == color.device and x.dtype == dtype and tuple(x.shape) == want and x.is_contiguous()):
-            raise ValueError(f"temporal_accumulate: {what} must be a contiguous {dtype} tensor of shape {want} on {color.device}, got "
-                             f"{type(x).__name__} {getattr(x, 'dtype', None)} {tuple(getattr(x, 'shape', ()))} on {getattr(x, 'device', None)}")
-        return x
+        if not _is_tensor(x, dtype, want, color.device):
+            _refuse(x, f"temporal_accumulate: {what} must be a contiguous {dtype} tensor of shape {want} on {color.device}")
 
     layout("motion", motion, False); layout("guide", guide, False); layout("prim", prim, True)
     if history is not None:
@@ -1981,10 +1683,7 @@ def temporal_accumulate(color, motion, guide, prim, history=None, max_history=32
             raise ValueError("temporal_accumulate: history must be None or a dict with 'color', 'stat', 'guide' and 'prim' (what an earlier call returned)")
         for k in ("color", "stat", "guide", "prim"):
             layout(f"history[{k!r}]", history[k], k == "prim")
-    H, W = shape[-3], shape[-2]
-    V = shape[0] if len(shape) == 4 else 1
-    if H < 1 or W < 1:
-        raise ValueError(f"temporal_accumulate: invalid image size {W} x {H}")
+    _image_size("temporal_accumulate", W, H)
     max_history, depth_tol, normal_cos = int(max_history), float(depth_tol), float(normal_cos)
     if max_history < 1:
         raise ValueError(f"temporal_accumulate: max_history must be at least 1, got {max_history}")
@@ -1994,20 +1693,16 @@ def temporal_accumulate(color, motion, guide, prim, history=None, max_history=32
     extra = [k for k in out if k not in ("color", "stat")]
     if extra:
         raise ValueError(f"temporal_accumulate: out holds {extra}; the outputs are 'color' and 'stat'")
-    hstream, tstream = _stream_pair(stream, color.device)
-    with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensors to the stream that writes them)
-        o_color = _out_tensor("temporal_accumulate: out['color']", out.get("color"), shape, torch.float32, color.device)
-        o_stat = _out_tensor("temporal_accumulate: out['stat']", out.get("stat"), shape, torch.float32, color.device)
+    hstream, _, o_color, o_stat = _outputs(stream, color.device, ("temporal_accumulate: out['color']", out.get("color"), shape, torch.float32),
+                                           ("temporal_accumulate: out['stat']", out.get("stat"), shape, torch.float32))
     res = {"color": o_color, "stat": o_stat, "guide": guide, "prim": prim}
     if V == 0:
         return res
-    ptr = lambda x: C.c_void_p(x.data_ptr() or None)
     h = history or {}
-    hptr = lambda k: ptr(h[k]) if h else None
     p = _abi.TemporalParams(C.sizeof(_abi.TemporalParams), W, H, V, max_history, depth_tol, normal_cos)
-    bufs = _abi.TemporalBuffers(C.sizeof(_abi.TemporalBuffers), 0, ptr(color), ptr(motion), ptr(guide), ptr(prim), hptr("color"), hptr("stat"), hptr("guide"), hptr("prim"),
-                                ptr(o_color), ptr(o_stat))
-    _check(lib().gnxr_temporal_accumulate_device(C.byref(p), C.byref(bufs), C.c_void_p(hstream or None)))
+    bufs = _abi.TemporalBuffers(C.sizeof(_abi.TemporalBuffers), 0, _ptr(color), _ptr(motion), _ptr(guide), _ptr(prim), _ptr(h.get("color")), _ptr(h.get("stat")), _ptr(h.get("guide")),
+                                _ptr(h.get("prim")), _ptr(o_color), _ptr(o_stat))
+    _check(lib().gnxr_temporal_accumulate_device(C.byref(p), C.byref(bufs), _addr(hstream)))
     return res
 
 
@@ -2030,13 +1725,10 @@ class TemporalAccumulator:
 
     def __init__(self, integrator, scene, width, height, spp, max_history=32, **accumulate_kw):
         width, height, spp, max_history = int(width), int(height), int(spp), int(max_history)
-        if width <= 0 or height <= 0:
-            raise ValueError(f"TemporalAccumulator: invalid image size {width} x {height}")
+        _image_size("TemporalAccumulator", width, height)
         if spp < 1 or max_history < 1:
             raise ValueError(f"TemporalAccumulator: spp and max_history must be at least 1, got {spp} and {max_history}")
-        unknown = [k for k in accumulate_kw if k not in ("depth_tol", "normal_cos")]
-        if unknown:
-            raise ValueError(f"TemporalAccumulator: unexpected arguments {unknown} (depth_tol, normal_cos)")
+        _only_kw("TemporalAccumulator", accumulate_kw, ("depth_tol", "normal_cos"))
         self.integrator, self.scene, self.width, self.height, self.spp, self.max_history = integrator, scene, width, height, spp, max_history
         self.accumulate_kw = dict(accumulate_kw)
         self.reset()
@@ -2063,7 +1755,7 @@ class TemporalAccumulator:
         C.memmove(C.byref(cam), C.byref(scene.camera), C.sizeof(Camera))
         device = torch.device("cuda", scene.device)
         hstream, tstream = _stream_pair(stream, device)
-        with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensor to the stream that writes it)
+        with torch.cuda.stream(tstream):
             img = torch.zeros((H, W, 4), dtype=torch.float32, device=device)
         lo = (self.k % M) * self.spp
         self.integrator.RenderDevice(scene, img.data_ptr(), W, H, M * self.spp, stream=hstream, spp_begin=lo, spp_end=lo + self.spp)
@@ -2091,14 +1783,11 @@ def skin_vertices(rest, bone_index, bone_weight, bones, morph_delta=None, morph_
     torch's current stream)."""
     import torch
     name = "skin_vertices"
-    _gpu_tensor(f"{name}: rest", rest, torch.float32, (3,))
+    _expect(f"{name}: rest", rest, torch.float32, (3,), ANY_GPU)
     dev, V = rest.device, rest.shape[0]
-    _gpu_tensor(f"{name}: bone_index", bone_index, torch.int32, (4,), dev)
-    _gpu_tensor(f"{name}: bone_weight", bone_weight, torch.float32, (4,), dev)
-    if isinstance(bones, torch.Tensor) and bones.dim() == 3:
-        _gpu_tensor(f"{name}: bones", bones, torch.float32, (3, 4), dev)
-    else:
-        _gpu_tensor(f"{name}: bones", bones, torch.float32, (12,), dev)
+    _expect(f"{name}: bone_index", bone_index, torch.int32, (4,), dev)
+    _expect(f"{name}: bone_weight", bone_weight, torch.float32, (4,), dev)
+    _expect(f"{name}: bones", bones, torch.float32, (3, 4) if isinstance(bones, torch.Tensor) and bones.dim() == 3 else (12,), dev)
     if bone_index.shape[0] != V or bone_weight.shape[0] != V:
         raise ValueError(f"{name}: {V} rest positions, {bone_index.shape[0]} index rows, {bone_weight.shape[0]} weight rows")
     if bones.shape[0] < 1:
@@ -2107,18 +1796,15 @@ def skin_vertices(rest, bone_index, bone_weight, bones, morph_delta=None, morph_
         raise ValueError(f"{name}: morph_delta and morph_weight come together or not at all")
     M = 0
     if morph_delta is not None:
-        _gpu_tensor(f"{name}: morph_delta", morph_delta, torch.float32, (V, 3), dev)
-        _gpu_tensor(f"{name}: morph_weight", morph_weight, torch.float32, (), dev)
+        _expect(f"{name}: morph_delta", morph_delta, torch.float32, (V, 3), dev)
+        _expect(f"{name}: morph_weight", morph_weight, torch.float32, (), dev)
         M = morph_delta.shape[0]
         if morph_weight.shape[0] != M:
             raise ValueError(f"{name}: {M} morph targets, {morph_weight.shape[0]} weights")
-    hstream, tstream = _stream_pair(stream, dev)
-    with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensor to the stream that writes it)
-        res = _out_tensor(f"{name}: out", out, (V, 3), torch.float32, dev)
-    ptr = lambda x: C.c_void_p(x.data_ptr() or None)
+    hstream, _, res = _outputs(stream, dev, (f"{name}: out", out, (V, 3), torch.float32))
     p = _abi.SkinParams(C.sizeof(_abi.SkinParams), V, int(bones.shape[0]), M)
-    _check(lib().gnxr_skin_vertices_device(C.byref(p), ptr(rest), ptr(bone_index), ptr(bone_weight), ptr(bones), ptr(morph_delta) if M else None,
-                                           ptr(morph_weight) if M else None, ptr(res), C.c_void_p(hstream or None)))
+    _check(lib().gnxr_skin_vertices_device(C.byref(p), _ptr(rest), _ptr(bone_index), _ptr(bone_weight), _ptr(bones), _ptr(morph_delta) if M else None,
+                                           _ptr(morph_weight) if M else None, _ptr(res), _addr(hstream)))
     return res
 
 
@@ -2160,19 +1846,6 @@ class SkinnedMesh:
         return self.prev_vertices
 
 
-def _display_image(name, color):
-    """`color` of the display calls, checked: (shape, V, H, W)"""
-    import torch
-    if not (isinstance(color, torch.Tensor) and color.is_cuda and color.dtype == torch.float32 and color.dim() in (3, 4) and color.shape[-1] == 4 and color.is_contiguous()):
-        raise ValueError(f"{name}: color must be a contiguous float32 (H, W, 4) or (V, H, W, 4) tensor on a GPU, got "
-                         f"{type(color).__name__} {getattr(color, 'dtype', None)} {tuple(getattr(color, 'shape', ()))} on {getattr(color, 'device', None)}")
-    shape = tuple(color.shape)
-    H, W = shape[-3], shape[-2]
-    if H < 1 or W < 1:
-        raise ValueError(f"{name}: invalid image size {W} x {H}")
-    return shape, (shape[0] if len(shape) == 4 else 1), H, W
-
-
 def _min_log2(name, min_log2):
     min_log2 = int(min_log2)
     if not -126 <= min_log2 <= 111:
@@ -2187,15 +1860,13 @@ def luminance_histogram(color, min_log2=-12, out=None, stream=None):
     above it, not finite, and a 0.  The counts are exact: the bin comes from the bit pattern of the luminance.  Queued on `stream` (by
     default torch's current stream); the call does not wait for the GPU.  Malformed arguments raise ValueError."""
     import torch
-    shape, V, H, W = _display_image("luminance_histogram", color)
+    shape, V, H, W = _image("luminance_histogram", "color", color)
     min_log2 = _min_log2("luminance_histogram", min_log2)
-    hstream, tstream = _stream_pair(stream, color.device)
-    with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensor to the stream that writes it)
-        out = _out_tensor("luminance_histogram: out", out, (V, _abi.HISTOGRAM_WORDS), torch.int32, color.device)
+    hstream, _, out = _outputs(stream, color.device, ("luminance_histogram: out", out, (V, _abi.HISTOGRAM_WORDS), torch.int32))
     if V == 0:
         return out
     p = _abi.HistogramParams(C.sizeof(_abi.HistogramParams), W, H, V, min_log2)
-    _check(lib().gnxr_luminance_histogram_device(C.byref(p), C.c_void_p(color.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(hstream or None)))
+    _check(lib().gnxr_luminance_histogram_device(C.byref(p), _ptr(color), _ptr(out), _addr(hstream)))
     return out
 
 
@@ -2210,13 +1881,11 @@ def auto_exposure(hist, prev=None, key=0.18, low=0.5, high=0.95, rate=1.0, min_e
     torch's current stream); the call does not wait for the GPU.  Malformed arguments raise ValueError."""
     import math
     import torch
-    if not (isinstance(hist, torch.Tensor) and hist.is_cuda and hist.dtype == torch.int32 and hist.dim() == 2 and hist.shape[1] == _abi.HISTOGRAM_WORDS and hist.is_contiguous()):
-        raise ValueError(f"auto_exposure: hist must be a contiguous int32 (V, {_abi.HISTOGRAM_WORDS}) tensor on a GPU (luminance_histogram), got "
-                         f"{type(hist).__name__} {getattr(hist, 'dtype', None)} {tuple(getattr(hist, 'shape', ()))} on {getattr(hist, 'device', None)}")
+    if not _is_tensor(hist, torch.int32, (None, _abi.HISTOGRAM_WORDS), ANY_GPU):
+        _refuse(hist, f"auto_exposure: hist must be a contiguous int32 (V, {_abi.HISTOGRAM_WORDS}) tensor on a GPU (luminance_histogram)")
     V = hist.shape[0]
-    if prev is not None and not (isinstance(prev, torch.Tensor) and prev.device == hist.device and prev.dtype == torch.float32 and tuple(prev.shape) == (V, 4) and prev.is_contiguous()):
-        raise ValueError(f"auto_exposure: prev must be None or a contiguous float32 ({V}, 4) tensor on {hist.device}, got "
-                         f"{type(prev).__name__} {getattr(prev, 'dtype', None)} {tuple(getattr(prev, 'shape', ()))} on {getattr(prev, 'device', None)}")
+    if prev is not None and not _is_tensor(prev, torch.float32, (V, 4), hist.device):
+        _refuse(prev, f"auto_exposure: prev must be None or a contiguous float32 ({V}, 4) tensor on {hist.device}")
     min_log2 = _min_log2("auto_exposure", min_log2)
     key, low, high, rate, min_exposure, max_exposure = (float(x) for x in (key, low, high, rate, min_exposure, max_exposure))
     if not all(math.isfinite(x) for x in (key, low, high, rate, min_exposure, max_exposure)):
@@ -2225,14 +1894,11 @@ def auto_exposure(hist, prev=None, key=0.18, low=0.5, high=0.95, rate=1.0, min_e
         raise ValueError(f"auto_exposure: 0 <= low < high <= 1 is required, got {low} and {high}")
     if not (key > 0 and 0 < rate <= 1 and 0 < min_exposure <= max_exposure):
         raise ValueError(f"auto_exposure: key > 0, 0 < rate <= 1 and 0 < min_exposure <= max_exposure are required, got {key}, {rate}, {min_exposure} and {max_exposure}")
-    hstream, tstream = _stream_pair(stream, hist.device)
-    with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensor to the stream that writes it)
-        out = _out_tensor("auto_exposure: out", out, (V, 4), torch.float32, hist.device)
+    hstream, _, out = _outputs(stream, hist.device, ("auto_exposure: out", out, (V, 4), torch.float32))
     if V == 0:
         return out
     p = _abi.ExposureParams(C.sizeof(_abi.ExposureParams), V, min_log2, 0, key, low, high, rate, min_exposure, max_exposure)
-    _check(lib().gnxr_exposure_device(C.byref(p), C.c_void_p(hist.data_ptr()), C.c_void_p(prev.data_ptr()) if prev is not None else None, C.c_void_p(out.data_ptr()),
-                                      C.c_void_p(hstream or None)))
+    _check(lib().gnxr_exposure_device(C.byref(p), _ptr(hist), _ptr(prev), _ptr(out), _addr(hstream)))
     return out
 
 
@@ -2249,7 +1915,7 @@ def tonemap(color, exposure=1.0, curve="aces", white=4.0, srgb=True, round=True,
     stream); the call does not wait for the GPU.  Malformed arguments raise ValueError."""
     import math
     import torch
-    shape, V, H, W = _display_image("tonemap", color)
+    shape, V, H, W = _image("tonemap", "color", color)
     if curve not in TONEMAP_CURVES:
         raise ValueError(f"tonemap: curve must be one of {sorted(TONEMAP_CURVES)}, got {curve!r}")
     white = float(white)
@@ -2257,9 +1923,8 @@ def tonemap(color, exposure=1.0, curve="aces", white=4.0, srgb=True, round=True,
         raise ValueError(f"tonemap: white must lie in [1e-3, 65504], got {white}")
     d_exposure, e = None, 1.0
     if isinstance(exposure, torch.Tensor):
-        if not (exposure.device == color.device and exposure.dtype == torch.float32 and tuple(exposure.shape) == (V, 4) and exposure.is_contiguous()):
-            raise ValueError(f"tonemap: an exposure tensor must be a contiguous float32 ({V}, 4) tensor on {color.device} (auto_exposure), got "
-                             f"{exposure.dtype} {tuple(exposure.shape)} on {exposure.device}")
+        if not _is_tensor(exposure, torch.float32, (V, 4), color.device):
+            _refuse(exposure, f"tonemap: an exposure tensor must be a contiguous float32 ({V}, 4) tensor on {color.device} (auto_exposure)", type_name=False)
         d_exposure = exposure
     else:
         try:
@@ -2268,15 +1933,12 @@ def tonemap(color, exposure=1.0, curve="aces", white=4.0, srgb=True, round=True,
             raise ValueError(f"tonemap: exposure must be a number or the tensor of auto_exposure, got {type(exposure).__name__}") from None
         if not (math.isfinite(e) and e >= 0):
             raise ValueError(f"tonemap: exposure must be finite and >= 0, got {e}")
-    hstream, tstream = _stream_pair(stream, color.device)
-    with torch.cuda.stream(tstream):   # (the caching allocator ties the new tensor to the stream that writes it)
-        out = _out_tensor("tonemap: out", out, shape, torch.uint8, color.device)
+    hstream, _, out = _outputs(stream, color.device, ("tonemap: out", out, shape, torch.uint8))
     if V == 0:
         return out
     flags = (_abi.TONEMAP_SRGB if srgb else 0) | (_abi.TONEMAP_ROUND if round else 0)
     p = _abi.TonemapParams(C.sizeof(_abi.TonemapParams), W, H, V, TONEMAP_CURVES[curve], flags, e, white)
-    _check(lib().gnxr_tonemap_device(C.byref(p), C.c_void_p(color.data_ptr()), C.c_void_p(d_exposure.data_ptr()) if d_exposure is not None else None,
-                                     C.c_void_p(out.data_ptr()), C.c_void_p(hstream or None)))
+    _check(lib().gnxr_tonemap_device(C.byref(p), _ptr(color), _ptr(d_exposure), _ptr(out), _addr(hstream)))
     return out
 
 
@@ -2299,9 +1961,7 @@ class Display:
         width, height, n_views = int(width), int(height), int(n_views)
         if width <= 0 or height <= 0 or n_views < 1:
             raise ValueError(f"Display: invalid size {n_views} x {width} x {height}")
-        unknown = [k for k in kw if k not in self._HIST + self._EXPOSURE + self._TONEMAP]
-        if unknown:
-            raise ValueError(f"Display: unexpected arguments {unknown} ({', '.join(self._HIST + self._EXPOSURE + self._TONEMAP)})")
+        _only_kw("Display", kw, self._HIST + self._EXPOSURE + self._TONEMAP)
         self.width, self.height, self.n_views = width, height, n_views
         self.min_log2 = _min_log2("Display", kw.get("min_log2", -12))
         self.exposure_kw = {k: kw[k] for k in self._EXPOSURE if k in kw}
@@ -2319,7 +1979,7 @@ class Display:
         "exposure" and "hist" are the Display's own tensors, which the next frame overwrites.  Runs on `stream` (by default torch's
         current stream)."""
         import torch
-        shape, V, H, W = _display_image("Display.present", color)
+        shape, V, H, W = _image("Display.present", "color", color)
         if (V, H, W) != (self.n_views, self.height, self.width):
             raise ValueError(f"Display.present: color is {V} x {H} x {W}, the display {self.n_views} x {self.height} x {self.width}")
         hstream, tstream = _stream_pair(stream, color.device)
