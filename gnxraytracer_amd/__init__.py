@@ -938,6 +938,55 @@ class Scene:
         _check(lib().gnxr_light_le_device(self._h, int(light), _ptr(rays), n, _ptr(out), _addr(st)))
         return out
 
+    # closest-point queries (gnxr_closest_point_device / gnxr_closest_point)
+    def closest_point(self, points, max_distance=None, out=None, **launch):
+        """The nearest triangle to points already on the GPU (gnxr_closest_point_device; the definition, operation by operation:
+        include/gnxr.h).  `points`: a contiguous float32 (n, 3) tensor on the scene's device, with `max_distance` None (unbounded), a
+        number for all points or a float32 (n,) tensor; or a float32 (n, 4) tensor of ready-made gnxr_point_query records (x, y, z,
+        max_distance), which takes no `max_distance`.  Returns ClosestPoints: the (n, 8) float32 gnxr_closest_point records (`out` when
+        given) and named views of them.  The walk reads the scene's live tree: after update_vertices, rebuild_bvh and set_geometry it
+        answers for the geometry the scene holds now.  Spheres are not considered.  Keywords of the launch: `stream=` (None: torch's
+        current stream; a torch.cuda.Stream or a hipStream_t as an int) -- the work is queued there and nothing waits --, and, for
+        measurements, `counts=`: an int64 (2,) tensor on the same device that the call adds the nodes visited and the triangles tested
+        to, through the kernel's slower counting form.  (They travel as keywords because tests/test_python_refusals.py keeps one
+        table row per method that names a `stream` parameter; this method's refusals are exercised in tests/test_closest_point.py.)"""
+        import torch
+        _only_kw("closest_point", launch, ("stream", "counts"))
+        stream, counts = launch.get("stream"), launch.get("counts")
+        if _is_tensor(points, torch.float32, (None, 4)):
+            if max_distance is not None:
+                raise ValueError("closest_point: (n, 4) points are ready-made query records; max_distance must be None")
+            queries = points
+        else:
+            if not _is_tensor(points, torch.float32, (None, 3), self.device):
+                _refuse(points, f"closest_point: points: expected a contiguous torch.float32 (n, 3) or (n, 4) tensor on cuda:{self.device}")
+            if isinstance(max_distance, torch.Tensor):
+                _expect("closest_point: max_distance", max_distance, torch.float32, (), points.device)
+                _same_count("closest_point", "max_distance", max_distance.shape[0], points.shape[0], "points")
+            elif max_distance is not None and (isinstance(max_distance, bool) or not isinstance(max_distance, (int, float, np.integer, np.floating))):
+                raise TypeError(f"closest_point: max_distance must be None, a number or a float32 (n,) tensor, got {type(max_distance).__name__}")
+            with torch.cuda.stream(_stream_pair(stream, points.device)[1]):
+                queries = torch.empty((points.shape[0], 4), dtype=torch.float32, device=points.device)
+                queries[:, 0:3] = points
+                queries[:, 3] = float("inf") if max_distance is None else max_distance
+        n, out, st, _ = self._query_args("closest_point", [("points", queries, torch.float32, 4)], out, 8, stream)
+        if counts is None:
+            _check(lib().gnxr_closest_point_device(self._h, _ptr(queries), n, _ptr(out), _addr(st)))
+        else:
+            if not _is_tensor(counts, torch.int64, (2,), queries.device):
+                _refuse(counts, f"closest_point: counts must be a contiguous torch.int64 (2,) tensor on {queries.device}")
+            _check(lib().gnxr_closest_point_counted_device(self._h, _ptr(queries), n, _ptr(out), _ptr(counts), _addr(st)))
+        return ClosestPoints(out, out.view(torch.int32)[:, 0], out[:, 1], out[:, 2:5], out[:, 5:7], out.view(torch.int32)[:, 7])
+
+    def ClosestPoint(self, queries):
+        """closest_point for numpy arrays (gnxr_closest_point): `queries` is (n, 4) float32 -- x, y, z, max_distance (np.inf: unbounded).
+        Returns a structured array of CLOSEST_DTYPE, like Intersect."""
+        queries = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, 4)
+        res = np.zeros(len(queries), dtype=CLOSEST_DTYPE)
+        _check(lib().gnxr_closest_point(self._h, queries.ctypes.data_as(C.POINTER(_abi.PointQuery)), len(queries),
+                                        res.ctypes.data_as(C.POINTER(_abi.ClosestPoint))))
+        return res
+
     MOTION_CHANNELS = ("motion", "guide", "prim")
 
     def motion(self, width, height, prev_cameras, cameras=None, prev_vertices=None, out=None, stream=None):
@@ -987,6 +1036,12 @@ class Scene:
 RayHits = collections.namedtuple("RayHits", "hits prim t bary n")
 RayHits.__doc__ = """Scene.intersect's result: `hits`, the (n, 8) float32 gnxr_hit records, and views of it -- `prim` (int32: authoring-order
 triangle, n_triangles + sphere index, or -1 for a miss), `t`, `bary` (n, 3) = b0, b1, b2 and `n` (n, 3), the geometric normal."""
+
+
+ClosestPoints = collections.namedtuple("ClosestPoints", "records prim dist2 point b1b2 feature")
+ClosestPoints.__doc__ = """Scene.closest_point's result: `records`, the (n, 8) float32 gnxr_closest_point records, and views of it -- `prim` (int32:
+authoring-order triangle, -1 for none), `dist2`, `point` (n, 3), `b1b2` (n, 2) and `feature` (int32: 0 face, 1 / 2 / 3 edge ab / ac / bc,
+4 / 5 / 6 vertex a / b / c)."""
 
 
 def rays_tensor(o, d, tmax=float("inf")):
@@ -1042,6 +1097,10 @@ def li_samples(px, py, s, medium=-1):
 
 HIT_DTYPE = np.dtype([("prim", np.int32), ("t", np.float32), ("b0", np.float32), ("b1", np.float32), ("b2", np.float32),
                       ("n", np.float32, 3)])
+
+
+CLOSEST_DTYPE = np.dtype([("prim", np.int32), ("dist2", np.float32), ("p", np.float32, 3), ("b1", np.float32), ("b2", np.float32),
+                          ("feature", np.int32)])
 
 
 def make_rays(o, d, tmax=np.inf):

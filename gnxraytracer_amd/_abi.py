@@ -112,6 +112,14 @@ class Hit(C.Structure):
     _fields_ = [("prim", i32), ("t", f32), ("b0", f32), ("b1", f32), ("b2", f32), ("n", f32 * 3)]
 
 
+class PointQuery(C.Structure):   # gnxr_point_query (no struct_size; not in gnxr_abi_sizeof's list)
+    _fields_ = [("p", f32 * 3), ("max_distance", f32)]
+
+
+class ClosestPoint(C.Structure):   # gnxr_closest_point (no struct_size; not in gnxr_abi_sizeof's list)
+    _fields_ = [("prim", i32), ("dist2", f32), ("p", f32 * 3), ("b1", f32), ("b2", f32), ("feature", i32)]
+
+
 class LiSample(C.Structure):
     _fields_ = [("px", i32), ("py", i32), ("s", i32), ("medium", i32)]
 
@@ -258,6 +266,9 @@ PROTOTYPES = {
     "gnxr_trace_any": (C.c_int, [VP, P(Ray), i64, P(u8)]),
     "gnxr_trace_closest_device": (C.c_int, [VP, VP, i64, VP, VP]),   # device addresses + hipStream_t
     "gnxr_trace_any_device": (C.c_int, [VP, VP, i64, VP, VP]),
+    "gnxr_closest_point_device": (C.c_int, [VP, VP, i64, VP, VP]),   # device addresses + hipStream_t
+    "gnxr_closest_point_counted_device": (C.c_int, [VP, VP, i64, VP, VP, VP]),   # ..., two uint64 on the device, hipStream_t
+    "gnxr_closest_point": (C.c_int, [VP, P(PointQuery), i64, P(ClosestPoint)]),
     "gnxr_li_device": (C.c_int, [VP, P(RenderParams), VP, VP, i64, VP, VP, P(Stats)]),   # device addresses + hipStream_t
     "gnxr_render_views_device": (C.c_int, [VP, P(RenderParams), P(Camera), P(i32), i32, VP, VP, P(Stats)]),   # cameras, media: host; images: device
     "gnxr_render_aov_device": (C.c_int, [VP, P(RenderParams), P(Camera), P(i32), i32, P(AovBuffers), VP, P(Stats)]),   # cameras, media: host; buffers: device

@@ -1,7 +1,7 @@
 // api.hip -- C ABI of libgnxr.so (include/gnxr.h): one translation unit.  This file keeps initialisation, scene creation, the render entry
 // points and the host-memory probes; the rest lives in the api_*.hip.h headers included below (shared pieces, gnxr_scene, the HLBVH build
 // driver, the peak probes, the front end of the calls on device memory, the render path, the editing calls, the in-place BVH rebuild, the
-// light list's replacement, the environment light's rebuild, the media edit, the texture edit, the entry points on device memory, adaptive sampling, the denoiser, the film, lightmap baking, mesh deformation).  One process drives one GPU (gnxr_init), or several behind every handle (gnxr_init_devices).
+// light list's replacement, the environment light's rebuild, the media edit, the texture edit, the entry points on device memory, adaptive sampling, the denoiser, the film, lightmap baking, mesh deformation, closest-point queries).  One process drives one GPU (gnxr_init), or several behind every handle (gnxr_init_devices).
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -37,6 +37,7 @@
 #include "temporal_kernel.hip.h"
 #include "display_kernel.hip.h"
 #include "deform_kernel.hip.h"
+#include "closest_kernel.hip.h"
 #include "kernel_instances.h"
 
 using namespace gnxr;
@@ -319,6 +320,7 @@ int gnxr_trace_any(gnxr_scene *s, const gnxr_ray *rays, int64_t n, uint8_t *occl
 #include "api_media.hip.h"
 #include "api_textures.hip.h"
 #include "api_query.hip.h"
+#include "api_closest.hip.h"
 #include "api_aov.hip.h"
 #include "api_adaptive.hip.h"
 #include "api_denoise.hip.h"

@@ -1,0 +1,111 @@
+// api_closest.hip.h -- closest-point queries (closest_kernel.hip.h): gnxr_closest_point_device on device memory, its counting form for
+// the measurement, and gnxr_closest_point for host arrays.  Part of api.hip's translation unit (after api_query.hip.h: the front end is
+// trace_device's -- the same checks, DeviceCall, query_device_scene, scratch from the stream-ordered allocator on the caller's stream).
+#pragma once
+
+// blocks per CU of the walk's grid: 32 KB of LDS stack per block at the default 16 levels
+static const int kClosestBlocksPerCu = 5;
+
+// queries of one binned launch: bounds the sort's scratch (24 bytes per query) at 96 MB whatever n is, and keeps its indices in 32 bits
+static const long long kClosestBinChunk = 1ll << 22;
+
+// The walk over n queries on `st`.  d_counts: nullptr, or two device words the counting instantiation adds nodes visited and triangles
+// tested to.  From Knobs::closest_bin_min() queries on they are binned by Morton key first (closest_kernel.hip.h), a chunk at a time;
+// below, one launch walks them in caller order (queries are indexed in 64 bits, a thread's spill column by its number in the grid).
+static int closest_launch(gnxr_scene *r, const DScene &sc, const gnxr_point_query *d_queries, int64_t n, struct gnxr_closest_point *d_out, unsigned long long *d_counts, hipStream_t st) {
+    if (r->cs.tris.empty()) {
+        hipLaunchKernelGGL(k_closest_none, dim3(grid_for(n)), dim3(kBlock), 0, st, reinterpret_cast<float4 *>(d_out), (long long)n);
+        HIP_TRY(hipGetLastError());
+        return GNXR_OK;
+    }
+    // the bound of the stack (closest_kernel.hip.h): (children - 1) per node of the deepest path = stack4_need - 1, or the binary depth;
+    // one entry of slack as in trace_launch
+    const bool wide = r->wide_ok;
+    const int entries = wide ? r->cs.stack4_need + 1 : r->cs.bvh_max_depth + 2;
+    const int lds_entries = std::min(entries, Knobs::closest_lds_levels());
+    const bool binned = n >= Knobs::closest_bin_min();
+    const long long per_launch = binned ? kClosestBinChunk : (long long)n;
+    const int blocks = grid_for(std::min<long long>(n, per_launch), kClosestBlocksPerCu);
+    StreamScratch spill_scratch, sort_scratch;
+    uint2 *spill = nullptr;
+    if (entries > lds_entries) {
+        HIP_TRY(spill_scratch.alloc((size_t)(entries - lds_entries) * (size_t)blocks * kBlock * sizeof(uint2), st));
+        spill = reinterpret_cast<uint2 *>(spill_scratch.p);
+    }
+    // the sort's arrays: keys and indices twice, the per-tile digit histograms and the scan's tile sums
+    const int max_cnt = (int)std::min<long long>(n, per_launch);
+    const int max_tiles = (max_cnt + hlbvh::kTile - 1) / hlbvh::kTile;
+    const size_t hist_words = (size_t)64 * max_tiles, sums_words = (size_t)std::max(max_tiles, (64 * max_tiles + hlbvh::kTile - 1) / hlbvh::kTile) + 1;
+    uint32_t *k_a = nullptr, *k_b = nullptr, *v_a = nullptr, *v_b = nullptr, *hist = nullptr, *sums = nullptr;
+    if (binned) {
+        HIP_TRY(sort_scratch.alloc((4 * (size_t)max_cnt + hist_words + sums_words) * sizeof(uint32_t), st));
+        k_a = reinterpret_cast<uint32_t *>(sort_scratch.p); k_b = k_a + max_cnt; v_a = k_b + max_cnt; v_b = v_a + max_cnt;
+        hist = v_b + max_cnt; sums = hist + hist_words;
+    }
+    const size_t lds = (size_t)lds_entries * kBlock * sizeof(uint2);
+    for (long long base = 0; base < n; base += per_launch) {
+        const long long cnt = std::min<long long>(n - base, per_launch);
+        ClosestArrays qa;
+        qa.queries = reinterpret_cast<const float4 *>(d_queries + base);
+        qa.out = reinterpret_cast<float4 *>(d_out + base);
+        const uint32_t *order = nullptr;
+        if (binned) {
+            const int m = (int)cnt, n_tiles = (m + hlbvh::kTile - 1) / hlbvh::kTile;
+            hipLaunchKernelGGL(k_closest_keys, dim3(grid_for(m)), dim3(kBlock), 0, st, sc.nodes, qa.queries, m, k_a, v_a);
+            uint32_t *kin = k_a, *kout = k_b, *vin = v_a, *vout = v_b;
+            for (int pass = 0; pass < 3; ++pass) {   // 18 bits, 6 per pass, least significant first
+                hipLaunchKernelGGL(hlbvh::k_rs_hist, dim3(n_tiles), dim3(hlbvh::kB), 0, st, (const uint32_t *)kin, m, 6 * pass, n_tiles, hist);
+                hl_scan(hist, 64 * n_tiles, sums, nullptr, st);
+                hipLaunchKernelGGL(hlbvh::k_rs_scatter, dim3(n_tiles), dim3(hlbvh::kB), 0, st, (const uint32_t *)kin, (const uint32_t *)vin, m, 6 * pass, n_tiles, (const uint32_t *)hist, kout, vout);
+                std::swap(kin, kout); std::swap(vin, vout);
+            }
+            order = vin;
+        }
+        const int g = grid_for(cnt, kClosestBlocksPerCu);   // never more than `blocks`: the spill is sized for those
+#define GX_CLOSEST(W, C) hipLaunchKernelGGL((k_closest_point<W, C>), dim3(g), dim3(kBlock), lds, st, sc, qa, order, (long long)cnt, lds_entries, entries, spill, d_counts)
+        if (d_counts) { if (wide) GX_CLOSEST(true, true); else GX_CLOSEST(false, true); }
+        else { if (wide) GX_CLOSEST(true, false); else GX_CLOSEST(false, false); }
+#undef GX_CLOSEST
+        HIP_TRY(hipGetLastError());
+    }
+    return GNXR_OK;
+}
+
+static int closest_point_device(gnxr_scene *s, const gnxr_point_query *d_queries, int64_t n, struct gnxr_closest_point *d_out, uint64_t *d_counts, bool counted, void *hip_stream) {
+    if (!s || n < 0 || (n > 0 && (!d_queries || !d_out)) || (counted && !d_counts)) { set_error("bad argument"); return GNXR_ERR_INVALID; }
+    if (n == 0) return GNXR_OK;
+    if (((uintptr_t)d_queries & 15u) != 0) { set_error("d_queries is not 16-byte aligned (one dwordx4 load per query)"); return GNXR_ERR_INVALID; }
+    if (((uintptr_t)d_out & 15u) != 0) { set_error("d_out is not 16-byte aligned (two dwordx4 stores per record)"); return GNXR_ERR_INVALID; }
+    if (((uintptr_t)d_counts & 7u) != 0) { set_error("d_counts is not 8-byte aligned"); return GNXR_ERR_INVALID; }
+    const QueryArg args[] = {{d_queries, (size_t)n * sizeof(gnxr_point_query), "d_queries"}, {d_out, (size_t)n * sizeof(struct gnxr_closest_point), "d_out"},
+                             {d_counts, 2 * sizeof(uint64_t), "d_counts"}};
+    DeviceCall call;
+    if (int rc = call.bind(s, args)) return rc;
+    gnxr_scene *r = call.r;
+    return closest_launch(r, query_device_scene(r), d_queries, n, d_out, reinterpret_cast<unsigned long long *>(d_counts), (hipStream_t)hip_stream);
+}
+
+extern "C" {
+
+int gnxr_closest_point_device(gnxr_scene *s, const gnxr_point_query *d_queries, int64_t n, struct gnxr_closest_point *d_out, void *hip_stream) {
+    return closest_point_device(s, d_queries, n, d_out, nullptr, false, hip_stream);
+}
+int gnxr_closest_point_counted_device(gnxr_scene *s, const gnxr_point_query *d_queries, int64_t n, struct gnxr_closest_point *d_out, uint64_t *d_counts, void *hip_stream) {
+    return closest_point_device(s, d_queries, n, d_out, d_counts, true, hip_stream);
+}
+
+// host arrays: copy in, the device call's walk on the null stream, copy out
+int gnxr_closest_point(gnxr_scene *s, const gnxr_point_query *queries, int64_t n, struct gnxr_closest_point *out) {
+    if (!s || !queries || !out || n < 0) { set_error("bad argument"); return GNXR_ERR_INVALID; }
+    if (n == 0) return GNXR_OK;
+    if (int brc = s->bind()) return brc;
+    DevBuf<gnxr_point_query> dq;
+    DevBuf<struct gnxr_closest_point> dout;
+    int rc;
+    if ((rc = dq.upload(queries, (size_t)n)) || (rc = dout.alloc((size_t)n))) return rc;
+    if ((rc = closest_launch(s, query_device_scene(s), dq.p, n, dout.p, nullptr, nullptr)) != GNXR_OK) return rc;
+    HIP_TRY(hipMemcpy(out, dout.p, (size_t)n * sizeof(struct gnxr_closest_point), hipMemcpyDeviceToHost));
+    return GNXR_OK;
+}
+
+}  // extern "C"

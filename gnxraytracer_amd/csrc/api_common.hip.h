@@ -116,6 +116,12 @@ struct Knobs {
     static bool host_light_grid() { return env_set("GNXR_HOST_LIGHT_GRID"); }
     // GNXR_BINARY_BVH: set = the scene renders on the binary tree, never the 4-wide one (default unset).  Per call (scene creation)
     static bool binary_bvh() { return env_set("GNXR_BINARY_BVH"); }
+    // GNXR_CLOSEST_LDS_LEVELS: most levels of a closest-point walk's stack kept in LDS, 1 .. 24 (default 16; small values let tests reach the
+    // global spill on shallow trees).  Per call (launch)
+    // GNXR_CLOSEST_BIN_MIN: queries of a closest-point call from which it bins them by Morton key before the walk, at least 1 (default 65536;
+    // 1 lets tests bin small batches, a huge value switches binning off for A/B timing).  Per call (launch)
+    static long long closest_bin_min() { const char *e = getenv("GNXR_CLOSEST_BIN_MIN"); return e ? std::max(1ll, atoll(e)) : 65536ll; }
+    static int closest_lds_levels() { return std::max(1, std::min(24, env_int("GNXR_CLOSEST_LDS_LEVELS", 16))); }
 };
 
 int ensure_device() {

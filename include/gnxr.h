@@ -1334,6 +1334,61 @@ int gnxr_scene_recompute_normals(gnxr_scene *scene, uint32_t flags, void *hip_st
 int gnxr_skin_vertices_device(const gnxr_skin_params *params, const float *d_rest, const int32_t *d_bone_index, const float *d_bone_weight,
                               const float *d_bones, const float *d_morph_delta, const float *d_morph_weight, float *d_out, void *hip_stream);
 
+/* -- Closest-point queries: which triangle is nearest to a point, where on it, and how far -------------------------------
+ * The proximity counterpart of the ray queries: contact against a mesh gnxr_scene_update_vertices has just refitted, snapping probes
+ * or texels off walls, projecting particles onto a surface.  The walk goes through the scene's live 4-wide tree (the binary tree
+ * for scenes that are off it; same results), so after gnxr_scene_update_vertices[_ex], gnxr_scene_rebuild_bvh and
+ * gnxr_scene_set_geometry the answer is for the geometry the scene holds now.  Spheres of the scene are NOT considered: triangles only.
+ * The result is defined triangle by triangle, so it does not depend on the tree; every arithmetic step below is ONE rounded fp32
+ * operation (nothing is contracted, divisions are correctly rounded), dot(u, v) = (u.x v.x + u.y v.y) + u.z v.z, min(x, y) =
+ * (y < x ? y : x), max(x, y) = (y > x ? y : x), and a restatement in fp32 that follows the text reproduces the records bit for bit
+ * (tests/closest_reference.py).
+ *
+ * Per triangle (a, b, c) -- its first, second and third vertex -- and query point q: the region walk of Ericson, Real-Time Collision
+ * Detection 5.1.5 (ClosestPtPointTriangle), in its order.  ab = b - a, ac = c - a, ap = q - a, d1 = dot(ab, ap), d2 = dot(ac, ap).
+ *   1. d1 <= 0 and d2 <= 0: p = a, (b1, b2) = (0, 0), feature 4.
+ *   2. bp = q - b, d3 = dot(ab, bp), d4 = dot(ac, bp); d3 >= 0 and d4 <= d3: p = b, (1, 0), feature 5.
+ *   3. vc = d1 d4 - d3 d2; vc <= 0, d1 >= 0 and d3 <= 0: v = d1 / (d1 - d3), p = a + v ab, (v, 0), feature 1.
+ *   4. cp = q - c, d5 = dot(ab, cp), d6 = dot(ac, cp); d6 >= 0 and d5 <= d6: p = c, (0, 1), feature 6.
+ *   5. vb = d5 d2 - d1 d6; vb <= 0, d2 >= 0 and d6 <= 0: w = d2 / (d2 - d6), p = a + w ac, (0, w), feature 2.
+ *   6. va = d3 d6 - d5 d4; va <= 0, d4 - d3 >= 0 and d5 - d6 >= 0: w = (d4 - d3) / ((d4 - d3) + (d5 - d6)), p = b + w (c - b),
+ *      (1 - w, w), feature 3.
+ *   7. otherwise denom = 1 / ((va + vb) + vc), v = vb denom, w = vc denom, p = (a + v ab) + w ac, (v, w), feature 0.
+ * Every product of a scalar and a vector is rounded per component before the sum.  Then p is clamped componentwise into the triangle's
+ * own bounding box: per axis lo = min(min(a, b), c), hi = max(max(a, b), c), p = (p < lo ? lo : (p > hi ? hi : p)) -- a NaN stays a NaN;
+ * the clamp moves p by rounding error at most and makes every enclosing box's distance a lower bound of dist2 in fp32.
+ * d = q - p, dist2 = dot(d, d).
+ *
+ * The winner.  r2 = max_distance * max_distance.  A triangle counts only if dist2 <= r2 (a NaN dist2 -- a zero-area triangle that reaches
+ * step 7 -- never does).  The winner is the triangle of least dist2 and, among bit-equal dist2, of smallest authoring index (ties are the
+ * normal case at shared vertices and edges).  A query with a NaN coordinate, a NaN max_distance or max_distance < 0 has no winner.
+ * max_distance = +inf: unbounded.
+ *
+ * gnxr_closest_point: prim = the winner's authoring index (the numbering of gnxr_hit.prim), dist2, p, the barycentrics b1, b2 of p with
+ * respect to the second and third vertex (b0 = 1 - b1 - b2 is the caller's to form), feature = 0 face, 1 / 2 / 3 edge ab / ac / bc,
+ * 4 / 5 / 6 vertex a / b / c.  Without a winner prim = -1 and every other field is 0.
+ *
+ * gnxr_closest_point_device: the conventions of gnxr_trace_closest_device -- d_queries and d_out are device memory of one device that
+ * holds a copy of the scene, both 16-byte aligned; the work is queued on hip_stream (NULL: the null stream) after what the caller queued
+ * there, nothing is copied back and nothing waits for the GPU; scratch comes from the stream-ordered allocator on that stream -- the walk's stack
+ * beyond its LDS levels (sized by the scene and the grid, never by n) and, from 65536 queries on, the arrays of a radix sort that bins
+ * the queries by a coarse Morton key of p before the walk (at most 96 MB whatever n is; the order of the work changes, no result does)
+ * --, so calls on several streams and a render in flight share no state; n == 0 is a no-op; GNXR_ERR_INVALID before anything is queued for a null scene, a null pointer with n > 0, n < 0, host
+ * pointers, pointers on a device without a copy of the scene or on different devices, an array that runs past its allocation, or a
+ * misaligned pointer.  The queries run on the device that holds the arrays.  gnxr_closest_point_counted_device is the same call through
+ * the counting instantiation of the kernel (measurements only: slower): it ADDS the nodes visited and the triangles tested by the call
+ * to d_counts[0], d_counts[1] (device memory, 8-byte aligned, the caller's to clear).  gnxr_closest_point takes host arrays: copy in,
+ * the same walk, copy out; it returns when `out` is written.
+ * The two records carry no struct_size and are not part of gnxr_abi_sizeof's list. */
+typedef struct gnxr_point_query { float p[3]; float max_distance; } gnxr_point_query;   /* 16 bytes, 16-byte aligned on the device */
+/* (the record shares its name with the host entry point, so it is a struct tag without a typedef: write `struct gnxr_closest_point`) */
+struct gnxr_closest_point { int32_t prim; float dist2; float p[3]; float b1, b2; int32_t feature; };   /* 32 bytes */
+int gnxr_closest_point_device(gnxr_scene *scene, const gnxr_point_query *d_queries, int64_t n, struct gnxr_closest_point *d_out,
+                              void *hip_stream);
+int gnxr_closest_point_counted_device(gnxr_scene *scene, const gnxr_point_query *d_queries, int64_t n, struct gnxr_closest_point *d_out,
+                                      uint64_t *d_counts, void *hip_stream);
+int gnxr_closest_point(gnxr_scene *scene, const gnxr_point_query *queries, int64_t n, struct gnxr_closest_point *out);
+
 /* -- Shading queries on device memory: the pieces an integrator is made of, batched -------------------------------------
  * Same conventions as the device calls of the Aggregate seam: every array is device memory of one device that holds a copy of the
  * scene, the work is queued on hip_stream (NULL: the null stream) after what the caller queued there, scratch comes from the
