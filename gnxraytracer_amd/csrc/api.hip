@@ -1,5 +1,6 @@
 // api.hip -- C ABI of libgnxr.so (include/gnxr.h): one translation unit.  This file keeps initialisation, scene creation, the render entry
-// points and the host-memory probes; the rest lives in the api_*.hip.h headers included below (shared pieces, gnxr_scene, the HLBVH build
+// points and the host-memory probes (gnxr_scene_create compiles into a local CompiledScene, uploads it and leaves the handle its facts:
+// host_scene.h); the rest lives in the api_*.hip.h headers included below (shared pieces, gnxr_scene, the HLBVH build
 // driver, the peak probes, the front end of the calls on device memory, the render path, the editing calls, the in-place BVH rebuild, the
 // light list's replacement, the environment light's rebuild, the media edit, the texture edit, the entry points on device memory, adaptive sampling, the denoiser, the film, lightmap baking, mesh deformation, closest-point queries).  One process drives one GPU (gnxr_init), or several behind every handle (gnxr_init_devices).
 #include <hip/hip_runtime.h>
@@ -145,32 +146,26 @@ int gnxr_debug_tail_stamp(unsigned long long *out12, int reset) {
 }
 #endif
 
-// device side of gnxr_scene_create: everything compile_scene produced goes to the copy's (bound) device (an each_copy callable)
-static int upload_scene(gnxr_scene *s, size_t) {
-    const CompiledScene &cs = s->cs;
+// device side of gnxr_scene_create: everything compile_scene produced goes to the copy's (bound) device -- the upload tables from the
+// caller's (they end with gnxr_scene_create), the tables among the facts from the handle's host scene
+static int upload_scene(gnxr_scene *s, const SceneUploadTables &up) {
+    const SceneFacts &cs = s->cs;
     int rc;
     if (cs.bvh_max_depth + 1 > 64) { set_error("BVH depth %d exceeds the 64-entry traversal stack (BVHAccel.cpp:661)", cs.bvh_max_depth); return GNXR_ERR_UNSUPPORTED; }
-    s->set_traversal(std::any_of(cs.nodes.begin(), cs.nodes.end(), [](const DNode &n) { return (n.meta & 0xffffu) > 127; }));
-#define UP(field) if ((rc = s->field.upload(cs.field)) != GNXR_OK) return rc;
-    UP(nodes) UP(nodes4) UP(tris) UP(leaf_boxes) UP(tri_class) UP(lights) UP(perms) UP(primes) UP(prime_sums) UP(prime_magic)
-    UP(dmedia) UP(grid_density) UP(tri_media) UP(spheres) UP(textures) UP(tex_texels) UP(ewa_lut) UP(tri_uv) UP(tri_n) UP(tri_s)
-    UP(aov_albedo)
-    UP(env_texels4) UP(env_cond_func) UP(env_cond_cdf) UP(env_cond_int) UP(env_marg_func) UP(env_marg_cdf) UP(env_marg_guide) UP(env_cond_guide)
+    s->set_traversal(std::any_of(up.nodes.begin(), up.nodes.end(), [](const DNode &n) { return (n.meta & 0xffffu) > 127; }));
+#define UP(from, field) if ((rc = s->field.upload(from.field)) != GNXR_OK) return rc;
+    UP(up, nodes) UP(up, nodes4) UP(up, tris) UP(up, leaf_boxes) UP(up, tri_class) UP(cs, lights) UP(cs, perms) UP(cs, primes) UP(cs, prime_sums) UP(cs, prime_magic)
+    UP(cs, dmedia) UP(up, grid_density) UP(up, tri_media) UP(cs, spheres) UP(cs, textures) UP(up, tex_texels) UP(up, ewa_lut) UP(up, tri_uv) UP(up, tri_n) UP(up, tri_s)
+    UP(cs, aov_albedo)
+    UP(cs, env_texels4) UP(cs, env_cond_func) UP(cs, env_cond_cdf) UP(cs, env_cond_int) UP(cs, env_marg_func) UP(cs, env_marg_cdf) UP(cs, env_marg_guide) UP(cs, env_cond_guide)
 #undef UP
     {   // materials, preceded by one record that carries the texture tables.  A material edit may give every authored material an attribute
         // copy: the buffers are sized for that once, so that no edit reallocates them under queries in flight
         const size_t worst = 2 * cs.desc_materials.size();
         if ((rc = s->material_authored.alloc(worst)) || (rc = s->materials.alloc(1 + worst)) || (rc = s->materials_single.alloc(1 + worst))) return rc;
         if ((rc = s->material_authored.upload(cs.material_authored)) != GNXR_OK) return rc;
-        const DTexTables rec = s->tex_tables(s->tri_uv.p, s->tri_n.p, s->tri_s.p);
-        for (int k = 0; k < 2; ++k) {
-            const std::vector<DMaterial> &src = k == 0 ? cs.materials : cs.materials_single;
-            std::vector<DMaterial> up(src.size() + 1);
-            memset(&up[0], 0, sizeof(DMaterial));
-            memcpy(&up[0], &rec, sizeof(rec));
-            std::copy(src.begin(), src.end(), up.begin() + 1);
-            if ((rc = (k == 0 ? s->materials : s->materials_single).upload(up)) != GNXR_OK) return rc;
-        }
+        const DTexTables at = s->tex_tables(s->tri_uv.p, s->tri_n.p, s->tri_s.p);   // (an empty upload still allocates: absent tables are null here)
+        if ((rc = s->write_material_tables(cs.materials, cs.materials_single, at.tri_uv, at.tri_n, at.tri_s)) != GNXR_OK) return rc;
     }
     if ((rc = s->infinite.upload(cs.infinite_lights)) != GNXR_OK) return rc;
     if ((rc = s->counters.alloc(1)) != GNXR_OK) return rc;
@@ -189,14 +184,20 @@ int gnxr_scene_create(const gnxr_scene_desc *desc, gnxr_scene **out) {
     if (rc) return rc;
     gnxr_scene *s = new (std::nothrow) gnxr_scene(g_device);
     if (!s) return GNXR_ERR_OOM;
-    if (!compile_scene(desc, &s->cs, device_hlbvh_build)) { delete s; return GNXR_ERR_INVALID; }
+    // the whole compiled scene lives in this call: its facts move into the handle (with the refit's seeds, which go to a device at the
+    // first edit), its upload tables go to the devices and end here
+    CompiledScene compiled;
+    if (!compile_scene(desc, &compiled, device_hlbvh_build)) { delete s; return GNXR_ERR_INVALID; }
+    s->cs = std::move(static_cast<SceneFacts &>(compiled));
+    s->cs.refit_seeds = std::move(static_cast<RefitSeeds &>(compiled));
     // gnxr_init_devices: a copy on every other device of the list, sharing the host scene; then the same tables on every device
     for (size_t i = 1; i < g_devices.size(); ++i) s->replicas.push_back(std::make_unique<gnxr_scene>(g_devices[i], s->host));
-    if ((rc = s->each_copy(upload_scene)) != GNXR_OK) { delete s; return rc; }
-    const CompiledScene &cs = s->cs;
+    s->host->copies_awaiting_seeds = s->n_copies();
+    if ((rc = s->each_copy([&](gnxr_scene *c, size_t) { return upload_scene(c, compiled); })) != GNXR_OK) { delete s; return rc; }
+    const SceneFacts &cs = s->cs;
     if (getenv("GNXR_VERBOSE"))
-        fprintf(stderr, "[gnxr] scene: %zu tris, %zu nodes (depth %d), %zu 4-wide nodes (stack %d), wide=%d, %zu device(s)\n", cs.tris.size(), cs.nodes.size(), cs.bvh_max_depth,
-                cs.nodes4.size(), cs.stack4_need, (int)s->wide_ok, s->n_copies());
+        fprintf(stderr, "[gnxr] scene: %zu tris, %zu nodes (depth %d), %zu 4-wide nodes (stack %d), wide=%d, %zu device(s)\n", cs.n_triangles, cs.n_nodes, cs.bvh_max_depth,
+                cs.n_nodes4, cs.stack4_need, (int)s->wide_ok, s->n_copies());
     *out = s;
     return GNXR_OK;
 }
@@ -204,7 +205,7 @@ void gnxr_scene_destroy(gnxr_scene *s) { delete s; }
 
 int gnxr_scene_info(const gnxr_scene *s, int32_t *n_nodes, int32_t *max_depth, int32_t *n_vox) {
     if (!s) return GNXR_ERR_INVALID;
-    if (n_nodes) *n_nodes = (int32_t)s->cs.nodes.size();
+    if (n_nodes) *n_nodes = (int32_t)s->cs.n_nodes;
     if (max_depth) *max_depth = s->cs.bvh_max_depth;
     if (n_vox) *n_vox = s->grid_strategy >= 0 ? s->grid.nvox[0] * s->grid.nvox[1] * s->grid.nvox[2] : 0;
     return GNXR_OK;
@@ -265,21 +266,24 @@ int gnxr_render(gnxr_scene *s, const gnxr_render_params *p, float *rgba_out, gnx
 
 int gnxr_scene_bvh(const gnxr_scene *sc, float *bounds6, int32_t *meta3, int32_t *ordered, int64_t node_capacity, int64_t *n_nodes) {
     if (!sc || !n_nodes) { set_error("bad argument"); return GNXR_ERR_INVALID; }
-    // const for the caller (the scene does not change); the host copies of the tree may still have to be refreshed after an update
+    // const for the caller (the scene does not change); the tables are read from the first device, as gnxr_scene_bvh4 reads them
     gnxr_scene *s = const_cast<gnxr_scene *>(sc);
-    const CompiledScene &cs = s->cs;
-    *n_nodes = (int64_t)cs.nodes.size();
-    if (!bounds6 || !meta3 || !ordered || node_capacity < *n_nodes) return GNXR_OK;
     std::lock_guard<std::recursive_mutex> lock(s->render_mutex);
-    if (int rc = s->sync_host_bvh()) return rc;
-    for (size_t i = 0; i < cs.nodes.size(); ++i) {
-        const DNode &n = cs.nodes[i];
+    *n_nodes = (int64_t)s->cs.n_nodes;
+    if (!bounds6 || !meta3 || !ordered || node_capacity < *n_nodes) return GNXR_OK;
+    if (int rc = s->bind()) return rc;
+    std::vector<DNode> nodes(s->cs.n_nodes);
+    std::vector<DTri> tris(s->cs.n_triangles);
+    HIP_TRY(hipMemcpy(nodes.data(), s->nodes.p, nodes.size() * sizeof(DNode), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(tris.data(), s->tris.p, tris.size() * sizeof(DTri), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < nodes.size(); ++i) {
+        const DNode &n = nodes[i];
         bounds6[6 * i + 0] = n.lo[0]; bounds6[6 * i + 1] = n.lo[1]; bounds6[6 * i + 2] = n.lo[2];
         bounds6[6 * i + 3] = n.hi0; bounds6[6 * i + 4] = n.hi1; bounds6[6 * i + 5] = n.hi2;
         const int nPrims = (int)(n.meta & 0xffffu);
         meta3[3 * i + 0] = n.offset; meta3[3 * i + 1] = nPrims; meta3[3 * i + 2] = nPrims ? 0 : (int)(n.meta >> 16);
     }
-    for (size_t i = 0; i < cs.tris.size(); ++i) ordered[i] = cs.tris[i].prim;
+    for (size_t i = 0; i < tris.size(); ++i) ordered[i] = tris[i].prim;
     return GNXR_OK;
 }
 

@@ -85,7 +85,7 @@ int gnxr_bake_texels_device(gnxr_scene *s, const float *d_tri_lm_uv, int32_t wid
         return GNXR_ERR_INVALID;
     }
     if (int rc = ensure_device()) return rc;
-    const int n_tris = (int)s->cs.tris.size();
+    const int n_tris = (int)s->cs.n_triangles;
     const size_t n_texels = (size_t)width * height;
     const QueryArg args[] = {{d_tri_lm_uv, (size_t)std::max(1, n_tris) * 24, "d_tri_lm_uv"}, {d_texel_tri, n_texels * 4, "d_texel_tri"}, {d_texel_bary, n_texels * 8, "d_texel_bary"}};
     DeviceCall call;
@@ -114,7 +114,7 @@ int gnxr_surface_rays_device(gnxr_scene *s, int32_t width, int32_t height, const
     if (int rc = call.bind(s, args)) return rc;
     gnxr_scene *r = call.r;
     std::lock_guard<std::recursive_mutex> lock(r->render_mutex);   // the triangles are what the editing calls and the rebuild rewrite
-    const int n_tris = (int)r->cs.tris.size();
+    const int n_tris = (int)r->cs.n_triangles;
     hipStream_t stream = (hipStream_t)hip_stream;
     StreamScratch scratch;   // [status word | pad to 16 B | leaf_of]
     HIP_TRY(scratch.alloc(16 + (size_t)std::max(1, n_tris) * sizeof(int), stream));
@@ -172,7 +172,7 @@ int gnxr_bake_lightmap_device(gnxr_scene *s, const gnxr_render_params *p, const 
     if (int rc = ensure_device()) return rc;
     const int W = p->width, H = p->height, spp = p->spp;
     const long long n_texels = (long long)W * H;
-    const int n_tris = (int)s->cs.tris.size();
+    const int n_tris = (int)s->cs.n_triangles;
     const QueryArg args[] = {{d_tri_lm_uv, (size_t)std::max(1, n_tris) * 24, "d_tri_lm_uv"}, {d_rgba_out, (size_t)n_texels * sizeof(float4), "d_rgba_out"}};
     DeviceCall call;
     if (int rc = call.bind(s, args)) return rc;

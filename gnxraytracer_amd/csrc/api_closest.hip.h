@@ -13,7 +13,7 @@ static const long long kClosestBinChunk = 1ll << 22;
 // tested to.  From Knobs::closest_bin_min() queries on they are binned by Morton key first (closest_kernel.hip.h), a chunk at a time;
 // below, one launch walks them in caller order (queries are indexed in 64 bits, a thread's spill column by its number in the grid).
 static int closest_launch(gnxr_scene *r, const DScene &sc, const gnxr_point_query *d_queries, int64_t n, struct gnxr_closest_point *d_out, unsigned long long *d_counts, hipStream_t st) {
-    if (r->cs.tris.empty()) {
+    if (r->cs.n_triangles == 0) {
         hipLaunchKernelGGL(k_closest_none, dim3(grid_for(n)), dim3(kBlock), 0, st, reinterpret_cast<float4 *>(d_out), (long long)n);
         HIP_TRY(hipGetLastError());
         return GNXR_OK;

@@ -9,11 +9,11 @@ namespace {
 
 // the scene's per-corner tables as the kernels see them (an empty upload still allocates: the host scene decides what exists)
 deform::AttrTables attr_tables(gnxr_scene *s) {
-    const CompiledScene &cs = s->cs;
+    const SceneFacts &cs = s->cs;
     deform::AttrTables t;
-    t.uv = cs.tri_uv.empty() ? nullptr : reinterpret_cast<float4 *>(s->tri_uv.p);
-    t.n = cs.tri_n.empty() ? nullptr : reinterpret_cast<float4 *>(s->tri_n.p);
-    t.s = cs.tri_s.empty() ? nullptr : reinterpret_cast<float4 *>(s->tri_s.p);
+    t.uv = cs.has_tri_uv ? reinterpret_cast<float4 *>(s->tri_uv.p) : nullptr;
+    t.n = cs.has_tri_n ? reinterpret_cast<float4 *>(s->tri_n.p) : nullptr;
+    t.s = cs.has_tri_s ? reinterpret_cast<float4 *>(s->tri_s.p) : nullptr;
     return t;
 }
 
@@ -39,8 +39,8 @@ struct AttrStage {
 int normals_adjacency(gnxr_scene *s, hipStream_t st) {
     using namespace hlbvh;
     if (s->adj_offsets.p) return GNXR_OK;
-    const CompiledScene &cs = s->cs;
-    const long long n_tris = (long long)cs.tris.size(), n_corners = 3 * n_tris;
+    const SceneFacts &cs = s->cs;
+    const long long n_tris = (long long)cs.n_triangles, n_corners = 3 * n_tris;
     const int V = cs.n_vertices;
     if (n_corners > 0x7fffffffLL) { set_error("recompute_normals: %lld corners exceed the sort's 2^31 - 1 items", n_corners); return GNXR_ERR_UNSUPPORTED; }
     const int n = (int)n_corners, n_tiles = (n + kTile - 1) / kTile;
@@ -70,8 +70,8 @@ int normals_adjacency(gnxr_scene *s, hipStream_t st) {
 
 // one copy's normals on its (bound) device, queued on st and waited for
 int normals_apply(gnxr_scene *s, float sign, hipStream_t st) {
-    const CompiledScene &cs = s->cs;
-    const int n_tris = (int)cs.tris.size(), V = cs.n_vertices;
+    const SceneFacts &cs = s->cs;
+    const int n_tris = (int)cs.n_triangles, V = cs.n_vertices;
     int rc;
     if ((rc = refit_tables(s)) || (rc = normals_adjacency(s, st)) || (rc = s->nrm_face.alloc(n_tris)) || (rc = s->nrm_vsum.alloc(V))) return rc;
     float4 *tri_n = reinterpret_cast<float4 *>(s->tri_n.p);
@@ -101,7 +101,7 @@ int gnxr_scene_update_attributes(gnxr_scene *s, int32_t first_triangle, int32_t 
     std::lock_guard<std::recursive_mutex> lock(s->render_mutex);
     int rc = s->bind();
     if (rc) return rc;
-    const CompiledScene &cs = s->cs;
+    const SceneFacts &cs = s->cs;
     // all arrays on one side (the rule of gnxr_scene_set_geometry)
     const void *arrays[] = {tri_uv, tri_n, tri_s};
     int side = -2;
@@ -123,12 +123,12 @@ int gnxr_scene_update_attributes(gnxr_scene *s, int32_t first_triangle, int32_t 
             if (((uintptr_t)p & 3u) != 0) { set_error("update_attributes: a device array is not 4-byte aligned"); return GNXR_ERR_INVALID; }
         }
     }
-    if ((tri_uv && cs.tri_uv.empty()) || (tri_n && cs.tri_n.empty()) || (tri_s && cs.tri_s.empty())) {
-        set_error("update_attributes: the scene was created without per-corner %s (gnxr_scene_set_geometry adds the table)", tri_uv && cs.tri_uv.empty() ? "uvs" : tri_n && cs.tri_n.empty() ? "normals" : "tangents");
+    if ((tri_uv && !cs.has_tri_uv) || (tri_n && !cs.has_tri_n) || (tri_s && !cs.has_tri_s)) {
+        set_error("update_attributes: the scene was created without per-corner %s (gnxr_scene_set_geometry adds the table)", tri_uv && !cs.has_tri_uv ? "uvs" : tri_n && !cs.has_tri_n ? "normals" : "tangents");
         return GNXR_ERR_UNSUPPORTED;
     }
     hipStream_t st = (hipStream_t)hip_stream;
-    const int nt = (int)cs.tris.size();
+    const int nt = (int)cs.n_triangles;
     // the primary: rows staged (or read where they lie, behind what the caller queued on st), refusals first, then the write
     AttrStage prim;
     if (side == 0) { if ((rc = prim.stage(tri_uv, tri_n, tri_s, first_triangle, n_triangles, st)) != GNXR_OK) return rc; }
@@ -158,7 +158,7 @@ int gnxr_scene_update_attributes(gnxr_scene *s, int32_t first_triangle, int32_t 
         if (tri_n) { h_n.resize(9 * c); HIP_TRY(hipMemcpy(h_n.data(), tri_n, 9 * c * sizeof(float), hipMemcpyDeviceToHost)); r_n = h_n.data(); }
         if (tri_s) { h_s.resize(9 * c); HIP_TRY(hipMemcpy(h_s.data(), tri_s, 9 * c * sizeof(float), hipMemcpyDeviceToHost)); r_s = h_s.data(); }
     }
-    rc = s->each_copy([&](gnxr_scene *c, size_t i) -> int {
+    return s->each_copy([&](gnxr_scene *c, size_t i) -> int {
         AttrStage rep;
         const deform::AttrRows *rows = &prim.rows;
         hipStream_t cst = i == 0 ? st : nullptr;
@@ -168,9 +168,6 @@ int gnxr_scene_update_attributes(gnxr_scene *s, int32_t first_triangle, int32_t 
         HIP_TRY(hipStreamSynchronize(cst));
         return GNXR_OK;
     });
-    s->host->host_bvh_stale = true;    // cs.tri_uv / tri_n / tri_s lag the device until sync_host_bvh()
-    s->host->host_attr_stale = true;
-    return rc;
 }
 
 // test hook: what the primary's device holds per triangle, back in authoring order and unpadded (which: 0 uv, 6 floats per triangle;
@@ -179,10 +176,10 @@ int gnxr_scene_triangle_attributes(gnxr_scene *s, int32_t which, float *out, int
     if (!s || !n_floats) { set_error("null argument"); return GNXR_ERR_INVALID; }
     if (which < 0 || which > 2) { set_error("triangle_attributes: which = %d (0 uv, 1 normals, 2 tangents)", which); return GNXR_ERR_INVALID; }
     std::lock_guard<std::recursive_mutex> lock(s->render_mutex);
-    const CompiledScene &cs = s->cs;
+    const SceneFacts &cs = s->cs;
     const deform::AttrTables tab = attr_tables(s);
     const float4 *table = which == 0 ? tab.uv : which == 1 ? tab.n : tab.s;
-    const int nt = (int)cs.tris.size();
+    const int nt = (int)cs.n_triangles;
     const int64_t n = table ? (int64_t)nt * (which == 0 ? 6 : 9) : 0;
     *n_floats = n;
     if (!out || capacity_floats < n || n == 0) return GNXR_OK;
@@ -200,13 +197,10 @@ int gnxr_scene_recompute_normals(gnxr_scene *s, uint32_t flags, void *hip_stream
     if (!s) { set_error("null scene"); return GNXR_ERR_INVALID; }
     if (flags & ~(uint32_t)GNXR_NORMALS_FLIP) { set_error("unknown normals flags 0x%x", flags); return GNXR_ERR_INVALID; }
     std::lock_guard<std::recursive_mutex> lock(s->render_mutex);
-    if (s->cs.tri_n.empty()) return GNXR_OK;   // no smooth triangle anywhere
+    if (!s->cs.has_tri_n) return GNXR_OK;   // no smooth triangle anywhere
     const float sign = (flags & GNXR_NORMALS_FLIP) ? -1.f : 1.f;
     // every copy computes its own: the same vertices, the same order of every sum, the same bits
-    const int rc = s->each_copy([&](gnxr_scene *c, size_t i) -> int { return normals_apply(c, sign, i == 0 ? (hipStream_t)hip_stream : nullptr); });
-    s->host->host_bvh_stale = true;
-    s->host->host_attr_stale = true;
-    return rc;
+    return s->each_copy([&](gnxr_scene *c, size_t i) -> int { return normals_apply(c, sign, i == 0 ? (hipStream_t)hip_stream : nullptr); });
 }
 
 int gnxr_skin_vertices_device(const gnxr_skin_params *p, const float *d_rest, const int32_t *d_bone_index, const float *d_bone_weight, const float *d_bones,

@@ -4,25 +4,28 @@
 // the device tables of every copy in turn (each_copy), under the primary's render_mutex.
 #pragma once
 
-// the refit's tables go to a device at the first update of the scene (the flag is allocated last: it marks the set complete)
+// the refit's tables go to a device at the first update of the scene, from the host's seeds (the flag is allocated last: it marks the set
+// complete).  The seeds are released when the last copy has taken them; a copy whose upload failed finds them at the next edit.
 static int refit_tables(gnxr_scene *s) {
     if (s->upd_flag.p) return GNXR_OK;
-    const CompiledScene &cs = s->cs;
+    SceneFacts &cs = s->cs;
+    const RefitSeeds &seeds = cs.refit_seeds;
     int rc;
-    if ((rc = s->upd_corner.upload(cs.corner_vertex)) || (rc = s->upd_parent.upload(cs.node_parent)) || (rc = s->upd_node4_src.upload(cs.node4_src)) ||
-        (rc = s->upd_arrived.alloc(cs.nodes.size())) || (rc = s->upd_flag.alloc(1)))
+    if ((rc = s->upd_corner.upload(seeds.corner_vertex)) || (rc = s->upd_parent.upload(seeds.node_parent)) || (rc = s->upd_node4_src.upload(seeds.node4_src)) ||
+        (rc = s->upd_arrived.alloc(cs.n_nodes)) || (rc = s->upd_flag.alloc(1)))
         return rc;
+    if (--s->host->copies_awaiting_seeds == 0) cs.refit_seeds = RefitSeeds();
     return GNXR_OK;
 }
 
 // positions of vertices [first, first + n) staged in s->upd_xyz -> triangles, binary tree, 4-wide tree on the scene's (bound) device;
 // returns the refitted root box.  Topology, primitive order and every id stay as they are, so the one-triangle leaves still have the
-// min / max of their triangle's corners as their box (k_refit_fit computes it so) and CompiledScene::leaf1_from_verts keeps its value.
+// min / max of their triangle's corners as their box (k_refit_fit computes it so) and SceneFacts::leaf1_from_verts keeps its value.
 // move_lights (GNXR_UPDATE_MOVE_LIGHTS): the AREA_TRI light records are recomputed from the moved triangles (k_refit_lights); with h_lights
 // every record comes back with the root box, behind the same synchronisation: refit_world uploads the host copy over the device's afterwards.
 static int refit_apply(gnxr_scene *s, int first, int n, hipStream_t st, float root6[6], bool move_lights = false, std::vector<DLight> *h_lights = nullptr) {
-    const CompiledScene &cs = s->cs;
-    const int nt = (int)cs.tris.size(), nn = (int)cs.nodes.size(), nslots = (int)cs.node4_src.size();
+    const SceneFacts &cs = s->cs;
+    const int nt = (int)cs.n_triangles, nn = (int)cs.n_nodes, nslots = (int)(4 * cs.n_nodes4);
     hipLaunchKernelGGL(refit::k_refit_tris, dim3(grid_for(nt)), dim3(refit::kB), 0, st, s->tris.p, (const int *)s->upd_corner.p, nt, first, n, (const float *)s->upd_xyz.p);
     HIP_TRY(hipMemsetAsync(s->upd_arrived.p, 0, (size_t)nn * sizeof(unsigned int), st));
     hipLaunchKernelGGL(refit::k_refit_fit, dim3(grid_for(nn)), dim3(refit::kB), 0, st, nn, s->nodes.p, (const int *)s->upd_parent.p, s->upd_arrived.p, (const DTri *)s->tris.p,
@@ -74,7 +77,7 @@ extern "C" int gnxr_scene_update_vertices_ex(gnxr_scene *s, int32_t first_vertex
     if (!move_lights) {
         // emissive triangles keep their vertices (their DLight records hold them): refuse before anything is written
         int h_flag = 0;
-        const int nt = (int)s->cs.tris.size();
+        const int nt = (int)s->cs.n_triangles;
         HIP_TRY(hipMemsetAsync(s->upd_flag.p, 0, sizeof(int), st));
         hipLaunchKernelGGL(refit::k_refit_check, dim3(grid_for(nt)), dim3(refit::kB), 0, st, (const DTri *)s->tris.p, (const int *)s->upd_corner.p, nt, first_vertex, n_vertices,
                            (const float *)s->upd_xyz.p, s->upd_flag.p);
@@ -107,7 +110,6 @@ extern "C" int gnxr_scene_update_vertices_ex(gnxr_scene *s, int32_t first_vertex
     // uploads them: the power table (build_light_grid) reads cs.lights[i].area, and a stale copy would undo the kernel's work
     if (move_lights) s->cs.lights = std::move(moved);
     refit_world_bound(&s->cs, root6);
-    s->host->host_bvh_stale = true;
     return s->each_copy(refit_world);
 }
 
@@ -119,7 +121,7 @@ extern "C" int gnxr_scene_update_vertices(gnxr_scene *s, int32_t first_vertex, i
 // change: AREA_TRI le / two_sided / n_samples (its triangle stays; corners, area and normal come from the vertices the scene holds NOW,
 // which cs.lights carries: gnxr_scene_update_vertices_ex and gnxr_scene_rebuild_bvh keep that copy current); POINT / SPOT / DISTANT
 // everything; SKYBOX centre and radius; INFINITE nothing (its importance tables and texels are rebuilt by gnxr_scene_update_environment).
-static int build_light_update(const CompiledScene &cs, int first, int n, const gnxr_light *in, std::vector<DLight> *lights, std::vector<gnxr_light> *desc) {
+static int build_light_update(const SceneFacts &cs, int first, int n, const gnxr_light *in, std::vector<DLight> *lights, std::vector<gnxr_light> *desc) {
     *lights = cs.lights;
     *desc = cs.desc_lights;
     for (int k = 0; k < n; ++k) {
@@ -159,12 +161,12 @@ extern "C" int gnxr_scene_update_lights(gnxr_scene *s, int32_t first_light, int3
     std::vector<gnxr_light> descs;
     if (int rc = build_light_update(s->cs, first_light, n_lights, lights, &recs, &descs)) return rc;
     // 2. the uploads; one that fails puts the host's records, still the old ones, back on the devices already written
-    const int rc = s->each_copy([&](gnxr_scene *d, size_t) -> int {
+    const int rc = s->apply_or_put_back([&](gnxr_scene *d, size_t) -> int {
         const hipError_t e = hipMemcpy(d->lights.p, recs.data(), recs.size() * sizeof(DLight), hipMemcpyHostToDevice);
         if (e != hipSuccess) { set_error("HIP error: %s", hipGetErrorString(e)); return GNXR_ERR_RUNTIME; }
         return GNXR_OK;
-    });
-    if (rc) { const std::string why = get_error(); (void)s->each_copy(refit_world); set_error("%s", why.c_str()); return rc; }
+    }, refit_world);
+    if (rc) return rc;
     // 3. the host scene (the render plan reads desc_lights' n_samples) and a new light-selection table at the next render
     s->cs.lights = std::move(recs);
     s->cs.desc_lights = std::move(descs);
@@ -178,7 +180,7 @@ extern "C" int gnxr_scene_update_lights(gnxr_scene *s, int32_t first_light, int3
 // the authoring-order tables of k_material_tris go to a (bound) device at the first material edit of the scene
 static int material_tables(gnxr_scene *s) {
     if (s->mat_map.p) return GNXR_OK;
-    const CompiledScene &cs = s->cs;
+    const SceneFacts &cs = s->cs;
     int rc;
     if ((rc = s->mat_tri.upload(cs.tri_material)) || (rc = s->mat_own.upload(cs.tri_own_attr)) || (rc = s->mat_map.alloc(cs.mat_map.size()))) return rc;
     return GNXR_OK;
@@ -192,7 +194,7 @@ struct MaterialEdit {
 };
 
 // the state the host scene holds, in the form of an edit (what a failed upload puts back)
-static MaterialEdit material_current(const CompiledScene &cs, int first, int n) {
+static MaterialEdit material_current(const SceneFacts &cs, int first, int n) {
     MaterialEdit e;
     e.mt.materials = cs.materials; e.mt.materials_single = cs.materials_single; e.mt.aov_albedo = cs.aov_albedo;
     e.mt.material_authored = cs.material_authored; e.mt.mat_map = cs.mat_map;
@@ -201,7 +203,7 @@ static MaterialEdit material_current(const CompiledScene &cs, int first, int n) 
     return e;
 }
 
-static std::vector<DSphere> material_spheres(const CompiledScene &cs, const std::vector<gnxr_material> &mats) {
+static std::vector<DSphere> material_spheres(const SceneFacts &cs, const std::vector<gnxr_material> &mats) {
     std::vector<DSphere> sp = cs.spheres;
     for (size_t i = 0; i < cs.sphere_material.size(); ++i) {
         const int m = cs.sphere_material[i];
@@ -212,9 +214,9 @@ static std::vector<DSphere> material_spheres(const CompiledScene &cs, const std:
 
 // One copy's share of a material edit, on its (bound) device: the small tables over the device's (their buffers were sized for the worst
 // case by upload_scene), the edited range of the authored ids, then one pass over the leaf-order triangles.  Everything is queued on st and
-// waited for.  Nothing here reads the host's leaf-order tables: they may be stale after a rebuild, and DTri::prim is all the kernel needs.
+// waited for.  The device holds the only leaf-order tables, and DTri::prim is all the kernel needs of them.
 static int material_apply(gnxr_scene *s, const MaterialEdit &e, hipStream_t st) {
-    const CompiledScene &cs = s->cs;
+    const SceneFacts &cs = s->cs;
     const size_t ni = e.mt.materials.size();
     if (int rc = material_tables(s)) return rc;
     if (ni + 1 > s->materials.n || ni + 1 > s->materials_single.n || ni > s->material_authored.n || e.mt.mat_map.size() > s->mat_map.n || e.mt.aov_albedo.size() > s->aov_albedo.n ||
@@ -229,7 +231,7 @@ static int material_apply(gnxr_scene *s, const MaterialEdit &e, hipStream_t st) 
     HIP_TRY(hipMemcpyAsync(s->mat_map.p, e.mt.mat_map.data(), e.mt.mat_map.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(s->spheres.p, e.spheres.data(), e.spheres.size() * sizeof(DSphere), hipMemcpyHostToDevice, st));
     if (e.n > 0) HIP_TRY(hipMemcpyAsync(s->mat_tri.p + e.first, e.ids, (size_t)e.n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    const int nt = (int)cs.tris.size();
+    const int nt = (int)cs.n_triangles;
     hipLaunchKernelGGL(matedit::k_material_tris, dim3(grid_for(nt)), dim3(refit::kB), 0, st, s->tris.p, s->tri_class.p, nt, (const int *)s->mat_tri.p,
                        (const unsigned char *)s->mat_own.p, reinterpret_cast<const int4 *>(s->mat_map.p));
     HIP_TRY(hipGetLastError());
@@ -239,13 +241,8 @@ static int material_apply(gnxr_scene *s, const MaterialEdit &e, hipStream_t st) 
 
 // every copy takes the edit (the primary on the caller's stream); a copy that fails puts the host's state, still the old one, back on all
 static int material_apply_all(gnxr_scene *s, const MaterialEdit &e, hipStream_t st) {
-    const int rc = s->each_copy([&](gnxr_scene *d, size_t i) -> int { return material_apply(d, e, i == 0 ? st : nullptr); });
-    if (rc == GNXR_OK) return rc;
-    const std::string why = get_error();
-    const MaterialEdit old = material_current(s->cs, e.first, e.n);
-    (void)s->each_copy([&](gnxr_scene *d, size_t) -> int { return d->mat_map.p ? material_apply(d, old, nullptr) : GNXR_OK; });
-    set_error("%s", why.c_str());
-    return rc;
+    return s->apply_or_put_back([&](gnxr_scene *d, size_t i) -> int { return material_apply(d, e, i == 0 ? st : nullptr); },
+                                [&](gnxr_scene *d, size_t) -> int { return d->mat_map.p ? material_apply(d, material_current(s->cs, e.first, e.n), nullptr) : GNXR_OK; });
 }
 
 extern "C" int gnxr_scene_update_materials(gnxr_scene *s, int32_t first_material, int32_t n_materials, const gnxr_material *materials) {
@@ -258,7 +255,7 @@ extern "C" int gnxr_scene_update_materials(gnxr_scene *s, int32_t first_material
     }
     if (n_materials == 0) return GNXR_OK;
     std::lock_guard<std::recursive_mutex> lock(s->render_mutex);
-    CompiledScene &cs = s->cs;
+    SceneFacts &cs = s->cs;
     // 1. all records into a copy: a refusal leaves the scene as it was
     std::vector<gnxr_material> descs = cs.desc_materials;
     std::copy(materials, materials + n_materials, descs.begin() + first_material);
@@ -272,7 +269,6 @@ extern "C" int gnxr_scene_update_materials(gnxr_scene *s, int32_t first_material
     e.mt.move_to(&cs);
     cs.desc_materials = std::move(descs);
     cs.spheres = std::move(e.spheres);
-    s->host->host_bvh_stale = true;   // cs.tris / cs.tri_class lag the device until sync_host_bvh()
     return GNXR_OK;
 }
 
@@ -288,7 +284,7 @@ extern "C" int gnxr_scene_set_triangle_materials(gnxr_scene *s, int32_t first_tr
     std::lock_guard<std::recursive_mutex> lock(s->render_mutex);
     int rc = s->bind();
     if (rc) return rc;
-    CompiledScene &cs = s->cs;
+    SceneFacts &cs = s->cs;
     hipStream_t st = (hipStream_t)hip_stream;
     // the ids come to the host (one copy path for host and device memory, ordered after what the caller queued on its stream): which
     // authored materials triangles with attributes of their own use decides the attribute copies.  Validated before anything is written.
@@ -308,7 +304,6 @@ extern "C" int gnxr_scene_set_triangle_materials(gnxr_scene *s, int32_t first_tr
     if ((rc = material_apply_all(s, e, st)) != GNXR_OK) return rc;
     e.mt.move_to(&cs);
     cs.tri_material = std::move(tri_material);
-    s->host->host_bvh_stale = true;
     return GNXR_OK;
 }
 

@@ -8,7 +8,7 @@
 // call leaves the scene as it was.  What crosses to the host: the at most 21 texels of the pyramid's top three levels (InfiniteAreaLight::
 // Power's lookup runs over them on the host, in the code gnxr_scene_create runs) and the marginal's funcInt; what crosses to the device
 // besides the map: the Lanczos weights (px + py records, computed by the host's resample_weights) and the light records.  The host copies
-// of the tables (CompiledScene::env_*) are marked stale and fetched when the host-built spatial light table asks for them (sync_host_env).
+// of the tables (SceneFacts::env_*) are marked stale and fetched when the host-built spatial light table asks for them (sync_host_env).
 #pragma once
 
 namespace {
@@ -110,7 +110,7 @@ extern "C" int gnxr_scene_update_environment(gnxr_scene *s, const gnxr_light *li
         }
     }
     std::lock_guard<std::recursive_mutex> lock(s->render_mutex);
-    CompiledScene &cs = s->cs;
+    SceneFacts &cs = s->cs;
     int idx = -1;
     for (size_t i = 0; i < cs.desc_lights.size() && idx < 0; ++i)
         if (cs.desc_lights[i].type == GNXR_LIGHT_INFINITE) idx = (int)i;
@@ -159,11 +159,11 @@ extern "C" int gnxr_scene_update_environment(gnxr_scene *s, const gnxr_light *li
         env.marg_func_int = built[0].marg_func_int;
     }
     // 2. the only writes that can still fail: the light records.  A failure puts the host's records, still the old ones, back
-    rc = s->each_copy([&](gnxr_scene *c, size_t) -> int {
+    rc = s->apply_or_put_back([&](gnxr_scene *c, size_t) -> int {
         HIP_TRY(hipMemcpy(c->lights.p, recs.data(), recs.size() * sizeof(DLight), hipMemcpyHostToDevice));
         return GNXR_OK;
-    });
-    if (rc) { const std::string why = get_error(); (void)s->each_copy(refit_world); set_error("%s", why.c_str()); return rc; }
+    }, refit_world);
+    if (rc) return rc;
     // 3. the host scene, then the swaps
     cs.lights = std::move(recs);
     cs.desc_lights[idx] = *light;
@@ -186,7 +186,7 @@ extern "C" int gnxr_scene_env_tables(gnxr_scene *s, int32_t which, void *out, in
     if (!s || !n_bytes) { set_error("null argument"); return GNXR_ERR_INVALID; }
     if (which < 0 || which > 9) { set_error("environment table %d outside [0, 10)", which); return GNXR_ERR_INVALID; }
     std::lock_guard<std::recursive_mutex> lock(s->render_mutex);
-    const CompiledScene &cs = s->cs;
+    const SceneFacts &cs = s->cs;
     const DEnv &e = cs.env;
     const size_t W2 = cs.has_env ? e.dw : 0, H2 = cs.has_env ? e.dh : 0, on = cs.has_env ? 1 : 0;
     const void *d_src = nullptr, *h_src = nullptr;

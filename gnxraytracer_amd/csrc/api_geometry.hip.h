@@ -89,7 +89,7 @@ int geometry_refusal(int flags) {
 // One copy's build on its (bound) device from the arrays `d` (device memory there).  `first`: the primary, which validates for all and
 // fills *hh (the material tables included); the other copies read *hh.  Nothing of `s` changes.
 int geometry_on_device(gnxr_scene *s, const gnxr_geometry &d, hipStream_t st, bool first, GeomHost *hh, Rebuilt *out) {
-    const CompiledScene &cs = s->cs;
+    const SceneFacts &cs = s->cs;
     const int nt = d.n_triangles, n_lights = (int)cs.desc_lights.size(), n_chk = 1 + 2 * n_lights;
     const size_t n = (size_t)nt;
     const bool has_media = d.tri_medium_inside != nullptr, has_uv = d.tri_uv != nullptr, has_n = d.tri_n != nullptr, has_s = d.tri_s != nullptr;
@@ -179,33 +179,20 @@ int geometry_write_tables(gnxr_scene *s, const std::vector<DMaterial> &materials
         set_error("set_geometry: %zu internal materials do not fit the scene's tables", ni);
         return GNXR_ERR_RUNTIME;
     }
-    DTexTables rec;
-    rec.textures = s->textures.p; rec.texels = reinterpret_cast<const float4 *>(s->tex_texels.p); rec.ewa_lut = s->ewa_lut.p;
-    rec.tri_uv = uv; rec.tri_n = n; rec.tri_s = sv;
-    for (int k = 0; k < 2; ++k) {
-        const std::vector<DMaterial> &src = k == 0 ? materials : materials_single;
-        std::vector<DMaterial> up(src.size() + 1);
-        memset(&up[0], 0, sizeof(DMaterial));
-        memcpy(&up[0], &rec, sizeof(rec));
-        std::copy(src.begin(), src.end(), up.begin() + 1);
-        HIP_TRY(hipMemcpy((k == 0 ? s->materials : s->materials_single).p, up.data(), up.size() * sizeof(DMaterial), hipMemcpyHostToDevice));
-    }
+    if (int rc = s->write_material_tables(materials, materials_single, uv, n, sv)) return rc;
     HIP_TRY(hipMemcpy(s->aov_albedo.p, aov_albedo.data(), aov_albedo.size() * sizeof(float), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(s->material_authored.p, material_authored.data(), ni * sizeof(int32_t), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(s->spheres.p, spheres.data(), spheres.size() * sizeof(DSphere), hipMemcpyHostToDevice));
     return GNXR_OK;
 }
 
-// the host scene, once: every vector sized by the triangle or the vertex count takes its new size (contents at the next sync_host_bvh),
-// tables the new mesh lacks disappear, and what follows the mesh is recomputed as compile_scene computes it
+// the host scene, once: the counts and flags of the new mesh's tables (which exist on the devices only), the authoring-order tables of the
+// material edits, and what follows the mesh, recomputed as compile_scene computes it
 void geometry_commit_host(gnxr_scene *s, const gnxr_geometry &g, GeomHost &hh, Rebuilt &r) {
-    CompiledScene &cs = s->cs;
-    const size_t n = (size_t)g.n_triangles;
-    rebuild_commit_host(s, r);   // node tables, result scalars, the light records, both lazy mirrors marked
-    cs.tris.resize(n); cs.tri_class.resize(n); cs.leaf_of_prim.resize(n);
-    cs.leaf_boxes.resize(8 * n); cs.corner_vertex.resize(3 * n);
-    cs.tri_media.resize(r.tri_media.p ? 2 * n : 0);
-    cs.tri_uv.resize(r.tri_uv.p ? 8 * n : 0); cs.tri_n.resize(r.tri_n.p ? 12 * n : 0); cs.tri_s.resize(r.tri_s.p ? 12 * n : 0);
+    SceneFacts &cs = s->cs;
+    rebuild_commit_host(s, r);   // node counts, result scalars, the light records
+    cs.n_triangles = (size_t)g.n_triangles;
+    cs.has_tri_media = r.tri_media.p != nullptr; cs.has_tri_uv = r.tri_uv.p != nullptr; cs.has_tri_n = r.tri_n.p != nullptr; cs.has_tri_s = r.tri_s.p != nullptr;
     cs.n_vertices = g.n_vertices;
     cs.tri_material = std::move(hh.tri_material);
     cs.tri_own_attr = std::move(hh.own_attr);
@@ -237,7 +224,7 @@ extern "C" int gnxr_scene_set_geometry(gnxr_scene *s, const gnxr_geometry *g, vo
     if (!g->vertices || !g->indices || !g->tri_material) { set_error("set_geometry: null vertices, indices or tri_material"); return GNXR_ERR_INVALID; }
     if ((g->tri_medium_inside != nullptr) != (g->tri_medium_outside != nullptr)) { set_error("set_geometry: only one of the two medium arrays"); return GNXR_ERR_INVALID; }
     std::lock_guard<std::recursive_mutex> lock(s->render_mutex);
-    const CompiledScene &cs = s->cs;
+    const SceneFacts &cs = s->cs;
     if (!g->tri_light)
         for (const gnxr_light &l : cs.desc_lights)
             if (l.type == GNXR_LIGHT_AREA_TRI) { set_error("set_geometry: null tri_light in a scene with AREA_TRI lights"); return GNXR_ERR_INVALID; }
@@ -278,20 +265,15 @@ extern "C" int gnxr_scene_set_geometry(gnxr_scene *s, const gnxr_geometry *g, vo
     for (size_t i = 1; i < built.size(); ++i)
         if (!built[i].same_tree(built[0])) { set_error("set_geometry: the devices disagree (internal error)"); return GNXR_ERR_RUNTIME; }
     // 2. the only writes that can still fail; a failure puts the tables the host scene still describes back on every copy
-    rc = s->each_copy([&](gnxr_scene *c, size_t i) -> int {
+    rc = s->apply_or_put_back([&](gnxr_scene *c, size_t i) -> int {
         const Rebuilt &r = built[i];
         if (int rc_ = refit_tables(c)) return rc_;   // the swaps below exchange the refit's tables: the set must exist (its flag marks it complete)
         return geometry_write_tables(c, hh.mt.materials, hh.mt.materials_single, hh.mt.aov_albedo, hh.mt.material_authored, hh.spheres, r.tri_uv.p, r.tri_n.p, r.tri_s.p);
+    }, [&](gnxr_scene *c, size_t) -> int {
+        const DTexTables old = c->tex_tables(c->tri_uv.p, c->tri_n.p, c->tri_s.p);
+        return geometry_write_tables(c, cs.materials, cs.materials_single, cs.aov_albedo, cs.material_authored, cs.spheres, old.tri_uv, old.tri_n, old.tri_s);
     });
-    if (rc) {
-        const std::string why = get_error();
-        (void)s->each_copy([&](gnxr_scene *c, size_t) -> int {
-            const DTexTables old = c->tex_tables(c->tri_uv.p, c->tri_n.p, c->tri_s.p);
-            return geometry_write_tables(c, cs.materials, cs.materials_single, cs.aov_albedo, cs.material_authored, cs.spheres, old.tri_uv, old.tri_n, old.tri_s);
-        });
-        set_error("%s", why.c_str());
-        return rc;
-    }
+    if (rc) return rc;
     // 3. the host scene, then the swaps, then what depends on the world bound and the light records
     geometry_commit_host(s, *g, hh, built[0]);
     for (size_t i = 0; i < s->n_copies(); ++i) geometry_commit_copy(s->copy(i), built[i]);

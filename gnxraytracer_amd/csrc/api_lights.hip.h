@@ -3,7 +3,7 @@
 //
 // The host compiles and checks the whole list first (compile_light_list, scene_compile.cpp).  Every device of the handle then takes the
 // records into a FRESH buffer (the count changes, and the old records must survive a failure), binds the AREA_TRI records to their
-// leaf-order triangles (k_lights_scatter, k_lights_bind: the host's leaf_of_prim may be stale and is not asked) and lets k_refit_lights
+// leaf-order triangles (k_lights_scatter, k_lights_bind: the device holds the only leaf order) and lets k_refit_lights
 // compute corners, area and normal.  DTri::light is the one thing written in place: a failure on any copy puts the old values, which the
 // still unchanged host scene describes, back on every copy.  Only then does the host scene change, once, and the copies swap buffers.
 // What crosses to the host: the finished records (gnxr_scene_update_lights and the power table read them) and one flag.
@@ -34,7 +34,7 @@ int lights_bind_back(gnxr_scene *s, const std::vector<int32_t> &light_of_prim) {
 // One copy's share on its (bound) device: `recs` (compile_light_list's, max(1, n) of them) and `infinite` into fresh buffers, DTri::light
 // in place, the finished records into out->h_lights.  Everything is queued on st and waited for.
 int lights_on_device(gnxr_scene *s, const std::vector<DLight> &recs, int n_lights, const std::vector<int32_t> &infinite, hipStream_t st, LightsBuilt *out) {
-    const CompiledScene &cs = s->cs;
+    const SceneFacts &cs = s->cs;
     const int nt = (int)cs.tri_material.size();
     DevBuf<int32_t> lop;
     DevBuf<int> flag;
@@ -47,7 +47,7 @@ int lights_on_device(gnxr_scene *s, const std::vector<DLight> &recs, int n_light
     HIP_TRY(hipMemsetAsync(flag.p, 0, sizeof(int), st));
     if (n_lights > 0) hipLaunchKernelGGL(lightedit::k_lights_scatter, dim3(grid_for(n_lights)), dim3(refit::kB), 0, st, (const DLight *)out->lights.p, n_lights, lop.p, nt);
     hipLaunchKernelGGL(lightedit::k_lights_bind, dim3(grid_for(nt)), dim3(refit::kB), 0, st, s->tris.p, nt, (const int *)lop.p, out->lights.p, n_lights,
-                       cs.tri_n.empty() ? (const float *)nullptr : (const float *)s->tri_n.p, cs.tri_s.empty() ? (const float *)nullptr : (const float *)s->tri_s.p, flag.p);
+                       cs.has_tri_n ? (const float *)s->tri_n.p : (const float *)nullptr, cs.has_tri_s ? (const float *)s->tri_s.p : (const float *)nullptr, flag.p);
     if (n_lights > 0) hipLaunchKernelGGL(refit::k_refit_lights, dim3(grid_for(n_lights)), dim3(refit::kB), 0, st, out->lights.p, n_lights, (const DTri *)s->tris.p, nt);
     HIP_TRY(hipGetLastError());
     int h_flag = 0;
@@ -66,7 +66,7 @@ extern "C" int gnxr_scene_set_lights(gnxr_scene *s, const gnxr_light *lights, in
     if (n_lights < 0) { set_error("set_lights: %d lights", n_lights); return GNXR_ERR_INVALID; }
     if (n_lights > 0 && !lights) { set_error("null light array"); return GNXR_ERR_INVALID; }
     std::lock_guard<std::recursive_mutex> lock(s->render_mutex);
-    CompiledScene &cs = s->cs;
+    SceneFacts &cs = s->cs;
     // 1. the whole list, compiled and checked on the host: a refusal has touched nothing
     std::vector<DLight> recs;
     std::vector<int32_t> infinite, light_of_prim;
@@ -80,20 +80,15 @@ extern "C" int gnxr_scene_set_lights(gnxr_scene *s, const gnxr_light *lights, in
         if (memcmp(built[i].h_lights.data(), built[0].h_lights.data(), recs.size() * sizeof(DLight)) != 0) { set_error("set_lights: the devices disagree (internal error)"); rc = GNXR_ERR_RUNTIME; }
     if (rc) {
         // DTri::light was written in place: the old values, from the list the host scene still holds, back on every copy
-        const std::string why = get_error();
         std::vector<int32_t> old(light_of_prim.size(), -1);
         for (size_t l = 0; l < cs.desc_lights.size(); ++l)
             if (cs.desc_lights[l].type == GNXR_LIGHT_AREA_TRI && (size_t)cs.desc_lights[l].tri < old.size()) old[cs.desc_lights[l].tri] = (int32_t)l;
-        (void)s->each_copy([&](gnxr_scene *c, size_t) -> int { (void)lights_bind_back(c, old); (void)hipGetLastError(); return GNXR_OK; });
-        set_error("%s", why.c_str());
-        return rc;
+        return s->put_back_after(rc, [&](gnxr_scene *c, size_t) -> int { (void)lights_bind_back(c, old); (void)hipGetLastError(); return GNXR_OK; });
     }
     // 3. the host scene, once ...
     cs.lights = std::move(built[0].h_lights);
     cs.desc_lights.assign(lights, lights + n_lights);
     cs.infinite_lights = std::move(infinite);
-    if (!s->host->host_bvh_stale)   // the leaf-order mirror is current: patched; a stale one takes the new words at the next sync_host_bvh
-        for (DTri &t : cs.tris) t.light = light_of_prim[t.prim];
     // ... then every copy: pointer swaps, and a new light-selection table at the next render
     for (size_t i = 0; i < s->n_copies(); ++i) {
         gnxr_scene *c = s->copy(i);
@@ -111,7 +106,7 @@ extern "C" int gnxr_scene_light_tables(gnxr_scene *s, int32_t which, void *out, 
     if (!s || !n_bytes) { set_error("null argument"); return GNXR_ERR_INVALID; }
     if (which < 0 || which > 1) { set_error("light table %d outside [0, 2)", which); return GNXR_ERR_INVALID; }
     std::lock_guard<std::recursive_mutex> lock(s->render_mutex);
-    const CompiledScene &cs = s->cs;
+    const SceneFacts &cs = s->cs;
     const int nt = (int)cs.tri_material.size();
     const size_t bytes = which == 0 ? cs.desc_lights.size() * sizeof(DLight) : (size_t)nt * sizeof(int32_t);
     *n_bytes = (int64_t)bytes;

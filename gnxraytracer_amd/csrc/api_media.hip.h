@@ -110,7 +110,7 @@ extern "C" int gnxr_scene_update_media(gnxr_scene *s, int32_t first_medium, int3
     if (!s) { set_error("null scene"); return GNXR_ERR_INVALID; }
     if (n_media > 0 && !media) { set_error("null medium array"); return GNXR_ERR_INVALID; }
     std::lock_guard<std::recursive_mutex> lock(s->render_mutex);
-    CompiledScene &cs = s->cs;
+    SceneFacts &cs = s->cs;
     const int64_t have = (int64_t)cs.media.size();   // (the number of media never changes)
     if (have == 0) { set_error("the scene was created without media (the medium list of a scene is fixed)"); return GNXR_ERR_UNSUPPORTED; }
     if (first_medium < 0 || n_media < 0 || (int64_t)first_medium + n_media > have) {
@@ -198,18 +198,16 @@ extern "C" int gnxr_scene_update_media(gnxr_scene *s, int32_t first_medium, int3
             if (lay.offset[i] >= 0) recs[i].density_offset = (int32_t)lay.offset[i];
     }
     // 3. the only writes that can still fail: the medium records.  A failure puts the host's records, still the old ones, back
-    rc = s->each_copy([&](gnxr_scene *c, size_t) -> int {
+    rc = s->apply_or_put_back([&](gnxr_scene *c, size_t) -> int {
         HIP_TRY(hipMemcpy(c->dmedia.p, recs.data(), recs.size() * sizeof(DMedium), hipMemcpyHostToDevice));
         return GNXR_OK;
-    });
-    if (rc) { const std::string why = get_error(); (void)s->each_copy(media_records_back); set_error("%s", why.c_str()); return rc; }
+    }, media_records_back);
+    if (rc) return rc;
     // 4. the host scene, then the swaps (the old buffers are released with `built`: hipFree waits for what still reads them)
     cs.media = std::move(descs);
     cs.dmedia = std::move(recs);
-    if (new_grids) {
-        std::vector<float>().swap(cs.grid_density);   // stale from here on: the devices hold the grids
+    if (new_grids)
         for (size_t i = 0; i < s->n_copies(); ++i) swap_buf(s->copy(i)->grid_density, built[i].grids);
-    }
     return GNXR_OK;
 }
 
@@ -219,7 +217,7 @@ extern "C" int gnxr_scene_media_tables(gnxr_scene *s, int32_t which, int32_t med
     if (!s || !n_bytes) { set_error("null argument"); return GNXR_ERR_INVALID; }
     if (which < 0 || which > 1) { set_error("media table %d outside [0, 2)", which); return GNXR_ERR_INVALID; }
     std::lock_guard<std::recursive_mutex> lock(s->render_mutex);
-    const CompiledScene &cs = s->cs;
+    const SceneFacts &cs = s->cs;
     const size_t n = cs.media.size();
     if (which == 1 && (medium < 0 || (size_t)medium >= n)) { set_error("medium %d outside the scene's %zu media", medium, n); return GNXR_ERR_INVALID; }
     const size_t bytes = which == 0 ? n * sizeof(DMedium)

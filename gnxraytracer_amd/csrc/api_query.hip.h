@@ -15,7 +15,7 @@ static const long long kQueryLaunchMax = 1ll << 30;
 
 // the tables the walk, the hit record and a BSDF read (device_scene() would also read the light and sampler state, which a render may be rebuilding)
 static DScene query_device_scene(gnxr_scene *r) {
-    const CompiledScene &cs = r->cs;
+    const SceneFacts &cs = r->cs;
     DScene sc = {};
     sc.nodes = reinterpret_cast<const float4 *>(r->nodes.p);
     sc.nodes4 = reinterpret_cast<const float4 *>(r->nodes4.p);

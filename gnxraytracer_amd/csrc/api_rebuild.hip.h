@@ -3,7 +3,7 @@
 //
 // Every device of the handle builds into FRESH buffers (rebuild_on_device); only when all of them have reported clean flags and the same
 // tree are the buffers swapped into the copies (rebuild_commit_copy, pointer swaps only; the one device write that could still fail, the
-// DTexTables record, is made before them: rebuild_point_tables) and the host scene told once (rebuild_commit_host), so a refused or failed
+// DTexTables record, is made before them: rebuild_point_tables) and the host scene told its facts once (rebuild_commit_host), so a refused or failed
 // call leaves the scene as it was.  What crosses to the host:
 // the six floats of the centroid bounds, the run / treelet / level counts of the HLBVH stage, the node counts, and the result scalars
 // (rebuild::R_*); and the DLight records, whose host copy refit_world uploads again after the next gnxr_scene_update_vertices (and from
@@ -47,16 +47,16 @@ struct RebuildSource {
     const DLight *lights = nullptr;
     bool refit_lights = false;
 };
-// the tables `s` holds (the refit's corner table goes to the device first; after a rebuild the device copy is the current one)
+// the tables `s` holds (the refit's corner table goes to the device first; after a rebuild the device's is the only one)
 int rebuild_source_of(gnxr_scene *s, RebuildSource *src) {
-    const CompiledScene &cs = s->cs;
+    const SceneFacts &cs = s->cs;
     if (int rc = refit_tables(s)) return rc;
-    src->n = (int)cs.tris.size();
+    src->n = (int)cs.n_triangles;
     src->tris = s->tris.p; src->tri_class = s->tri_class.p; src->corner = s->upd_corner.p;
-    src->tri_media = cs.tri_media.empty() ? nullptr : s->tri_media.p;
-    src->tri_uv = cs.tri_uv.empty() ? nullptr : s->tri_uv.p;
-    src->tri_n = cs.tri_n.empty() ? nullptr : s->tri_n.p;
-    src->tri_s = cs.tri_s.empty() ? nullptr : s->tri_s.p;
+    src->tri_media = cs.has_tri_media ? s->tri_media.p : nullptr;
+    src->tri_uv = cs.has_tri_uv ? s->tri_uv.p : nullptr;
+    src->tri_n = cs.has_tri_n ? s->tri_n.p : nullptr;
+    src->tri_s = cs.has_tri_s ? s->tri_s.p : nullptr;
     src->lights = s->lights.p;
     return GNXR_OK;
 }
@@ -64,7 +64,7 @@ int rebuild_source_of(gnxr_scene *s, RebuildSource *src) {
 // the tree over the triangles of `src` on the (bound) device of `s`, into `r`; nothing of `s` changes
 int rebuild_on_device(gnxr_scene *s, const RebuildSource &src, hipStream_t st, Rebuilt *r) {
     using namespace rebuild;
-    const CompiledScene &cs = s->cs;
+    const SceneFacts &cs = s->cs;
     const int n = src.n;
     const int n_lights = (int)cs.desc_lights.size();
     int rc;
@@ -198,22 +198,17 @@ int rebuild_on_device(gnxr_scene *s, const RebuildSource &src, hipStream_t st, R
 bool rebuild_has_attrs(const Rebuilt &r) { return r.tri_uv.p || r.tri_n.p || r.tri_s.p; }
 int rebuild_point_tables(gnxr_scene *s, const Rebuilt &r, bool to_new) {
     if (!rebuild_has_attrs(r)) return GNXR_OK;
-    const DTexTables rec = to_new ? s->tex_tables(r.tri_uv.p, r.tri_n.p, r.tri_s.p) : s->tex_tables(s->tri_uv.p, s->tri_n.p, s->tri_s.p);
-    HIP_TRY(hipMemcpy(s->materials.p, &rec, sizeof(rec), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(s->materials_single.p, &rec, sizeof(rec), hipMemcpyHostToDevice));
-    return GNXR_OK;
+    const DTexTables at = to_new ? s->tex_tables(r.tri_uv.p, r.tri_n.p, r.tri_s.p) : s->tex_tables(s->tri_uv.p, s->tri_n.p, s->tri_s.p);
+    return s->write_material_tables(s->cs.materials, s->cs.materials_single, at.tri_uv, at.tri_n, at.tri_s);   // (the materials stay what they are)
 }
 
-// The new tree into the scene, in two steps that cannot fail.  First the host scene, once, from the primary's result: sizes now, contents
-// at the next sync_host_bvh.
+// The new tree into the scene, in two steps that cannot fail.  First the host scene, once, from the primary's result: the facts of the
+// tree (the tables themselves exist on the devices only).
 void rebuild_commit_host(gnxr_scene *s, Rebuilt &r) {
-    CompiledScene &cs = s->cs;
-    cs.nodes.resize(r.n_nodes); cs.node_parent.resize(r.n_nodes);
-    cs.nodes4.resize(r.n_nodes4); cs.node4_src.resize(4 * (size_t)r.n_nodes4);
+    SceneFacts &cs = s->cs;
+    cs.n_nodes = (size_t)r.n_nodes; cs.n_nodes4 = (size_t)r.n_nodes4;
     cs.root4 = r.root4; cs.stack4_need = r.stack4_need; cs.bvh_max_depth = r.max_depth; cs.leaf1_from_verts = r.leaf1_from_verts;
     cs.lights = std::move(r.h_lights);
-    s->host->host_bvh_stale = true;
-    s->host->host_order_stale = true;
 }
 // ... then every copy's tables: pointer swaps, and what the copy derives from the host scene
 void rebuild_commit_copy(gnxr_scene *s, Rebuilt &r) {
@@ -247,11 +242,9 @@ extern "C" int gnxr_scene_rebuild_bvh(gnxr_scene *s, void *hip_stream) {
     for (size_t i = 1; i < built.size(); ++i)
         if (!built[i].same_tree(built[0])) { set_error("BVH rebuild: the devices disagree (internal error)"); return GNXR_ERR_RUNTIME; }
     // 2. the only writes that can still fail; a failure points every record back at the tables the scene holds
-    if ((rc = s->each_copy([&](gnxr_scene *c, size_t i) { return rebuild_point_tables(c, built[i], /*to_new=*/true); }))) {
-        const std::string why = get_error();
-        (void)s->each_copy([&](gnxr_scene *c, size_t i) { return rebuild_point_tables(c, built[i], /*to_new=*/false); });
-        set_error("%s", why.c_str()); return rc;
-    }
+    if ((rc = s->apply_or_put_back([&](gnxr_scene *c, size_t i) { return rebuild_point_tables(c, built[i], /*to_new=*/true); },
+                                   [&](gnxr_scene *c, size_t i) { return rebuild_point_tables(c, built[i], /*to_new=*/false); })))
+        return rc;
     // 3. the host scene, then the swaps
     rebuild_commit_host(s, built[0]);
     for (size_t i = 0; i < s->n_copies(); ++i) rebuild_commit_copy(s->copy(i), built[i]);
@@ -263,11 +256,11 @@ extern "C" int gnxr_scene_bvh4(const gnxr_scene *sc, void *nodes128, int64_t nod
     if (!sc || !n_nodes4) { set_error("bad argument"); return GNXR_ERR_INVALID; }
     gnxr_scene *s = const_cast<gnxr_scene *>(sc);
     std::lock_guard<std::recursive_mutex> lock(s->render_mutex);
-    *n_nodes4 = (int64_t)s->cs.nodes4.size();
+    *n_nodes4 = (int64_t)s->cs.n_nodes4;
     if (root4) *root4 = s->cs.root4;
     if (stack_need) *stack_need = s->cs.stack4_need;
     if (!nodes128 || node_capacity < *n_nodes4) return GNXR_OK;
     if (int rc = s->bind()) return rc;
-    HIP_TRY(hipMemcpy(nodes128, s->nodes4.p, s->cs.nodes4.size() * sizeof(DNode4), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(nodes128, s->nodes4.p, s->cs.n_nodes4 * sizeof(DNode4), hipMemcpyDeviceToHost));
     return GNXR_OK;
 }

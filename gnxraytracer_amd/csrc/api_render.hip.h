@@ -25,7 +25,7 @@ static TraceLaunch trace_launch(const gnxr_scene *s, bool wide, bool spheres, lo
     t.lds_entries = std::min(std::min(t.entries, Knobs::trace_lds_levels()), std::max(2, (int)(((160 * 1024) / per_cu - 1024 - fixed_b) / (kBlock * sizeof(int)))));
     t.spill_needed = t.entries > t.lds_entries;
     t.lds = (size_t)t.lds_entries * kBlock * sizeof(int) + fixed_b;
-    t.n_top = (int)std::min<size_t>(kTopCache, s->cs.root4 >= 0 ? s->cs.nodes4.size() : 0);
+    t.n_top = (int)std::min<size_t>(kTopCache, s->cs.root4 >= 0 ? s->cs.n_nodes4 : 0);
     // persistent waves: enough blocks to fill the chip, never more than the work needs
     t.blocks = (int)std::min<long long>((long long)g_num_cus * per_cu, (total + kBlock - 1) / kBlock);
     return t;
@@ -136,7 +136,7 @@ enum ShadeQueueKernel { SHADE_Q_NONE = 0, SHADE_Q_DIFFUSE, SHADE_Q_GLOSSY, SHADE
 // rough-dielectric kernels carry none of the other's code.  Needed are class 0, the kinds present, class 2 and class 3 / the escape queue
 // if present; beyond four, all class-1 materials share queue 1 and k_shade<LM_GLOSSY>.  Sphere hits get their class from the traversal
 // kernels (pclass), which know no kinds: a scene with spheres keeps the shared queue.
-static void plan_shade_queues(const CompiledScene &cs, RenderPlan *pl) {
+static void plan_shade_queues(const SceneFacts &cs, RenderPlan *pl) {
     int *qk = pl->queue_kernel;
     qk[0] = SHADE_Q_DIFFUSE;
     qk[1] = (pl->class_mask & 2) ? SHADE_Q_GLOSSY : SHADE_Q_NONE;
@@ -166,7 +166,7 @@ static const double kStateFreeFraction = 0.45;                              // o
 static const unsigned long long kStateCapBytes = 150ull * 1000 * 1000 * 1000;   // never more path state than this
 
 // Validates the parameters and derives what follows from them and the scene alone.  No device is touched.
-static int plan_render(const CompiledScene &cs, const gnxr_render_params *pin, const RaySource *src, const ViewSource *views, const PixelListSource *pix, RenderPlan *out) {
+static int plan_render(const SceneFacts &cs, const gnxr_render_params *pin, const RaySource *src, const ViewSource *views, const PixelListSource *pix, RenderPlan *out) {
     RenderPlan &pl = *out;
     gnxr_render_params &p = pl.p;
     p = *pin;

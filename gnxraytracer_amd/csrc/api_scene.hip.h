@@ -1,5 +1,5 @@
 // api_scene.hip.h -- gnxr_scene: one copy of a scene (its device tables, per-render state and light-selection table) and the host scene
-// all copies of a handle share.
+// all copies of a handle share: the scene's facts, no copy of anything the devices hold in leaf or node order.
 // Part of api.hip's translation unit (after api_common.hip.h).
 #pragma once
 
@@ -49,20 +49,21 @@ struct RenderState {
     VolPackSet pack_set(bool alt);
 };
 
-// The host side of a handle: ONE per gnxr_scene_create, shared by the copies on every device of gnxr_init_devices.  Written only under the
-// primary's render_mutex (the editing calls, sync_host_bvh); the workers of render_sharded and the calls bound to a replica read it.
+// The host side of a handle: ONE per gnxr_scene_create, shared by the copies on every device of gnxr_init_devices.  It holds the scene's
+// FACTS only (SceneFacts, host_scene.h): what the host authored or keeps reading.  Nothing in leaf or node order lives here -- the devices
+// hold the only copy of the geometry, attribute, media, texel and grid tables, and the editing calls change it there -- except the refit's
+// seeds until every copy has uploaded them (SceneFacts::refit_seeds).  Written only under the primary's render_mutex (the editing calls);
+// the workers of render_sharded and the calls bound to a replica read it.
 struct SceneHost {
-    CompiledScene cs;
-    bool host_bvh_stale = false;     // after an update cs.nodes / nodes4 / tris / leaf_boxes lag the primary's device until sync_host_bvh()
-    bool host_order_stale = false;   // after gnxr_scene_rebuild_bvh the host copies of what is held in leaf or node order lag too (the upd_* tables are current)
-    bool host_attr_stale = false;    // after gnxr_scene_update_attributes / gnxr_scene_recompute_normals cs.tri_uv / tri_n / tri_s lag the primary's device until sync_host_bvh() (with host_bvh_stale)
+    SceneFacts cs;
+    size_t copies_awaiting_seeds = 0;   // copies of the scene that have not uploaded cs.refit_seeds yet (refit_tables releases the seeds at 0)
     bool host_env_stale = false;     // after gnxr_scene_update_environment cs.env_texels / env_texels4 / env_cond_* / env_marg_* lag the devices until sync_host_env()
     std::mutex env_mutex;            // sync_host_env may be reached from the worker of any copy (ensure_grid)
 };
 
 struct gnxr_scene {
     const std::shared_ptr<SceneHost> host;
-    CompiledScene &cs;   // host->cs
+    SceneFacts &cs;   // host->cs
     explicit gnxr_scene(int device_, std::shared_ptr<SceneHost> h = std::make_shared<SceneHost>()) : host(std::move(h)), cs(host->cs), device(device_) {}
     // device tables
     DevBuf<DNode> nodes;
@@ -74,7 +75,7 @@ struct gnxr_scene {
     DevBuf<DMaterial> materials, materials_single;
     DevBuf<DTexture> textures;
     DevBuf<float> tex_texels, ewa_lut, tri_uv, tri_n, tri_s;
-    DevBuf<float> aov_albedo;            // feature buffers (api_aov.hip.h): CompiledScene::aov_albedo / material_authored
+    DevBuf<float> aov_albedo;            // feature buffers (api_aov.hip.h): SceneFacts::aov_albedo / material_authored
     DevBuf<int32_t> material_authored;
     DevBuf<DLight> lights;
     DevBuf<int32_t> infinite;
@@ -121,16 +122,30 @@ struct gnxr_scene {
         (void)hipGetLastError(); (void)hipSetDevice(device);
         return rc;
     }
+    // An edit that writes the copies in place: apply(copy, i) on every copy; after a failure put_back(copy, i) on every copy (its own
+    // status does not count) and the failure's message and status stand.  put_back_after is the second half, for a failure found elsewhere.
+    template <typename F>
+    int put_back_after(int rc, F &&put_back) {
+        const std::string why = get_error();
+        (void)each_copy(put_back);
+        set_error("%s", why.c_str());
+        return rc;
+    }
+    template <typename A, typename F>
+    int apply_or_put_back(A &&apply, F &&put_back) {
+        const int rc = each_copy(apply);
+        return rc == GNXR_OK ? rc : put_back_after(rc, put_back);
+    }
     DevBuf<float4> shard_out;            // a replica's full-size output plane; its rows are peer-copied into the primary's image
     void *h_stage = nullptr;             // pinned: a replica's rows on their way to the primary when the two devices have no peer access
     size_t h_stage_bytes = 0;
-    // gnxr_scene_update_vertices: the refit's tables (CompiledScene::corner_vertex / node_parent / node4_src, uploaded at the first update),
+    // gnxr_scene_update_vertices: the refit's tables (SceneFacts::refit_seeds, uploaded at the first update; a rebuild swaps its own in),
     // the arrival counters of k_refit_fit, the staged positions and the emissive-vertex flag
     DevBuf<int32_t> upd_corner, upd_parent, upd_node4_src;
     DevBuf<unsigned int> upd_arrived;
     DevBuf<float> upd_xyz;
     DevBuf<int> upd_flag;
-    // gnxr_scene_update_materials / gnxr_scene_set_triangle_materials: CompiledScene::tri_material / tri_own_attr / mat_map, uploaded at the
+    // gnxr_scene_update_materials / gnxr_scene_set_triangle_materials: SceneFacts::tri_material / tri_own_attr / mat_map, uploaded at the
     // first edit (material_tables; the map is allocated last: it marks the set complete) and kept current by every edit after it
     DevBuf<int32_t> mat_tri, mat_map;
     DevBuf<uint8_t> mat_own;
@@ -144,37 +159,6 @@ struct gnxr_scene {
     std::vector<DCamera> h_view_cams;
 
     int bind() const { HIP_TRY(hipSetDevice(device)); return GNXR_OK; }
-    // the host copies of the geometry tables, downloaded on demand after gnxr_scene_update_vertices / gnxr_scene_rebuild_bvh (only
-    // readers pay for them; the rebuild has already given the vectors their new sizes).  Called on the handle: the primary's device is read.
-    int sync_host_bvh() {
-        if (!host->host_bvh_stale) return GNXR_OK;
-        if (int rc = bind()) return rc;
-        HIP_TRY(hipMemcpy(cs.nodes.data(), nodes.p, cs.nodes.size() * sizeof(DNode), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(cs.nodes4.data(), nodes4.p, cs.nodes4.size() * sizeof(DNode4), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(cs.tris.data(), tris.p, cs.tris.size() * sizeof(DTri), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(cs.leaf_boxes.data(), leaf_boxes.p, cs.leaf_boxes.size() * sizeof(float), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(cs.tri_class.data(), tri_class.p, cs.tri_class.size(), hipMemcpyDeviceToHost));   // (a material edit rewrites it on the device)
-        if (host->host_order_stale) {
-            HIP_TRY(hipMemcpy(cs.corner_vertex.data(), upd_corner.p, cs.corner_vertex.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(cs.node_parent.data(), upd_parent.p, cs.node_parent.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(cs.node4_src.data(), upd_node4_src.p, cs.node4_src.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-            if (!cs.tri_media.empty()) HIP_TRY(hipMemcpy(cs.tri_media.data(), tri_media.p, cs.tri_media.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-            if (!cs.tri_uv.empty()) HIP_TRY(hipMemcpy(cs.tri_uv.data(), tri_uv.p, cs.tri_uv.size() * sizeof(float), hipMemcpyDeviceToHost));
-            if (!cs.tri_n.empty()) HIP_TRY(hipMemcpy(cs.tri_n.data(), tri_n.p, cs.tri_n.size() * sizeof(float), hipMemcpyDeviceToHost));
-            if (!cs.tri_s.empty()) HIP_TRY(hipMemcpy(cs.tri_s.data(), tri_s.p, cs.tri_s.size() * sizeof(float), hipMemcpyDeviceToHost));
-            for (size_t li = 0; li < cs.tris.size(); ++li) cs.leaf_of_prim[cs.tris[li].prim] = (int32_t)li;
-            host->host_order_stale = false;
-            host->host_attr_stale = false;
-        }
-        if (host->host_attr_stale) {
-            if (!cs.tri_uv.empty()) HIP_TRY(hipMemcpy(cs.tri_uv.data(), tri_uv.p, cs.tri_uv.size() * sizeof(float), hipMemcpyDeviceToHost));
-            if (!cs.tri_n.empty()) HIP_TRY(hipMemcpy(cs.tri_n.data(), tri_n.p, cs.tri_n.size() * sizeof(float), hipMemcpyDeviceToHost));
-            if (!cs.tri_s.empty()) HIP_TRY(hipMemcpy(cs.tri_s.data(), tri_s.p, cs.tri_s.size() * sizeof(float), hipMemcpyDeviceToHost));
-            host->host_attr_stale = false;
-        }
-        host->host_bvh_stale = false;
-        return GNXR_OK;
-    }
     // the host copies of the environment tables, downloaded on demand after gnxr_scene_update_environment (their one reader is the
     // host-built spatial light table: build_light_grid).  Every copy holds the same tables: the (bound) device of this one is read.
     int sync_host_env() {
@@ -247,20 +231,36 @@ struct gnxr_scene {
     DTexTables tex_tables(const float *uv, const float *n, const float *s) const {
         DTexTables tt;
         tt.textures = textures.p; tt.texels = reinterpret_cast<const float4 *>(tex_texels.p); tt.ewa_lut = ewa_lut.p;
-        tt.tri_uv = cs.tri_uv.empty() ? nullptr : uv; tt.tri_n = cs.tri_n.empty() ? nullptr : n; tt.tri_s = cs.tri_s.empty() ? nullptr : s;
+        tt.tri_uv = cs.has_tri_uv ? uv : nullptr; tt.tri_n = cs.has_tri_n ? n : nullptr; tt.tri_s = cs.has_tri_s ? s : nullptr;
         return tt;
+    }
+    // The one way to write the material tables of the (bound) device: record 0 with the texture tables and the per-corner attribute tables
+    // at exactly the addresses given (null: absent), followed by the materials.  In place: upload_scene sized both buffers for the worst case.
+    int write_material_tables(const std::vector<DMaterial> &mats, const std::vector<DMaterial> &mats_single, const float *uv, const float *n, const float *s) {
+        DTexTables rec;
+        rec.textures = textures.p; rec.texels = reinterpret_cast<const float4 *>(tex_texels.p); rec.ewa_lut = ewa_lut.p;
+        rec.tri_uv = uv; rec.tri_n = n; rec.tri_s = s;
+        for (int k = 0; k < 2; ++k) {
+            const std::vector<DMaterial> &src = k == 0 ? mats : mats_single;
+            std::vector<DMaterial> up(src.size() + 1);
+            memset(&up[0], 0, sizeof(DMaterial));
+            memcpy(&up[0], &rec, sizeof(rec));
+            std::copy(src.begin(), src.end(), up.begin() + 1);
+            HIP_TRY(hipMemcpy((k == 0 ? materials : materials_single).p, up.data(), up.size() * sizeof(DMaterial), hipMemcpyHostToDevice));
+        }
+        return GNXR_OK;
     }
     // what the tree allows: the binary walk's stack size and whether the 4-wide traversal can hold it (leaf sizes / triangle count fit the
     // reference encoding).  leaf_over_127: some leaf holds more than 127 primitives.
     void set_traversal(bool leaf_over_127) {
         stack_size = cs.bvh_max_depth + 1 <= 32 ? 32 : 64;
-        wide_ok = cs.tris.size() < (1u << 24) && cs.stack4_need + 1 <= 128 && !Knobs::binary_bvh() && !leaf_over_127;
+        wide_ok = cs.n_triangles < (1u << 24) && cs.stack4_need + 1 <= 128 && !Knobs::binary_bvh() && !leaf_over_127;
     }
     DMediaTables media_tables() {
         DMediaTables m;
         m.media = dmedia.p;
         m.density = grid_density.p;
-        m.tri_media = cs.tri_media.empty() ? nullptr : reinterpret_cast<const int2 *>(tri_media.p);
+        m.tri_media = cs.has_tri_media ? reinterpret_cast<const int2 *>(tri_media.p) : nullptr;
         return m;
     }
     // light-selection table (core/LightDistribution.cpp).  The spatial strategy's dense voxel table is filled on the device

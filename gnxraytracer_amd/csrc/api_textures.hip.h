@@ -167,7 +167,7 @@ extern "C" int gnxr_scene_update_textures(gnxr_scene *s, int32_t first_texture, 
     if (!s) { set_error("null scene"); return GNXR_ERR_INVALID; }
     if (n_textures > 0 && !textures) { set_error("null texture array"); return GNXR_ERR_INVALID; }
     std::lock_guard<std::recursive_mutex> lock(s->render_mutex);
-    CompiledScene &cs = s->cs;
+    SceneFacts &cs = s->cs;
     const int64_t have = (int64_t)cs.textures.size();   // (the number of textures never changes)
     if (have == 0) { set_error("the scene was created without textures (the texture list of a scene is fixed)"); return GNXR_ERR_UNSUPPORTED; }
     if (first_texture < 0 || n_textures < 0 || (int64_t)first_texture + n_textures > have) {
@@ -248,15 +248,13 @@ extern "C" int gnxr_scene_update_textures(gnxr_scene *s, int32_t first_texture, 
         if (rc) return rc;
     }
     // 3. the only writes that can still fail: the texture records and the address of the new buffer.  A failure puts the old ones back
-    rc = s->each_copy([&](gnxr_scene *c, size_t i) -> int { return tex_write_records(c, recs, texels ? built[i].p : c->tex_texels.p); });
-    if (rc) { const std::string why = get_error(); (void)s->each_copy(tex_records_back); set_error("%s", why.c_str()); return rc; }
+    rc = s->apply_or_put_back([&](gnxr_scene *c, size_t i) -> int { return tex_write_records(c, recs, texels ? built[i].p : c->tex_texels.p); }, tex_records_back);
+    if (rc) return rc;
     // 4. the host scene, then the swaps (the old buffers are released with `built`: hipFree waits for what still reads them)
     cs.desc_textures = std::move(descs);
     cs.textures = std::move(recs);
-    if (texels) {
-        std::vector<float>().swap(cs.tex_texels);   // stale from here on: the devices hold the texels
+    if (texels)
         for (size_t i = 0; i < s->n_copies(); ++i) swap_buf(s->copy(i)->tex_texels, built[i]);
-    }
     return GNXR_OK;
 }
 
@@ -266,7 +264,7 @@ extern "C" int gnxr_scene_texture_tables(gnxr_scene *s, int32_t which, int32_t t
     if (!s || !n_bytes) { set_error("null argument"); return GNXR_ERR_INVALID; }
     if (which < 0 || which > 1) { set_error("texture table %d outside [0, 2)", which); return GNXR_ERR_INVALID; }
     std::lock_guard<std::recursive_mutex> lock(s->render_mutex);
-    const CompiledScene &cs = s->cs;
+    const SceneFacts &cs = s->cs;
     const size_t n = cs.textures.size();
     if (which == 1 && (texture < 0 || (size_t)texture >= n)) { set_error("texture %d outside the scene's %zu textures", texture, n); return GNXR_ERR_INVALID; }
     const size_t bytes = which == 0 ? n * sizeof(DTexture) : (size_t)texture_texels(cs.textures[texture]) * sizeof(float4);

@@ -1,5 +1,6 @@
 // host_scene.h -- host side of libgnxr: scene authoring (mirror of ui/ModelList.cpp and
-// ui/MaterialList.cpp) and the scene compiler that flattens a gnxr_scene_desc into device tables.
+// ui/MaterialList.cpp) and the scene compiler that flattens a gnxr_scene_desc into a CompiledScene: the tables a device takes once
+// (SceneUploadTables) and the facts a live scene's host side keeps (SceneFacts).
 #pragma once
 #include <string>
 #include <vector>
@@ -41,35 +42,53 @@ bool read_model_3d(const char *path, std::vector<float> *verts, std::vector<int3
 bool write_synthetic_3d(const char *path, int target_tris, uint32_t seed);
 bool read_rgbe(const char *path, std::vector<float> *rgb, int *w, int *h);  // what stbi_loadf returns for a .hdr
 
-// ---------------- compiled scene (host copies of the device tables) ----------------
-struct CompiledScene {
-    // geometry
+// ---------------- compiled scene ----------------
+// What compile_scene produces comes in two parts.  The UPLOAD TABLES are bulk data that exists to be copied to a device once: after
+// gnxr_scene_create the devices hold the only copy, and every edit of a live scene (refit, rebuild, set_geometry, material, attribute, media
+// and texture edits) changes it there.  The SCENE FACTS are what the host authored or keeps reading; a handle keeps exactly these
+// (SceneHost, api_scene.hip.h).  Nothing in leaf or node order is a fact, except the refit's seeds until they are uploaded (RefitSeeds).
+struct SceneUploadTables {
     std::vector<DNode> nodes;
     std::vector<DNode4> nodes4;          // 4-wide collapse of `nodes`, cuts of least surface area (wide_collapse.h; same leaf visiting order)
-    int32_t root4 = 0;                   // root reference (a leaf ref when the scene has a single leaf)
-    int stack4_need = 1;                 // worst-case traversal stack entries for nodes4
     std::vector<DTri> tris;              // leaf order
     std::vector<float> leaf_boxes;       // 8 floats per leaf-order triangle, valid at the first triangle of each leaf: the leaf's LinearBVHNode bounds (lo.xyz hi.x | hi.yz 0 0)
-    int leaf1_from_verts = 0;            // every one-triangle leaf's bounds == min / max of its triangle's vertices (checked in compile_scene)
     std::vector<uint8_t> tri_class;      // per leaf-order triangle: the key the binning pass gives a path that hit it: DMaterial::shade_class of its material (0 for null materials) | material_kind() << kClassKeyKindShift
     std::vector<int32_t> leaf_of_prim;   // authoring index -> leaf index
-    int bvh_max_depth = 0;
-    Box3 world_bound;
-    // refit (gnxr_scene_update_vertices): host-only until the first update, when they go to the device
-    int n_vertices = 0;                  // gnxr_scene_desc::n_vertices
+    std::vector<int32_t> tri_media;      // leaf order, (inside, outside) per triangle; empty when no triangle is a medium boundary
+    std::vector<float> tri_uv;           // empty, or 8 floats per leaf-order triangle: (u,v) x 3 corners + pad
+    std::vector<float> tri_n;            // empty, or 12 floats per leaf-order triangle: 3 shading normals + pad (zeros == none)
+    std::vector<float> tri_s;            // the same for TriangleMesh::s (shading tangents)
+    std::vector<float> tex_texels;       // float4 (rgb_) per texel, all levels of all textures (SceneFacts::textures holds their offsets)
+    std::vector<float> grid_density;     // the media's density grids (SceneFacts::dmedia holds their offsets)
+    std::vector<float> ewa_lut;          // MIPMap::weightLut
+};
+
+// The refit's seed tables (gnxr_scene_update_vertices): the one set that goes to a device lazily, at the first edit of the scene, so that a
+// scene that is never edited takes no device memory for them.  compile_scene fills them in the CompiledScene; gnxr_scene_create moves them
+// into SceneFacts::refit_seeds, which releases them once every copy of the scene holds its own (refit_tables, api_edit.hip.h).  After
+// gnxr_scene_rebuild_bvh or gnxr_scene_set_geometry the devices' tables are the only ones.
+struct RefitSeeds {
     std::vector<int32_t> corner_vertex;  // 3 per leaf-order triangle: the authored vertex of each corner
     std::vector<int32_t> node_parent;    // per DNode: its parent (-1 at the root)
     std::vector<int32_t> node4_src;      // 4 per DNode4: the DNode behind each child slot (-1: kNode4Empty)
+};
+
+struct SceneFacts {
+    // geometry: the counts and flags of the upload tables (compile_scene fills them; rebuild and set_geometry keep them current)
+    size_t n_triangles = 0, n_nodes = 0, n_nodes4 = 0;   // tris / nodes / nodes4
+    bool has_tri_media = false, has_tri_uv = false, has_tri_n = false, has_tri_s = false;   // the table exists (is not empty)
+    int32_t root4 = 0;                   // root reference (a leaf ref when the scene has a single leaf)
+    int stack4_need = 1;                 // worst-case traversal stack entries for nodes4
+    int leaf1_from_verts = 0;            // every one-triangle leaf's bounds == min / max of its triangle's vertices (checked in compile_scene)
+    int bvh_max_depth = 0;
+    Box3 world_bound;
+    int n_vertices = 0;                  // gnxr_scene_desc::n_vertices
+    RefitSeeds refit_seeds;              // a live scene's, until every copy holds them (empty in a CompiledScene, which carries them itself)
     // shading
     std::vector<DMaterial> materials;
     std::vector<DMaterial> materials_single;   // allowMultipleLobes == false (Whitted)
-    std::vector<DTexture> textures;            // image textures: parameters + level offsets into tex_texels
-    std::vector<float> tex_texels;             // float4 (rgb_) per texel, all levels of all textures; read by the upload at creation only, cleared by the first gnxr_scene_update_textures with texels (the devices hold them, `textures` their offsets)
+    std::vector<DTexture> textures;            // image textures: parameters + level offsets into the texel table
     std::vector<gnxr_texture> desc_textures;   // gnxr_scene_desc::textures with texel_offset zeroed (the raw texels are not retained): what a parameters-only texture edit compares against
-    std::vector<float> ewa_lut;                // MIPMap::weightLut
-    std::vector<float> tri_uv;                 // empty, or 8 floats per leaf-order triangle: (u,v) x 3 corners + pad
-    std::vector<float> tri_n;                  // empty, or 12 floats per leaf-order triangle: 3 shading normals + pad (zeros == none)
-    std::vector<float> tri_s;                  // the same for TriangleMesh::s (shading tangents)
     std::vector<float> aov_albedo;             // feature buffers: float4 per AUTHORED material, gnxr_material_albedo's rgb + the bits of kd_texture
     std::vector<int32_t> material_authored;    // per entry of `materials` (the attribute copies included): the authored material index
     // material edits (gnxr_scene_update_materials / gnxr_scene_set_triangle_materials): what compile_materials reads, in AUTHORING order and
@@ -97,16 +116,17 @@ struct CompiledScene {
     // media
     std::vector<gnxr_medium> media;
     std::vector<DMedium> dmedia;
-    std::vector<float> grid_density;     // read by the upload at creation only; cleared by the first gnxr_scene_update_media (the devices hold the grids, dmedia their offsets)
     std::vector<DSphere> spheres;
     int n_spheres = 0;
-    std::vector<int32_t> tri_media;      // leaf order, (inside, outside) per triangle; empty when no triangle is a medium boundary
     // camera description (matrices depend on the render resolution)
     gnxr_camera camera;
     int camera_medium = -1;
     // copy of the description for the light grid builder
     std::vector<gnxr_light> desc_lights;
 };
+
+// the whole of what compile_scene produces (the stand-alone host checks and gnxr_scene_create's local)
+struct CompiledScene : SceneUploadTables, RefitSeeds, SceneFacts {};
 
 // HLBVH (GNXR_BVH_HLBVH, BVHAccel.cpp:369-626) is built by the caller's device stage (api_hlbvh.hip.h + hlbvh_build.hip.h): Morton codes, radix
 // sort, one LBVH per treelet and the SAH over the treelet roots.  It returns the build tree -- leaves index the sorted primitive array
@@ -124,7 +144,7 @@ struct MaterialTables {
     std::vector<DMaterial> materials, materials_single;
     std::vector<float> aov_albedo;
     std::vector<int32_t> material_authored, mat_map;
-    void move_to(CompiledScene *cs);
+    void move_to(SceneFacts *cs);
 };
 bool compile_materials(const gnxr_material *mats, int n_materials, int n_textures, const std::vector<int32_t> &sphere_material, const int32_t *tri_material,
                        const uint8_t *tri_own_attr, int n_triangles, const int32_t *visit, MaterialTables *mt);
@@ -134,7 +154,7 @@ void triangle_material(const int32_t *mat_map, int32_t authored, uint8_t own_att
 int material_kind(const DMaterial &m);
 // after a refit: the root box of the binary BVH (lo.xyz hi.xyz) -> world_bound (grown by the spheres), the environment light's bounding
 // sphere and the distant lights' radius, computed as compile_scene computes them
-void refit_world_bound(CompiledScene *cs, const float root6[6]);
+void refit_world_bound(SceneFacts *cs, const float root6[6]);
 // one DLight from its description, as compile_scene makes it (gnxr_scene_update_lights): for AREA_TRI from the corners of its triangle and
 // its leaf index; for INFINITE the record without the environment tables; false (error set) for an unknown type
 bool compile_light(const gnxr_light &l, int index, const Vec3 corners[3], int tri_leaf, const Box3 &world_bound, DLight *out);
@@ -144,7 +164,7 @@ bool compile_light(const gnxr_light &l, int index, const Vec3 corners[3], int tr
 // INFINITE and SKYBOX records; light_of_prim per authored triangle the light that names it or -1.  Returns GNXR_OK, GNXR_ERR_INVALID (a
 // triangle out of range or named twice, an unknown type) or GNXR_ERR_UNSUPPORTED (an INFINITE record added, dropped, changed in any byte or
 // moved across a SKYBOX record: its tables are gnxr_scene_update_environment's), with the error set.
-int compile_light_list(const CompiledScene &cs, const gnxr_light *in, int n, std::vector<DLight> *recs, std::vector<int32_t> *infinite, std::vector<int32_t> *light_of_prim);
+int compile_light_list(const SceneFacts &cs, const gnxr_light *in, int n, std::vector<DLight> *recs, std::vector<int32_t> *infinite, std::vector<int32_t> *light_of_prim);
 // one DMedium from its description and, for a GRID medium, the maximum of its grid (GridDensityMedium.h:28-31: the fold from +0 over
 // std::max), as compile_scene makes it (gnxr_scene_update_media): sigma_t, w2m = Inverse(medium_to_world), inv_max_density = 1 / max_density.
 // density_offset is left 0: where the grid sits is the caller's.  false (error set) for an unknown type or an empty grid
@@ -166,10 +186,10 @@ DCamera make_camera(const gnxr_camera &c, int W, int H, int medium);      // cam
 void camera_world_to_raster(const gnxr_camera &c, int W, int H, float w2r[16]);   // (s2r * c2s) * lookat of make_camera's factors
 DHalton make_halton(int W, int H);                                          // samplers/HaltonSampler.cpp:33-60
 // light-selection table: dense restatement of core/LightDistribution.cpp (uniform / power / spatial)
-void build_light_grid(const CompiledScene &cs, int strategy, DLightGrid *grid, std::vector<float> *table, bool layout_only = false);
-void light_grid_probes(const CompiledScene &cs, float *ri /* [5][128] */);
+void build_light_grid(const SceneFacts &cs, int strategy, DLightGrid *grid, std::vector<float> *table, bool layout_only = false);
+void light_grid_probes(const SceneFacts &cs, float *ri /* [5][128] */);
 
 // host restatements used by probes and the light grid
-float host_radical_inverse(const CompiledScene &cs, int baseIndex, uint64_t a);
+float host_radical_inverse(const SceneFacts &cs, int baseIndex, uint64_t a);
 
 }  // namespace gnxr

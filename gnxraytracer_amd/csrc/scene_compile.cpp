@@ -525,7 +525,7 @@ static void build_sampler_tables(CompiledScene *cs) {
     }
 }
 
-float host_radical_inverse(const CompiledScene &cs, int baseIndex, uint64_t a) {  // LowDiscrepancy.cpp:358-372,396-403
+float host_radical_inverse(const SceneFacts &cs, int baseIndex, uint64_t a) {  // LowDiscrepancy.cpp:358-372,396-403
     if (baseIndex == 0) {
         uint32_t lo = (uint32_t)a, hi = (uint32_t)(a >> 32);
         auto rev = [](uint32_t n) {
@@ -652,7 +652,7 @@ static void dist1d(const float *f, int n, float *cdf /*n+1*/, float *funcInt) { 
 
 // ---- what depends on Scene::WorldBound (compile_scene, and refit_world_bound after gnxr_scene_update_vertices)
 // Scene::WorldBound covers every primitive (the light-selection grid is laid over it): the BVH's root box grown by the spheres
-static void grow_by_spheres(CompiledScene *cs) {
+static void grow_by_spheres(SceneFacts *cs) {
     for (int i = 0; i < cs->n_spheres; ++i) {
         const DSphere &sp = cs->spheres[i];
         Box3 b;
@@ -662,7 +662,7 @@ static void grow_by_spheres(CompiledScene *cs) {
     }
 }
 // InfiniteAreaLight::Preprocess: scene.WorldBound().BoundingSphere (InfiniteAreaLight.h:23-26)
-static void env_bounding_sphere(CompiledScene *cs) {
+static void env_bounding_sphere(SceneFacts *cs) {
     DEnv &e = cs->env;
     Vec3 c = (cs->world_bound.lo + cs->world_bound.hi) / 2;
     e.world_center[0] = c.x; e.world_center[1] = c.y; e.world_center[2] = c.z;
@@ -715,7 +715,7 @@ bool compile_light(const gnxr_light &l, int index, const Vec3 corners[3], int tr
 }
 
 // The light list of gnxr_scene_set_lights: compile_scene's lights section without the environment tables, for a scene that exists.
-int compile_light_list(const CompiledScene &cs, const gnxr_light *in, int n, std::vector<DLight> *recs, std::vector<int32_t> *infinite, std::vector<int32_t> *light_of_prim) {
+int compile_light_list(const SceneFacts &cs, const gnxr_light *in, int n, std::vector<DLight> *recs, std::vector<int32_t> *infinite, std::vector<int32_t> *light_of_prim) {
     const int nt = (int)cs.tri_material.size();
     recs->resize((size_t)std::max(1, n));
     memset(recs->data(), 0, sizeof(DLight) * recs->size());
@@ -760,7 +760,7 @@ int compile_light_list(const CompiledScene &cs, const gnxr_light *in, int n, std
     return GNXR_OK;
 }
 
-void refit_world_bound(CompiledScene *cs, const float root6[6]) {
+void refit_world_bound(SceneFacts *cs, const float root6[6]) {
     cs->world_bound = Box3();
     cs->world_bound.lo = Vec3(root6[0], root6[1], root6[2]);
     cs->world_bound.hi = Vec3(root6[3], root6[4], root6[5]);
@@ -1070,7 +1070,7 @@ static bool sphere_material_ok(const gnxr_material *mats, int n_materials, int m
     return true;
 }
 
-void MaterialTables::move_to(CompiledScene *cs) {
+void MaterialTables::move_to(SceneFacts *cs) {
     cs->materials = std::move(materials); cs->materials_single = std::move(materials_single);
     cs->aov_albedo = std::move(aov_albedo); cs->material_authored = std::move(material_authored); cs->mat_map = std::move(mat_map);
 }
@@ -1420,6 +1420,9 @@ bool compile_scene(const gnxr_scene_desc *d, CompiledScene *cs, HlbvhBuildFn hlb
     if (d->n_media > 0 && (d->camera_medium < -1 || d->camera_medium >= d->n_media)) { set_error("camera_medium %d out of range (%d media)", d->camera_medium, d->n_media); return false; }
     cs->camera_medium = d->n_media > 0 ? d->camera_medium : -1;
     build_sampler_tables(cs);
+    // the facts a live scene keeps of the upload tables: their counts and which of the optional ones exist
+    cs->n_triangles = cs->tris.size(); cs->n_nodes = cs->nodes.size(); cs->n_nodes4 = cs->nodes4.size();
+    cs->has_tri_media = !cs->tri_media.empty(); cs->has_tri_uv = !cs->tri_uv.empty(); cs->has_tri_n = !cs->tri_n.empty(); cs->has_tri_s = !cs->tri_s.empty();
     return true;
 }
 
@@ -1449,7 +1452,7 @@ static float sample_continuous(const float *func, const float *cdf, int n, float
     return (offset + du) / n;
 }
 // returns Li.y()/pdf contribution (0 when pdf == 0)
-static float light_contrib(const CompiledScene &cs, int j, Vec3 ref, float u0, float u1) {
+static float light_contrib(const SceneFacts &cs, int j, Vec3 ref, float u0, float u1) {
     const DLight &l = cs.lights[j];
     if (l.type == GNXR_LIGHT_AREA_TRI) {
         // Triangle::Sample + Shape::Sample(ref) + DiffuseAreaLight::Sample_Li
@@ -1524,7 +1527,7 @@ static float light_contrib(const CompiledScene &cs, int j, Vec3 ref, float u0, f
 }
 }  // namespace
 
-void build_light_grid(const CompiledScene &cs, int strategy, DLightGrid *grid, std::vector<float> *table, bool layout_only) {
+void build_light_grid(const SceneFacts &cs, int strategy, DLightGrid *grid, std::vector<float> *table, bool layout_only) {
     int nl = (int)cs.desc_lights.size();
     memset(grid, 0, sizeof(*grid));
     grid->n_lights = nl;
@@ -1623,7 +1626,7 @@ void build_light_grid(const CompiledScene &cs, int strategy, DLightGrid *grid, s
 }
 
 // RadicalInverse(k, i), k = 0..4, i = 0..127: the probe points / light samples of ComputeDistribution (LightDistribution.cpp:226-234)
-void light_grid_probes(const CompiledScene &cs, float *ri /* [5][128] */) {
+void light_grid_probes(const SceneFacts &cs, float *ri /* [5][128] */) {
     for (int i = 0; i < 128; ++i)
         for (int k = 0; k < 5; ++k) ri[k * 128 + i] = host_radical_inverse(cs, k, i);
 }

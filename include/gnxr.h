@@ -367,9 +367,9 @@ int gnxr_probe_gather_peak(double *giga_lane_loads_per_s);
 /* -- scene (replaces `Scene(make_shared<BVHAccel>(prims,1), lights)`, RenderThread.cpp:155) */
 int gnxr_scene_create(const gnxr_scene_desc *desc, gnxr_scene **out);
 void gnxr_scene_destroy(gnxr_scene *scene);
-/* Test hook: the flattened binary BVH (the reference's LinearBVHNode[]: per node 6 floats of bounds into `bounds6`, then
- * offset / nPrimitives / axis into `meta3`) and the primitive order (`ordered`, n_triangles entries); *n_nodes receives the node
- * count, arrays are filled when node_capacity allows. */
+/* Test hook: the flattened binary BVH of the scene's first device (the reference's LinearBVHNode[]: per node 6 floats of bounds
+ * into `bounds6`, then offset / nPrimitives / axis into `meta3`) and the primitive order (`ordered`, n_triangles entries);
+ * *n_nodes receives the node count, arrays are filled when node_capacity allows. */
 int gnxr_scene_bvh(const gnxr_scene *scene, float *bounds6, int32_t *meta3, int32_t *ordered, int64_t node_capacity, int64_t *n_nodes);
 /* Test hook: the 4-wide node table of the scene's first device (128 bytes per node into `nodes128`, filled when node_capacity
  * allows; *n_nodes4 receives the node count) and the quantities the traversal plan is sized from: the root reference and the
