@@ -987,6 +987,105 @@ class Scene:
                                         res.ctypes.data_as(C.POINTER(_abi.ClosestPoint))))
         return res
 
+    # all-hits ray queries (gnxr_trace_all_device / gnxr_trace_all)
+    def _all_hits(self, name, rays, max_hits, out, counts_out, launch):
+        import torch
+        _only_kw(name, launch, ("stream", "counts"))
+        stream, work = launch.get("stream"), launch.get("counts")
+        if isinstance(max_hits, bool) or not isinstance(max_hits, (int, np.integer)):
+            raise TypeError(f"{name}: max_hits must be an integer, got {type(max_hits).__name__}")
+        max_hits = int(max_hits)
+        if not 0 <= max_hits <= ALL_HITS_MAX:
+            raise ValueError(f"{name}: max_hits must be in [0, {ALL_HITS_MAX}], got {max_hits}")
+        _expect(f"{name}: rays", rays, torch.float32, (8,), self.device)
+        n = rays.shape[0]
+        st, _, out, counts_out = _outputs(stream, rays.device, (f"{name}: out", out, (n, max_hits, 4), torch.float32),
+                                          (f"{name}: counts_out", counts_out, (n,), torch.int32))
+        hits = _ptr(out) if max_hits else None
+        if work is None:
+            _check(lib().gnxr_trace_all_device(self._h, _ptr(rays), n, max_hits, hits, _ptr(counts_out), _addr(st)))
+        else:
+            if not _is_tensor(work, torch.int64, (3,), rays.device):
+                _refuse(work, f"{name}: counts must be a contiguous torch.int64 (3,) tensor on {rays.device}")
+            _check(lib().gnxr_trace_all_counted_device(self._h, _ptr(rays), n, max_hits, hits, _ptr(counts_out), _ptr(work), _addr(st)))
+        return RayHitLists(out, out[:, :, 0], out.view(torch.int32)[:, :, 1], out[:, :, 2:4], counts_out)
+
+    def all_hits(self, rays, max_hits, out=None, counts_out=None, **launch):
+        """EVERY triangle that rays already on the GPU pass through (gnxr_trace_all_device; the definition, triangle by triangle:
+        include/gnxr.h).  `rays`: a contiguous float32 (n, 8) tensor in the gnxr_ray layout (rays_tensor) on the scene's device;
+        `max_hits` = K in [0, ALL_HITS_MAX].  Returns RayHitLists: `count`, int32 (n,) (`counts_out` when given) -- all hits within
+        tmax, never clamped to K --, and the (n, K, 4) float32 gnxr_ray_hit records (`out` when given) of the first min(count, K) hits
+        in ascending (t, prim), the remaining slots (+inf, -1, 0, 0), with named views of them.  Nothing is pruned by distance: the
+        walk visits every triangle along the ray whatever K is; bound tmax to see less.  The walk reads the scene's live tree (after
+        update_vertices, rebuild_bvh and set_geometry it answers for the geometry the scene holds now); spheres are not considered.
+        Keywords of the launch, as for closest_point: `stream=` (None: torch's current stream; a torch.cuda.Stream or a hipStream_t
+        as an int; the work is queued there and nothing waits) and, for measurements, `counts=`: an int64 (3,) tensor on the same
+        device that the call adds nodes visited, own-box tests and triangle tests to, through the kernel's slower counting form.
+        (Their refusals are exercised in tests/test_all_hits.py.)"""
+        return self._all_hits("all_hits", rays, max_hits, out, counts_out, launch)
+
+    def count_hits(self, rays, **launch):
+        """all_hits with max_hits = 0: the int32 (n,) number of triangles each ray passes through within its tmax, and no list."""
+        return self._all_hits("count_hits", rays, 0, None, None, launch).count
+
+    def _parity_rays(self, name, points, direction, stream):
+        import torch
+        _expect(f"{name}: points", points, torch.float32, (3,), self.device)
+        if direction is None:
+            direction = CONTAINS_DIRECTION
+        try:
+            d = tuple(float(x) for x in direction)
+        except (TypeError, ValueError):
+            raise TypeError(f"{name}: direction must be None or three numbers, got {type(direction).__name__}") from None
+        if len(d) != 3 or not all(np.isfinite(d)) or not any(d):
+            raise ValueError(f"{name}: direction must be three finite numbers, not all zero, got {d}")
+        with torch.cuda.stream(_stream_pair(stream, points.device)[1]):
+            rays = torch.empty((points.shape[0], 8), dtype=torch.float32, device=points.device)
+            rays[:, 0:3] = points
+            rays[:, 3] = float("inf")
+            for k in range(3):
+                rays[:, 4 + k] = d[k]
+            rays[:, 7] = 0.0
+        return rays
+
+    def contains(self, points, direction=None, **launch):
+        """Whether points already on the GPU lie inside the scene's triangle mesh: uint8 (n,), count_hits & 1 along the rays
+        (p, direction, +inf), which are built on the device.  `points`: a contiguous float32 (n, 3) tensor on the scene's device;
+        `direction`: three numbers (default CONTAINS_DIRECTION: (3, 2, 1) / sqrt(14) to within an ulp of fp32).  The mesh must be
+        CLOSED for the parity to mean anything.  A ray through a shared edge or vertex EXACTLY can count one crossing twice (or
+        none): a caller who cannot accept that votes over several directions.  `stream=`, `counts=`: as for all_hits."""
+        import torch
+        _only_kw("contains", launch, ("stream", "counts"))
+        rays = self._parity_rays("contains", points, direction, launch.get("stream"))
+        with torch.cuda.stream(_stream_pair(launch.get("stream"), points.device)[1]):
+            return (self._all_hits("contains", rays, 0, None, None, launch).count & 1).to(torch.uint8)
+
+    def signed_distance(self, points, direction=None, **launch):
+        """The distance from points already on the GPU to the scene's triangle mesh, negative inside: float32 (n,),
+        sqrt(closest_point(points).dist2), negated where contains(points, direction) -- it equals that chain of public calls on bits.
+        +inf where closest_point has no winner (a scene without triangles).  The limits are those of contains: a closed mesh, and
+        rays that cross an edge exactly.  `stream=`: as for all_hits."""
+        import torch
+        _only_kw("signed_distance", launch, ("stream",))
+        _expect("signed_distance: points", points, torch.float32, (3,), self.device)
+        inside = self.contains(points, direction, **launch)
+        nearest = self.closest_point(points, **launch)
+        with torch.cuda.stream(_stream_pair(launch.get("stream"), points.device)[1]):
+            dist = torch.sqrt(nearest.dist2)
+            dist = torch.where(inside != 0, -dist, dist)
+            return torch.where(nearest.prim < 0, torch.full_like(dist, float("inf")), dist)
+
+    def AllHits(self, rays, max_hits):
+        """all_hits for numpy arrays (gnxr_trace_all): `rays` is (n, 8) float32 in the gnxr_ray layout (make_rays).  Returns
+        (hits, counts): an (n, max_hits) structured array of RAY_HIT_DTYPE and the int32 (n,) counts."""
+        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+        max_hits = int(max_hits)
+        hits = np.zeros((len(rays), max_hits), dtype=RAY_HIT_DTYPE)
+        counts = np.zeros(len(rays), dtype=np.int32)
+        _check(lib().gnxr_trace_all(self._h, rays.ctypes.data_as(C.POINTER(_abi.Ray)), len(rays), max_hits,
+                                    hits.ctypes.data_as(C.POINTER(_abi.RayHit)) if max_hits > 0 else None, counts.ctypes.data_as(C.POINTER(C.c_int32))))
+        return hits, counts
+
     MOTION_CHANNELS = ("motion", "guide", "prim")
 
     def motion(self, width, height, prev_cameras, cameras=None, prev_vertices=None, out=None, stream=None):
@@ -1042,6 +1141,15 @@ ClosestPoints = collections.namedtuple("ClosestPoints", "records prim dist2 poin
 ClosestPoints.__doc__ = """Scene.closest_point's result: `records`, the (n, 8) float32 gnxr_closest_point records, and views of it -- `prim` (int32:
 authoring-order triangle, -1 for none), `dist2`, `point` (n, 3), `b1b2` (n, 2) and `feature` (int32: 0 face, 1 / 2 / 3 edge ab / ac / bc,
 4 / 5 / 6 vertex a / b / c)."""
+
+
+RayHitLists = collections.namedtuple("RayHitLists", "records t prim b count")
+RayHitLists.__doc__ = """Scene.all_hits's result: `records`, the (n, K, 4) float32 gnxr_ray_hit records -- per ray the first min(count, K)
+hits in ascending (t, prim), then (+inf, -1, 0, 0) --, views of it -- `t` (n, K), `prim` (n, K) (int32: authoring-order triangle, -1 in an
+empty slot) and `b` (n, K, 2) = b1, b2, the weights of the second and third vertex -- and `count`, int32 (n,): all hits, never clamped."""
+
+ALL_HITS_MAX = 32   # GNXR_ALL_HITS_MAX
+CONTAINS_DIRECTION = (0.8017837, 0.5345225, 0.26726124)   # GNXR_CONTAINS_DIRECTION_*: (3, 2, 1) / sqrt(14) to within an ulp of fp32
 
 
 def rays_tensor(o, d, tmax=float("inf")):
@@ -1101,6 +1209,9 @@ HIT_DTYPE = np.dtype([("prim", np.int32), ("t", np.float32), ("b0", np.float32),
 
 CLOSEST_DTYPE = np.dtype([("prim", np.int32), ("dist2", np.float32), ("p", np.float32, 3), ("b1", np.float32), ("b2", np.float32),
                           ("feature", np.int32)])
+
+
+RAY_HIT_DTYPE = np.dtype([("t", np.float32), ("prim", np.int32), ("b1", np.float32), ("b2", np.float32)])
 
 
 def make_rays(o, d, tmax=np.inf):

@@ -120,6 +120,10 @@ class ClosestPoint(C.Structure):   # gnxr_closest_point (no struct_size; not in 
     _fields_ = [("prim", i32), ("dist2", f32), ("p", f32 * 3), ("b1", f32), ("b2", f32), ("feature", i32)]
 
 
+class RayHit(C.Structure):   # gnxr_ray_hit (no struct_size; not in gnxr_abi_sizeof's list)
+    _fields_ = [("t", f32), ("prim", i32), ("b1", f32), ("b2", f32)]
+
+
 class LiSample(C.Structure):
     _fields_ = [("px", i32), ("py", i32), ("s", i32), ("medium", i32)]
 
@@ -269,6 +273,9 @@ PROTOTYPES = {
     "gnxr_closest_point_device": (C.c_int, [VP, VP, i64, VP, VP]),   # device addresses + hipStream_t
     "gnxr_closest_point_counted_device": (C.c_int, [VP, VP, i64, VP, VP, VP]),   # ..., two uint64 on the device, hipStream_t
     "gnxr_closest_point": (C.c_int, [VP, P(PointQuery), i64, P(ClosestPoint)]),
+    "gnxr_trace_all_device": (C.c_int, [VP, VP, i64, i32, VP, VP, VP]),   # rays, n, max_hits, hits, counts: device addresses + hipStream_t
+    "gnxr_trace_all_counted_device": (C.c_int, [VP, VP, i64, i32, VP, VP, VP, VP]),   # ..., three uint64 on the device, hipStream_t
+    "gnxr_trace_all": (C.c_int, [VP, P(Ray), i64, i32, P(RayHit), P(i32)]),
     "gnxr_li_device": (C.c_int, [VP, P(RenderParams), VP, VP, i64, VP, VP, P(Stats)]),   # device addresses + hipStream_t
     "gnxr_render_views_device": (C.c_int, [VP, P(RenderParams), P(Camera), P(i32), i32, VP, VP, P(Stats)]),   # cameras, media: host; images: device
     "gnxr_render_aov_device": (C.c_int, [VP, P(RenderParams), P(Camera), P(i32), i32, P(AovBuffers), VP, P(Stats)]),   # cameras, media: host; buffers: device

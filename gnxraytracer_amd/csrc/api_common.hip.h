@@ -122,6 +122,9 @@ struct Knobs {
     // 1 lets tests bin small batches, a huge value switches binning off for A/B timing).  Per call (launch)
     static long long closest_bin_min() { const char *e = getenv("GNXR_CLOSEST_BIN_MIN"); return e ? std::max(1ll, atoll(e)) : 65536ll; }
     static int closest_lds_levels() { return std::max(1, std::min(24, env_int("GNXR_CLOSEST_LDS_LEVELS", 16))); }
+    // GNXR_ALLHITS_LDS_LEVELS: most levels of an all-hits walk's stack kept in LDS, 1 .. 32 (default 16; small values let tests reach the
+    // global spill on shallow trees).  Per call (launch)
+    static int allhits_lds_levels() { return std::max(1, std::min(32, env_int("GNXR_ALLHITS_LDS_LEVELS", 16))); }
 };
 
 int ensure_device() {

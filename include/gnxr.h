@@ -1389,6 +1389,76 @@ int gnxr_closest_point_counted_device(gnxr_scene *scene, const gnxr_point_query 
                                       uint64_t *d_counts, void *hip_stream);
 int gnxr_closest_point(gnxr_scene *scene, const gnxr_point_query *queries, int64_t n, struct gnxr_closest_point *out);
 
+/* -- All-hits ray queries: EVERYTHING a ray passes through, counted and listed in order -----------------------------------
+ * gnxr_trace_closest_device answers with the nearest hit of a ray, gnxr_trace_any_device with whether there is one.  This call answers
+ * with all of them: thickness, transmission through stacked sheets, multi-return range scans, CSG classification -- and, through the
+ * parity of the crossing count, whether a point lies inside a closed mesh, which with gnxr_closest_point is a signed distance.  The walk
+ * goes through the scene's live 4-wide tree (the binary tree for scenes that are off it; same results), so after
+ * gnxr_scene_update_vertices[_ex], gnxr_scene_rebuild_bvh and gnxr_scene_set_geometry the answer is for the geometry the scene holds
+ * now.  Spheres of the scene are NOT considered: triangles only.
+ *
+ * The result is defined triangle by triangle, so it does not depend on the tree.  For a ray (o, d, tmax) and a triangle with vertices
+ * p0, p1, p2 and authoring index prim, the triangle is a HIT iff both of these accept, each with the ray's own tmax (never a shrunk one):
+ *   1. The own-box test.  Per axis lo = min(min(p0, p1), p2), hi = max(max(p0, p1), p2) with min(x, y) = (y < x ? y : x), max(x, y) =
+ *      (y > x ? y : x) -- selection, no arithmetic.  Then Bounds3::IntersectP(ray, invDir, dirIsNeg) of the reference on [lo, hi] in its
+ *      comparison sequence: invDir = 1 / d per component, dirIsNeg = invDir < 0; per axis tNear = (near - o) * invDir, tFar = (far - o)
+ *      * invDir with near / far the bound dirIsNeg selects; tFar *= k, k = 1 + 2 * gamma(3), gamma(n) = (n * 2^-24) / (1 - n * 2^-24)
+ *      in fp32; reject if tMin > tyMax or tyMin > tMax; if (tyMin > tMin) tMin = tyMin; if (tyMax < tMax) tMax = tyMax; the same with z;
+ *      accept iff tMin < tmax and tMax > 0.  Every step is one rounded fp32 operation.
+ *   2. The triangle test: the ray-space part of the reference's watertight Triangle::Intersect (translate by o, permute so that |d| is
+ *      largest in z, shear, the three edge functions -- recomputed in fp64 when one of them is exactly 0 --, the sign test, det,
+ *      tScaled against 0 and tmax * det, then t = tScaled / det against the error bound deltaT).  t, b1 = e1 / det, b2 = e2 / det are
+ *      that function's outputs: b1 and b2 weight the second and the third vertex, the convention of gnxr_closest_point.
+ * The own-box test is part of the definition, not of the implementation: the slab arithmetic is monotone in the box, so a triangle
+ * whose own box accepts has every enclosing box accepting, the tests inside the tree only choose the subtrees that are walked, and a
+ * brute force over all triangles (tests/allhits_reference.py) reproduces the output byte for byte whatever tree the scene has
+ * (DESIGN.md).  A one-triangle leaf of the reference's tree tests exactly this box; a leaf of several triangles tests a wider one, so a
+ * hit that grazes the own box by an ulp and that gnxr_trace_closest_device reports through its leaf's wider box can in principle be
+ * absent here.
+ *
+ * Invalid rays have no hits: a non-finite component of o or d, a NaN tmax, or d == (0, 0, 0).  tmax = +inf is valid; tmax <= 0 falls
+ * out of the arithmetic as no hits.  Results for triangles with non-finite vertices are not defined (the call neither faults nor loops).
+ * (A direction ALL of whose components are so small that 1 / d overflows -- |d| below 3e-39 -- is a valid ray for which the triangle test
+ * can accept with a NaN t; the order of such hits is not defined.  Scale d.)
+ *
+ * There is NO pruning by distance: every triangle along the ray within tmax is visited, whatever max_hits is.  (A walk that stops at
+ * the K nearest would need an fp32 bound between a box's slab entry and the watertight test's t; nobody has one.  K-nearest pruning is
+ * out of scope.)  A caller who wants fewer hits bounds tmax.
+ *
+ * Output, per ray: d_counts[i] = the number of hits, all of them, never clamped to max_hits.  The first min(count, max_hits) hits in
+ * ascending order of (t, prim) -- t compared as a float (it is always > 0), bit-equal t ordered by the smaller authoring index, so
+ * coincident triangles are both kept -- as records d_hits[i * max_hits + j] = (t, prim, b1, b2); the slots from min(count, max_hits)
+ * up to max_hits - 1 are written as (+inf, -1, 0, 0), so the whole output is defined and comparable on bytes.  max_hits == 0 is the
+ * count-only form (d_hits must be NULL); max_hits is at most GNXR_ALL_HITS_MAX.  A scene without triangles gives counts of 0 and empty
+ * slots.
+ *
+ * Containment.  For a CLOSED mesh a point p is inside iff the count along (p, dir, +inf) is odd, for any direction that crosses no
+ * edge or vertex exactly; GNXR_CONTAINS_DIRECTION_X / _Y / _Z are (3, 2, 1) / sqrt(14) to within an ulp of fp32, a direction that is
+ * parallel to no axis or diagonal plane (Scene.contains and Scene.signed_distance of the Python module use it).  A ray through a shared
+ * edge EXACTLY can count one crossing twice; a caller who cannot accept that votes over several directions.
+ *
+ * gnxr_trace_all_device: the conventions of gnxr_trace_closest_device and gnxr_closest_point_device -- every array is device memory of
+ * one device that holds a copy of the scene, d_rays and d_hits 16-byte aligned, d_counts 4-byte aligned; the work is queued on
+ * hip_stream (NULL: the null stream) after what the caller queued there, nothing is copied back and nothing waits for the GPU; scratch
+ * (the walk's stack beyond its LDS levels, sized by the scene and the grid, never by n) comes from the stream-ordered allocator on that
+ * stream; n == 0 is a no-op; GNXR_ERR_INVALID before anything is queued for a null scene, a null pointer with n > 0, n < 0, max_hits
+ * outside [0, GNXR_ALL_HITS_MAX], d_hits set with max_hits == 0 or missing with max_hits > 0, a misaligned pointer, host pointers,
+ * pointers on a device without a copy of the scene or on different devices, or an array that runs past its allocation.
+ * gnxr_trace_all_counted_device is the same call through the counting instantiation of the kernel (measurements only: slower): it ADDS
+ * the nodes visited, the own-box tests and the triangle tests of the call to d_work[0 .. 3) (device memory, 8-byte aligned, the
+ * caller's to clear).  gnxr_trace_all takes host arrays: copy in, the same walk, copy out; it returns when the arrays are written.
+ * The record carries no struct_size and is not part of gnxr_abi_sizeof's list. */
+#define GNXR_ALL_HITS_MAX 32
+#define GNXR_CONTAINS_DIRECTION_X 0.8017837f
+#define GNXR_CONTAINS_DIRECTION_Y 0.5345225f
+#define GNXR_CONTAINS_DIRECTION_Z 0.26726124f
+typedef struct gnxr_ray_hit { float t; int32_t prim; float b1, b2; } gnxr_ray_hit;   /* 16 bytes, 16-byte aligned on the device */
+int gnxr_trace_all_device(gnxr_scene *scene, const gnxr_ray *d_rays, int64_t n, int32_t max_hits, gnxr_ray_hit *d_hits, int32_t *d_counts,
+                          void *hip_stream);
+int gnxr_trace_all_counted_device(gnxr_scene *scene, const gnxr_ray *d_rays, int64_t n, int32_t max_hits, gnxr_ray_hit *d_hits,
+                                  int32_t *d_counts, uint64_t *d_work, void *hip_stream);
+int gnxr_trace_all(gnxr_scene *scene, const gnxr_ray *rays, int64_t n, int32_t max_hits, gnxr_ray_hit *hits, int32_t *counts);
+
 /* -- Shading queries on device memory: the pieces an integrator is made of, batched -------------------------------------
  * Same conventions as the device calls of the Aggregate seam: every array is device memory of one device that holds a copy of the
  * scene, the work is queued on hip_stream (NULL: the null stream) after what the caller queued there, scratch comes from the
