@@ -325,6 +325,7 @@ int gnxr_trace_any(gnxr_scene *s, const gnxr_ray *rays, int64_t n, uint8_t *occl
 #include "api_media.hip.h"
 #include "api_textures.hip.h"
 #include "api_query.hip.h"
+#include "api_walk.hip.h"
 #include "api_closest.hip.h"
 #include "api_allhits.hip.h"
 #include "api_aov.hip.h"

@@ -4,9 +4,6 @@
 // allocator on the caller's stream).
 #pragma once
 
-// blocks per CU of the walk's grid: 16 KB of LDS stack per block at the default 16 levels
-static const int kAllHitsBlocksPerCu = 5;
-
 // rays of one launch: the kernel indexes rays and slots in 64 bits, a thread's spill column by its number in the grid; the cut keeps
 // n * max_hits of one launch far inside them
 static const long long kAllHitsLaunchMax = 1ll << 30;
@@ -20,18 +17,8 @@ static int all_hits_launch(gnxr_scene *r, const DScene &sc, const gnxr_ray *d_ra
         HIP_TRY(hipGetLastError());
         return GNXR_OK;
     }
-    // the bound of the stack is closest-point's: (children - 1) per node of the deepest path = stack4_need - 1, or the binary depth; slack as there
-    const bool wide = r->wide_ok;
-    const int entries = wide ? r->cs.stack4_need + 1 : r->cs.bvh_max_depth + 2;
-    const int lds_entries = std::min(entries, Knobs::allhits_lds_levels());
-    const int blocks = grid_for(std::min<long long>(n, kAllHitsLaunchMax), kAllHitsBlocksPerCu);
-    StreamScratch spill_scratch;
-    int *spill = nullptr;
-    if (entries > lds_entries) {
-        HIP_TRY(spill_scratch.alloc((size_t)(entries - lds_entries) * (size_t)blocks * kBlock * sizeof(int), st));
-        spill = reinterpret_cast<int *>(spill_scratch.p);
-    }
-    const size_t lds = (size_t)lds_entries * kBlock * sizeof(int);
+    WalkLaunch w;
+    if (int rc = w.plan(r, sizeof(int), Knobs::allhits_lds_levels(), std::min<long long>(n, kAllHitsLaunchMax), st)) return rc;
     for (long long base = 0; base < n; base += kAllHitsLaunchMax) {
         const long long cnt = std::min<long long>(n - base, kAllHitsLaunchMax);
         AllHitsArrays qa;
@@ -39,9 +26,9 @@ static int all_hits_launch(gnxr_scene *r, const DScene &sc, const gnxr_ray *d_ra
         qa.hits = K > 0 ? reinterpret_cast<float4 *>(d_hits + base * K) : nullptr;
         qa.counts = d_counts + base;
         qa.K = K;
-        const int g = grid_for(cnt, kAllHitsBlocksPerCu);   // never more than `blocks`: the spill is sized for those
-#define GX_ALLHITS(W, L, C) hipLaunchKernelGGL((k_all_hits<W, L, C>), dim3(g), dim3(kBlock), lds, st, sc, qa, (long long)cnt, lds_entries, entries, spill, d_work)
-#define GX_ALLHITS_WL(C) do { if (wide) { if (K > 0) GX_ALLHITS(true, true, C); else GX_ALLHITS(true, false, C); } \
+#define GX_ALLHITS(W, L, C) hipLaunchKernelGGL((k_all_hits<W, L, C>), dim3(w.grid(cnt)), dim3(kBlock), w.lds, st, sc, qa, (long long)cnt, w.lds_entries, w.entries, \
+                                               (int *)w.spill, d_work)
+#define GX_ALLHITS_WL(C) do { if (w.wide) { if (K > 0) GX_ALLHITS(true, true, C); else GX_ALLHITS(true, false, C); } \
                               else { if (K > 0) GX_ALLHITS(false, true, C); else GX_ALLHITS(false, false, C); } } while (0)
         if (d_work) GX_ALLHITS_WL(true);
         else GX_ALLHITS_WL(false);

@@ -3,9 +3,6 @@
 // trace_device's -- the same checks, DeviceCall, query_device_scene, scratch from the stream-ordered allocator on the caller's stream).
 #pragma once
 
-// blocks per CU of the walk's grid: 32 KB of LDS stack per block at the default 16 levels
-static const int kClosestBlocksPerCu = 5;
-
 // queries of one binned launch: bounds the sort's scratch (24 bytes per query) at 96 MB whatever n is, and keeps its indices in 32 bits
 static const long long kClosestBinChunk = 1ll << 22;
 
@@ -18,22 +15,14 @@ static int closest_launch(gnxr_scene *r, const DScene &sc, const gnxr_point_quer
         HIP_TRY(hipGetLastError());
         return GNXR_OK;
     }
-    // the bound of the stack (closest_kernel.hip.h): (children - 1) per node of the deepest path = stack4_need - 1, or the binary depth;
-    // one entry of slack as in trace_launch
-    const bool wide = r->wide_ok;
-    const int entries = wide ? r->cs.stack4_need + 1 : r->cs.bvh_max_depth + 2;
-    const int lds_entries = std::min(entries, Knobs::closest_lds_levels());
     const bool binned = n >= Knobs::closest_bin_min();
     const long long per_launch = binned ? kClosestBinChunk : (long long)n;
-    const int blocks = grid_for(std::min<long long>(n, per_launch), kClosestBlocksPerCu);
-    StreamScratch spill_scratch, sort_scratch;
-    uint2 *spill = nullptr;
-    if (entries > lds_entries) {
-        HIP_TRY(spill_scratch.alloc((size_t)(entries - lds_entries) * (size_t)blocks * kBlock * sizeof(uint2), st));
-        spill = reinterpret_cast<uint2 *>(spill_scratch.p);
-    }
+    const long long most = std::min<long long>(n, per_launch);   // queries of one launch
+    WalkLaunch w;
+    if (int rc = w.plan(r, sizeof(uint2), Knobs::closest_lds_levels(), most, st)) return rc;
     // the sort's arrays: keys and indices twice, the per-tile digit histograms and the scan's tile sums
-    const int max_cnt = (int)std::min<long long>(n, per_launch);
+    StreamScratch sort_scratch;
+    const int max_cnt = (int)most;
     const int max_tiles = (max_cnt + hlbvh::kTile - 1) / hlbvh::kTile;
     const size_t hist_words = (size_t)64 * max_tiles, sums_words = (size_t)std::max(max_tiles, (64 * max_tiles + hlbvh::kTile - 1) / hlbvh::kTile) + 1;
     uint32_t *k_a = nullptr, *k_b = nullptr, *v_a = nullptr, *v_b = nullptr, *hist = nullptr, *sums = nullptr;
@@ -42,7 +31,6 @@ static int closest_launch(gnxr_scene *r, const DScene &sc, const gnxr_point_quer
         k_a = reinterpret_cast<uint32_t *>(sort_scratch.p); k_b = k_a + max_cnt; v_a = k_b + max_cnt; v_b = v_a + max_cnt;
         hist = v_b + max_cnt; sums = hist + hist_words;
     }
-    const size_t lds = (size_t)lds_entries * kBlock * sizeof(uint2);
     for (long long base = 0; base < n; base += per_launch) {
         const long long cnt = std::min<long long>(n - base, per_launch);
         ClosestArrays qa;
@@ -61,10 +49,10 @@ static int closest_launch(gnxr_scene *r, const DScene &sc, const gnxr_point_quer
             }
             order = vin;
         }
-        const int g = grid_for(cnt, kClosestBlocksPerCu);   // never more than `blocks`: the spill is sized for those
-#define GX_CLOSEST(W, C) hipLaunchKernelGGL((k_closest_point<W, C>), dim3(g), dim3(kBlock), lds, st, sc, qa, order, (long long)cnt, lds_entries, entries, spill, d_counts)
-        if (d_counts) { if (wide) GX_CLOSEST(true, true); else GX_CLOSEST(false, true); }
-        else { if (wide) GX_CLOSEST(true, false); else GX_CLOSEST(false, false); }
+#define GX_CLOSEST(W, C) hipLaunchKernelGGL((k_closest_point<W, C>), dim3(w.grid(cnt)), dim3(kBlock), w.lds, st, sc, qa, order, (long long)cnt, w.lds_entries, w.entries, \
+                                            (uint2 *)w.spill, d_counts)
+        if (d_counts) { if (w.wide) GX_CLOSEST(true, true); else GX_CLOSEST(false, true); }
+        else { if (w.wide) GX_CLOSEST(true, false); else GX_CLOSEST(false, false); }
 #undef GX_CLOSEST
         HIP_TRY(hipGetLastError());
     }

@@ -1,0 +1,78 @@
+// bvh_walk.hip.h -- the mechanics the per-lane query walks share (k_closest_point, k_all_hits): the stack, the node decode and the
+// children of an interior node with their boxes.  Nothing here decides a result: what a kernel does with a box, in which order it visits
+// and what it tests at a leaf is that kernel's own.  DESIGN.md, "The walk the queries share", has the bound of the stack and why.
+#pragma once
+#include "kernels.hip.h"
+
+namespace gnxr {
+
+// min / max by selection (the result is one of the arguments, never arithmetic), and a triangle's own box made of them
+GX_DEV float sel_min(float x, float y) { return y < x ? y : x; }
+GX_DEV float sel_max(float x, float y) { return y > x ? y : x; }
+GX_DEV void tri_own_box(V3 a, V3 b, V3 c, V3 *lo, V3 *hi) {
+    *lo = V3(sel_min(sel_min(a.x, b.x), c.x), sel_min(sel_min(a.y, b.y), c.y), sel_min(sel_min(a.z, b.z), c.z));
+    *hi = V3(sel_max(sel_max(a.x, b.x), c.x), sel_max(sel_max(a.y, b.y), c.y), sel_max(sel_max(a.z, b.z), c.z));
+}
+
+// One lane's stack: entry `level`.  Levels below lds_entries are in the block's LDS as stack[level][lane], the others in a global spill,
+// [level][thread] as well.  Entry is 4 bytes (int: bank == lane, conflict-free whatever level each lane is at) or 8 (uint2: lane l of a
+// 32-lane half reads banks 2 l and 2 l + 1 of 64, so ds_read_b64 is conflict-free too; a ds_write_b64, banked modulo 32, costs two passes,
+// where two 4-byte planes would cost two instructions instead).
+template <typename Entry>
+struct WalkStack {
+    Entry *lds;        // this lane's column of the block's LDS stack (stride kBlock)
+    Entry *spill;      // this thread's column of the global spill (stride `threads`)
+    int lds_entries, entries;   // entries: LDS and spill levels together, the bound of the walk (never reached past: put() refuses)
+    long long threads;          // of the grid: the stride of the spill and of the grid-stride loop
+    GX_DEV void init(Entry *lds_base, Entry *spill_base, int lds_entries_, int entries_) {
+        lds = lds_base + threadIdx.x;
+        threads = (long long)gridDim.x * kBlock;
+        spill = spill_base + (blockIdx.x * (long long)kBlock + threadIdx.x);
+        lds_entries = lds_entries_;
+        entries = entries_;
+    }
+    GX_DEV void put(int &sp, Entry e) {
+        if (sp >= entries) return;
+        if (sp < lds_entries) lds[sp * kBlock] = e;
+        else spill[(long long)(sp - lds_entries) * threads] = e;
+        ++sp;
+    }
+    GX_DEV Entry get(int level) const { return level < lds_entries ? lds[level * kBlock] : spill[(long long)(level - lds_entries) * threads]; }
+};
+
+// What a reference says.  WIDE (the 4-wide tree, from DScene::root4): cur < 0 is a leaf and ~cur = first | count << 24, as in k_trace4.
+// Binary (DScene::nodes, from node 0): the node's second dwordx4 holds the count (0: interior) and `first`, which is a leaf's first
+// triangle and an interior node's second child.
+struct WalkNode { bool leaf; int first, count; };
+template <bool WIDE>
+GX_DEV WalkNode walk_decode(const DScene &sc, int cur) {
+    if (WIDE) {
+        const unsigned code = (unsigned)~cur;
+        return cur < 0 ? WalkNode{true, (int)(code & 0xffffffu), (int)(code >> 24)} : WalkNode{false, 0, 0};
+    }
+    const float4 n1 = sc.nodes[2 * cur + 1];
+    const int count = (int)(__float_as_uint(n1.w) & 0xffffu);
+    return {count > 0, __float_as_int(n1.z), count};
+}
+
+// The children of interior node `cur`: f(slot, ref, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z) once per slot, slot a constant.  WIDE: four
+// slots from one load of the DNode4's six SoA planes and its child dwordx4; a slot whose ref is kNode4Empty is absent (f decides what
+// that means).  Binary: slots 0 and 1, the DNode children cur + 1 and `second` (WalkNode::first of cur).
+template <bool WIDE, typename F>
+GX_DEV void walk_children(const DScene &sc, int cur, int second, F f) {
+    if (WIDE) {
+        const float4 *nd = sc.nodes4 + 8 * (long long)cur;
+        const float4 lox = nd[0], loy = nd[1], loz = nd[2], hix = nd[3], hiy = nd[4], hiz = nd[5], ch = nd[6];
+        f(0, __float_as_int(ch.x), lox.x, loy.x, loz.x, hix.x, hiy.x, hiz.x);
+        f(1, __float_as_int(ch.y), lox.y, loy.y, loz.y, hix.y, hiy.y, hiz.y);
+        f(2, __float_as_int(ch.z), lox.z, loy.z, loz.z, hix.z, hiy.z, hiz.z);
+        f(3, __float_as_int(ch.w), lox.w, loy.w, loz.w, hix.w, hiy.w, hiz.w);
+    } else {
+        const int c0 = cur + 1, c1 = second;
+        const float4 a0 = sc.nodes[2 * c0], a1 = sc.nodes[2 * c0 + 1], b0 = sc.nodes[2 * c1], b1 = sc.nodes[2 * c1 + 1];
+        f(0, c0, a0.x, a0.y, a0.z, a0.w, a1.x, a1.y);
+        f(1, c1, b0.x, b0.y, b0.z, b0.w, b1.x, b1.y);
+    }
+}
+
+}  // namespace gnxr

@@ -10,10 +10,7 @@
 // every box encloses those, and subtraction, squaring and addition round monotonically), so `bd2 > best` never drops the winner and
 // `bd2 == best` is entered because a smaller authoring index may tie.  No epsilon anywhere.
 //
-// The stack holds at most (children - 1) entries per node on the path from the root: CompiledScene::stack4_need - 1 on the 4-wide tree,
-// the depth on the binary one.  Its first lds_entries levels live in LDS as 8-byte entries, stack[level][lane]: lane l of a 32-lane half
-// reads banks 2 l and 2 l + 1 of 64, so ds_read_b64 is conflict-free whatever level each lane is at (a ds_write_b64, banked modulo 32,
-// costs two passes; two 4-byte planes would cost two instructions instead); the levels above go to a global spill, [level][thread] as well.
+// The stack (8-byte entries), the node decode and the children's boxes are bvh_walk.hip.h's.
 //
 // Queries arrive in caller order, and neighbouring lanes that walk to different corners of the tree share neither node loads nor control
 // flow.  From kClosestBinMin queries on, the call therefore bins them first: an 18-bit Morton key of p over the root's box (64 cells per
@@ -21,8 +18,8 @@
 // indices -- it gathers the record and scatters the result itself, so nothing else moves.  The key orders the work and nothing more: the
 // records are the same bytes with and without it (DESIGN.md has both timings).
 #pragma once
+#include "bvh_walk.hip.h"
 #include "hlbvh_build.hip.h"
-#include "kernels.hip.h"
 
 namespace gnxr {
 
@@ -33,8 +30,6 @@ struct ClosestArrays {
 };
 
 GX_DEV float cp_dot(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-GX_DEV float cp_min(float x, float y) { return y < x ? y : x; }
-GX_DEV float cp_max(float x, float y) { return y > x ? y : x; }
 GX_DEV float cp_clamp(float p, float lo, float hi) { return p < lo ? lo : (p > hi ? hi : p); }
 
 struct ClosestOnTri {
@@ -81,9 +76,9 @@ GX_DEV float closest_on_triangle(V3 a, V3 b, V3 c, V3 q, ClosestOnTri *r) {
         const float v = vb * denom, w = vc * denom;
         p = (a + v * ab) + w * ac; b1 = v; b2 = w; feature = 0;
     } while (false);
-    p.x = cp_clamp(p.x, cp_min(cp_min(a.x, b.x), c.x), cp_max(cp_max(a.x, b.x), c.x));
-    p.y = cp_clamp(p.y, cp_min(cp_min(a.y, b.y), c.y), cp_max(cp_max(a.y, b.y), c.y));
-    p.z = cp_clamp(p.z, cp_min(cp_min(a.z, b.z), c.z), cp_max(cp_max(a.z, b.z), c.z));
+    V3 lo, hi;
+    tri_own_box(a, b, c, &lo, &hi);
+    p = V3(cp_clamp(p.x, lo.x, hi.x), cp_clamp(p.y, lo.y, hi.y), cp_clamp(p.z, lo.z, hi.z));
     const V3 d = q - p;
     r->p = p; r->b1 = b1; r->b2 = b2; r->feature = feature;
     return cp_dot(d, d);
@@ -91,9 +86,9 @@ GX_DEV float closest_on_triangle(V3 a, V3 b, V3 c, V3 q, ClosestOnTri *r) {
 
 // squared distance from q to the box [lo, hi], per axis e = max(max(lo - q, q - hi), 0): the shape of a triangle's dist2
 GX_DEV float box_dist2(float lox, float loy, float loz, float hix, float hiy, float hiz, V3 q) {
-    const float ex = cp_max(cp_max(lox - q.x, q.x - hix), 0.f);
-    const float ey = cp_max(cp_max(loy - q.y, q.y - hiy), 0.f);
-    const float ez = cp_max(cp_max(loz - q.z, q.z - hiz), 0.f);
+    const float ex = sel_max(sel_max(lox - q.x, q.x - hix), 0.f);
+    const float ey = sel_max(sel_max(loy - q.y, q.y - hiy), 0.f);
+    const float ez = sel_max(sel_max(loz - q.z, q.z - hiz), 0.f);
     return (ex * ex + ey * ey) + ez * ez;
 }
 
@@ -117,38 +112,20 @@ GX_DEV void closest_leaf(const DTri *__restrict__ tris, int first, int n, V3 q, 
 // keys of the child sort: the bits of a non-negative float order as the float does (a NaN, which only a box with a NaN bound gives, sorts
 // behind +inf and is still entered); an absent or dropped child sorts last
 constexpr unsigned kClosestDropped = 0xffffffffu;
+template <bool WIDE>
+GX_DEV unsigned cp_key(int ref, float bd2, float best_d2) { return ((WIDE && ref == kNode4Empty) || bd2 > best_d2) ? kClosestDropped : __float_as_uint(bd2); }
 GX_DEV void cp_sort2(unsigned &ka, int &ra, unsigned &kb, int &rb) {
     if (kb < ka) { const unsigned k = ka; ka = kb; kb = k; const int r = ra; ra = rb; rb = r; }
 }
 
-// One block's stack: entry `level` of this lane.  Levels below lds_entries in LDS, the others in the global spill.
-struct ClosestStack {
-    uint2 *lds;        // this lane's column of the block's LDS stack (stride kBlock)
-    uint2 *spill;      // this thread's column of the global spill (stride `threads`)
-    int lds_entries, entries;   // entries: LDS and spill levels together, the bound of the walk (never reached past: put() refuses)
-    long long threads;
-    GX_DEV void put(int &sp, int ref, unsigned key) {
-        if (sp >= entries) return;
-        const uint2 e = make_uint2((unsigned)ref, key);
-        if (sp < lds_entries) lds[sp * kBlock] = e;
-        else spill[(long long)(sp - lds_entries) * threads] = e;
-        ++sp;
-    }
-    GX_DEV uint2 get(int level) const { return level < lds_entries ? lds[level * kBlock] : spill[(long long)(level - lds_entries) * threads]; }
-};
-
 // WIDE: the 4-wide tree from sc.root4; else the binary tree from node 0.  COUNT: nodes visited and triangles tested of the whole launch are
-// added to counts[0], counts[1] (the measurement's instantiation; never the timed path).
+// added to counts[0], counts[1] (the measurement's instantiation; never the timed path).  A stack entry is (child reference, key).
 template <bool WIDE, bool COUNT>
 static __global__ void __launch_bounds__(kBlock) k_closest_point(DScene sc, ClosestArrays qa, const uint32_t *__restrict__ order, long long n, int lds_entries, int entries,
                                                                  uint2 *spill, unsigned long long *counts) {
     extern __shared__ uint2 cp_stack_lds[];
-    ClosestStack stack;
-    stack.lds = cp_stack_lds + threadIdx.x;
-    stack.threads = (long long)gridDim.x * kBlock;
-    stack.spill = spill + (blockIdx.x * (long long)kBlock + threadIdx.x);
-    stack.lds_entries = lds_entries;
-    stack.entries = entries;
+    WalkStack<uint2> stack;
+    stack.init(cp_stack_lds, spill, lds_entries, entries);
     unsigned long long cntNodes = 0, cntTris = 0;
     for (long long slot = blockIdx.x * (long long)kBlock + threadIdx.x; slot < n; slot += stack.threads) {
         const long long i = order ? (long long)order[slot] : slot;   // binned: the slot-th query in Morton order
@@ -161,47 +138,30 @@ static __global__ void __launch_bounds__(kBlock) k_closest_point(DScene sc, Clos
             int sp = 0;
             int cur = WIDE ? sc.root4 : 0;
             while (true) {
-                bool leaf;
-                int first = 0, count = 0;
-                if (WIDE) {
-                    leaf = cur < 0;
-                    if (leaf) { const unsigned code = (unsigned)~cur; first = (int)(code & 0xffffffu); count = (int)(code >> 24); }
-                } else {
-                    const float4 n1 = sc.nodes[2 * cur + 1];
-                    const unsigned meta = __float_as_uint(n1.w);
-                    count = (int)(meta & 0xffffu);
-                    leaf = count > 0;
-                    first = __float_as_int(n1.z);   // a leaf's first triangle, an interior node's second child
-                }
+                const WalkNode node = walk_decode<WIDE>(sc, cur);
                 if (COUNT) cntNodes++;
                 int next = kNode4Empty;   // the child to enter, or none
-                if (leaf) {
-                    if (COUNT) cntTris += (unsigned)count;
-                    closest_leaf(sc.tris, first, count, q, &best);
-                } else if (WIDE) {
-                    const float4 *nd = sc.nodes4 + 8 * (long long)cur;
-                    const float4 lox = nd[0], loy = nd[1], loz = nd[2], hix = nd[3], hiy = nd[4], hiz = nd[5];
-                    const float4 ch = nd[6];
-                    int r0 = __float_as_int(ch.x), r1 = __float_as_int(ch.y), r2c = __float_as_int(ch.z), r3 = __float_as_int(ch.w);
-                    const float b0 = box_dist2(lox.x, loy.x, loz.x, hix.x, hiy.x, hiz.x, q), b1 = box_dist2(lox.y, loy.y, loz.y, hix.y, hiy.y, hiz.y, q);
-                    const float b2 = box_dist2(lox.z, loy.z, loz.z, hix.z, hiy.z, hiz.z, q), b3 = box_dist2(lox.w, loy.w, loz.w, hix.w, hiy.w, hiz.w, q);
-                    unsigned k0 = (r0 == kNode4Empty || b0 > best.d2) ? kClosestDropped : __float_as_uint(b0);
-                    unsigned k1 = (r1 == kNode4Empty || b1 > best.d2) ? kClosestDropped : __float_as_uint(b1);
-                    unsigned k2 = (r2c == kNode4Empty || b2 > best.d2) ? kClosestDropped : __float_as_uint(b2);
-                    unsigned k3 = (r3 == kNode4Empty || b3 > best.d2) ? kClosestDropped : __float_as_uint(b3);
-                    cp_sort2(k0, r0, k1, r1); cp_sort2(k2, r2c, k3, r3); cp_sort2(k0, r0, k2, r2c); cp_sort2(k1, r1, k3, r3); cp_sort2(k1, r1, k2, r2c);
-                    if (k3 != kClosestDropped) stack.put(sp, r3, k3);
-                    if (k2 != kClosestDropped) stack.put(sp, r2c, k2);
-                    if (k1 != kClosestDropped) stack.put(sp, r1, k1);
-                    if (k0 != kClosestDropped) next = r0;
+                if (node.leaf) {
+                    if (COUNT) cntTris += (unsigned)node.count;
+                    closest_leaf(sc.tris, node.first, node.count, q, &best);
                 } else {
-                    int r0 = cur + 1, r1 = first;
-                    const float4 a0 = sc.nodes[2 * r0], a1 = sc.nodes[2 * r0 + 1], c0 = sc.nodes[2 * r1], c1 = sc.nodes[2 * r1 + 1];
-                    const float b0 = box_dist2(a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, q), b1 = box_dist2(c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, q);
-                    unsigned k0 = b0 > best.d2 ? kClosestDropped : __float_as_uint(b0);
-                    unsigned k1 = b1 > best.d2 ? kClosestDropped : __float_as_uint(b1);
-                    cp_sort2(k0, r0, k1, r1);
-                    if (k1 != kClosestDropped) stack.put(sp, r1, k1);
+                    int r[4]; float b[4];   // slots 2 and 3 exist on the 4-wide tree only
+                    walk_children<WIDE>(sc, cur, node.first, [&](int s, int ref, float lox, float loy, float loz, float hix, float hiy, float hiz) __attribute__((always_inline)) {
+                        r[s] = ref;
+                        b[s] = box_dist2(lox, loy, loz, hix, hiy, hiz, q);
+                    });
+                    int r0 = r[0], r1 = r[1];   // scalars for the sort: on the arrays' elements hipcc builds the exchanges from selects, 6 VGPRs more
+                    unsigned k0 = cp_key<WIDE>(r0, b[0], best.d2), k1 = cp_key<WIDE>(r1, b[1], best.d2);
+                    if (WIDE) {
+                        int r2 = r[2], r3 = r[3];
+                        unsigned k2 = cp_key<WIDE>(r2, b[2], best.d2), k3 = cp_key<WIDE>(r3, b[3], best.d2);
+                        cp_sort2(k0, r0, k1, r1); cp_sort2(k2, r2, k3, r3); cp_sort2(k0, r0, k2, r2); cp_sort2(k1, r1, k3, r3); cp_sort2(k1, r1, k2, r2);
+                        if (k3 != kClosestDropped) stack.put(sp, make_uint2((unsigned)r3, k3));
+                        if (k2 != kClosestDropped) stack.put(sp, make_uint2((unsigned)r2, k2));
+                    } else {
+                        cp_sort2(k0, r0, k1, r1);
+                    }
+                    if (k1 != kClosestDropped) stack.put(sp, make_uint2((unsigned)r1, k1));
                     if (k0 != kClosestDropped) next = r0;
                 }
                 while (next == kNode4Empty && sp > 0) {

@@ -28,7 +28,6 @@ struct DenoiseImage {
 };
 
 GX_DEV float denoise_lum(float r, float g, float b) { return (0.212671f * r + 0.715160f * g) + 0.072169f * b; }
-GX_DEV bool denoise_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
 // div = max(albedo + (1 - coverage), 1/1024) per channel, a NaN giving 1/1024; 1 without an albedo buffer
 GX_DEV void denoise_divisor(const float4 *__restrict__ albedo, long long p, float *dr, float *dg, float *db) {
     *dr = *dg = *db = 1.f;
@@ -54,7 +53,7 @@ static __global__ void __launch_bounds__(kBlock) k_denoise_prepare(const float4 
         } else {
             cr = ca.x / dr; cg = ca.y / dg; cb = ca.z / db;
         }
-        const bool ok = denoise_finite(cr) && denoise_finite(cg) && denoise_finite(cb) && denoise_finite(v);
+        const bool ok = gx_finite(cr) && gx_finite(cg) && gx_finite(cb) && gx_finite(v);
         work[p] = ok ? make_float4(cr, cg, cb, v) : make_float4(0.f, 0.f, 0.f, -1.f);
         float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
         if (normal) { const float4 n = normal[p]; g.x = n.x; g.y = n.y; g.z = n.z; }

@@ -25,6 +25,8 @@ static constexpr float GX_MACH_EPS = 0x1p-24f;       // std::numeric_limits<floa
 static constexpr float GX_SHADOW_EPS = 0.0001f;
 // gamma(n) = (n * MachineEpsilon) / (1 - n * MachineEpsilon), GNXRayTracer.h:354-357 (constant-folded in fp32)
 #define GX_GAMMA(n) (((n) * GX_MACH_EPS) / (1 - (n) * GX_MACH_EPS))
+// neither an infinity nor a NaN, read off the exponent bits
+GX_DEV bool gx_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
 
 // ---- float libm: glibc 2.35's own algorithms (sysdeps/ieee754/flt-32/{e_logf,e_expf,s_sinf,s_cosf}.c, the ARM
 // optimized-routines implementations: table + short polynomial evaluated in double, one rounding to float at the end).

@@ -71,8 +71,6 @@ struct ExposureParams {
     float key, low, high, rate, min_exposure, max_exposure;
 };
 
-GX_DEV bool display_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
-
 constexpr int kExposureBlock = 64;   // one wave per view: 64 lanes x 4 words are the 256 bins
 
 struct ExposureSums { float skip, keep, sw, sx; };
@@ -114,7 +112,7 @@ static __global__ void __launch_bounds__(kExposureBlock) k_exposure(const unsign
                 w = next;
             }
             const float pv = prev ? prev[v].x : 0.f;
-            const bool prev_ok = pv > 0.f && display_finite(pv);
+            const bool prev_ok = pv > 0.f && gx_finite(pv);
             float L = 0.f, target;
             if (e.sw > 0.f) {
                 const float m = e.sx / e.sw;

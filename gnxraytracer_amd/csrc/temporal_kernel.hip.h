@@ -35,8 +35,6 @@ struct MotionOut {
     int *prim;
 };
 
-GX_DEV bool temporal_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
-
 // camera_ray (kernels.hip.h) for the film sample (fx, fy) = (0.5, 0.5) and lens_radius taken as 0: the same operations in the same order,
 // without the sampler.  tMax is the caller's (+inf).
 GX_DEV void camera_ray_centre(const DCamera &cam, int px, int py, V3 *o, V3 *d) {
@@ -127,7 +125,7 @@ __global__ void __launch_bounds__(kBlock) k_motion(DScene sc, const MotionView *
                 tq = gx_sqrt((e.x * e.x + e.y * e.y) + e.z * e.z);
             }
         }
-        const bool ok = w > 0.f && temporal_finite(xq) && temporal_finite(yq) && temporal_finite(tq);
+        const bool ok = w > 0.f && gx_finite(xq) && gx_finite(yq) && gx_finite(tq);
         out.motion[lp] = ok ? make_float4(xq, yq, tq, 1.f) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
 }
@@ -167,7 +165,7 @@ GX_DEV TemporalTap temporal_tap(const TemporalArrays &a, long long view_base, lo
 struct TemporalSums { float sw, cr, cg, cb, s1, s2, sN; };
 GX_DEV void temporal_weigh(const TemporalTap &t, int prim, float4 g, float tq, const TemporalParams &tp, TemporalSums *s) {
     bool ok = t.b > 0.f && t.inside && t.s.z > 0.f && t.prim == prim;
-    ok = ok && temporal_finite(t.c.x) && temporal_finite(t.c.y) && temporal_finite(t.c.z) && temporal_finite(t.s.x) && temporal_finite(t.s.y);
+    ok = ok && gx_finite(t.c.x) && gx_finite(t.c.y) && gx_finite(t.c.z) && gx_finite(t.s.x) && gx_finite(t.s.y);
     if (prim >= 0) {
         ok = ok && fabsf(t.g.w - tq) <= tp.depth_tol * tq;
         ok = ok && ((g.x * t.g.x + g.y * t.g.y) + g.z * t.g.z) >= tp.normal_cos;
@@ -190,7 +188,7 @@ static __global__ void __launch_bounds__(kBlock) k_temporal_accumulate(TemporalA
     for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < tp.npix; p += (long long)gridDim.x * blockDim.x) {
         const float4 c = a.color[p];
         const float l = (0.212671f * c.x + 0.715160f * c.y) + 0.072169f * c.z;
-        const bool cur_ok = temporal_finite(c.x) && temporal_finite(c.y) && temporal_finite(c.z);
+        const bool cur_ok = gx_finite(c.x) && gx_finite(c.y) && gx_finite(c.z);
         TemporalSums s = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         if (a.hist_color) {   // uniform
             const float4 mo = a.motion[p];

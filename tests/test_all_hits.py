@@ -13,7 +13,7 @@ import torch
 import allhits_reference as ar
 import scenes
 from conftest import ROOT
-from test_closest_point import chain_scene, concentric_mesh, dragon, mesh_of, mesh_scene
+from test_closest_point import binary_depth, chain_scene, concentric_mesh, dragon, mesh_of, mesh_scene
 
 ERR_INVALID = -1
 F = np.float32
@@ -88,6 +88,30 @@ def case(name):
         rays[::5, 3] = rng.uniform(0.5, 4.0, len(rays[::5]))   # a fifth with a finite tmax inside the scene
         _cases[name] = Case(v, idx, rays)
     return _cases[name]
+
+
+_deep_tree_cache = []
+
+
+def deep_tree_case(gx):
+    """(rays, brute force with K = 32) of chain_scene(36): rays along and around the x axis through the chain; computed once, shared, never
+    written"""
+    if not _deep_tree_cache:
+        v, idx = mesh_of(chain_scene(gx))
+        rng = np.random.default_rng(8)
+        n = 1024
+        # from just beyond the small end, so that the watertight test's error bound (which grows with the distance) keeps every triangle
+        o = np.stack([-(2.0 ** -rng.uniform(30, 44, n)), np.zeros(n), np.zeros(n)], axis=1)
+        o[:64, 0] = -(2.0 ** -40)
+        d = np.stack([np.ones(n), np.zeros(n), np.zeros(n)], axis=1)
+        o[64:, 1:] = rng.normal(0, 0.2, (n - 64, 2)) * 2.0 ** -rng.uniform(0, 40, (n - 64, 1))   # off the axis: the small triangles are missed
+        d[512:, 1:] = rng.normal(0, 0.1, (n - 512, 2))
+        rays = rays_of(o, d)
+        want = ar.all_hits(v, idx, rays, 32)
+        for x in (rays,) + tuple(want):
+            x.setflags(write=False)
+        _deep_tree_cache.extend([rays, want])
+    return _deep_tree_cache
 
 
 def box_mesh_closed(lo=(-1, -1, -1), hi=(1, 1, 1)):
@@ -452,20 +476,9 @@ def test_deep_tree(gpu):
     """chain_scene(36): rays along the x axis pass through all 36 triangles with a sibling on the stack per level.  Run with the default
     LDS levels, where the tree's need exceeds them (the global spill carries the rest), and forced onto 2 LDS levels through
     GNXR_ALLHITS_LDS_LEVELS, the launch's knob."""
-    b = chain_scene(gpu)
-    v, idx = mesh_of(b)
-    rng = np.random.default_rng(8)
-    n = 1024
-    # from just beyond the small end, so that the watertight test's error bound (which grows with the distance) keeps every triangle
-    o = np.stack([-(2.0 ** -rng.uniform(30, 44, n)), np.zeros(n), np.zeros(n)], axis=1)
-    o[:64, 0] = -(2.0 ** -40)
-    d = np.stack([np.ones(n), np.zeros(n), np.zeros(n)], axis=1)
-    o[64:, 1:] = rng.normal(0, 0.2, (n - 64, 2)) * 2.0 ** -rng.uniform(0, 40, (n - 64, 1))   # off the axis: the small triangles are missed
-    d[512:, 1:] = rng.normal(0, 0.1, (n - 512, 2))
-    rays = rays_of(o, d)
-    want = ar.all_hits(v, idx, rays, 32)
+    rays, want = deep_tree_case(gpu)
     assert (want[1][:64] == 36).all() and (want[1] > 32).sum() > 64 and len(set(want[1])) > 20
-    scene = gpu.Scene(b)
+    scene = gpu.Scene(chain_scene(gpu))
     assert scene.bvh4()[2] > 16, scene.bvh4()[2]   # more than the default LDS levels
     assert_same(device_lists(scene, rays, 32), want)
     os.environ["GNXR_ALLHITS_LDS_LEVELS"] = "2"
@@ -473,6 +486,24 @@ def test_deep_tree(gpu):
         assert_same(device_lists(scene, rays, 32), want)
         c = case("dragon")
         assert_same(device_lists(gpu.Scene(dragon()), c.rays, 4), c.want(4))
+    finally:
+        del os.environ["GNXR_ALLHITS_LDS_LEVELS"]
+
+
+@pytest.mark.gpu
+def test_deep_binary_tree_spills(gpu):
+    """test_deep_tree's chain and rays on a scene kept on the binary tree by the creation switch, with 2 LDS levels: the binary walk, its
+    LDS levels and its global spill together.  chain_scene(36) creates (its depth stays inside the 64-entry limit of scene creation)."""
+    rays, want = deep_tree_case(gpu)
+    os.environ["GNXR_BINARY_BVH"] = "1"
+    try:
+        scene = gpu.Scene(chain_scene(gpu))
+    finally:
+        del os.environ["GNXR_BINARY_BVH"]
+    assert binary_depth(scene) + 2 > 2   # the walk's bound on this tree against the LDS levels below: the spill carries the rest
+    os.environ["GNXR_ALLHITS_LDS_LEVELS"] = "2"
+    try:
+        assert_same(device_lists(scene, rays, 32), want)
     finally:
         del os.environ["GNXR_ALLHITS_LDS_LEVELS"]
 

@@ -114,6 +114,27 @@ def dragon_case():
     return _dragon_cache
 
 
+_deep_tree_cache = []
+
+
+def deep_tree_case(gx):
+    """(queries, brute force) of chain_scene(36): points on and around the x axis beyond the smallest triangle, and some anywhere; computed
+    once, shared, never written"""
+    if not _deep_tree_cache:
+        v, idx = mesh_of(chain_scene(gx))
+        rng = np.random.default_rng(8)
+        x = (2.0 ** -35) * rng.uniform(-2, 1, 4096)
+        pts = np.stack([x, rng.normal(0, 2.0 ** -36, 4096), rng.normal(0, 2.0 ** -36, 4096)], axis=1).astype(F)
+        pts[:64, 1:] = 0   # exactly on the axis
+        pts = np.concatenate([pts, uniform_in(*bound_of(v), 512, rng, 1.5)])
+        q = queries_of(pts)
+        want = cr.closest_points(v, idx, q)
+        q.setflags(write=False)
+        want.setflags(write=False)
+        _deep_tree_cache.extend([q, want])
+    return _deep_tree_cache
+
+
 # ---------------------------------------------------------------- CPU
 def test_symbols_and_records(gx):
     lib = C.CDLL(gx.LIB_PATH)
@@ -331,23 +352,46 @@ def test_deep_tree(gpu, order):
     """chain_scene(36): from points on the x axis beyond the smallest triangle the walk descends the whole chain with a sibling on its stack
     per level.  Run with the default LDS levels, where the tree's need exceeds them (the global spill carries the rest), and forced onto 2
     LDS levels through GNXR_CLOSEST_LDS_LEVELS, the launch's knob."""
-    b = chain_scene(gpu)
-    v, idx = mesh_of(b)
-    rng = np.random.default_rng(8)
-    x = (2.0 ** -35) * rng.uniform(-2, 1, 4096)
-    pts = np.stack([x, rng.normal(0, 2.0 ** -36, 4096), rng.normal(0, 2.0 ** -36, 4096)], axis=1).astype(F)
-    pts[:64, 1:] = 0   # exactly on the axis
-    pts = np.concatenate([pts, uniform_in(*bound_of(v), 512, rng, 1.5)])
-    q = queries_of(pts)
-    want = cr.closest_points(v, idx, q)
+    q, want = deep_tree_case(gpu)
     assert (want["prim"] >= 30).sum() > 3000
-    scene = gpu.Scene(b)
+    scene = gpu.Scene(chain_scene(gpu))
     assert scene.bvh4()[2] > 16, scene.bvh4()[2]   # more than the default LDS levels
     assert_same(device_records(scene, q), want)
     os.environ["GNXR_CLOSEST_LDS_LEVELS"] = "2"
     try:
         assert_same(device_records(scene, q), want)
         assert_same(device_records(gpu.Scene(dragon()), dragon_case()["q"]), dragon_case()["want"])
+    finally:
+        del os.environ["GNXR_CLOSEST_LDS_LEVELS"]
+
+
+def binary_depth(scene):
+    """the depth of the flattened binary tree (the root at 0), walked through scene.bvh(): an interior node's children are the next node
+    and the node at its offset"""
+    _, meta, _ = scene.bvh()
+    depth, todo = 0, [(0, 0)]
+    while todo:
+        i, d = todo.pop()
+        depth = max(depth, d)
+        if meta[i, 1] == 0:
+            todo += [(i + 1, d + 1), (int(meta[i, 0]), d + 1)]
+    return depth
+
+
+@pytest.mark.gpu
+def test_deep_binary_tree_spills(gpu, order):
+    """test_deep_tree's chain and points on a scene kept on the binary tree by the creation switch, with 2 LDS levels: the binary walk,
+    its LDS levels and its global spill together.  chain_scene(36) creates (its depth stays inside the 64-entry limit of scene creation)."""
+    q, want = deep_tree_case(gpu)
+    os.environ["GNXR_BINARY_BVH"] = "1"
+    try:
+        scene = gpu.Scene(chain_scene(gpu))
+    finally:
+        del os.environ["GNXR_BINARY_BVH"]
+    assert binary_depth(scene) + 2 > 2   # the walk's bound on this tree against the LDS levels below: the spill carries the rest
+    os.environ["GNXR_CLOSEST_LDS_LEVELS"] = "2"
+    try:
+        assert_same(device_records(scene, q), want)
     finally:
         del os.environ["GNXR_CLOSEST_LDS_LEVELS"]
 
