@@ -939,6 +939,28 @@ class Scene:
         return out
 
     # closest-point queries (gnxr_closest_point_device / gnxr_closest_point)
+    def _point_queries(self, name, points, max_distance, stream, radius="max_distance"):
+        """The (n, 4) float32 gnxr_point_query records of the point queries (closest_point, within, count_within, nearest): `points` as
+        ready-made records, or (n, 3) points with `max_distance` (the argument the method calls `radius`) None, a number or an (n,)
+        tensor, packed on `stream`.  The device of ready-made records is checked by the caller's _query_args / _expect."""
+        import torch
+        if _is_tensor(points, torch.float32, (None, 4)):
+            if max_distance is not None:
+                raise ValueError(f"{name}: (n, 4) points are ready-made query records; {radius} must be None")
+            return points
+        if not _is_tensor(points, torch.float32, (None, 3), self.device):
+            _refuse(points, f"{name}: points: expected a contiguous torch.float32 (n, 3) or (n, 4) tensor on cuda:{self.device}")
+        if isinstance(max_distance, torch.Tensor):
+            _expect(f"{name}: {radius}", max_distance, torch.float32, (), points.device)
+            _same_count(name, radius, max_distance.shape[0], points.shape[0], "points")
+        elif max_distance is not None and (isinstance(max_distance, bool) or not isinstance(max_distance, (int, float, np.integer, np.floating))):
+            raise TypeError(f"{name}: {radius} must be None, a number or a float32 (n,) tensor, got {type(max_distance).__name__}")
+        with torch.cuda.stream(_stream_pair(stream, points.device)[1]):
+            queries = torch.empty((points.shape[0], 4), dtype=torch.float32, device=points.device)
+            queries[:, 0:3] = points
+            queries[:, 3] = float("inf") if max_distance is None else max_distance
+        return queries
+
     def closest_point(self, points, max_distance=None, out=None, **launch):
         """The nearest triangle to points already on the GPU (gnxr_closest_point_device; the definition, operation by operation:
         include/gnxr.h).  `points`: a contiguous float32 (n, 3) tensor on the scene's device, with `max_distance` None (unbounded), a
@@ -953,22 +975,7 @@ class Scene:
         import torch
         _only_kw("closest_point", launch, ("stream", "counts"))
         stream, counts = launch.get("stream"), launch.get("counts")
-        if _is_tensor(points, torch.float32, (None, 4)):
-            if max_distance is not None:
-                raise ValueError("closest_point: (n, 4) points are ready-made query records; max_distance must be None")
-            queries = points
-        else:
-            if not _is_tensor(points, torch.float32, (None, 3), self.device):
-                _refuse(points, f"closest_point: points: expected a contiguous torch.float32 (n, 3) or (n, 4) tensor on cuda:{self.device}")
-            if isinstance(max_distance, torch.Tensor):
-                _expect("closest_point: max_distance", max_distance, torch.float32, (), points.device)
-                _same_count("closest_point", "max_distance", max_distance.shape[0], points.shape[0], "points")
-            elif max_distance is not None and (isinstance(max_distance, bool) or not isinstance(max_distance, (int, float, np.integer, np.floating))):
-                raise TypeError(f"closest_point: max_distance must be None, a number or a float32 (n,) tensor, got {type(max_distance).__name__}")
-            with torch.cuda.stream(_stream_pair(stream, points.device)[1]):
-                queries = torch.empty((points.shape[0], 4), dtype=torch.float32, device=points.device)
-                queries[:, 0:3] = points
-                queries[:, 3] = float("inf") if max_distance is None else max_distance
+        queries = self._point_queries("closest_point", points, max_distance, stream)
         n, out, st, _ = self._query_args("closest_point", [("points", queries, torch.float32, 4)], out, 8, stream)
         if counts is None:
             _check(lib().gnxr_closest_point_device(self._h, _ptr(queries), n, _ptr(out), _addr(st)))
@@ -1086,6 +1093,71 @@ class Scene:
                                     hits.ctypes.data_as(C.POINTER(_abi.RayHit)) if max_hits > 0 else None, counts.ctypes.data_as(C.POINTER(C.c_int32))))
         return hits, counts
 
+    # neighbour queries (gnxr_near_device / gnxr_near)
+    def _near(self, name, points, radius, max_near, lowest, flags, out, counts_out, launch, radius_name="radius"):
+        import torch
+        _only_kw(name, launch, ("stream", "counts"))
+        stream, work = launch.get("stream"), launch.get("counts")
+        what = "k" if flags else "max_near"
+        if isinstance(max_near, bool) or not isinstance(max_near, (int, np.integer)):
+            raise TypeError(f"{name}: {what} must be an integer, got {type(max_near).__name__}")
+        max_near = int(max_near)
+        if not lowest <= max_near <= NEAR_MAX:
+            raise ValueError(f"{name}: {what} must be in [{lowest}, {NEAR_MAX}], got {max_near}")
+        queries = self._point_queries(name, points, radius, stream, radius_name)
+        _expect(f"{name}: points", queries, torch.float32, (4,), self.device)
+        n = queries.shape[0]
+        st, _, out, counts_out = _outputs(stream, queries.device, (f"{name}: out", out, (n, max_near, 8), torch.float32),
+                                          (f"{name}: counts_out", counts_out, (n,), torch.int32))
+        records = _ptr(out) if max_near else None
+        if work is None:
+            _check(lib().gnxr_near_device(self._h, _ptr(queries), n, max_near, flags, records, _ptr(counts_out), _addr(st)))
+        else:
+            if not _is_tensor(work, torch.int64, (2,), queries.device):
+                _refuse(work, f"{name}: counts must be a contiguous torch.int64 (2,) tensor on {queries.device}")
+            _check(lib().gnxr_near_counted_device(self._h, _ptr(queries), n, max_near, flags, records, _ptr(counts_out), _ptr(work), _addr(st)))
+        ints = out.view(torch.int32)
+        return NearLists(counts_out, out, ints[:, :, 0], out[:, :, 1], out[:, :, 2:5], out[:, :, 5], out[:, :, 6], ints[:, :, 7])
+
+    def within(self, points, radius, max_near, out=None, counts_out=None, **launch):
+        """EVERY triangle within `radius` of points already on the GPU (gnxr_near_device, GNXR_NEAR_ALL; the definition, triangle by
+        triangle: include/gnxr.h, "Neighbour queries").  `points` and `radius` take the forms closest_point takes for its points and
+        max_distance: a contiguous float32 (n, 3) tensor on the scene's device with `radius` None (unbounded: every triangle), a number
+        or a float32 (n,) tensor; or (n, 4) ready-made gnxr_point_query records with `radius` None.  `max_near` = K in [0, NEAR_MAX].
+        Returns NearLists: `count`, int32 (n,) (`counts_out` when given) -- all triangles with dist2 <= radius^2, never clamped to K --,
+        and the (n, K, 8) float32 gnxr_closest_point records (`out` when given) of the first min(count, K) of them in ascending
+        (dist2, prim), the remaining slots empty (prim -1, dist2 +inf, the rest 0), with named views of them.  The walk reads the
+        scene's live tree (after update_vertices, rebuild_bvh, set_geometry and SkinnedMesh.pose it answers for the geometry the scene
+        holds now); spheres are not considered.  Keywords of the launch, as for closest_point: `stream=` (None: torch's current
+        stream; a torch.cuda.Stream or a hipStream_t as an int; the work is queued there and nothing waits) and, for measurements,
+        `counts=`: an int64 (2,) tensor on the same device that the call adds nodes visited and triangles tested to, through the
+        kernel's slower counting form.  (Their refusals are exercised in tests/test_near.py.)"""
+        return self._near("within", points, radius, max_near, 0, _abi.NEAR_ALL, out, counts_out, launch)
+
+    def count_within(self, points, radius, **launch):
+        """within with max_near = 0: the int32 (n,) number of triangles within `radius` of each point, and no list."""
+        return self._near("count_within", points, radius, 0, 0, _abi.NEAR_ALL, None, None, launch).count
+
+    def nearest(self, points, k, max_distance=None, out=None, counts_out=None, **launch):
+        """The `k` nearest triangles to points already on the GPU (gnxr_near_device, GNXR_NEAR_NEAREST), k in [1, NEAR_MAX]: the lists
+        are within(points, max_distance, k)'s byte for byte, `count` is the number of slots filled, min(within's count, k), and the
+        walk prunes on the k-th distance once a list is full, so it visits no more of the tree than the k nearest need.  nearest(points,
+        1) holds closest_point's record wherever that has a winner.  `points`, `max_distance`, `out`, `counts_out` and the launch
+        keywords: as for within."""
+        return self._near("nearest", points, max_distance, k, 1, _abi.NEAR_NEAREST, out, counts_out, launch, "max_distance")
+
+    def Near(self, queries, max_near, nearest=False):
+        """within / nearest for numpy arrays (gnxr_near): `queries` is (n, 4) float32 -- x, y, z, max_distance (np.inf: unbounded).
+        Returns (records, counts): an (n, max_near) structured array of CLOSEST_DTYPE and the int32 (n,) counts."""
+        queries = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, 4)
+        max_near = int(max_near)
+        records = np.zeros((len(queries), max(max_near, 0)), dtype=CLOSEST_DTYPE)
+        counts = np.zeros(len(queries), dtype=np.int32)
+        _check(lib().gnxr_near(self._h, queries.ctypes.data_as(C.POINTER(_abi.PointQuery)), len(queries), max_near,
+                               _abi.NEAR_NEAREST if nearest else _abi.NEAR_ALL,
+                               records.ctypes.data_as(C.POINTER(_abi.ClosestPoint)) if max_near > 0 else None, counts.ctypes.data_as(C.POINTER(C.c_int32))))
+        return records, counts
+
     MOTION_CHANNELS = ("motion", "guide", "prim")
 
     def motion(self, width, height, prev_cameras, cameras=None, prev_vertices=None, out=None, stream=None):
@@ -1148,7 +1220,14 @@ RayHitLists.__doc__ = """Scene.all_hits's result: `records`, the (n, K, 4) float
 hits in ascending (t, prim), then (+inf, -1, 0, 0) --, views of it -- `t` (n, K), `prim` (n, K) (int32: authoring-order triangle, -1 in an
 empty slot) and `b` (n, K, 2) = b1, b2, the weights of the second and third vertex -- and `count`, int32 (n,): all hits, never clamped."""
 
+NearLists = collections.namedtuple("NearLists", "count records prim dist2 p b1 b2 feature")
+NearLists.__doc__ = """Scene.within's and Scene.nearest's result: `count`, int32 (n,) -- within: all triangles inside the radius, never clamped;
+nearest: the slots filled --, `records`, the (n, K, 8) float32 gnxr_closest_point records -- per query the first min(count, K) near
+triangles in ascending (dist2, prim), then empty slots (prim -1, dist2 +inf, the rest 0) --, and views of it: `prim` (n, K) (int32:
+authoring-order triangle), `dist2` (n, K), `p` (n, K, 3), `b1`, `b2` (n, K) and `feature` (n, K) (int32, as in ClosestPoints)."""
+
 ALL_HITS_MAX = 32   # GNXR_ALL_HITS_MAX
+NEAR_MAX = 32   # GNXR_NEAR_MAX
 CONTAINS_DIRECTION = (0.8017837, 0.5345225, 0.26726124)   # GNXR_CONTAINS_DIRECTION_*: (3, 2, 1) / sqrt(14) to within an ulp of fp32
 
 

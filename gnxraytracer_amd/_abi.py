@@ -18,6 +18,7 @@ INTEGRATOR_PATH, INTEGRATOR_VOLPATH, INTEGRATOR_WHITTED, INTEGRATOR_DIRECT = 0, 
 DIRECT_SAMPLE_ALL, DIRECT_SAMPLE_ONE = 0, 1
 LIGHTS_SPATIAL, LIGHTS_UNIFORM, LIGHTS_POWER = 0, 1, 2
 MEDIUM_HOMOGENEOUS, MEDIUM_GRID = 1, 2
+NEAR_ALL, NEAR_NEAREST = 0, 1   # GNXR_NEAR_*: the flag word of gnxr_near_device
 DMEDIUM_BYTES = 128   # one record of gnxr_scene_media_tables(which = 0): sizeof(DMedium), csrc/gnxr_device_types.h
 DLIGHT_BYTES = 112   # one record of gnxr_scene_light_tables(which = 0): sizeof(DLight), csrc/gnxr_device_types.h
 DTEXTURE_BYTES = 112   # one record of gnxr_scene_texture_tables(which = 0): sizeof(DTexture), csrc/gnxr_device_types.h
@@ -276,6 +277,9 @@ PROTOTYPES = {
     "gnxr_trace_all_device": (C.c_int, [VP, VP, i64, i32, VP, VP, VP]),   # rays, n, max_hits, hits, counts: device addresses + hipStream_t
     "gnxr_trace_all_counted_device": (C.c_int, [VP, VP, i64, i32, VP, VP, VP, VP]),   # ..., three uint64 on the device, hipStream_t
     "gnxr_trace_all": (C.c_int, [VP, P(Ray), i64, i32, P(RayHit), P(i32)]),
+    "gnxr_near_device": (C.c_int, [VP, VP, i64, i32, u32, VP, VP, VP]),   # queries, n, max_near, flags, records, counts: device addresses + hipStream_t
+    "gnxr_near_counted_device": (C.c_int, [VP, VP, i64, i32, u32, VP, VP, VP, VP]),   # ..., two uint64 on the device, hipStream_t
+    "gnxr_near": (C.c_int, [VP, P(PointQuery), i64, i32, u32, P(ClosestPoint), P(i32)]),
     "gnxr_li_device": (C.c_int, [VP, P(RenderParams), VP, VP, i64, VP, VP, P(Stats)]),   # device addresses + hipStream_t
     "gnxr_render_views_device": (C.c_int, [VP, P(RenderParams), P(Camera), P(i32), i32, VP, VP, P(Stats)]),   # cameras, media: host; images: device
     "gnxr_render_aov_device": (C.c_int, [VP, P(RenderParams), P(Camera), P(i32), i32, P(AovBuffers), VP, P(Stats)]),   # cameras, media: host; buffers: device

@@ -6,8 +6,39 @@
 // queries of one binned launch: bounds the sort's scratch (24 bytes per query) at 96 MB whatever n is, and keeps its indices in 32 bits
 static const long long kClosestBinChunk = 1ll << 22;
 
+// The Morton binning of a batch of point queries (closest_kernel.hip.h: k_closest_keys, then three passes of the HLBVH stage's radix sort
+// over (key, index)), shared by closest_launch and near_launch.  reserve() takes the sort's arrays for launches of at most `most` queries
+// from the stream-ordered allocator; sort() queues the key and the passes for the m queries at `queries` and returns their indices in
+// Morton order (valid until the next sort()).  The key orders the work and nothing more.
+struct QueryBinning {
+    StreamScratch scratch;
+    uint32_t *k_a = nullptr, *k_b = nullptr, *v_a = nullptr, *v_b = nullptr, *hist = nullptr, *sums = nullptr;
+    int reserve(long long most, hipStream_t st) {
+        // keys and indices twice, the per-tile digit histograms and the scan's tile sums
+        const int max_cnt = (int)most;
+        const int max_tiles = (max_cnt + hlbvh::kTile - 1) / hlbvh::kTile;
+        const size_t hist_words = (size_t)64 * max_tiles, sums_words = (size_t)std::max(max_tiles, (64 * max_tiles + hlbvh::kTile - 1) / hlbvh::kTile) + 1;
+        HIP_TRY(scratch.alloc((4 * (size_t)max_cnt + hist_words + sums_words) * sizeof(uint32_t), st));
+        k_a = reinterpret_cast<uint32_t *>(scratch.p); k_b = k_a + max_cnt; v_a = k_b + max_cnt; v_b = v_a + max_cnt;
+        hist = v_b + max_cnt; sums = hist + hist_words;
+        return GNXR_OK;
+    }
+    const uint32_t *sort(const DScene &sc, const float4 *queries, int m, hipStream_t st) {
+        const int n_tiles = (m + hlbvh::kTile - 1) / hlbvh::kTile;
+        hipLaunchKernelGGL(k_closest_keys, dim3(grid_for(m)), dim3(kBlock), 0, st, sc.nodes, queries, m, k_a, v_a);
+        uint32_t *kin = k_a, *kout = k_b, *vin = v_a, *vout = v_b;
+        for (int pass = 0; pass < 3; ++pass) {   // 18 bits, 6 per pass, least significant first
+            hipLaunchKernelGGL(hlbvh::k_rs_hist, dim3(n_tiles), dim3(hlbvh::kB), 0, st, (const uint32_t *)kin, m, 6 * pass, n_tiles, hist);
+            hl_scan(hist, 64 * n_tiles, sums, nullptr, st);
+            hipLaunchKernelGGL(hlbvh::k_rs_scatter, dim3(n_tiles), dim3(hlbvh::kB), 0, st, (const uint32_t *)kin, (const uint32_t *)vin, m, 6 * pass, n_tiles, (const uint32_t *)hist, kout, vout);
+            std::swap(kin, kout); std::swap(vin, vout);
+        }
+        return vin;
+    }
+};
+
 // The walk over n queries on `st`.  d_counts: nullptr, or two device words the counting instantiation adds nodes visited and triangles
-// tested to.  From Knobs::closest_bin_min() queries on they are binned by Morton key first (closest_kernel.hip.h), a chunk at a time;
+// tested to.  From Knobs::closest_bin_min() queries on they are binned by Morton key first (QueryBinning), a chunk at a time;
 // below, one launch walks them in caller order (queries are indexed in 64 bits, a thread's spill column by its number in the grid).
 static int closest_launch(gnxr_scene *r, const DScene &sc, const gnxr_point_query *d_queries, int64_t n, struct gnxr_closest_point *d_out, unsigned long long *d_counts, hipStream_t st) {
     if (r->cs.n_triangles == 0) {
@@ -20,35 +51,14 @@ static int closest_launch(gnxr_scene *r, const DScene &sc, const gnxr_point_quer
     const long long most = std::min<long long>(n, per_launch);   // queries of one launch
     WalkLaunch w;
     if (int rc = w.plan(r, sizeof(uint2), Knobs::closest_lds_levels(), most, st)) return rc;
-    // the sort's arrays: keys and indices twice, the per-tile digit histograms and the scan's tile sums
-    StreamScratch sort_scratch;
-    const int max_cnt = (int)most;
-    const int max_tiles = (max_cnt + hlbvh::kTile - 1) / hlbvh::kTile;
-    const size_t hist_words = (size_t)64 * max_tiles, sums_words = (size_t)std::max(max_tiles, (64 * max_tiles + hlbvh::kTile - 1) / hlbvh::kTile) + 1;
-    uint32_t *k_a = nullptr, *k_b = nullptr, *v_a = nullptr, *v_b = nullptr, *hist = nullptr, *sums = nullptr;
-    if (binned) {
-        HIP_TRY(sort_scratch.alloc((4 * (size_t)max_cnt + hist_words + sums_words) * sizeof(uint32_t), st));
-        k_a = reinterpret_cast<uint32_t *>(sort_scratch.p); k_b = k_a + max_cnt; v_a = k_b + max_cnt; v_b = v_a + max_cnt;
-        hist = v_b + max_cnt; sums = hist + hist_words;
-    }
+    QueryBinning bins;
+    if (binned) { if (int rc = bins.reserve(most, st)) return rc; }
     for (long long base = 0; base < n; base += per_launch) {
         const long long cnt = std::min<long long>(n - base, per_launch);
         ClosestArrays qa;
         qa.queries = reinterpret_cast<const float4 *>(d_queries + base);
         qa.out = reinterpret_cast<float4 *>(d_out + base);
-        const uint32_t *order = nullptr;
-        if (binned) {
-            const int m = (int)cnt, n_tiles = (m + hlbvh::kTile - 1) / hlbvh::kTile;
-            hipLaunchKernelGGL(k_closest_keys, dim3(grid_for(m)), dim3(kBlock), 0, st, sc.nodes, qa.queries, m, k_a, v_a);
-            uint32_t *kin = k_a, *kout = k_b, *vin = v_a, *vout = v_b;
-            for (int pass = 0; pass < 3; ++pass) {   // 18 bits, 6 per pass, least significant first
-                hipLaunchKernelGGL(hlbvh::k_rs_hist, dim3(n_tiles), dim3(hlbvh::kB), 0, st, (const uint32_t *)kin, m, 6 * pass, n_tiles, hist);
-                hl_scan(hist, 64 * n_tiles, sums, nullptr, st);
-                hipLaunchKernelGGL(hlbvh::k_rs_scatter, dim3(n_tiles), dim3(hlbvh::kB), 0, st, (const uint32_t *)kin, (const uint32_t *)vin, m, 6 * pass, n_tiles, (const uint32_t *)hist, kout, vout);
-                std::swap(kin, kout); std::swap(vin, vout);
-            }
-            order = vin;
-        }
+        const uint32_t *order = binned ? bins.sort(sc, qa.queries, (int)cnt, st) : nullptr;
 #define GX_CLOSEST(W, C) hipLaunchKernelGGL((k_closest_point<W, C>), dim3(w.grid(cnt)), dim3(kBlock), w.lds, st, sc, qa, order, (long long)cnt, w.lds_entries, w.entries, \
                                             (uint2 *)w.spill, d_counts)
         if (d_counts) { if (w.wide) GX_CLOSEST(true, true); else GX_CLOSEST(false, true); }

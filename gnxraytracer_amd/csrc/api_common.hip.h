@@ -125,6 +125,10 @@ struct Knobs {
     // GNXR_ALLHITS_LDS_LEVELS: most levels of an all-hits walk's stack kept in LDS, 1 .. 32 (default 16; small values let tests reach the
     // global spill on shallow trees).  Per call (launch)
     static int allhits_lds_levels() { return std::max(1, std::min(32, env_int("GNXR_ALLHITS_LDS_LEVELS", 16))); }
+    // GNXR_NEAR_LDS_LEVELS: most levels of a neighbour walk's stack kept in LDS, 1 .. 24 (default 16: with the 8-byte entries of the
+    // NEAREST mode a block's stack is 32 KB, five blocks fill a CU's LDS; small values let tests reach the global spill on shallow
+    // trees).  Per call (launch)
+    static int near_lds_levels() { return std::max(1, std::min(24, env_int("GNXR_NEAR_LDS_LEVELS", 16))); }
 };
 
 int ensure_device() {

@@ -1459,6 +1459,65 @@ int gnxr_trace_all_counted_device(gnxr_scene *scene, const gnxr_ray *d_rays, int
                                   int32_t *d_counts, uint64_t *d_work, void *hip_stream);
 int gnxr_trace_all(gnxr_scene *scene, const gnxr_ray *rays, int64_t n, int32_t max_hits, gnxr_ray_hit *hits, int32_t *counts);
 
+/* -- Neighbour queries: the triangles within a radius of a point, and the K nearest ------------------------------------------
+ * gnxr_closest_point_device answers with the one nearest triangle.  This call answers with everything near a point: the contact
+ * manifold against a mesh that has just been refitted, the k nearest faces for attribute transfer or a blended distance field, the
+ * candidate set of a particle within its own radius.  The walk goes through the scene's live 4-wide tree (the binary tree for scenes
+ * that are off it; same results), so after gnxr_scene_update_vertices[_ex], gnxr_scene_rebuild_bvh and gnxr_scene_set_geometry the
+ * answer is for the geometry the scene holds now.  Spheres of the scene are NOT considered: triangles only.
+ *
+ * The result is defined triangle by triangle, so it does not depend on the tree, the split method, the binning of the queries, or on
+ * K beyond the cut.  For a query (p, max_distance) and every triangle in authoring order:
+ *   1. dist2 and the record (prim, dist2, p, b1, b2, feature) are exactly those of "Closest-point queries" above: the same region walk,
+ *      the same clamp into the triangle's own bounds, the same single rounded fp32 operations, the same 32-byte gnxr_closest_point.
+ *   2. r2 = max_distance * max_distance, one fp32 product.  The triangle is NEAR iff dist2 <= r2; a NaN dist2 (a zero-area triangle
+ *      that reaches step 7) fails.
+ *   3. The query is valid under the closest-point rule: a NaN coordinate, a NaN max_distance or max_distance < 0 gives no neighbours.
+ *      max_distance = +inf is allowed; in the GNXR_NEAR_ALL mode every triangle with a dist2 that is not NaN is then near.
+ *   4. The list of the query is its near triangles in ascending (dist2, prim): dist2 compared as a float, bit-equal dist2 ordered by
+ *      the smaller authoring index, so coincident triangles are both kept.  The list is cut to its first max_near = K entries.
+ *   5. Output: the records d_out[i * K + j], j < min(near triangles, K), in that order; the slots behind them are EMPTY: prim = -1,
+ *      dist2 = +inf and every other field 0, so the whole output is defined and comparable on bytes.  (gnxr_closest_point's record
+ *      without a winner has dist2 = 0; an empty slot here has +inf, so that a row of dist2 is ascending through its empty slots.)
+ * A brute force over all triangles that follows this text (tests/near_reference.py) reproduces records and counts byte for byte.
+ *
+ * Two modes share the flag word; any other bit is refused.
+ *   GNXR_NEAR_ALL (0)      d_counts[i] = the number of ALL near triangles, never clamped to K.  K in [0, GNXR_NEAR_MAX]; K == 0 is the
+ *                          count-only form (d_out must be NULL).  The walk drops a box iff its distance bd2 > r2, a fixed bound, so its
+ *                          cost follows the radius, not K.
+ *   GNXR_NEAR_NEAREST (1)  the list is the same, byte for byte, as GNXR_NEAR_ALL gives for the same query and K; d_counts[i] = the
+ *                          number of slots filled, min(count of GNXR_NEAR_ALL, K).  K in [1, GNXR_NEAR_MAX].  Once the list is full the
+ *                          bound becomes the K-th key: a box is dropped iff bd2 > the K-th dist2, and a box with bd2 == the K-th dist2
+ *                          is entered, because a smaller authoring index may tie.  bd2 is a lower bound in fp32 of the dist2 of every
+ *                          triangle under the box and the K-th key only shrinks, so nothing that belongs to the first K is dropped
+ *                          (DESIGN.md); no epsilon anywhere.  With K == 1 the one record equals gnxr_closest_point's wherever that has
+ *                          a winner.
+ * A scene without triangles gives counts of 0 and empty slots.
+ *
+ * gnxr_near_device: the conventions of gnxr_closest_point_device and gnxr_trace_all_device -- every array is device memory of one
+ * device that holds a copy of the scene, d_queries and d_out 16-byte aligned, d_counts 4-byte aligned; the work is queued on hip_stream
+ * (NULL: the null stream) after what the caller queued there, nothing is copied back and nothing waits for the GPU; scratch comes from
+ * the stream-ordered allocator on that stream -- the walk's stack beyond its LDS levels (sized by the scene and the grid, never by n)
+ * and, from 65536 queries on, the arrays of the radix sort that bins the queries by a coarse Morton key of p before the walk, the one
+ * of gnxr_closest_point_device (at most 96 MB whatever n is; the order of the work changes, no result does); n == 0 is a no-op;
+ * GNXR_ERR_INVALID with a message, before anything is queued and with the scene untouched, for a null scene, a null pointer with
+ * n > 0, n < 0, max_near out of range for the mode, d_out set with max_near == 0 or missing with max_near > 0, unknown flag bits, a
+ * misaligned pointer, host pointers, pointers on a device without a copy of the scene or on different devices, or an array that runs
+ * past its allocation.  While a query is walked its row of d_out is the walk's own working list; it holds the result when the call's
+ * work on the stream is done.  gnxr_near_counted_device is the same call through the counting instantiation of the kernel
+ * (measurements only: slower): it ADDS the nodes visited and the triangles tested by the call to d_work[0], d_work[1] (device memory,
+ * 8-byte aligned, the caller's to clear).  gnxr_near takes host arrays: copy in, the same walk, copy out; it returns when the arrays
+ * are written.  The calls add no struct: the records are gnxr_point_query and gnxr_closest_point. */
+#define GNXR_NEAR_MAX 32
+#define GNXR_NEAR_ALL 0u
+#define GNXR_NEAR_NEAREST 1u
+int gnxr_near_device(gnxr_scene *scene, const gnxr_point_query *d_queries, int64_t n, int32_t max_near, uint32_t flags,
+                     struct gnxr_closest_point *d_out, int32_t *d_counts, void *hip_stream);
+int gnxr_near_counted_device(gnxr_scene *scene, const gnxr_point_query *d_queries, int64_t n, int32_t max_near, uint32_t flags,
+                             struct gnxr_closest_point *d_out, int32_t *d_counts, uint64_t *d_work, void *hip_stream);
+int gnxr_near(gnxr_scene *scene, const gnxr_point_query *queries, int64_t n, int32_t max_near, uint32_t flags,
+              struct gnxr_closest_point *out, int32_t *counts);
+
 /* -- Shading queries on device memory: the pieces an integrator is made of, batched -------------------------------------
  * Same conventions as the device calls of the Aggregate seam: every array is device memory of one device that holds a copy of the
  * scene, the work is queued on hip_stream (NULL: the null stream) after what the caller queued there, scratch comes from the
