@@ -1158,6 +1158,70 @@ class Scene:
                                records.ctypes.data_as(C.POINTER(_abi.ClosestPoint)) if max_near > 0 else None, counts.ctypes.data_as(C.POINTER(C.c_int32))))
         return records, counts
 
+    # sphere casts (gnxr_sphere_cast_device / gnxr_sphere_cast)
+    def _sphere_casts(self, origins, directions, radius, tmax, stream):
+        """The (n, 8) float32 gnxr_sphere_cast records of sphere_cast: `origins` as ready-made records, or (n, 3) origins and
+        directions with `radius` a number or an (n,) tensor and `tmax` None, a number or an (n,) tensor, packed on `stream`."""
+        import torch
+        if _is_tensor(origins, torch.float32, (None, 8)):
+            if directions is not None or radius is not None or tmax is not None:
+                raise ValueError("sphere_cast: (n, 8) origins are ready-made cast records; directions, radius and tmax must be None")
+            return origins
+        if not _is_tensor(origins, torch.float32, (None, 3), self.device):
+            _refuse(origins, f"sphere_cast: origins: expected a contiguous torch.float32 (n, 3) or (n, 8) tensor on cuda:{self.device}")
+        _expect("sphere_cast: directions", directions, torch.float32, (3,), origins.device)
+        _same_count("sphere_cast", "directions", directions.shape[0], origins.shape[0], "origins")
+        for what, x, may_be_none in (("radius", radius, False), ("tmax", tmax, True)):
+            if isinstance(x, torch.Tensor):
+                _expect(f"sphere_cast: {what}", x, torch.float32, (), origins.device)
+                _same_count("sphere_cast", what, x.shape[0], origins.shape[0], "origins")
+            elif not (x is None and may_be_none) and (isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating))):
+                raise TypeError(f"sphere_cast: {what} must be {'None, ' if may_be_none else ''}a number or a float32 (n,) tensor, got {type(x).__name__}")
+        with torch.cuda.stream(_stream_pair(stream, origins.device)[1]):
+            casts = torch.empty((origins.shape[0], 8), dtype=torch.float32, device=origins.device)
+            casts[:, 0:3] = origins
+            casts[:, 3] = radius
+            casts[:, 4:7] = directions
+            casts[:, 7] = float("inf") if tmax is None else tmax
+        return casts
+
+    def sphere_cast(self, origins, directions, radius, tmax=None, out=None, **launch):
+        """The first impact of moving balls against the mesh, for casts already on the GPU (gnxr_sphere_cast_device; the definition,
+        operation by operation: include/gnxr.h, "Sphere casts").  Ball i has its centre at origins[i] + t directions[i] for t in
+        [0, tmax[i]] -- `directions` is not normalised, t is in its units -- and radius[i].  `origins`, `directions`: contiguous float32
+        (n, 3) tensors on the scene's device; `radius`: a number for all casts or a float32 (n,) tensor; `tmax`: None (unbounded), a
+        number or a float32 (n,) tensor.  Or `origins` is a float32 (n, 8) tensor of ready-made gnxr_sphere_cast records (o.xyz,
+        radius, d.xyz, tmax) and the other three are None.  Returns SphereCasts: the (n, 8) float32 records (`out` when given) and
+        named views of them -- `prim` (-1: no hit), `t`, and `p`, `b1`, `b2`, `feature`, closest_point's answer for the winning
+        triangle at the centre of the time of impact; the contact normal is (origins + t directions - p) / radius.  The walk reads
+        the scene's live tree (after update_vertices, rebuild_bvh, set_geometry and SkinnedMesh.pose it answers for the geometry the
+        scene holds now); spheres are not considered.  Keywords of the launch, which travel as keywords for the reason given in
+        closest_point's docstring: `stream=` (None: torch's current stream; a torch.cuda.Stream or a hipStream_t as an int; the work
+        is queued there and nothing waits) and, for measurements, `counts=`: an int64 (2,) tensor on the same device that the call
+        adds nodes visited and triangles tested to, through the kernel's slower counting form.  (The refusals are exercised in
+        tests/test_sphere_cast.py.)"""
+        import torch
+        _only_kw("sphere_cast", launch, ("stream", "counts"))
+        stream, counts = launch.get("stream"), launch.get("counts")
+        casts = self._sphere_casts(origins, directions, radius, tmax, stream)
+        n, out, st, _ = self._query_args("sphere_cast", [("origins", casts, torch.float32, 8)], out, 8, stream)
+        if counts is None:
+            _check(lib().gnxr_sphere_cast_device(self._h, _ptr(casts), n, _ptr(out), _addr(st)))
+        else:
+            if not _is_tensor(counts, torch.int64, (2,), casts.device):
+                _refuse(counts, f"sphere_cast: counts must be a contiguous torch.int64 (2,) tensor on {casts.device}")
+            _check(lib().gnxr_sphere_cast_counted_device(self._h, _ptr(casts), n, _ptr(out), _ptr(counts), _addr(st)))
+        ints = out.view(torch.int32)
+        return SphereCasts(out, ints[:, 0], out[:, 1], out[:, 2:5], out[:, 5], out[:, 6], ints[:, 7])
+
+    def SphereCast(self, casts):
+        """sphere_cast for numpy arrays (gnxr_sphere_cast): `casts` is (n, 8) float32 -- o.xyz, radius, d.xyz, tmax (np.inf:
+        unbounded).  Returns a structured array of CLOSEST_DTYPE whose `dist2` field holds t."""
+        casts = np.ascontiguousarray(casts, dtype=np.float32).reshape(-1, 8)
+        res = np.zeros(len(casts), dtype=CLOSEST_DTYPE)
+        _check(lib().gnxr_sphere_cast(self._h, casts.ctypes.data_as(C.POINTER(_abi.SphereCast)), len(casts), res.ctypes.data_as(C.POINTER(_abi.ClosestPoint))))
+        return res
+
     MOTION_CHANNELS = ("motion", "guide", "prim")
 
     def motion(self, width, height, prev_cameras, cameras=None, prev_vertices=None, out=None, stream=None):
@@ -1225,6 +1289,11 @@ NearLists.__doc__ = """Scene.within's and Scene.nearest's result: `count`, int32
 nearest: the slots filled --, `records`, the (n, K, 8) float32 gnxr_closest_point records -- per query the first min(count, K) near
 triangles in ascending (dist2, prim), then empty slots (prim -1, dist2 +inf, the rest 0) --, and views of it: `prim` (n, K) (int32:
 authoring-order triangle), `dist2` (n, K), `p` (n, K, 3), `b1`, `b2` (n, K) and `feature` (n, K) (int32, as in ClosestPoints)."""
+
+SphereCasts = collections.namedtuple("SphereCasts", "records prim t p b1 b2 feature")
+SphereCasts.__doc__ = """Scene.sphere_cast's result: `records`, the (n, 8) float32 gnxr_closest_point records with t in the dist2 slot, and views of
+it -- `prim` (int32: the authoring-order triangle the ball touches first, -1 without a hit), `t` (the time of impact in units of the
+direction, +inf without a hit), `p` (n, 3), `b1`, `b2` and `feature` (int32, as in ClosestPoints): the contact point on that triangle."""
 
 ALL_HITS_MAX = 32   # GNXR_ALL_HITS_MAX
 NEAR_MAX = 32   # GNXR_NEAR_MAX

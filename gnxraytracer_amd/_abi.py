@@ -125,6 +125,10 @@ class RayHit(C.Structure):   # gnxr_ray_hit (no struct_size; not in gnxr_abi_siz
     _fields_ = [("t", f32), ("prim", i32), ("b1", f32), ("b2", f32)]
 
 
+class SphereCast(C.Structure):   # gnxr_sphere_cast (no struct_size; not in gnxr_abi_sizeof's list)
+    _fields_ = [("o", f32 * 3), ("radius", f32), ("d", f32 * 3), ("tmax", f32)]
+
+
 class LiSample(C.Structure):
     _fields_ = [("px", i32), ("py", i32), ("s", i32), ("medium", i32)]
 
@@ -280,6 +284,9 @@ PROTOTYPES = {
     "gnxr_near_device": (C.c_int, [VP, VP, i64, i32, u32, VP, VP, VP]),   # queries, n, max_near, flags, records, counts: device addresses + hipStream_t
     "gnxr_near_counted_device": (C.c_int, [VP, VP, i64, i32, u32, VP, VP, VP, VP]),   # ..., two uint64 on the device, hipStream_t
     "gnxr_near": (C.c_int, [VP, P(PointQuery), i64, i32, u32, P(ClosestPoint), P(i32)]),
+    "gnxr_sphere_cast_device": (C.c_int, [VP, VP, i64, VP, VP]),   # casts, n, records: device addresses + hipStream_t
+    "gnxr_sphere_cast_counted_device": (C.c_int, [VP, VP, i64, VP, VP, VP]),   # ..., two uint64 on the device, hipStream_t
+    "gnxr_sphere_cast": (C.c_int, [VP, P(SphereCast), i64, P(ClosestPoint)]),
     "gnxr_li_device": (C.c_int, [VP, P(RenderParams), VP, VP, i64, VP, VP, P(Stats)]),   # device addresses + hipStream_t
     "gnxr_render_views_device": (C.c_int, [VP, P(RenderParams), P(Camera), P(i32), i32, VP, VP, P(Stats)]),   # cameras, media: host; images: device
     "gnxr_render_aov_device": (C.c_int, [VP, P(RenderParams), P(Camera), P(i32), i32, P(AovBuffers), VP, P(Stats)]),   # cameras, media: host; buffers: device

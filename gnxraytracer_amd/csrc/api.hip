@@ -2,7 +2,7 @@
 // points and the host-memory probes (gnxr_scene_create compiles into a local CompiledScene, uploads it and leaves the handle its facts:
 // host_scene.h); the rest lives in the api_*.hip.h headers included below (shared pieces, gnxr_scene, the HLBVH build
 // driver, the peak probes, the front end of the calls on device memory, the render path, the editing calls, the in-place BVH rebuild, the
-// light list's replacement, the environment light's rebuild, the media edit, the texture edit, the entry points on device memory, adaptive sampling, the denoiser, the film, lightmap baking, mesh deformation, closest-point queries, all-hits ray queries, neighbour queries).  One process drives one GPU (gnxr_init), or several behind every handle (gnxr_init_devices).
+// light list's replacement, the environment light's rebuild, the media edit, the texture edit, the entry points on device memory, adaptive sampling, the denoiser, the film, lightmap baking, mesh deformation, closest-point queries, all-hits ray queries, neighbour queries, sphere casts).  One process drives one GPU (gnxr_init), or several behind every handle (gnxr_init_devices).
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -41,6 +41,7 @@
 #include "closest_kernel.hip.h"
 #include "allhits_kernel.hip.h"
 #include "near_kernel.hip.h"
+#include "spherecast_kernel.hip.h"
 #include "kernel_instances.h"
 
 using namespace gnxr;
@@ -330,6 +331,7 @@ int gnxr_trace_any(gnxr_scene *s, const gnxr_ray *rays, int64_t n, uint8_t *occl
 #include "api_closest.hip.h"
 #include "api_allhits.hip.h"
 #include "api_near.hip.h"
+#include "api_spherecast.hip.h"
 #include "api_aov.hip.h"
 #include "api_adaptive.hip.h"
 #include "api_denoise.hip.h"

@@ -1,4 +1,4 @@
-// api_walk.hip.h -- the launch plan of a per-lane query walk (bvh_walk.hip.h), for closest_launch, all_hits_launch and near_launch.  Part of api.hip's
+// api_walk.hip.h -- the launch plan of a per-lane query walk (bvh_walk.hip.h), for closest_launch, all_hits_launch, near_launch and sphere_cast_launch.  Part of api.hip's
 // translation unit.
 #pragma once
 

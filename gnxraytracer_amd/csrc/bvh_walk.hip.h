@@ -1,4 +1,4 @@
-// bvh_walk.hip.h -- the mechanics the per-lane query walks share (k_closest_point, k_all_hits, k_near): the stack, the node decode and the
+// bvh_walk.hip.h -- the mechanics the per-lane query walks share (k_closest_point, k_all_hits, k_near, k_sphere_cast): the stack, the node decode and the
 // children of an interior node with their boxes.  Nothing here decides a result: what a kernel does with a box, in which order it visits
 // and what it tests at a leaf is that kernel's own.  DESIGN.md, "The walk the queries share", has the bound of the stack and why.
 #pragma once

@@ -1518,6 +1518,73 @@ int gnxr_near_counted_device(gnxr_scene *scene, const gnxr_point_query *d_querie
 int gnxr_near(gnxr_scene *scene, const gnxr_point_query *queries, int64_t n, int32_t max_near, uint32_t flags,
               struct gnxr_closest_point *out, int32_t *counts);
 
+/* -- Sphere casts: the first impact of a moving ball ---------------------------------------------------------------------
+ * The swept query beside the ray, overlap and closest-point calls: a ball of radius r whose centre is o + t d for t in [0, tmax]; when
+ * does it first touch the mesh, and on which triangle.  A particle with a radius, the end caps of a character capsule, a camera boom, a
+ * probe that must keep clearance.  (A ray along the centre line misses what the ball's rim touches first; stepping
+ * gnxr_closest_point_device along the path tunnels through thin geometry and costs a launch per step.)  The walk goes through the
+ * scene's live 4-wide tree (the binary tree for scenes that are off it; same results), so after gnxr_scene_update_vertices[_ex],
+ * gnxr_scene_rebuild_bvh and gnxr_scene_set_geometry the answer is for the geometry the scene holds now.  Spheres of the scene are NOT
+ * considered: triangles only.  d is not normalised and t is in units of d; tmax = +inf: unbounded; radius = 0 is allowed (nothing
+ * promises that it equals gnxr_trace_closest_device).
+ *
+ * The result is defined triangle by triangle, so it does not depend on the tree.  The conventions are those of "Closest-point queries":
+ * every arithmetic step is ONE rounded fp32 operation (nothing is contracted, divisions and square roots are correctly rounded),
+ * dot(u, v) = (u.x v.x + u.y v.y) + u.z v.z, min(x, y) = (y < x ? y : x), max(x, y) = (y > x ? y : x), a product of a scalar and a
+ * vector is rounded per component before a sum, closest(q) is that section's steps 1-7 with the clamp, giving (dist2, p, b1, b2,
+ * feature).  A restatement in fp32 that follows the text reproduces the records bit for bit (tests/spherecast_reference.py).
+ *
+ * Per cast (o, r, d, tmax):
+ *   0. The cast is INVALID -- no triangle hits -- if o, d, r or tmax holds a NaN, r < 0 or tmax < 0; a cast with an infinite component
+ *      of o or d hits nothing either.  r = +inf and tmax = +inf are allowed.  r2 = r r, dd = dot(d, d), inv = 1 / d per axis.  An axis
+ *      whose inv is not finite (d is zero or so small that 1 / d overflows) is STATIC, the others MOVE.
+ * Per triangle (a, b, c), in authoring order:
+ *   1. The grown-box test.  lo = min(min(a, b), c), hi = max(max(a, b), c) per axis; glo = lo - r, ghi = hi + r.  A static axis k
+ *      passes iff glo_k <= o_k <= ghi_k, and gives no time.  A moving axis k has near_k = (inv_k < 0 ? ghi_k : glo_k), far_k the
+ *      other one, entry_k = (near_k - o_k) inv_k, exit_k = (far_k - o_k) inv_k.  tb = max over {0, entry_k of the moving axes},
+ *      tx = min over {+inf, exit_k of the moving axes}.  The test passes iff every static axis passes, tb <= tx and tb <= tmax.
+ *      (tx is not widened: step 3 makes that unnecessary.  With o and d finite no operand is a NaN and inv is never 0, so
+ *      0 * inf does not occur; a static axis is never multiplied.)
+ *   2. The analytic time ta, the smallest of the following; a candidate t counts iff 0 <= t < +inf (a NaN fails).
+ *      start     closest(o).dist2 <= r2: ta = 0 (the ball starts in contact), and nothing else is looked at.
+ *      face      ab = b - a, ac = c - a, n = (ab.y ac.z - ab.z ac.y, ab.z ac.x - ab.x ac.z, ab.x ac.y - ab.y ac.x), nn = dot(n, n).
+ *                Only if nn > 0 (a degenerate triangle has no face term): len = sqrt(nn), sd = dot(n, o - a), dn = dot(n, d),
+ *                h = r len, tf = ((sd < 0 ? -h : h) - sd) / dn -- the plane offset by r towards o.  tf counts iff
+ *                closest(o + tf d).feature == 0.
+ *      edges     (p0, p1) = (a, b), (a, c), (b, c): e = p1 - p0, m = o - p0, me = dot(m, e), de = dot(d, e), ee = dot(e, e),
+ *                md = dot(m, d), mm = dot(m, m); A = ee dd - de de, C = ee (mm - r2) - me me, B = ee md - de me, disc = B B - A C.
+ *                Only if A > 0 and disc >= 0: t = (-B - sqrt(disc)) / A, w = me + t de; t counts iff 0 <= w <= ee (the axial
+ *                parameter w / ee within [0, 1]).
+ *      vertices  v = a, b, c: m = o - v, bq = dot(m, d), cq = dot(m, m) - r2, disc = bq bq - dd cq.  Only if dd > 0 and disc >= 0:
+ *                t = (-bq - sqrt(disc)) / dd.
+ *      Only entering roots are taken: a ball that starts inside a cylinder or a sphere and is not in contact at t = 0 meets the
+ *      triangle through another term first.  Ties between the terms need no rule (the record comes from closest()).
+ *   3. t = max(tb, ta) = (ta > tb ? ta : tb).  The triangle HITS iff step 1 passed, ta exists (ta < +inf) and t <= tmax.
+ * The winner is the triangle of least t and, among bit-equal t, of smallest authoring index.  Step 3 is what lets a walk through any
+ * tree prune with no epsilon: tb of every box that encloses the triangle's own box is <= tb of the own box <= t in fp32.
+ *
+ * The answer is a gnxr_closest_point record with the dist2 slot holding t: prim = the winner's authoring index, dist2 = t, and
+ * (p, b1, b2, feature) = closest(o + t d) of the winner -- the contact point; the contact normal is (o + t d - p) / r.  Without a hit,
+ * and for an invalid cast: prim = -1, t = +inf, every other field 0.
+ *
+ * gnxr_sphere_cast_device: the conventions of gnxr_closest_point_device -- d_casts and d_out are device memory of one device that
+ * holds a copy of the scene, both 16-byte aligned; the work is queued on hip_stream (NULL: the null stream) after what the caller
+ * queued there, nothing is copied back and nothing waits for the GPU; scratch (the walk's stack beyond its LDS levels, sized by the
+ * scene and the grid, never by n) comes from the stream-ordered allocator on that stream; casts are walked in caller order (no
+ * binning); n == 0 is a no-op; GNXR_ERR_INVALID before anything is queued for a null scene, a null pointer with n > 0, n < 0, host
+ * pointers, pointers on a device without a copy of the scene or on different devices, an array that runs past its allocation, or a
+ * misaligned pointer.  gnxr_sphere_cast_counted_device is the same call through the counting instantiation of the kernel
+ * (measurements only: slower): it ADDS the nodes visited and the triangles taken to step 2 by the call to d_work[0], d_work[1]
+ * (device memory, 8-byte aligned, the caller's to clear).  gnxr_sphere_cast takes host arrays: copy in, the same walk, copy out; it
+ * returns when `out` is written.  The record carries no struct_size and is not part of gnxr_abi_sizeof's list. */
+/* (the record shares its name with the host entry point, so it is a struct tag without a typedef: write `struct gnxr_sphere_cast`) */
+struct gnxr_sphere_cast { float o[3]; float radius; float d[3]; float tmax; };   /* 32 bytes, 16-byte aligned on the device */
+int gnxr_sphere_cast_device(gnxr_scene *scene, const struct gnxr_sphere_cast *d_casts, int64_t n, struct gnxr_closest_point *d_out,
+                            void *hip_stream);
+int gnxr_sphere_cast_counted_device(gnxr_scene *scene, const struct gnxr_sphere_cast *d_casts, int64_t n,
+                                    struct gnxr_closest_point *d_out, uint64_t *d_work, void *hip_stream);
+int gnxr_sphere_cast(gnxr_scene *scene, const struct gnxr_sphere_cast *casts, int64_t n, struct gnxr_closest_point *out);
+
 /* -- Shading queries on device memory: the pieces an integrator is made of, batched -------------------------------------
  * Same conventions as the device calls of the Aggregate seam: every array is device memory of one device that holds a copy of the
  * scene, the work is queued on hip_stream (NULL: the null stream) after what the caller queued there, scratch comes from the
