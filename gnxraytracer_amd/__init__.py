@@ -57,6 +57,27 @@ def _check(rc):
     return rc
 
 
+def _walk_call(name, plain, counted, args, counts, n_counts, device, st):
+    """The tail of the per-lane walk queries (closest_point, all_hits, within / nearest, sphere_cast): `plain(*args, stream)`, or, with
+    `counts=` given -- it must be an int64 (n_counts,) tensor on `device` --, `counted(*args, counts, stream)`."""
+    import torch
+    if counts is None:
+        return _check(plain(*args, _addr(st)))
+    if not _is_tensor(counts, torch.int64, (n_counts,), device):
+        _refuse(counts, f"{name}: counts must be a contiguous torch.int64 ({n_counts},) tensor on {device}")
+    return _check(counted(*args, _ptr(counts), _addr(st)))
+
+
+def _list_length(name, what, k, lowest, highest):
+    """K of a query that keeps a list per record (`what`: its name in the messages): an integer in [lowest, highest]"""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise TypeError(f"{name}: {what} must be an integer, got {type(k).__name__}")
+    k = int(k)
+    if not lowest <= k <= highest:
+        raise ValueError(f"{name}: {what} must be in [{lowest}, {highest}], got {k}")
+    return k
+
+
 def _f3(v):
     return (C.c_float * 3)(*[float(x) for x in v])
 
@@ -977,12 +998,8 @@ class Scene:
         stream, counts = launch.get("stream"), launch.get("counts")
         queries = self._point_queries("closest_point", points, max_distance, stream)
         n, out, st, _ = self._query_args("closest_point", [("points", queries, torch.float32, 4)], out, 8, stream)
-        if counts is None:
-            _check(lib().gnxr_closest_point_device(self._h, _ptr(queries), n, _ptr(out), _addr(st)))
-        else:
-            if not _is_tensor(counts, torch.int64, (2,), queries.device):
-                _refuse(counts, f"closest_point: counts must be a contiguous torch.int64 (2,) tensor on {queries.device}")
-            _check(lib().gnxr_closest_point_counted_device(self._h, _ptr(queries), n, _ptr(out), _ptr(counts), _addr(st)))
+        _walk_call("closest_point", lib().gnxr_closest_point_device, lib().gnxr_closest_point_counted_device,
+                   (self._h, _ptr(queries), n, _ptr(out)), counts, 2, queries.device, st)
         return ClosestPoints(out, out.view(torch.int32)[:, 0], out[:, 1], out[:, 2:5], out[:, 5:7], out.view(torch.int32)[:, 7])
 
     def ClosestPoint(self, queries):
@@ -999,22 +1016,14 @@ class Scene:
         import torch
         _only_kw(name, launch, ("stream", "counts"))
         stream, work = launch.get("stream"), launch.get("counts")
-        if isinstance(max_hits, bool) or not isinstance(max_hits, (int, np.integer)):
-            raise TypeError(f"{name}: max_hits must be an integer, got {type(max_hits).__name__}")
-        max_hits = int(max_hits)
-        if not 0 <= max_hits <= ALL_HITS_MAX:
-            raise ValueError(f"{name}: max_hits must be in [0, {ALL_HITS_MAX}], got {max_hits}")
+        max_hits = _list_length(name, "max_hits", max_hits, 0, ALL_HITS_MAX)
         _expect(f"{name}: rays", rays, torch.float32, (8,), self.device)
         n = rays.shape[0]
         st, _, out, counts_out = _outputs(stream, rays.device, (f"{name}: out", out, (n, max_hits, 4), torch.float32),
                                           (f"{name}: counts_out", counts_out, (n,), torch.int32))
         hits = _ptr(out) if max_hits else None
-        if work is None:
-            _check(lib().gnxr_trace_all_device(self._h, _ptr(rays), n, max_hits, hits, _ptr(counts_out), _addr(st)))
-        else:
-            if not _is_tensor(work, torch.int64, (3,), rays.device):
-                _refuse(work, f"{name}: counts must be a contiguous torch.int64 (3,) tensor on {rays.device}")
-            _check(lib().gnxr_trace_all_counted_device(self._h, _ptr(rays), n, max_hits, hits, _ptr(counts_out), _ptr(work), _addr(st)))
+        _walk_call(name, lib().gnxr_trace_all_device, lib().gnxr_trace_all_counted_device,
+                   (self._h, _ptr(rays), n, max_hits, hits, _ptr(counts_out)), work, 3, rays.device, st)
         return RayHitLists(out, out[:, :, 0], out.view(torch.int32)[:, :, 1], out[:, :, 2:4], counts_out)
 
     def all_hits(self, rays, max_hits, out=None, counts_out=None, **launch):
@@ -1070,7 +1079,7 @@ class Scene:
     def signed_distance(self, points, direction=None, **launch):
         """The distance from points already on the GPU to the scene's triangle mesh, negative inside: float32 (n,),
         sqrt(closest_point(points).dist2), negated where contains(points, direction) -- it equals that chain of public calls on bits.
-        +inf where closest_point has no winner (a scene without triangles).  The limits are those of contains: a closed mesh, and
+        +inf where closest_point has no winner (an invalid point: a NaN coordinate).  The limits are those of contains: a closed mesh, and
         rays that cross an edge exactly.  `stream=`: as for all_hits."""
         import torch
         _only_kw("signed_distance", launch, ("stream",))
@@ -1098,24 +1107,15 @@ class Scene:
         import torch
         _only_kw(name, launch, ("stream", "counts"))
         stream, work = launch.get("stream"), launch.get("counts")
-        what = "k" if flags else "max_near"
-        if isinstance(max_near, bool) or not isinstance(max_near, (int, np.integer)):
-            raise TypeError(f"{name}: {what} must be an integer, got {type(max_near).__name__}")
-        max_near = int(max_near)
-        if not lowest <= max_near <= NEAR_MAX:
-            raise ValueError(f"{name}: {what} must be in [{lowest}, {NEAR_MAX}], got {max_near}")
+        max_near = _list_length(name, "k" if flags else "max_near", max_near, lowest, NEAR_MAX)
         queries = self._point_queries(name, points, radius, stream, radius_name)
         _expect(f"{name}: points", queries, torch.float32, (4,), self.device)
         n = queries.shape[0]
         st, _, out, counts_out = _outputs(stream, queries.device, (f"{name}: out", out, (n, max_near, 8), torch.float32),
                                           (f"{name}: counts_out", counts_out, (n,), torch.int32))
         records = _ptr(out) if max_near else None
-        if work is None:
-            _check(lib().gnxr_near_device(self._h, _ptr(queries), n, max_near, flags, records, _ptr(counts_out), _addr(st)))
-        else:
-            if not _is_tensor(work, torch.int64, (2,), queries.device):
-                _refuse(work, f"{name}: counts must be a contiguous torch.int64 (2,) tensor on {queries.device}")
-            _check(lib().gnxr_near_counted_device(self._h, _ptr(queries), n, max_near, flags, records, _ptr(counts_out), _ptr(work), _addr(st)))
+        _walk_call(name, lib().gnxr_near_device, lib().gnxr_near_counted_device,
+                   (self._h, _ptr(queries), n, max_near, flags, records, _ptr(counts_out)), work, 2, queries.device, st)
         ints = out.view(torch.int32)
         return NearLists(counts_out, out, ints[:, :, 0], out[:, :, 1], out[:, :, 2:5], out[:, :, 5], out[:, :, 6], ints[:, :, 7])
 
@@ -1205,12 +1205,8 @@ class Scene:
         stream, counts = launch.get("stream"), launch.get("counts")
         casts = self._sphere_casts(origins, directions, radius, tmax, stream)
         n, out, st, _ = self._query_args("sphere_cast", [("origins", casts, torch.float32, 8)], out, 8, stream)
-        if counts is None:
-            _check(lib().gnxr_sphere_cast_device(self._h, _ptr(casts), n, _ptr(out), _addr(st)))
-        else:
-            if not _is_tensor(counts, torch.int64, (2,), casts.device):
-                _refuse(counts, f"sphere_cast: counts must be a contiguous torch.int64 (2,) tensor on {casts.device}")
-            _check(lib().gnxr_sphere_cast_counted_device(self._h, _ptr(casts), n, _ptr(out), _ptr(counts), _addr(st)))
+        _walk_call("sphere_cast", lib().gnxr_sphere_cast_device, lib().gnxr_sphere_cast_counted_device,
+                   (self._h, _ptr(casts), n, _ptr(out)), counts, 2, casts.device, st)
         ints = out.view(torch.int32)
         return SphereCasts(out, ints[:, 0], out[:, 1], out[:, 2:5], out[:, 5], out[:, 6], ints[:, 7])
 

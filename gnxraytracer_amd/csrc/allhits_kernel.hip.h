@@ -14,7 +14,8 @@
 //                       sequence implies (an entry of +inf or an exit of -inf always rejects) and is monotone in the box as well.
 // The order of visits does not matter: at a node the first accepted child is entered and the others are pushed as 4-byte references.
 //
-// The stack (4-byte entries), the node decode and the children's boxes are bvh_walk.hip.h's.
+// The stack (4-byte entries), the node decode and the children's boxes are bvh_walk.hip.h's; the step that enters every accepted child
+// is its walk_enter_all, written out here.
 //
 // The list (LIST): the lane's own output row hits[i K .. i K + K) IS the list -- a lane re-reads only what it wrote itself --, kept sorted
 // by insertion; the number held and the K-th key stay in registers, so a hit that does not beat a full list costs one comparison and no
@@ -133,6 +134,7 @@ static __global__ void __launch_bounds__(kBlock) k_all_hits(DScene sc, AllHitsAr
                         c[s] = ref;
                         e[s] = !(WIDE && ref == kNode4Empty) && ah_enter(ray, lox, loy, loz, hix, hiy, hiz);
                     });
+                    // walk_enter_all's ladder, written out: through the helper this kernel timed outside the parent's spread
                     if (WIDE) {
                         if (e[3]) { if (e[0] || e[1] || e[2]) stack.put(sp, c[3]); else next = c[3]; }
                         if (e[2]) { if (e[0] || e[1]) stack.put(sp, c[2]); else next = c[2]; }
@@ -140,7 +142,7 @@ static __global__ void __launch_bounds__(kBlock) k_all_hits(DScene sc, AllHitsAr
                     if (e[1]) { if (e[0]) stack.put(sp, c[1]); else next = c[1]; }
                     if (e[0]) next = c[0];
                 }
-                if (next == kNode4Empty) {
+                if (next == kNode4Empty) {   // nothing shrinks, so every deferred child is walked: no walk_pop and its test
                     if (sp == 0) break;
                     next = stack.get(--sp);
                 }
@@ -155,14 +157,6 @@ static __global__ void __launch_bounds__(kBlock) k_all_hits(DScene sc, AllHitsAr
         atomicAdd(&work[0], cntNodes);
         atomicAdd(&work[1], cntBoxes);
         atomicAdd(&work[2], cntTris);
-    }
-}
-
-// a scene without triangles: counts of 0 and empty slots
-static __global__ void __launch_bounds__(kBlock) k_all_hits_none(float4 *hits, int *counts, long long n, int K) {
-    for (long long i = blockIdx.x * (long long)kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock) {
-        counts[i] = 0;
-        for (int j = 0; j < K; ++j) hits[i * (long long)K + j] = make_float4(GX_INF, __int_as_float(-1), 0.f, 0.f);
     }
 }
 

@@ -10,7 +10,7 @@
 // every box encloses those, and subtraction, squaring and addition round monotonically), so `bd2 > best` never drops the winner and
 // `bd2 == best` is entered because a smaller authoring index may tie.  No epsilon anywhere.
 //
-// The stack (8-byte entries), the node decode and the children's boxes are bvh_walk.hip.h's.
+// The stack (8-byte entries), the node decode, the children's boxes, the sort with its keys and the pop are bvh_walk.hip.h's.
 //
 // Queries arrive in caller order, and neighbouring lanes that walk to different corners of the tree share neither node loads nor control
 // flow.  From kClosestBinMin queries on, the call therefore bins them first: an 18-bit Morton key of p over the root's box (64 cells per
@@ -109,15 +109,6 @@ GX_DEV void closest_leaf(const DTri *__restrict__ tris, int first, int n, V3 q, 
     }
 }
 
-// keys of the child sort: the bits of a non-negative float order as the float does (a NaN, which only a box with a NaN bound gives, sorts
-// behind +inf and is still entered); an absent or dropped child sorts last
-constexpr unsigned kClosestDropped = 0xffffffffu;
-template <bool WIDE>
-GX_DEV unsigned cp_key(int ref, float bd2, float best_d2) { return ((WIDE && ref == kNode4Empty) || bd2 > best_d2) ? kClosestDropped : __float_as_uint(bd2); }
-GX_DEV void cp_sort2(unsigned &ka, int &ra, unsigned &kb, int &rb) {
-    if (kb < ka) { const unsigned k = ka; ka = kb; kb = k; const int r = ra; ra = rb; rb = r; }
-}
-
 // WIDE: the 4-wide tree from sc.root4; else the binary tree from node 0.  COUNT: nodes visited and triangles tested of the whole launch are
 // added to counts[0], counts[1] (the measurement's instantiation; never the timed path).  A stack entry is (child reference, key).
 template <bool WIDE, bool COUNT>
@@ -145,29 +136,14 @@ static __global__ void __launch_bounds__(kBlock) k_closest_point(DScene sc, Clos
                     if (COUNT) cntTris += (unsigned)node.count;
                     closest_leaf(sc.tris, node.first, node.count, q, &best);
                 } else {
-                    int r[4]; float b[4];   // slots 2 and 3 exist on the 4-wide tree only
+                    int r[4]; unsigned k[4];   // slots 2 and 3 exist on the 4-wide tree only
                     walk_children<WIDE>(sc, cur, node.first, [&](int s, int ref, float lox, float loy, float loz, float hix, float hiy, float hiz) __attribute__((always_inline)) {
                         r[s] = ref;
-                        b[s] = box_dist2(lox, loy, loz, hix, hiy, hiz, q);
+                        k[s] = walk_key<WIDE>(ref, box_dist2(lox, loy, loz, hix, hiy, hiz, q), best.d2);
                     });
-                    int r0 = r[0], r1 = r[1];   // scalars for the sort: on the arrays' elements hipcc builds the exchanges from selects, 6 VGPRs more
-                    unsigned k0 = cp_key<WIDE>(r0, b[0], best.d2), k1 = cp_key<WIDE>(r1, b[1], best.d2);
-                    if (WIDE) {
-                        int r2 = r[2], r3 = r[3];
-                        unsigned k2 = cp_key<WIDE>(r2, b[2], best.d2), k3 = cp_key<WIDE>(r3, b[3], best.d2);
-                        cp_sort2(k0, r0, k1, r1); cp_sort2(k2, r2, k3, r3); cp_sort2(k0, r0, k2, r2); cp_sort2(k1, r1, k3, r3); cp_sort2(k1, r1, k2, r2);
-                        if (k3 != kClosestDropped) stack.put(sp, make_uint2((unsigned)r3, k3));
-                        if (k2 != kClosestDropped) stack.put(sp, make_uint2((unsigned)r2, k2));
-                    } else {
-                        cp_sort2(k0, r0, k1, r1);
-                    }
-                    if (k1 != kClosestDropped) stack.put(sp, make_uint2((unsigned)r1, k1));
-                    if (k0 != kClosestDropped) next = r0;
+                    next = walk_enter_nearest<WIDE>(r, k, [&](int ref, unsigned key) __attribute__((always_inline)) { stack.put_child(sp, ref, key); });
                 }
-                while (next == kNode4Empty && sp > 0) {
-                    const uint2 e = stack.get(--sp);
-                    if (!(__uint_as_float(e.y) > best.d2)) next = (int)e.x;   // the best may have shrunk since the push
-                }
+                next = walk_pop(stack, sp, next, [&](uint2 e) __attribute__((always_inline)) { return walk_within(e, best.d2); });   // the best may have shrunk since the push
                 if (next == kNode4Empty) break;
                 cur = next;
             }
@@ -202,14 +178,6 @@ static __global__ void __launch_bounds__(kBlock) k_closest_keys(const float4 *__
         const uint32_t cz = (uint32_t)fminf(fmaxf((q.z - n0.z) / (n1.y - n0.z) * 64.f, 0.f), 63.f);
         keys[i] = (hlbvh::left_shift3(cz) << 2) | (hlbvh::left_shift3(cy) << 1) | hlbvh::left_shift3(cx);
         vals[i] = (uint32_t)i;
-    }
-}
-
-// prim = -1 and zeros everywhere: a scene without triangles
-static __global__ void __launch_bounds__(kBlock) k_closest_none(float4 *out, long long n) {
-    for (long long i = blockIdx.x * (long long)kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock) {
-        out[2 * i] = make_float4(__int_as_float(-1), 0.f, 0.f, 0.f);
-        out[2 * i + 1] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
 }
 

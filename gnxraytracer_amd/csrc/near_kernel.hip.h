@@ -7,10 +7,10 @@
 // closest_on_triangle's and a box's bd2 is box_dist2's (closest_kernel.hip.h: called, not copied), so bd2 is a lower bound IN FP32 of the
 // dist2 of every triangle under the box.
 //   ALL      a box is dropped iff bd2 > r2, a fixed bound; the order of visits does not matter: the first child that stays is entered and
-//            the others are pushed as 4-byte references, as in k_all_hits.  count = every near triangle, never clamped to K.
+//            the others are pushed as 4-byte references (walk_enter_all, as in k_all_hits).  count = every near triangle, never clamped to K.
 //   NEAREST  the bound is r2 until the list is full and the K-th key's dist2 from then on, which only shrinks; children are sorted by bd2
-//            and walked nearest-first with (reference, bd2) stack entries, and a popped entry is tested against the bound again, as in
-//            k_closest_point.  A box with bd2 == the K-th dist2 is entered: a smaller authoring index may tie.  count = slots filled.
+//            and walked nearest-first with (reference, bd2) stack entries, and a popped entry is tested against the bound again
+//            (walk_enter_nearest and walk_pop, as in k_closest_point).  A box with bd2 == the K-th dist2 is entered: a smaller authoring index may tie.  count = slots filled.
 // No epsilon anywhere.
 //
 // The list (LIST): the lane's own output row out[i K .. i K + K) IS the list -- a lane re-reads only what it wrote itself --, kept sorted
@@ -64,12 +64,6 @@ GX_DEV void near_empty_slot(float4 *slot) {
 // a stack entry: NEAREST (child reference, bd2 bits), ALL the child reference alone
 template <bool NEAREST> struct NearEntry { typedef int type; };
 template <> struct NearEntry<true> { typedef uint2 type; };
-GX_DEV void near_put(WalkStack<uint2> &stack, int &sp, int ref, unsigned key) { stack.put(sp, make_uint2((unsigned)ref, key)); }
-GX_DEV void near_put(WalkStack<int> &stack, int &sp, int ref, unsigned) { stack.put(sp, ref); }
-GX_DEV bool near_still_in(uint2 e, float bound) { return !(__uint_as_float(e.y) > bound); }
-GX_DEV bool near_still_in(int, float) { return true; }
-GX_DEV int near_ref(uint2 e) { return (int)e.x; }
-GX_DEV int near_ref(int e) { return e; }
 
 // WIDE: the 4-wide tree from sc.root4; else the binary tree from node 0.  NEAREST: the mode (it implies LIST).  LIST: K > 0 (else the
 // count alone; no list memory is touched).  COUNT: nodes visited and triangles tested of the whole launch are added to work[0], work[1]
@@ -113,43 +107,16 @@ static __global__ void __launch_bounds__(kBlock) k_near(DScene sc, NearArrays qa
                     }
                 } else {
                     const float bound = NEAREST ? list.kd : r2;   // kd is r2 until the list is full
-                    int r[4]; float b[4];   // slots 2 and 3 exist on the 4-wide tree only
+                    int r[4]; unsigned k[4]; bool e[4];   // slots 2 and 3 exist on the 4-wide tree only
                     walk_children<WIDE>(sc, cur, node.first, [&](int s, int ref, float lox, float loy, float loz, float hix, float hiy, float hiz) __attribute__((always_inline)) {
                         r[s] = ref;
-                        b[s] = box_dist2(lox, loy, loz, hix, hiy, hiz, q);
+                        k[s] = walk_key<WIDE>(ref, box_dist2(lox, loy, loz, hix, hiy, hiz, q), bound);
+                        e[s] = k[s] != kWalkDropped;
                     });
-                    if (NEAREST) {
-                        int c0 = r[0], c1 = r[1];   // scalars for the sort, as in k_closest_point
-                        unsigned k0 = cp_key<WIDE>(c0, b[0], bound), k1 = cp_key<WIDE>(c1, b[1], bound);
-                        if (WIDE) {
-                            int c2 = r[2], c3 = r[3];
-                            unsigned k2 = cp_key<WIDE>(c2, b[2], bound), k3 = cp_key<WIDE>(c3, b[3], bound);
-                            cp_sort2(k0, c0, k1, c1); cp_sort2(k2, c2, k3, c3); cp_sort2(k0, c0, k2, c2); cp_sort2(k1, c1, k3, c3); cp_sort2(k1, c1, k2, c2);
-                            if (k3 != kClosestDropped) near_put(stack, sp, c3, k3);
-                            if (k2 != kClosestDropped) near_put(stack, sp, c2, k2);
-                        } else {
-                            cp_sort2(k0, c0, k1, c1);
-                        }
-                        if (k1 != kClosestDropped) near_put(stack, sp, c1, k1);
-                        if (k0 != kClosestDropped) next = c0;
-                    } else {
-                        bool e[4];
-                        e[0] = cp_key<WIDE>(r[0], b[0], bound) != kClosestDropped;
-                        e[1] = cp_key<WIDE>(r[1], b[1], bound) != kClosestDropped;
-                        if (WIDE) {
-                            e[2] = cp_key<WIDE>(r[2], b[2], bound) != kClosestDropped;
-                            e[3] = cp_key<WIDE>(r[3], b[3], bound) != kClosestDropped;
-                            if (e[3]) { if (e[0] || e[1] || e[2]) near_put(stack, sp, r[3], 0u); else next = r[3]; }
-                            if (e[2]) { if (e[0] || e[1]) near_put(stack, sp, r[2], 0u); else next = r[2]; }
-                        }
-                        if (e[1]) { if (e[0]) near_put(stack, sp, r[1], 0u); else next = r[1]; }
-                        if (e[0]) next = r[0];
-                    }
+                    if (NEAREST) next = walk_enter_nearest<WIDE>(r, k, [&](int ref, unsigned key) __attribute__((always_inline)) { stack.put_child(sp, ref, key); });
+                    else next = walk_enter_all<WIDE>(r, e, [&](int ref) __attribute__((always_inline)) { stack.put_child(sp, ref, 0u); });
                 }
-                while (next == kNode4Empty && sp > 0) {
-                    const Entry e = stack.get(--sp);
-                    if (near_still_in(e, list.kd)) next = near_ref(e);   // NEAREST: the K-th key may have shrunk since the push
-                }
+                next = walk_pop(stack, sp, next, [&](Entry e) __attribute__((always_inline)) { return walk_within(e, list.kd); });   // NEAREST: the K-th key may have shrunk since the push
                 if (next == kNode4Empty) break;
                 cur = next;
             }
@@ -171,14 +138,6 @@ static __global__ void __launch_bounds__(kBlock) k_near(DScene sc, NearArrays qa
     if (COUNT) {
         atomicAdd(&work[0], cntNodes);
         atomicAdd(&work[1], cntTris);
-    }
-}
-
-// a scene without triangles: counts of 0 and empty slots
-static __global__ void __launch_bounds__(kBlock) k_near_none(float4 *out, int *counts, long long n, int K) {
-    for (long long i = blockIdx.x * (long long)kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock) {
-        counts[i] = 0;
-        for (int j = 0; j < K; ++j) near_empty_slot(out + 2 * (i * (long long)K + j));
     }
 }
 

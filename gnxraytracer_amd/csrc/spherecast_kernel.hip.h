@@ -10,8 +10,8 @@
 // by a fixed 1 / d round monotonically), `tb > best` never drops the winner and `tb == best` is entered because a smaller authoring index
 // may tie.  No epsilon anywhere.
 //
-// The stack (8-byte entries), the node decode and the children's boxes are bvh_walk.hip.h's; closest_on_triangle, the child sort and
-// its keys are closest_kernel.hip.h's (tb >= 0, so its bits order as the float does).  Casts run in caller order: QueryBinning takes
+// The stack (8-byte entries), the node decode, the children's boxes, the child sort with its keys (tb >= 0, so its bits order as the
+// float does) and the pop are bvh_walk.hip.h's; closest_on_triangle is closest_kernel.hip.h's.  Casts run in caller order: QueryBinning takes
 // 16-byte records.
 #pragma once
 #include "closest_kernel.hip.h"
@@ -174,26 +174,11 @@ static __global__ void __launch_bounds__(kBlock) k_sphere_cast(DScene sc, Sphere
                         float tb;
                         const bool in = sc_box(s, lox, loy, loz, hix, hiy, hiz, best.t, &tb);
                         r[slot] = ref;
-                        k[slot] = in ? cp_key<WIDE>(ref, tb, best.t) : kClosestDropped;
+                        k[slot] = in ? walk_key<WIDE>(ref, tb, best.t) : kWalkDropped;
                     });
-                    int r0 = r[0], r1 = r[1];   // scalars for the sort, as in k_closest_point
-                    unsigned k0 = k[0], k1 = k[1];
-                    if (WIDE) {
-                        int r2 = r[2], r3 = r[3];
-                        unsigned k2 = k[2], k3 = k[3];
-                        cp_sort2(k0, r0, k1, r1); cp_sort2(k2, r2, k3, r3); cp_sort2(k0, r0, k2, r2); cp_sort2(k1, r1, k3, r3); cp_sort2(k1, r1, k2, r2);
-                        if (k3 != kClosestDropped) stack.put(sp, make_uint2((unsigned)r3, k3));
-                        if (k2 != kClosestDropped) stack.put(sp, make_uint2((unsigned)r2, k2));
-                    } else {
-                        cp_sort2(k0, r0, k1, r1);
-                    }
-                    if (k1 != kClosestDropped) stack.put(sp, make_uint2((unsigned)r1, k1));
-                    if (k0 != kClosestDropped) next = r0;
+                    next = walk_enter_nearest<WIDE>(r, k, [&](int ref, unsigned key) __attribute__((always_inline)) { stack.put_child(sp, ref, key); });
                 }
-                while (next == kNode4Empty && sp > 0) {
-                    const uint2 e = stack.get(--sp);
-                    if (!(__uint_as_float(e.y) > best.t)) next = (int)e.x;   // the best may have shrunk since the push
-                }
+                next = walk_pop(stack, sp, next, [&](uint2 e) __attribute__((always_inline)) { return walk_within(e, best.t); });   // the best may have shrunk since the push
                 if (next == kNode4Empty) break;
                 cur = next;
             }
@@ -213,14 +198,6 @@ static __global__ void __launch_bounds__(kBlock) k_sphere_cast(DScene sc, Sphere
     if (COUNT) {
         atomicAdd(&work[0], cntNodes);
         atomicAdd(&work[1], cntTris);
-    }
-}
-
-// prim = -1, t = +inf and zeros: a scene without triangles
-static __global__ void __launch_bounds__(kBlock) k_sphere_cast_none(float4 *out, long long n) {
-    for (long long i = blockIdx.x * (long long)kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock) {
-        out[2 * i] = make_float4(__int_as_float(-1), GX_INF, 0.f, 0.f);
-        out[2 * i + 1] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
 }
 

@@ -13,7 +13,7 @@ import torch
 import allhits_reference as ar
 import scenes
 from conftest import ROOT
-from test_closest_point import binary_depth, chain_scene, concentric_mesh, dragon, mesh_of, mesh_scene
+from query_cases import binary_depth, chain_scene, concentric_mesh, dragon, mesh_of, mesh_scene
 
 ERR_INVALID = -1
 F = np.float32

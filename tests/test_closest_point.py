@@ -10,29 +10,15 @@ import torch
 
 import closest_reference as cr
 import scenes
-from conftest import GOLDEN
+from query_cases import (assert_same, binary_depth, bound_of, chain_scene, concentric_mesh, dragon, mesh_of, mesh_scene, order, queries_of,  # noqa: F401
+                         surface_samples, uniform_in)
 
 ERR_INVALID = -1
-MESH2K = os.path.join(GOLDEN, "mesh_2k.3d")
 F = np.float32
 INF = F(np.inf)
 
 
 # ---------------------------------------------------------------- helpers
-def mesh_of(b):
-    """(vertices, indices) of a builder in authoring order, copied"""
-    d = b.desc()
-    return (np.ctypeslib.as_array(d.vertices, shape=(d.n_vertices, 3)).astype(F, copy=True),
-            np.ctypeslib.as_array(d.indices, shape=(d.n_triangles, 3)).astype(np.int32, copy=True))
-
-
-def queries_of(points, max_distance=np.inf):
-    q = np.zeros((len(points), 4), F)
-    q[:, 0:3] = points
-    q[:, 3] = max_distance
-    return q
-
-
 def device_records(scene, queries, **kw):
     res = scene.closest_point(torch.from_numpy(np.array(queries, F)).cuda(), **kw)
     torch.cuda.synchronize()
@@ -41,59 +27,6 @@ def device_records(scene, queries, **kw):
 
 def same_bytes(x, y):
     return x.dtype.itemsize == y.dtype.itemsize and len(x) == len(y) and x.tobytes() == y.tobytes()
-
-
-def assert_same(got, want):
-    if not same_bytes(got, want):
-        bad = np.flatnonzero((got.view(np.uint8).reshape(len(got), -1) != want.view(np.uint8).reshape(len(want), -1)).any(axis=1))
-        raise AssertionError(f"{len(bad)} of {len(want)} records differ; first {bad[0]}: got {got[bad[0]]}, want {want[bad[0]]}")
-
-
-def bound_of(v):
-    return v.min(axis=0), v.max(axis=0)
-
-
-def uniform_in(lo, hi, n, rng, scale=1.0):
-    c, h = 0.5 * (lo + hi), 0.5 * (hi - lo) * scale
-    return rng.uniform(c - h, c + h, (n, 3)).astype(F)
-
-
-def surface_samples(v, idx, n, rng, jitter):
-    t = idx[rng.integers(0, len(idx), n)]
-    u = rng.uniform(0, 1, (n, 2))
-    flip = u.sum(axis=1) > 1
-    u[flip] = 1 - u[flip]
-    p = v[t[:, 0]] + u[:, 0:1] * (v[t[:, 1]] - v[t[:, 0]]) + u[:, 1:2] * (v[t[:, 2]] - v[t[:, 0]])
-    return (p + rng.uniform(-jitter, jitter, (n, 3))).astype(F)
-
-
-def chain_scene(gx, n=36):
-    """tests/test_ray_queries_device.py's chain, restated: n small triangles facing +x at x = 2^-k on the x axis.  The middle split peels
-    one off per level, so the binary tree is a chain n - 1 deep."""
-    v, idx = [], []
-    for k in range(n):
-        x, s = 2.0 ** -k, 0.3 * 2.0 ** -k
-        v += [(x, -s, -s), (x, s, -s), (x, 0.0, 2 * s)]
-        idx.append((3 * k, 3 * k + 1, 3 * k + 2))
-    b = gx.SceneBuilder()
-    b.add_mesh(np.array(v, F), np.array(idx, np.int32), b.MatteMaterial(scenes.WHITE, 60.0))
-    b.set_bvh_split_method("middle")
-    return b
-
-
-def dragon(split=None):
-    b = scenes.dragon_cornell(2000, "glass+metal", mesh_path=MESH2K)
-    if split:
-        b.set_bvh_split_method(split)
-    return b
-
-
-def mesh_scene(gx, v, idx, split=None):
-    b = gx.SceneBuilder()
-    b.add_mesh(np.ascontiguousarray(v, F), np.ascontiguousarray(idx, np.int32), b.MatteMaterial(scenes.WHITE, 60.0))
-    if split:
-        b.set_bvh_split_method(split)
-    return b
 
 
 _dragon_cache = {}
@@ -238,14 +171,6 @@ def test_python_refuses_other_inputs_before_the_library(gx):
 
 
 # ---------------------------------------------------------------- GPU
-@pytest.fixture(params=["caller_order", "binned"])
-def order(request):
-    """Both ways a call takes its queries to the walk: in caller order (batches below 65536 queries) and binned by Morton key first, which
-    GNXR_CLOSEST_BIN_MIN=1 asks of every batch.  The records must not notice."""
-    if request.param == "binned":
-        os.environ["GNXR_CLOSEST_BIN_MIN"] = "1"
-    yield request.param
-    os.environ.pop("GNXR_CLOSEST_BIN_MIN", None)
 
 
 def cornell_points(v, idx):
@@ -365,19 +290,6 @@ def test_deep_tree(gpu, order):
         del os.environ["GNXR_CLOSEST_LDS_LEVELS"]
 
 
-def binary_depth(scene):
-    """the depth of the flattened binary tree (the root at 0), walked through scene.bvh(): an interior node's children are the next node
-    and the node at its offset"""
-    _, meta, _ = scene.bvh()
-    depth, todo = 0, [(0, 0)]
-    while todo:
-        i, d = todo.pop()
-        depth = max(depth, d)
-        if meta[i, 1] == 0:
-            todo += [(i + 1, d + 1), (int(meta[i, 0]), d + 1)]
-    return depth
-
-
 @pytest.mark.gpu
 def test_deep_binary_tree_spills(gpu, order):
     """test_deep_tree's chain and points on a scene kept on the binary tree by the creation switch, with 2 LDS levels: the binary walk,
@@ -394,18 +306,6 @@ def test_deep_binary_tree_spills(gpu, order):
         assert_same(device_records(scene, q), want)
     finally:
         del os.environ["GNXR_CLOSEST_LDS_LEVELS"]
-
-
-def concentric_mesh(rng):
-    """130 nested triangles whose bounds share one centre (no split separates them: one leaf over 127 primitives) and 50 others"""
-    v, idx = [], []
-    for k in range(130):
-        s = 0.5 + 0.01 * k
-        v += [(-s, -s, -s), (s, -s, s), (-s, s, s)]
-    for k in range(50):
-        c = rng.uniform(-4, 4, 3)
-        v += [tuple(c + rng.uniform(-0.3, 0.3, 3)) for _ in range(3)]
-    return np.array(v, F), np.arange(3 * 180, dtype=np.int32).reshape(-1, 3)
 
 
 @pytest.mark.gpu

@@ -12,79 +12,23 @@ import torch
 import closest_reference as cr
 import near_reference as nr
 import scenes
-from conftest import GOLDEN, ROOT
+from conftest import ROOT
+from query_cases import (FAN_D, assert_same, bound_of, chain_scene, concentric_mesh, dragon, fan_mesh, mesh_of, mesh_scene, order, queries_of,  # noqa: F401
+                         sliver_mesh, surface_samples, uniform_in)
 
 ERR_INVALID = -1
-MESH2K = os.path.join(GOLDEN, "mesh_2k.3d")
 F = np.float32
 INF = F(np.inf)
 EMPTY = nr.empty_slots(1)[0]
 
 
 # ---------------------------------------------------------------- helpers
-def mesh_of(b):
-    """(vertices, indices) of a builder in authoring order, copied"""
-    d = b.desc()
-    return (np.ctypeslib.as_array(d.vertices, shape=(d.n_vertices, 3)).astype(F, copy=True),
-            np.ctypeslib.as_array(d.indices, shape=(d.n_triangles, 3)).astype(np.int32, copy=True))
-
-
-def queries_of(points, max_distance=np.inf):
-    q = np.zeros((len(points), 4), F)
-    q[:, 0:3] = points
-    q[:, 3] = max_distance
-    return q
-
-
-def mesh_scene(gx, v, idx, split=None):
-    b = gx.SceneBuilder()
-    b.add_mesh(np.ascontiguousarray(v, F), np.ascontiguousarray(idx, np.int32), b.MatteMaterial(scenes.WHITE, 60.0))
-    if split:
-        b.set_bvh_split_method(split)
-    return b
-
-
-def dragon(split=None):
-    b = scenes.dragon_cornell(2000, "glass+metal", mesh_path=MESH2K)
-    if split:
-        b.set_bvh_split_method(split)
-    return b
-
-
-def bound_of(v):
-    return v.min(axis=0), v.max(axis=0)
-
-
-def uniform_in(lo, hi, n, rng, scale=1.0):
-    c, h = 0.5 * (lo + hi), 0.5 * (hi - lo) * scale
-    return rng.uniform(c - h, c + h, (n, 3)).astype(F)
-
-
-def surface_samples(v, idx, n, rng, jitter):
-    t = idx[rng.integers(0, len(idx), n)]
-    u = rng.uniform(0, 1, (n, 2))
-    flip = u.sum(axis=1) > 1
-    u[flip] = 1 - u[flip]
-    p = v[t[:, 0]] + u[:, 0:1] * (v[t[:, 1]] - v[t[:, 0]]) + u[:, 1:2] * (v[t[:, 2]] - v[t[:, 0]])
-    return (p + rng.uniform(-jitter, jitter, (n, 3))).astype(F)
-
-
 def device_lists(scene, queries, K, nearest, **kw):
     """(records (n, K) of nr.RECORD, counts) of one device call on ready-made (n, 4) records"""
     q = torch.from_numpy(np.array(queries, F)).cuda()
     res = scene.nearest(q, K, **kw) if nearest else scene.within(q, None, K, **kw)
     torch.cuda.synchronize()
     return res.records.cpu().numpy().view(nr.RECORD).reshape(len(q), K), res.count.cpu().numpy()
-
-
-def assert_same(got, want, what=""):
-    """bytes of two arrays of records or counts"""
-    got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
-    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.dtype, got.shape, want.dtype, want.shape)
-    if got.tobytes() != want.tobytes():
-        g, w = got.reshape(-1), want.reshape(-1)
-        bad = np.flatnonzero((g.view(np.uint8).reshape(len(g), -1) != w.view(np.uint8).reshape(len(w), -1)).any(axis=1))
-        raise AssertionError(f"{what}: {len(bad)} of {len(w)} entries differ; first {bad[0]}: got {g[bad[0]]}, want {w[bad[0]]}")
 
 
 def check_both_modes(scene, v, idx, q, Ks, want=None):
@@ -98,66 +42,6 @@ def check_both_modes(scene, v, idx, q, Ks, want=None):
             got, cnt = device_lists(scene, q, K, True)
             assert_same(cnt, count_nearest, f"NEAREST K={K} counts")
             assert_same(got, rec, f"NEAREST K={K}")
-
-
-def chain_scene(gx, n=36):
-    """n small triangles facing +x at x = 2^-k on the x axis.  The middle split peels one off per level: a binary tree n - 1 deep."""
-    v, idx = [], []
-    for k in range(n):
-        x, s = 2.0 ** -k, 0.3 * 2.0 ** -k
-        v += [(x, -s, -s), (x, s, -s), (x, 0.0, 2 * s)]
-        idx.append((3 * k, 3 * k + 1, 3 * k + 2))
-    b = gx.SceneBuilder()
-    b.add_mesh(np.array(v, F), np.array(idx, np.int32), b.MatteMaterial(scenes.WHITE, 60.0))
-    b.set_bvh_split_method("middle")
-    return b
-
-
-def concentric_mesh(rng):
-    """130 nested triangles whose bounds share one centre (no split separates them: one leaf over 127 primitives) and 50 others"""
-    v = []
-    for k in range(130):
-        s = 0.5 + 0.01 * k
-        v += [(-s, -s, -s), (s, -s, s), (-s, s, s)]
-    for k in range(50):
-        c = rng.uniform(-4, 4, 3)
-        v += [tuple(c + rng.uniform(-0.3, 0.3, 3)) for _ in range(3)]
-    return np.array(v, F), np.arange(3 * 180, dtype=np.int32).reshape(-1, 3)
-
-
-def sliver_mesh(rng, n=240):
-    """long thin triangles through one region: every box overlaps most others, so leaves are large and boxes say little"""
-    a = rng.uniform(-2, 2, (n, 3))
-    d = rng.normal(0, 1, (n, 3))
-    d /= np.linalg.norm(d, axis=1, keepdims=True)
-    v = np.stack([a - 3 * d, a + 3 * d, a + 3 * d + rng.normal(0, 1e-3, (n, 3))], axis=1).reshape(-1, 3)
-    return v.astype(F), np.arange(3 * n, dtype=np.int32).reshape(-1, 3)
-
-
-FAN_D = 1.5   # the query's height over the apex: dist2 = 2.25 and max_distance = 1.5 gives r2 = 2.25 exactly
-
-
-def fan_mesh(rng, copies=1, others=0):
-    """12 triangles around the apex (0, 0, 0), a cone that opens towards -z, in shuffled authoring order with randomly rotated corner
-    order; `copies` of the fan (coincident triangles); `others` small triangles at least 2 FAN_D from the query (0, 0, FAN_D), shuffled
-    in between.  Returns (v, idx, the fan's authoring indices ascending)."""
-    ang = 2 * np.pi * np.arange(12) / 12
-    ring = np.stack([np.cos(ang), np.sin(ang), np.full(12, -0.75)], axis=1)
-    v = np.concatenate([[(0.0, 0.0, 0.0)], ring])
-    tris = [np.roll((0, 1 + i, 1 + (i + 1) % 12), rng.integers(0, 3)) for i in range(12)] * copies
-    is_fan = [True] * len(tris)
-    for _ in range(others):
-        while True:
-            c = rng.uniform(-9, 9, 3)
-            if np.linalg.norm(c - (0, 0, FAN_D)) >= 2 * FAN_D + 0.5:
-                break
-        base = len(v)
-        v = np.concatenate([v, c + rng.uniform(-0.25, 0.25, (3, 3))])
-        tris.append(np.array((base, base + 1, base + 2)))
-        is_fan.append(False)
-    perm = rng.permutation(len(tris))
-    idx = np.array([tris[j] for j in perm], np.int32)
-    return v.astype(F), idx, np.flatnonzero(np.array(is_fan)[perm])
 
 
 _dragon_cache = {}
@@ -179,16 +63,6 @@ def dragon_case():
             x.setflags(write=False)
         _dragon_cache.update(v=v, idx=idx, q=q, want=want)
     return _dragon_cache
-
-
-@pytest.fixture(params=["caller_order", "binned"])
-def order(request):
-    """Both ways a call takes its queries to the walk: in caller order (batches below 65536 queries) and binned by Morton key first, which
-    GNXR_CLOSEST_BIN_MIN=1 asks of every batch.  Records and counts must not notice."""
-    if request.param == "binned":
-        os.environ["GNXR_CLOSEST_BIN_MIN"] = "1"
-    yield request.param
-    os.environ.pop("GNXR_CLOSEST_BIN_MIN", None)
 
 
 # ---------------------------------------------------------------- CPU
@@ -574,8 +448,8 @@ def test_degenerate_input(gpu, order):
     on = queries_of(v[idx[:, 0]], 0.0)
     assert (nr.near_lists(v, idx, on, 1)[1] >= 1).all()
     check_both_modes(scene, v, idx, on, (0, 2))
-    # A scene with only a sphere would give counts 0 and empty slots (the restatement's answer without triangles is asserted in
-    # test_restatement_exact_cases), but scene creation refuses a description without triangles, so no such scene exists to ask ...
+    # Every scene has a triangle: scene creation refuses a description without one (the restatement's answer without triangles, counts 0
+    # and empty slots, is asserted in test_restatement_exact_cases; the library has no such path) ...
     b = gpu.SceneBuilder()
     b.AddSphere((0, 0, 0), 1.0, b.MatteMaterial(scenes.WHITE, 60.0))
     b.AddSkyLight()
@@ -664,6 +538,23 @@ def test_one_binned_batch(gpu):
     for res, cnt in zip(binned, (count_all, count_nearest)):
         assert_same(res.records.cpu().numpy().view(nr.RECORD).reshape(len(q_host), 8)[pick], rec)
         assert_same(res.count.cpu().numpy()[pick], cnt)
+
+
+@pytest.mark.gpu
+def test_second_binned_launch(gpu):
+    """2^22 + 257 queries: a binned call walks 2^22 per launch, so the second launch starts at query 2^22 and its rows at 2^22 K.  The
+    queries tile cornell_case's 384 and the expectation tiles their brute force; both stay on the device (the records are 268 MB) and
+    are compared there, on bits."""
+    b, v, idx, q = cornell_case()
+    n, K = (1 << 22) + 257, 2
+    rec, count, _ = nr.near_lists(v, idx, q, K)
+    tile = torch.arange(n, device="cuda") % len(q)
+    want_rec = torch.from_numpy(np.ascontiguousarray(rec).view(np.int32).reshape(len(q), K, 8)).cuda()[tile]
+    want_count = torch.from_numpy(count).cuda()[tile]
+    res = gpu.Scene(b).within(torch.from_numpy(q).cuda()[tile], None, K)
+    torch.cuda.synchronize()
+    assert res.records.shape == (n, K, 8) and torch.equal(res.records.view(torch.int32), want_rec)
+    assert res.count.dtype == torch.int32 and torch.equal(res.count, want_count)
 
 
 @pytest.mark.gpu

@@ -13,8 +13,8 @@ import torch
 import scenes
 import spherecast_reference as sr
 from conftest import ROOT
-from test_near import (assert_same, bound_of, chain_scene, concentric_mesh, dragon, fan_mesh, mesh_of, mesh_scene, sliver_mesh, surface_samples,
-                       uniform_in)
+from query_cases import (assert_same, bound_of, chain_scene, concentric_mesh, dragon, fan_mesh, mesh_of, mesh_scene, sliver_mesh, surface_samples,
+                         uniform_in)
 
 ERR_INVALID = -1
 F = np.float32
@@ -549,8 +549,8 @@ def test_degenerate_input(gpu):
     assert (want["prim"] >= 0).mean() > 0.4
     scene = gpu.Scene(mesh_scene(gpu, v, idx))
     assert_same(device_casts(scene, casts), want)
-    # A scene without triangles would answer prim -1, t +inf (k_sphere_cast_none; the restatement's answer is asserted in
-    # test_restatement_exact_cases), but scene creation refuses a description without triangles, so no such scene exists to ask ...
+    # Every scene has a triangle: scene creation refuses a description without one (the restatement's answer without triangles, prim -1
+    # and t +inf, is asserted in test_restatement_exact_cases; the library has no such path) ...
     b = gpu.SceneBuilder()
     b.AddSphere((0, 0, 0), 1.0, b.MatteMaterial(scenes.WHITE, 60.0))
     b.AddSkyLight()
