@@ -1218,6 +1218,132 @@ class Scene:
         _check(lib().gnxr_sphere_cast(self._h, casts.ctypes.data_as(C.POINTER(_abi.SphereCast)), len(casts), res.ctypes.data_as(C.POINTER(_abi.ClosestPoint))))
         return res
 
+    # box overlap queries (gnxr_overlap_box_device / gnxr_overlap_box)
+    def _box_queries(self, name, lo, hi, stream):
+        """The (n, 8) float32 gnxr_box_query records of the overlap queries: `lo` as ready-made records with `hi` None, or (n, 3) lower
+        and upper corners, packed on `stream` (pad words 0)."""
+        import torch
+        if _is_tensor(lo, torch.float32, (None, 8)):
+            if hi is not None:
+                raise ValueError(f"{name}: (n, 8) lo are ready-made box records; hi must be None")
+            return _expect(f"{name}: lo", lo, torch.float32, (8,), self.device)
+        if not _is_tensor(lo, torch.float32, (None, 3), self.device):
+            _refuse(lo, f"{name}: lo: expected a contiguous torch.float32 (n, 3) or (n, 8) tensor on cuda:{self.device}")
+        _expect(f"{name}: hi", hi, torch.float32, (3,), lo.device)
+        _same_count(name, "hi", hi.shape[0], lo.shape[0], "lo")
+        with torch.cuda.stream(_stream_pair(stream, lo.device)[1]):
+            boxes = torch.zeros((lo.shape[0], 8), dtype=torch.float32, device=lo.device)
+            boxes[:, 0:3] = lo
+            boxes[:, 4:7] = hi
+        return boxes
+
+    def overlap_box(self, lo, hi=None, max_prims=None, out=None, counts_out=None, **launch):
+        """EVERY triangle that touches axis-aligned boxes already on the GPU (gnxr_overlap_box_device; the definition, triangle by
+        triangle: include/gnxr.h, "Overlap queries").  `lo`, `hi`: contiguous float32 (n, 3) tensors on the scene's device, the boxes'
+        lower and upper corners; or `lo` is a float32 (n, 8) tensor of ready-made gnxr_box_query records (lo.xyz, pad, hi.xyz, pad) and
+        `hi` is None.  Touching counts; an inverted box, a NaN or an infinite bound overlaps nothing.
+        With an integer `max_prims` = K in [0, OVERLAP_MAX]: returns OverlapLists -- `count`, int32 (n,) (`counts_out` when given): all
+        overlapping triangles, never clamped to K --, and `prims`, int32 (n, K) (`out` when given): per box the min(count, K) smallest
+        authoring indices among them, ascending, then -1.
+        With `max_prims` None: the complete lists, as OverlapCSR -- `count` as above, `offsets`, int64 (n + 1,), and `prims`, int32
+        (offsets[-1],): box i's triangles are prims[offsets[i]:offsets[i + 1]], ascending.  That is a count-only call, torch.cumsum into
+        the offsets, one allocation of their total -- the one point where the host waits for the stream -- and the call that fills
+        the rows, all on the same stream; `out` must be None.
+        The walk reads the scene's live tree (after update_vertices, rebuild_bvh, set_geometry and SkinnedMesh.pose it answers for the
+        geometry the scene holds now); spheres are not considered.  Keywords of the launch, as for within: `stream=` (None: torch's
+        current stream; a torch.cuda.Stream or a hipStream_t as an int) and, for measurements, `counts=`: an int64 (2,) tensor on the
+        same device that every walk of the call adds nodes visited and triangles tested to, through the kernel's slower counting
+        form.  (Their refusals are exercised in tests/test_overlap_box.py.)"""
+        return self._overlap_box("overlap_box", lo, hi, max_prims, out, counts_out, launch)
+
+    def _overlap_box(self, name, lo, hi, max_prims, out, counts_out, launch):
+        import torch
+        _only_kw(name, launch, ("stream", "counts"))
+        stream, work = launch.get("stream"), launch.get("counts")
+        csr = max_prims is None
+        if csr and out is not None:
+            raise ValueError(f"{name}: with max_prims None the lists are allocated by the call; out must be None")
+        K = 0 if csr else _list_length(name, "max_prims", max_prims, 0, OVERLAP_MAX)
+        boxes = self._box_queries(name, lo, hi, stream)
+        n = boxes.shape[0]
+        st, tstream, out, counts_out = _outputs(stream, boxes.device, (f"{name}: out", out, (n, K), torch.int32), (f"{name}: counts_out", counts_out, (n,), torch.int32))
+        call = lambda k, offsets, prims: _walk_call(name, lib().gnxr_overlap_box_device, lib().gnxr_overlap_box_counted_device,
+                                                    (self._h, _ptr(boxes), n, k, _ptr(offsets), _ptr(prims), _ptr(counts_out)), work, 2, boxes.device, st)
+        call(K, None, out if K else None)
+        if not csr:
+            return OverlapLists(counts_out, out)
+        with torch.cuda.stream(tstream):
+            offsets = torch.zeros(n + 1, dtype=torch.int64, device=boxes.device)
+            torch.cumsum(counts_out, 0, dtype=torch.int64, out=offsets[1:])
+            prims = torch.empty(int(offsets[-1]), dtype=torch.int32, device=boxes.device)
+        if prims.numel():
+            call(-1, offsets, prims)
+        return OverlapCSR(counts_out, offsets, prims)
+
+    def count_in_box(self, lo, hi=None, **launch):
+        """overlap_box with max_prims = 0: the int32 (n,) number of triangles that touch each box, and no list."""
+        return self._overlap_box("count_in_box", lo, hi, 0, None, None, launch).count
+
+    def OverlapBox(self, boxes, max_prims):
+        """overlap_box for numpy arrays (gnxr_overlap_box): `boxes` is (n, 8) float32 -- lo.xyz, pad, hi.xyz, pad.  With an integer
+        `max_prims` it returns (prims, counts): int32 (n, max_prims) and int32 (n,).  With `max_prims` None it returns (prims, counts,
+        offsets): the complete lists as CSR, from a count-only call, numpy's cumsum and the call that fills the rows."""
+        boxes = np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1, 8)
+        n = len(boxes)
+        counts = np.zeros(n, dtype=np.int32)
+        I32, I64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        call = lambda k, offsets, prims: _check(lib().gnxr_overlap_box(self._h, boxes.ctypes.data_as(C.POINTER(_abi.BoxQuery)), n, k,
+                                                                       offsets.ctypes.data_as(I64) if offsets is not None else None,
+                                                                       prims.ctypes.data_as(I32) if prims is not None else None, counts.ctypes.data_as(I32)))
+        if max_prims is not None:
+            max_prims = int(max_prims)
+            prims = np.zeros((n, max(max_prims, 0)), dtype=np.int32)
+            call(max_prims, None, prims if max_prims > 0 else None)
+            return prims, counts
+        call(0, None, None)
+        offsets = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(counts, dtype=np.int64, out=offsets[1:])
+        prims = np.zeros(int(offsets[-1]), dtype=np.int32)
+        if len(prims):
+            call(-1, offsets, prims)
+        return prims, counts, offsets
+
+    def voxelize(self, origin, cell, dims, fill=False, counts=False, chunk=1 << 22, **launch):
+        """The scene's triangle mesh as a voxel grid: an (nz, ny, nx) bool tensor on the scene's device in which a voxel is set iff
+        count_in_box of its box -- voxel_boxes(origin, cell, dims) -- is positive: the voxel touches a triangle (closed, so a triangle
+        lying exactly in the face two voxels share sets both).  `counts=True` returns the int32 counts instead.  `fill=True` ORs the
+        result with contains() of the voxel centres 0.5 lo + 0.5 hi, so that the inside of the mesh is set as well; the limits are those
+        of contains: the mesh must be CLOSED for the parity to mean anything, and a ray through a shared edge or vertex EXACTLY can count
+        one crossing twice (or none): a caller who cannot accept that votes over several directions.  `fill` and `counts` do not go
+        together.  The grid is walked `chunk` voxels at a time (the boxes of a chunk are 32 bytes per voxel) and the result equals the
+        chain voxel_boxes -> count_in_box (-> contains) of public calls on bits.  `stream=`: as for overlap_box (it travels as a keyword
+        for the reason given in closest_point's docstring)."""
+        import torch
+        _only_kw("voxelize", launch, ("stream",))
+        stream = launch.get("stream")
+        if fill and counts:
+            raise ValueError("voxelize: fill sets voxels and counts returns numbers of triangles: ask for one of them")
+        if isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or chunk < 1:
+            raise ValueError(f"voxelize: chunk must be a positive integer, got {chunk!r}")
+        device = torch.device("cuda", self.device)
+        origin, cell, (nx, ny, nz) = _voxel_grid("voxelize", origin, cell, dims)
+        total = nx * ny * nz
+        _, tstream = _stream_pair(stream, device)
+        with torch.cuda.stream(tstream):
+            grid = torch.empty(total, dtype=torch.int32 if counts else torch.bool, device=device)
+            for first in range(0, total, int(chunk)):
+                m = min(int(chunk), total - first)
+                boxes = _voxel_box_records(origin, cell, (nx, ny, nz), first, m, device)
+                count = self.count_in_box(boxes, stream=stream)
+                if counts:
+                    grid[first:first + m] = count
+                    continue
+                grid[first:first + m] = count > 0
+                if fill:
+                    centres = (0.5 * boxes[:, 0:3] + 0.5 * boxes[:, 4:7]).contiguous()
+                    grid[first:first + m] |= self.contains(centres, stream=stream) != 0
+        return grid.view(nz, ny, nx)
+
     MOTION_CHANNELS = ("motion", "guide", "prim")
 
     def motion(self, width, height, prev_cameras, cameras=None, prev_vertices=None, out=None, stream=None):
@@ -1291,9 +1417,72 @@ SphereCasts.__doc__ = """Scene.sphere_cast's result: `records`, the (n, 8) float
 it -- `prim` (int32: the authoring-order triangle the ball touches first, -1 without a hit), `t` (the time of impact in units of the
 direction, +inf without a hit), `p` (n, 3), `b1`, `b2` and `feature` (int32, as in ClosestPoints): the contact point on that triangle."""
 
+OverlapLists = collections.namedtuple("OverlapLists", "count prims")
+OverlapLists.__doc__ = """Scene.overlap_box's result with an integer max_prims = K: `count`, int32 (n,) -- all triangles that touch the box, never clamped --,
+and `prims`, int32 (n, K): per box the min(count, K) smallest authoring indices among them, ascending, then -1."""
+
+OverlapCSR = collections.namedtuple("OverlapCSR", "count offsets prims")
+OverlapCSR.__doc__ = """Scene.overlap_box's result with max_prims None: `count`, int32 (n,), `offsets`, int64 (n + 1,) = the exclusive prefix sum of the
+counts, and `prims`, int32 (offsets[-1],): box i's triangles are prims[offsets[i]:offsets[i + 1]], authoring indices ascending."""
+
 ALL_HITS_MAX = 32   # GNXR_ALL_HITS_MAX
 NEAR_MAX = 32   # GNXR_NEAR_MAX
+OVERLAP_MAX = 32   # GNXR_OVERLAP_MAX
 CONTAINS_DIRECTION = (0.8017837, 0.5345225, 0.26726124)   # GNXR_CONTAINS_DIRECTION_*: (3, 2, 1) / sqrt(14) to within an ulp of fp32
+
+
+def _voxel_grid(name, origin, cell, dims):
+    """(origin, cell) as three float32 each -- `cell` a number or three -- and dims = (nx, ny, nz) as ints, each in [1, 2^24] (an index
+    is exact as a float32)"""
+    try:
+        o = np.array([float(x) for x in origin], np.float32)
+        c = np.array([float(cell)] * 3 if isinstance(cell, (int, float, np.integer, np.floating)) and not isinstance(cell, bool) else [float(x) for x in cell], np.float32)
+        d = tuple(int(x) for x in dims)
+    except (TypeError, ValueError):
+        raise TypeError(f"{name}: origin is three numbers, cell a number or three, dims three integers (nx, ny, nz)") from None
+    if o.shape != (3,) or c.shape != (3,) or len(d) != 3 or any(isinstance(x, (bool, float, np.floating)) for x in dims):
+        raise ValueError(f"{name}: origin is three numbers, cell a number or three, dims three integers (nx, ny, nz), got {origin!r}, {cell!r}, {dims!r}")
+    if not (np.isfinite(o).all() and np.isfinite(c).all() and (c > 0).all()):
+        raise ValueError(f"{name}: origin must be finite and cell finite and positive, got {origin!r}, {cell!r}")
+    if not all(1 <= x <= 1 << 24 for x in d):
+        raise ValueError(f"{name}: every dimension must be in [1, {1 << 24}], got {d}")
+    return o, c, d
+
+
+def _voxel_box_records(origin, cell, dims, first, count, device):
+    """the records of voxels first .. first + count of the grid in x-fastest order, on torch's current stream (voxel_boxes has the
+    definition)"""
+    import torch
+    nx, ny, _ = dims
+    flat = torch.arange(first, first + count, dtype=torch.int64, device=device)
+    index = (flat % nx, (flat // nx) % ny, flat // (nx * ny))
+    boxes = torch.zeros((count, 8), dtype=torch.float32, device=device)
+    o, c = torch.from_numpy(origin).to(device), torch.from_numpy(cell).to(device)
+    for k in range(3):
+        boxes[:, k] = index[k].to(torch.float32) * c[k] + o[k]
+        boxes[:, 4 + k] = (index[k] + 1).to(torch.float32) * c[k] + o[k]
+    return boxes
+
+
+def voxel_boxes(origin, cell, dims, out=None, **launch):
+    """The gnxr_box_query records of a voxel grid, for Scene.overlap_box / count_in_box: a float32 (nz * ny * nx, 8) tensor (`out` when
+    given), x fastest -- voxel (ix, iy, iz) is record (iz * ny + iy) * nx + ix.  `origin`: the grid's lower corner, three numbers;
+    `cell`: the edge of a voxel, a number or three; `dims` = (nx, ny, nz).  Per axis, with origin and cell rounded to float32 first:
+        lo = float32(i) * cell + origin          hi = float32(i + 1) * cell + origin
+    one float32 product and one float32 sum each, the pad words 0.  hi of voxel i and lo of voxel i + 1 are the same two operations on
+    the same numbers, so neighbours share their face bit for bit and a triangle in that face touches both.  Plain torch on `stream=`
+    (None: torch's current stream; it travels as a keyword for the reason given in Scene.closest_point's docstring) and on `device=`
+    (default: `out`'s device, else the device gnxr_init bound)."""
+    import torch
+    _only_kw("voxel_boxes", launch, ("stream", "device"))
+    origin, cell, dims = _voxel_grid("voxel_boxes", origin, cell, dims)
+    total = dims[0] * dims[1] * dims[2]
+    device = launch.get("device")
+    device = (out.device if _is_torch(out) else torch.device("cuda", _device)) if device is None else torch.device(device)
+    _, tstream, out = _outputs(launch.get("stream"), device, ("voxel_boxes: out", out, (total, 8), torch.float32))
+    with torch.cuda.stream(tstream):
+        out.copy_(_voxel_box_records(origin, cell, dims, 0, total, device))
+    return out
 
 
 def rays_tensor(o, d, tmax=float("inf")):

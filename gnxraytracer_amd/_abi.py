@@ -129,6 +129,10 @@ class SphereCast(C.Structure):   # gnxr_sphere_cast (no struct_size; not in gnxr
     _fields_ = [("o", f32 * 3), ("radius", f32), ("d", f32 * 3), ("tmax", f32)]
 
 
+class BoxQuery(C.Structure):   # gnxr_box_query (no struct_size; not in gnxr_abi_sizeof's list)
+    _fields_ = [("lo", f32 * 3), ("_pad0", f32), ("hi", f32 * 3), ("_pad1", f32)]
+
+
 class LiSample(C.Structure):
     _fields_ = [("px", i32), ("py", i32), ("s", i32), ("medium", i32)]
 
@@ -287,6 +291,9 @@ PROTOTYPES = {
     "gnxr_sphere_cast_device": (C.c_int, [VP, VP, i64, VP, VP]),   # casts, n, records: device addresses + hipStream_t
     "gnxr_sphere_cast_counted_device": (C.c_int, [VP, VP, i64, VP, VP, VP]),   # ..., two uint64 on the device, hipStream_t
     "gnxr_sphere_cast": (C.c_int, [VP, P(SphereCast), i64, P(ClosestPoint)]),
+    "gnxr_overlap_box_device": (C.c_int, [VP, VP, i64, i32, VP, VP, VP, VP]),   # boxes, n, max_prims, offsets (or NULL), prims, counts: device addresses + hipStream_t
+    "gnxr_overlap_box_counted_device": (C.c_int, [VP, VP, i64, i32, VP, VP, VP, VP, VP]),   # ..., two uint64 on the device, hipStream_t
+    "gnxr_overlap_box": (C.c_int, [VP, P(BoxQuery), i64, i32, P(i64), P(i32), P(i32)]),
     "gnxr_li_device": (C.c_int, [VP, P(RenderParams), VP, VP, i64, VP, VP, P(Stats)]),   # device addresses + hipStream_t
     "gnxr_render_views_device": (C.c_int, [VP, P(RenderParams), P(Camera), P(i32), i32, VP, VP, P(Stats)]),   # cameras, media: host; images: device
     "gnxr_render_aov_device": (C.c_int, [VP, P(RenderParams), P(Camera), P(i32), i32, P(AovBuffers), VP, P(Stats)]),   # cameras, media: host; buffers: device

@@ -132,6 +132,9 @@ struct Knobs {
     // GNXR_SPHERECAST_LDS_LEVELS: most levels of a sphere cast's stack (8-byte entries) kept in LDS, 1 .. 24 (default 16: a block's stack
     // is 32 KB, five blocks fill a CU's LDS; small values let tests reach the global spill on shallow trees).  Per call (launch)
     static int spherecast_lds_levels() { return std::max(1, std::min(24, env_int("GNXR_SPHERECAST_LDS_LEVELS", 16))); }
+    // GNXR_OVERLAP_LDS_LEVELS: most levels of a box overlap walk's stack (4-byte entries) kept in LDS, 1 .. 32 (default 16: a block's stack
+    // is 16 KB; small values let tests reach the global spill on shallow trees).  Per call (launch)
+    static int overlap_lds_levels() { return std::max(1, std::min(32, env_int("GNXR_OVERLAP_LDS_LEVELS", 16))); }
 };
 
 int ensure_device() {

@@ -1585,6 +1585,79 @@ int gnxr_sphere_cast_counted_device(gnxr_scene *scene, const struct gnxr_sphere_
                                     struct gnxr_closest_point *d_out, uint64_t *d_work, void *hip_stream);
 int gnxr_sphere_cast(gnxr_scene *scene, const struct gnxr_sphere_cast *casts, int64_t n, struct gnxr_closest_point *out);
 
+/* -- Overlap queries: the triangles an axis-aligned box touches ------------------------------------------------------------
+ * The volume query beside the ray, point and swept-sphere calls: which triangles touch this box.  Broad-phase collision against a mesh
+ * that has just been refitted, region selection, trigger volumes, an occupancy or navigation grid (a voxel grid is many boxes), the
+ * triangles to re-bake after an edit.  (gnxr_near_device with the box's half diagonal answers with a superset that grows with the
+ * box's aspect ratio.)  The walk goes through the scene's live 4-wide tree (the binary tree for scenes that are off it; same results),
+ * so after gnxr_scene_update_vertices[_ex], gnxr_scene_rebuild_bvh and gnxr_scene_set_geometry the answer is for the geometry the
+ * scene holds now.  Spheres of the scene are NOT considered: triangles only.
+ *
+ * A query is a gnxr_box_query (lo, hi); the two pad words are ignored.  The result is defined triangle by triangle, so it does not
+ * depend on the tree.  Every arithmetic step is ONE rounded fp32 operation (nothing is contracted), min(x, y) = (y < x ? y : x),
+ * max(x, y) = (y > x ? y : x), dot(u, v) = (u.x v.x + u.y v.y) + u.z v.z.  Per box:
+ *   1. Box validity.  If any lo[k] <= hi[k] is false (a NaN bound fails the comparison) or any of the six bounds is not finite, NOTHING
+ *      overlaps: the count is 0 and the list is empty.  lo == hi, a point, is a valid box.  (A caller who wants "everything" passes
+ *      the scene's bounds.)
+ *      Of a valid box: ctr[k] = 0.5 lo[k] + 0.5 hi[k] and h[k] = 0.5 hi[k] - 0.5 lo[k]: two products, then one sum / one difference.
+ * Per triangle (a, b, c), the vertices the scene holds, in authoring order:
+ *   2. Bounds test.  tlo = min(min(a, b), c), thi = max(max(a, b), c) per axis: selections, no arithmetic.  The triangle passes iff
+ *      tlo[k] <= hi[k] && thi[k] >= lo[k] on every axis k -- closed: touching counts.  This is also the ONLY test a tree applies to a
+ *      node's box: a node's box is the min / max of the vertices under it, so a triangle that passes has every enclosing node passing,
+ *      and a walk prunes on plain comparisons with no epsilon.
+ *   3. ua = a - ctr, ub = b - ctr, uc = c - ctr per component; e0 = ub - ua, e1 = uc - ub, e2 = ua - uc (of the rounded u).
+ *   4. Nine edge axes (Akenine-Moller's triangle-box test).  For the edges in the order e0, e1, e2, each with its pair of vertices of
+ *      distinct projections (p, q) = (ua, uc), (ub, ua), (uc, ub) -- the edge's first vertex and the vertex off the edge --, and for the
+ *      box axes in the order x, y, z with (i, j) = (y, z), (z, x), (x, y):
+ *          p0 = e[i] p[j] - e[j] p[i],   p1 = e[i] q[j] - e[j] q[i]      (two products and a difference each)
+ *          r  = h[i] |e[j]| + h[j] |e[i]|                                  (two products and a sum)
+ *      the axis SEPARATES iff min(p0, p1) > r || max(p0, p1) < -r.
+ *   5. Plane test.  n = (e0.y e1.z - e0.z e1.y, e0.z e1.x - e0.x e1.z, e0.x e1.y - e0.y e1.x).  Per axis k: below = (-h[k]) - ua[k],
+ *      above = h[k] - ua[k]; vmin[k] = (n[k] > 0 ? below : above), vmax[k] = (n[k] > 0 ? above : below).  The plane SEPARATES iff
+ *      dot(n, vmin) > 0 || !(dot(n, vmax) >= 0).
+ * The triangle OVERLAPS iff step 2 passes and neither step 4 nor step 5 separates.  Step 2 stands in for the original's three box-axis
+ * tests, which would round.  Steps 4 and 5 round: a triangle and a box that only just touch, or only just miss, may fall on either
+ * side, within a few ulps of the scene's size (DESIGN.md has the measured float64 margin); the answer is the same on every tree,
+ * every device and in the restatement.  A zero-area triangle has n = 0 and is decided by steps 2 and 4.  A brute force over all
+ * triangles in numpy float32 that follows this text (tests/overlap_reference.py) reproduces lists and counts byte for byte.
+ *
+ * The list of a box is the authoring indices (gnxr_hit.prim) of its overlapping triangles, ASCENDING, cut to the capacity of its row:
+ * a row shorter than the count holds the smallest indices; the slots behind the list hold -1; d_counts[i] is the number of ALL
+ * overlapping triangles, never clamped.  Two row layouts:
+ *   rows mode (d_offsets == NULL)  row i is d_prims[i K .. (i + 1) K), K = max_prims in [0, GNXR_OVERLAP_MAX].  K == 0 is the
+ *                                  count-only form and requires d_prims == NULL.
+ *   CSR mode (d_offsets given)     n + 1 ascending int64 values on the device, 8-byte aligned; row i is
+ *                                  d_prims[d_offsets[i] .. d_offsets[i + 1]) and its capacity is that difference (not limited by
+ *                                  GNXR_OVERLAP_MAX; 0 when the two are out of order).  max_prims must be -1 and d_prims must be
+ *                                  given.  The usual sequence is a count-only call, an exclusive prefix sum of the counts, one
+ *                                  allocation, and this call.  Nothing outside a row is ever written, so offsets that are stale
+ *                                  for the geometry cut or pad rows and corrupt nothing; the offsets themselves are the caller's
+ *                                  word for where d_prims may be written.
+ * While a box is walked its row is the walk's own working list (insertion: a row of length L costs up to L^2 / 2 dword moves); it
+ * holds the result when the call's work on the stream is done.
+ *
+ * gnxr_overlap_box_device: the conventions of gnxr_trace_all_device -- every array is device memory of one device that holds a copy
+ * of the scene, d_boxes 16-byte aligned, d_offsets 8-byte, d_prims and d_counts 4-byte aligned; the work is queued on hip_stream
+ * (NULL: the null stream) after what the caller queued there, nothing is copied back and nothing waits for the GPU; scratch (the
+ * walk's stack beyond its LDS levels, sized by the scene and the grid, never by n) comes from the stream-ordered allocator on that
+ * stream; boxes are walked in caller order (no binning); n == 0 is a no-op; GNXR_ERR_INVALID with a message, before anything is queued
+ * and with the scene untouched, for a null scene, a null pointer with n > 0, n < 0, max_prims outside [0, GNXR_OVERLAP_MAX] in rows
+ * mode, d_prims set with max_prims == 0 or missing with max_prims > 0, max_prims != -1 together with d_offsets or -1 without them, a
+ * misaligned pointer, host pointers, pointers on a device without a copy of the scene or on different devices, or an array that runs
+ * past its allocation (the extent of CSR rows lives on the device and is not looked at).  gnxr_overlap_box_counted_device is the same
+ * call through the counting instantiation of the kernel (measurements only: slower): it ADDS the nodes visited and the triangles
+ * taken to step 2 by the call to d_work[0], d_work[1] (device memory, 8-byte aligned, the caller's to clear).  gnxr_overlap_box
+ * takes host arrays: copy in, the same walk, copy out; it returns when the arrays are written, and, since it can read them, refuses
+ * offsets that are negative or do not ascend.  The record carries no struct_size and is not part of gnxr_abi_sizeof's list. */
+#define GNXR_OVERLAP_MAX 32
+typedef struct gnxr_box_query { float lo[3]; float pad0; float hi[3]; float pad1; } gnxr_box_query;   /* 32 bytes, 16-byte aligned on the device */
+int gnxr_overlap_box_device(gnxr_scene *scene, const gnxr_box_query *d_boxes, int64_t n, int32_t max_prims, const int64_t *d_offsets,
+                            int32_t *d_prims, int32_t *d_counts, void *hip_stream);
+int gnxr_overlap_box_counted_device(gnxr_scene *scene, const gnxr_box_query *d_boxes, int64_t n, int32_t max_prims,
+                                    const int64_t *d_offsets, int32_t *d_prims, int32_t *d_counts, uint64_t *d_work, void *hip_stream);
+int gnxr_overlap_box(gnxr_scene *scene, const gnxr_box_query *boxes, int64_t n, int32_t max_prims, const int64_t *offsets,
+                     int32_t *prims, int32_t *counts);
+
 /* -- Shading queries on device memory: the pieces an integrator is made of, batched -------------------------------------
  * Same conventions as the device calls of the Aggregate seam: every array is device memory of one device that holds a copy of the
  * scene, the work is queued on hip_stream (NULL: the null stream) after what the caller queued there, scratch comes from the
