@@ -1257,6 +1257,12 @@ class Scene:
         return self._overlap_box("overlap_box", lo, hi, max_prims, out, counts_out, launch)
 
     def _overlap_box(self, name, lo, hi, max_prims, out, counts_out, launch):
+        return self._overlap_lists(name, max_prims, out, counts_out, launch, lambda stream: self._box_queries(name, lo, hi, stream), (), "gnxr_overlap_box")
+
+    def _overlap_lists(self, name, max_prims, out, counts_out, launch, queries, flags, entry):
+        """The rows / CSR plumbing the overlap queries share (overlap_box, overlap_triangles, self_intersections).  `queries(stream)`:
+        the checked record tensor of the call, or the number of queries of a call whose queries are the scene's own; `flags`: what the
+        C call takes between n and max_prims, as a tuple; `entry`: the C calls' common name, "<entry>_device" and "<entry>_counted_device"."""
         import torch
         _only_kw(name, launch, ("stream", "counts"))
         stream, work = launch.get("stream"), launch.get("counts")
@@ -1264,18 +1270,21 @@ class Scene:
         if csr and out is not None:
             raise ValueError(f"{name}: with max_prims None the lists are allocated by the call; out must be None")
         K = 0 if csr else _list_length(name, "max_prims", max_prims, 0, OVERLAP_MAX)
-        boxes = self._box_queries(name, lo, hi, stream)
-        n = boxes.shape[0]
-        st, tstream, out, counts_out = _outputs(stream, boxes.device, (f"{name}: out", out, (n, K), torch.int32), (f"{name}: counts_out", counts_out, (n,), torch.int32))
-        call = lambda k, offsets, prims: _walk_call(name, lib().gnxr_overlap_box_device, lib().gnxr_overlap_box_counted_device,
-                                                    (self._h, _ptr(boxes), n, k, _ptr(offsets), _ptr(prims), _ptr(counts_out)), work, 2, boxes.device, st)
+        records = queries(stream)
+        if isinstance(records, int):
+            records, n, device = None, records, torch.device("cuda", self.device)
+        else:
+            n, device = records.shape[0], records.device
+        st, tstream, out, counts_out = _outputs(stream, device, (f"{name}: out", out, (n, K), torch.int32), (f"{name}: counts_out", counts_out, (n,), torch.int32))
+        call = lambda k, offsets, prims: _walk_call(name, getattr(lib(), entry + "_device"), getattr(lib(), entry + "_counted_device"), (self._h, _ptr(records), n, *flags, k, _ptr(offsets), _ptr(prims), _ptr(counts_out)),
+                                                    work, 2, device, st)
         call(K, None, out if K else None)
         if not csr:
             return OverlapLists(counts_out, out)
         with torch.cuda.stream(tstream):
-            offsets = torch.zeros(n + 1, dtype=torch.int64, device=boxes.device)
+            offsets = torch.zeros(n + 1, dtype=torch.int64, device=device)
             torch.cumsum(counts_out, 0, dtype=torch.int64, out=offsets[1:])
-            prims = torch.empty(int(offsets[-1]), dtype=torch.int32, device=boxes.device)
+            prims = torch.empty(int(offsets[-1]), dtype=torch.int32, device=device)
         if prims.numel():
             call(-1, offsets, prims)
         return OverlapCSR(counts_out, offsets, prims)
@@ -1293,6 +1302,81 @@ class Scene:
         counts = np.zeros(n, dtype=np.int32)
         I32, I64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
         call = lambda k, offsets, prims: _check(lib().gnxr_overlap_box(self._h, boxes.ctypes.data_as(C.POINTER(_abi.BoxQuery)), n, k,
+                                                                       offsets.ctypes.data_as(I64) if offsets is not None else None,
+                                                                       prims.ctypes.data_as(I32) if prims is not None else None, counts.ctypes.data_as(I32)))
+        if max_prims is not None:
+            max_prims = int(max_prims)
+            prims = np.zeros((n, max(max_prims, 0)), dtype=np.int32)
+            call(max_prims, None, prims if max_prims > 0 else None)
+            return prims, counts
+        call(0, None, None)
+        offsets = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(counts, dtype=np.int64, out=offsets[1:])
+        prims = np.zeros(int(offsets[-1]), dtype=np.int32)
+        if len(prims):
+            call(-1, offsets, prims)
+        return prims, counts, offsets
+
+    # triangle overlap queries (gnxr_overlap_tri_device / gnxr_overlap_tri)
+    def _tri_queries(self, name, tris, stream):
+        """`tris` as checked (n, 12) gnxr_tri_query records on the scene's device: ready-made, or packed by triangle_queries on `stream`
+        from corners or from a (vertices, indices) pair"""
+        import torch
+        if _is_tensor(tris, torch.float32, (None, 12)):
+            return _expect(f"{name}: tris", tris, torch.float32, (12,), self.device)
+        vertices, indices = tris if isinstance(tris, tuple) and len(tris) == 2 else (tris, None)
+        return _tri_records(name, vertices, indices, None, stream, self.device)
+
+    def overlap_triangles(self, tris, max_prims=None, skip_shared=False, out=None, counts_out=None, **launch):
+        """EVERY triangle of the scene that touches query triangles already on the GPU -- mesh against mesh, exactly
+        (gnxr_overlap_tri_device; the definition, triangle by triangle: include/gnxr.h, "Triangle overlap queries").  `tris`: a float32
+        (n, 12) tensor of ready-made gnxr_tri_query records on the scene's device (a.xyz, pad, b.xyz, pad, c.xyz, pad), or anything
+        triangle_queries takes: (n, 3, 3) or (n, 9) corners, or a (vertices, indices) tuple.  Touching counts; a zero-area triangle (a
+        segment, a point) is a legitimate query; a coordinate that is not finite overlaps nothing.  `skip_shared=True` leaves out every
+        triangle that shares a vertex position with the query (GNXR_OVERLAP_TRI_SKIP_SHARED).  `max_prims`, the results (OverlapLists
+        with an integer, OverlapCSR with None), `out`, `counts_out` and the launch keywords `stream=` and `counts=` are overlap_box's.
+        (The refusals are exercised in tests/test_overlap_triangles.py.)"""
+        return self._overlap_tri("overlap_triangles", tris, max_prims, skip_shared, out, counts_out, launch)
+
+    def _overlap_tri(self, name, tris, max_prims, skip_shared, out, counts_out, launch):
+        flags = _abi.OVERLAP_TRI_SKIP_SHARED if skip_shared else 0
+        return self._overlap_lists(name, max_prims, out, counts_out, launch, lambda stream: self._tri_queries(name, tris, stream), (flags,), "gnxr_overlap_tri")
+
+    def count_overlapping_triangles(self, tris, skip_shared=False, **launch):
+        """overlap_triangles with max_prims = 0: the int32 (n,) number of triangles that touch each query triangle, and no list."""
+        return self._overlap_tri("count_overlapping_triangles", tris, 0, skip_shared, None, None, launch).count
+
+    def self_intersections(self, max_prims=None, pairs=False, **launch):
+        """The scene's mesh against itself (gnxr_overlap_tri_device with GNXR_OVERLAP_TRI_SELF): query i is the scene's own triangle with
+        authoring index i, and every triangle that shares a vertex position with it -- itself, its edge and vertex neighbours -- is left
+        out, so what is reported is the mesh passing through itself.  Returns overlap_triangles' OverlapLists / OverlapCSR over the
+        n_triangles triangles, rows and counts indexed by authoring index.  `pairs=True` (with `max_prims` None): an (m, 2) int32 tensor
+        of the unique pairs (i, j), i < j, reported in either direction, sorted lexicographically -- built with torch on the CSR result,
+        on the same stream; m == 0 means the pose is free of self-intersections.  Launch keywords: overlap_box's."""
+        import torch
+        name = "self_intersections"
+        if pairs and max_prims is not None:
+            raise ValueError(f"{name}: pairs are built from the complete lists; max_prims must be None")
+        n = self.n_triangles
+        res = self._overlap_lists(name, max_prims, None, None, launch, lambda stream: n, (_abi.OVERLAP_TRI_SELF,), "gnxr_overlap_tri")
+        if not pairs:
+            return res
+        with torch.cuda.stream(_stream_pair(launch.get("stream"), res.prims.device)[1]):
+            i = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=res.prims.device), res.count.to(torch.int64), output_size=res.prims.numel())
+            j = res.prims.to(torch.int64)
+            key = torch.unique(torch.minimum(i, j) * n + torch.maximum(i, j))   # sorted: lexicographic in (i, j)
+            return torch.stack([key // n, key % n], dim=1).to(torch.int32)
+
+    def OverlapTriangles(self, tris, max_prims, flags=0):
+        """overlap_triangles for numpy arrays (gnxr_overlap_tri): `tris` is (n, 12) float32 -- a.xyz, pad, b.xyz, pad, c.xyz, pad --, or
+        None with OVERLAP_TRI_SELF in `flags` (OVERLAP_TRI_SKIP_SHARED | OVERLAP_TRI_SELF).  Returns what OverlapBox returns: (prims,
+        counts) with an integer `max_prims`, (prims, counts, offsets) with None."""
+        if tris is not None:
+            tris = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 12)
+        n = self.n_triangles if tris is None else len(tris)
+        counts = np.zeros(n, dtype=np.int32)
+        I32, I64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        call = lambda k, offsets, prims: _check(lib().gnxr_overlap_tri(self._h, tris.ctypes.data_as(C.POINTER(_abi.TriQuery)) if tris is not None else None, n, int(flags), k,
                                                                        offsets.ctypes.data_as(I64) if offsets is not None else None,
                                                                        prims.ctypes.data_as(I32) if prims is not None else None, counts.ctypes.data_as(I32)))
         if max_prims is not None:
@@ -1428,6 +1512,7 @@ counts, and `prims`, int32 (offsets[-1],): box i's triangles are prims[offsets[i
 ALL_HITS_MAX = 32   # GNXR_ALL_HITS_MAX
 NEAR_MAX = 32   # GNXR_NEAR_MAX
 OVERLAP_MAX = 32   # GNXR_OVERLAP_MAX
+OVERLAP_TRI_SKIP_SHARED, OVERLAP_TRI_SELF = _abi.OVERLAP_TRI_SKIP_SHARED, _abi.OVERLAP_TRI_SELF   # GNXR_OVERLAP_TRI_*
 CONTAINS_DIRECTION = (0.8017837, 0.5345225, 0.26726124)   # GNXR_CONTAINS_DIRECTION_*: (3, 2, 1) / sqrt(14) to within an ulp of fp32
 
 
@@ -1483,6 +1568,42 @@ def voxel_boxes(origin, cell, dims, out=None, **launch):
     with torch.cuda.stream(tstream):
         out.copy_(_voxel_box_records(origin, cell, dims, 0, total, device))
     return out
+
+
+def _tri_records(name, vertices, indices, out, stream, device=None):
+    """triangle_queries behind its checks; `device`: None (the corners' own GPU) or the index of the GPU they must be on"""
+    import torch
+    where = ANY_GPU if device is None else device
+    on = "a GPU" if device is None else f"cuda:{device}"
+    if indices is None:
+        if not (_is_tensor(vertices, torch.float32, (None, 3, 3), where) or _is_tensor(vertices, torch.float32, (None, 9), where)):
+            _refuse(vertices, f"{name}: tris: expected a contiguous torch.float32 (n, 12), (n, 3, 3) or (n, 9) tensor on {on}, or (vertices (V, 3), indices (n, 3))")
+        corners = vertices.view(-1, 3, 3)
+    else:
+        if not _is_tensor(vertices, torch.float32, (None, 3), where):
+            _refuse(vertices, f"{name}: vertices: expected a contiguous torch.float32 (V, 3) tensor on {on}")
+        if not (_is_tensor(indices, torch.int32, (None, 3), vertices.device) or _is_tensor(indices, torch.int64, (None, 3), vertices.device)):
+            _refuse(indices, f"{name}: indices: expected a contiguous torch.int32 or torch.int64 (n, 3) tensor on {vertices.device}")
+        corners = None
+    n = (corners if indices is None else indices).shape[0]
+    _, tstream, out = _outputs(stream, vertices.device, (f"{name}: out", out, (n, 12), torch.float32))
+    with torch.cuda.stream(tstream):
+        if corners is None:
+            corners = vertices[indices.to(torch.int64)]
+        rec = out.view(n, 3, 4)
+        rec[:, :, 0:3] = corners
+        rec[:, :, 3] = 0
+    return out
+
+
+def triangle_queries(vertices, indices=None, out=None, **launch):
+    """The gnxr_tri_query records of Scene.overlap_triangles, packed on the device: a float32 (n, 12) tensor (`out` when given) of
+    a.xyz, pad, b.xyz, pad, c.xyz, pad with the pads 0.  `vertices`: contiguous float32 (n, 3, 3) or (n, 9) corners on a GPU; or, with
+    `indices` an int32 / int64 (n, 3) tensor on the same device, a (V, 3) vertex array the corners are gathered from (an index outside
+    [0, V) is the caller's error, as for any torch gather).  Plain torch on `stream=` (None: torch's current stream; it travels as a
+    keyword for the reason given in Scene.closest_point's docstring)."""
+    _only_kw("triangle_queries", launch, ("stream",))
+    return _tri_records("triangle_queries", vertices, indices, out, launch.get("stream"))
 
 
 def rays_tensor(o, d, tmax=float("inf")):

@@ -133,6 +133,13 @@ class BoxQuery(C.Structure):   # gnxr_box_query (no struct_size; not in gnxr_abi
     _fields_ = [("lo", f32 * 3), ("_pad0", f32), ("hi", f32 * 3), ("_pad1", f32)]
 
 
+OVERLAP_TRI_SKIP_SHARED, OVERLAP_TRI_SELF = 1, 2   # GNXR_OVERLAP_TRI_*: the flags of gnxr_overlap_tri_device
+
+
+class TriQuery(C.Structure):   # gnxr_tri_query (no struct_size; not in gnxr_abi_sizeof's list)
+    _fields_ = [("a", f32 * 3), ("_pad0", f32), ("b", f32 * 3), ("_pad1", f32), ("c", f32 * 3), ("_pad2", f32)]
+
+
 class LiSample(C.Structure):
     _fields_ = [("px", i32), ("py", i32), ("s", i32), ("medium", i32)]
 
@@ -294,6 +301,9 @@ PROTOTYPES = {
     "gnxr_overlap_box_device": (C.c_int, [VP, VP, i64, i32, VP, VP, VP, VP]),   # boxes, n, max_prims, offsets (or NULL), prims, counts: device addresses + hipStream_t
     "gnxr_overlap_box_counted_device": (C.c_int, [VP, VP, i64, i32, VP, VP, VP, VP, VP]),   # ..., two uint64 on the device, hipStream_t
     "gnxr_overlap_box": (C.c_int, [VP, P(BoxQuery), i64, i32, P(i64), P(i32), P(i32)]),
+    "gnxr_overlap_tri_device": (C.c_int, [VP, VP, i64, u32, i32, VP, VP, VP, VP]),   # tris (NULL with SELF), n, flags, max_prims, offsets (or NULL), prims, counts: device addresses + hipStream_t
+    "gnxr_overlap_tri_counted_device": (C.c_int, [VP, VP, i64, u32, i32, VP, VP, VP, VP, VP]),   # ..., two uint64 on the device, hipStream_t
+    "gnxr_overlap_tri": (C.c_int, [VP, P(TriQuery), i64, u32, i32, P(i64), P(i32), P(i32)]),
     "gnxr_li_device": (C.c_int, [VP, P(RenderParams), VP, VP, i64, VP, VP, P(Stats)]),   # device addresses + hipStream_t
     "gnxr_render_views_device": (C.c_int, [VP, P(RenderParams), P(Camera), P(i32), i32, VP, VP, P(Stats)]),   # cameras, media: host; images: device
     "gnxr_render_aov_device": (C.c_int, [VP, P(RenderParams), P(Camera), P(i32), i32, P(AovBuffers), VP, P(Stats)]),   # cameras, media: host; buffers: device

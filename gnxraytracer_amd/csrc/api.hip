@@ -43,6 +43,7 @@
 #include "near_kernel.hip.h"
 #include "spherecast_kernel.hip.h"
 #include "overlap_kernel.hip.h"
+#include "overlap_tri_kernel.hip.h"
 #include "kernel_instances.h"
 
 using namespace gnxr;
@@ -334,6 +335,7 @@ int gnxr_trace_any(gnxr_scene *s, const gnxr_ray *rays, int64_t n, uint8_t *occl
 #include "api_near.hip.h"
 #include "api_spherecast.hip.h"
 #include "api_overlap.hip.h"
+#include "api_overlap_tri.hip.h"
 #include "api_aov.hip.h"
 #include "api_adaptive.hip.h"
 #include "api_denoise.hip.h"

@@ -1,8 +1,8 @@
 // api_walk.hip.h -- how a per-lane query walk (bvh_walk.hip.h) is run: the one driver under closest points, all hits, neighbours,
-// sphere casts and box overlaps.  It owns the launch plan (WalkLaunch), the Morton binning of point queries (QueryBinning), the chunk loop with its
+// sphere casts, box overlaps and triangle overlaps.  It owns the launch plan (WalkLaunch), the Morton binning of point queries (QueryBinning), the chunk loop with its
 // launches (walk_launch), the front end of the entry points on device memory (walk_device: the null tests, the n == 0 return, the
 // alignment, DeviceCall, query_device_scene) and the upload / walk / download of the entry points on host arrays (walk_host).  A query
-// kind describes itself to it in a small struct (ClosestWalk, AllHitsWalk, NearWalk, SphereCastWalk, OverlapWalk in the five api_*.hip.h that follow):
+// kind describes itself to it in a small struct (ClosestWalk, AllHitsWalk, NearWalk, SphereCastWalk, OverlapWalk, OverlapTriWalk in the six api_*.hip.h that follow):
 //     Arrays, Spill       the kernel's arrays struct and the type of its spill pointer
 //     kBinnable           the queries are 16-byte point records QueryBinning can sort; the kernel then takes their order
 //     work                nullptr, or the device words the counting instantiation adds its counters to
@@ -11,7 +11,7 @@
 //     at(base)            the arrays of the chunk that starts at query `base`
 //     kernel(wide)        the instantiation to launch for (wide, the kind's own mode, work != nullptr)
 // The launch path is a template over that struct: no virtual call, nothing type-erased.  Part of api.hip's translation unit (after
-// api_query.hip.h, before the five kinds).
+// api_query.hip.h, before the six kinds).
 #pragma once
 
 // blocks per CU of a walk's grid: at the default 16 LDS levels a block's stack is 32 KB with 8-byte entries, 16 KB with 4-byte ones

@@ -1,4 +1,4 @@
-// bvh_walk.hip.h -- the mechanics the per-lane query walks share (k_closest_point, k_all_hits, k_near, k_sphere_cast, k_overlap_box): the stack, the
+// bvh_walk.hip.h -- the mechanics the per-lane query walks share (k_closest_point, k_all_hits, k_near, k_sphere_cast, k_overlap_box, k_overlap_tri): the stack, the
 // node decode, the children of an interior node with their boxes, and the descent step in its two orders (walk_enter_nearest,
 // walk_enter_all) with the pop that follows it (walk_pop).  Nothing here decides a result: the callers supply the keys and the bounds --
 // what a box is worth to a kernel, which children stay and what is tested at a leaf is that kernel's own.  DESIGN.md, "The walk the

@@ -1658,6 +1658,76 @@ int gnxr_overlap_box_counted_device(gnxr_scene *scene, const gnxr_box_query *d_b
 int gnxr_overlap_box(gnxr_scene *scene, const gnxr_box_query *boxes, int64_t n, int32_t max_prims, const int64_t *offsets,
                      int32_t *prims, int32_t *counts);
 
+/* -- Triangle overlap queries: the triangles another triangle touches, and a mesh against itself ----------------------------
+ * The exact test beside the box query: which triangles of the scene touch this triangle.  Mesh against mesh -- a tool, a garment, a
+ * second character, a prop: one query per foreign triangle -- and, with the scene's own triangles as the queries, self-intersection:
+ * did this pose fold the mesh through itself?  (gnxr_overlap_box_device on a foreign triangle's bounds answers with a superset, which
+ * for a thin or diagonal triangle is most of what it returns.)  The walk, the live tree and the spheres are as for the box queries.
+ *
+ * A query is a gnxr_tri_query (a, b, c); the three pad words are ignored.  The result is defined triangle by triangle, so it does not
+ * depend on the tree.  The conventions are the box section's: every arithmetic step is ONE rounded fp32 operation (nothing is
+ * contracted), min(x, y) = (y < x ? y : x), max(x, y) = (y > x ? y : x), of three values min(min(x, y), z) and max(max(x, y), z) in the
+ * order they are written below, dot(u, v) = (u.x v.x + u.y v.y) + u.z v.z, u - v per component, and
+ * cross(u, v) = (u.y v.z - u.z v.y, u.z v.x - u.x v.z, u.x v.y - u.y v.x): two products and a difference per component.
+ * Per query (qa, qb, qc):
+ *   1. Validity.  If any of the nine coordinates is not finite, NOTHING overlaps: the count is 0 and the list is empty.  Every finite
+ *      triangle is valid, zero-area ones included: a segment or a point is a legitimate query.
+ *      Of a valid query: qlo = min(min(qa, qb), qc), qhi = max(max(qa, qb), qc) per axis (selections); ub = qb - qa, uc = qc - qa;
+ *      f0 = ub, f1 = uc - ub, f2 = uc; nq = cross(ub, uc).
+ * Per triangle (a, b, c), the vertices the scene holds, in authoring order:
+ *   2. Bounds test.  Step 2 of the box queries against the box [qlo, qhi]: tlo = min(min(a, b), c), thi = max(max(a, b), c) per axis,
+ *      and the triangle passes iff tlo[k] <= qhi[k] && thi[k] >= qlo[k] on every axis k -- closed, comparisons only.  This is the ONLY
+ *      test a tree applies to a node's box, so a walk visits exactly the nodes gnxr_overlap_box_device visits for the box [qlo, qhi]
+ *      and prunes with no epsilon.
+ *   3. Shared vertices (only with GNXR_OVERLAP_TRI_SKIP_SHARED).  If any of the nine pairs (query vertex, triangle vertex) compares
+ *      equal with == on all three coordinates (-0 == +0; a NaN equals nothing), the triangle is SKIPPED: neither counted nor listed.
+ *      With the scene's own triangles as the queries this leaves out the triangle itself and its edge and vertex neighbours, which
+ *      touch by construction: what remains is self-intersection.  The rule looks at positions only, so the duplicated vertices of a
+ *      crease or a texture seam count as shared.
+ *   4. Translate.  ta = a - qa, tb = b - qa, tc = c - qa; e0 = tb - ta, e1 = tc - tb, e2 = ta - tc (of the rounded t);
+ *      nt = cross(e0, e1).
+ *   5. Seventeen separating axes L: nq; nt; cross(f_i, e_j) for i, j in 0..2; cross(nq, f_i) for i in 0..2; cross(nt, e_j) for j in
+ *      0..2 -- the last two groups are the in-plane axes that decide coplanar pairs.  On an axis, with the query's vertices at 0, ub,
+ *      uc after the translation:
+ *          qmin = min(min(0, dot(L, ub)), dot(L, uc)),          qmax = max(max(0, dot(L, ub)), dot(L, uc))
+ *          tmin = min(min(dot(L, ta), dot(L, tb)), dot(L, tc)),  tmax = max(max(dot(L, ta), dot(L, tb)), dot(L, tc))
+ *      and the axis SEPARATES iff tmin > qmax || tmax < qmin -- closed: touching counts.  A zero axis (a zero-area triangle, parallel
+ *      edges) gives two intervals [0, 0] and never separates.  Where an axis overflows to NaN (inf - inf) the comparisons are false
+ *      and it does not separate: the answer is then conservative, and still the same bits everywhere.
+ * The triangle OVERLAPS iff step 2 passes, step 3 does not skip it and no axis of step 5 separates.  The axes are independent of each
+ * other: an implementation may evaluate them in any order, stop at the first that separates, and compute what depends on the query
+ * alone (nq, the three cross(nq, f_i), the query's intervals on those four) once per query; the bits do not change.
+ * Limits.  (i) The translation is by the QUERY's first vertex, so at the rounding margin overlaps(Q, T) and overlaps(T, Q) may differ;
+ * a caller who needs a symmetric relation ORs the two directions (as the pairs of a self-intersection call do).  (ii) Steps 4 and 5
+ * round: a touching answer means "within a few ulps of the coordinates' size", as for boxes (DESIGN.md has the measured float64
+ * margin).  (iii) A zero-area triangle has no normal and so no in-plane axes of its own: a segment lying in the plane of a triangle
+ * it passes beside can be reported (conservative).  A brute force over all triangles in numpy float32 that follows this text
+ * (tests/overlap_tri_reference.py) reproduces lists and counts byte for byte.
+ *
+ * Lists, counts and row layouts are exactly gnxr_overlap_box_device's: authoring indices ASCENDING, cut to the capacity of the row, -1
+ * behind the list, d_counts[i] never clamped; rows mode with max_prims in [0, GNXR_OVERLAP_MAX] (0: count only, d_prims NULL) or CSR
+ * mode through d_offsets with max_prims == -1; nothing outside a row is written.
+ *
+ * flags: GNXR_OVERLAP_TRI_SKIP_SHARED applies step 3.  GNXR_OVERLAP_TRI_SELF: the queries are the scene's own triangles -- d_tris must
+ * be NULL, n must equal the scene's triangle count, SKIP_SHARED is implied, query i is the triangle with authoring index i, and rows,
+ * offsets and counts are indexed by authoring index.  (The kernel takes the triangles in the tree's leaf order, where neighbouring
+ * lanes walk nearly the same path; other queries are walked in caller order.)
+ *
+ * gnxr_overlap_tri_device: the conventions, alignments and refusals of gnxr_overlap_box_device, with d_tris 16-byte aligned (three
+ * 16-byte loads per record); in addition GNXR_ERR_INVALID with a message for an unknown flag bit, for SELF with a non-NULL d_tris and
+ * for SELF with n other than the scene's triangle count.  gnxr_overlap_tri_counted_device ADDS nodes visited and triangles taken to
+ * step 2 to d_work[0], d_work[1] (measurements only: slower).  gnxr_overlap_tri takes host arrays, as gnxr_overlap_box does.  The
+ * record carries no struct_size and is not part of gnxr_abi_sizeof's list. */
+#define GNXR_OVERLAP_TRI_SKIP_SHARED 1u
+#define GNXR_OVERLAP_TRI_SELF        2u
+typedef struct gnxr_tri_query { float a[3]; float pad0; float b[3]; float pad1; float c[3]; float pad2; } gnxr_tri_query;   /* 48 bytes, 16-byte aligned on the device */
+int gnxr_overlap_tri_device(gnxr_scene *scene, const gnxr_tri_query *d_tris, int64_t n, uint32_t flags, int32_t max_prims,
+                            const int64_t *d_offsets, int32_t *d_prims, int32_t *d_counts, void *hip_stream);
+int gnxr_overlap_tri_counted_device(gnxr_scene *scene, const gnxr_tri_query *d_tris, int64_t n, uint32_t flags, int32_t max_prims,
+                                    const int64_t *d_offsets, int32_t *d_prims, int32_t *d_counts, uint64_t *d_work, void *hip_stream);
+int gnxr_overlap_tri(gnxr_scene *scene, const gnxr_tri_query *tris, int64_t n, uint32_t flags, int32_t max_prims, const int64_t *offsets,
+                     int32_t *prims, int32_t *counts);
+
 /* -- Shading queries on device memory: the pieces an integrator is made of, batched -------------------------------------
  * Same conventions as the device calls of the Aggregate seam: every array is device memory of one device that holds a copy of the
  * scene, the work is queued on hip_stream (NULL: the null stream) after what the caller queued there, scratch comes from the
