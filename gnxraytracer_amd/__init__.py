@@ -393,6 +393,18 @@ class Scene:
         _check(lib().gnxr_scene_nee_apply_counts(self._h, C.byref(t), C.byref(w)))
         return int(t.value), int(w.value)
 
+    def hot_leaf_counts(self):
+        """gnxr_scene_hot_leaf_counts: (triangles the last render's counting traversal took from LDS, triangles it loaded)."""
+        h, t = C.c_uint64(), C.c_uint64()
+        _check(lib().gnxr_scene_hot_leaf_counts(self._h, C.byref(h), C.byref(t)))
+        return int(h.value), int(t.value)
+
+    def trace_plan(self, total=1 << 24):
+        """gnxr_scene_trace_plan: the shape of a traversal launch of `total` work items on this scene, as a dict."""
+        t = _abi.TracePlan()
+        _check(lib().gnxr_scene_trace_plan(self._h, int(total), C.byref(t)))
+        return {k: int(getattr(t, k)) for k, _ in _abi.TracePlan._fields_ if k != "_pad"}
+
     # editing between frames (gnxr_scene_update_vertices / gnxr_scene_set_camera)
     def update_vertices(self, xyz, first_vertex=0, stream=None, move_lights=False):
         """Move vertices [first_vertex, first_vertex + len(xyz)) of the description's vertex array to xyz (world space, (n, 3) float32):

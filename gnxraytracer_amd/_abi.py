@@ -157,6 +157,11 @@ class LightResult(C.Structure):
     _fields_ = [("Li", f32 * 3), ("pdf", f32), ("wi", f32 * 3), ("pdf_li", f32), ("pdf_select", f32), ("p_light", f32 * 3)]
 
 
+class TracePlan(C.Structure):   # gnxr_trace_plan (gnxr_scene_trace_plan)
+    _fields_ = [("wide", i32), ("stack_entries", i32), ("lds_entries", i32), ("n_top", i32), ("hot_bytes", i32), ("blocks", i32), ("blocks_per_cu", i32), ("_pad", i32),
+                ("lds_bytes", i64)]
+
+
 class Geometry(C.Structure):   # gnxr_geometry: the arrays are host or device addresses (not in gnxr_abi_sizeof's list: it carries struct_size)
     _fields_ = [("struct_size", i32), ("n_vertices", i32), ("n_triangles", i32), ("_pad", i32),
                 ("vertices", C.c_void_p), ("indices", C.c_void_p), ("tri_material", C.c_void_p), ("tri_light", C.c_void_p),
@@ -282,6 +287,8 @@ PROTOTYPES = {
     "gnxr_render_device": (C.c_int, [VP, P(RenderParams), VP, VP, P(Stats)]),
     "gnxr_render_reserve": (C.c_int, [VP, P(RenderParams)]),
     "gnxr_scene_nee_apply_counts": (C.c_int, [VP, P(u64), P(u64)]),
+    "gnxr_scene_hot_leaf_counts": (C.c_int, [VP, P(u64), P(u64)]),
+    "gnxr_scene_trace_plan": (C.c_int, [VP, i64, P(TracePlan)]),
     "gnxr_trace_closest": (C.c_int, [VP, P(Ray), i64, P(Hit)]),
     "gnxr_trace_any": (C.c_int, [VP, P(Ray), i64, P(u8)]),
     "gnxr_trace_closest_device": (C.c_int, [VP, VP, i64, VP, VP]),   # device addresses + hipStream_t

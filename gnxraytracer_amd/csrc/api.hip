@@ -231,6 +231,32 @@ int gnxr_scene_nee_apply_counts(gnxr_scene *s, uint64_t *in_trace, uint64_t *by_
     return GNXR_OK;
 }
 
+// What k_trace4<COUNT> counted in the handle's last render (Counters::tris_hot / tris), summed over its devices.
+int gnxr_scene_hot_leaf_counts(gnxr_scene *s, uint64_t *tris_from_lds, uint64_t *tris_loaded) {
+    if (!s) { set_error("null argument"); return GNXR_ERR_INVALID; }
+    std::lock_guard<std::recursive_mutex> lock(s->render_mutex);
+    uint64_t h = 0, t = 0;
+    for (size_t i = 0; i <= s->replicas.size(); ++i) {
+        const Counters *c = s->copy(i)->h_counters;
+        if (c) { h += c->tris_hot; t += c->tris; }
+    }
+    if (tris_from_lds) *tris_from_lds = h;
+    if (tris_loaded) *tris_loaded = t;
+    return GNXR_OK;
+}
+
+// The launch shape trace_launch gives a render's timed traversal launches on this scene (a launch of `total` work items): what a test pins.
+int gnxr_scene_trace_plan(const gnxr_scene *s, int64_t total, gnxr_trace_plan *out) {
+    if (!s || !out || total < 0) { set_error("null argument"); return GNXR_ERR_INVALID; }
+    const TraceLaunch t = trace_launch(s, s->wide_ok, s->cs.n_spheres > 0, total);
+    out->wide = s->wide_ok ? 1 : 0;
+    out->stack_entries = t.entries; out->lds_entries = t.lds_entries;
+    out->lds_bytes = (int64_t)t.lds;
+    out->n_top = t.n_top; out->hot_bytes = t.hot_bytes;
+    out->blocks = t.blocks; out->blocks_per_cu = g_trace_blocks_per_cu;
+    return GNXR_OK;
+}
+
 int gnxr_render_device(gnxr_scene *s, const gnxr_render_params *pin, void *d_rgba_out, void *hip_stream, gnxr_stats *stats) {
     return render_sharded(s, pin, d_rgba_out, hip_stream, stats);
 }

@@ -50,7 +50,7 @@ static int query_trace4(gnxr_scene *r, const DScene &sc, const gnxr_ray *d_rays,
         TraceWork w = {};
         w.n_closest = (int)cnt;
         HIP_TRY(hipMemsetAsync(cursor, 0, sizeof(unsigned int), st));
-#define GX_QUERY4(S, P, Q) hipLaunchKernelGGL((k_trace4<false, S, P, Q>), dim3(t.blocks), dim3(kBlock), t.lds, st, sc, qa, w, cursor, (Counters *)nullptr, t.lds_entries, spill, kTraceChunk, t.n_top)
+#define GX_QUERY4(S, P, Q) hipLaunchKernelGGL((k_trace4<false, S, P, Q>), dim3(t.blocks), dim3(kBlock), t.lds, st, sc, qa, w, cursor, (Counters *)nullptr, t.lds_entries, spill, kTraceChunk, t.n_top, t.hot_bytes)
 #define GX_QUERY4_SP(Q) do { if (spheres) { if (t.spill_needed) GX_QUERY4(true, true, Q); else GX_QUERY4(true, false, Q); } \
                              else { if (t.spill_needed) GX_QUERY4(false, true, Q); else GX_QUERY4(false, false, Q); } } while (0)
         if (any) GX_QUERY4_SP(kT4QueryAny);

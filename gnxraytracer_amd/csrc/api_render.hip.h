@@ -10,6 +10,7 @@ struct TraceLaunch {
     bool spill_needed;
     size_t lds;        // dynamic LDS bytes per block
     int n_top;         // 4-wide nodes served from the block's LDS copy
+    int hot_bytes;     // LDS bytes for the leaves those nodes reference (0: no hot table)
     int blocks;
 };
 static TraceLaunch trace_launch(const gnxr_scene *s, bool wide, bool spheres, long long total) {
@@ -20,12 +21,14 @@ static TraceLaunch trace_launch(const gnxr_scene *s, bool wide, bool spheres, lo
     // the 4-wide kernel, the set-up ray records and the node cache -- must fit 5 times into the 160 KB; deeper levels spill to
     // global memory (LDS levels are worth more than a bigger node cache: profiles/README.md, r02 A/B table)
     const int per_cu = g_trace_blocks_per_cu;
-    // besides the stack: the set-up ray records, the top-of-tree node cache and the order table
-    const size_t fixed_b = wide ? (size_t)(kRayRecDwords + (spheres ? 1 : 0)) * kRqStride * sizeof(int) + (size_t)kTopCache * 128 + kOrderTableBytes : 0;
+    // besides the stack: the set-up ray records, the top-of-tree node cache, the order table and the hot leaves
+    const size_t fixed_b = wide ? (size_t)(kRayRecDwords + (spheres ? 1 : 0)) * kRqStride * sizeof(int) + (size_t)kTopCache * 128 + kOrderTableBytes + kHotBytes : 0;
     t.lds_entries = std::min(std::min(t.entries, Knobs::trace_lds_levels()), std::max(2, (int)(((160 * 1024) / per_cu - 1024 - fixed_b) / (kBlock * sizeof(int)))));
     t.spill_needed = t.entries > t.lds_entries;
     t.lds = (size_t)t.lds_entries * kBlock * sizeof(int) + fixed_b;
     t.n_top = (int)std::min<size_t>(kTopCache, s->cs.root4 >= 0 ? s->cs.n_nodes4 : 0);
+    // (a hot reference takes its offset from the top of the 24-bit range: a scene with that many triangles keeps the global path)
+    t.hot_bytes = (wide && t.n_top > 0 && s->cs.n_triangles < (size_t)kHotBase) ? kHotBytes : 0;
     // persistent waves: enough blocks to fill the chip, never more than the work needs
     t.blocks = (int)std::min<long long>((long long)g_num_cus * per_cu, (total + kBlock - 1) / kBlock);
     return t;
@@ -479,7 +482,7 @@ void RenderRun::launch_trace(TraceWork w, int n_sh, int n_mis, bool count_rays) 
     // rays per atomic: at most kTraceChunk; the kernel shrinks the chunk for thin launches so that every wave gets one (trace_chunk())
     const int chunk = Knobs::trace_chunk();
 #define GX_TRACE(C, W, S) hipLaunchKernelGGL((k_trace<C, W, S>), dim3(tl.blocks), dim3(kBlock), tl.lds, stream, sc, pa, w, &dctr->cursor, dctr, tl.lds_entries, st.trace_spill.p, chunk)
-#define GX_TRACE4(C, S, P) hipLaunchKernelGGL((k_trace4<C, S, P>), dim3(tl.blocks), dim3(kBlock), tl.lds, stream, sc, pa, w, &dctr->cursor, dctr, tl.lds_entries, st.trace_spill.p, chunk, tl.n_top)
+#define GX_TRACE4(C, S, P) hipLaunchKernelGGL((k_trace4<C, S, P>), dim3(tl.blocks), dim3(kBlock), tl.lds, stream, sc, pa, w, &dctr->cursor, dctr, tl.lds_entries, st.trace_spill.p, chunk, tl.n_top, tl.hot_bytes)
 #define GX_TRACE4_CS(C, S) do { if (tl.spill_needed) GX_TRACE4(C, S, true); else GX_TRACE4(C, S, false); } while (0)
     if (wide) {   // the 4-wide walk (trace4_kernel.hip.h); count_wide: its counting variant
         if (spheres) { if (count_wide) GX_TRACE4_CS(true, true); else GX_TRACE4_CS(false, true); }

@@ -95,6 +95,7 @@ struct Counters {
     unsigned long long li_bad;                      // gnxr_li_device: ~index of the first sample record out of range (0: none; li_kernel.hip.h)
     unsigned int compact_stall;                     // k_compact: a look-back reached its poll cap (never in a correct run; the host reports GNXR_ERR_RUNTIME)
     unsigned long long nee_applied_trace, nee_applied_sweep;   // NEE vertices whose light estimate was added by k_trace4's set-up batches / by k_nee_combine (one atomic per wave)
+    unsigned long long tris_hot;                    // k_trace4<COUNT>: of `tris`, the triangles served from the block's LDS copy of the hot leaves
 };
 
 struct DScene {

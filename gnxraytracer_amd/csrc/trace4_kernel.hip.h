@@ -64,7 +64,13 @@ constexpr int kOrderTableBytes = 256;
 #define GX_T4_CACHE 64
 #endif
 constexpr int kTopCache = GX_T4_CACHE;   // DNode4[0 .. kTopCache) -- the breadth-first top of the tree -- are served from LDS
-constexpr int kRayRecDwords = 11;        // LDS record of a set-up ray: o.xyz tMax | 1/d.xyz Sx | Sy flags path  (+1 with spheres: hit code)
+// Hot leaves: the leaves the cached nodes reference (in a room, the walls: large triangles that SAH isolates next to the root, and where
+// nearly every ray ends) are served from LDS too.  A hot reference keeps the count field of a leaf reference; its offset field is
+// kHotBase + (box slot << 4) + triangle slot, from the top of the 24-bit range (a scene with that many triangles gets no hot table).
+constexpr int kHotBytes = 768;           // 48 B per triangle + 32 B per leaf box: what five blocks per CU leave beside 11 stack levels
+constexpr int kHotBase = 0x1000000 - 256;
+static_assert(kHotBytes % 16 == 0 && kHotBytes / 48 <= 16 && kHotBytes / 80 <= 16, "triangle and box slots of a hot reference are 4 bits each");
+constexpr int kRayRecDwords = 11;       // LDS record of a set-up ray: o.xyz tMax | 1/d.xyz Sx | Sy flags path  (+1 with spheres: hit code)
 #ifndef GX_T4_RQ
 #define GX_T4_RQ 64
 #endif
@@ -97,9 +103,11 @@ GX_DEV int trace4_lds_dwords_per_thread(bool sph) { return kRayRecDwords + (sph 
 #define GX_T4_BOUNDS __launch_bounds__(kBlock)
 #endif
 template <bool COUNT, bool SPH, bool SPILL, int Q = kT4Render>
-__global__ void GX_T4_BOUNDS k_trace4(DScene sc, typename Trace4Src<Q>::type pa, TraceWork w, unsigned int *cursor, Counters *ctr, int lds_entries, int *spill, int chunk, int n_top) {
+__global__ void GX_T4_BOUNDS k_trace4(DScene sc, typename Trace4Src<Q>::type pa, TraceWork w, unsigned int *cursor, Counters *ctr, int lds_entries, int *spill, int chunk, int n_top, int hot_bytes) {
     // LDS: [lds_entries * kBlock] stack columns | [(11 | 12) * kRqStride] ray records (SoA: field * kRqStride + wave * kRayQueue + slot) |
-    //      [8 * kTopCache float4] top-of-tree nodes, SoA by plane (plane * kTopCache + node: conflict-free across nodes) | [kOrderTableBytes] order table
+    //      [8 * kTopCache float4] top-of-tree nodes, SoA by plane (plane * kTopCache + node: conflict-free across nodes) | [kOrderTableBytes] order table |
+    //      [kHotBytes] hot leaves (hot_bytes != 0): triangles as 3 float4 each from the front (.w of the first = the triangle's leaf-order
+    //      index; a 48-byte stride puts up to 16 triangles on 16 different groups of four banks), leaf boxes as 2 float4 each from the back
     extern __shared__ int smem[];
     typedef __attribute__((address_space(3))) float lds_float;
     lds_int *const stk = (lds_int *)&smem[threadIdx.x];
@@ -125,12 +133,46 @@ __global__ void GX_T4_BOUNDS k_trace4(DScene sc, typename Trace4Src<Q>::type pa,
     typedef __attribute__((address_space(3))) unsigned char lds_u8;
     lds_f4 *const topN = (lds_f4 *)&smem[lds_entries * kBlock + (kRayRecDwords + (SPH ? 1 : 0)) * kRqStride];
     lds_u8 *const lut = (lds_u8 *)(topN + 8 * kTopCache);
+    lds_f4 *const hotT = (lds_f4 *)(lut + kOrderTableBytes);   // hot triangles upwards from here, hot leaf boxes downwards from hotT + kHotBytes / 16
     {   // fill the block's node cache and order table.  A vector-memory gather costs ~1 lane per clock per CU whatever it hits
         // (tools/probes/gather_probe.hip: 18 B/clk/CU for 16-byte gathers, L1-resident or not), and over half of all node visits go to
         // these few nodes (tests/dev_stats.py): from LDS they cost a ds_read instead.
         const f4v *gn = reinterpret_cast<const f4v *>(sc.nodes4);
         for (int i = threadIdx.x; i < n_top * 8; i += kBlock) topN[(i & 7) * kTopCache + (i >> 3)] = gn[i];
         if (threadIdx.x < kOrderTableBytes) lut[threadIdx.x] = (unsigned char)order_entry(threadIdx.x >> 4, threadIdx.x & 15u);
+        if (hot_bytes) {   // block-uniform; only ever 0 or kHotBytes: the launch has reserved the region or it has not
+            // the hot leaves: thread i looks at child slot i & 3 of cached node i >> 2.  A leaf needs 48 B per triangle and 32 B for its box
+            // where phase B can ask for it; leaves are admitted in thread order -- a prefix sum over (triangles | boxes << 16), no atomics, the
+            // same table in every block -- until the first one that does not fit whole: the sum runs over every leaf, so no later, smaller
+            // leaf gets in behind it.  The live device tables are read at every launch: an edit needs nothing.
+            const int node = threadIdx.x >> 2, slot = threadIdx.x & 3;
+            int ref = -1;
+            if (node < n_top) ref = reinterpret_cast<const int *>(sc.nodes4)[node * 32 + 24 + slot];
+            const bool leaf = ref < -1;   // (kNode4Empty is positive)
+            const int lr = ~ref, first = lr & 0xffffff, n = (lr >> 24) & 0x7f;
+            const int box = (n > 1 || !sc.leaf1_from_verts) ? 1 : 0;
+            unsigned incl = leaf ? (unsigned)n | ((unsigned)box << 16) : 0u;
+            for (int o = 1; o < 64; o <<= 1) { const unsigned v = __shfl_up(incl, o); if (lane >= o) incl += v; }
+            if (lane == 63) smem[threadIdx.x >> 6] = (int)incl;   // (the stack columns are not in use yet)
+            __syncthreads();                                      // the waves' totals; and the node copy above is complete
+            for (unsigned wv = 0; wv < (threadIdx.x >> 6); ++wv) incl += (unsigned)smem[wv];
+            const unsigned nT = incl & 0xffffu, nB = incl >> 16;   // triangles / boxes up to and including this leaf
+            if (leaf && nT * 48u + nB * 32u <= (unsigned)kHotBytes) {
+                const f4v *gt = reinterpret_cast<const f4v *>(tris + first);
+                lds_f4 *dt = hotT + 3 * (nT - (unsigned)n);
+                for (int j = 0; j < n; ++j) {
+                    f4v a = gt[3 * j];
+                    a.w = __int_as_float(first + j);   // what hitLeaf gets
+                    dt[3 * j] = a; dt[3 * j + 1] = gt[3 * j + 1]; dt[3 * j + 2] = gt[3 * j + 2];
+                }
+                if (box) {
+                    const f4v *gb = reinterpret_cast<const f4v *>(sc.leaf_box) + 2 * (size_t)first;
+                    lds_f4 *db = hotT + kHotBytes / 16 - 2 * nB;
+                    db[0] = gb[0]; db[1] = gb[1];
+                }
+                ((lds_int *)(topN + 6 * kTopCache + node))[slot] = ~((n << 24) | (kHotBase + (int)(((nB - (unsigned)box) << 4) + nT - (unsigned)n)));
+            }
+        }
         __syncthreads();
     }
 
@@ -163,7 +205,7 @@ __global__ void GX_T4_BOUNDS k_trace4(DScene sc, typename Trace4Src<Q>::type pa,
     unsigned oNX = 0, oNY = 16, oNZ = 32;   // byte offset of the near plane of each axis inside a DNode4 (far = 48 | 80 | 112 - near ... see below)
     unsigned ordShift = 0;                  // bit offset of this octant's 4-bit code in the node's `codes`
     int cur = -1, toVisit = 0, leafOff = 0, leafN = 0, hitLeaf = -1;
-    uint32_t cntNodes = 0, cntTris = 0, cntRetests = 0, cntNodesGlobal = 0;
+    uint32_t cntNodes = 0, cntTris = 0, cntRetests = 0, cntNodesGlobal = 0, cntTrisHot = 0;   // cntTris counts every triangle loaded, the hot ones (cntTrisHot) too
 #ifdef GX_TRACE_STATS
     unsigned long long st_[24] = {0};
 #endif
@@ -576,8 +618,14 @@ __global__ void GX_T4_BOUNDS k_trace4(DScene sc, typename Trace4Src<Q>::type pa,
             const bool retest = first && (SPH ? hitLeaf != -1 : hitLeaf >= 0);
             const bool fromVerts = retest && leafN == 1 && sc.leaf1_from_verts;
             int neg[3] = {inv.x < 0, inv.y < 0, inv.z < 0};
+            const bool hot = leafOff >= kHotBase;   // the leaf is in the block's LDS: the same bits from there
             if (retest && !fromVerts) {
-                const float4 b0 = sc.leaf_box[2 * (size_t)leafOff], b1 = sc.leaf_box[2 * (size_t)leafOff + 1];
+                float4 b0, b1;
+                if (hot) {
+                    const lds_f4 *B = hotT + (kHotBytes / 16 - 2) - 2 * ((leafOff >> 4) & 15);
+                    const f4v u = B[0], v = B[1];
+                    b0 = make_float4(u.x, u.y, u.z, u.w); b1 = make_float4(v.x, v.y, v.z, v.w);
+                } else { b0 = sc.leaf_box[2 * (size_t)leafOff]; b1 = sc.leaf_box[2 * (size_t)leafOff + 1]; }
                 if (COUNT) cntRetests++;
                 visit = slab_test(b0, b1, ro, inv, neg, tMax);
             }
@@ -588,7 +636,14 @@ __global__ void GX_T4_BOUNDS k_trace4(DScene sc, typename Trace4Src<Q>::type pa,
                 shear.kz = kz; shear.kx = kz == 2 ? 0 : kz + 1; shear.ky = shear.kx == 2 ? 0 : shear.kx + 1;
                 shear.Sx = Sx; shear.Sy = Sy; shear.Sz = kz == 0 ? inv.x : (kz == 1 ? inv.y : inv.z);
                 V3 p0, p1, p2;
-                load_tri(tris, leafOff, &p0, &p1, &p2);
+                int leafIdx = leafOff;   // the triangle's leaf-order index
+                if (hot) {
+                    const lds_f4 *T = hotT + 3 * (leafOff & 15);
+                    const f4v a = T[0], b = T[1], c = T[2];
+                    p0 = V3(a.x, a.y, a.z); p1 = V3(b.x, b.y, b.z); p2 = V3(c.x, c.y, c.z);
+                    leafIdx = __float_as_int(a.w);
+                    if (COUNT) cntTrisHot++;
+                } else load_tri(tris, leafOff, &p0, &p1, &p2);
 #ifndef GX_COUNT_TRI_TESTS   // the counter is the triangles LOADED (what the byte model of bench.py charges), box-culled one-triangle leaves included;
                 if (COUNT) cntTris++;   // -DGX_COUNT_TRI_TESTS (development builds) counts the triangles TESTED: the same number for every collapse of one binary tree
 #endif
@@ -604,7 +659,7 @@ __global__ void GX_T4_BOUNDS k_trace4(DScene sc, typename Trace4Src<Q>::type pa,
 #endif
                 TriHit h;
                 if (inBox && tri_test_sheared(p0, p1, p2, ro, shear, tMax, &h)) {
-                    hitLeaf = leafOff;
+                    hitLeaf = leafIdx;
                     if (pk & 64) { cur = -1; more = false; }   // IntersectP returns at the first hit (and so may a MIS ray that expects a miss)
                     else tMax = h.t;                            // GeometricPrimitive::Intersect shrinks ray.tMax
                 }
@@ -625,6 +680,7 @@ __global__ void GX_T4_BOUNDS k_trace4(DScene sc, typename Trace4Src<Q>::type pa,
         atomicAdd(&ctr->tris, (unsigned long long)cntTris);
         atomicAdd(&ctr->retests, (unsigned long long)cntRetests);
         atomicAdd(&ctr->nodes_global, (unsigned long long)cntNodesGlobal);
+        atomicAdd(&ctr->tris_hot, (unsigned long long)cntTrisHot);
     }
 #ifdef GX_TAIL_STAMP
     if (Q == kT4Render && lane == 0) {

@@ -652,6 +652,22 @@ int gnxr_render_reserve(gnxr_scene *scene, const gnxr_render_params *params);
  * with GNXR_NO_TRACE_NEE_APPLY set in the environment the first is 0.  Either pointer may be NULL.  (Not part of gnxr_stats: its layout is fixed.) */
 int gnxr_scene_nee_apply_counts(gnxr_scene *scene, uint64_t *in_trace, uint64_t *by_sweep);
 
+/* Diagnostics of the handle's last render under gnxr_set_profiling(4) (the counting 4-wide traversal): the triangles its traversal launches
+ * loaded (gnxr_stats::tris_tested) and how many of them came from the block-local copy of the leaves next to the root of the tree.
+ * Both are 0 after a render without the counting traversal.  Either pointer may be NULL. */
+int gnxr_scene_hot_leaf_counts(gnxr_scene *scene, uint64_t *tris_from_lds, uint64_t *tris_loaded);
+
+/* Diagnostics: the shape of the traversal launches of a render of this scene, for a launch of `total` work items, as the library sizes it.
+ * stack_entries: the deepest traversal stack the walk can need; lds_entries: how many of them live in LDS (the others spill to memory);
+ * lds_bytes: dynamic LDS per block of 256 threads; n_top: 4-wide nodes served from the block's LDS copy; hot_bytes: LDS bytes for the leaves
+ * those nodes reference (0: none); blocks: blocks of the launch; blocks_per_cu: the blocks a compute unit is meant to hold at once
+ * (lds_bytes and 1 KB kept back per block must fit that many times into its 160 KB); wide: the scene uses the 4-wide walk. */
+typedef struct gnxr_trace_plan {
+    int32_t wide, stack_entries, lds_entries, n_top, hot_bytes, blocks, blocks_per_cu, _pad;
+    int64_t lds_bytes;
+} gnxr_trace_plan;
+int gnxr_scene_trace_plan(const gnxr_scene *scene, int64_t total, gnxr_trace_plan *plan);
+
 /* -- Aggregate seam (replaces Scene::Intersect / Scene::IntersectP), batched ------------ */
 int gnxr_trace_closest(gnxr_scene *scene, const gnxr_ray *rays, int64_t n, gnxr_hit *hits);
 int gnxr_trace_any(gnxr_scene *scene, const gnxr_ray *rays, int64_t n, uint8_t *occluded);
